@@ -15,7 +15,11 @@ all-reduce of the accuracy statistics at the end of the timed region (RCCL over 
 the timed region sees a different batch of episodes (a pool generated in HBM before timing), so the reported accuracy and CI
 are over distinct episodes.  Rank 0 prints one JSON line.
 
-Extra legs (rank 0, N = 1 only):
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the result line (and, with --dump-outputs DIR, what the
+last timed step returned, as DIR/<name>.npy).  The episode pool then holds min(--pool, --steps) batches; batch i is seeded the same way in
+every run, so a plain and a --full run time the same inputs.
+
+Extra legs (--full; rank 0, N = 1 only; the --no-* options drop single ones):
   roofline      per-launch HIP-event timing inside the timed region (engine profile mode) -> the dominant kernel's
                 algorithmic TFLOP/s against the 2.5 PFLOP/s dense bf16 MFMA peak; HBM traffic / MFMA-busy fraction of that
                 kernel from the committed rocprofv3 PMC passes (profiles/).
@@ -67,12 +71,15 @@ def parse(argv=None):
     ap.add_argument('--chunk', type=int, default=int(os.environ.get('FSVIT_CHUNK', 12800)), help='images per encoder chunk')
     ap.add_argument('--pool', type=int, default=16, help='distinct episode batches generated in HBM before timing (steps cycle through them); '
                                                          '16 x 128 = 2048 episodes = the configs[1] evaluation size')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-modes', action='store_true', help='skip the parity-mode leg and the agreement figures')
-    ap.add_argument('--no-legs', action='store_true', help="skip the other configurations' legs (train / deit / deit_train / end_to_end)")
+    ap.add_argument('--full', action='store_true', help='also run the extra legs: roofline profile, other numerics modes + agreement, the other '
+                                                        "configurations' legs, CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned to DIR/<name>.npy (float32 / float64, <= 64 MB)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline profile')
+    ap.add_argument('--no-modes', action='store_true', help='with --full: skip the parity-mode leg and the agreement figures')
+    ap.add_argument('--no-legs', action='store_true', help="with --full: skip the other configurations' legs (train / deit / deit_train / end_to_end)")
     ap.add_argument('--cpu-episodes', type=int, default=20, help='timed episodes of the CPU baseline (BASELINE.md 3b: 3 warm-up + >= 20 timed)')
-    ap.add_argument('--layers', action='store_true', help='print the per-layer timing table to stderr')
+    ap.add_argument('--layers', action='store_true', help='print the per-layer timing table to stderr (profiles the timed steps, as the roofline leg does)')
     ap.add_argument('--mode', default='eval', choices=['eval', 'train', 'distill'],
                     help="eval = BASELINE configs[1] (the headline metric); train = configs[2], one SUN-M meta-tuning step "
                          "(train_meta_mini_visformer_5shot.yaml geometry: 8 episodes x 10-way (5 shot + 5 query) = 800 images)")
@@ -81,7 +88,11 @@ def parse(argv=None):
     ap.add_argument('--via-launcher', action='store_true', help='start the rank process(es) from a GPU-untouched parent even for --gpus 1 (the route --gpus N > 1 takes when invoked plainly)')
     ap.add_argument('--selftest-launcher', action='store_true',
                     help='exercise the rank launcher and the timing / statistics exchange on the CPU (gloo), no GPU work: tests/test_bench_launcher_cpu.py')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_modes = args.no_legs = True
+        args.no_roofline = not args.layers
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ rank launcher
@@ -197,6 +208,34 @@ def device_episodes(seed, n_ep, way, shot, query, dev, img=80):
     x_shot = x[:, :, :shot].contiguous()
     x_query = x[:, :, shot:].contiguous().view(n_ep, way * query, 3, img, img)
     return x_shot, x_query
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 1 << 20
+
+
+def param_sample(params, n=PARAM_SAMPLE, seed=0):
+    """A fixed, seeded sample of n entries of the concatenated parameters (all of them when there are fewer): what a training step changed."""
+    flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+    if flat.numel() <= n:
+        return flat
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: arrays (name -> tensor) as d/<name>.npy, float64 kept, everything else float32."""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        out[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError('bench.py --dump-outputs: %d bytes, the limit is %d' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + '.npy'), a)
 
 
 def _physical_cores():
@@ -413,9 +452,10 @@ def _max_over_ranks(elapsed, world, dev):
     return elapsed
 
 
-def train_leg(model_name, numerics, E, steps, warmup, rank, world, dev):
+def train_leg(model_name, numerics, E, steps, warmup, rank, world, dev, outputs=None):
     """`steps` timed meta-tuning steps of `model_name` (forward + CE + backward + (gradient all-reduce) + SGD) on E episodes per GPU of
-    10-way 5-shot 5-query; returns (whole-job episodes/s, ms per step, final loss, state dict)."""
+    10-way 5-shot 5-query; returns (whole-job episodes/s, ms per step, final loss, state dict).  A dict `outputs` receives the last step's
+    loss, accuracy and logits and a sample of the parameters it updated."""
     from fewshot_vit_amd import models, synthetic, utils, parallel
     from fewshot_vit_amd.utils import few_shot as fs
     vis = model_name == 'visformer_micro_80'
@@ -432,24 +472,26 @@ def train_leg(model_name, numerics, E, steps, warmup, rank, world, dev):
     reducer = parallel.GradBucket(model) if world > 1 else None
 
     def step():       # train_meta.train_step without its end-of-step .item() (loss and accuracy stay on the device)
-        loss, _acc, _ = model.forward_loss(x_shot, x_query, label)        # head + F.cross_entropy + compute_acc in one launch (fsvit_proto_head_ce)
+        loss, acc, logits = model.forward_loss(x_shot, x_query, label)    # head + F.cross_entropy + compute_acc in one launch (fsvit_proto_head_ce)
         opt.zero_grad()
         loss.backward()
         if reducer is not None:
             reducer.allreduce_mean()
         opt.step()
-        return loss
+        return loss, acc, logits
 
     for _ in range(warmup):
         step()
     _barrier(world)
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = step()
+        loss, acc, logits = step()
     _barrier(world)
     local = time.perf_counter() - t0
     elapsed = _max_over_ranks(local, world, dev)
     train_leg.ranks = _ranks_seen(E * steps / local, rank, world, dev)
+    if outputs is not None:
+        outputs.update(loss=loss, accuracy=acc, logits=logits, params_sample=param_sample(model.parameters()))
     return world * E * steps / elapsed, 1e3 * elapsed / steps, float(loss.detach()), sd
 
 
@@ -466,7 +508,8 @@ def train_main(args, rank, world, dev):
     """BASELINE configs[2]: one meta-tuning step = model.train() forward, CE, backward, (grad all-reduce), SGD step."""
     vis = args.model == 'visformer_micro_80'
     E = args.train_episodes
-    eps, ms, loss, sd = train_leg(args.model, args.numerics, E, args.steps, args.warmup, rank, world, dev)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    eps, ms, loss, sd = train_leg(args.model, args.numerics, E, args.steps, args.warmup, rank, world, dev, outputs)
     if train_leg.ranks[0] != world:
         sys.stderr.write('bench.py: rank %d: the collective saw %d ranks, expected %d\n' % (rank, train_leg.ranks[0], world))
         sys.exit(3)
@@ -485,7 +528,9 @@ def train_main(args, rank, world, dev):
                'roofline': {'bound': 'mfma', 'achieved': eps * flops_ep / 1e12, 'peak': peak, 'unit': 'TFLOP/s',
                             'frac': eps * flops_ep / 1e12 / peak, 'traffic': None, 'kernel': 'whole training step (forward + backward + SGD)'},
                'final_loss': loss}
-        if vis and args.numerics == 'bf16' and E == 8:
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
+        if args.full and vis and args.numerics == 'bf16' and E == 8:
             out['roofline'].update({'hbm': leg_roofline('train_', ms, eps * flops_ep / 1e12 / peak)})
         if world == 1 and not args.no_cpu_baseline and vis:
             out['cpu_baseline'] = cpu_train_baseline(sd)
@@ -556,10 +601,11 @@ def extra_legs(args, dev):
     return legs
 
 
-def distill_leg(dev, batch=512, steps=8, warm=3, n_classes=64):
+def distill_leg(dev, batch=512, steps=8, warm=3, n_classes=64, outputs=None):
     """BASELINE configs[3] at its own size (sun_meta_training/offline.py:263-309): one SUN meta-training step = `token-label` student over
     Visformer-S in train mode (drop_path 0.1) on a batch of 512 images, global CE + 0.5 x SoftTargetCrossEntropy of its 25 x 65 token logits
-    against soft labels generated from the FROZEN teacher's token logits (eval engine), backward, AdamW.  Images resident in HBM."""
+    against soft labels generated from the FROZEN teacher's token logits (eval engine), backward, AdamW.  Images resident in HBM.  A dict
+    `outputs` receives the last step's loss and accuracy and a sample of the student parameters it updated."""
     from fewshot_vit_amd import models, offline, synthetic
     from fewshot_vit_amd.models.classifier import FsvitAdamW, SoftTargetCrossEntropy
     margs = dict(encoder='visformer_micro_80', encoder_args=dict(drop_path_rate=0.1, return_map=True, numerics='bf16'), classifier='linear-classifier',
@@ -584,6 +630,8 @@ def distill_leg(dev, batch=512, steps=8, warm=3, n_classes=64):
         loss, acc = offline.distill_step(student, teacher, opt, crit, x, x, label)
     torch.cuda.synchronize()
     ms = 1e3 * (time.perf_counter() - t0) / steps
+    if outputs is not None:
+        outputs.update(loss=loss, accuracy=acc, params_sample=param_sample(student.parameters()))
     flop = 4.0 * MODELS['visformer_micro_80'][0] * batch              # student forward + data gradient + weight gradient, teacher forward
     tf = flop / (ms * 1e-3) / 1e12
     return {'value': batch / (ms * 1e-3), 'unit': 'images/s', 'ms_per_step': ms, 'steps': steps, 'warmup': warm, 'dtype': 'bf16', 'images_per_step': batch,
@@ -776,8 +824,8 @@ def eval_main(args, rank, world, dev):
         engine.profile_begin()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        _, acc, _ = step(engine, i)
-        accs.append(acc)
+        last = step(engine, i)
+        accs.append(last[1])
     # the one exchange of the path: all-reduce of (sum acc, sum acc^2, n) -> mean accuracy +- CI
     acc_all = torch.stack(accs[:n_pool]).double().flatten()                    # distinct episodes only
     stats = torch.stack([acc_all.sum(), (acc_all * acc_all).sum(), torch.tensor(float(acc_all.numel()), device=dev, dtype=torch.float64)])
@@ -799,6 +847,8 @@ def eval_main(args, rank, world, dev):
     ci = (var / n) ** 0.5 * float(scipy.stats.t.ppf(0.975, max(1.0, n - 1.0)))
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(('logits', 'accuracy', 'loss'), last)))
 
     total_eps = world * E * args.steps
     eps = total_eps / elapsed
@@ -1005,7 +1055,11 @@ def main(argv=None):
         train_main(args, rank, world, dev)
     elif args.mode == 'distill':            # BASELINE configs[3] on one GPU: the `legs.distill` entry alone (for profiling)
         if rank == 0:
-            print(json.dumps(dict(distill_leg(dev, steps=args.steps, warm=args.warmup), metric='distill_images_per_sec_batch512_visformer_s', n_gpus=1)), flush=True)
+            outputs = {} if args.dump_outputs else None
+            out = distill_leg(dev, steps=args.steps, warm=args.warmup, outputs=outputs)
+            if outputs is not None:
+                dump_outputs(args.dump_outputs, outputs)
+            print(json.dumps(dict(out, metric='distill_images_per_sec_batch512_visformer_s', n_gpus=1)), flush=True)
     else:
         eval_main(args, rank, world, dev)
     if world > 1:

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(REPO, 'bench.py')
 
@@ -36,6 +38,40 @@ def test_under_external_launcher_env_is_a_rank():
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.loads(r.stdout.strip().splitlines()[-1])['n_gpus'] == 1
+
+
+@pytest.fixture
+def bench():
+    """bench.py imported in this process, without the HIP setting it exports at import for its own runtime (later tests of the session open the GPU)."""
+    had = os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY')
+    if REPO not in sys.path:
+        sys.path.insert(0, REPO)
+    import bench as mod
+    if had is None:
+        os.environ.pop('HSA_ENABLE_IPC_MODE_LEGACY', None)
+    return mod
+
+
+def test_plain_run_times_the_headline_only_and_full_adds_the_legs(bench):
+    plain = bench.parse(['--steps', '7'])
+    assert not plain.full and plain.steps == 7 and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_modes and plain.no_legs and plain.no_roofline
+    assert not bench.parse(['--layers']).no_roofline                              # the per-layer table asks for the profile itself
+    full = bench.parse(['--full', '--no-legs'])
+    assert not (full.no_cpu_baseline or full.no_modes or full.no_roofline) and full.no_legs
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(bench, tmp_path):
+    import numpy as np
+    import torch
+    bench.dump_outputs(str(tmp_path), {'logits': torch.randn(2, 75, 5), 'loss': torch.tensor(1.5), 'stat': torch.ones(3, dtype=torch.float64),
+                                       'hits': torch.ones(4, dtype=torch.int64)})
+    got = {k: np.load(tmp_path / (k + '.npy')) for k in ('logits', 'loss', 'stat', 'hits')}
+    assert got['logits'].shape == (2, 75, 5) and got['loss'].shape == () and float(got['loss']) == 1.5
+    assert [got[k].dtype for k in ('logits', 'loss', 'stat', 'hits')] == [np.float32, np.float32, np.float64, np.float32]
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / 'big').exists()
 
 
 def test_more_gpus_than_visible_fails_cleanly():

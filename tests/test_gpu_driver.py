@@ -118,12 +118,38 @@ def test_bench_rank_launcher_route_on_a_gpu_box():
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--via-launcher', '--steps', '3', '--warmup', '1', '--episodes', '16',
-                        '--chunk', '1600', '--no-modes', '--no-cpu-baseline', '--no-legs'], capture_output=True, text=True, timeout=900, env=env)
+                        '--chunk', '1600', '--full', '--no-modes', '--no-cpu-baseline', '--no-legs'], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 1 and line['steps'] == 3 and line['value'] > 0 and line['roofline']['kernel']
     r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '64', '--steps', '1'], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 2 and 'GPU(s) visible' in r.stderr
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py` times the headline only, and --dump-outputs writes what its last timed step returned; two runs with the same
+    arguments see the same seeded episodes, so their outputs agree."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ('run%d' % run)
+        r = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--episodes', '16',
+                            '--chunk', '1600', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['unit'] == 'episodes/s' and line['dtype'] == 'bf16'
+        assert line['config']['distinct_episode_batches'] == 3
+        assert not {'roofline', 'kernels', 'modes', 'agreement', 'legs', 'cpu_baseline'} & set(line)
+        out = {k: np.load(d / (k + '.npy')) for k in ('logits', 'accuracy', 'loss')}
+        assert out['logits'].shape == (16, 75, 5) and out['accuracy'].shape == (16,) and out['loss'].shape == (16,)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+        label = np.repeat(np.arange(5), 15)
+        assert np.allclose(out['accuracy'], (out['logits'].argmax(-1) == label).mean(-1), atol=1e-6)
+        dumps.append(out)
+    assert np.abs(dumps[0]['logits'] - dumps[1]['logits']).max() <= 1e-4
 
 
 RCCL_CHILD = r'''
