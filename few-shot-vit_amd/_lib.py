@@ -31,6 +31,12 @@ class VitCfg(C.Structure):
                 ('num_heads', C.c_int), ('mlp_ratio', C.c_float), ('ln_eps', C.c_float)]
 
 
+class LvvitCfg(C.Structure):
+    _fields_ = [('img_size', C.c_int), ('stem_channels', C.c_int), ('embed_dim', C.c_int), ('depth', C.c_int),
+                ('num_heads', C.c_int), ('mlp_ratio', C.c_float), ('skip_lam', C.c_float), ('ln_eps', C.c_float),
+                ('bn_eps', C.c_float)]
+
+
 class ProfRec(C.Structure):
     _fields_ = [('layer', C.c_char * 48), ('kernel_id', C.c_int), ('launches', C.c_int), ('flops', C.c_double),
                 ('ms', C.c_double)]
@@ -56,6 +62,12 @@ SIGNATURES = {
     'fsvit_vit_out_dim': (_i, [_vp]),
     'fsvit_vit_workspace_bytes': (_sz, [_vp, _i]),
     'fsvit_vit_forward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp, _sz, _vp]),
+    'fsvit_lvvit_create': (_i, [C.POINTER(LvvitCfg), C.POINTER(Tensor), _i, _i, C.POINTER(_vp)]),
+    'fsvit_lvvit_destroy': (None, [_vp]),
+    'fsvit_lvvit_out_dim': (_i, [_vp]),
+    'fsvit_lvvit_workspace_bytes': (_sz, [_vp, _i]),
+    'fsvit_lvvit_forward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp, _sz, _vp]),
+    'fsvit_stem96_conv': (_i, [_vp, _vp, _fp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     'fsvit_encoder_set_tap': (_i, [_vp, C.c_char_p, _vp, _sz]),
     'fsvit_encoder_profile_begin': (_i, [_vp]),
     'fsvit_encoder_profile_end': (_i, [_vp, C.POINTER(ProfRec), _i, C.POINTER(_i)]),

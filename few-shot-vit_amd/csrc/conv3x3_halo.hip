@@ -102,7 +102,11 @@ __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
 
-template <int CIN, bool FUSE_TAIL, bool STATS = false>
+// CREAL < CIN (the LV-ViT stem, CREAL = 96 on the CIN = 128 schedule): the maps hold CREAL channels (input and output pixel = CREAL * 2 bytes); halo
+// chunks past CREAL are filled from the zero page, the weights come as the zero-padded 128-channel image (ConvGemmParams::w_cpad), and outputs past
+// CREAL are neither loaded (bias / pos) nor stored.  Every CREAL-specific statement is `if constexpr (CREAL != CIN)`: the 64 / 128 instantiations
+// compile to what they were.
+template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN>
 __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmParams p, const int n_tiles) {
   using namespace halo;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -154,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   };
   // source of (halo row hr, halo column hc) of this wave's chunk plane = base + hr * x_rs + (hc - 1) * x_ps bytes: NHWC (pixel = CIN * 2 bytes, the wave's
   // chunk 16 bytes into the half) or row-chunk-planar (conv_gemm.h x_planar: a row of one chunk = W * 16 contiguous bytes)
-  const int x_rs = p.x_planar ? (CIN / 8) * p.W * 16 : p.W * CIN * 2, x_ps = p.x_planar ? 16 : CIN * 2;
+  const int x_rs = p.x_planar ? (CIN / 8) * p.W * 16 : p.W * CREAL * 2, x_ps = p.x_planar ? 16 : CREAL * 2;
   // one piece of the halo tile whose pixel (row r0 - 1, column 0, first channel of the half) is at `base` into buffer nb; base == nullptr:
   // nothing to fetch (zero page) - the piece is still issued so that the counted waits below see the same number of operations in
   // flight on every path.  top / bot: the tile touches the upper / lower image border (halo row 0 / 9 is zero padding).
@@ -169,6 +173,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   };
   auto halo_base = [&](int tile, int h) {
     const int bb = tile / tiles_per_img, rr = (tile - bb * tiles_per_img) * TR;
+    if constexpr (CREAL != CIN) {            // this wave's 8-channel chunk lies past the map's channels: zero page (issue_piece)
+      if (h * 64 + wave * 8 >= CREAL) return (const unsigned char*)nullptr;
+    }
     return Xb + (long)(bb * p.H + rr - 1) * x_rs + (p.x_planar ? (h * 8 + wave) * p.W * 16 : h * 128 + wave * 16);
   };
 
@@ -362,8 +369,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
       const int fr_e = ((lrow_e >> 3) & 1) * 2 + ((lrow_e >> 1) & 1), fc_e = ((lrow_e >> 2) & 1) * 2 + (lrow_e & 1);
       f32x4 bv[NT];
 #pragma unroll
-      for (int j = 0; j < NT; ++j)
-        bv[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + wn * 64 + (j >> 1) * 32 + lq_e * 8 + (j & 1) * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < NT; ++j) {
+        const int nb = wn * 64 + (j >> 1) * 32 + lq_e * 8 + (j & 1) * 4;
+        bool bok = p.bias != nullptr;
+        if constexpr (CREAL != CIN) bok = bok && nb < CREAL;
+        bv[j] = bok ? *reinterpret_cast<const f32x4*>(p.bias + nb) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
       if constexpr (STATS) {               // BatchNorm statistics of the stored map (training forward): per-lane running sums over every tile of this workgroup
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -385,6 +396,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
             const int py = (r0 + prow_i) >> 1, px = pcol_i >> 1;
             orow = (size_t)(b * ph + py) * pw + px;
             posrow = p.pos + (size_t)(py * pw + px) * p.y_cstride;
+            if constexpr (CREAL != CIN) posrow = p.pos ? posrow : nullptr;
           } else {
             orow = (size_t)(b * p.H + r0 + prow_i) * p.W + pcol_i;
           }
@@ -404,10 +416,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
                   v[u][e] = fmaxf(v[u][e], quad_xor<0xB1>(v[u][e]));      // lanes ^ 1: quad_perm [1,0,3,2]
                   v[u][e] = fmaxf(v[u][e], quad_xor<0x4E>(v[u][e]));      // lanes ^ 2: quad_perm [2,3,0,1]
                 }
-                v[u] += *reinterpret_cast<const f32x4*>(posrow + n + 4 * u);
+                if constexpr (CREAL != CIN) {
+                  if (posrow && n < CREAL) v[u] += *reinterpret_cast<const f32x4*>(posrow + n + 4 * u);
+                } else v[u] += *reinterpret_cast<const f32x4*>(posrow + n + 4 * u);
               }
             }
-            if (!FUSE_TAIL || (lrow_e & 3) == 0) {
+            bool nst = true;
+            if constexpr (CREAL != CIN) nst = n < CREAL;
+            if (nst && (!FUSE_TAIL || (lrow_e & 3) == 0)) {
               const bf16x8 o = {(bf16)v[0][0], (bf16)v[0][1], (bf16)v[0][2], (bf16)v[0][3], (bf16)v[1][0], (bf16)v[1][1], (bf16)v[1][2], (bf16)v[1][3]};
               if (!FUSE_TAIL && p.y_planar) *reinterpret_cast<bf16x8*>(Y + (((size_t)(b * p.H + r0 + prow_i) * (p.y_cstride >> 3) + (n >> 3)) * p.W + pcol_i) * 8) = o;
               else *reinterpret_cast<bf16x8*>(Y + orow * p.y_cstride + n) = o;
@@ -422,12 +438,16 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
       auto finish_pooled = [&](auto actf) {
         const int u_e = lrow_e & 3;
         const int nq = wn * 64 + (u_e >> 1) * 32 + lq_e * 8 + (u_e & 1) * 4;             // the 4 channels this lane finishes
-        const f32x4 bq = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + nq) : f32x4{0.f, 0.f, 0.f, 0.f};
+        bool qok = true;
+        if constexpr (CREAL != CIN) qok = nq < CREAL;
+        const f32x4 bq = (p.bias && qok) ? *reinterpret_cast<const f32x4*>(p.bias + nq) : f32x4{0.f, 0.f, 0.f, 0.f};
         const int ph = p.H >> 1, pw = p.W >> 1;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
           const int py = (r0 + blk_r(i) * 4 + fr_e) >> 1, px = (blk_c(i) * 4 + fc_e) >> 1;
-          const f32x4 pq = *reinterpret_cast<const f32x4*>(p.pos + (size_t)(py * pw + px) * p.y_cstride + nq);
+          f32x4 pq;
+          if constexpr (CREAL != CIN) pq = (p.pos && qok) ? *reinterpret_cast<const f32x4*>(p.pos + (size_t)(py * pw + px) * p.y_cstride + nq) : f32x4{0.f, 0.f, 0.f, 0.f};
+          else pq = *reinterpret_cast<const f32x4*>(p.pos + (size_t)(py * pw + px) * p.y_cstride + nq);
           f32x4 m[NT];
 #pragma unroll
           for (int j = 0; j < NT; ++j) {
@@ -444,7 +464,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = actf(v[e]);
           v += pq;
-          store4<bf16>(Y + ((size_t)(b * ph + py) * pw + px) * p.y_cstride + nq, v);
+          if (qok) store4<bf16>(Y + ((size_t)(b * ph + py) * pw + px) * p.y_cstride + nq, v);
         }
       };
       if (FUSE_TAIL && p.act == ACT_LRELU) finish_pooled([](float x) { return fmaxf(x, 0.1f * x); });
@@ -490,6 +510,13 @@ bool conv3x3_halo_eligible(const ConvGemmParams& p, int dtype) {
   constexpr bool off = false;
   if (off || dtype != 1) return false;
   if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.groups != 1) return false;
+  if (p.w_cpad) {     // the LV-ViT stem (96 channels) on the 128-channel schedule: weights as the zero-padded 128-channel image
+    if (p.w_cpad != 128 || p.Cin != 96 || p.N != 96 || p.x_cstride != 96 || p.y_cstride != 96 || p.K != 9 * 96) return false;
+    if (p.W != halo::TW || (p.H % halo::TR) || p.OH != p.H || p.OW != p.W) return false;
+    if (p.res || p.y2 || p.act == ACT_MUL || p.act == ACT_GELU || p.y_rpi || p.out_f32 || p.w_rstride || p.w_gstride || p.stats || p.x_planar || p.y_planar) return false;
+    if (p.pool2) return p.x2 && p.K2 == 32 && p.x2_cstride >= 32 && p.Kw == 9 * 128 + 64;
+    return !p.x2 && !p.pos && p.Kw == 9 * 128;
+  }
   if (p.N != 128 || p.y_cstride != 128 || p.W != halo::TW || (p.H % halo::TR) || p.OH != p.H || p.OW != p.W) return false;
   if (p.res || p.y2 || p.act == ACT_MUL || p.y_rpi || p.out_f32 || p.w_rstride || p.w_gstride) return false;
   if (p.Cin != p.x_cstride || p.K != 9 * p.Cin) return false;
@@ -508,10 +535,10 @@ int conv3x3_halo_stats_rows(const ConvGemmParams& p, int dtype) {
   return conv3x3_halo_eligible(q, dtype) ? halo_grid(p) : 0;
 }
 
-template <int CIN, bool FUSE_TAIL, bool STATS = false>
+template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN>
 static int launch_halo_t(const ConvGemmParams& p, hipStream_t stream) {
   const int n_tiles = p.B * (p.H / halo::TR);
-  auto kern = conv3x3_halo_kernel<CIN, FUSE_TAIL, STATS>;
+  auto kern = conv3x3_halo_kernel<CIN, FUSE_TAIL, STATS, CREAL>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, halo::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
   const int grid = n_tiles < 256 ? n_tiles : 256;
@@ -520,6 +547,7 @@ static int launch_halo_t(const ConvGemmParams& p, hipStream_t stream) {
 }
 
 int launch_conv3x3_halo(const ConvGemmParams& p, hipStream_t stream) {
+  if (p.w_cpad) return p.pool2 ? launch_halo_t<128, true, false, 96>(p, stream) : launch_halo_t<128, false, false, 96>(p, stream);
   if (p.pool2) return launch_halo_t<128, true>(p, stream);
   if (p.stats) return p.Cin == 64 ? launch_halo_t<64, false, true>(p, stream) : launch_halo_t<128, false, true>(p, stream);
   return p.Cin == 64 ? launch_halo_t<64, false>(p, stream) : launch_halo_t<128, false>(p, stream);

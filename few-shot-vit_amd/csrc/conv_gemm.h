@@ -73,6 +73,9 @@ struct ConvGemmParams {
   // of each: 20 % of the kernel's time went into the halo fetch, tools/probes/variants/conv3x3_halo.diag.patch -DH_NO_HDMA); from this layout the lanes of
   // a piece read row segments of 640 contiguous bytes.  Same size as NHWC; only stem_conv1 / conv3x3_halo produce and consume it.
   int x_planar = 0, y_planar = 0;
+  // conv3x3_halo only (the LV-ViT stem, Cin = N = 96): w_cpad == 128 -> the weight rows are the 128-channel image of the layer: 128 rows (rows >= N
+  // zero), k = tap * 128 + c with c >= Cin zero, the tail slice behind the 9 * 128 main columns.  0: the standard packing above.
+  int w_cpad = 0;
 };
 
 }  // namespace fsvit_types

@@ -198,8 +198,14 @@ __global__ __launch_bounds__(256, MINB) void conv_gemm_v2_kernel(const ConvGemmP
     const int k = kt * BKE + sc * EPC;
     int ky = 0, kx = 0, cc = k;
     if (multi_tap) {
-      const int tap = k >> p.log2Cin;
-      cc = k & (p.Cin - 1);
+      int tap;
+      if ((p.Cin & (p.Cin - 1)) == 0) {    // power-of-two Cin: shift / mask (every Visformer / DeiT geometry)
+        tap = k >> p.log2Cin;
+        cc = k & (p.Cin - 1);
+      } else {                             // any other Cin % EPC == 0 (LV-ViT's 96-channel stem): a 16-byte chunk never straddles two taps
+        tap = (int)((unsigned)k / (unsigned)p.Cin);
+        cc = k - tap * p.Cin;
+      }
       ky = tap / p.KW;
       kx = tap - ky * p.KW;
     }
@@ -553,6 +559,7 @@ int conv_stats_rows(const ConvGemmParams& p, int dtype) {
 int launch_conv_gemm(const ConvGemmParams& p, int dtype, hipStream_t stream) {
   if (conv3x3_halo_eligible(p, dtype)) return launch_conv3x3_halo(p, stream);
   if (p.x_planar || p.y_planar) return (int)hipErrorInvalidValue;      // only conv3x3_halo reads / writes the row-chunk-planar layout
+  if (p.w_cpad) return (int)hipErrorInvalidValue;                      // only conv3x3_halo reads the 128-channel weight image
   if (gconv3x3_x2_eligible(p, dtype)) return launch_gconv3x3_x2(p, stream);
   if (gemm256_eligible(p, dtype)) return run_gemm256(p, dtype, stream);
   // A plain 1x1 layer whose activation matrix is past gemm256's 32-bit DMA offsets (a 12 800-image ViT chunk: 2.5 M rows x 1536 columns)

@@ -142,7 +142,7 @@ struct ProfEntry { std::string layer; int kernel; double flops; hipEvent_t e0, e
 
 // State shared by every encoder handle (the C-ABI functions that take "any encoder" rely on it being
 // the first base sub-object).
-enum { KIND_VISFORMER = 1, KIND_VIT = 2 };
+enum { KIND_VISFORMER = 1, KIND_VIT = 2, KIND_LVVIT = 3 };
 struct EngineBase {
   int kind = 0;
   int dtype = 0, es = 4;
@@ -1044,7 +1044,7 @@ extern "C" int fsvit_conv_gemm(const void* x, const void* w, const float* bias, 
   const int es = storage_bytes(dtype), epc = 16 / es, bke = 128 / es;
   if (Cin % epc || x_cstride % epc || N % 4 || y_cstride % 4 || Kw % bke || Kw < KH * KW * Cin)
     return fail(FSVIT_ERR_ARG, "conv_gemm alignment: Cin/x_cstride %% %d, N/y_cstride %% 4, Kw %% %d", epc, bke);
-  if (KH * KW > 1 && !is_pow2(Cin)) return fail(FSVIT_ERR_ARG, "multi-tap conv needs power-of-two Cin");
+  if (KH * KW > 1 && !is_pow2(Cin) && Cin % 32) return fail(FSVIT_ERR_ARG, "multi-tap conv needs a power-of-two Cin or a multiple of 32");
   Layer L; L.w = const_cast<void*>(w); L.bias = const_cast<float*>(bias); L.N = N; L.K = KH * KW * Cin; L.Kw = Kw; L.groups = groups;
   ConvGemmParams p = conv_params(L, x, y, B, H, W, Cin, x_cstride, KH, KW, stride, pad, y_cstride, act, res, res_first, pos);
   RC_TRY(K(launch_conv_gemm)(p, kg(dtype), (hipStream_t)stream));
@@ -1060,11 +1060,28 @@ extern "C" int fsvit_conv_stem_tail(const void* x, const void* w, const float* b
   if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
   if (!x || !w || !y || !x2 || !pos) return fail(FSVIT_ERR_ARG, "null argument");
   const int es = storage_bytes(dtype), epc = 16 / es, bke = 128 / es;
-  if (Cin % epc || !is_pow2(Cin) || N % 4 || Kw % bke || Kw < 9 * Cin + bke || K2 > bke || x2_cstride < K2 || (H & 1) || (W & 1))
+  if (Cin % epc || (!is_pow2(Cin) && Cin % 32) || N % 4 || Kw % bke || Kw < 9 * Cin + bke || K2 > bke || x2_cstride < K2 || (H & 1) || (W & 1))
     return fail(FSVIT_ERR_ARG, "fsvit_conv_stem_tail: bad geometry");
   Layer L; L.w = const_cast<void*>(w); L.bias = const_cast<float*>(bias); L.N = N; L.K = 9 * Cin; L.Kw = Kw; L.groups = 1;
   ConvGemmParams p = conv_params(L, x, y, B, H, W, Cin, Cin, 3, 3, 1, 1, N, ACT_LRELU, nullptr, 0, pos);
   p.x2 = x2; p.x2_cstride = x2_cstride; p.K2 = K2; p.pool2 = 1;
+  RC_TRY(K(launch_conv_gemm)(p, kg(dtype), (hipStream_t)stream));
+  return 0;
+}
+
+/* LV-ViT's 96-channel stem convs on the dedicated conv3x3_halo instantiation (bf16 / f16 only; an error where it does not apply): pool == 0: conv2,
+ * y = LeakyReLU(conv3x3(x) + bias) [B][H][W][96]; pool == 1: conv3 + tail, y = MaxPool2d(2)(LeakyReLU(conv3x3(x) + x2 . tail + bias)) [B][H/2][W/2][96].
+ * w: the 128-channel image [128][9 * 128 (+ 64)], k = tap * 128 + c, zero past 96 channels / rows, the tail slice (im2col rows x2, K2 <= 32) last. */
+extern "C" int fsvit_stem96_conv(const void* x, const void* w, const float* bias, const void* x2, int x2_cstride, int K2, void* y, int B, int H, int W,
+                                 int pool, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (dtype != FSVIT_BF16 && dtype != FSVIT_F16) return fail(FSVIT_ERR_ARG, "fsvit_stem96_conv: bf16 / f16 only");
+  if (!x || !w || !y || (pool && !x2)) return fail(FSVIT_ERR_ARG, "null argument");
+  Layer L; L.w = const_cast<void*>(w); L.bias = const_cast<float*>(bias); L.N = 96; L.K = 9 * 96; L.Kw = 9 * 128 + (pool ? 64 : 0); L.groups = 1;
+  ConvGemmParams p = conv_params(L, x, y, B, H, W, 96, 96, 3, 3, 1, 1, 96, ACT_LRELU, nullptr, 0, nullptr);
+  p.w_cpad = 128;
+  if (pool) { p.x2 = x2; p.x2_cstride = x2_cstride; p.K2 = K2; p.pool2 = 1; }
+  if (K(conv_gemm_route)(p, kg(dtype)) != 0) return fail(FSVIT_ERR_ARG, "fsvit_stem96_conv: geometry not supported (W = 40, H a multiple of 8, K2 = 32)");
   RC_TRY(K(launch_conv_gemm)(p, kg(dtype), (hipStream_t)stream));
   return 0;
 }
@@ -1162,7 +1179,7 @@ extern "C" int fsvit_vit_block_tail(const void* x, void* y, const void* ctx, con
                                     const float* b1, const void* w2, int k2w, const float* b2, int M, int C, int hid, float eps, void* stream) {
   const int kdt = FSVIT_BF16;
   if (!x || !y || !ctx || !wp || !bp || !w1 || !b1 || !w2 || !b2) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!K(mlp_rows_ln_supported)(1, C, hid, KC)) return fail(FSVIT_ERR_ARG, "fsvit_vit_block_tail: only C = 384 / hidden = 1536 / KC = 384 (bf16) is built");
+  if (!K(mlp_rows_ln_supported)(1, C, hid, KC)) return fail(FSVIT_ERR_ARG, "fsvit_vit_block_tail: only C = 384 / hidden = 1536 or 1152 / KC = 384 (bf16) is built");
   if (k1w < C || k2w < hid || kpw < KC) return fail(FSVIT_ERR_ARG, "weight rows shorter than K");
   hipStream_t st = (hipStream_t)stream;
   void *img = nullptr, *b1i = nullptr;
@@ -1452,6 +1469,81 @@ std::vector<double> add_vec(const std::vector<double>& a, const float* b, int n)
   return r;
 }
 
+// Packs blocks.<i>.* (i < depth) of a pre-LN ViT encoder - DeiT (deit.py:62-77) and LV-ViT (lvvit.py:140-155) - into `blocks`.  LayerNorm gains /
+// shifts are folded into the following Linear.  qkv_bias = false: the qkv Linear has no bias of its own (LV-ViT), the packed bias is then the
+// folded norm1 shift W beta alone.  res_scale != 1 multiplies both residual branches (LV-ViT's 1 / skip_lam): it is folded into the proj and fc2
+// weights and biases, exact for a power of two in every storage format.
+int pack_vit_blocks(EngineBase* h, const SD& sd, int depth, int D, int heads, int hd, int hdp, int hid, int S, bool qkv_bias, double res_scale,
+                    std::vector<VitBlock>* blocks_out) {
+  std::vector<VitBlock>& blocks = *blocks_out;
+  std::vector<int> rowmap(3 * heads * hd), colmap(heads * hd);
+  for (int x = 0; x < 3; ++x)
+    for (int y = 0; y < heads; ++y)
+      for (int z = 0; z < hd; ++z) rowmap[(x * heads + y) * hd + z] = (x * heads + y) * hdp + z;
+  for (int y = 0; y < heads; ++y)
+    for (int z = 0; z < hd; ++z) colmap[y * hd + z] = y * hdp + z;
+  const bool scaled = res_scale != 1.0;
+  const std::vector<double> rs(D, res_scale);
+  blocks.resize(depth);
+  for (int i = 0; i < depth; ++i) {
+    const std::string bp = "blocks." + std::to_string(i) + ".";
+    const float* g1 = sd.get(bp + "norm1.weight", {D});
+    const float* b1 = sd.get(bp + "norm1.bias", {D});
+    const float* g2 = sd.get(bp + "norm2.weight", {D});
+    const float* b2 = sd.get(bp + "norm2.bias", {D});
+    const float* wq = sd.get(bp + "attn.qkv.weight", {3 * heads * hd, D});
+    const float* bq = qkv_bias ? sd.get(bp + "attn.qkv.bias", {3 * heads * hd}) : nullptr;
+    const float* wp = sd.get(bp + "attn.proj.weight", {D, heads * hd});
+    const float* bpj = sd.get(bp + "attn.proj.bias", {D});
+    const float* w1 = sd.get(bp + "mlp.fc1.weight", {hid, D});
+    const float* bf1 = sd.get(bp + "mlp.fc1.bias", {hid});
+    const float* w2 = sd.get(bp + "mlp.fc2.weight", {D, hid});
+    const float* bf2 = sd.get(bp + "mlp.fc2.bias", {D});
+    if (!g1 || !b1 || !g2 || !b2 || !wq || (qkv_bias && !bq) || !wp || !bpj || !w1 || !bf1 || !w2 || !bf2) return FSVIT_ERR_KEY;
+    std::vector<double> s1(g1, g1 + D), t1(b1, b1 + D), s2(g2, g2 + D), t2(b2, b2 + D);
+    std::vector<double> vbp(bpj, bpj + D), vb2(bf2, bf2 + D);
+    if (scaled)
+      for (int o = 0; o < D; ++o) { vbp[o] *= res_scale; vb2[o] *= res_scale; }
+    const std::vector<double> bqkv = qkv_bias ? add_vec(prenorm_bias(wq, 3 * heads * hd, D, t1), bq, 3 * heads * hd) : prenorm_bias(wq, 3 * heads * hd, D, t1);
+    RC_TRY(pack_layer(h, &blocks[i].qkv, wq, 3 * heads * hd, D, 1, 1, 1, nullptr, &s1, bqkv, true, &rowmap, 3 * heads * hdp, nullptr, 0));
+    RC_TRY(pack_layer(h, &blocks[i].proj, wp, D, heads * hd, 1, 1, 1, scaled ? &rs : nullptr, nullptr, vbp, true, nullptr, 0, &colmap, heads * hdp));
+    RC_TRY(pack_layer(h, &blocks[i].fc1, w1, hid, D, 1, 1, 1, nullptr, &s2, add_vec(prenorm_bias(w1, hid, D, t2), bf1, hid), true, nullptr, 0, nullptr, 0));
+    RC_TRY(pack_layer(h, &blocks[i].fc2, w2, D, hid, 1, 1, 1, scaled ? &rs : nullptr, nullptr, vb2, true, nullptr, 0, nullptr, 0));
+    const int kdt = h->dtype;
+    if (K(mlp_rows_ln_supported)(kd(kdt), D, hid, heads * hdp)) {      // proj + residual + norm2 + Mlp in one row-wise kernel
+      VitBlock& b = blocks[i];
+      void *img = nullptr, *b1i = nullptr;
+      HIP_TRY(hipMalloc(&img, K(mlp_rows_image_bytes)(D, hid, heads * hdp)));
+      h->allocs.push_back(img);
+      HIP_TRY(hipMalloc(&b1i, (size_t)hid * 4));
+      h->allocs.push_back(b1i);
+      RC_TRY(K(launch_mlp_pack)(b.fc1.w, b.fc1.Kw, b.fc1.bias, b.fc2.w, b.fc2.Kw, b.proj.w, b.proj.Kw, heads * hdp, img, (float*)b1i, D, hid, nullptr));
+      HIP_TRY(hipDeviceSynchronize());
+      b.mlp_img = img;
+      b.mlp_b1 = (float*)b1i;
+    }
+    if (K(ln_gemm_rows_supported)(kd(kdt), D, 3 * heads * hdp)) {         // norm1 + qkv in one row-wise kernel
+      VitBlock& b = blocks[i];
+      void* img = nullptr;
+      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
+      h->allocs.push_back(img);
+      RC_TRY(K(launch_ln_gemm_pack)(b.qkv.w, b.qkv.Kw, img, D, 3 * heads * hdp, nullptr));
+      HIP_TRY(hipDeviceSynchronize());
+      b.qkv_img = img;
+    }
+    if (K(vit_attn_rows_supported)(kd(kdt), D, heads, hdp, S)) {       // norm1 + qkv + attention core in one launch: the qkv tensor never reaches HBM
+      VitBlock& b = blocks[i];
+      void* img = nullptr;
+      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
+      h->allocs.push_back(img);
+      RC_TRY(K(launch_qkv_attn_rows_pack)(b.qkv.w, b.qkv.Kw, img, D, heads, hdp, nullptr));
+      HIP_TRY(hipDeviceSynchronize());
+      b.attn_img = img;
+    }
+  }
+  return 0;
+}
+
 int build_vit(fsvit_vit* h, const SD& sd) {
   const fsvit_vit_cfg& cf = h->cfg;
   const int epc = 16 / h->es, kch = 64 / h->es;
@@ -1487,69 +1579,7 @@ int build_vit(fsvit_vit* h, const SD& sd) {
     RC_TRY(upload(h, gg, false, &dv)); h->ng = (float*)dv;
     RC_TRY(upload(h, bb, false, &dv)); h->nb = (float*)dv;
   }
-  const int hd = h->hd, hdp = h->hdp;
-  std::vector<int> rowmap(3 * heads * hd), colmap(heads * hd);
-  for (int x = 0; x < 3; ++x)
-    for (int y = 0; y < heads; ++y)
-      for (int z = 0; z < hd; ++z) rowmap[(x * heads + y) * hd + z] = (x * heads + y) * hdp + z;
-  for (int y = 0; y < heads; ++y)
-    for (int z = 0; z < hd; ++z) colmap[y * hd + z] = y * hdp + z;
-  std::vector<double> nob;
-  h->blocks.resize(cf.depth);
-  for (int i = 0; i < cf.depth; ++i) {
-    const std::string bp = "blocks." + std::to_string(i) + ".";
-    const float* g1 = sd.get(bp + "norm1.weight", {D});
-    const float* b1 = sd.get(bp + "norm1.bias", {D});
-    const float* g2 = sd.get(bp + "norm2.weight", {D});
-    const float* b2 = sd.get(bp + "norm2.bias", {D});
-    const float* wq = sd.get(bp + "attn.qkv.weight", {3 * D, D});
-    const float* bq = sd.get(bp + "attn.qkv.bias", {3 * D});
-    const float* wp = sd.get(bp + "attn.proj.weight", {D, D});
-    const float* bpj = sd.get(bp + "attn.proj.bias", {D});
-    const float* w1 = sd.get(bp + "mlp.fc1.weight", {h->hid, D});
-    const float* bf1 = sd.get(bp + "mlp.fc1.bias", {h->hid});
-    const float* w2 = sd.get(bp + "mlp.fc2.weight", {D, h->hid});
-    const float* bf2 = sd.get(bp + "mlp.fc2.bias", {D});
-    if (!g1 || !b1 || !g2 || !b2 || !wq || !bq || !wp || !bpj || !w1 || !bf1 || !w2 || !bf2) return FSVIT_ERR_KEY;
-    std::vector<double> s1(g1, g1 + D), t1(b1, b1 + D), s2(g2, g2 + D), t2(b2, b2 + D);
-    std::vector<double> vbp(bpj, bpj + D), vb2(bf2, bf2 + D);
-    RC_TRY(pack_layer(h, &h->blocks[i].qkv, wq, 3 * D, D, 1, 1, 1, nullptr, &s1, add_vec(prenorm_bias(wq, 3 * D, D, t1), bq, 3 * D), true, &rowmap, 3 * heads * hdp, nullptr, 0));
-    RC_TRY(pack_layer(h, &h->blocks[i].proj, wp, D, heads * hd, 1, 1, 1, nullptr, nullptr, vbp, true, nullptr, 0, &colmap, heads * hdp));
-    RC_TRY(pack_layer(h, &h->blocks[i].fc1, w1, h->hid, D, 1, 1, 1, nullptr, &s2, add_vec(prenorm_bias(w1, h->hid, D, t2), bf1, h->hid), true, nullptr, 0, nullptr, 0));
-    RC_TRY(pack_layer(h, &h->blocks[i].fc2, w2, D, h->hid, 1, 1, 1, nullptr, nullptr, vb2, true, nullptr, 0, nullptr, 0));
-    const int kdt = h->dtype;
-    if (K(mlp_rows_ln_supported)(kd(kdt), D, h->hid, heads * hdp)) {      // proj + residual + norm2 + Mlp in one row-wise kernel
-      VitBlock& b = h->blocks[i];
-      void *img = nullptr, *b1i = nullptr;
-      HIP_TRY(hipMalloc(&img, K(mlp_rows_image_bytes)(D, h->hid, heads * hdp)));
-      h->allocs.push_back(img);
-      HIP_TRY(hipMalloc(&b1i, (size_t)h->hid * 4));
-      h->allocs.push_back(b1i);
-      RC_TRY(K(launch_mlp_pack)(b.fc1.w, b.fc1.Kw, b.fc1.bias, b.fc2.w, b.fc2.Kw, b.proj.w, b.proj.Kw, heads * hdp, img, (float*)b1i, D, h->hid, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.mlp_img = img;
-      b.mlp_b1 = (float*)b1i;
-    }
-    if (K(ln_gemm_rows_supported)(kd(kdt), D, 3 * heads * hdp)) {         // norm1 + qkv in one row-wise kernel
-      VitBlock& b = h->blocks[i];
-      void* img = nullptr;
-      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
-      h->allocs.push_back(img);
-      RC_TRY(K(launch_ln_gemm_pack)(b.qkv.w, b.qkv.Kw, img, D, 3 * heads * hdp, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.qkv_img = img;
-    }
-    if (K(vit_attn_rows_supported)(kd(kdt), D, heads, hdp, h->S)) {       // norm1 + qkv + attention core in one launch: the qkv tensor never reaches HBM
-      VitBlock& b = h->blocks[i];
-      void* img = nullptr;
-      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
-      h->allocs.push_back(img);
-      RC_TRY(K(launch_qkv_attn_rows_pack)(b.qkv.w, b.qkv.Kw, img, D, heads, hdp, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.attn_img = img;
-    }
-  }
-  return 0;
+  return pack_vit_blocks(h, sd, cf.depth, D, heads, h->hd, h->hdp, h->hid, h->S, true, 1.0, &h->blocks);
 }
 
 struct VitPlan { size_t patches, tokens, xn, qkv, ctx, hid, total; };
@@ -1571,6 +1601,47 @@ VitPlan make_vit_plan(const fsvit_vit* h, size_t Bc) {
 
 enum { KID_PATCHIFY = 10, KID_LN = 11 };
 
+// The encoder blocks of a pre-LN ViT (DeiT, LV-ViT) on the token rows `tokens` [Bc * S][D], in place; taps blocks.<i>.
+int vit_blocks_forward(EngineBase* h, const std::vector<VitBlock>& blocks, void* tokens, void* xn, void* qkv, void* ctx, void* hid, int Bc, int S,
+                       int D, int heads, int hd, int hdp, int hidc, float eps, bool first, hipStream_t st) {
+  const int kdt = h->dtype, dt = kd(kdt);
+  const size_t es = h->es;
+  const int M = Bc * S;
+  const float scale = 1.0f / std::sqrt((float)hd);
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    const VitBlock& b = blocks[i];
+    if (b.attn_img) {
+      RC_TRY(timed(h, st, "blocks.norm1+qkv+attn", KID_VITATTNROWS, 2.0 * M * 3.0 * D * D + 4.0 * Bc * heads * (double)S * S * hd, [&]() {
+        return K(launch_vit_attn_rows)(tokens, ctx, b.attn_img, b.qkv.bias, Bc, S, D, heads, hdp, eps, scale, st);
+      }));
+    } else {
+    if (b.qkv_img) {
+      RC_TRY(timed(h, st, "blocks.norm1+qkv", KID_LNGEMM, 2.0 * M * 3.0 * D * D, [&]() {
+        return K(launch_ln_gemm_rows)(tokens, qkv, b.qkv_img, b.qkv.bias, M, D, 3 * heads * hdp, eps, st);
+      }));
+    } else {
+      RC_TRY(timed(h, st, "blocks.norm1", KID_LN, 0.0, [&]() { return K(launch_layernorm)(tokens, xn, M, D, eps, dt, st); }));
+      RC_TRY(run_gemm(h, st, "blocks.attn.qkv", b.qkv, conv_params(b.qkv, xn, qkv, Bc, S, 1, D, D, 1, 1, 1, 0, 3 * heads * hdp, ACT_NONE, nullptr, 0, nullptr), 3.0 * D, D));
+    }
+    RC_TRY(timed(h, st, "blocks.attn.core", KID_ATTN, 4.0 * Bc * heads * (double)S * S * hd,
+                 [&]() { return K(launch_attention)(qkv, ctx, Bc, S, heads, hdp, scale, is_x2(h->dtype) ? 2 : dt, st); }));
+    }
+    if (b.mlp_img) {
+      RC_TRY(timed(h, st, "blocks.proj+norm2+mlp", KID_MLPROWS, 2.0 * M * ((double)heads * hd * D + 2.0 * D * hidc), [&]() {
+        return K(launch_mlp_rows_ln)(tokens, tokens, b.mlp_img, b.mlp_b1, b.proj.bias, b.fc2.bias, ctx, heads * hdp, M, D, hidc, eps, st);
+      }));
+      RC_TRY(tap(h, "blocks." + std::to_string(i), tokens, (size_t)M * D * es, first, st));
+      continue;
+    }
+    RC_TRY(run_gemm(h, st, "blocks.attn.proj", b.proj, conv_params(b.proj, ctx, tokens, Bc, S, 1, heads * hdp, heads * hdp, 1, 1, 1, 0, D, ACT_NONE, tokens, 0, nullptr), D, D));
+    RC_TRY(timed(h, st, "blocks.norm2", KID_LN, 0.0, [&]() { return K(launch_layernorm)(tokens, xn, M, D, eps, dt, st); }));
+    RC_TRY(run_gemm(h, st, "blocks.mlp.fc1", b.fc1, conv_params(b.fc1, xn, hid, Bc, S, 1, D, D, 1, 1, 1, 0, hidc, ACT_GELU, nullptr, 0, nullptr), hidc, D));
+    RC_TRY(run_gemm(h, st, "blocks.mlp.fc2", b.fc2, conv_params(b.fc2, hid, tokens, Bc, S, 1, hidc, hidc, 1, 1, 1, 0, D, ACT_NONE, tokens, 0, nullptr), D, hidc));
+    RC_TRY(tap(h, "blocks." + std::to_string(i), tokens, (size_t)M * D * es, first, st));
+  }
+  return 0;
+}
+
 int vit_forward_chunk(fsvit_vit* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
   const VitPlan pl = make_vit_plan(h, Bc);
   const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, heads = h->cfg.num_heads, hdp = h->hdp;
@@ -1586,38 +1657,7 @@ int vit_forward_chunk(fsvit_vit* h, const float* x, int Bc, float* feat, unsigne
   }
   RC_TRY(timed(h, st, "cls_token", KID_PATCHIFY, 0.0, [&]() { return K(launch_cls_pos)(h->cls_pos0, tokens, Bc, S, D, dt, st); }));
   RC_TRY(tap(h, "embed", tokens, (size_t)M * D * es, first, st));
-  const float scale = 1.0f / std::sqrt((float)h->hd);
-  for (size_t i = 0; i < h->blocks.size(); ++i) {
-    const VitBlock& b = h->blocks[i];
-    if (b.attn_img) {
-      RC_TRY(timed(h, st, "blocks.norm1+qkv+attn", KID_VITATTNROWS, 2.0 * M * 3.0 * D * D + 4.0 * Bc * heads * (double)S * S * h->hd, [&]() {
-        return K(launch_vit_attn_rows)(tokens, ctx, b.attn_img, b.qkv.bias, Bc, S, D, heads, hdp, h->cfg.ln_eps, scale, st);
-      }));
-    } else {
-    if (b.qkv_img) {
-      RC_TRY(timed(h, st, "blocks.norm1+qkv", KID_LNGEMM, 2.0 * M * 3.0 * D * D, [&]() {
-        return K(launch_ln_gemm_rows)(tokens, qkv, b.qkv_img, b.qkv.bias, M, D, 3 * heads * hdp, h->cfg.ln_eps, st);
-      }));
-    } else {
-      RC_TRY(timed(h, st, "blocks.norm1", KID_LN, 0.0, [&]() { return K(launch_layernorm)(tokens, xn, M, D, h->cfg.ln_eps, dt, st); }));
-      RC_TRY(run_gemm(h, st, "blocks.attn.qkv", b.qkv, conv_params(b.qkv, xn, qkv, Bc, S, 1, D, D, 1, 1, 1, 0, 3 * heads * hdp, ACT_NONE, nullptr, 0, nullptr), 3.0 * D, D));
-    }
-    RC_TRY(timed(h, st, "blocks.attn.core", KID_ATTN, 4.0 * Bc * heads * (double)S * S * h->hd,
-                 [&]() { return K(launch_attention)(qkv, ctx, Bc, S, heads, hdp, scale, is_x2(h->dtype) ? 2 : dt, st); }));
-    }
-    if (b.mlp_img) {
-      RC_TRY(timed(h, st, "blocks.proj+norm2+mlp", KID_MLPROWS, 2.0 * M * ((double)heads * h->hd * D + 2.0 * D * h->hid), [&]() {
-        return K(launch_mlp_rows_ln)(tokens, tokens, b.mlp_img, b.mlp_b1, b.proj.bias, b.fc2.bias, ctx, heads * hdp, M, D, h->hid, h->cfg.ln_eps, st);
-      }));
-      RC_TRY(tap(h, "blocks." + std::to_string(i), tokens, (size_t)M * D * es, first, st));
-      continue;
-    }
-    RC_TRY(run_gemm(h, st, "blocks.attn.proj", b.proj, conv_params(b.proj, ctx, tokens, Bc, S, 1, heads * hdp, heads * hdp, 1, 1, 1, 0, D, ACT_NONE, tokens, 0, nullptr), D, D));
-    RC_TRY(timed(h, st, "blocks.norm2", KID_LN, 0.0, [&]() { return K(launch_layernorm)(tokens, xn, M, D, h->cfg.ln_eps, dt, st); }));
-    RC_TRY(run_gemm(h, st, "blocks.mlp.fc1", b.fc1, conv_params(b.fc1, xn, hid, Bc, S, 1, D, D, 1, 1, 1, 0, h->hid, ACT_GELU, nullptr, 0, nullptr), h->hid, D));
-    RC_TRY(run_gemm(h, st, "blocks.mlp.fc2", b.fc2, conv_params(b.fc2, hid, tokens, Bc, S, 1, h->hid, h->hid, 1, 1, 1, 0, D, ACT_NONE, tokens, 0, nullptr), D, h->hid));
-    RC_TRY(tap(h, "blocks." + std::to_string(i), tokens, (size_t)M * D * es, first, st));
-  }
+  RC_TRY(vit_blocks_forward(h, h->blocks, tokens, xn, qkv, ctx, hid, Bc, S, D, heads, h->hd, hdp, h->hid, h->cfg.ln_eps, first, st));
   RC_TRY(timed(h, st, "norm.cls", KID_LN, 0.0, [&]() { return K(launch_final_ln_cls)(tokens, h->ng, h->nb, feat, Bc, S, D, h->cfg.ln_eps, dt, st); }));
   return 0;
 }
@@ -1675,13 +1715,234 @@ extern "C" int fsvit_vit_forward(fsvit_vit* h, const float* x, int n_img, int im
   return 0;
 }
 
+// ==================================================================================== LV-ViT encoder
+// meta_tuning_sun_m/models/lvvit.py:277-318, :413-546 (factory lvvit_micro_80, :583).  The stem is the Visformer ConvBlock at stem_channels
+// (conv1 s2 | conv2 | conv3 + downsample identity, eval BatchNorm folded, LeakyReLU(0.1), MaxPool2d(2)) followed by a 4 x 4 / stride 4 Conv2d
+// projection to embed_dim; cls token + pos_embed; pre-LN blocks with skip_lam; features = norm(x)[:, 0].
+// Stem route: im2col27 + a K = 32 GEMM for conv1; conv2 and conv3 (+ downsample as the tail K slice over the same im2col rows + LeakyReLU +
+// MaxPool2d) on conv_gemm_v2 (a 96-channel map is no power of two: the tap is found per K chunk by division); the projection is the same
+// implicit GEMM as a 4 x 4 / stride 4 conv over the pooled NHWC map, writing token rows 1..np of every image with bias + pos_embed[1:].
+struct fsvit_lvvit : EngineBase {
+  fsvit_lvvit_cfg cfg;
+  int C0 = 0, D = 0, H0 = 0, H1 = 0, npw = 0, np = 0, S = 0, hd = 0, hdp = 0, hid = 0;
+  Layer conv1, conv2, conv3f, pe;
+  Layer conv2h, conv3h;        // bf16 / f16 at 96 channels: the 128-channel weight images of conv2 / conv3f for conv3x3_halo (w = nullptr: not built)
+  float *pos_patch = nullptr, *cls_pos0 = nullptr, *ng = nullptr, *nb = nullptr;
+  std::vector<VitBlock> blocks;
+};
+
+namespace {
+
+int build_lvvit(fsvit_lvvit* h, const SD& sd) {
+  const fsvit_lvvit_cfg& cf = h->cfg;
+  const int kch = 64 / h->es;
+  const int C0 = cf.stem_channels, D = cf.embed_dim, heads = cf.num_heads;
+  if (cf.img_size % 16) return fail(FSVIT_ERR_ARG, "img_size %d must be a multiple of 16", cf.img_size);
+  if (C0 % 32) return fail(FSVIT_ERR_ARG, "stem_channels %d must be a multiple of 32", C0);
+  if (D % heads || D % 32) return fail(FSVIT_ERR_ARG, "unsupported LV-ViT geometry");
+  if (!(cf.skip_lam > 0.0f)) return fail(FSVIT_ERR_ARG, "skip_lam must be positive");
+  h->C0 = C0; h->D = D;
+  h->H0 = cf.img_size / 2; h->H1 = cf.img_size / 4; h->npw = h->H1 / 4; h->np = h->npw * h->npw; h->S = h->np + 1;
+  h->hd = D / heads; h->hdp = round_up(h->hd, kch); h->hid = (int)(D * cf.mlp_ratio);
+  if (h->hid % 32) return fail(FSVIT_ERR_ARG, "hidden width must be a multiple of 32");
+  if (h->S > (h->es == 4 ? 208 : 224)) return fail(FSVIT_ERR_ARG, "attention supports at most %d tokens", h->es == 4 ? 208 : 224);
+  const double eps = cf.bn_eps;
+  {   // ---- stem: BatchNorm folded exactly as build() folds the Visformer stem's
+    const float* w1 = sd.get("patch_embed.conv1.weight", {C0, 3, 3, 3});
+    const float* wd = sd.get("patch_embed.downsample.0.weight", {C0, 3, 3, 3});
+    const float* w2 = sd.get("patch_embed.conv2.weight", {C0, C0, 3, 3});
+    const float* w3 = sd.get("patch_embed.conv3.weight", {C0, C0, 3, 3});
+    const float* wp = sd.get("patch_embed.proj.weight", {D, C0, 4, 4});
+    const float* bp = sd.get("patch_embed.proj.bias", {D});
+    Affine b1 = bn_affine(sd, "patch_embed.bn1", C0, eps), b2 = bn_affine(sd, "patch_embed.bn2", C0, eps);
+    Affine b3 = bn_affine(sd, "patch_embed.bn3", C0, eps), bd = bn_affine(sd, "patch_embed.downsample.1", C0, eps);
+    if (!w1 || !wd || !w2 || !w3 || !wp || !bp || !b1.ok || !b2.ok || !b3.ok || !bd.ok) return FSVIT_ERR_KEY;
+    std::vector<int> cm(27);
+    for (int k = 0; k < 27; ++k) cm[k] = k;
+    RC_TRY(pack_layer(h, &h->conv1, w1, C0, 3, 3, 3, 1, &b1.s, nullptr, b1.t, true, nullptr, 0, &cm, 32));
+    RC_TRY(pack_layer(h, &h->conv2, w2, C0, C0, 3, 3, 1, &b2.s, nullptr, b2.t, true, nullptr, 0, nullptr, 0));
+    {  // conv3f rows = [ bn3-scaled conv3 (K = 9*C0, padded to the K slice) | one tail slice: bn_d-scaled downsample taps ]
+      const int bke = 128 / h->es, K = 9 * C0, Kmain = round_up(K, bke), Kw = Kmain + bke;
+      std::vector<float> pk((size_t)C0 * Kw, 0.0f), pb(C0);
+      for (int o = 0; o < C0; ++o) {
+        for (int c = 0; c < C0; ++c)
+          for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + t9 * C0 + c] = (float)((double)w3[((size_t)o * C0 + c) * 9 + t9] * b3.s[o]);
+        for (int c = 0; c < 3; ++c)
+          for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + Kmain + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
+        pb[o] = (float)(b3.t[o] + bd.t[o]);
+      }
+      h->conv3f.N = C0; h->conv3f.K = K; h->conv3f.Kw = Kw; h->conv3f.groups = 1;
+      RC_TRY(upload(h, pk, true, &h->conv3f.w));
+      void* bdev; RC_TRY(upload(h, pb, false, &bdev)); h->conv3f.bias = (float*)bdev;
+    }
+    std::vector<double> bias(bp, bp + D);
+    RC_TRY(pack_layer(h, &h->pe, wp, D, C0, 4, 4, 1, nullptr, nullptr, bias, true, nullptr, 0, nullptr, 0));   // K = (ky, kx, c): 16 taps of C0
+    // FSVIT_LVVIT_STEM=gemm (read once per build): conv2 / conv3 stay on conv_gemm_v2 - the A/B switch of tools/bench_lvvit.py
+    const char* stem_env = getenv("FSVIT_LVVIT_STEM");
+    if (kd(h->dtype) == 1 && C0 == 96 && !(stem_env && strcmp(stem_env, "gemm") == 0)) {
+      // conv3x3_halo's images (ConvGemmParams::w_cpad = 128): 128 rows, k = tap * 128 + c, zeros past the 96 channels / rows; conv3's tail slice of
+      // downsample taps behind the 9 * 128 main columns.  Same folded values as conv2 / conv3f (the bias tables are shared: 96 entries).
+      for (int which = 0; which < 2; ++which) {
+        const int Kw = 9 * 128 + (which ? 64 : 0);
+        std::vector<float> pk((size_t)128 * Kw, 0.0f);
+        for (int o = 0; o < C0; ++o) {
+          const double so = which ? b3.s[o] : b2.s[o];
+          const float* w = which ? w3 : w2;
+          for (int c = 0; c < C0; ++c)
+            for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + t9 * 128 + c] = (float)((double)w[((size_t)o * C0 + c) * 9 + t9] * so);
+          if (which)
+            for (int c = 0; c < 3; ++c)
+              for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + 9 * 128 + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
+        }
+        Layer& L = which ? h->conv3h : h->conv2h;
+        L.N = C0; L.K = 9 * C0; L.Kw = Kw; L.groups = 1; L.bias = which ? h->conv3f.bias : h->conv2.bias;
+        RC_TRY(upload(h, pk, true, &L.w));
+      }
+    }
+  }
+  {
+    const float* cls = sd.get("cls_token", {1, 1, D});
+    const float* pos = sd.get("pos_embed", {1, h->S, D});
+    const float* g = sd.get("norm.weight", {D});
+    const float* bt = sd.get("norm.bias", {D});
+    if (!cls || !pos || !g || !bt) return FSVIT_ERR_KEY;
+    std::vector<float> pp((size_t)h->np * D), c0(D), gg(g, g + D), bb(bt, bt + D);
+    for (int i = 0; i < h->np; ++i)
+      for (int d = 0; d < D; ++d) pp[(size_t)i * D + d] = pos[(size_t)(i + 1) * D + d];
+    for (int d = 0; d < D; ++d) c0[d] = cls[d] + pos[d];
+    void* dv;
+    RC_TRY(upload(h, pp, false, &dv)); h->pos_patch = (float*)dv;
+    RC_TRY(upload(h, c0, false, &dv)); h->cls_pos0 = (float*)dv;
+    RC_TRY(upload(h, gg, false, &dv)); h->ng = (float*)dv;
+    RC_TRY(upload(h, bb, false, &dv)); h->nb = (float*)dv;
+  }
+  return pack_vit_blocks(h, sd, cf.depth, D, heads, h->hd, h->hdp, h->hid, h->S, false, 1.0 / (double)cf.skip_lam, &h->blocks);
+}
+
+// Workspace of a chunk of Bc images: the token rows, then ONE region shared by the stem scratch of a slice (im2col rows, conv1 / conv2 maps and
+// the pooled map of at most stem_slice_images() images - sized per slice, not per chunk) and the block scratch of the whole chunk.
+struct LvvitPlan { size_t tokens, patches, c1, c2, p1, xn, qkv, ctx, hid, total; int slice; };
+
+LvvitPlan make_lvvit_plan(const fsvit_lvvit* h, size_t Bc) {
+  LvvitPlan p;
+  const size_t es = h->es, P0 = (size_t)h->H0 * h->H0, P1 = (size_t)h->H1 * h->H1, heads = h->cfg.num_heads;
+  const size_t Ss = Bc < (size_t)stem_slice_images() ? Bc : (size_t)stem_slice_images();
+  p.slice = (int)Ss;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
+  p.tokens = take(Bc * h->S * h->D * es);
+  const size_t scratch0 = off;
+  p.patches = take(Ss * P0 * 32 * es);
+  p.c1 = take(Ss * P0 * h->C0 * es);
+  p.c2 = take(Ss * P0 * h->C0 * es);
+  p.p1 = take(Ss * P1 * h->C0 * es);
+  size_t hi = off;
+  off = scratch0;
+  p.xn = take(Bc * h->S * h->D * es);
+  p.qkv = take(Bc * h->S * 3 * heads * h->hdp * es);
+  p.ctx = take(Bc * h->S * heads * h->hdp * es);
+  p.hid = take(Bc * h->S * h->hid * es);
+  p.total = off > hi ? off : hi;
+  return p;
+}
+
+int lvvit_forward_chunk(fsvit_lvvit* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+  const LvvitPlan pl = make_lvvit_plan(h, Bc);
+  const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, C0 = h->C0, heads = h->cfg.num_heads, img = h->cfg.img_size;
+  const size_t es = h->es;
+  void *tokens = ws + pl.tokens, *patches = ws + pl.patches, *c1 = ws + pl.c1, *c2 = ws + pl.c2, *p1 = ws + pl.p1;
+  h->prof_last = nullptr;
+  for (int g0 = 0; g0 < Bc; g0 += pl.slice) {
+    const int n = Bc - g0 < pl.slice ? Bc - g0 : pl.slice;
+    const float* src = x + (size_t)g0 * 3 * img * img;
+    RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() { return K(launch_im2col27)(src, patches, n, img, img, h->H0, h->H0, dt, st); }));
+    RC_TRY(run_gemm(h, st, "stem.conv1", h->conv1, conv_params(h->conv1, patches, c1, n, h->H0, h->H0, 32, 32, 1, 1, 1, 0, C0, ACT_LRELU, nullptr, 0, nullptr), C0, 27));
+    // conv2 and conv3 (+ downsample tail + LeakyReLU + MaxPool2d): the dedicated conv3x3_halo instantiation in bf16 / f16, conv_gemm_v2 otherwise
+    const bool halo = h->conv2h.w && h->conv3h.w;
+    const Layer& L2 = halo ? h->conv2h : h->conv2;
+    const Layer& L3 = halo ? h->conv3h : h->conv3f;
+    ConvGemmParams p2 = conv_params(L2, c1, c2, n, h->H0, h->H0, C0, C0, 3, 3, 1, 1, C0, ACT_LRELU, nullptr, 0, nullptr);
+    ConvGemmParams p3 = conv_params(L3, c2, p1, n, h->H0, h->H0, C0, C0, 3, 3, 1, 1, C0, ACT_LRELU, nullptr, 0, nullptr);
+    p3.x2 = patches; p3.x2_cstride = 32; p3.K2 = 32; p3.pool2 = 1;
+    if (halo) p2.w_cpad = p3.w_cpad = 128;
+    RC_TRY(run_gemm(h, st, "stem.conv2", L2, p2, C0, 9.0 * C0));
+    RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", L3, p3, C0, 9.0 * C0 + 27.0));
+    if (g0 == 0) RC_TRY(tap(h, "stem", p1, (size_t)n * h->H1 * h->H1 * C0 * es, first, st));
+    ConvGemmParams pp = conv_params(h->pe, p1, (unsigned char*)tokens + (size_t)g0 * S * D * es, n, h->H1, h->H1, C0, C0, 4, 4, 4, 0, D, ACT_NONE, nullptr, 0,
+                                    h->pos_patch);
+    pp.y_rpi = S; pp.y_row0 = 1;                                 // patch token i of image b -> row b*S + 1 + i
+    RC_TRY(run_gemm(h, st, "patch_embed.proj", h->pe, pp, D, 16.0 * C0));
+  }
+  RC_TRY(timed(h, st, "cls_token", KID_PATCHIFY, 0.0, [&]() { return K(launch_cls_pos)(h->cls_pos0, tokens, Bc, S, D, dt, st); }));
+  RC_TRY(tap(h, "embed", tokens, (size_t)Bc * S * D * es, first, st));
+  RC_TRY(vit_blocks_forward(h, h->blocks, tokens, ws + pl.xn, ws + pl.qkv, ws + pl.ctx, ws + pl.hid, Bc, S, D, heads, h->hd, h->hdp, h->hid,
+                            h->cfg.ln_eps, first, st));
+  RC_TRY(timed(h, st, "norm.cls", KID_LN, 0.0, [&]() { return K(launch_final_ln_cls)(tokens, h->ng, h->nb, feat, Bc, S, D, h->cfg.ln_eps, dt, st); }));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int fsvit_lvvit_create(const fsvit_lvvit_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors, int dtype, fsvit_lvvit** out) {
+  if (!cfg || !state_dict || !out || n_tensors <= 0) return fail(FSVIT_ERR_ARG, "null argument");
+  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
+  if (cfg->num_heads < 1 || cfg->embed_dim < 32 || cfg->depth < 0 || cfg->stem_channels < 32) return fail(FSVIT_ERR_ARG, "bad LV-ViT configuration");
+  fsvit_lvvit* h = new fsvit_lvvit();
+  h->kind = KIND_LVVIT;
+  h->cfg = *cfg;
+  h->dtype = dtype;
+  h->es = storage_bytes(dtype);
+  SD sd{state_dict, n_tensors};
+  int rc = build_lvvit(h, sd);
+  if (rc != 0) { fsvit_lvvit_destroy(h); return rc; }
+  *out = h;
+  return 0;
+}
+
+extern "C" void fsvit_lvvit_destroy(fsvit_lvvit* h) {
+  if (!h) return;
+  for (void* p : h->allocs) (void)hipFree(p);
+  delete h;
+}
+
+extern "C" int fsvit_lvvit_out_dim(const fsvit_lvvit* h) { return h ? h->D : 0; }
+
+extern "C" size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_images) {
+  if (!h || chunk_images <= 0) return 0;
+  return make_lvvit_plan(h, (size_t)chunk_images).total;
+}
+
+extern "C" int fsvit_lvvit_forward(fsvit_lvvit* h, const float* x, int n_img, int img_h, int img_w, float* feat, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (h && n_img <= 0) return 0;
+  if (!h || !x || !feat || !ws) return fail(FSVIT_ERR_ARG, "null argument");
+  if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)
+    return fail(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) doesn't match model (%d*%d).", img_h, img_w, h->cfg.img_size, h->cfg.img_size);
+  if (((uintptr_t)ws & 255) != 0) return fail(FSVIT_ERR_ARG, "workspace must be 256-byte aligned");
+  int lo = 0, hi = n_img;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) / 2;
+    if (make_lvvit_plan(h, (size_t)mid).total <= ws_bytes) lo = mid; else hi = mid - 1;
+  }
+  if (lo < 1) return fail(FSVIT_ERR_WORKSPACE, "workspace of %zu bytes cannot hold one image (need %zu)", ws_bytes, make_lvvit_plan(h, 1).total);
+  const size_t img_elems = (size_t)3 * img_h * img_w;
+  for (int off = 0; off < n_img; off += lo) {
+    const int bc = n_img - off < lo ? n_img - off : lo;
+    int rc = lvvit_forward_chunk(h, x + (size_t)off * img_elems, bc, feat + (size_t)off * h->D, (unsigned char*)ws, off == 0, (hipStream_t)stream);
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
 static int encoder_forward_any(void* hv, const float* x, int n, int img_h, int img_w, float* feat, void* ws, size_t ws_bytes, void* stream) {
   EngineBase* b = static_cast<EngineBase*>(hv);
   if (b->kind == KIND_VISFORMER) return fsvit_visformer_forward(static_cast<fsvit_visformer*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
   if (b->kind == KIND_VIT) return fsvit_vit_forward(static_cast<fsvit_vit*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
+  if (b->kind == KIND_LVVIT) return fsvit_lvvit_forward(static_cast<fsvit_lvvit*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
   return fail(FSVIT_ERR_ARG, "not an fsvit encoder handle");
 }
 static int encoder_out_dim_any(void* hv) {
   EngineBase* b = static_cast<EngineBase*>(hv);
+  if (b->kind == KIND_LVVIT) return static_cast<fsvit_lvvit*>(b)->D;
   return b->kind == KIND_VISFORMER ? static_cast<fsvit_visformer*>(b)->C3 : (b->kind == KIND_VIT ? static_cast<fsvit_vit*>(b)->D : 0);
 }

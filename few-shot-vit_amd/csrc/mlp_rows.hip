@@ -306,6 +306,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
   constexpr int FD = MR_FD;
   static_assert((SL == 32 || (SL == 24 && RB == 1)) && 2 * NKS == PPC * SLF && (PPC == 1 || PPC == 2), "register budget: <= 128 x + 256 y VGPRs");
   static_assert(!LN || (KC > 0 && RB == 1), "the LayerNorm variant continues from the proj prologue");
+  static_assert(NCH % 2 == 0, "the hidden-chunk loop runs bodies in pairs behind a fixed head and tail: an even number of 32-wide chunks");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* const b1tab = reinterpret_cast<float*>(smem + MR_NST * MR_SLOT);
   float* const bptab = b1tab + HID;                      // LN: proj bias, fc2 bias (channel order)
@@ -1492,7 +1493,7 @@ __global__ void mlp_pack_kernel(const bf16* __restrict__ w1, int k1w, const floa
 // the ViT / DeiT block (proj + bias + residual, LayerNorm, Mlp with biases): DeiT-S geometry (was bit 3 of the retired FSVIT_MLP_ROWS switch)
 bool mlp_rows_ln_supported(int dtype, int C, int hid, int KC) {
   constexpr int mode = 15;
-  return dtype == 1 && (mode & 8) && C == 384 && hid == 1536 && KC == 384;
+  return dtype == 1 && (mode & 8) && C == 384 && (hid == 1536 || hid == 1152) && KC == 384;     // 1152: LV-ViT (mlp_ratio 3, 36 hidden chunks)
 }
 bool mlp_rows_supported(int dtype, int C, int hid) {
   constexpr int mode = 7;      // bit 0: C = 256, bit 1: C = 512, bit 2: proj fusion
@@ -1553,6 +1554,7 @@ int launch_mlp_rows_ln(const void* x, void* y, const void* wimg, const float* b1
   if (M <= 0) return 0;
   if (!ctx || !bproj || !b2) return (int)hipErrorInvalidValue;
   if (C == 384 && hid == 1536 && KC == 384) return launch_mlp_rows_t<384, 1536, 1, 384, true>(x, y, wimg, b1img, b2, ctx, bproj, eps, M, s);
+  if (C == 384 && hid == 1152 && KC == 384) return launch_mlp_rows_t<384, 1152, 1, 384, true>(x, y, wimg, b1img, b2, ctx, bproj, eps, M, s);
   return (int)hipErrorInvalidValue;
 }
 

@@ -445,6 +445,21 @@ class VitEngine(_EncoderEngine):
         return c
 
 
+class LvvitEngine(_EncoderEngine):
+    """cfg: dict(img_size, stem_channels, embed_dim, depth, num_heads[, mlp_ratio, skip_lam, ln_eps, bn_eps]) (lvvit.py:583-587);
+    eval only."""
+    _fn = dict(create='fsvit_lvvit_create', destroy='fsvit_lvvit_destroy', out_dim='fsvit_lvvit_out_dim',
+               workspace_bytes='fsvit_lvvit_workspace_bytes', forward='fsvit_lvvit_forward')
+    _default_chunk = 12800      # as the other encoders; shrinks to half of the free device memory in workspace()
+
+    def _make_cfg(self, cfg):
+        c = _lib.LvvitCfg()
+        c.img_size, c.stem_channels, c.embed_dim, c.depth = cfg['img_size'], cfg['stem_channels'], cfg['embed_dim'], cfg['depth']
+        c.num_heads, c.mlp_ratio, c.skip_lam = cfg['num_heads'], cfg.get('mlp_ratio', 3.0), cfg.get('skip_lam', 2.0)
+        c.ln_eps, c.bn_eps = cfg.get('ln_eps', 1e-5), cfg.get('bn_eps', 1e-5)
+        return c
+
+
 class ops:
     """Operator-level entry points (storage dtype follows the input tensors: fp32 or bf16)."""
     _sgd_tables = {}
@@ -499,9 +514,9 @@ class ops:
         return y
 
     @staticmethod
-    def conv_stem_tail(x, w, bias, pos, x2, K2):
+    def conv_stem_tail(x, w, bias, pos, x2, K2, numerics=None):
         """Fused stem tail: x NHWC [B,H,W,Cin], w [N][Kw] (conv3 taps | one tail K slice), x2 [B*H*W][x2_cstride] im2col rows,
-        pos [(H/2)*(W/2)][N] fp32 -> y NHWC [B,H/2,W/2,N]."""
+        pos [(H/2)*(W/2)][N] fp32 -> y NHWC [B,H/2,W/2,N].  numerics 'bf16x2' / 'f16x2': x / x2 fp32, w = ops.x2_limbs(packed fp32 weights)."""
         _require_cuda(x, w, x2, pos)
         lib = _lib.load()
         B, H, W, Cin = x.shape
@@ -509,7 +524,20 @@ class ops:
         y = torch.empty(B, H // 2, W // 2, N, dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(lib.fsvit_conv_stem_tail(_ptr(x), _ptr(w), _ptr(bias), _ptr(pos), _ptr(x2), x2.shape[-1], int(K2), _ptr(y), B, H, W, Cin, N,
-                                                w.shape[-1], ops._dt(x), _stream_ptr(x.device)))
+                                                w.shape[-1], DTYPES[numerics] if numerics else ops._dt(x), _stream_ptr(x.device)))
+        return y
+
+    @staticmethod
+    def stem96_conv(x, w_img, bias, x2=None, K2=32):
+        """LV-ViT stem conv2 (x2 None) or conv3 + downsample tail + LeakyReLU + MaxPool2d(2) on the dedicated kernel (fsvit_stem96_conv): x NHWC
+        [B,H,40,96] bf16 / f16, w_img the 128-channel image [128][9*128 (+64)] (k = tap*128 + c), bias [96] fp32 -> y NHWC, 96 channels."""
+        _require_cuda(x, w_img)
+        B, H, W, _ = x.shape
+        pool = x2 is not None
+        y = torch.empty(B, H // 2 if pool else H, W // 2 if pool else W, 96, dtype=x.dtype, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().fsvit_stem96_conv(_ptr(x), _ptr(w_img), _ptr(bias), _ptr(x2), x2.shape[-1] if pool else 0, int(K2) if pool else 0,
+                                                     _ptr(y), B, H, W, int(pool), ops._dt(x), _stream_ptr(x.device)))
         return y
 
     @staticmethod

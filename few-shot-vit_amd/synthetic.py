@@ -56,11 +56,15 @@ def load_bn_calibration(name: str = 'visformer_micro_80') -> Dict[str, torch.Ten
         return {k: torch.from_numpy(z[k].copy()) for k in z.files}
 
 
+# encoders whose procedural weights give O(1) activations without calibrated BatchNorm statistics (no calibration file is shipped)
+CALIBRATION_FREE = ('lvvit_micro_80',)
+
+
 def synthetic_checkpoint_sd(shapes: Dict[str, tuple], calib: str = 'visformer_micro_80'):
     """Procedural weights + shipped BN calibration = the synthetic 'checkpoint' used by the
     parity tests, the benchmark and the CPU baseline alike."""
     sd = procedural_state_dict(shapes)
-    if calib is not None:
+    if calib is not None and calib not in CALIBRATION_FREE:
         stats = load_bn_calibration(calib)
         for k, v in stats.items():
             if k not in sd or tuple(sd[k].shape) != tuple(v.shape):

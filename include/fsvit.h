@@ -126,6 +126,38 @@ size_t fsvit_vit_workspace_bytes(const fsvit_vit* h, int chunk_images);
 int fsvit_vit_forward(fsvit_vit* h, const float* x_nchw_dev, int n_img, int img_h, int img_w, float* feat_dev,
                       void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- LV-ViT encoder
+ * Replaces `LV_ViT.__init__` + `load_state_dict` + `forward` in eval mode for the `lvvit_micro_80` factory
+ * (meta_tuning_sun_m/models/lvvit.py:413-546, :583): ConvBlock stem (conv1 s2 / conv2 / conv3 + downsample at stem_channels, eval
+ * BatchNorm, LeakyReLU(0.1), MaxPool2d(2)), a 4x4 / stride 4 projection to embed_dim, cls token + pos_embed, pre-LN blocks
+ * (qkv_bias=False, residual branches divided by skip_lam), features = norm(x)[:, 0].  Same conventions as the ViT handle;
+ * state-dict keys `patch_embed.{conv1,bn1,conv2,bn2,conv3,bn3,downsample.0,downsample.1,proj}.*`, `cls_token`, `pos_embed`,
+ * `blocks.N.*`, `norm.*`.  Eval only. */
+typedef struct fsvit_lvvit fsvit_lvvit;
+typedef struct fsvit_lvvit_cfg {        /* lvvit.py:583-587 */
+  int img_size;                         /* 80 */
+  int stem_channels;                    /* 96: a multiple of 32 */
+  int embed_dim;                        /* 384 */
+  int depth;                            /* 8 */
+  int num_heads;                        /* 6 */
+  float mlp_ratio;                      /* 3 */
+  float skip_lam;                       /* 2 */
+  float ln_eps;                         /* 1e-5 (nn.LayerNorm default) */
+  float bn_eps;                         /* 1e-5 */
+} fsvit_lvvit_cfg;
+int fsvit_lvvit_create(const fsvit_lvvit_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors, int dtype, fsvit_lvvit** out);
+void fsvit_lvvit_destroy(fsvit_lvvit* h);
+int fsvit_lvvit_out_dim(const fsvit_lvvit* h);
+size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_images);
+int fsvit_lvvit_forward(fsvit_lvvit* h, const float* x_nchw_dev, int n_img, int img_h, int img_w, float* feat_dev,
+                        void* ws_dev, size_t ws_bytes, void* stream);
+
+/* LV-ViT stem conv2 (pool = 0) or conv3 + downsample tail + LeakyReLU + MaxPool2d(2) (pool = 1) at 96 channels on the dedicated kernel: x NHWC
+ * [B][H][W][96] (bf16 / f16, W = 40, H a multiple of 8), w the 128-channel weight image [128][9 * 128 (+ 64)] (k = tap * 128 + c, zero past 96
+ * channels and rows; tail slice last), bias [96] fp32 or NULL, x2 the im2col rows [B*H*W][x2_cstride] (pool = 1, K2 = 32); y NHWC, 96 channels. */
+int fsvit_stem96_conv(const void* x_dev, const void* w_dev, const float* bias_dev, const void* x2_dev, int x2_cstride, int K2, void* y_dev,
+                      int B, int H, int W, int pool, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- episode head
  * Replaces MetaBaseline.forward after the encoder call (test_phase/models/meta_baseline.py:33-47),
  * utils.compute_logits (utils/__init__.py:78-101) and, per episode, F.cross_entropy +
@@ -143,7 +175,7 @@ int fsvit_proto_head_devtemp(const float* feat_shot_dev, const float* feat_query
 /* Whole `MetaBaseline.forward(x_shot, x_query)` (meta_baseline.py:24-47) in eval mode:
  * x_shot_dev [E,way,shot,3,H,W], x_query_dev [E,Q,3,H,W] fp32 -> logits_dev [E,Q,way].
  * feat_dev: scratch [(E*way*shot + E*Q), out_dim] fp32. */
-int fsvit_meta_baseline_forward(void* encoder /* fsvit_visformer* or fsvit_vit* */, const float* x_shot_dev, const float* x_query_dev,
+int fsvit_meta_baseline_forward(void* encoder /* fsvit_visformer*, fsvit_vit* or fsvit_lvvit* */, const float* x_shot_dev, const float* x_query_dev,
                                 int E, int way, int shot, int Q, int img_h, int img_w, float temp, int method,
                                 float* logits_dev, float* acc_dev, float* loss_dev, float* feat_dev,
                                 void* ws_dev, size_t ws_bytes, void* stream);
