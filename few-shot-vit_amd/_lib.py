@@ -128,6 +128,35 @@ SIGNATURES = {
     'fsvit_image_transform_gather': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i,
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _vp]),
     'fsvit_attention_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    # operator entry points (tests, tools): the memory-bound training kernels one by one
+    'fsvit_op_bn_reduce_blocks': (_i, [_i]),
+    'fsvit_op_ln_bwd_blocks': (_i, [_i]),
+    'fsvit_op_pool_bn_bwd_blocks': (_i, [_i, _i, _i, _i, _i]),
+    'fsvit_op_bn_train_forward': (_i, [_vp, _i, _i, _i, _fp, _fp, _fp, _fp, _f, _f, _i, _vp, _vp, _fp, _i, _vp, _i, _vp, _fp, _fp, _vp]),
+    'fsvit_op_bn_train_backward': (_i, [_vp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _vp, _fp, _vp, _i, _vp, _fp, _fp, _fp, _fp, _vp]),
+    'fsvit_op_bn_act_bwd': (_i, [_vp, _vp, _fp, _fp, _vp, _vp, _i, _i, _i, _vp]),
+    'fsvit_op_stem_tail_train_forward': (_i, [_vp, _fp, _fp, _vp, _fp, _fp, _fp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_stem_tail_train_backward': (_i, [_vp, _vp, _vp, _vp, _fp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_pool_act_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_maxpool2_idx': (_i, [_vp, _fp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_maxpool2_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_ln_train_forward': (_i, [_vp, _fp, _fp, _vp, _fp, _fp, _i, _i, _f, _i, _vp]),
+    'fsvit_op_ln_train_backward': (_i, [_vp, _vp, _fp, _fp, _fp, _vp, _vp, _fp, _fp, _fp, _i, _i, _i, _vp]),
+    'fsvit_op_vit_assemble': (_i, [_vp, _fp, _fp, _vp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_vit_patch_rows': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_vit_cls_ln_forward': (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _vp]),
+    'fsvit_op_vit_cls_ln_backward': (_i, [_fp, _vp, _fp, _fp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_gelu': (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    'fsvit_op_add_scaled': (_i, [_vp, _vp, _fp, _vp, _sz, _sz, _i, _vp]),
+    'fsvit_op_avgpool_bwd': (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_batch_sum': (_i, [_vp, _fp, _i, _sz, _i, _vp]),
+    'fsvit_op_bcast_add': (_i, [_vp, _fp, _vp, _i, _sz, _i, _vp]),
+    'fsvit_op_colsum': (_i, [_vp, _fp, _fp, _i, _i, _i, _vp]),
+    'fsvit_op_unpatch2': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_droppath_scales': (_i, [_fp, _fp, _i, _i, C.POINTER(C.c_float), _vp]),
+    'fsvit_op_fill_f32': (_i, [_fp, _f, _sz, _vp]),
+    'fsvit_op_scale_copy': (_i, [_fp, _fp, _sz, _f, _vp]),
+    'fsvit_op_fold_prenorm': (_i, [_fp, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_sampler_draw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 

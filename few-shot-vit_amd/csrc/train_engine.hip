@@ -1433,3 +1433,272 @@ extern "C" int fsvit_visformer_train_set_token_grad(fsvit_visformer_trainer* t, 
   t->dtokens = dtokens_dev;               // consumed (and cleared) by the next fsvit_visformer_train_backward; NULL: none
   return 0;
 }
+
+// ================================================================ operator entry points (tests, tools)
+// Thin wrappers of the launchers in train_kernels.h: they validate what the kernels assume and launch nothing on a shape the kernels do not cover.
+// No engine path goes through them.  Storage dtype: FSVIT_F32 or FSVIT_BF16 (train_kernels.hip is built for these two only).
+namespace {
+#define OP_FAIL(...) return fsvit_set_error(FSVIT_ERR_ARG, __VA_ARGS__)
+#define OP_DT(fn) do { if (dtype != FSVIT_F32 && dtype != FSVIT_BF16) OP_FAIL(fn ": storage dtype %d (the training kernels are built for FSVIT_F32 and FSVIT_BF16 only)", dtype); } while (0)
+#define OP_RUN(fn, expr) do { int _rc = (expr); if (_rc) return fsvit_set_error(_rc > 0 ? _rc : FSVIT_ERR_ARG, fn ": launch failed (%d)", _rc); } while (0)
+// channel counts bn_reduce_kernel covers: 4 (bf16: 8 where C % 8 == 0) channels per lane, and past 256 lanes whole passes of 256 only (the block
+// barrier sits inside the per-pass loop)
+const char* bn_channels_bad(int C, int dtype) {
+  if (C <= 0 || C % 4) return "C must be a positive multiple of 4";
+  const int V = (dtype != FSVIT_F32 && C % 8 == 0) ? 8 : 4, lanes = C / V;
+  if (lanes > 256 && lanes % 256) return "more than 256 channel lanes must come in whole passes of 256";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int fsvit_op_bn_reduce_blocks(int M) { return bn_reduce_blocks(M); }
+extern "C" int fsvit_op_ln_bwd_blocks(int M) { return ln_bwd_blocks(M); }
+extern "C" int fsvit_op_pool_bn_bwd_blocks(int B, int OH, int OW, int C, int dtype) {
+  if (B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || C % 8 || (dtype != FSVIT_F32 && dtype != FSVIT_BF16) || !pool_bn_bwd_supported(C, dtype)) return 0;
+  return pool_bn_bwd_blocks(B, OH, OW, C, dtype);
+}
+
+extern "C" int fsvit_op_bn_train_forward(void* z, int M, int C, int dtype, const float* gamma, const float* beta, float* running_mean, float* running_var, float eps,
+                                         float momentum, int frozen, const void* add_a, const void* add_b, const float* add_scale, int rows_per_img, const void* res,
+                                         int act, void* y, float* stats, float* partial, void* stream) {
+  OP_DT("fsvit_op_bn_train_forward");
+  if (!z || !gamma || !beta || !stats || !partial) OP_FAIL("fsvit_op_bn_train_forward: null argument");
+  if (const char* why = bn_channels_bad(C, dtype)) OP_FAIL("fsvit_op_bn_train_forward: C = %d: %s", C, why);
+  if (M < 1 || (!frozen && M < 2)) OP_FAIL("fsvit_op_bn_train_forward: Expected more than 1 value per channel when training (M = %d)", M);
+  if (frozen && (!running_mean || !running_var)) OP_FAIL("fsvit_op_bn_train_forward: frozen statistics need running_mean / running_var");
+  if ((running_mean == nullptr) != (running_var == nullptr)) OP_FAIL("fsvit_op_bn_train_forward: running_mean and running_var come together");
+  if (act != FSVIT_ACT_NONE && act != FSVIT_ACT_LRELU) OP_FAIL("fsvit_op_bn_train_forward: act %d (none | LeakyReLU)", act);
+  if ((add_a || add_scale) && !add_b) OP_FAIL("fsvit_op_bn_train_forward: add_a / add_scale without add_b");
+  if (add_b && !add_a) OP_FAIL("fsvit_op_bn_train_forward: the fused residual add needs both operands");
+  if (add_scale && (rows_per_img <= 0 || M % rows_per_img)) OP_FAIL("fsvit_op_bn_train_forward: M = %d is not images * rows_per_img (%d)", M, rows_per_img);
+  hipStream_t st = (hipStream_t)stream;
+  float *mean = stats, *invstd = stats + C, *sa = stats + 2 * C, *sb = stats + 3 * C;
+  if (frozen) {
+    if (add_b) OP_RUN("add_scaled", launch_add_scaled(add_a, add_b, add_scale, z, (size_t)M * C, (size_t)(add_scale ? rows_per_img : M) * C, dtype, st));
+    OP_RUN("bn_frozen_coeffs", launch_bn_frozen_coeffs(C, eps, gamma, beta, running_mean, running_var, mean, invstd, sa, sb, st));
+  } else {
+    if (add_b) OP_RUN("bn_reduce", launch_bn_reduce(z, nullptr, nullptr, nullptr, partial, M, C, 0, dtype, st, add_a, add_b, add_scale, add_scale ? rows_per_img : M));
+    else OP_RUN("bn_reduce", launch_bn_reduce(z, nullptr, nullptr, nullptr, partial, M, C, 0, dtype, st));
+    OP_RUN("bn_fwd_finalize", launch_bn_fwd_finalize(partial, M, C, eps, momentum, gamma, beta, running_mean, running_var, mean, invstd, sa, sb, st));
+  }
+  if (y) OP_RUN("bn_apply", launch_bn_apply(z, sa, sb, res, y, (size_t)M, C, act, dtype, st));
+  return 0;
+}
+
+extern "C" int fsvit_op_bn_train_backward(const void* dy, const void* z, const float* mean, const float* invstd, const float* gamma, int M, int C, int dtype, int frozen,
+                                          const float* act_sa, const float* act_sb, const void* acc, const float* scale2, void* out2, int rows_per_img, void* dz,
+                                          float* dgamma, float* dbeta, float* coef, float* partial, void* stream) {
+  OP_DT("fsvit_op_bn_train_backward");
+  if (!dy || !z || !mean || !invstd || !gamma || !dz || !dgamma || !dbeta || !coef || !partial) OP_FAIL("fsvit_op_bn_train_backward: null argument");
+  if (const char* why = bn_channels_bad(C, dtype)) OP_FAIL("fsvit_op_bn_train_backward: C = %d: %s", C, why);
+  if (M < 1) OP_FAIL("fsvit_op_bn_train_backward: M = %d", M);
+  if ((act_sa == nullptr) != (act_sb == nullptr)) OP_FAIL("fsvit_op_bn_train_backward: act_sa and act_sb come together");
+  if (scale2 && !out2) OP_FAIL("fsvit_op_bn_train_backward: scale2 without out2");
+  if (scale2 && (rows_per_img <= 0 || M % rows_per_img)) OP_FAIL("fsvit_op_bn_train_backward: M = %d is not images * rows_per_img (%d)", M, rows_per_img);
+  hipStream_t st = (hipStream_t)stream;
+  OP_RUN("bn_reduce", launch_bn_reduce(dy, z, mean, invstd, partial, M, C, 1, dtype, st, nullptr, nullptr, nullptr, 0, act_sa, act_sb));
+  OP_RUN("bn_bwd_finalize", launch_bn_bwd_finalize(partial, M, C, gamma, invstd, dgamma, dbeta, coef, coef + C, coef + 2 * C, frozen ? 1 : 0, st));
+  OP_RUN("bn_bwd_apply", launch_bn_bwd_apply(dy, z, mean, invstd, coef, coef + C, coef + 2 * C, dz, (size_t)M, C, dtype, st, acc, scale2, out2,
+                                            (size_t)(scale2 ? rows_per_img : 0), act_sa, act_sb));
+  return 0;
+}
+
+extern "C" int fsvit_op_bn_act_bwd(const void* dout, const void* z, const float* sa, const float* sb, const void* res, void* g, int M, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_bn_act_bwd");
+  if (!dout || !z || !sa || !sb || !g) OP_FAIL("fsvit_op_bn_act_bwd: null argument");
+  if (M < 1 || C <= 0 || C % 4) OP_FAIL("fsvit_op_bn_act_bwd: M = %d, C = %d (C a multiple of 4)", M, C);
+  OP_RUN("bn_act_bwd", launch_bn_act_bwd(dout, z, sa, sb, res, g, (size_t)M, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+
+static int op_pool_shape(const char* fn, int B, int OH, int OW, int C, int cmul) {
+  if (B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || C % cmul) return fsvit_set_error(FSVIT_ERR_ARG, "%s: B %d, OH %d, OW %d, C %d (C a multiple of %d)", fn, B, OH, OW, C, cmul);
+  return 0;
+}
+
+extern "C" int fsvit_op_stem_tail_train_forward(const void* z, const float* sa, const float* sb, const void* res, const float* rsa, const float* rsb, const float* pos,
+                                                void* out, unsigned char* arg, int B, int OH, int OW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_stem_tail_train_forward");
+  if (!z || !sa || !sb || !out || !arg) OP_FAIL("fsvit_op_stem_tail_train_forward: null argument");
+  if (int rc = op_pool_shape("fsvit_op_stem_tail_train_forward", B, OH, OW, C, 8)) return rc;
+  if ((rsa == nullptr) != (rsb == nullptr) || (rsa && !res)) OP_FAIL("fsvit_op_stem_tail_train_forward: rsa / rsb come together and need res");
+  OP_RUN("bn_pool_fwd", launch_bn_pool_fwd(z, sa, sb, res, pos, out, arg, B, OH, OW, C, dtype, (hipStream_t)stream, rsa, rsb));
+  return 0;
+}
+
+// stats3 / statsd: mean | invstd ([2][C]); coef: [6][C] scratch (ca | cb | cc of both BatchNorms); partial: 4 * C * fsvit_op_pool_bn_bwd_blocks() floats
+extern "C" int fsvit_op_stem_tail_train_backward(const void* dout, const unsigned char* arg, const void* z3, const void* zd, const float* stats3, const float* statsd,
+                                                 const float* gamma3, const float* gammad, void* dz3, void* dzd, float* dgamma3, float* dbeta3, float* dgammad,
+                                                 float* dbetad, float* coef, float* partial, int B, int OH, int OW, int C, int dtype, int frozen, void* stream) {
+  OP_DT("fsvit_op_stem_tail_train_backward");
+  if (!dout || !arg || !z3 || !zd || !stats3 || !statsd || !gamma3 || !gammad || !dz3 || !dzd || !dgamma3 || !dbeta3 || !dgammad || !dbetad || !coef || !partial)
+    OP_FAIL("fsvit_op_stem_tail_train_backward: null argument");
+  if (int rc = op_pool_shape("fsvit_op_stem_tail_train_backward", B, OH, OW, C, 8)) return rc;
+  if (!pool_bn_bwd_supported(C, dtype))
+    OP_FAIL("fsvit_op_stem_tail_train_backward: C = %d has no row-walking form (channel lanes must divide 256): use pool_act_bwd + two bn_train_backward", C);
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = pool_bn_bwd_blocks(B, OH, OW, C, dtype);
+  const long M0 = (long)B * OH * OW * 4;
+  if (M0 > 0x7fffffffL) OP_FAIL("fsvit_op_stem_tail_train_backward: map too large");
+  float *coef3 = coef, *coefd = coef + 3 * C, *partd = partial + (size_t)nb * 2 * C;
+  OP_RUN("pool_bn_bwd_reduce", launch_pool_bn_bwd_reduce(dout, arg, z3, zd, stats3, stats3 + C, statsd, statsd + C, partial, partd, B, OH, OW, C, dtype, st));
+  OP_RUN("bn_bwd_finalize", launch_bn_bwd_finalize_nblk(partial, nb, (int)M0, C, gamma3, stats3 + C, dgamma3, dbeta3, coef3, coef3 + C, coef3 + 2 * C, frozen ? 1 : 0, st));
+  OP_RUN("bn_bwd_finalize", launch_bn_bwd_finalize_nblk(partd, nb, (int)M0, C, gammad, statsd + C, dgammad, dbetad, coefd, coefd + C, coefd + 2 * C, frozen ? 1 : 0, st));
+  OP_RUN("pool_bn_bwd_apply", launch_pool_bn_bwd_apply(dout, arg, z3, zd, stats3, stats3 + C, statsd, statsd + C, coef3, coefd, dz3, dzd, B, OH, OW, C, dtype, st));
+  return 0;
+}
+
+extern "C" int fsvit_op_pool_act_bwd(const void* dout, const unsigned char* arg, void* g, int B, int OH, int OW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_pool_act_bwd");
+  if (!dout || !arg || !g) OP_FAIL("fsvit_op_pool_act_bwd: null argument");
+  if (int rc = op_pool_shape("fsvit_op_pool_act_bwd", B, OH, OW, C, 8)) return rc;
+  OP_RUN("pool_act_bwd", launch_pool_act_bwd(dout, arg, g, B, OH, OW, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_maxpool2_idx(const void* in, const float* pos, void* out, unsigned char* arg, int B, int OH, int OW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_maxpool2_idx");
+  if (!in || !out || !arg) OP_FAIL("fsvit_op_maxpool2_idx: null argument");
+  if (int rc = op_pool_shape("fsvit_op_maxpool2_idx", B, OH, OW, C, 1)) return rc;
+  OP_RUN("maxpool2_idx", launch_maxpool2_idx(in, pos, out, arg, B, OH, OW, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_maxpool2_bwd(const void* dout, const unsigned char* arg, void* din, int B, int OH, int OW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_maxpool2_bwd");
+  if (!dout || !arg || !din) OP_FAIL("fsvit_op_maxpool2_bwd: null argument");
+  if (int rc = op_pool_shape("fsvit_op_maxpool2_bwd", B, OH, OW, C, 1)) return rc;
+  OP_RUN("maxpool2_bwd", launch_maxpool2_bwd(dout, arg, din, B, OH, OW, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+
+// LayerNorm rows: one wave per row and, in the backward, 8 * D floats of LDS per block -> D a multiple of 4, at most 2048
+static int op_ln_shape(const char* fn, int M, int D) {
+  if (M < 1 || D <= 0 || D % 4 || D > 2048) return fsvit_set_error(FSVIT_ERR_ARG, "%s: M = %d, D = %d (D a multiple of 4, at most 2048)", fn, M, D);
+  return 0;
+}
+extern "C" int fsvit_op_ln_train_forward(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps, int dtype,
+                                         void* stream) {
+  OP_DT("fsvit_op_ln_train_forward");
+  if (!x || !gamma || !beta || !y || !mean || !rstd) OP_FAIL("fsvit_op_ln_train_forward: null argument");
+  if (int rc = op_ln_shape("fsvit_op_ln_train_forward", M, D)) return rc;
+  OP_RUN("ln_train_fwd", launch_ln_train_fwd(x, gamma, beta, y, mean, rstd, M, D, eps, dtype, (hipStream_t)stream));
+  return 0;
+}
+// partial: fsvit_op_ln_bwd_blocks(M) * 2 * D floats; add (may be dx), dgamma, dbeta may be null
+extern "C" int fsvit_op_ln_train_backward(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const void* add, void* dx,
+                                          float* partial, float* dgamma, float* dbeta, int M, int D, int dtype, void* stream) {
+  OP_DT("fsvit_op_ln_train_backward");
+  if (!dy || !x || !mean || !rstd || !gamma || !dx || !partial) OP_FAIL("fsvit_op_ln_train_backward: null argument");
+  if (int rc = op_ln_shape("fsvit_op_ln_train_backward", M, D)) return rc;
+  OP_RUN("ln_bwd", launch_ln_bwd(dy, x, mean, rstd, gamma, add, dx, partial, dgamma, dbeta, M, D, dtype, (hipStream_t)stream));
+  return 0;
+}
+static int op_vit_shape(const char* fn, int B, int S, int D) {
+  if (B < 1 || S < 1 || D <= 0 || D % 4) return fsvit_set_error(FSVIT_ERR_ARG, "%s: B = %d, S = %d, D = %d (D a multiple of 4)", fn, B, S, D);
+  return 0;
+}
+extern "C" int fsvit_op_vit_assemble(const void* zpe, const float* cls, const float* pos, void* tokens, int B, int S, int D, int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_assemble");
+  if ((!zpe && S > 1) || !cls || !pos || !tokens) OP_FAIL("fsvit_op_vit_assemble: null argument");
+  if (int rc = op_vit_shape("fsvit_op_vit_assemble", B, S, D)) return rc;
+  OP_RUN("vit_assemble", launch_vit_assemble(zpe, cls, pos, tokens, B, S, D, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_vit_patch_rows(const void* dtok, void* dzpe, int B, int S, int D, int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_patch_rows");
+  if (!dtok || (!dzpe && S > 1)) OP_FAIL("fsvit_op_vit_patch_rows: null argument");
+  if (int rc = op_vit_shape("fsvit_op_vit_patch_rows", B, S, D)) return rc;
+  if (S == 1) return 0;                                  // no patch rows
+  OP_RUN("vit_patch_rows", launch_vit_patch_rows(dtok, dzpe, B, S, D, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_vit_cls_ln_forward(const void* tokens, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int B, int S, int D, float eps,
+                                           int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_cls_ln_forward");
+  if (!tokens || !gamma || !beta || !feat || !mean || !rstd) OP_FAIL("fsvit_op_vit_cls_ln_forward: null argument");
+  if (B < 1 || S < 1 || D < 1) OP_FAIL("fsvit_op_vit_cls_ln_forward: B = %d, S = %d, D = %d", B, S, D);
+  OP_RUN("vit_cls_ln_fwd", launch_vit_cls_ln_fwd(tokens, gamma, beta, feat, mean, rstd, B, S, D, eps, dtype, (hipStream_t)stream));
+  return 0;
+}
+// dtok [B][S][D] is zeroed here (the kernel writes the cls rows only); partial: B * 2 * D floats
+extern "C" int fsvit_op_vit_cls_ln_backward(const float* dfeat, const void* tokens, const float* mean, const float* rstd, const float* gamma, void* dtok, float* partial,
+                                            float* dgamma, float* dbeta, int B, int S, int D, int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_cls_ln_backward");
+  if (!dfeat || !tokens || !mean || !rstd || !gamma || !dtok || !partial) OP_FAIL("fsvit_op_vit_cls_ln_backward: null argument");
+  if (B < 1 || S < 1 || D < 1) OP_FAIL("fsvit_op_vit_cls_ln_backward: B = %d, S = %d, D = %d", B, S, D);
+  hipError_t e = hipMemsetAsync(dtok, 0, (size_t)B * S * D * (dtype == FSVIT_F32 ? 4 : 2), (hipStream_t)stream);
+  if (e != hipSuccess) return fsvit_set_error((int)e, "fsvit_op_vit_cls_ln_backward: memset");
+  OP_RUN("vit_cls_ln_bwd", launch_vit_cls_ln_bwd(dfeat, tokens, mean, rstd, gamma, dtok, partial, dgamma, dbeta, B, S, D, dtype, (hipStream_t)stream));
+  return 0;
+}
+
+// elementwise kernels with 4-element accesses: n (and per_img) multiples of 4
+extern "C" int fsvit_op_gelu(const void* dh, const void* z, void* out, size_t n, int dtype, void* stream) {      // dh == NULL: forward
+  OP_DT("fsvit_op_gelu");
+  if (!z || !out || n == 0 || n % 4) OP_FAIL("fsvit_op_gelu: null argument or n = %zu not a positive multiple of 4", n);
+  if (dh) OP_RUN("gelu_bwd", launch_gelu_bwd(dh, z, out, n, dtype, (hipStream_t)stream));
+  else OP_RUN("gelu_fwd", launch_gelu_fwd(z, out, n, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_add_scaled(const void* a, const void* br, const float* scale, void* out, size_t n, size_t per_img, int dtype, void* stream) {
+  OP_DT("fsvit_op_add_scaled");
+  if (!br || !out || n == 0 || n % 4) OP_FAIL("fsvit_op_add_scaled: null argument or n = %zu not a positive multiple of 4", n);
+  if (scale && (per_img == 0 || per_img % 4 || n % per_img)) OP_FAIL("fsvit_op_add_scaled: per_img = %zu (a multiple of 4 that divides n)", per_img);
+  OP_RUN("add_scaled", launch_add_scaled(a, br, scale, out, n, scale ? per_img : n, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_avgpool_bwd(const float* dfeat, void* dx, int B, int HW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_avgpool_bwd");
+  if (!dfeat || !dx || B < 1 || HW < 1 || C < 1) OP_FAIL("fsvit_op_avgpool_bwd: bad argument");
+  OP_RUN("avgpool_bwd", launch_avgpool_bwd(dfeat, dx, B, HW, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_batch_sum(const void* g, float* out, int B, size_t per_img, int dtype, void* stream) {
+  OP_DT("fsvit_op_batch_sum");
+  if (!g || !out || B < 1 || per_img == 0 || per_img % 4) OP_FAIL("fsvit_op_batch_sum: null argument, B < 1 or per_img = %zu not a positive multiple of 4", per_img);
+  OP_RUN("batch_sum", launch_batch_sum(g, out, B, per_img, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_bcast_add(const void* x, const float* p, void* y, int B, size_t per_img, int dtype, void* stream) {
+  OP_DT("fsvit_op_bcast_add");
+  if (!x || !p || !y || B < 1 || per_img == 0 || per_img % 4) OP_FAIL("fsvit_op_bcast_add: null argument, B < 1 or per_img = %zu not a positive multiple of 4", per_img);
+  OP_RUN("bcast_add", launch_bcast_add(x, p, y, B, per_img, dtype, (hipStream_t)stream));
+  return 0;
+}
+// partial: fsvit_op_bn_reduce_blocks(M) * 2 * C floats
+extern "C" int fsvit_op_colsum(const void* a, float* partial, float* out, int M, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_colsum");
+  if (!a || !partial || !out || M < 1) OP_FAIL("fsvit_op_colsum: null argument or M < 1");
+  if (const char* why = bn_channels_bad(C, dtype)) OP_FAIL("fsvit_op_colsum: C = %d: %s", C, why);
+  OP_RUN("colsum", launch_colsum(a, partial, out, M, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int dtype, void* stream) {
+  OP_DT("fsvit_op_unpatch2");
+  if (!g || !dx) OP_FAIL("fsvit_op_unpatch2: null argument");
+  if (int rc = op_pool_shape("fsvit_op_unpatch2", B, OH, OW, C, 1)) return rc;
+  OP_RUN("unpatch2", launch_unpatch2(g, dx, B, OH, OW, C, dtype, (hipStream_t)stream));
+  return 0;
+}
+// keep_host [ncalls]: host array of keep probabilities; masks / scales [ncalls][n_img] on the device
+extern "C" int fsvit_op_droppath_scales(const float* masks, float* scales, int ncalls, int n_img, const float* keep_host, void* stream) {
+  if (!masks || !scales || !keep_host || ncalls < 1 || n_img < 1) OP_FAIL("fsvit_op_droppath_scales: bad argument");
+  for (int i = 0; i < ncalls; ++i) if (!(keep_host[i] > 0.f)) OP_FAIL("fsvit_op_droppath_scales: keep[%d] = %g", i, (double)keep_host[i]);
+  OP_RUN("droppath_scales", launch_droppath_scales(masks, scales, ncalls, n_img, keep_host, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_fill_f32(float* p, float v, size_t n, void* stream) {
+  if (!p || n == 0) OP_FAIL("fsvit_op_fill_f32: null argument or n = 0");
+  OP_RUN("fill_f32", launch_fill_f32(p, v, n, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_scale_copy(const float* in, float* out, size_t n, float scale, void* stream) {
+  if (!in || !out || n == 0) OP_FAIL("fsvit_op_scale_copy: null argument or n = 0");
+  OP_RUN("scale_copy", launch_scale_copy(in, out, n, scale, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_fold_prenorm(const float* W, const float* sa, const float* sb, void* wf, float* bf, int N, int C, int Kw, int dtype, void* stream) {
+  OP_DT("fsvit_op_fold_prenorm");
+  if (!W || !sa || !sb || !wf || !bf || N < 1 || C < 1 || Kw < C) OP_FAIL("fsvit_op_fold_prenorm: null argument or N %d, C %d, Kw %d (Kw >= C)", N, C, Kw);
+  OP_RUN("fold_prenorm", launch_fold_prenorm(W, sa, sb, wf, bf, N, C, Kw, dtype, (hipStream_t)stream));
+  return 0;
+}

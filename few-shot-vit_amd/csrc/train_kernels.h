@@ -29,6 +29,8 @@ int launch_im2col_t(const void* x, void* out, int B, int H, int W, int ld, int c
                     int dtype, hipStream_t s);
 int launch_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int dtype, hipStream_t s);
 int bn_reduce_blocks(int M);
+// CALLERS: C / V channel lanes (V = 4, bf16 8 where C % 8 == 0) beyond 256 must be a multiple of 256 - the kernel's block barrier sits inside its per-pass
+// channel loop, a partial last pass would leave threads behind it.  Neither this launcher nor launch_colsum checks that (the fsvit_op_* entries do).
 int launch_bn_reduce(const void* a, const void* z, const float* mean, const float* invstd, float* partial, int M, int C, int bwd, int dtype, hipStream_t s,
                      const void* add_a = nullptr, const void* add_b = nullptr, const float* add_scale = nullptr, int rows_per_img = 0,
                      const float* act_sa = nullptr, const float* act_sb = nullptr);

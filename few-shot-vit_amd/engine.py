@@ -966,3 +966,246 @@ class ops:
                 _lib.check(lib.fsvit_proto_head(_ptr(feat_shot.contiguous().float()), _ptr(feat_query.contiguous().float()), E, way,
                                                 shot, Q, D, float(temp), m, _ptr(logits), _ptr(acc), _ptr(loss), _stream_ptr(dev)))
         return logits, acc, loss
+
+    # ---- operator entry points of the memory-bound training kernels (fsvit_op_*: tests, tools).  Maps are [M, C] / NHWC tensors in the storage
+    # dtype (fp32 or bf16), statistics / parameters fp32; outputs and the kernels' `partial` scratch are allocated here.
+    @staticmethod
+    def _op(x, name, *args):
+        lib = _lib.load()
+        with torch.cuda.device(x.device):
+            _lib.check(getattr(lib, 'fsvit_op_' + name)(*args, _stream_ptr(x.device)))
+
+    @staticmethod
+    def _scratch(n, dev):
+        return torch.empty(max(int(n), 1), dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def bn_train_forward(z, gamma, beta, running_mean=None, running_var=None, eps=1e-5, momentum=0.1, frozen=False, add_a=None, add_b=None,
+                         add_scale=None, rows_per_img=0, res=None, act=_lib.ACT_NONE, apply=True):
+        """z [M,C] (overwritten with add_a + scale * add_b when add_b is given) -> (y or None, mean, invstd, sa, sb); running stats updated in place."""
+        _require_cuda(z, gamma, beta, running_mean, running_var, add_a, add_b, add_scale, res)
+        M, Cc = z.shape
+        stats = torch.empty(4, Cc, dtype=torch.float32, device=z.device)
+        partial = ops._scratch(_lib.load().fsvit_op_bn_reduce_blocks(M) * 2 * Cc, z.device)
+        y = torch.empty_like(z) if apply else None
+        ops._op(z, 'bn_train_forward', _ptr(z), M, Cc, ops._dt(z), _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), float(eps), float(momentum),
+                int(frozen), _ptr(add_a), _ptr(add_b), _ptr(add_scale), int(rows_per_img), _ptr(res), int(act), _ptr(y), _ptr(stats), _ptr(partial))
+        return y, stats[0], stats[1], stats[2], stats[3]
+
+    @staticmethod
+    def bn_train_backward(dy, z, mean, invstd, gamma, frozen=False, act_sa=None, act_sb=None, acc=None, scale2=None, out2=None, rows_per_img=0, dz=None):
+        """-> (dz, dgamma, dbeta, coef [3,C]); dz may be `acc`, out2 may be `dy` (both written in place when passed)."""
+        _require_cuda(dy, z, mean, invstd, gamma, act_sa, act_sb, acc, scale2, out2, dz)
+        M, Cc = z.shape
+        dz = torch.empty_like(z) if dz is None else dz
+        dgamma, dbeta = ops._scratch(Cc, z.device), ops._scratch(Cc, z.device)
+        coef = torch.empty(3, Cc, dtype=torch.float32, device=z.device)
+        partial = ops._scratch(_lib.load().fsvit_op_bn_reduce_blocks(M) * 2 * Cc, z.device)
+        ops._op(z, 'bn_train_backward', _ptr(dy), _ptr(z), _ptr(mean), _ptr(invstd), _ptr(gamma), M, Cc, ops._dt(z), int(frozen), _ptr(act_sa), _ptr(act_sb),
+                _ptr(acc), _ptr(scale2), _ptr(out2), int(rows_per_img), _ptr(dz), _ptr(dgamma), _ptr(dbeta), _ptr(coef), _ptr(partial))
+        return dz, dgamma, dbeta, coef
+
+    @staticmethod
+    def bn_act_bwd(dout, z, sa, sb, res=None):
+        _require_cuda(dout, z, sa, sb, res)
+        g = torch.empty_like(z)
+        ops._op(z, 'bn_act_bwd', _ptr(dout), _ptr(z), _ptr(sa), _ptr(sb), _ptr(res), _ptr(g), z.shape[0], z.shape[1], ops._dt(z))
+        return g
+
+    @staticmethod
+    def stem_tail_train_forward(z, sa, sb, res=None, rsa=None, rsb=None, pos=None):
+        """z / res [B,2OH,2OW,C] -> (out [B,OH,OW,C], arg uint8 [B,OH,OW,C]); pos [OH*OW, C] fp32."""
+        _require_cuda(z, sa, sb, res, rsa, rsb, pos)
+        B, H, W, Cc = z.shape
+        out = torch.empty(B, H // 2, W // 2, Cc, dtype=z.dtype, device=z.device)
+        arg = torch.empty(B, H // 2, W // 2, Cc, dtype=torch.uint8, device=z.device)
+        ops._op(z, 'stem_tail_train_forward', _ptr(z), _ptr(sa), _ptr(sb), _ptr(res), _ptr(rsa), _ptr(rsb), _ptr(pos), _ptr(out), _ptr(arg), B, H // 2, W // 2, Cc,
+                ops._dt(z))
+        return out, arg
+
+    @staticmethod
+    def stem_tail_train_backward(dout, arg, z3, zd, mean3, invstd3, meand, invstdd, gamma3, gammad, frozen=False):
+        """-> (dz3, dzd, dgamma3, dbeta3, dgammad, dbetad)"""
+        _require_cuda(dout, arg, z3, zd, mean3, invstd3, meand, invstdd, gamma3, gammad)
+        B, OH, OW, Cc = dout.shape
+        dev = z3.device
+        nb = _lib.load().fsvit_op_pool_bn_bwd_blocks(B, OH, OW, Cc, ops._dt(z3))
+        stats3, statsd = torch.stack([mean3, invstd3]).contiguous(), torch.stack([meand, invstdd]).contiguous()
+        dz3, dzd = torch.empty_like(z3), torch.empty_like(zd)
+        pg = [ops._scratch(Cc, dev) for _ in range(4)]
+        coef, partial = ops._scratch(6 * Cc, dev), ops._scratch(nb * 4 * Cc, dev)
+        ops._op(z3, 'stem_tail_train_backward', _ptr(dout), _ptr(arg), _ptr(z3), _ptr(zd), _ptr(stats3), _ptr(statsd), _ptr(gamma3), _ptr(gammad), _ptr(dz3), _ptr(dzd),
+                _ptr(pg[0]), _ptr(pg[1]), _ptr(pg[2]), _ptr(pg[3]), _ptr(coef), _ptr(partial), B, OH, OW, Cc, ops._dt(z3), int(frozen))
+        return (dz3, dzd) + tuple(pg)
+
+    @staticmethod
+    def pool_act_bwd(dout, arg):
+        _require_cuda(dout, arg)
+        B, OH, OW, Cc = dout.shape
+        g = torch.empty(B, 2 * OH, 2 * OW, Cc, dtype=dout.dtype, device=dout.device)
+        ops._op(dout, 'pool_act_bwd', _ptr(dout), _ptr(arg), _ptr(g), B, OH, OW, Cc, ops._dt(dout))
+        return g
+
+    @staticmethod
+    def maxpool2_idx(x, pos=None):
+        _require_cuda(x, pos)
+        B, H, W, Cc = x.shape
+        out = torch.empty(B, H // 2, W // 2, Cc, dtype=x.dtype, device=x.device)
+        arg = torch.empty(B, H // 2, W // 2, Cc, dtype=torch.uint8, device=x.device)
+        ops._op(x, 'maxpool2_idx', _ptr(x), _ptr(pos), _ptr(out), _ptr(arg), B, H // 2, W // 2, Cc, ops._dt(x))
+        return out, arg
+
+    @staticmethod
+    def maxpool2_bwd(dout, arg):
+        _require_cuda(dout, arg)
+        B, OH, OW, Cc = dout.shape
+        din = torch.empty(B, 2 * OH, 2 * OW, Cc, dtype=dout.dtype, device=dout.device)
+        ops._op(dout, 'maxpool2_bwd', _ptr(dout), _ptr(arg), _ptr(din), B, OH, OW, Cc, ops._dt(dout))
+        return din
+
+    @staticmethod
+    def ln_train_forward(x, gamma, beta, eps=1e-6):
+        """x [M,D] -> (y, mean [M], rstd [M])"""
+        _require_cuda(x, gamma, beta)
+        M, D = x.shape
+        y = torch.empty_like(x)
+        mean, rstd = ops._scratch(M, x.device), ops._scratch(M, x.device)
+        ops._op(x, 'ln_train_forward', _ptr(x), _ptr(gamma), _ptr(beta), _ptr(y), _ptr(mean), _ptr(rstd), M, D, float(eps), ops._dt(x))
+        return y, mean, rstd
+
+    @staticmethod
+    def ln_train_backward(dy, x, mean, rstd, gamma, add=None, dx=None, param_grads=True):
+        """-> (dx, dgamma, dbeta) (the last two None without param_grads); dx may be `add`."""
+        _require_cuda(dy, x, mean, rstd, gamma, add, dx)
+        M, D = x.shape
+        dx = torch.empty_like(x) if dx is None else dx
+        dgamma = ops._scratch(D, x.device) if param_grads else None
+        dbeta = ops._scratch(D, x.device) if param_grads else None
+        partial = ops._scratch(_lib.load().fsvit_op_ln_bwd_blocks(M) * 2 * D, x.device)
+        ops._op(x, 'ln_train_backward', _ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(add), _ptr(dx), _ptr(partial), _ptr(dgamma), _ptr(dbeta), M, D,
+                ops._dt(x))
+        return dx, dgamma, dbeta
+
+    @staticmethod
+    def vit_assemble(zpe, cls, pos, B, S):
+        """zpe [B*(S-1), D], cls [D], pos [S, D] -> tokens [B, S, D]"""
+        _require_cuda(zpe, cls, pos)
+        D = pos.shape[-1]
+        tokens = torch.empty(B, S, D, dtype=zpe.dtype, device=zpe.device)
+        ops._op(zpe, 'vit_assemble', _ptr(zpe), _ptr(cls), _ptr(pos), _ptr(tokens), B, S, D, ops._dt(zpe))
+        return tokens
+
+    @staticmethod
+    def vit_patch_rows(dtok):
+        _require_cuda(dtok)
+        B, S, D = dtok.shape
+        dzpe = torch.empty(B * (S - 1), D, dtype=dtok.dtype, device=dtok.device)
+        ops._op(dtok, 'vit_patch_rows', _ptr(dtok), _ptr(dzpe), B, S, D, ops._dt(dtok))
+        return dzpe
+
+    @staticmethod
+    def vit_cls_ln_forward(tokens, gamma, beta, eps=1e-6):
+        _require_cuda(tokens, gamma, beta)
+        B, S, D = tokens.shape
+        feat = torch.empty(B, D, dtype=torch.float32, device=tokens.device)
+        mean, rstd = ops._scratch(B, tokens.device), ops._scratch(B, tokens.device)
+        ops._op(tokens, 'vit_cls_ln_forward', _ptr(tokens), _ptr(gamma), _ptr(beta), _ptr(feat), _ptr(mean), _ptr(rstd), B, S, D, float(eps), ops._dt(tokens))
+        return feat, mean, rstd
+
+    @staticmethod
+    def vit_cls_ln_backward(dfeat, tokens, mean, rstd, gamma):
+        _require_cuda(dfeat, tokens, mean, rstd, gamma)
+        B, S, D = tokens.shape
+        dtok = torch.empty_like(tokens)
+        dgamma, dbeta, partial = ops._scratch(D, tokens.device), ops._scratch(D, tokens.device), ops._scratch(B * 2 * D, tokens.device)
+        ops._op(tokens, 'vit_cls_ln_backward', _ptr(dfeat), _ptr(tokens), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dtok), _ptr(partial), _ptr(dgamma), _ptr(dbeta),
+                B, S, D, ops._dt(tokens))
+        return dtok, dgamma, dbeta
+
+    @staticmethod
+    def gelu_train(z, dh=None):
+        """gelu(z), or with dh its backward dh * gelu'(z)"""
+        _require_cuda(z, dh)
+        out = torch.empty_like(z)
+        ops._op(z, 'gelu', _ptr(dh), _ptr(z), _ptr(out), z.numel(), ops._dt(z))
+        return out
+
+    @staticmethod
+    def add_scaled(a, br, scale=None, per_img=0):
+        _require_cuda(a, br, scale)
+        out = torch.empty_like(br)
+        ops._op(br, 'add_scaled', _ptr(a), _ptr(br), _ptr(scale), _ptr(out), br.numel(), int(per_img), ops._dt(br))
+        return out
+
+    @staticmethod
+    def avgpool_bwd(dfeat, HW, dtype):
+        _require_cuda(dfeat)
+        B, Cc = dfeat.shape
+        dx = torch.empty(B, HW, Cc, dtype=dtype, device=dfeat.device)
+        ops._op(dfeat, 'avgpool_bwd', _ptr(dfeat), _ptr(dx), B, HW, Cc, ops._dt(dx))
+        return dx
+
+    @staticmethod
+    def batch_sum(g):
+        """g [B, n] -> [n] fp32"""
+        _require_cuda(g)
+        out = torch.empty(g.shape[1], dtype=torch.float32, device=g.device)
+        ops._op(g, 'batch_sum', _ptr(g), _ptr(out), g.shape[0], g.shape[1], ops._dt(g))
+        return out
+
+    @staticmethod
+    def bcast_add(x, p):
+        _require_cuda(x, p)
+        y = torch.empty_like(x)
+        ops._op(x, 'bcast_add', _ptr(x), _ptr(p), _ptr(y), x.shape[0], x[0].numel(), ops._dt(x))
+        return y
+
+    @staticmethod
+    def colsum(a):
+        _require_cuda(a)
+        M, Cc = a.shape
+        out = torch.empty(Cc, dtype=torch.float32, device=a.device)
+        partial = ops._scratch(_lib.load().fsvit_op_bn_reduce_blocks(M) * 2 * Cc, a.device)
+        ops._op(a, 'colsum', _ptr(a), _ptr(partial), _ptr(out), M, Cc, ops._dt(a))
+        return out
+
+    @staticmethod
+    def unpatch2(g, B, OH, OW):
+        """g [B*OH*OW, 4*C] -> dx [B, 2*OH, 2*OW, C]"""
+        _require_cuda(g)
+        Cc = g.shape[1] // 4
+        dx = torch.empty(B, 2 * OH, 2 * OW, Cc, dtype=g.dtype, device=g.device)
+        ops._op(g, 'unpatch2', _ptr(g), _ptr(dx), B, OH, OW, Cc, ops._dt(g))
+        return dx
+
+    @staticmethod
+    def droppath_scales(masks, keep):
+        """masks [ncalls, n_img] fp32, keep: ncalls probabilities -> scales [ncalls, n_img]"""
+        _require_cuda(masks)
+        scales = torch.empty_like(masks)
+        k = (C.c_float * len(keep))(*[float(v) for v in keep])
+        ops._op(masks, 'droppath_scales', _ptr(masks), _ptr(scales), masks.shape[0], masks.shape[1], k)
+        return scales
+
+    @staticmethod
+    def fold_prenorm(W, sa, sb, Kw, dtype):
+        """W [N,C] fp32 -> (wf [N,Kw] in `dtype`, bf [N] fp32)"""
+        _require_cuda(W, sa, sb)
+        N, Cc = W.shape
+        wf = torch.empty(N, Kw, dtype=dtype, device=W.device)
+        bf = torch.empty(N, dtype=torch.float32, device=W.device)
+        ops._op(W, 'fold_prenorm', _ptr(W), _ptr(sa), _ptr(sb), _ptr(wf), _ptr(bf), N, Cc, Kw, ops._dt(wf))
+        return wf, bf
+
+    @staticmethod
+    def fill_f32(n, v, device):
+        out = torch.empty(n, dtype=torch.float32, device=device)
+        ops._op(out, 'fill_f32', _ptr(out), float(v), n)
+        return out
+
+    @staticmethod
+    def scale_copy(x, scale):
+        _require_cuda(x)
+        out = torch.empty_like(x)
+        ops._op(x, 'scale_copy', _ptr(x), _ptr(out), x.numel(), float(scale))
+        return out

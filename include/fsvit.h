@@ -417,6 +417,80 @@ int fsvit_conv1x1_wgrad(const void* x_dev, const void* dz_dev, float* dw_dev, in
 int fsvit_attention_backward(const void* qkv_dev, const void* dctx_dev, void* dqkv_dev, int B, int S, int heads, int hd, int hdp,
                              float scale, int dtype, void* stream);
 
+/* ================================================================ operator entry points (tests, tools)
+ * The memory-bound kernels of the training step (train_kernels.hip), one entry per engine-level operation, so that each can be held against a
+ * plain reference on its own (tests/test_gpu_train_ops.py).  No engine path calls them.  dtype = storage type of the maps: FSVIT_F32 or FSVIT_BF16
+ * (the training kernels are built for these two; anything else is FSVIT_ERR_ARG).  Statistics, parameters and parameter gradients are fp32.  A shape a
+ * kernel does not cover is rejected with FSVIT_ERR_ARG and a message; nothing is launched on it.  Maps are row-major [M][C] / NHWC.
+ *
+ * Scratch sizes (floats): `partial` of the BatchNorm / colsum entries: fsvit_op_bn_reduce_blocks(M) * 2 * C; of ln_train_backward:
+ * fsvit_op_ln_bwd_blocks(M) * 2 * D; of stem_tail_train_backward: fsvit_op_pool_bn_bwd_blocks(..) * 4 * C (0 blocks: that C has no fused form). */
+int fsvit_op_bn_reduce_blocks(int M);
+int fsvit_op_ln_bwd_blocks(int M);
+int fsvit_op_pool_bn_bwd_blocks(int B, int OH, int OW, int C, int dtype);
+
+/* Train-mode BatchNorm over the rows of z [M][C]: bn_reduce -> bn_fwd_finalize -> bn_apply.  stats [4][C] = mean | invstd | sa | sb (y = sa z + sb).
+ * add_b != NULL: the residual add in front rides in the reduce pass - z := T(add_a + add_scale[row / rows_per_img] * add_b) is STORED and the
+ * statistics are taken of the stored values (add_scale NULL: 1; with add_scale M must be images * rows_per_img).  running_mean / running_var (may both
+ * be NULL) are updated with `momentum` and the unbiased variance.  frozen: the running statistics normalise, nothing is updated, the add runs on
+ * its own.  y may be NULL (statistics only); res (may be NULL) is added before `act` (FSVIT_ACT_NONE | FSVIT_ACT_LRELU, slope 0.1).  M >= 2 unless frozen.
+ * C: a multiple of 4; beyond 256 channel lanes (4 channels, bf16: 8 where C % 8 == 0) a multiple of 256 lanes. */
+int fsvit_op_bn_train_forward(void* z_dev, int M, int C, int dtype, const float* gamma, const float* beta, float* running_mean, float* running_var, float eps,
+                              float momentum, int frozen, const void* add_a, const void* add_b, const float* add_scale, int rows_per_img, const void* res,
+                              int act, void* y_dev, float* stats, float* partial, void* stream);
+/* Its backward: bn_reduce (backward form) -> bn_bwd_finalize -> bn_bwd_apply.  dz = ca dy + cb + cc xhat (+ acc; dz may be acc), coef [3][C] = ca | cb | cc.
+ * act_sa / act_sb != NULL: dy is the gradient BEHIND a LeakyReLU(0.1) that followed this BatchNorm (y = act_sa z + act_sb), the slope is applied on the
+ * fly.  out2 != NULL (may be dy): out2 = scale2[row / rows_per_img] * T(dz) (scale2 NULL: 1). */
+int fsvit_op_bn_train_backward(const void* dy, const void* z, const float* mean, const float* invstd, const float* gamma, int M, int C, int dtype, int frozen,
+                               const float* act_sa, const float* act_sb, const void* acc, const float* scale2, void* out2, int rows_per_img, void* dz,
+                               float* dgamma, float* dbeta, float* coef, float* partial, void* stream);
+/* g = dout * lrelu'(sa z + sb (+ res)) */
+int fsvit_op_bn_act_bwd(const void* dout, const void* z, const float* sa, const float* sb, const void* res, void* g, int M, int C, int dtype, void* stream);
+
+/* Stem tail (bn_pool_fwd): out [B,OH,OW,C] = MaxPool2d(2)(LeakyReLU(sa z + sb + r)) + pos, z / res [B,2OH,2OW,C]; r = res, or with rsa / rsb the
+ * identity path's BatchNorm T(rsa res + rsb); arg = window position of the maximum (first of equals) | 4 if it is positive.  C % 8 == 0. */
+int fsvit_op_stem_tail_train_forward(const void* z, const float* sa, const float* sb, const void* res, const float* rsa, const float* rsb, const float* pos,
+                                     void* out, unsigned char* arg, int B, int OH, int OW, int C, int dtype, void* stream);
+/* Both BatchNorm backwards behind that tail straight from the pooled gradient (pool_bn_bwd_reduce -> 2 x bn_bwd_finalize -> pool_bn_bwd_apply).
+ * stats3 / statsd [2][C] = mean | invstd; coef [6][C] scratch.  Only where the channel lanes divide 256 (fsvit_op_pool_bn_bwd_blocks() != 0); other C:
+ * FSVIT_ERR_ARG - the unfused chain pool_act_bwd + two bn_train_backward is the engine's path there. */
+int fsvit_op_stem_tail_train_backward(const void* dout, const unsigned char* arg, const void* z3, const void* zd, const float* stats3, const float* statsd,
+                                      const float* gamma3, const float* gammad, void* dz3, void* dzd, float* dgamma3, float* dbeta3, float* dgammad,
+                                      float* dbetad, float* coef, float* partial, int B, int OH, int OW, int C, int dtype, int frozen, void* stream);
+int fsvit_op_pool_act_bwd(const void* dout, const unsigned char* arg, void* g, int B, int OH, int OW, int C, int dtype, void* stream);
+int fsvit_op_maxpool2_idx(const void* in, const float* pos, void* out, unsigned char* arg, int B, int OH, int OW, int C, int dtype, void* stream);
+int fsvit_op_maxpool2_bwd(const void* dout, const unsigned char* arg, void* din, int B, int OH, int OW, int C, int dtype, void* stream);
+
+/* LayerNorm with kept row statistics and its backward (dx = LN backward of dy (+ add; add may be dx); dgamma / dbeta may be NULL).  D % 4 == 0, D <= 2048. */
+int fsvit_op_ln_train_forward(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps, int dtype,
+                              void* stream);
+int fsvit_op_ln_train_backward(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, const void* add, void* dx,
+                               float* partial, float* dgamma, float* dbeta, int M, int D, int dtype, void* stream);
+/* tokens[b][0] = cls + pos[0], tokens[b][1 + i] = zpe[b (S - 1) + i] + pos[1 + i]; dzpe = the patch rows of dtok; the final norm on the cls row (fp32
+ * feat) and its backward (dtok is zeroed, its cls rows written; partial B * 2 * D floats) */
+int fsvit_op_vit_assemble(const void* zpe, const float* cls, const float* pos, void* tokens, int B, int S, int D, int dtype, void* stream);
+int fsvit_op_vit_patch_rows(const void* dtok, void* dzpe, int B, int S, int D, int dtype, void* stream);
+int fsvit_op_vit_cls_ln_forward(const void* tokens, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int B, int S, int D, float eps,
+                                int dtype, void* stream);
+int fsvit_op_vit_cls_ln_backward(const float* dfeat, const void* tokens, const float* mean, const float* rstd, const float* gamma, void* dtok, float* partial,
+                                 float* dgamma, float* dbeta, int B, int S, int D, int dtype, void* stream);
+
+/* Elementwise / small reductions.  gelu: dh NULL -> out = gelu(z), else out = dh * gelu'(z) (erf form); add_scaled: out = a + scale[i / per_img] * br
+ * (a, scale may be NULL); avgpool_bwd: dx[b][hw][c] = dfeat[b][c] / HW; batch_sum: out[i] = sum_b g[b][i]; bcast_add: y[b][i] = x[b][i] + p[i];
+ * colsum: out[c] = sum_m a[m][c]; unpatch2: g [B*OH*OW][4C] -> dx [B,2OH,2OW,C]; droppath_scales: scales[k][b] = masks[k][b] / keep_host[k];
+ * fold_prenorm: wf[n][c] = T(W[n][c] sa[c]) ([N][Kw], zero padded), bf[n] = sum_c W[n][c] sb[c].  n, per_img: multiples of 4. */
+int fsvit_op_gelu(const void* dh, const void* z, void* out, size_t n, int dtype, void* stream);
+int fsvit_op_add_scaled(const void* a, const void* br, const float* scale, void* out, size_t n, size_t per_img, int dtype, void* stream);
+int fsvit_op_avgpool_bwd(const float* dfeat, void* dx, int B, int HW, int C, int dtype, void* stream);
+int fsvit_op_batch_sum(const void* g, float* out, int B, size_t per_img, int dtype, void* stream);
+int fsvit_op_bcast_add(const void* x, const float* p, void* y, int B, size_t per_img, int dtype, void* stream);
+int fsvit_op_colsum(const void* a, float* partial, float* out, int M, int C, int dtype, void* stream);
+int fsvit_op_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int dtype, void* stream);
+int fsvit_op_droppath_scales(const float* masks, float* scales, int ncalls, int n_img, const float* keep_host, void* stream);
+int fsvit_op_fill_f32(float* p, float v, size_t n, void* stream);                                   /* p[i] = v */
+int fsvit_op_scale_copy(const float* in, float* out, size_t n, float scale, void* stream);          /* out[i] = in[i] * scale */
+int fsvit_op_fold_prenorm(const float* W, const float* sa, const float* sb, void* wf, float* bf, int N, int C, int Kw, int dtype, void* stream);
+
 /* ---------------------------------------------------------------- episode sampler (host only, no GPU)
  * The draws of `CategoriesSampler.__iter__` (test_phase/datasets/samplers.py:19-35) replayed natively on the legacy numpy generator state: per episode
  * `np.random.choice(n_cat, n_cls, replace=False)`, then per chosen class `np.random.choice(catlocs[c], n_per, replace=False)`.  mt_key [624] / mt_pos =
