@@ -507,8 +507,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
 }
 
 bool conv3x3_halo_eligible(const ConvGemmParams& p, int dtype) {
-  constexpr bool off = false;
-  if (off || dtype != 1) return false;
+  if (dtype != 1) return false;
   if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.groups != 1) return false;
   if (p.w_cpad) {     // the LV-ViT stem (96 channels) on the 128-channel schedule: weights as the zero-padded 128-channel image
     if (p.w_cpad != 128 || p.Cin != 96 || p.N != 96 || p.x_cstride != 96 || p.y_cstride != 96 || p.K != 9 * 96) return false;

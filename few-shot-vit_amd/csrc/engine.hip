@@ -146,6 +146,12 @@ enum { KIND_VISFORMER = 1, KIND_VIT = 2, KIND_LVVIT = 3 };
 struct EngineBase {
   int kind = 0;
   int dtype = 0, es = 4;
+  int img_size = 0, out_dim = 0;       // input side; feature width (set by the build function)
+  // what differs between the handle types behind the shared create / workspace_bytes / forward (encoder_create sets them): the workspace a chunk of
+  // Bc images needs, the forward of one chunk, and the image-size message (printf format: got h, w, model h, w)
+  size_t (*plan_bytes)(const EngineBase* h, size_t Bc) = nullptr;
+  int (*chunk)(EngineBase* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) = nullptr;
+  const char* size_fmt = nullptr;
   std::map<std::string, Tap> taps;
   std::vector<void*> allocs;
   bool profiling = false;
@@ -159,7 +165,7 @@ struct fsvit_visformer : EngineBase {
   int H0 = 0, H1 = 0, H2 = 0, H3 = 0;
   int hid1 = 0, hid2 = 0, hid3 = 0;
   int hd2 = 0, hdp2 = 0, hd3 = 0, hdp3 = 0;
-  Layer conv1, down, conv2, conv3, conv3f, pe2, pe3;   // conv3f: conv3 + downsample folded in as a tail K slice
+  Layer conv1, conv2, conv3f, pe2, pe3;   // conv3f: conv3 + bn3 with the downsample conv + bn_d folded in as a tail K slice
   void* pe_img[2] = {nullptr, nullptr};                // mlp_rows.hip: fragment-major image of patch_embed2 / 3 for the row-wise kernel (null: conv_gemm)
   float *pos1 = nullptr, *pos2 = nullptr, *pos3 = nullptr;
   std::vector<Block1> s1;
@@ -227,6 +233,18 @@ int upload(EngineBase* h, const std::vector<float>& src, bool as_storage, void**
     HIP_TRY(hipMemcpy(d, src.data(), src.size() * 4, hipMemcpyHostToDevice));
   }
   *out = d;
+  return 0;
+}
+
+// A device buffer of `bytes` owned by the handle, filled by one pack launch `launch(buffer)` on the null stream (complete on return).
+template <typename F>
+int packed_image(EngineBase* h, size_t bytes, void** out, F&& launch) {
+  void* img = nullptr;
+  HIP_TRY(hipMalloc(&img, bytes));
+  h->allocs.push_back(img);
+  RC_TRY(launch(img));
+  HIP_TRY(hipDeviceSynchronize());
+  *out = img;
   return 0;
 }
 
@@ -358,19 +376,17 @@ int build(fsvit_visformer* h, const SD& sd) {
   const double eps = cf.bn_eps;
   const int epc = 16 / h->es;
   const int D = cf.embed_dim;
-  h->C0 = cf.init_channels; h->C1 = D / 2; h->C2 = D; h->C3 = D * 2;
+  h->C0 = cf.init_channels; h->C1 = D / 2; h->C2 = D; h->C3 = h->out_dim = D * 2;
   if (cf.img_size % 16 != 0) return fail(FSVIT_ERR_ARG, "img_size %d must be a multiple of 16", cf.img_size);
   h->H0 = cf.img_size / 2; h->H1 = cf.img_size / 4; h->H2 = cf.img_size / 8; h->H3 = cf.img_size / 16;
   if (cf.group < 2) return fail(FSVIT_ERR_ARG, "group < 2 ('net' setting, visformer.py:137-138) is not supported");
   h->hid1 = h->C1 * 2;
   h->hid2 = (int)(h->C2 * cf.mlp_ratio);
   h->hid3 = (int)(h->C3 * cf.mlp_ratio);
-  const int kch = 64 / h->es;                                  // head dim padded to the 64-byte MFMA K chunk
   h->hd2 = (int)std::lround((double)(h->C2 / cf.num_heads));  // round(dim // heads * 1.0), visformer.py:172
   h->hd3 = (int)std::lround((double)(h->C3 / cf.num_heads));
   h->hdp2 = K(attention_padded_head_dim)(h->hd2, h->H2 * h->H2, kd(kdt));
   h->hdp3 = K(attention_padded_head_dim)(h->hd3, h->H3 * h->H3, kd(kdt));
-  (void)kch;
   const int Cg = h->hid1 / cf.group;
   if (h->C0 % epc || h->C1 % epc || h->hid1 % cf.group || Cg % epc)
     return fail(FSVIT_ERR_ARG, "channel counts must be multiples of %d for 16-byte K chunks", epc);
@@ -401,7 +417,7 @@ int build(fsvit_visformer* h, const SD& sd) {
     Affine b1 = bn_affine(sd, "stem.bn1", h->C0, eps), b2 = bn_affine(sd, "stem.bn2", h->C1, eps);
     Affine b3 = bn_affine(sd, "stem.bn3", h->C1, eps), bd = bn_affine(sd, "stem.downsample.1", h->C1, eps);
     if (!w1 || !wd || !w2 || !w3 || !b1.ok || !b2.ok || !b3.ok || !bd.ok) return FSVIT_ERR_KEY;
-    // conv1 / downsample consume the 32-wide im2col rows: K columns 0..26 = (ky,kx,c), 27..31 = 0
+    // conv1 (and the downsample taps inside conv3f) consume the 32-wide im2col rows: K columns 0..26 = (ky,kx,c), 27..31 = 0
     std::vector<int> cm(27);
     for (int k = 0; k < 27; ++k) cm[k] = k;
     // operand means: the normalised image 0 (no correction for conv1 / downsample); conv2 / conv3 read LeakyReLU(BN(z)), z_c ~ N(beta_c, gamma_c^2)
@@ -414,9 +430,7 @@ int build(fsvit_visformer* h, const SD& sd) {
     }
     const std::vector<double> tf0 = tap_fraction(h->H0, 1, 3, 1);
     RC_TRY(pack_layer(h, &h->conv1, w1, h->C0, 3, 3, 3, 1, &b1.s, nullptr, b1.t, true, nullptr, 0, &cm, 32));
-    RC_TRY(pack_layer(h, &h->down, wd, h->C1, 3, 3, 3, 1, &bd.s, nullptr, bd.t, true, nullptr, 0, &cm, 32));
     RC_TRY(pack_layer(h, &h->conv2, w2, h->C1, h->C0, 3, 3, 1, &b2.s, nullptr, b2.t, true, nullptr, 0, nullptr, 0, &wr, &m2, tf0.data()));
-    RC_TRY(pack_layer(h, &h->conv3, w3, h->C1, h->C1, 3, 3, 1, &b3.s, nullptr, b3.t, true, nullptr, 0, nullptr, 0, &wr, &m3, tf0.data()));
     {  // conv3f rows = [ bn3-scaled conv3 (K = 9*C1, padded to the K slice) | one tail slice: bn_d-scaled downsample taps ]
       const int bke = 128 / h->es, K = 9 * h->C1, Kmain = round_up(K, bke), Kw = Kmain + bke;
       std::vector<float> pk((size_t)h->C1 * Kw, 0.0f), pb(h->C1);
@@ -490,10 +504,7 @@ int build(fsvit_visformer* h, const SD& sd) {
     RC_TRY(pack_layer(h, &h->s1[i].c3, w3, h->C1, h->hid1, 1, 1, 1, nullptr, nullptr, nob, false, nullptr, 0, nullptr, 0, &wr, &mh2, nullptr, false, &corr3));
     if (kd(kdt) == 1 && h->s1[i].c3.Kw == h->hid1) {
       const size_t n3 = (size_t)h->C1 * h->s1[i].c3.Kw;
-      HIP_TRY(hipMalloc(&h->s1[i].c3s, n3 * 2));
-      h->allocs.push_back(h->s1[i].c3s);
-      RC_TRY(K(launch_stage1_w4_prescale)(h->s1[i].c3.w, h->s1[i].c3s, (int)n3, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
+      RC_TRY(packed_image(h, n3 * 2, &h->s1[i].c3s, [&](void* img) { return K(launch_stage1_w4_prescale)(h->s1[i].c3.w, img, (int)n3, nullptr); }));
     }
     if (wr.on) {
       x_mean.assign(h->C1, 0.0);                  // E[x] behind this block = running mean + conv3 E[h2]: the next PatchEmbed's operand mean
@@ -533,14 +544,9 @@ int build(fsvit_visformer* h, const SD& sd) {
       }
     }
     const Layer& pe = s == 2 ? h->pe2 : h->pe3;
-    if (K(patch_embed_rows_supported)(kd(kdt), Ci, s == 2 ? h->H1 : h->H2, Co) && pe.Kw == 4 * Ci) {
-      void* img = nullptr;
-      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(4 * Ci, Co)));
-      h->allocs.push_back(img);
-      RC_TRY(K(launch_ln_gemm_pack)(pe.w, pe.Kw, img, 4 * Ci, Co, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      h->pe_img[s - 2] = img;
-    }
+    if (K(patch_embed_rows_supported)(kd(kdt), Ci, s == 2 ? h->H1 : h->H2, Co) && pe.Kw == 4 * Ci)
+      RC_TRY(packed_image(h, K(ln_gemm_rows_image_bytes)(4 * Ci, Co), &h->pe_img[s - 2],
+                          [&](void* img) { return K(launch_ln_gemm_pack)(pe.w, pe.Kw, img, 4 * Ci, Co, nullptr); }));
    }
     const int C = s == 2 ? h->C2 : h->C3, hid = s == 2 ? h->hid2 : h->hid3;
     const int hd = s == 2 ? h->hd2 : h->hd3, hdp = s == 2 ? h->hdp2 : h->hdp3;
@@ -598,39 +604,25 @@ int build(fsvit_visformer* h, const SD& sd) {
       }
       if (K(mlp_rows_supported)(kd(kdt), C, hid)) {                // fused row-wise Mlp: re-pack [proj,] fc1, fc2 as the MFMA fragment stream
         const int kc = K(mlp_rows_proj_supported)(C, hid, heads * hdp) ? heads * hdp : 0;
-        void *img = nullptr, *b1i = nullptr;
-        HIP_TRY(hipMalloc(&img, K(mlp_rows_image_bytes)(C, hid, kc)));
-        h->allocs.push_back(img);
-        HIP_TRY(hipMalloc(&b1i, (size_t)hid * 4));
-        h->allocs.push_back(b1i);
-        RC_TRY(K(launch_mlp_pack)(blocks[i].fc1.w, blocks[i].fc1.Kw, blocks[i].fc1.bias, blocks[i].fc2.w, blocks[i].fc2.Kw, blocks[i].proj.w, blocks[i].proj.Kw,
-                               kc, img, (float*)b1i, C, hid, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        blocks[i].mlp_img = img;
-        blocks[i].mlp_b1 = (float*)b1i;
-        blocks[i].mlp_kc = kc;
+        BlockA& b = blocks[i];
+        void* b1i = nullptr;
+        RC_TRY(packed_image(h, K(mlp_rows_image_bytes)(C, hid, kc), &b.mlp_img, [&](void* img) {
+          HIP_TRY(hipMalloc(&b1i, (size_t)hid * 4));
+          h->allocs.push_back(b1i);
+          return K(launch_mlp_pack)(b.fc1.w, b.fc1.Kw, b.fc1.bias, b.fc2.w, b.fc2.Kw, b.proj.w, b.proj.Kw, kc, img, (float*)b1i, C, hid, nullptr);
+        }));
+        b.mlp_b1 = (float*)b1i;
+        b.mlp_kc = kc;
       }
       if (K(qkv_attn_supported)(kd(kdt), C, heads, hdp, (s == 2 ? h->H2 : h->H3) * (s == 2 ? h->H2 : h->H3))) {   // fused qkv conv + attention: re-pack qkv as the MFMA fragment stream
-        void* img = nullptr;
-        HIP_TRY(hipMalloc(&img, K(qkv_attn_image_bytes)()));
-        h->allocs.push_back(img);
-        RC_TRY(K(launch_qkv_attn_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        blocks[i].qa_img = img;
+        RC_TRY(packed_image(h, K(qkv_attn_image_bytes)(), &blocks[i].qa_img,
+                            [&](void* img) { return K(launch_qkv_attn_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, nullptr); }));
       } else if (K(qkv_attn_rows_supported)(kd(kdt), C, heads, hdp, (s == 2 ? h->H2 : h->H3) * (s == 2 ? h->H2 : h->H3))) {   // stage 3, <= 32 tokens
-        void* img = nullptr;
-        HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp)));
-        h->allocs.push_back(img);
-        RC_TRY(K(launch_qkv_attn_rows_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, C, heads, hdp, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        blocks[i].qar_img = img;
+        RC_TRY(packed_image(h, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp), &blocks[i].qar_img,
+                            [&](void* img) { return K(launch_qkv_attn_rows_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, C, heads, hdp, nullptr); }));
       } else if (K(gemm_rows_supported)(kd(kdt), C, 3 * heads * hdp)) {      // stage 3: the qkv conv as a row-wise GEMM
-        void* img = nullptr;
-        HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp)));
-        h->allocs.push_back(img);
-        RC_TRY(K(launch_ln_gemm_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, C, 3 * heads * hdp, nullptr));
-        HIP_TRY(hipDeviceSynchronize());
-        blocks[i].qr_img = img;
+        RC_TRY(packed_image(h, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp), &blocks[i].qr_img,
+                            [&](void* img) { return K(launch_ln_gemm_pack)(blocks[i].qkv.w, blocks[i].qkv.Kw, img, C, 3 * heads * hdp, nullptr); }));
       }
     }
   }
@@ -648,7 +640,7 @@ int build(fsvit_visformer* h, const SD& sd) {
 
 // ---- workspace plan for a chunk of Bc images
 struct Plan {
-  size_t patches, c1, ident, c2, c3;     // stem scratch
+  size_t patches, c1, c2;                // stem scratch
   size_t ha, hb;                         // stage-1 hidden
   size_t qkv, ctx, hid;                  // stage-2/3 scratch
   size_t x1, x1b, x2, x3;                // residual streams (x1b: ping-pong partner for the fused stage-1 block)
@@ -671,9 +663,7 @@ Plan make_plan(const fsvit_visformer* h, size_t Bc) {
   // stem
   p.patches = take(Bc * P0 * 32 * es);
   p.c1 = take(Bc * P0 * h->C0 * es);
-  p.ident = take(Bc * P0 * h->C1 * es);
   p.c2 = take(Bc * P0 * h->C1 * es);
-  p.c3 = take(Bc * P0 * h->C1 * es);
   size_t hi = off;
   // stage 1 (reuses the stem scratch)
   off = scratch0;
@@ -756,21 +746,21 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
   const int kdt = h->dtype, dt = kd(kdt);
   const size_t es = h->es;
   const int heads = h->cfg.num_heads;
-  void *patches = ws + pl.patches, *c1 = ws + pl.c1, *ident = ws + pl.ident, *c2 = ws + pl.c2, *c3 = ws + pl.c3;
+  void *patches = ws + pl.patches, *c1 = ws + pl.c1, *c2 = ws + pl.c2;
   void *x1 = ws + pl.x1, *x1b = ws + pl.x1b, *x2 = ws + pl.x2, *x3 = ws + pl.x3, *ha = ws + pl.ha, *hb = ws + pl.hb;
   void *qkv = ws + pl.qkv, *ctx = ws + pl.ctx, *hid = ws + pl.hid;
   const int img = h->cfg.img_size;
 
-  // stem: conv1 / downsample as K=32 GEMMs over the im2col rows, conv2, conv3 (+identity, LeakyReLU), max-pool + pos1
+  // stem: conv1 over the im2col rows, conv2, conv3 + bn3 + (downsample conv + bn_d as a tail K slice over the im2col rows) + LeakyReLU + MaxPool2d(2) + pos_embed1
   h->prof_last = nullptr;
   if (!xsrc2) B1 = Bc;
-  constexpr bool stem_fused_on = true;
-  // Round 6: when the whole stem runs on its dedicated kernels (stem_conv1 -> conv3x3_halo -> conv3x3_halo + tail) the two intermediate maps c1 / c2 are
+  const bool conv1_fused = K(stem_conv1_supported)(dt, img, h->C0);      // im2col + conv1 + bn1 + LeakyReLU in one pass over the image
+  // When the whole stem runs on its dedicated kernels (stem_conv1 -> conv3x3_halo -> conv3x3_halo + tail) the two intermediate maps c1 / c2 are
   // stored row-chunk-planar (conv_gemm.h x_planar): the halo fetch of the consumer then reads row segments instead of 16 bytes of every 128-byte line
   ConvGemmParams p2 = conv_params(h->conv2, c1, c2, Bc, h->H0, h->H0, h->C0, h->C0, 3, 3, 1, 1, h->C1, ACT_LRELU, nullptr, 0, nullptr);
   ConvGemmParams p3 = conv_params(h->conv3f, c2, x1, Bc, h->H0, h->H0, h->C1, h->C1, 3, 3, 1, 1, h->C1, ACT_LRELU, nullptr, 0, h->pos1);
   p3.x2 = patches; p3.x2_cstride = 32; p3.K2 = 32; p3.pool2 = 1;
-  const bool planar = stem_fused_on && K(stem_conv1_supported)(dt, img, h->C0) && K(conv_gemm_route)(p2, kg(kdt)) == 0 && K(conv_gemm_route)(p3, kg(kdt)) == 0;
+  const bool planar = conv1_fused && K(conv_gemm_route)(p2, kg(kdt)) == 0 && K(conv_gemm_route)(p3, kg(kdt)) == 0;
   p2.x_planar = p2.y_planar = p3.x_planar = planar ? 1 : 0;
   if (planar) {
     // The dedicated stem runs in SLICES of the chunk (stem_conv1 -> conv2 -> conv3 + tail per slice of STEM_SLICE images): the two halo convs take
@@ -778,7 +768,7 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
     // latency, and a slice's maps are produced and consumed within a few ms), while every later kernel wants the whole chunk.
     const int S = stem_slice_images();
     const size_t s_pat = (size_t)h->H0 * h->H0 * 32 * es, s_c1 = (size_t)h->H0 * h->H0 * h->C0 * es, s_c2 = (size_t)h->H0 * h->H0 * h->C1 * es,
-                 s_x1 = (size_t)h->H1 * h->H1 * h->C1 * es, s_img = (size_t)3 * img * img * sizeof(float);
+                 s_x1 = (size_t)h->H1 * h->H1 * h->C1 * es;
     const double fl1 = 2.0 * 27.0 * h->C0 * h->H0 * h->H0;
     for (int g0 = 0; g0 < Bc; g0 += S) {
       const int g1 = g0 + S < Bc ? g0 + S : Bc;
@@ -786,7 +776,6 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
         const int a = part == 0 ? g0 : (g0 > B1 ? g0 : B1), b = part == 0 ? (g1 < B1 ? g1 : B1) : g1;
         if (a >= b) continue;
         const float* src = part == 0 ? x + (size_t)a * 3 * img * img : xsrc2 + (size_t)(a - B1) * 3 * img * img;
-        (void)s_img;
         RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * (b - a), [&]() {
           return K(launch_stem_conv1)(src, (unsigned char*)patches + a * s_pat, (unsigned char*)c1 + a * s_c1, h->conv1.w, h->conv1.Kw, h->conv1.bias, b - a, st, 1); }));
       }
@@ -797,15 +786,15 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
       RC_TRY(run_gemm(h, st, "stem.conv2", h->conv2, q2, h->C1, 9.0 * h->C0));
       RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, q3, h->C1, 9.0 * h->C1 + 27.0));
     }
-  } else {
-  if (stem_fused_on && K(stem_conv1_supported)(dt, img, h->C0)) {      // im2col + conv1 + bn1 + LeakyReLU in one pass over the image
+  } else {      // the general route: other image sizes, geometries and numerics modes
+    if (conv1_fused) {
       const double fl1 = 2.0 * 27.0 * h->C0 * h->H0 * h->H0;
       RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * B1, [&]() {
-        return K(launch_stem_conv1)(x, patches, c1, h->conv1.w, h->conv1.Kw, h->conv1.bias, B1, st, planar); }));
+        return K(launch_stem_conv1)(x, patches, c1, h->conv1.w, h->conv1.Kw, h->conv1.bias, B1, st, 0); }));
       if (Bc > B1)
         RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * (Bc - B1), [&]() {
           return K(launch_stem_conv1)(xsrc2, (unsigned char*)patches + (size_t)B1 * h->H0 * h->H0 * 32 * es, (unsigned char*)c1 + (size_t)B1 * h->H0 * h->H0 * h->C0 * es,
-                                   h->conv1.w, h->conv1.Kw, h->conv1.bias, Bc - B1, st, planar); }));
+                                   h->conv1.w, h->conv1.Kw, h->conv1.bias, Bc - B1, st, 0); }));
     } else {
       RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() { return K(launch_im2col27)(x, patches, B1, img, img, h->H0, h->H0, dt, st); }));
       if (Bc > B1)
@@ -814,24 +803,14 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
       RC_TRY(run_gemm(h, st, "stem.conv1", h->conv1, conv_params(h->conv1, patches, c1, Bc, h->H0, h->H0, 32, 32, 1, 1, 1, 0, h->C0, ACT_LRELU, nullptr, 0, nullptr), h->C0, 27));
     }
     RC_TRY(run_gemm(h, st, "stem.conv2", h->conv2, p2, h->C1, 9.0 * h->C0));
-    constexpr bool split_stem = false;
-    if (!split_stem) {
-      // conv3 + bn3 + (downsample conv + bn_d as a tail K slice over the im2col rows) + LeakyReLU + MaxPool2d(2) + pos_embed1
-      RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, p3, h->C1, 9.0 * h->C1 + 27.0));
-    } else {
-      RC_TRY(run_gemm(h, st, "stem.downsample", h->down, conv_params(h->down, patches, ident, Bc, h->H0, h->H0, 32, 32, 1, 1, 1, 0, h->C1, ACT_NONE, nullptr, 0, nullptr), h->C1, 27));
-      RC_TRY(run_gemm(h, st, "stem.conv3", h->conv3, conv_params(h->conv3, c2, c3, Bc, h->H0, h->H0, h->C1, h->C1, 3, 3, 1, 1, h->C1, ACT_LRELU, ident, 1, nullptr), h->C1, 9.0 * h->C1));
-      RC_TRY(timed(h, st, "stem.maxpool", KID_MAXPOOL, 0.0, [&]() { return K(launch_maxpool2_pos)(c3, h->pos1, x1, Bc, h->H1, h->H1, h->C1, dt, st); }));
-    }
+    RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, p3, h->C1, 9.0 * h->C1 + 27.0));
   }
   RC_TRY(tap(h, "stem", x1, (size_t)Bc * h->H1 * h->H1 * h->C1 * es, first, st));
 
   // stage 1: x += conv3(GELU(conv2_g(GELU(conv1(BN(x))))))
   const int Cg = h->hid1 / h->cfg.group;
-  constexpr bool no_fuse = false;
-  // one LDS-resident kernel per block (stage1_w4.hip / stage1_ring.hip, any map up to 20 wide); other geometries / numerics modes and FSVIT_NO_FUSE=1 take the three-launch route
-  const bool ring_ok = K(stage1_ring_supported)(dt, h->C1, h->hid1, h->cfg.group, h->H1) && h->s1.size() && h->s1[0].c2.Kw == 320;
-  const bool fuse1 = !no_fuse && ring_ok && K(stage1_ring_preferred)();
+  // one LDS-resident kernel per block (stage1_w4.hip, any map up to 20 wide); other geometries / numerics modes take the three-launch route
+  const bool fuse1 = K(stage1_ring_supported)(dt, h->C1, h->hid1, h->cfg.group, h->H1) && h->s1.size() && h->s1[0].c2.Kw == 320;
   for (size_t i = 0; i < h->s1.size(); ++i) {
     const Block1& b = h->s1[i];
     if (fuse1) {   // one LDS-resident kernel per block, ping-pong between x1 and x1b
@@ -905,40 +884,84 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
   return 0;
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------ C ABI
-extern "C" int fsvit_visformer_create(const fsvit_visformer_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors,
-                                      int dtype, fsvit_visformer** out) {
-  if (!cfg || !state_dict || !out || n_tensors <= 0) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
-  if (cfg->num_heads < 1 || cfg->embed_dim < 2 || cfg->init_channels < 1 || cfg->depth[0] < 0 || cfg->depth[1] < 0 || cfg->depth[2] < 0)
-    return fail(FSVIT_ERR_ARG, "bad Visformer configuration");
-  fsvit_visformer* h = new fsvit_visformer();
-  h->kind = KIND_VISFORMER;
-  h->cfg = *cfg;
-  h->dtype = dtype;
-  h->es = storage_bytes(dtype);
-  SD sd{state_dict, n_tensors};
-  int rc = build(h, sd);
-  if (rc != 0) { fsvit_visformer_destroy(h); return rc; }
-  *out = h;
-  return 0;
+size_t visformer_plan_bytes(const EngineBase* h, size_t Bc) { return make_plan(static_cast<const fsvit_visformer*>(h), Bc).total; }
+int visformer_chunk(EngineBase* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+  return forward_chunk(static_cast<fsvit_visformer*>(h), x, Bc, feat, ws, first, st);
 }
 
-extern "C" void fsvit_visformer_destroy(fsvit_visformer* h) {
+// ---- the handle plumbing every encoder shares behind its fsvit_<encoder>_* entry points
+template <class H>
+void encoder_destroy(H* h) {
   if (!h) return;
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
 }
 
-extern "C" int fsvit_visformer_out_dim(const fsvit_visformer* h) { return h ? h->C3 : 0; }
-extern "C" int fsvit_visformer_dtype(const fsvit_visformer* h) { return h ? h->dtype : -1; }
-
-extern "C" size_t fsvit_visformer_workspace_bytes(const fsvit_visformer* h, int chunk_images) {
-  if (!h || chunk_images <= 0) return 0;
-  return make_plan(h, (size_t)chunk_images).total;
+// bad_cfg / bad_cfg_msg: the caller's range check of *cfg (false for a null cfg); build_fn packs the state dict into the new handle
+template <class H, class Cfg>
+int encoder_create(const Cfg* cfg, const fsvit_tensor* state_dict, int n_tensors, int dtype, H** out, bool bad_cfg, const char* bad_cfg_msg, int kind,
+                   int (*build_fn)(H*, const SD&), size_t (*plan_bytes)(const EngineBase*, size_t),
+                   int (*chunk)(EngineBase*, const float*, int, float*, unsigned char*, bool, hipStream_t), const char* size_fmt) {
+  if (!cfg || !state_dict || !out || n_tensors <= 0) return fail(FSVIT_ERR_ARG, "null argument");
+  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
+  if (bad_cfg) return fail(FSVIT_ERR_ARG, "%s", bad_cfg_msg);
+  H* h = new H();
+  h->kind = kind;
+  h->cfg = *cfg;
+  h->img_size = cfg->img_size;
+  h->dtype = dtype;
+  h->es = storage_bytes(dtype);
+  h->plan_bytes = plan_bytes; h->chunk = chunk; h->size_fmt = size_fmt;
+  SD sd{state_dict, n_tensors};
+  int rc = build_fn(h, sd);
+  if (rc != 0) { encoder_destroy(h); return rc; }
+  *out = h;
+  return 0;
 }
+
+size_t encoder_workspace_bytes(const EngineBase* h, int chunk_images) {
+  if (!h || chunk_images <= 0) return 0;
+  return h->plan_bytes(h, (size_t)chunk_images);
+}
+
+// the image-size messages restate the reference's asserts (visformer.py:283-284,431: "does not match"; deit.py:96-97 and lvvit.py: "doesn't match")
+const char* const SIZE_FMT_VISFORMER = "Input image size (%d*%d) does not match model (%d*%d).";
+const char* const SIZE_FMT_VIT = "Input image size (%d*%d) doesn't match model (%d*%d).";
+
+int encoder_forward(EngineBase* h, const float* x, int n_img, int img_h, int img_w, float* feat, void* ws, size_t ws_bytes, void* stream) {
+  if (h && n_img <= 0) return 0;
+  if (!h || !x || !feat || !ws) return fail(FSVIT_ERR_ARG, "null argument");
+  if (img_h != h->img_size || img_w != h->img_size) return fail(FSVIT_ERR_IMG_SIZE, h->size_fmt, img_h, img_w, h->img_size, h->img_size);
+  if (((uintptr_t)ws & 255) != 0) return fail(FSVIT_ERR_ARG, "workspace must be 256-byte aligned");
+  // largest chunk that fits the workspace (plan size is monotone in the chunk)
+  int lo = 0, hi = n_img;
+  while (lo < hi) {
+    int mid = (lo + hi + 1) / 2;
+    if (h->plan_bytes(h, (size_t)mid) <= ws_bytes) lo = mid; else hi = mid - 1;
+  }
+  if (lo < 1) return fail(FSVIT_ERR_WORKSPACE, "workspace of %zu bytes cannot hold one image (need %zu)", ws_bytes, h->plan_bytes(h, 1));
+  const size_t img_elems = (size_t)3 * img_h * img_w;
+  for (int off = 0; off < n_img; off += lo) {
+    const int bc = n_img - off < lo ? n_img - off : lo;
+    int rc = h->chunk(h, x + (size_t)off * img_elems, bc, feat + (size_t)off * h->out_dim, (unsigned char*)ws, off == 0, (hipStream_t)stream);
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------ C ABI
+extern "C" int fsvit_visformer_create(const fsvit_visformer_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors,
+                                      int dtype, fsvit_visformer** out) {
+  const bool bad = cfg && (cfg->num_heads < 1 || cfg->embed_dim < 2 || cfg->init_channels < 1 || cfg->depth[0] < 0 || cfg->depth[1] < 0 || cfg->depth[2] < 0);
+  return encoder_create(cfg, state_dict, n_tensors, dtype, out, bad, "bad Visformer configuration", KIND_VISFORMER, build, visformer_plan_bytes, visformer_chunk,
+                        SIZE_FMT_VISFORMER);
+}
+extern "C" void fsvit_visformer_destroy(fsvit_visformer* h) { encoder_destroy(h); }
+extern "C" int fsvit_visformer_out_dim(const fsvit_visformer* h) { return h ? h->out_dim : 0; }
+extern "C" int fsvit_visformer_dtype(const fsvit_visformer* h) { return h ? h->dtype : -1; }
+extern "C" size_t fsvit_visformer_workspace_bytes(const fsvit_visformer* h, int chunk_images) { return encoder_workspace_bytes(h, chunk_images); }
 
 extern "C" int fsvit_encoder_set_tap(void* hv, const char* name, void* dst_dev, size_t bytes) {
   EngineBase* h = static_cast<EngineBase*>(hv);
@@ -950,28 +973,7 @@ extern "C" int fsvit_encoder_set_tap(void* hv, const char* name, void* dst_dev, 
 
 extern "C" int fsvit_visformer_forward(fsvit_visformer* h, const float* x, int n_img, int img_h, int img_w,
                                        float* feat, void* ws, size_t ws_bytes, void* stream) {
-  if (h && n_img <= 0) return 0;
-  if (!h || !x || !feat || !ws) return fail(FSVIT_ERR_ARG, "null argument");
-  if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)   // PatchEmbed assert / pos_embed mismatch (visformer.py:283-284,431)
-    return fail(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) does not match model (%d*%d).", img_h, img_w, h->cfg.img_size, h->cfg.img_size);
-  if (n_img <= 0) return 0;
-  if (((uintptr_t)ws & 255) != 0) return fail(FSVIT_ERR_ARG, "workspace must be 256-byte aligned");
-  // largest chunk that fits the workspace (plan size is monotone in the chunk)
-  int lo = 0, hi = n_img;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) / 2;
-    if (make_plan(h, (size_t)mid).total <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  if (lo < 1) return fail(FSVIT_ERR_WORKSPACE, "workspace of %zu bytes cannot hold one image (need %zu)", ws_bytes, make_plan(h, 1).total);
-  const int chunk = lo;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t img_elems = (size_t)3 * img_h * img_w;
-  for (int off = 0; off < n_img; off += chunk) {
-    const int bc = n_img - off < chunk ? n_img - off : chunk;
-    int rc = forward_chunk(h, x + (size_t)off * img_elems, bc, feat + (size_t)off * h->C3, (unsigned char*)ws, off == 0, st);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return encoder_forward(h, x, n_img, img_h, img_w, feat, ws, ws_bytes, stream);
 }
 
 /* Post-norm token map [n_img][H3*H3][C3] fp32 of the images of the LAST fsvit_visformer_forward call on this handle (same workspace,
@@ -1005,22 +1007,20 @@ extern "C" int fsvit_proto_head_devtemp(const float* fs, const float* fq, int E,
   return 0;
 }
 
-static int encoder_forward_any(void* hv, const float* x, int n, int img_h, int img_w, float* feat, void* ws, size_t ws_bytes, void* stream);
-static int encoder_out_dim_any(void* hv);
-
 extern "C" int fsvit_meta_baseline_forward(void* hv, const float* x_shot, const float* x_query, int E, int way,
                                            int shot, int Q, int img_h, int img_w, float temp, int method, float* logits,
                                            float* acc, float* loss, float* feat, void* ws, size_t ws_bytes, void* stream) {
   if (!hv || !feat) return fail(FSVIT_ERR_ARG, "null argument");
-  const int ns = E * way * shot, nq = E * Q, D = encoder_out_dim_any(hv);
+  EngineBase* eb = static_cast<EngineBase*>(hv);
+  if (!eb->chunk) return fail(FSVIT_ERR_ARG, "not an fsvit encoder handle");
+  const int ns = E * way * shot, nq = E * Q, D = eb->out_dim;
   // the reference encodes cat([shots, queries]) in one call (meta_baseline.py:29-32); eval mode is
   // per-image independent, so two passes into one feature buffer are equivalent
   {   // Visformer: ONE pass over shots + queries when the workspace holds them all (larger launches, fewer tile tails)
-    EngineBase* eb = static_cast<EngineBase*>(hv);
     if (eb->kind == KIND_VISFORMER && x_shot && x_query && ns > 0 && nq > 0) {
       fsvit_visformer* h = static_cast<fsvit_visformer*>(eb);
       if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)
-        return fail(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) does not match model (%d*%d).", img_h, img_w, h->cfg.img_size, h->cfg.img_size);
+        return fail(FSVIT_ERR_IMG_SIZE, SIZE_FMT_VISFORMER, img_h, img_w, h->cfg.img_size, h->cfg.img_size);
       if (ws && ((uintptr_t)ws & 255) == 0 && make_plan(h, (size_t)ns + nq).total <= ws_bytes) {
         int rc1 = forward_chunk(h, x_shot, ns + nq, feat, (unsigned char*)ws, true, (hipStream_t)stream, x_query, ns);
         if (rc1 != 0) return rc1;
@@ -1028,9 +1028,9 @@ extern "C" int fsvit_meta_baseline_forward(void* hv, const float* x_shot, const 
       }
     }
   }
-  int rc = encoder_forward_any(hv, x_shot, ns, img_h, img_w, feat, ws, ws_bytes, stream);
+  int rc = encoder_forward(eb, x_shot, ns, img_h, img_w, feat, ws, ws_bytes, stream);
   if (rc != 0) return rc;
-  rc = encoder_forward_any(hv, x_query, nq, img_h, img_w, feat + (size_t)ns * D, ws, ws_bytes, stream);
+  rc = encoder_forward(eb, x_query, nq, img_h, img_w, feat + (size_t)ns * D, ws, ws_bytes, stream);
   if (rc != 0) return rc;
   return fsvit_proto_head(feat, feat + (size_t)ns * D, E, way, shot, Q, D, temp, method, logits, acc, loss, stream);
 }
@@ -1375,22 +1375,20 @@ extern "C" int fsvit_pool_affine(const void* x, const float* scale, const float*
 }
 
 // ------------------------------------------------------------------------------------ profiling
-static bool K_w4_enabled(int kdt) { return K(stage1_w4_enabled)(); }
 extern "C" const char* fsvit_kernel_name(int kernel_id, int dtype) {
-  static const char* f32n[] = {"gemm256_kernel", "conv_gemm_v2_kernel<float,128,64,2,2,3>", "conv_gemm_v2_kernel<float,128,32,4,1,3>",
-                               "im2col27_kernel<float>", "maxpool2_pos_kernel<float>", "attention_v2_kernel<float,...>", "pool_affine_kernel<float>", "proto_head_kernel", "stage1_block_kernel", "conv_gemm_v2_kernel<float,128,128,2,2,2>",
-                               "patchify_kernel<float>", "layernorm_kernel<float>", "conv3x3_halo_kernel", "mlp_rows_kernel", "-", "qkv_attn_kernel", "stem_conv1_kernel", "stage1_ring_kernel", "ln_gemm_rows_kernel", "qkv_attn_rows_kernel", "vit_attn_rows_kernel"};
-  static const char* bf16n[] = {"gemm256_kernel", "conv_gemm_v2_kernel<__bf16,128,64,2,2,3>", "conv_gemm_v2_kernel<__bf16,128,32,4,1,3>",
-                                "im2col27_kernel<__bf16>", "maxpool2_pos_kernel<__bf16>", "attention_v2_kernel<__bf16,...>", "pool_affine_kernel<__bf16>", "proto_head_kernel", "stage1_block_kernel", "conv_gemm_v2_kernel<__bf16,128,128,2,2,2>",
-                                "patchify_kernel<__bf16>", "layernorm_kernel<__bf16>", "conv3x3_halo_kernel", "mlp_rows_kernel", "-", "qkv_attn_kernel", "stem_conv1_kernel", "stage1_ring_kernel", "ln_gemm_rows_kernel", "qkv_attn_rows_kernel", "vit_attn_rows_kernel"};
-  static const char* f16n[] = {"gemm256_kernel", "conv_gemm_v2_kernel<_Float16,128,64,2,2,3>", "conv_gemm_v2_kernel<_Float16,128,32,4,1,3>",
-                               "im2col27_kernel<_Float16>", "maxpool2_pos_kernel<_Float16>", "attention_v2_kernel<_Float16,...>", "pool_affine_kernel<_Float16>", "proto_head_kernel", "stage1_block_kernel", "conv_gemm_v2_kernel<_Float16,128,128,2,2,2>",
-                               "patchify_kernel<_Float16>", "layernorm_kernel<_Float16>", "conv3x3_halo_kernel", "mlp_rows_kernel", "-", "qkv_attn_kernel", "stem_conv1_kernel", "stage1_ring_kernel", "ln_gemm_rows_kernel", "qkv_attn_rows_kernel", "vit_attn_rows_kernel"};
+  // one table, instantiated for the element type as the compiler spells it
+#define FSVIT_KERNEL_NAMES(T)                                                                                                                              \
+  {"gemm256_kernel", "conv_gemm_v2_kernel<" T ",128,64,2,2,3>", "conv_gemm_v2_kernel<" T ",128,32,4,1,3>", "im2col27_kernel<" T ">", "maxpool2_pos_kernel<" T ">", \
+   "attention_v2_kernel<" T ",...>", "pool_affine_kernel<" T ">", "proto_head_kernel", "stage1_block_kernel", "conv_gemm_v2_kernel<" T ",128,128,2,2,2>",          \
+   "patchify_kernel<" T ">", "layernorm_kernel<" T ">", "conv3x3_halo_kernel", "mlp_rows_kernel", "-", "qkv_attn_kernel", "stem_conv1_kernel",                   \
+   "stage1_ring_kernel", "ln_gemm_rows_kernel", "qkv_attn_rows_kernel", "vit_attn_rows_kernel"}
+  static const char* const names[3][21] = {FSVIT_KERNEL_NAMES("float"), FSVIT_KERNEL_NAMES("__bf16"), FSVIT_KERNEL_NAMES("_Float16")};
+#undef FSVIT_KERNEL_NAMES
   static const char* x2n[] = {"gemm256_x2_kernel", "conv_gemm_v2_kernel<f32x2l,128,64,2,2,3>", "conv_gemm_v2_kernel<f32x2l,128,32,4,1,3>", "", "", "", "", "", "", "conv_gemm_v2_kernel<f32x2l,128,128,2,2,2>"};
   if (kernel_id < 0 || kernel_id > 20) return "?";
-  if (kernel_id == KID_STAGE1RING && kd(dtype) == 1 && K_w4_enabled(dtype)) return "stage1_w4_kernel";      // (launch_stage1_ring dispatches to stage1_w4.hip)
-  if (is_x2(dtype)) return kernel_id == 14 ? "gconv3x3_x2_kernel" : (kernel_id == 0 || kernel_id == 1 || kernel_id == 2 || kernel_id == 9) ? x2n[kernel_id] : f32n[kernel_id];
-  return dtype == FSVIT_F32 ? f32n[kernel_id] : dtype == FSVIT_F16 ? f16n[kernel_id] : bf16n[kernel_id];
+  if (kernel_id == KID_STAGE1RING && kd(dtype) == 1) return "stage1_w4_kernel";      // (launch_stage1_ring forwards to stage1_w4.hip)
+  if (is_x2(dtype)) return kernel_id == 14 ? "gconv3x3_x2_kernel" : (kernel_id == 0 || kernel_id == 1 || kernel_id == 2 || kernel_id == 9) ? x2n[kernel_id] : names[0][kernel_id];
+  return names[dtype == FSVIT_F32 ? 0 : dtype == FSVIT_F16 ? 2 : 1][kernel_id];
 }
 
 extern "C" int fsvit_encoder_profile_begin(void* hv) {
@@ -1510,52 +1508,54 @@ int pack_vit_blocks(EngineBase* h, const SD& sd, int depth, int D, int heads, in
     RC_TRY(pack_layer(h, &blocks[i].fc1, w1, hid, D, 1, 1, 1, nullptr, &s2, add_vec(prenorm_bias(w1, hid, D, t2), bf1, hid), true, nullptr, 0, nullptr, 0));
     RC_TRY(pack_layer(h, &blocks[i].fc2, w2, D, hid, 1, 1, 1, scaled ? &rs : nullptr, nullptr, vb2, true, nullptr, 0, nullptr, 0));
     const int kdt = h->dtype;
+    VitBlock& b = blocks[i];
     if (K(mlp_rows_ln_supported)(kd(kdt), D, hid, heads * hdp)) {      // proj + residual + norm2 + Mlp in one row-wise kernel
-      VitBlock& b = blocks[i];
-      void *img = nullptr, *b1i = nullptr;
-      HIP_TRY(hipMalloc(&img, K(mlp_rows_image_bytes)(D, hid, heads * hdp)));
-      h->allocs.push_back(img);
-      HIP_TRY(hipMalloc(&b1i, (size_t)hid * 4));
-      h->allocs.push_back(b1i);
-      RC_TRY(K(launch_mlp_pack)(b.fc1.w, b.fc1.Kw, b.fc1.bias, b.fc2.w, b.fc2.Kw, b.proj.w, b.proj.Kw, heads * hdp, img, (float*)b1i, D, hid, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.mlp_img = img;
+      void* b1i = nullptr;
+      RC_TRY(packed_image(h, K(mlp_rows_image_bytes)(D, hid, heads * hdp), &b.mlp_img, [&](void* img) {
+        HIP_TRY(hipMalloc(&b1i, (size_t)hid * 4));
+        h->allocs.push_back(b1i);
+        return K(launch_mlp_pack)(b.fc1.w, b.fc1.Kw, b.fc1.bias, b.fc2.w, b.fc2.Kw, b.proj.w, b.proj.Kw, heads * hdp, img, (float*)b1i, D, hid, nullptr);
+      }));
       b.mlp_b1 = (float*)b1i;
     }
-    if (K(ln_gemm_rows_supported)(kd(kdt), D, 3 * heads * hdp)) {         // norm1 + qkv in one row-wise kernel
-      VitBlock& b = blocks[i];
-      void* img = nullptr;
-      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
-      h->allocs.push_back(img);
-      RC_TRY(K(launch_ln_gemm_pack)(b.qkv.w, b.qkv.Kw, img, D, 3 * heads * hdp, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.qkv_img = img;
-    }
-    if (K(vit_attn_rows_supported)(kd(kdt), D, heads, hdp, S)) {       // norm1 + qkv + attention core in one launch: the qkv tensor never reaches HBM
-      VitBlock& b = blocks[i];
-      void* img = nullptr;
-      HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp)));
-      h->allocs.push_back(img);
-      RC_TRY(K(launch_qkv_attn_rows_pack)(b.qkv.w, b.qkv.Kw, img, D, heads, hdp, nullptr));
-      HIP_TRY(hipDeviceSynchronize());
-      b.attn_img = img;
-    }
+    if (K(ln_gemm_rows_supported)(kd(kdt), D, 3 * heads * hdp))          // norm1 + qkv in one row-wise kernel
+      RC_TRY(packed_image(h, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp), &b.qkv_img,
+                          [&](void* img) { return K(launch_ln_gemm_pack)(b.qkv.w, b.qkv.Kw, img, D, 3 * heads * hdp, nullptr); }));
+    if (K(vit_attn_rows_supported)(kd(kdt), D, heads, hdp, S))        // norm1 + qkv + attention core in one launch: the qkv tensor never reaches HBM
+      RC_TRY(packed_image(h, K(ln_gemm_rows_image_bytes)(D, 3 * heads * hdp), &b.attn_img,
+                          [&](void* img) { return K(launch_qkv_attn_rows_pack)(b.qkv.w, b.qkv.Kw, img, D, heads, hdp, nullptr); }));
   }
+  return 0;
+}
+
+// The token constants of a ViT handle H (fsvit_vit / fsvit_lvvit): pos_embed[1:] -> pos_patch [np][D], cls_token + pos_embed[0] -> cls_pos0 [D], the final
+// LayerNorm's gain / shift -> ng / nb
+template <class H>
+int upload_token_consts(H* h, const float* cls, const float* pos, const float* g, const float* bt) {
+  const int D = h->D;
+  std::vector<float> pp((size_t)h->np * D), c0(D), gg(g, g + D), bb(bt, bt + D);
+  for (int i = 0; i < h->np; ++i)
+    for (int d = 0; d < D; ++d) pp[(size_t)i * D + d] = pos[(size_t)(i + 1) * D + d];
+  for (int d = 0; d < D; ++d) c0[d] = cls[d] + pos[d];
+  void* dv;
+  RC_TRY(upload(h, pp, false, &dv)); h->pos_patch = (float*)dv;
+  RC_TRY(upload(h, c0, false, &dv)); h->cls_pos0 = (float*)dv;
+  RC_TRY(upload(h, gg, false, &dv)); h->ng = (float*)dv;
+  RC_TRY(upload(h, bb, false, &dv)); h->nb = (float*)dv;
   return 0;
 }
 
 int build_vit(fsvit_vit* h, const SD& sd) {
   const fsvit_vit_cfg& cf = h->cfg;
-  const int epc = 16 / h->es, kch = 64 / h->es;
+  const int kch = 64 / h->es;
   const int D = cf.embed_dim, p = cf.patch_size, heads = cf.num_heads;
   if (cf.img_size % p || D % heads || D % 8) return fail(FSVIT_ERR_ARG, "unsupported ViT geometry");
-  h->D = D; h->npw = cf.img_size / p; h->np = h->npw * h->npw; h->S = h->np + 1;
+  h->D = h->out_dim = D; h->npw = cf.img_size / p; h->np = h->npw * h->npw; h->S = h->np + 1;
   h->hd = D / heads; h->hdp = round_up(h->hd, kch); h->hid = (int)(D * cf.mlp_ratio);
   if (h->hid % 8) return fail(FSVIT_ERR_ARG, "hidden width must be a multiple of 8");
   if (h->S > (h->es == 4 ? 208 : 224)) return fail(FSVIT_ERR_ARG, "attention supports at most %d tokens", h->es == 4 ? 208 : 224);
   const int K = 3 * p * p;
   h->Kp = round_up(K, 8);
-  (void)epc;
   {
     const float* w = sd.get("patch_embed.proj.weight", {D, 3, p, p});
     const float* b = sd.get("patch_embed.proj.bias", {D});
@@ -1569,15 +1569,7 @@ int build_vit(fsvit_vit* h, const SD& sd) {
     std::vector<double> bias(D);
     for (int i = 0; i < D; ++i) bias[i] = b[i];
     RC_TRY(pack_layer(h, &h->pe, w, D, K, 1, 1, 1, nullptr, nullptr, bias, true, nullptr, 0, &cm, h->Kp));
-    std::vector<float> pp((size_t)h->np * D), c0(D), gg(g, g + D), bb(bt, bt + D);
-    for (int i = 0; i < h->np; ++i)
-      for (int d = 0; d < D; ++d) pp[(size_t)i * D + d] = pos[(size_t)(i + 1) * D + d];
-    for (int d = 0; d < D; ++d) c0[d] = cls[d] + pos[d];
-    void* dv;
-    RC_TRY(upload(h, pp, false, &dv)); h->pos_patch = (float*)dv;
-    RC_TRY(upload(h, c0, false, &dv)); h->cls_pos0 = (float*)dv;
-    RC_TRY(upload(h, gg, false, &dv)); h->ng = (float*)dv;
-    RC_TRY(upload(h, bb, false, &dv)); h->nb = (float*)dv;
+    RC_TRY(upload_token_consts(h, cls, pos, g, bt));
   }
   return pack_vit_blocks(h, sd, cf.depth, D, heads, h->hd, h->hdp, h->hid, h->S, true, 1.0, &h->blocks);
 }
@@ -1642,7 +1634,10 @@ int vit_blocks_forward(EngineBase* h, const std::vector<VitBlock>& blocks, void*
   return 0;
 }
 
-int vit_forward_chunk(fsvit_vit* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+size_t vit_plan_bytes(const EngineBase* h, size_t Bc) { return make_vit_plan(static_cast<const fsvit_vit*>(h), Bc).total; }
+
+int vit_forward_chunk(EngineBase* hb, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+  fsvit_vit* h = static_cast<fsvit_vit*>(hb);
   const VitPlan pl = make_vit_plan(h, Bc);
   const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, heads = h->cfg.num_heads, hdp = h->hdp;
   const size_t es = h->es;
@@ -1665,54 +1660,15 @@ int vit_forward_chunk(fsvit_vit* h, const float* x, int Bc, float* feat, unsigne
 }  // namespace
 
 extern "C" int fsvit_vit_create(const fsvit_vit_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors, int dtype, fsvit_vit** out) {
-  if (!cfg || !state_dict || !out || n_tensors <= 0) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
-  if (cfg->num_heads < 1 || cfg->embed_dim < 8 || cfg->depth < 0 || cfg->patch_size < 1) return fail(FSVIT_ERR_ARG, "bad ViT configuration");
-  fsvit_vit* h = new fsvit_vit();
-  h->kind = KIND_VIT;
-  h->cfg = *cfg;
-  h->dtype = dtype;
-  h->es = storage_bytes(dtype);
-  SD sd{state_dict, n_tensors};
-  int rc = build_vit(h, sd);
-  if (rc != 0) { fsvit_vit_destroy(h); return rc; }
-  *out = h;
-  return 0;
+  const bool bad = cfg && (cfg->num_heads < 1 || cfg->embed_dim < 8 || cfg->depth < 0 || cfg->patch_size < 1);
+  return encoder_create(cfg, state_dict, n_tensors, dtype, out, bad, "bad ViT configuration", KIND_VIT, build_vit, vit_plan_bytes, vit_forward_chunk, SIZE_FMT_VIT);
 }
-
-extern "C" void fsvit_vit_destroy(fsvit_vit* h) {
-  if (!h) return;
-  for (void* p : h->allocs) (void)hipFree(p);
-  delete h;
-}
-
-extern "C" int fsvit_vit_out_dim(const fsvit_vit* h) { return h ? h->D : 0; }
-
-extern "C" size_t fsvit_vit_workspace_bytes(const fsvit_vit* h, int chunk_images) {
-  if (!h || chunk_images <= 0) return 0;
-  return make_vit_plan(h, (size_t)chunk_images).total;
-}
-
+extern "C" void fsvit_vit_destroy(fsvit_vit* h) { encoder_destroy(h); }
+extern "C" int fsvit_vit_out_dim(const fsvit_vit* h) { return h ? h->out_dim : 0; }
+extern "C" size_t fsvit_vit_workspace_bytes(const fsvit_vit* h, int chunk_images) { return encoder_workspace_bytes(h, chunk_images); }
 extern "C" int fsvit_vit_forward(fsvit_vit* h, const float* x, int n_img, int img_h, int img_w, float* feat, void* ws,
                                  size_t ws_bytes, void* stream) {
-  if (h && n_img <= 0) return 0;
-  if (!h || !x || !feat || !ws) return fail(FSVIT_ERR_ARG, "null argument");
-  if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)      // PatchEmbed assert (deit.py:96-97)
-    return fail(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) doesn't match model (%d*%d).", img_h, img_w, h->cfg.img_size, h->cfg.img_size);
-  if (((uintptr_t)ws & 255) != 0) return fail(FSVIT_ERR_ARG, "workspace must be 256-byte aligned");
-  int lo = 0, hi = n_img;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) / 2;
-    if (make_vit_plan(h, (size_t)mid).total <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  if (lo < 1) return fail(FSVIT_ERR_WORKSPACE, "workspace of %zu bytes cannot hold one image (need %zu)", ws_bytes, make_vit_plan(h, 1).total);
-  const size_t img_elems = (size_t)3 * img_h * img_w;
-  for (int off = 0; off < n_img; off += lo) {
-    const int bc = n_img - off < lo ? n_img - off : lo;
-    int rc = vit_forward_chunk(h, x + (size_t)off * img_elems, bc, feat + (size_t)off * h->D, (unsigned char*)ws, off == 0, (hipStream_t)stream);
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return encoder_forward(h, x, n_img, img_h, img_w, feat, ws, ws_bytes, stream);
 }
 
 // ==================================================================================== LV-ViT encoder
@@ -1741,7 +1697,7 @@ int build_lvvit(fsvit_lvvit* h, const SD& sd) {
   if (C0 % 32) return fail(FSVIT_ERR_ARG, "stem_channels %d must be a multiple of 32", C0);
   if (D % heads || D % 32) return fail(FSVIT_ERR_ARG, "unsupported LV-ViT geometry");
   if (!(cf.skip_lam > 0.0f)) return fail(FSVIT_ERR_ARG, "skip_lam must be positive");
-  h->C0 = C0; h->D = D;
+  h->C0 = C0; h->D = h->out_dim = D;
   h->H0 = cf.img_size / 2; h->H1 = cf.img_size / 4; h->npw = h->H1 / 4; h->np = h->npw * h->npw; h->S = h->np + 1;
   h->hd = D / heads; h->hdp = round_up(h->hd, kch); h->hid = (int)(D * cf.mlp_ratio);
   if (h->hid % 32) return fail(FSVIT_ERR_ARG, "hidden width must be a multiple of 32");
@@ -1806,15 +1762,7 @@ int build_lvvit(fsvit_lvvit* h, const SD& sd) {
     const float* g = sd.get("norm.weight", {D});
     const float* bt = sd.get("norm.bias", {D});
     if (!cls || !pos || !g || !bt) return FSVIT_ERR_KEY;
-    std::vector<float> pp((size_t)h->np * D), c0(D), gg(g, g + D), bb(bt, bt + D);
-    for (int i = 0; i < h->np; ++i)
-      for (int d = 0; d < D; ++d) pp[(size_t)i * D + d] = pos[(size_t)(i + 1) * D + d];
-    for (int d = 0; d < D; ++d) c0[d] = cls[d] + pos[d];
-    void* dv;
-    RC_TRY(upload(h, pp, false, &dv)); h->pos_patch = (float*)dv;
-    RC_TRY(upload(h, c0, false, &dv)); h->cls_pos0 = (float*)dv;
-    RC_TRY(upload(h, gg, false, &dv)); h->ng = (float*)dv;
-    RC_TRY(upload(h, bb, false, &dv)); h->nb = (float*)dv;
+    RC_TRY(upload_token_consts(h, cls, pos, g, bt));
   }
   return pack_vit_blocks(h, sd, cf.depth, D, heads, h->hd, h->hdp, h->hid, h->S, false, 1.0 / (double)cf.skip_lam, &h->blocks);
 }
@@ -1846,7 +1794,10 @@ LvvitPlan make_lvvit_plan(const fsvit_lvvit* h, size_t Bc) {
   return p;
 }
 
-int lvvit_forward_chunk(fsvit_lvvit* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+size_t lvvit_plan_bytes(const EngineBase* h, size_t Bc) { return make_lvvit_plan(static_cast<const fsvit_lvvit*>(h), Bc).total; }
+
+int lvvit_forward_chunk(EngineBase* hb, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
+  fsvit_lvvit* h = static_cast<fsvit_lvvit*>(hb);
   const LvvitPlan pl = make_lvvit_plan(h, Bc);
   const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, C0 = h->C0, heads = h->cfg.num_heads, img = h->cfg.img_size;
   const size_t es = h->es;
@@ -1884,65 +1835,14 @@ int lvvit_forward_chunk(fsvit_lvvit* h, const float* x, int Bc, float* feat, uns
 }  // namespace
 
 extern "C" int fsvit_lvvit_create(const fsvit_lvvit_cfg* cfg, const fsvit_tensor* state_dict, int n_tensors, int dtype, fsvit_lvvit** out) {
-  if (!cfg || !state_dict || !out || n_tensors <= 0) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
-  if (cfg->num_heads < 1 || cfg->embed_dim < 32 || cfg->depth < 0 || cfg->stem_channels < 32) return fail(FSVIT_ERR_ARG, "bad LV-ViT configuration");
-  fsvit_lvvit* h = new fsvit_lvvit();
-  h->kind = KIND_LVVIT;
-  h->cfg = *cfg;
-  h->dtype = dtype;
-  h->es = storage_bytes(dtype);
-  SD sd{state_dict, n_tensors};
-  int rc = build_lvvit(h, sd);
-  if (rc != 0) { fsvit_lvvit_destroy(h); return rc; }
-  *out = h;
-  return 0;
+  const bool bad = cfg && (cfg->num_heads < 1 || cfg->embed_dim < 32 || cfg->depth < 0 || cfg->stem_channels < 32);
+  return encoder_create(cfg, state_dict, n_tensors, dtype, out, bad, "bad LV-ViT configuration", KIND_LVVIT, build_lvvit, lvvit_plan_bytes, lvvit_forward_chunk,
+                        SIZE_FMT_VIT);
 }
-
-extern "C" void fsvit_lvvit_destroy(fsvit_lvvit* h) {
-  if (!h) return;
-  for (void* p : h->allocs) (void)hipFree(p);
-  delete h;
-}
-
-extern "C" int fsvit_lvvit_out_dim(const fsvit_lvvit* h) { return h ? h->D : 0; }
-
-extern "C" size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_images) {
-  if (!h || chunk_images <= 0) return 0;
-  return make_lvvit_plan(h, (size_t)chunk_images).total;
-}
-
+extern "C" void fsvit_lvvit_destroy(fsvit_lvvit* h) { encoder_destroy(h); }
+extern "C" int fsvit_lvvit_out_dim(const fsvit_lvvit* h) { return h ? h->out_dim : 0; }
+extern "C" size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_images) { return encoder_workspace_bytes(h, chunk_images); }
 extern "C" int fsvit_lvvit_forward(fsvit_lvvit* h, const float* x, int n_img, int img_h, int img_w, float* feat, void* ws,
                                    size_t ws_bytes, void* stream) {
-  if (h && n_img <= 0) return 0;
-  if (!h || !x || !feat || !ws) return fail(FSVIT_ERR_ARG, "null argument");
-  if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)
-    return fail(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) doesn't match model (%d*%d).", img_h, img_w, h->cfg.img_size, h->cfg.img_size);
-  if (((uintptr_t)ws & 255) != 0) return fail(FSVIT_ERR_ARG, "workspace must be 256-byte aligned");
-  int lo = 0, hi = n_img;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) / 2;
-    if (make_lvvit_plan(h, (size_t)mid).total <= ws_bytes) lo = mid; else hi = mid - 1;
-  }
-  if (lo < 1) return fail(FSVIT_ERR_WORKSPACE, "workspace of %zu bytes cannot hold one image (need %zu)", ws_bytes, make_lvvit_plan(h, 1).total);
-  const size_t img_elems = (size_t)3 * img_h * img_w;
-  for (int off = 0; off < n_img; off += lo) {
-    const int bc = n_img - off < lo ? n_img - off : lo;
-    int rc = lvvit_forward_chunk(h, x + (size_t)off * img_elems, bc, feat + (size_t)off * h->D, (unsigned char*)ws, off == 0, (hipStream_t)stream);
-    if (rc != 0) return rc;
-  }
-  return 0;
-}
-
-static int encoder_forward_any(void* hv, const float* x, int n, int img_h, int img_w, float* feat, void* ws, size_t ws_bytes, void* stream) {
-  EngineBase* b = static_cast<EngineBase*>(hv);
-  if (b->kind == KIND_VISFORMER) return fsvit_visformer_forward(static_cast<fsvit_visformer*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
-  if (b->kind == KIND_VIT) return fsvit_vit_forward(static_cast<fsvit_vit*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
-  if (b->kind == KIND_LVVIT) return fsvit_lvvit_forward(static_cast<fsvit_lvvit*>(b), x, n, img_h, img_w, feat, ws, ws_bytes, stream);
-  return fail(FSVIT_ERR_ARG, "not an fsvit encoder handle");
-}
-static int encoder_out_dim_any(void* hv) {
-  EngineBase* b = static_cast<EngineBase*>(hv);
-  if (b->kind == KIND_LVVIT) return static_cast<fsvit_lvvit*>(b)->D;
-  return b->kind == KIND_VISFORMER ? static_cast<fsvit_visformer*>(b)->C3 : (b->kind == KIND_VIT ? static_cast<fsvit_vit*>(b)->D : 0);
+  return encoder_forward(h, x, n_img, img_h, img_w, feat, ws, ws_bytes, stream);
 }

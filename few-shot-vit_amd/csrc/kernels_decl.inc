@@ -26,16 +26,11 @@ int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const 
 
 // fused stage-1 block; x and y must be different buffers.  stage1_ring.hip: wave = channel group and register-resident weights, on the packed layers themselves (w1 [256][128], w2 [256][320], w3 [128][256])
 bool stage1_ring_supported(int dtype, int C1, int hid, int group, int H1);
-bool stage1_ring_preferred();   // false under FSVIT_STAGE1_RING=0
 int launch_stage1_ring(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, hipStream_t s, const void* w3s = nullptr);
 int launch_stage1_ring16(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, hipStream_t s);
-int launch_stage1_ring_train(const void* xn, void* z3, const void* w1, const void* w2, const void* w3, void* h1, void* g1, void* h2, void* g2, int B, int H,
-                             int W, hipStream_t s);
 // stage1_w4.hip: the block at one wave per SIMD with 32x32x16 MFMAs and hand-slotted GELUs (same arguments as launch_stage1_ring)
-bool stage1_w4_enabled();
 int launch_stage1_w4(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, hipStream_t s, const void* w3s = nullptr);
 int launch_stage1_w4_prescale(const void* w, void* ws, int n, hipStream_t s);
-int stage1_ring_block_train_rows(int B, int H, int W);
 int launch_stage1_ring_block_train(const void* x, void* out, const void* w1f, const float* b1f, const void* w2, const void* w3, void* h1, void* g1, void* h2, void* g2,
                                    void* xn, const float* sa, const float* sb, const float* scale, float* stats, int B, int H, int W, hipStream_t s);
 int launch_stage1_ring_dgrad(const void* dz3, void* dxn, const void* w3t, const void* w2t, const void* w1t, const void* g2, const void* g1, void* dz2, void* dz1,

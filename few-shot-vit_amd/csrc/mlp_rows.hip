@@ -1338,13 +1338,11 @@ __global__ void ln_gemm_pack_kernel(const bf16* __restrict__ w, int kw, bf16* __
 }
 
 bool ln_gemm_rows_supported(int dtype, int C, int N) {
-  constexpr bool on = true;
-  return on && dtype == 1 && C == 384 && N >= 32 && N % 32 == 0;
+  return dtype == 1 && C == 384 && N >= 32 && N % 32 == 0;
 }
-// the same kernel without the LayerNorm at C = 512 (Visformer stage-3 qkv) (dispatch switch retired in round 6: tools/probes/variants/dispatch_switches.r06.patch)
+// the same kernel without the LayerNorm at C = 512 (Visformer stage-3 qkv)
 bool gemm_rows_supported(int dtype, int C, int N) {
-  constexpr bool on = true;
-  return on && dtype == 1 && C == 512 && N >= 32 && N % 32 == 0;
+  return dtype == 1 && C == 512 && N >= 32 && N % 32 == 0;
 }
 size_t ln_gemm_rows_image_bytes(int C, int N) { return (size_t)(N / 32) * (C / 16) * 1024; }
 int launch_ln_gemm_pack(const void* w, int kw, void* wimg, int C, int N, hipStream_t s) {
@@ -1352,10 +1350,9 @@ int launch_ln_gemm_pack(const void* w, int kw, void* wimg, int C, int N, hipStre
   hipLaunchKernelGGL(ln_gemm_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const bf16*)w, kw, (bf16*)wimg, C, N, 0, 0);
   return (int)hipGetLastError();
 }
-// qkv conv + attention on the rows kernel: C = 512, head dim padded to 96, maps of at most 32 tokens (dispatch switch retired in round 6)
+// qkv conv + attention on the rows kernel: C = 512, head dim padded to 96, maps of at most 32 tokens
 bool qkv_attn_rows_supported(int dtype, int C, int heads, int hdp, int S) {
-  constexpr bool on = true;
-  return on && dtype == 1 && C == 512 && hdp == 96 && heads >= 1 && S >= 1 && S <= 32;
+  return dtype == 1 && C == 512 && hdp == 96 && heads >= 1 && S >= 1 && S <= 32;
 }
 int launch_qkv_attn_rows_pack(const void* w, int kw, void* wimg, int C, int heads, int hdp, hipStream_t s) {
   const int N = 3 * heads * hdp;
@@ -1379,10 +1376,9 @@ int launch_qkv_attn_rows(const void* x, void* ctx, const void* wimg, const float
                      S, heads, n_tiles);
   return (int)hipGetLastError();
 }
-// norm1 + qkv + attention of a ViT block in one launch (vit_attn_rows_kernel): C = 384, head dim 64, up to 256 tokens (dispatch switch retired in round 6)
+// norm1 + qkv + attention of a ViT block in one launch (vit_attn_rows_kernel): C = 384, head dim 64, up to 256 tokens
 bool vit_attn_rows_supported(int dtype, int C, int heads, int hdp, int S) {
-  constexpr bool on = true;
-  return on && dtype == 1 && C == 384 && hdp == 64 && heads >= 1 && S >= 1 && S <= 256;
+  return dtype == 1 && C == 384 && hdp == 64 && heads >= 1 && S >= 1 && S <= 256;
 }
 // ctx [B*S][heads*64] = softmax(scale q k^T) v per image and head, q | k | v = bias + W' LN(x)   (image from launch_qkv_attn_rows_pack with C = 384)
 int launch_vit_attn_rows(const void* x, void* ctx, const void* wimg, const float* bias, int B, int S, int C, int heads, int hdp, float eps, float scale,
@@ -1423,8 +1419,7 @@ static int launch_gemm_rows_t(const void* x, void* y, const void* wimg, const fl
 }
 // 2 x 2 / stride-2 patch embedding on the rows kernel: x NHWC [B][H][H][Ci] with 4 Ci = 512, y [B (H/2)^2][N] = bias + W patches + pos
 bool patch_embed_rows_supported(int dtype, int Ci, int H, int N) {
-  constexpr bool on = true;
-  return on && dtype == 1 && 4 * Ci == 512 && H >= 2 && H % 2 == 0 && N >= 32 && N % 32 == 0;
+  return dtype == 1 && 4 * Ci == 512 && H >= 2 && H % 2 == 0 && N >= 32 && N % 32 == 0;
 }
 int launch_patch_embed_rows(const void* x, void* y, const void* wimg, const float* bias, const float* pos, int B, int H, int Ci, int N, hipStream_t s) {
   if (B <= 0) return 0;
@@ -1490,20 +1485,16 @@ __global__ void mlp_pack_kernel(const bf16* __restrict__ w1, int k1w, const floa
   wimg[idx] = v;
 }
 
-// the ViT / DeiT block (proj + bias + residual, LayerNorm, Mlp with biases): DeiT-S geometry (was bit 3 of the retired FSVIT_MLP_ROWS switch)
+// the ViT / DeiT block (proj + bias + residual, LayerNorm, Mlp with biases): DeiT-S geometry
 bool mlp_rows_ln_supported(int dtype, int C, int hid, int KC) {
-  constexpr int mode = 15;
-  return dtype == 1 && (mode & 8) && C == 384 && (hid == 1536 || hid == 1152) && KC == 384;     // 1152: LV-ViT (mlp_ratio 3, 36 hidden chunks)
+  return dtype == 1 && C == 384 && (hid == 1536 || hid == 1152) && KC == 384;     // 1152: LV-ViT (mlp_ratio 3, 36 hidden chunks)
 }
 bool mlp_rows_supported(int dtype, int C, int hid) {
-  constexpr int mode = 7;      // bit 0: C = 256, bit 1: C = 512, bit 2: proj fusion
-  if (dtype != 1) return false;
-  return (C == 256 && hid == 1024 && (mode & 1)) || (C == 512 && hid == 2048 && (mode & 2));
+  return dtype == 1 && ((C == 256 && hid == 1024) || (C == 512 && hid == 2048));
 }
 // proj fusion is built for the Visformer-S geometries: (C, KC) = (256, 288) and (512, 576) (6 heads x head dim padded to 48 / 96)
 bool mlp_rows_proj_supported(int C, int hid, int KC) {
-  constexpr int mode = 7;
-  return (mode & 4) && ((C == 256 && hid == 1024 && KC == 288) || (C == 512 && hid == 2048 && KC == 576));
+  return (C == 256 && hid == 1024 && KC == 288) || (C == 512 && hid == 2048 && KC == 576);
 }
 size_t mlp_rows_image_bytes(int C, int hid, int KC) {
   const size_t slf = (size_t)mr_slot_frags(C);

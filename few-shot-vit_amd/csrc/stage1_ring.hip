@@ -64,16 +64,14 @@ __device__ __forceinline__ f32x4 s1r_gelu4(f32x4 v) {
   return f32x4{a[0], a[1], b[0], b[1]};
 }
 
-// TRAIN (the meta-tuning step's forward, train_engine.hip): x = the block's NORMALISED input (the BatchNorm statistics are a pass of their own), no
-// bias, no residual (the scaled residual add rides in the next BatchNorm's reduce pass): y = conv3(h2), and the hidden maps h1 / h2 with the GELU
-// derivatives g1 / g2 at their pre-activations go to HBM for the backward pass ([M][256] each) - the three GEMM launches of a block and their
-// hidden-map round trips in one kernel.
+// The training kernels' HBM maps ([M][256] each): MODE 3 writes the hidden maps h1 / h2 and the GELU derivatives g1 / g2 at their pre-activations for
+// the backward pass; MODE 2 reads the derivatives and writes dz2 / dz1.
 struct S1Train { bf16 *h1, *g1, *h2, *g2; };
-// MODE 3 (round 4: the training forward of a whole stage-1 BLOCK): x = the block's RAW input, the batch-statistics BatchNorm folded into conv1 exactly
-// as the eval engine folds the running statistics (w1 = W1 diag(sa) rounded once, b1 = W1 sb; fold_prenorm_kernel makes them after the BatchNorm's
-// finalize), the residual from the x ring with the block's DropPath scale per image: y = x + scale[image] * conv3(h2).  Also written: h1 / g1 / h2 / g2
-// as in MODE 1, the normalised input xn = sa x + sb of the workgroup's own pixels (the backward's weight-gradient operand), and the per-workgroup
-// partial sums of y and y^2 - the statistics of the NEXT block's BatchNorm.  Replaces bn_apply + stage1_ring_train + the residual add / reduce pass.
+// MODE 3 (the training forward of a whole stage-1 BLOCK, train_engine.hip): x = the block's RAW input, the batch-statistics BatchNorm folded into conv1
+// exactly as the eval engine folds the running statistics (w1 = W1 diag(sa) rounded once, b1 = W1 sb; fold_prenorm_kernel makes them after the
+// BatchNorm's finalize), the residual from the x ring with the block's DropPath scale per image: y = x + scale[image] * conv3(h2).  Also written:
+// h1 / g1 / h2 / g2 and the normalised input xn = sa x + sb of the workgroup's own pixels (the backward's weight-gradient operand).  `stats` is not
+// written: the output statistics from this kernel cost 16 VGPRs more than it has (train_engine.hip).
 struct S1Fused { bf16* xn; const float *sa, *sb, *scale; float* stats; };
 __device__ __forceinline__ void s1r_gelu4_d(f32x4 v, f32x4& h, f32x4& d) {
   f32x2 da, db;
@@ -90,9 +88,7 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
                                                  const float* __restrict__ b1, const bf16* __restrict__ w2, const bf16* __restrict__ w3, int M,
                                                  int H, int W, int n_chunks, int chunks_per_wg, const S1Train tr, const S1Fused fu = S1Fused{}) {
   using namespace s1r;
-  constexpr bool TRAIN = MODE == 1 || MODE == 3;
-  constexpr bool FUSED = MODE == 3 || MODE == 4;
-  constexpr bool FSTATS = MODE == 4;                                // (the statistics epilogue costs 16 VGPRs the kernel does not have: 25 spills, +95 us - kept for reference, not launched)
+  constexpr bool FUSED = MODE == 3;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int t = threadIdx.x, lane = t & 63, lrow = lane & 15, lq = lane >> 4;
   const int g = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -129,10 +125,7 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
   if constexpr (FUSED) {
     if (t < HID) reinterpret_cast<float*>(smem + BIAS)[t] = b1[t];      // (visible after the first barrier below)
   }
-  f32x4 st0[FSTATS ? 2 : 1], st1[FSTATS ? 2 : 1];                         // FUSED: running sums of this lane's 8 output channels (y, y^2) over all its pixels
-#pragma unroll
-  for (int nt = 0; nt < (FSTATS ? 2 : 1); ++nt) st0[nt] = st1[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const long own_lo = (long)q0 * CH;                                   // TRAIN: this workgroup stores h1 / g1 of its OWN pixels only (the halo is recomputed by the neighbours)
+  const long own_lo = (long)q0 * CH;                                   // MODE 2 / 3: this workgroup stores h1 / g1 of its OWN pixels only (the halo is recomputed by the neighbours)
   long own_hi = (long)q1 * CH; own_hi = own_hi < M ? own_hi : M;
 
   // ---- x batches: 64 consecutive pixels from linear index P0 (pixels outside [0, M) are stored as zeros); 2 x 16 B per thread
@@ -204,7 +197,7 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
                                    acc[1] * f32x4{(float)mg[4], (float)mg[5], (float)mg[6], (float)mg[7]});
         *reinterpret_cast<u32x4*>(h1w + slot) = hp;
         if (pp >= own_lo && pp < own_hi) *reinterpret_cast<u32x4*>(tr.h1 + o) = hp;
-      } else if constexpr (TRAIN) {
+      } else if constexpr (FUSED) {
         f32x4 h0, h1v, d0, d1;
         s1r_gelu4_d(acc[0], h0, d0);
         s1r_gelu4_d(acc[1], h1v, d1);
@@ -283,7 +276,7 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
                                    acc[1] * f32x4{(float)mg[4], (float)mg[5], (float)mg[6], (float)mg[7]});
         *reinterpret_cast<u32x4*>(h2w + (mt * 16 + lrow) * 16) = hp;
         if (m < M) *reinterpret_cast<u32x4*>(tr.h2 + o) = hp;
-      } else if constexpr (TRAIN) {
+      } else if constexpr (FUSED) {
         f32x4 h0, h1v, d0, d1;
         s1r_gelu4_d(acc[0], h0, d0);
         s1r_gelu4_d(acc[1], h1v, d1);
@@ -325,11 +318,6 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
         const bf16x8 r = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(xres + (m & (RING - 1)) * 16));
         acc[0] = acc[0] * sc + f32x4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
         acc[1] = acc[1] * sc + f32x4{(float)r[4], (float)r[5], (float)r[6], (float)r[7]};
-        if constexpr (FSTATS) {
-          const float mk = inr ? 1.0f : 0.0f;
-#pragma unroll
-          for (int nt = 0; nt < 2; ++nt) { st0[nt] += acc[nt] * mk; st1[nt] += acc[nt] * acc[nt] * mk; }
-        }
       }
       *reinterpret_cast<u32x4*>(outw + (mt * 16 + lrow) * OROW) = s1r_pack8(acc[0], acc[1]);
     }
@@ -341,40 +329,12 @@ __device__ __forceinline__ void stage1_ring_body(const bf16* __restrict__ x, bf1
       if (m < M) *reinterpret_cast<u32x4*>(y + (size_t)m * C1 + c8 * 8) = *reinterpret_cast<const u32x4*>(smem + OUT + p * OROW + c8 * 16);
     }
   }
-  if constexpr (FSTATS) {
-    // workgroup partial of the output statistics: the 16 pixel lanes of a channel octet (shuffles), then the two waves (ph3 = 0, 1) that share the
-    // 32 channels, in fixed order (bit-reproducible); stats[(wg * 2 + which) * 128 + channel]
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);               // [8 waves][2][32 channels]
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float a = st0[nt][e], q = st1[nt][e];
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { a += __shfl_xor(a, o); q += __shfl_xor(q, o); }
-        if (lrow == 0) {
-          red[(g * 2 + 0) * 32 + lq * 8 + nt * 4 + e] = a;
-          red[(g * 2 + 1) * 32 + lq * 8 + nt * 4 + e] = q;
-        }
-      }
-    __syncthreads();
-    if (t < 256) {
-      const int which = t >> 7, c = t & 127, np = c >> 5, cl = c & 31;
-      fu.stats[((size_t)blockIdx.x * 2 + which) * C1 + c] = red[((np * 2 + 0) * 2 + which) * 32 + cl] + red[((np * 2 + 1) * 2 + which) * 32 + cl];
-    }
-  }
 }
 
 __global__ __launch_bounds__(512, 1) void stage1_ring_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, const bf16* __restrict__ w1,
                                                              const float* __restrict__ b1, const bf16* __restrict__ w2, const bf16* __restrict__ w3, int M,
                                                              int H, int W, int n_chunks, int chunks_per_wg) {
   stage1_ring_body<0>(x, y, w1, b1, w2, w3, M, H, W, n_chunks, chunks_per_wg, S1Train{nullptr, nullptr, nullptr, nullptr});
-}
-__global__ __launch_bounds__(512, 1) void stage1_ring_train_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, const bf16* __restrict__ w1,
-                                                                   const bf16* __restrict__ w2, const bf16* __restrict__ w3, int M, int H, int W, int n_chunks,
-                                                                   int chunks_per_wg, const S1Train tr) {
-  stage1_ring_body<1>(x, y, w1, nullptr, w2, w3, M, H, W, n_chunks, chunks_per_wg, tr);
 }
 __global__ __launch_bounds__(512, 1) void stage1_ring_dgrad_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, const bf16* __restrict__ w1,
                                                                    const bf16* __restrict__ w2, const bf16* __restrict__ w3, int M, int H, int W, int n_chunks,
@@ -391,25 +351,28 @@ __global__ __launch_bounds__(512, 1) void stage1_ring_block_train_kernel(const b
 bool stage1_ring_supported(int dtype, int C1, int hid, int group, int H1) {
   return dtype == 1 && C1 == s1r::C1 && hid == s1r::HID && group == s1r::G && H1 >= 4 && H1 <= 20;
 }
-// The engines run the block as one launch for every supported map (stage1_w4.hip; this kernel for the
-// training modes and behind fsvit_stage1_block).  The three-launch route (conv1 / grouped conv2 / conv3 through the GEMM kernels) serves the geometries and numerics modes this
-// kernel does not (the FSVIT_STAGE1_RING / FSVIT_STAGE1_W4 / FSVIT_NO_FUSE switches were retired in rounds 5 / 6: tools/probes/variants/*.patch).
-bool stage1_ring_preferred() { return true; }
-
-// w1 [256][128], w2 [256][320] (columns (tap, c)), w3 [128][256]: the packed layers of the block (engine.hip pack_layer)
+// The engines run the block as one launch for every supported map (stage1_w4.hip in eval; this file's kernels in the training modes and behind
+// fsvit_stage1_block).  Other geometries and numerics modes take the three-launch route (conv1 / grouped conv2 / conv3 through the GEMM kernels).
+// w1 [256][128], w2 [256][320] (columns (tap, c)), w3 [128][256]: the packed layers of the block (engine.hip pack_layer); w3s: 8 x w3 or null
 int launch_stage1_ring(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, hipStream_t s, const void* w3s) {
-  if (stage1_w4_enabled()) return launch_stage1_w4(x, y, w1, b1, w2, w3, B, H, W, s, w3s);      // w3s: 8 x w3 or null (stage1_w4.hip)
-  return launch_stage1_ring16(x, y, w1, b1, w2, w3, B, H, W, s);
+  return launch_stage1_w4(x, y, w1, b1, w2, w3, B, H, W, s, w3s);
+}
+// persistent grid: one 8-wave workgroup per CU (150 KB of LDS), the chunks spread evenly; returns the number of 64-pixel chunks
+static inline int s1r_grid(int M, int* wgs, int* cpw) {
+  const int n_chunks = (M + s1r::CH - 1) / s1r::CH;
+  int w = n_chunks < 256 ? n_chunks : 256;
+  *cpw = (n_chunks + w - 1) / w;
+  *wgs = (n_chunks + *cpw - 1) / *cpw;
+  return n_chunks;
 }
 // this file's kernel (fsvit_stage1_block: the cross-check of the two kernels in one process)
 int launch_stage1_ring16(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, hipStream_t s) {
   const long Ml = (long)B * H * W;
   if (Ml <= 0) return 0;
   if (Ml >= (1L << 31) - 256 || W > 20 || H * W < 16) return (int)hipErrorInvalidValue;
-  const int M = (int)Ml, n_chunks = (M + s1r::CH - 1) / s1r::CH;
-  int wgs = n_chunks < 256 ? n_chunks : 256;              // one 8-wave workgroup per CU (150 KB of LDS)
-  const int cpw = (n_chunks + wgs - 1) / wgs;
-  wgs = (n_chunks + cpw - 1) / cpw;
+  const int M = (int)Ml;
+  int wgs, cpw;
+  const int n_chunks = s1r_grid(M, &wgs, &cpw);
   {    // per launch: the attribute is per DEVICE (a process-wide "done" flag skipped it on a second GPU), and the call is cheap
     hipError_t e = hipFuncSetAttribute((const void*)stage1_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, s1r::LDS_BYTES);
     if (e != hipSuccess) return (int)e;
@@ -419,44 +382,16 @@ int launch_stage1_ring16(const void* x, void* y, const void* w1, const float* b1
   return (int)hipGetLastError();
 }
 
-// training forward of a stage-1 Mlp: xn [M][128] normalised input -> z3 [M][128], h1 / g1 / h2 / g2 [M][256] (see stage1_ring_body<true>)
-int launch_stage1_ring_train(const void* xn, void* z3, const void* w1, const void* w2, const void* w3, void* h1, void* g1, void* h2, void* g2, int B, int H,
-                             int W, hipStream_t s) {
-  const long Ml = (long)B * H * W;
-  if (Ml <= 0) return 0;
-  if (Ml >= (1L << 31) - 256 || W > 20 || H * W < 16) return (int)hipErrorInvalidValue;
-  const int M = (int)Ml, n_chunks = (M + s1r::CH - 1) / s1r::CH;
-  int wgs = n_chunks < 256 ? n_chunks : 256;
-  const int cpw = (n_chunks + wgs - 1) / wgs;
-  wgs = (n_chunks + cpw - 1) / cpw;
-  hipError_t e = hipFuncSetAttribute((const void*)stage1_ring_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, s1r::LDS_BYTES);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(stage1_ring_train_kernel, dim3(wgs), dim3(512), s1r::LDS_BYTES, s, (const bf16*)xn, (bf16*)z3, (const bf16*)w1, (const bf16*)w2, (const bf16*)w3, M, H, W,
-                     n_chunks, cpw, S1Train{(bf16*)h1, (bf16*)g1, (bf16*)h2, (bf16*)g2});
-  return (int)hipGetLastError();
-}
 // Training forward of a whole stage-1 block (MODE 3, see S1Fused): x [M][128] raw block input, w1f / b1f = conv1 with the batch-statistics BatchNorm folded
-// (fold_prenorm), scale = DropPath scale per image or NULL, out = x + scale * conv3(...), xn = sa x + sb, stats = partial sums of out / out^2:
-// stage1_ring_block_train_rows(M) rows of 2 x 128 floats.
-static inline void s1r_grid(int M, int* wgs, int* cpw) {
-  const int n_chunks = (M + s1r::CH - 1) / s1r::CH;
-  int w = n_chunks < 256 ? n_chunks : 256;
-  *cpw = (n_chunks + w - 1) / w;
-  *wgs = (n_chunks + *cpw - 1) / *cpw;
-}
-int stage1_ring_block_train_rows(int B, int H, int W) {
-  int wgs, cpw;
-  s1r_grid(B * H * W, &wgs, &cpw);
-  return wgs;
-}
+// (fold_prenorm), scale = DropPath scale per image or NULL, out = x + scale * conv3(...), xn = sa x + sb; h1 / g1 / h2 / g2 [M][256].
 int launch_stage1_ring_block_train(const void* x, void* out, const void* w1f, const float* b1f, const void* w2, const void* w3, void* h1, void* g1, void* h2, void* g2,
                                    void* xn, const float* sa, const float* sb, const float* scale, float* stats, int B, int H, int W, hipStream_t s) {
   const long Ml = (long)B * H * W;
   if (Ml <= 0) return 0;
   if (Ml >= (1L << 31) - 256 || W > 20 || H * W < 16 || x == out) return (int)hipErrorInvalidValue;
-  const int M = (int)Ml, n_chunks = (M + s1r::CH - 1) / s1r::CH;
+  const int M = (int)Ml;
   int wgs, cpw;
-  s1r_grid(M, &wgs, &cpw);
+  const int n_chunks = s1r_grid(M, &wgs, &cpw);
   hipError_t e = hipFuncSetAttribute((const void*)stage1_ring_block_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, s1r::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(stage1_ring_block_train_kernel, dim3(wgs), dim3(512), s1r::LDS_BYTES, s, (const bf16*)x, (bf16*)out, (const bf16*)w1f, b1f, (const bf16*)w2, (const bf16*)w3,
@@ -470,10 +405,9 @@ int launch_stage1_ring_dgrad(const void* dz3, void* dxn, const void* w3t, const 
   const long Ml = (long)B * H * W;
   if (Ml <= 0) return 0;
   if (Ml >= (1L << 31) - 256 || W > 20 || H * W < 16 || dz3 == dxn) return (int)hipErrorInvalidValue;
-  const int M = (int)Ml, n_chunks = (M + s1r::CH - 1) / s1r::CH;
-  int wgs = n_chunks < 256 ? n_chunks : 256;
-  const int cpw = (n_chunks + wgs - 1) / wgs;
-  wgs = (n_chunks + cpw - 1) / cpw;
+  const int M = (int)Ml;
+  int wgs, cpw;
+  const int n_chunks = s1r_grid(M, &wgs, &cpw);
   hipError_t e = hipFuncSetAttribute((const void*)stage1_ring_dgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, s1r::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(stage1_ring_dgrad_kernel, dim3(wgs), dim3(512), s1r::LDS_BYTES, s, (const bf16*)dz3, (bf16*)dxn, (const bf16*)w3t, (const bf16*)w2t, (const bf16*)w1t, M, H,

@@ -633,13 +633,6 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
   }
 }
 
-// The engines' stage-1 kernel since round 4 (round 6: 1.91 ms per 12 800-image launch, stage1_ring's eight-wave kernel 2.22).  The FSVIT_STAGE1_W4=0 switch
-// left the sources in round 6 (tools/probes/variants/dispatch_switches.r06.patch re-adds it and the other retired dispatch switches)
-bool stage1_w4_enabled() {
-  constexpr bool off = false;
-  return !off;
-}
-
 __global__ __launch_bounds__(256) void stage1_w4_prescale_kernel(const bf16* __restrict__ w, bf16* __restrict__ ws, int n) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) ws[i] = (bf16)((float)w[i] * 8.0f);      // exact: a power of two
 }
@@ -658,8 +651,7 @@ int launch_stage1_w4(const void* x, void* y, const void* w1, const float* b1, co
   int wgs = n_chunks < 256 ? n_chunks : 256;              // one 4-wave workgroup per CU (156 KB of LDS)
   const int cpw = (n_chunks + wgs - 1) / wgs;
   wgs = (n_chunks + cpw - 1) / cpw;
-  // (the unpipelined variant <false, false> and the FSVIT_STAGE1_W4_PIPE / _PRESCALE switches of round 4 are out of the shipped dispatch:
-  // tools/probes/variants/stage1_switches.r05.patch re-adds them for timing)
+  // (the unpipelined variant <false, false> is not dispatched: tools/probes/variants/stage1_switches.r05.patch, cut from commit 3c70b37, archives its switch)
   const bool sc = w3s != nullptr;
   auto kern = sc ? stage1_w4_kernel<true, true> : stage1_w4_kernel<true, false>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, s1w::LDS_BYTES);

@@ -585,10 +585,9 @@ int train_forward_impl(TR* t, const float* x, float* feat) {
   // Round 4: a block is ONE launch behind its BatchNorm's statistics (stage1_ring.hip MODE 3): the batch statistics are folded into conv1 as the eval
   // engine folds the running statistics (fold_prenorm), the residual with the DropPath scale is added in the same kernel - no apply pass, and the
   // reduce pass reads one finished map instead of adding two and storing a third.  (The statistics of the block's output from the same kernel were
-  // built and measured: 16 more VGPRs than the kernel has, 25 spills, +95 us per launch.)  (FSVIT_STAGE1_BLOCK_FUSED / _TRAIN_FUSED: retired in round 6, dispatch_switches.r06.patch.)
-  constexpr bool block_off = false;
-  constexpr bool fused_off = false;
-  const bool block_fused = !block_off && !fused_off && stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1);
+  // built and measured: 16 more VGPRs than the kernel has, 25 spills, +95 us per launch.)  Other geometries and numerics modes run the BatchNorm apply
+  // pass and the Mlp's three conv launches.
+  const bool block_fused = stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1);
   const size_t s1_mark = t->tmp.off;
   for (int i = 0; i < t->cfg.depth[0]; ++i, ++blk) {
     auto& b = t->s1[i];
@@ -619,20 +618,9 @@ int train_forward_impl(TR* t, const float* x, float* feat) {
     void* z3 = take_tmp(t, M1 * t->C1); NEED(z3);
     T_TRY(bn_fwd(t, p + "norm2.bn", b.x, (int)M1, t->C1, ACT_NONE, nullptr, b.xn, &b.bn, &pend));
     // (z1 / z2 hold the GELU DERIVATIVES at the pre-activations, written next to h1 / h2 by the conv epilogues)
-    if (!fused_off && stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1)) {
-      // the three GEMM launches of the Mlp and the round trips of its hidden maps in ONE kernel (stage1_ring.hip, training variant)
-      void *pk1 = nullptr, *pk2 = nullptr, *pk3 = nullptr;
-      int kw2 = 0;
-      T_TRY(conv_pack_fwd(t, sp.s1c1[i], &pk1));
-      T_TRY(conv_pack_fwd(t, sp.s1c2[i], &pk2, &kw2));
-      T_TRY(conv_pack_fwd(t, sp.s1c3[i], &pk3));
-      if (kw2 != 320) return fsvit_set_error(FSVIT_ERR_ARG, "stage-1 grouped conv pack: Kw %d", kw2);
-      T_RUN(launch_stage1_ring_train(b.xn, z3, pk1, pk2, pk3, b.h1, b.z1, b.h2, b.z2, B, H1, H1, st));
-    } else {
-      T_TRY(conv_fwd(t, sp.s1c1[i], b.xn, B, H1, H1, b.h1, nullptr, b.z1));
-      T_TRY(conv_fwd(t, sp.s1c2[i], b.h1, B, H1, H1, b.h2, nullptr, b.z2));
-      T_TRY(conv_fwd(t, sp.s1c3[i], b.h2, B, H1, H1, z3, nullptr));
-    }
+    T_TRY(conv_fwd(t, sp.s1c1[i], b.xn, B, H1, H1, b.h1, nullptr, b.z1));
+    T_TRY(conv_fwd(t, sp.s1c2[i], b.h1, B, H1, H1, b.h2, nullptr, b.z2));
+    T_TRY(conv_fwd(t, sp.s1c3[i], b.h2, B, H1, H1, z3, nullptr));
     b.scale = dp_scale(t, dp_call, blk, nblk);
     if (t->dp_rate * blk > 0.f) ++dp_call;
     // b.out = b.x + scale * z3: queued for the next block's BatchNorm reduce pass (z3 must outlive this block's tmp scope: it is the first
@@ -812,9 +800,8 @@ int train_backward_impl(TR* t, const float* dfeat) {
     const size_t mark = t->tmp.off;
     void* dz3 = take_tmp(t, M1 * t->C1); NEED(dz3);
     if (i == (int)t->s1.size() - 1) { T_TRY(side_guard(t, dz3, M1 * t->C1 * t->es)); T_RUN(launch_add_scaled(nullptr, dx, b.scale, dz3, M1 * t->C1, (size_t)H1 * H1 * t->C1, dt, st)); }
-    constexpr bool fused_off = false;
     void* dxn = dz3;                                                                           // d(xn): in place over dz3 on the three-launch route
-    if (!fused_off && stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1)) {
+    if (stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1)) {
       // the block's data-gradient chain dz3 -> dz2 -> dz1 -> d(xn) in ONE kernel (stage1_ring.hip MODE 2), then the three weight gradients
       void *pk3 = nullptr, *pk2 = nullptr, *pk1 = nullptr;
       int kw2 = 0;

@@ -1,7 +1,7 @@
 """The run-time knobs the shipped library still reads (round 6): FSVIT_WROUND, FSVIT_BN_PRODUCER_STATS, FSVIT_WGRAD_SIDE_STREAM (+ FSVIT_SIDE_STREAMS /
 FSVIT_WGRAD_WGS, FSVIT_NUMERICS, FSVIT_CHUNK).  The eighteen dispatch switches that only reached retired routes (FSVIT_STAGE1_W4, FSVIT_QKV_ATTN,
-FSVIT_HALO, FSVIT_GEMM256, FSVIT_MLP_ROWS, ...) left the sources in round 6: `git apply tools/probes/variants/dispatch_switches.r06.patch`
-puts them back, and tools/probes/variants/test_dispatch_switches_r05.py.txt is this file as it tested them.  The general kernels those switches
+FSVIT_HALO, FSVIT_GEMM256, FSVIT_MLP_ROWS, ...) left the sources in round 6: tools/probes/variants/dispatch_switches.r06.patch is the archived reverse patch, cut from commit b2a8cf8
+(it applies to that commit's sources only), and tools/probes/variants/test_dispatch_switches_r05.py.txt is this file as it tested them.  The general kernels those switches
 selected stay covered where they are the product path: fp32 `parity` mode, the tiny / deit_micro geometries, image sizes other than 80.
 The knobs are read once per process, so each setting runs in a child process."""
 import os

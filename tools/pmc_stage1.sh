@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC of the stage-1 block operator (stage1_w4.hip), 12 800 images, a kernel trace + two SQ counter passes
 # usage (GPU box, repo root): bash tools/pmc_stage1.sh <tag>   -> gpurun_out/<tag>/stage1_pmc.txt
-# (until round 5 this compared stage1_ring under FSVIT_STAGE1_W4=0; the switch is retired - tools/probes/variants/dispatch_switches.r06.patch)
+# (until round 5 this compared stage1_ring under FSVIT_STAGE1_W4=0; the switch is retired - archived in tools/probes/variants/dispatch_switches.r06.patch, cut from commit b2a8cf8)
 tag=${1:-r06}
 R=$PWD; out=$R/gpurun_out/$tag; mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
