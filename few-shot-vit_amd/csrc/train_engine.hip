@@ -1,8 +1,9 @@
 // Visformer meta-tuning step (meta_tuning_sun_m/train_meta.py:161-177): train-mode forward
 // (batch-statistics BatchNorm with running-stat update, DropPath) with saved activations, and the full backward
 // to every parameter gradient.  GEMM-shaped work (forward convs, data gradients, split-K weight gradients) runs on
-// conv_gemm_v2; everything else is train_kernels.hip / attention_bwd.hip / head.hip.  This first version is
-// correctness-first: nothing is fused and BatchNorm is never folded (its statistics depend on the batch).
+// conv_gemm_v2 and the direct kernels of wgrad3x3.hip / stage1_ring.hip; everything else is train_kernels.hip / attention_bwd.hip / head.hip.
+// Both trainers (Visformer, ViT / DeiT) are a TrainerBase - parameter table, two arenas, batched weight pack, side streams, ONE step driver
+// (trainer_forward / trainer_backward) - plus the model's forward and backward walk, whose launch order is the product.
 #include "../../include/fsvit.h"
 
 #include <hip/hip_runtime.h>
@@ -72,36 +73,32 @@ struct BnSave { void* z = nullptr; float *mean = nullptr, *invstd = nullptr, *sa
 
 }  // namespace
 
-struct fsvit_visformer_trainer {
-  fsvit_visformer_cfg cfg;
+// What both trainer handles are made of: the shared machinery below works on this part only, and the step driver (trainer_forward / trainer_backward)
+// asks the model for the rest through plain function pointers (as EngineBase in engine.hip: a handle is deleted through its concrete type, no vtable).
+struct TrainerBase {
   int dtype = 0, es = 4;          // storage type of activations / activation gradients (FSVIT_F32 | FSVIT_BF16) and its element size
   int gdt = 0;                    // GEMM kernel type (conv_gemm.h): = dtype, or 2 for FSVIT_BF16X2 (fp32 storage, every GEMM as two-limb 16-bit MFMAs on limb-packed weights)
-  int C0, C1, C2, C3, H0, H1, H2, H3, hid1, hid2, hid3, hd2, hdp2, hd3, hdp3, Cg;
+  // ---- set by the model's create: the two walks, the keep-probability of every DropPath call with a non-zero rate (returns their number; keep may be
+  // null), the image side and the image-size message (printf format: got h, w, model h, w), an optional refusal checked before anything is sized
+  int (*forward_walk)(TrainerBase* t, const float* x, float* feat) = nullptr;
+  int (*backward_walk)(TrainerBase* t, const float* dfeat) = nullptr;
+  int (*droppath_calls)(const TrainerBase* t, float rate, std::vector<float>* keep) = nullptr;
+  int img_size = 0;
+  const char* size_fmt = nullptr;
+  int (*pre_check)(const TrainerBase* t, int n_img) = nullptr;
   // ---- per-call state
   std::map<std::string, const fsvit_param*> P;
   hipStream_t st = nullptr;
   Arena save, tmp;
   int B = 0;
   float dp_rate = 0.f;
-  bool freeze_bn = false;                 // BatchNorm layers in eval mode inside the step (utils.freeze_bn): running statistics, no update
   // batched weight pack: the sizing pass (dry arenas) records every pack of forward + backward in call order; the real forward runs them in
   // one or two launches and the real conv calls pick their packed weights up by position
   std::vector<PackJob> jobs;
   std::vector<size_t> job_off;
   size_t pack_bytes = 0, job_cursor = 0;
   unsigned char* pack_base = nullptr;
-  const float* masks = nullptr;           // [n_droppath_calls][B] 0/1
-  // saved forward state (pointers into `save`)
-  struct Stem { void *patches, *z1, *a1, *zd, *ad, *z2, *a2, *z3, *a3; unsigned char* arg; BnSave b1, bd, b2, b3; void* x1; } stem;
-  struct S1 { void *x, *xn, *z1, *h1, *z2, *h2; BnSave bn; const float* scale; void* out; };
-  struct SA { void *x, *xn1, *qkv, *ctx, *xa, *xn2, *z1, *h; BnSave bn1, bn2; const float *s1, *s2; void* out; };
-  struct PE { void *xin, *z; BnSave bn; void* out; };
-  std::vector<S1> s1;
-  std::vector<SA> s2, s3;
-  PE pe2, pe3;
-  BnSave bnf;
   float* scales = nullptr;                // [n_calls][B] = mask / keep
-  const float* dtokens = nullptr;         // optional gradient of the post-norm token map for the next backward (distillation head)
   // weight-gradient split slabs of a backward pass stay in the `save` arena and are summed by ONE table-driven launch at the end of the pass
   std::vector<FinJob> fin;
   size_t save_after_forward = 0;
@@ -125,18 +122,48 @@ struct fsvit_visformer_trainer {
   bool side_on = false;
   struct Range { const unsigned char *lo, *hi; int seq; };
   std::vector<Range> pend;
-  ~fsvit_visformer_trainer() {
+  ~TrainerBase() {
     if (ev_a) (void)hipEventDestroy(ev_a);
     for (hipEvent_t e : ev_done) (void)hipEventDestroy(e);
     for (hipStream_t q : sides) if (q) (void)hipStreamDestroy(q);
   }
 };
 
+struct fsvit_visformer_trainer : TrainerBase {
+  fsvit_visformer_cfg cfg;
+  int C0, C1, C2, C3, H0, H1, H2, H3, hid1, hid2, hid3, hd2, hdp2, hd3, hdp3, Cg;
+  bool freeze_bn = false;                 // BatchNorm layers in eval mode inside the step (utils.freeze_bn): running statistics, no update
+  // saved forward state (pointers into `save`)
+  struct Stem { void *patches, *z1, *a1, *zd, *ad, *z2, *a2, *z3, *a3; unsigned char* arg; BnSave b1, bd, b2, b3; void* x1; } stem;
+  struct S1 { void *x, *xn, *z1, *h1, *z2, *h2; BnSave bn; const float* scale; void* out; };
+  struct SA { void *x, *xn1, *qkv, *ctx, *xa, *xn2, *z1, *h; BnSave bn1, bn2; const float *s1, *s2; void* out; };
+  struct PE { void *xin, *z; BnSave bn; void* out; };
+  std::vector<S1> s1;
+  std::vector<SA> s2, s3;
+  PE pe2, pe3;
+  BnSave bnf;
+  const float* dtokens = nullptr;         // optional gradient of the post-norm token map for the next backward (distillation head)
+};
+
+// ViT / DeiT (deit.py:61-78 Block, :139-218 VisionTransformer): nn.Linear = a 1x1 "conv" of the shared machinery; its own: LayerNorm with kept row
+// statistics, token assembly, the final norm on the cls row
+struct fsvit_vit_trainer : TrainerBase {
+  fsvit_vit_cfg vcfg;
+  int D = 0, S = 0, np = 0, npw = 0, K = 0, Kp = 0, hidv = 0, heads = 0, hd = 0, hdp = 0;
+  struct Blk { void *x, *xn1, *qkv, *ctx, *x1, *xn2, *z1, *h; float *m1, *r1, *m2, *r2; const float *s1, *s2; };
+  std::vector<Blk> blk;
+  void* patches = nullptr;
+  void* xlast = nullptr;
+  float *mf = nullptr, *rf = nullptr;
+};
+
 namespace {
 
+typedef TrainerBase TB;
 typedef fsvit_visformer_trainer TR;
+typedef fsvit_vit_trainer VT;
 
-const fsvit_param* getp(TR* t, const std::string& name) {
+const fsvit_param* getp(TB* t, const std::string& name) {
   auto it = t->P.find(name);
   if (it == t->P.end()) { fsvit_set_error(FSVIT_ERR_KEY, "missing parameter: %s", name.c_str()); return nullptr; }
   return it->second;
@@ -156,7 +183,7 @@ ConvGemmParams gemm_params(const void* x, const void* w, void* y, int B, int H, 
 }
 
 // packed weights of one layer: recorded in the sizing pass, served from the batch in the real pass (fallback: packed here and now)
-int packed_weight(TR* t, const PackJob& job, size_t bytes, void** out) {
+int packed_weight(TB* t, const PackJob& job, size_t bytes, void** out) {
   if (t->tmp.dry) {
     t->jobs.push_back(job);
     t->job_off.push_back(t->pack_bytes);
@@ -179,7 +206,7 @@ int packed_weight(TR* t, const PackJob& job, size_t bytes, void** out) {
   return 0;
 }
 // runs every recorded pack (call after the sizing pass, with the real arenas in place)
-int run_packs(TR* t) {
+int run_packs(TB* t) {
   t->pack_base = nullptr; t->job_cursor = 0;
   if (t->jobs.empty()) return 0;
   unsigned char* base = (unsigned char*)t->save.take(t->pack_bytes);
@@ -194,7 +221,7 @@ int run_packs(TR* t) {
 // ---------------------------------------------------------------- conv forward: z = conv(x) (+ bias)
 // gp != nullptr: z = GELU(conv(x) + bias) and gp = the GELU's derivative at the pre-activation, both written by the GEMM's epilogue (conv_gemm.h y2)
 // the forward pack of a layer: [groups][rows_fwd][Kw], row n = output channel, k = (tap, input channel)
-int conv_pack_fwd(TR* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
+int conv_pack_fwd(TB* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
   const fsvit_param* w = getp(t, c.wname);
   if (!w) return FSVIT_ERR_KEY;
   const int bke = 128 / t->es, Ng = c.rows_fwd(), K = c.kpad_cols(), Kw = round_up(K, bke);
@@ -204,7 +231,7 @@ int conv_pack_fwd(TR* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
 }
 // st_rows != nullptr: ask the layer's kernel for the BatchNorm statistics of z (ConvGemmParams::stats); *st_partial / *st_rows receive the partial
 // sums (tmp arena) and their row count, 0 rows = this layer's kernel does not produce them (the caller runs the reduce pass)
-int conv_fwd(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, void* z, const float* bias, void* gp = nullptr, float** st_partial = nullptr,
+int conv_fwd(TB* t, const ConvSpec& c, const void* x, int B, int H, int W, void* z, const float* bias, void* gp = nullptr, float** st_partial = nullptr,
              int* st_rows = nullptr) {
   if (st_rows) *st_rows = 0;
   const fsvit_param* w = getp(t, c.wname);
@@ -224,7 +251,7 @@ int conv_fwd(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, void*
   if (gp) { p.act = ACT_GELU; p.y2 = gp; }
   if (st_rows) {
     static const bool off = [] { const char* e = getenv("FSVIT_BN_PRODUCER_STATS"); return e && e[0] == '0'; }();
-    *st_rows = (off || t->freeze_bn) ? 0 : conv_stats_rows(p, t->gdt);
+    *st_rows = off ? 0 : conv_stats_rows(p, t->gdt);
     if (*st_rows > 0) {
       *st_partial = (float*)t->tmp.take((size_t)*st_rows * 2 * p.y_cstride * 4);
       if (!*st_partial) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (producer statistics)");
@@ -236,10 +263,10 @@ int conv_fwd(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, void*
 }
 
 // ---------------------------------------------------------------- data gradient: dx = conv^T(dz)   (stride-1 convs and 1x1)
-int side_guard(TR* t, const void* p, size_t bytes);       // (side stream of the backward pass, below)
+int side_guard(TB* t, const void* p, size_t bytes);       // (side stream of the backward pass, below)
 // mul != nullptr: dx = conv^T(dz) * mul (the saved GELU derivative of the layer in front: its backward rides in this epilogue)
 // the transposed ("dgrad") pack of a layer: [groups][Ig_pad rows][Kw], row = input channel, k = (flipped tap, output channel)
-int conv_pack_bwd(TR* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
+int conv_pack_bwd(TB* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
   const fsvit_param* w = getp(t, c.wname);
   if (!w) return FSVIT_ERR_KEY;
   const int bke = 128 / t->es, Ng_pad = c.rows_fwd(), Ig_pad = c.Ig / c.hd_cols * c.hdp_cols;
@@ -248,7 +275,7 @@ int conv_pack_bwd(TR* t, const ConvSpec& c, void** pk, int* Kw_out = nullptr) {
   return packed_weight(t, PackJob{w->data, nullptr, c.O, c.Ig, c.KH, c.KW, c.groups, 1, Ig_pad, Kw, c.hd_cols, c.hdp_cols, c.hd_rows, c.hdp_rows},
                        (size_t)c.groups * Ig_pad * Kw * t->es, pk);
 }
-int conv_bwd_data(TR* t, const ConvSpec& c, const void* dz, int B, int OH, int OW, void* dx, const void* mul = nullptr) {
+int conv_bwd_data(TB* t, const ConvSpec& c, const void* dz, int B, int OH, int OW, void* dx, const void* mul = nullptr) {
   const fsvit_param* w = getp(t, c.wname);
   if (!w) return FSVIT_ERR_KEY;
   const int bke = 128 / t->es;
@@ -271,9 +298,9 @@ int conv_bwd_data(TR* t, const ConvSpec& c, const void* dz, int B, int OH, int O
 }
 
 // ---------------------------------------------------------------- side stream of the backward pass
-int side_begin(TR* t) {                       // the side stream may start once everything queued on the main stream so far is done
+int side_begin(TB* t) {                       // the side stream may start once everything queued on the main stream so far is done
   if (!t->sides[0]) {
-    static const int n = [] { const char* e = getenv("FSVIT_SIDE_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > TR::MAX_SIDE ? TR::MAX_SIDE : v); }();
+    static const int n = [] { const char* e = getenv("FSVIT_SIDE_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > TB::MAX_SIDE ? TB::MAX_SIDE : v); }();
     t->n_side = n;
     for (int i = 0; i < n; ++i) T_TRY((int)hipStreamCreateWithFlags(&t->sides[i], hipStreamNonBlocking));
     T_TRY((int)hipEventCreateWithFlags(&t->ev_a, hipEventDisableTiming));
@@ -284,20 +311,20 @@ int side_begin(TR* t) {                       // the side stream may start once 
   return 0;
 }
 // behind a side launch: its completion event, and the byte ranges it reads
-int side_end(TR* t, const void* p0, size_t b0, const void* p1, size_t b1) {
+int side_end(TB* t, const void* p0, size_t b0, const void* p1, size_t b1) {
   if ((int)t->ev_done.size() <= t->side_seq) {
     hipEvent_t e = nullptr;
     T_TRY((int)hipEventCreateWithFlags(&e, hipEventDisableTiming));
     t->ev_done.push_back(e);
   }
   T_TRY((int)hipEventRecord(t->ev_done[t->side_seq], t->side));
-  t->pend.push_back(TR::Range{(const unsigned char*)p0, (const unsigned char*)p0 + b0, t->side_seq});
-  t->pend.push_back(TR::Range{(const unsigned char*)p1, (const unsigned char*)p1 + b1, t->side_seq});
+  t->pend.push_back(TB::Range{(const unsigned char*)p0, (const unsigned char*)p0 + b0, t->side_seq});
+  t->pend.push_back(TB::Range{(const unsigned char*)p1, (const unsigned char*)p1 + b1, t->side_seq});
   ++t->side_seq;
   return 0;
 }
 // the main stream waits for the side launches up to `seq` (the side stream is in order) and forgets their ranges
-int side_wait(TR* t, int seq) {
+int side_wait(TB* t, int seq) {
   for (int q = 0; q < t->n_side; ++q) {        // per side stream: its youngest launch <= seq (the stream runs in order), unless already waited for
     const int i = seq - ((seq - q) % t->n_side + t->n_side) % t->n_side;
     if (i >= 0 && i > t->side_waited[q]) {
@@ -311,7 +338,7 @@ int side_wait(TR* t, int seq) {
   t->pend.resize(k);
   return 0;
 }
-int side_sync(TR* t) {                        // ... for every side launch so far
+int side_sync(TB* t) {                        // ... for every side launch so far
   if (t->save.dry || t->side_seq == 0) { t->pend.clear(); return 0; }
   T_TRY(side_wait(t, t->side_seq - 1));
   t->pend.clear();
@@ -319,18 +346,17 @@ int side_sync(TR* t) {                        // ... for every side launch so fa
 }
 // error exit of a backward pass: nothing may still be running on a side stream when the caller sees the error (it may free or reuse the workspace the
 // pending weight-gradient launches read)
-template <typename T_>
-int side_drain(T_* t, int rc) {
+int side_drain(TB* t, int rc) {
   if (rc != 0)
     for (hipStream_t q : t->sides)
       if (q) (void)hipStreamSynchronize(q);
   return rc;
 }
 // call before a main-stream launch that WRITES [p, p + bytes): waits for the youngest pending side launch that still reads any of it
-int side_guard(TR* t, const void* p, size_t bytes) {
+int side_guard(TB* t, const void* p, size_t bytes) {
   const unsigned char *lo = (const unsigned char*)p, *hi = lo + bytes;
   int seq = -1;
-  for (const TR::Range& r : t->pend)
+  for (const TB::Range& r : t->pend)
     if (lo < r.hi && r.lo < hi && r.seq > seq) seq = r.seq;
   return seq >= 0 ? side_wait(t, seq) : 0;
 }
@@ -338,7 +364,7 @@ int side_guard(TR* t, const void* p, size_t bytes) {
 // ---------------------------------------------------------------- weight gradient: dW = sum_m dz[m] (x) xcol[m]   (split-K GEMM over transposed operands)
 // A grouped conv is computed as ONE dense GEMM over all channels (the cross-group blocks are discarded by the finalize
 // pass): 8 x the useful FLOPs of the stage-1 3x3 conv, but one full-width launch instead of 8 quarter-empty ones.
-int conv_bwd_weight(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, const void* dz) {
+int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W, const void* dz) {
   const fsvit_param* w = getp(t, c.wname);
   if (!w) return FSVIT_ERR_KEY;
   if (!w->grad && !t->save.dry) return 0;      // (the sizing pass always counts the weight-gradient scratch)
@@ -407,7 +433,7 @@ int conv_bwd_weight(TR* t, const ConvSpec& c, const void* x, int B, int H, int W
 }
 
 // every deferred split-slab finalize of this backward pass (one or two launches)
-int run_finalizes(TR* t) {
+int run_finalizes(TB* t) {
   T_TRY(side_sync(t));
   if (t->save.dry || t->fin.empty()) return 0;
   T_RUN(launch_wgrad_finalize_multi(t->fin.data(), (int)t->fin.size(), t->st));
@@ -471,12 +497,18 @@ int bn_bwd(TR* t, const std::string& name, const BnSave& sv, const void* dy, voi
   return 0;
 }
 
-void* take_act(TR* t, size_t elems) { return t->save.take(elems * t->es); }
-void* take_tmp(TR* t, size_t elems) { return t->tmp.take(elems * t->es); }
+// conv_fwd of a stem layer whose kernel hands its BatchNorm the statistics of the map it stores - not asked for with frozen BatchNorm layers
+int conv_fwd_stats(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, void* z, float** st_partial, int* st_rows) {
+  *st_rows = 0;
+  return conv_fwd(t, c, x, B, H, W, z, nullptr, nullptr, st_partial, t->freeze_bn ? nullptr : st_rows);
+}
+
+void* take_act(TB* t, size_t elems) { return t->save.take(elems * t->es); }
+void* take_tmp(TB* t, size_t elems) { return t->tmp.take(elems * t->es); }
 #define NEED(ptr) do { if (!(ptr)) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small"); } while (0)
 
-const float* dp_scale(TR* t, int call, int block_index, int nblocks) {
-  // per-block rates linspace(0, rate, depth) (visformer.py:312); rate 0 -> plain residual
+const float* dp_scale(TB* t, int call, int block_index, int nblocks) {
+  // per-block rates linspace(0, rate, depth) (visformer.py:312, deit.py:161); rate 0 -> plain residual
   const float r = nblocks > 1 ? t->dp_rate * (float)block_index / (float)(nblocks - 1) : 0.f;
   if (r == 0.f || !t->scales) return nullptr;
   return t->scales + (size_t)call * t->B;
@@ -522,7 +554,8 @@ Specs make_specs(const TR* t) {
 }
 
 // ================================================================ forward
-int train_forward_impl(TR* t, const float* x, float* feat) {
+int train_forward_impl(TB* tb, const float* x, float* feat) {
+  TR* t = static_cast<TR*>(tb);
   const Specs sp = make_specs(t);
   const int B = t->B, dt = t->dtype;
   hipStream_t st = t->st;
@@ -542,10 +575,10 @@ int train_forward_impl(TR* t, const float* x, float* feat) {
     const size_t mark = t->tmp.off;
     float* stp = nullptr;
     int str = 0;
-    T_TRY(conv_fwd(t, sp.conv1, S.patches, B, H0, H0, S.z1, nullptr, nullptr, &stp, &str));
+    T_TRY(conv_fwd_stats(t, sp.conv1, S.patches, B, H0, H0, S.z1, &stp, &str));
     T_TRY(bn_fwd(t, "stem.bn1", S.z1, (int)M0, t->C0, ACT_LRELU, nullptr, S.a1, &S.b1, nullptr, stp, str));
     t->tmp.off = mark;
-    T_TRY(conv_fwd(t, sp.down, S.patches, B, H0, H0, S.zd, nullptr, nullptr, &stp, &str));
+    T_TRY(conv_fwd_stats(t, sp.down, S.patches, B, H0, H0, S.zd, &stp, &str));
     T_TRY(bn_fwd(t, "stem.downsample.1", S.zd, (int)M0, t->C1, ACT_NONE, nullptr, nullptr, &S.bd, nullptr, stp, str));      // statistics only: applied inside the pooling pass
     t->tmp.off = mark;
   }
@@ -554,10 +587,10 @@ int train_forward_impl(TR* t, const float* x, float* feat) {
     const size_t mark = t->tmp.off;
     float* stp = nullptr;
     int str = 0;
-    T_TRY(conv_fwd(t, sp.conv2, S.a1, B, H0, H0, S.z2, nullptr, nullptr, &stp, &str));
+    T_TRY(conv_fwd_stats(t, sp.conv2, S.a1, B, H0, H0, S.z2, &stp, &str));
     T_TRY(bn_fwd(t, "stem.bn2", S.z2, (int)M0, t->C1, ACT_LRELU, nullptr, S.a2, &S.b2, nullptr, stp, str));
     t->tmp.off = mark;
-    T_TRY(conv_fwd(t, sp.conv3, S.a2, B, H0, H0, S.z3, nullptr, nullptr, &stp, &str));
+    T_TRY(conv_fwd_stats(t, sp.conv3, S.a2, B, H0, H0, S.z3, &stp, &str));
     T_TRY(bn_fwd(t, "stem.bn3", S.z3, (int)M0, t->C1, ACT_LRELU, nullptr, nullptr, &S.b3, nullptr, stp, str));      // statistics only: applied inside the pooling pass below
     t->tmp.off = mark;
   }
@@ -696,7 +729,8 @@ int train_forward_impl(TR* t, const float* x, float* feat) {
 }
 
 // ================================================================ backward
-int train_backward_impl(TR* t, const float* dfeat) {
+int train_backward_impl(TB* tb, const float* dfeat) {
+  TR* t = static_cast<TR*>(tb);
   const Specs sp = make_specs(t);
   const int B = t->B, dt = t->dtype;
   hipStream_t st = t->st;
@@ -890,25 +924,7 @@ int train_backward_impl(TR* t, const float* dfeat) {
   return run_finalizes(t);
 }
 
-}  // namespace
-
-// ================================================================ ViT / DeiT trainer (deit.py:61-78 Block, :139-218 VisionTransformer)
-// Same machinery as the Visformer trainer (parameter table, two arenas, conv_fwd / conv_bwd_data / conv_bwd_weight on 1x1 "convs" = nn.Linear,
-// attention forward / backward, GELU, DropPath scales); new: LayerNorm with kept row statistics, token assembly, the final norm on the cls row.
-struct fsvit_vit_trainer : fsvit_visformer_trainer {
-  fsvit_vit_cfg vcfg;
-  int D = 0, S = 0, np = 0, npw = 0, K = 0, Kp = 0, hidv = 0, heads = 0, hd = 0, hdp = 0;
-  struct Blk { void *x, *xn1, *qkv, *ctx, *x1, *xn2, *z1, *h; float *m1, *r1, *m2, *r2; const float *s1, *s2; };
-  std::vector<Blk> blk;
-  void* patches = nullptr;
-  void* xlast = nullptr;
-  float *mf = nullptr, *rf = nullptr;
-};
-
-namespace {
-
-typedef fsvit_vit_trainer VT;
-
+// ================================================================ ViT / DeiT trainer
 ConvSpec lin(const std::string& w, int O, int I) { ConvSpec c; c.wname = w; c.O = O; c.Ig = I; return c; }
 
 struct VSpecs { ConvSpec pe; std::vector<ConvSpec> qkv, proj, fc1, fc2; };
@@ -981,14 +997,8 @@ int vit_ln_bwd(VT* t, const std::string& name, const void* dy, const void* x, co
   return 0;
 }
 
-const float* vit_dp_scale(VT* t, int call, int i) {
-  const int depth = t->vcfg.depth;
-  const float r = depth > 1 ? t->dp_rate * (float)i / (float)(depth - 1) : 0.f;          // deit.py:161 linspace(0, rate, depth)
-  if (r == 0.f || !t->scales) return nullptr;
-  return t->scales + (size_t)call * t->B;
-}
-
-int vit_forward_impl(VT* t, const float* x, float* feat) {
+int vit_forward_impl(TB* tb, const float* x, float* feat) {
+  VT* t = static_cast<VT*>(tb);
   const VSpecs sp = vit_specs(t);
   const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
   const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
@@ -1025,13 +1035,13 @@ int vit_forward_impl(VT* t, const float* x, float* feat) {
     T_TRY(conv_fwd(t, sp.qkv[i], b.xn1, B, S, 1, b.qkv, bqp));
     T_RUN(launch_attention(b.qkv, b.ctx, B, S, heads, hdp, scale, t->gdt == 2 ? 2 : dt, st));
     T_TRY(conv_fwd(t, sp.proj[i], b.ctx, B, S, 1, zp, bp->data));
-    b.s1 = vit_dp_scale(t, dp_call, i);
+    b.s1 = dp_scale(t, dp_call, i, t->vcfg.depth);
     if (t->dp_rate * i > 0.f) ++dp_call;
     T_RUN(launch_add_scaled(b.x, zp, b.s1, b.x1, M * D, (size_t)S * D, dt, st));
     T_TRY(vit_ln_fwd(t, p + "norm2", b.x1, b.xn2, &b.m2, &b.r2, (int)M));
     T_TRY(conv_fwd(t, sp.fc1[i], b.xn2, B, S, 1, b.h, b1->data, b.z1));                       // b.z1 = GELU'(fc1(xn2) + b1)
     T_TRY(conv_fwd(t, sp.fc2[i], b.h, B, S, 1, zp, b2->data));
-    b.s2 = vit_dp_scale(t, dp_call, i);
+    b.s2 = dp_scale(t, dp_call, i, t->vcfg.depth);
     if (t->dp_rate * i > 0.f) ++dp_call;
     T_RUN(launch_add_scaled(b.x1, zp, b.s2, xout, M * D, (size_t)S * D, dt, st));
     t->tmp.off = mark;
@@ -1046,7 +1056,8 @@ int vit_forward_impl(VT* t, const float* x, float* feat) {
   return 0;
 }
 
-int vit_backward_impl(VT* t, const float* dfeat) {
+int vit_backward_impl(TB* tb, const float* dfeat) {
+  VT* t = static_cast<VT*>(tb);
   const VSpecs sp = vit_specs(t);
   const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
   const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
@@ -1118,7 +1129,8 @@ int vit_backward_impl(VT* t, const float* dfeat) {
   return run_finalizes(t);
 }
 
-int vit_droppath_calls(const VT* t, float rate, std::vector<float>* keep) {
+int vit_droppath_calls(const TB* tb, float rate, std::vector<float>* keep) {
+  const VT* t = static_cast<const VT*>(tb);
   int n = 0;
   for (int i = 0; i < t->vcfg.depth; ++i) {
     const float r = t->vcfg.depth > 1 ? rate * (float)i / (float)(t->vcfg.depth - 1) : 0.f;
@@ -1129,124 +1141,8 @@ int vit_droppath_calls(const VT* t, float rate, std::vector<float>* keep) {
   return n;
 }
 
-int vit_size_workspace(VT* t, int n_img, float rate, size_t* save_bytes, size_t* tmp_bytes) {
-  t->B = n_img; t->dp_rate = rate; t->scales = nullptr;
-  t->save = Arena(); t->tmp = Arena();
-  t->save.dry = t->tmp.dry = true;
-  t->jobs.clear(); t->job_off.clear(); t->pack_bytes = 0; t->pack_base = nullptr; t->job_cursor = 0;
-  int rc = vit_forward_impl(t, nullptr, nullptr);
-  if (rc) return rc;
-  size_t tp = t->tmp.peak;
-  t->tmp.off = 0;
-  rc = vit_backward_impl(t, nullptr);
-  if (rc) return rc;
-  if (t->tmp.peak > tp) tp = t->tmp.peak;
-  *save_bytes = align256(t->save.peak + t->pack_bytes + 256 + (size_t)vit_droppath_calls(t, rate, nullptr) * n_img * 4 + 256);
-  *tmp_bytes = align256(tp);
-  return 0;
-}
-
-}  // namespace
-
-static bool side_stream_default(bool dflt);
-extern "C" int fsvit_vit_trainer_create(const fsvit_vit_cfg* cfg, int dtype, fsvit_vit_trainer** out) {
-  if (!cfg || !out) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
-  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16 && dtype != FSVIT_BF16X2) return fsvit_set_error(FSVIT_ERR_ARG, "trainer dtype %d (FSVIT_F32 | FSVIT_BF16 | FSVIT_BF16X2)", dtype);
-  if (cfg->embed_dim % cfg->num_heads || cfg->img_size % cfg->patch_size || cfg->embed_dim % 8) return fsvit_set_error(FSVIT_ERR_ARG, "bad ViT configuration");
-  VT* t = new VT();
-  t->vcfg = *cfg; t->gdt = dtype == FSVIT_BF16X2 ? 2 : dtype; t->dtype = dtype == FSVIT_BF16X2 ? FSVIT_F32 : dtype; t->es = t->dtype == FSVIT_F32 ? 4 : 2;
-  const int kch = 64 / t->es;
-  t->D = cfg->embed_dim; t->npw = cfg->img_size / cfg->patch_size; t->np = t->npw * t->npw; t->S = t->np + 1;
-  t->K = 3 * cfg->patch_size * cfg->patch_size; t->Kp = round_up(t->K, 128 / t->es);
-  t->hidv = (int)(cfg->embed_dim * cfg->mlp_ratio); t->heads = cfg->num_heads; t->hd = cfg->embed_dim / cfg->num_heads; t->hdp = round_up(t->hd, kch);
-  t->side_on = side_stream_default(true);
-  *out = t;
-  return 0;
-}
-extern "C" void fsvit_vit_trainer_destroy(fsvit_vit_trainer* t) { delete t; }
-extern "C" int fsvit_vit_trainer_droppath_calls(const fsvit_vit_trainer* t, float drop_path_rate) { return t ? vit_droppath_calls(t, drop_path_rate, nullptr) : 0; }
-
-extern "C" size_t fsvit_vit_trainer_workspace_bytes(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
-  if (!t || !params || n_img <= 0) return 0;
-  t->P.clear();
-  for (int i = 0; i < n_params; ++i) t->P[params[i].name] = &params[i];
-  size_t sb = 0, tb = 0;
-  if (vit_size_workspace(t, n_img, drop_path_rate, &sb, &tb)) return 0;
-  return sb + tb;
-}
-
-extern "C" int fsvit_vit_train_forward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
-                                       float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-  if (!t || !params || !x_nchw_dev || !feat_dev || !ws_dev || n_img <= 0) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
-  if (img_h != t->vcfg.img_size || img_w != t->vcfg.img_size)
-    return fsvit_set_error(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) doesn't match model (%d*%d).", img_h, img_w, t->vcfg.img_size, t->vcfg.img_size);
-  if (drop_path_rate > 0.f && !masks_dev) return fsvit_set_error(FSVIT_ERR_ARG, "DropPath masks required when drop_path_rate > 0");
-  t->P.clear();
-  for (int i = 0; i < n_params; ++i) t->P[params[i].name] = &params[i];
-  size_t sb = 0, tb = 0;
-  T_TRY(vit_size_workspace(t, n_img, drop_path_rate, &sb, &tb));
-  if (ws_bytes < sb + tb) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace of %zu bytes is too small (need %zu)", ws_bytes, sb + tb);
-  t->st = (hipStream_t)stream;
-  t->save = Arena(); t->save.base = (unsigned char*)ws_dev; t->save.size = sb;
-  t->tmp = Arena(); t->tmp.base = (unsigned char*)ws_dev + sb; t->tmp.size = ws_bytes - sb;
-  t->scales = nullptr;
-  if (drop_path_rate > 0.f) {                       // DropPath scale = mask / keep_prob per call (timm DropPath, deit.py:70,76-77)
-    std::vector<float> keep;
-    const int ncalls = vit_droppath_calls(t, drop_path_rate, &keep);
-    t->scales = (float*)t->save.take((size_t)ncalls * n_img * 4);
-    if (!t->scales) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small");
-    T_RUN(launch_droppath_scales(masks_dev, t->scales, ncalls, n_img, keep.data(), t->st));
-  }
-  T_TRY(run_packs(t));
-  const int rc_f = vit_forward_impl(t, x_nchw_dev, feat_dev);
-  t->save_after_forward = t->save.off;
-  return rc_f;
-}
-
-extern "C" int fsvit_vit_train_backward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
-  if (!t || !params || !dfeat_dev) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
-  if (!t->save.base || t->save.dry) return fsvit_set_error(FSVIT_ERR_ARG, "train_backward called without a preceding train_forward");
-  t->P.clear();
-  for (int i = 0; i < n_params; ++i) t->P[params[i].name] = &params[i];
-  t->st = (hipStream_t)stream;
-  t->tmp.off = 0;
-  t->save.off = t->save_after_forward;            // the pass's weight-gradient slabs are appended to the saved activations
-  t->fin.clear();
-  t->side_seq = 0; t->pend.clear();
-  for (int& v : t->side_waited) v = -1;
-  return side_drain(t, vit_backward_impl(t, dfeat_dev));
-}
-
-// ================================================================ C ABI
-extern "C" int fsvit_visformer_trainer_create(const fsvit_visformer_cfg* cfg, int dtype, fsvit_visformer_trainer** out) {
-  if (!cfg || !out) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
-  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16 && dtype != FSVIT_BF16X2) return fsvit_set_error(FSVIT_ERR_ARG, "trainer dtype %d (FSVIT_F32 | FSVIT_BF16 | FSVIT_BF16X2)", dtype);
-  TR* t = new TR();
-  t->cfg = *cfg; t->gdt = dtype == FSVIT_BF16X2 ? 2 : dtype; t->dtype = dtype == FSVIT_BF16X2 ? FSVIT_F32 : dtype; t->es = t->dtype == FSVIT_F32 ? 4 : 2;
-  const int D = cfg->embed_dim, kch = 64 / t->es;
-  t->C0 = cfg->init_channels; t->C1 = D / 2; t->C2 = D; t->C3 = D * 2;
-  t->H0 = cfg->img_size / 2; t->H1 = cfg->img_size / 4; t->H2 = cfg->img_size / 8; t->H3 = cfg->img_size / 16;
-  t->hid1 = t->C1 * 2; t->hid2 = (int)(t->C2 * cfg->mlp_ratio); t->hid3 = (int)(t->C3 * cfg->mlp_ratio);
-  t->hd2 = t->C2 / cfg->num_heads; t->hd3 = t->C3 / cfg->num_heads;
-  t->hdp2 = round_up(t->hd2, kch); t->hdp3 = round_up(t->hd3, kch);
-  t->Cg = t->hid1 / cfg->group;
-  t->side_on = side_stream_default(true);      // round 4: the direct weight-gradient launches beside the data-gradient chain: 14.26 -> 14.15 ms per 800-image step (same box)
-  *out = t;
-  return 0;
-}
-
-static bool side_stream_default(bool dflt) {
-  const char* e = getenv("FSVIT_WGRAD_SIDE_STREAM");
-  return e ? e[0] != '0' : dflt;
-}
-extern "C" void fsvit_visformer_trainer_destroy(fsvit_visformer_trainer* t) { delete t; }
-
-static void bind_params(TR* t, const fsvit_param* params, int n) {
-  t->P.clear();
-  for (int i = 0; i < n; ++i) t->P[params[i].name] = &params[i];
-}
-
-static int droppath_calls(const TR* t, float rate, std::vector<float>* keep) {
+int droppath_calls(const TB* tb, float rate, std::vector<float>* keep) {
+  const TR* t = static_cast<const TR*>(tb);
   const int depth = t->cfg.depth[0] + t->cfg.depth[1] + t->cfg.depth[2];
   int ncalls = 0;
   for (int b = 0; b < depth; ++b) {
@@ -1259,65 +1155,112 @@ static int droppath_calls(const TR* t, float rate, std::vector<float>* keep) {
   return ncalls;
 }
 
+// nn.BatchNorm2d in train mode needs more than one value per channel; the smallest map is the final H3 x H3 one (B = 1 at 80x80 is valid)
+int bn_pre_check(const TB* t, int n_img) {
+  const int h3 = t->img_size / 16;
+  if ((long)n_img * h3 * h3 < 2) return fsvit_set_error(FSVIT_ERR_ARG, "Expected more than 1 value per channel when training (BatchNorm)");
+  return 0;
+}
+
+// the image-size messages restate the reference's asserts (visformer.py:283-284,431: "does not match"; deit.py:96-97: "doesn't match")
+void visformer_init(TR* t, const fsvit_visformer_cfg& cfg) {
+  t->cfg = cfg;
+  t->forward_walk = train_forward_impl; t->backward_walk = train_backward_impl; t->droppath_calls = droppath_calls; t->pre_check = bn_pre_check;
+  t->img_size = cfg.img_size; t->size_fmt = "Input image size (%d*%d) does not match model (%d*%d).";
+  const int D = cfg.embed_dim, kch = 64 / t->es;
+  t->C0 = cfg.init_channels; t->C1 = D / 2; t->C2 = D; t->C3 = D * 2;
+  t->H0 = cfg.img_size / 2; t->H1 = cfg.img_size / 4; t->H2 = cfg.img_size / 8; t->H3 = cfg.img_size / 16;
+  t->hid1 = t->C1 * 2; t->hid2 = (int)(t->C2 * cfg.mlp_ratio); t->hid3 = (int)(t->C3 * cfg.mlp_ratio);
+  t->hd2 = t->C2 / cfg.num_heads; t->hd3 = t->C3 / cfg.num_heads;
+  t->hdp2 = round_up(t->hd2, kch); t->hdp3 = round_up(t->hd3, kch);
+  t->Cg = t->hid1 / cfg.group;
+}
+void vit_init(VT* t, const fsvit_vit_cfg& cfg) {
+  t->vcfg = cfg;
+  t->forward_walk = vit_forward_impl; t->backward_walk = vit_backward_impl; t->droppath_calls = vit_droppath_calls;
+  t->img_size = cfg.img_size; t->size_fmt = "Input image size (%d*%d) doesn't match model (%d*%d).";
+  const int kch = 64 / t->es;
+  t->D = cfg.embed_dim; t->npw = cfg.img_size / cfg.patch_size; t->np = t->npw * t->npw; t->S = t->np + 1;
+  t->K = 3 * cfg.patch_size * cfg.patch_size; t->Kp = round_up(t->K, 128 / t->es);
+  t->hidv = (int)(cfg.embed_dim * cfg.mlp_ratio); t->heads = cfg.num_heads; t->hd = cfg.embed_dim / cfg.num_heads; t->hdp = round_up(t->hd, kch);
+}
+
+// ================================================================ the step driver of both trainers
+// bad_cfg: the caller's range check of *cfg (false for a null cfg); init: the model's geometry and its entries of TrainerBase
+template <class H, class Cfg>
+int trainer_create(const Cfg* cfg, int dtype, H** out, bool bad_cfg, const char* bad_cfg_msg, void (*init)(H*, const Cfg&)) {
+  if (!cfg || !out) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16 && dtype != FSVIT_BF16X2) return fsvit_set_error(FSVIT_ERR_ARG, "trainer dtype %d (FSVIT_F32 | FSVIT_BF16 | FSVIT_BF16X2)", dtype);
+  if (bad_cfg) return fsvit_set_error(FSVIT_ERR_ARG, "%s", bad_cfg_msg);
+  H* t = new H();
+  t->gdt = dtype == FSVIT_BF16X2 ? 2 : dtype; t->dtype = dtype == FSVIT_BF16X2 ? FSVIT_F32 : dtype; t->es = t->dtype == FSVIT_F32 ? 4 : 2;
+  // the direct weight-gradient launches beside the data-gradient chain (TrainerBase::side_on): on unless FSVIT_WGRAD_SIDE_STREAM=0
+  const char* e = getenv("FSVIT_WGRAD_SIDE_STREAM");
+  t->side_on = e ? e[0] != '0' : true;
+  init(t, *cfg);
+  *out = t;
+  return 0;
+}
+
+void bind_params(TB* t, const fsvit_param* params, int n) {
+  t->P.clear();
+  for (int i = 0; i < n; ++i) t->P[params[i].name] = &params[i];
+}
+
 // Sizing pass: walk forward + backward with dry arenas (no launches) and record both peaks.
-static int size_workspace(TR* t, int n_img, float rate, size_t* save_bytes, size_t* tmp_bytes) {
+int trainer_size_workspace(TB* t, int n_img, float rate, size_t* save_bytes, size_t* tmp_bytes) {
   t->B = n_img; t->dp_rate = rate; t->scales = nullptr;
   t->save = Arena(); t->tmp = Arena();
   t->save.dry = t->tmp.dry = true;
   t->jobs.clear(); t->job_off.clear(); t->pack_bytes = 0; t->pack_base = nullptr; t->job_cursor = 0;
-  int rc = train_forward_impl(t, nullptr, nullptr);
+  int rc = t->forward_walk(t, nullptr, nullptr);
   if (rc) return rc;
   size_t tp = t->tmp.peak;
   t->tmp.off = 0;
-  rc = train_backward_impl(t, nullptr);
+  rc = t->backward_walk(t, nullptr);
   if (rc) return rc;
   if (t->tmp.peak > tp) tp = t->tmp.peak;
-  *save_bytes = align256(t->save.peak + t->pack_bytes + 256 + (size_t)droppath_calls(t, rate, nullptr) * n_img * 4 + 256);
+  *save_bytes = align256(t->save.peak + t->pack_bytes + 256 + (size_t)t->droppath_calls(t, rate, nullptr) * n_img * 4 + 256);
   *tmp_bytes = align256(tp);
   return 0;
 }
 
-extern "C" size_t fsvit_visformer_trainer_workspace_bytes(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
+size_t trainer_workspace_bytes(TB* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
   if (!t || !params || n_img <= 0) return 0;
   bind_params(t, params, n_params);
   size_t sb = 0, tb = 0;
-  if (size_workspace(t, n_img, drop_path_rate, &sb, &tb)) return 0;
+  if (trainer_size_workspace(t, n_img, drop_path_rate, &sb, &tb)) return 0;
   return sb + tb;
 }
 
-extern "C" int fsvit_visformer_train_forward(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img,
-                                             int img_h, int img_w, float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev,
-                                             size_t ws_bytes, void* stream) {
+int trainer_forward(TB* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w, float drop_path_rate,
+                    const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
   if (!t || !params || !x_nchw_dev || !feat_dev || !ws_dev || n_img <= 0) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
-  if (img_h != t->cfg.img_size || img_w != t->cfg.img_size)
-    return fsvit_set_error(FSVIT_ERR_IMG_SIZE, "Input image size (%d*%d) does not match model (%d*%d).", img_h, img_w, t->cfg.img_size, t->cfg.img_size);
-  {   // nn.BatchNorm2d in train mode needs more than one value per channel; the smallest map is the final H3 x H3 one (B = 1 at 80x80 is valid)
-    const int h3 = t->cfg.img_size / 16;
-    if ((long)n_img * h3 * h3 < 2) return fsvit_set_error(FSVIT_ERR_ARG, "Expected more than 1 value per channel when training (BatchNorm)");
-  }
+  if (img_h != t->img_size || img_w != t->img_size) return fsvit_set_error(FSVIT_ERR_IMG_SIZE, t->size_fmt, img_h, img_w, t->img_size, t->img_size);
+  if (t->pre_check) T_TRY(t->pre_check(t, n_img));
   if (drop_path_rate > 0.f && !masks_dev) return fsvit_set_error(FSVIT_ERR_ARG, "DropPath masks required when drop_path_rate > 0");
   bind_params(t, params, n_params);
   size_t sb = 0, tb = 0;
-  T_TRY(size_workspace(t, n_img, drop_path_rate, &sb, &tb));
+  T_TRY(trainer_size_workspace(t, n_img, drop_path_rate, &sb, &tb));
   if (ws_bytes < sb + tb) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace of %zu bytes is too small (need %zu)", ws_bytes, sb + tb);
   t->st = (hipStream_t)stream;
   t->save = Arena(); t->save.base = (unsigned char*)ws_dev; t->save.size = sb;
   t->tmp = Arena(); t->tmp.base = (unsigned char*)ws_dev + sb; t->tmp.size = ws_bytes - sb;
   t->scales = nullptr;
-  if (drop_path_rate > 0.f) {                       // DropPath scale = mask / keep_prob per call (visformer.py:92-96)
+  if (drop_path_rate > 0.f) {                       // DropPath scale = mask / keep_prob per call (visformer.py:92-96; timm DropPath, deit.py:70,76-77)
     std::vector<float> keep;
-    const int ncalls = droppath_calls(t, drop_path_rate, &keep);
+    const int ncalls = t->droppath_calls(t, drop_path_rate, &keep);
     t->scales = (float*)t->save.take((size_t)ncalls * n_img * 4);
     if (!t->scales) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small");
     T_RUN(launch_droppath_scales(masks_dev, t->scales, ncalls, n_img, keep.data(), t->st));
   }
   T_TRY(run_packs(t));                              // every weight pack of this step (forward + data-gradient layouts) in one or two launches
-  const int rc_f = train_forward_impl(t, x_nchw_dev, feat_dev);
+  const int rc_f = t->forward_walk(t, x_nchw_dev, feat_dev);
   t->save_after_forward = t->save.off;
   return rc_f;
 }
 
-extern "C" int fsvit_visformer_train_backward(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
+int trainer_backward(TB* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
   if (!t || !params || !dfeat_dev) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
   if (!t->save.base || t->save.dry) return fsvit_set_error(FSVIT_ERR_ARG, "train_backward called without a preceding train_forward");
   bind_params(t, params, n_params);
@@ -1327,7 +1270,43 @@ extern "C" int fsvit_visformer_train_backward(fsvit_visformer_trainer* t, const 
   t->fin.clear();
   t->side_seq = 0; t->pend.clear();
   for (int& v : t->side_waited) v = -1;
-  return side_drain(t, train_backward_impl(t, dfeat_dev));
+  return side_drain(t, t->backward_walk(t, dfeat_dev));
+}
+
+}  // namespace
+
+// ================================================================ C ABI
+extern "C" int fsvit_visformer_trainer_create(const fsvit_visformer_cfg* cfg, int dtype, fsvit_visformer_trainer** out) {
+  return trainer_create(cfg, dtype, out, false, "", visformer_init);
+}
+extern "C" void fsvit_visformer_trainer_destroy(fsvit_visformer_trainer* t) { delete t; }
+extern "C" size_t fsvit_visformer_trainer_workspace_bytes(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
+  return trainer_workspace_bytes(t, params, n_params, n_img, drop_path_rate);
+}
+extern "C" int fsvit_visformer_train_forward(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img,
+                                             int img_h, int img_w, float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev,
+                                             size_t ws_bytes, void* stream) {
+  return trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
+}
+extern "C" int fsvit_visformer_train_backward(fsvit_visformer_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
+  return trainer_backward(t, params, n_params, dfeat_dev, stream);
+}
+
+extern "C" int fsvit_vit_trainer_create(const fsvit_vit_cfg* cfg, int dtype, fsvit_vit_trainer** out) {
+  const bool bad = cfg && (cfg->embed_dim % cfg->num_heads || cfg->img_size % cfg->patch_size || cfg->embed_dim % 8);
+  return trainer_create(cfg, dtype, out, bad, "bad ViT configuration", vit_init);
+}
+extern "C" void fsvit_vit_trainer_destroy(fsvit_vit_trainer* t) { delete t; }
+extern "C" int fsvit_vit_trainer_droppath_calls(const fsvit_vit_trainer* t, float drop_path_rate) { return t ? vit_droppath_calls(t, drop_path_rate, nullptr) : 0; }
+extern "C" size_t fsvit_vit_trainer_workspace_bytes(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
+  return trainer_workspace_bytes(t, params, n_params, n_img, drop_path_rate);
+}
+extern "C" int fsvit_vit_train_forward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
+                                       float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+  return trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
+}
+extern "C" int fsvit_vit_train_backward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
+  return trainer_backward(t, params, n_params, dfeat_dev, stream);
 }
 
 extern "C" int fsvit_proto_head_backward(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D,

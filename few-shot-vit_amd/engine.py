@@ -246,10 +246,18 @@ class VisformerEngine(_EncoderEngine):
         return c
 
 
-class VisformerTrainer:
-    """Train-mode Visformer (meta-tuning step, train_meta.py:161-177): forward with batch-statistics BN + DropPath
-    and saved activations, backward to all parameter gradients.  Parameters are read from (and running stats are
-    updated in) the caller's own fp32 cuda tensors every call - nothing is packed ahead of time."""
+class _Trainer:
+    """One train-mode encoder handle on one GPU (shared plumbing of the Visformer and ViT trainers): forward with saved activations, backward to
+    all parameter gradients.  Parameters are read from (and running stats are updated in) the caller's own fp32 cuda tensors every call -
+    nothing is packed ahead of time."""
+
+    _fn = {}          # C entry points: create / destroy / workspace_bytes / forward / backward [/ token_grad: the handle takes a token-map gradient]
+
+    def _make_cfg(self, cfg: dict):
+        raise NotImplementedError
+
+    def _out_dim(self, cfg: dict) -> int:
+        raise NotImplementedError
 
     def __init__(self, cfg: dict, numerics: str = None, device=None):
         self.lib = _lib.load()
@@ -262,12 +270,12 @@ class VisformerTrainer:
         log_numerics_once(numerics, type(self).__name__)
         self.device = torch.device(device if device is not None else 'cuda')
         if self.device.type != 'cuda':
-            raise RuntimeError('VisformerTrainer needs a GPU device (no CPU fallback)')
+            raise RuntimeError(f'{type(self).__name__} needs a GPU device (no CPU fallback)')
         self.cfg = dict(cfg)
-        self.out_dim = cfg['embed_dim'] * 2
-        c = VisformerEngine._make_cfg(None, cfg)
+        self.out_dim = self._out_dim(cfg)
+        c = self._make_cfg(cfg)
         h = C.c_void_p()
-        _lib.check(self.lib.fsvit_visformer_trainer_create(C.byref(c), self.dtype, C.byref(h)))
+        _lib.check(getattr(self.lib, self._fn['create'])(C.byref(c), self.dtype, C.byref(h)))
         self.h = h
         self._ws = None
         self._keep = None
@@ -277,23 +285,9 @@ class VisformerTrainer:
         h, self.h = getattr(self, 'h', None), None
         if h:
             try:
-                self.lib.fsvit_visformer_trainer_destroy(h)
+                getattr(self.lib, self._fn['destroy'])(h)
             except Exception:
                 pass
-
-    def set_freeze_bn(self, on: bool):
-        """BatchNorm layers in eval mode inside the step (utils.freeze_bn): the running statistics normalise and are not updated; gamma / beta
-        still receive gradients, dz = gamma * invstd * dy."""
-        _lib.check(self.lib.fsvit_visformer_trainer_set_freeze_bn(self.h, int(bool(on))))
-
-    def n_droppath_calls(self, rate: float) -> int:
-        d = self.cfg['depth']
-        depth = sum(d)
-        n = 0
-        for b in range(depth):
-            if depth > 1 and rate * b / (depth - 1) > 0:
-                n += 1 if b < d[0] else 2
-        return n
 
     @staticmethod
     def _table(tensors: Dict[str, torch.Tensor], grads: Optional[Dict[str, torch.Tensor]]):
@@ -319,7 +313,7 @@ class VisformerTrainer:
         x = x.contiguous().float()
         B = x.shape[0]
         arr, keep = self._table(tensors, None)
-        need = self.lib.fsvit_visformer_trainer_workspace_bytes(self.h, arr, len(tensors), B, float(drop_path_rate))
+        need = getattr(self.lib, self._fn['workspace_bytes'])(self.h, arr, len(tensors), B, float(drop_path_rate))
         if need == 0:
             _lib.check(_lib.ERR_KEY if 'missing' in self.lib.fsvit_last_error().decode() else _lib.ERR_ARG)
         if self._ws is None or self._ws.numel() < need:
@@ -329,11 +323,58 @@ class VisformerTrainer:
         if masks is not None:
             masks = masks.contiguous().float()
         with torch.cuda.device(x.device):
-            _lib.check(self.lib.fsvit_visformer_train_forward(self.h, arr, len(tensors), _ptr(x), B, x.shape[2], x.shape[3],
-                                                              float(drop_path_rate), _ptr(masks), _ptr(feat), _ptr(self._ws),
-                                                              self._ws.numel(), _stream_ptr(x.device)))
+            _lib.check(getattr(self.lib, self._fn['forward'])(self.h, arr, len(tensors), _ptr(x), B, x.shape[2], x.shape[3],
+                                                             float(drop_path_rate), _ptr(masks), _ptr(feat), _ptr(self._ws),
+                                                             self._ws.numel(), _stream_ptr(x.device)))
         self._keep = (x, masks)
         self.generation += 1
+        return feat
+
+    def backward(self, tensors: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], dfeat: torch.Tensor, dtokens: torch.Tensor = None):
+        """Overwrites grads[name] (same shapes as tensors[name]) from dfeat [B,out_dim] (+ dtokens [B,T,out_dim], the gradient of the
+        token map handed out by `tokens`, Visformer only)."""
+        _require_cuda(dfeat)
+        if self._keep is None:
+            raise RuntimeError('fsvit: backward without a pending train-mode forward (the saved activations were already consumed)')
+        if dtokens is not None and 'token_grad' not in self._fn:
+            raise NotImplementedError('fsvit: the ViT trainer returns the cls feature only')
+        dfeat = dfeat.contiguous().float()
+        arr, keep = self._table(tensors, grads)
+        if dtokens is not None:
+            dtokens = dtokens.contiguous().float()
+            _lib.check(getattr(self.lib, self._fn['token_grad'])(self.h, _ptr(dtokens)))
+        with torch.cuda.device(dfeat.device):
+            _lib.check(getattr(self.lib, self._fn['backward'])(self.h, arr, len(tensors), _ptr(dfeat), _stream_ptr(dfeat.device)))
+        self._keep = None
+
+
+class VisformerTrainer(_Trainer):
+    """Train-mode Visformer (meta-tuning step, train_meta.py:161-177): batch-statistics BN + DropPath."""
+    _fn = dict(create='fsvit_visformer_trainer_create', destroy='fsvit_visformer_trainer_destroy', workspace_bytes='fsvit_visformer_trainer_workspace_bytes',
+               forward='fsvit_visformer_train_forward', backward='fsvit_visformer_train_backward', token_grad='fsvit_visformer_train_set_token_grad')
+
+    def _make_cfg(self, cfg):
+        return VisformerEngine._make_cfg(None, cfg)
+
+    def _out_dim(self, cfg):
+        return cfg['embed_dim'] * 2
+
+    def set_freeze_bn(self, on: bool):
+        """BatchNorm layers in eval mode inside the step (utils.freeze_bn): the running statistics normalise and are not updated; gamma / beta
+        still receive gradients, dz = gamma * invstd * dy."""
+        _lib.check(self.lib.fsvit_visformer_trainer_set_freeze_bn(self.h, int(bool(on))))
+
+    def droppath_keep(self, rate: float) -> list:
+        """Keep-probability of every DropPath call with a non-zero rate, in call order (a stage-1 block calls once, an attention block twice;
+        per-block rates linspace(0, rate, depth), visformer.py:312)."""
+        d = self.cfg['depth']
+        return [1.0 - r for b, r in enumerate(torch.linspace(0, rate, sum(d)).tolist()) if r > 0 for _ in range(1 if b < d[0] else 2)]
+
+    def n_droppath_calls(self, rate: float) -> int:
+        return len(self.droppath_keep(rate))
+
+    def forward(self, tensors, x, drop_path_rate=0.0, masks=None):
+        feat = super().forward(tensors, x, drop_path_rate, masks)
         # BatchNorm running statistics were updated in place
         bump_weight_generation(v for k, v in tensors.items() if k.endswith(('running_mean', 'running_var')))
         return feat
@@ -345,91 +386,20 @@ class VisformerTrainer:
             _lib.check(self.lib.fsvit_visformer_train_tokens(self.h, _ptr(out), _stream_ptr(self.device)))
         return out
 
-    def backward(self, tensors: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], dfeat: torch.Tensor, dtokens: torch.Tensor = None):
-        """Overwrites grads[name] (same shapes as tensors[name]) from dfeat [B,out_dim] (+ dtokens [B,T,out_dim], the gradient of the
-        token map handed out by `tokens`)."""
-        _require_cuda(dfeat)
-        if self._keep is None:
-            raise RuntimeError('fsvit: backward without a pending train-mode forward (the saved activations were already consumed)')
-        dfeat = dfeat.contiguous().float()
-        arr, keep = self._table(tensors, grads)
-        if dtokens is not None:
-            dtokens = dtokens.contiguous().float()
-            _lib.check(self.lib.fsvit_visformer_train_set_token_grad(self.h, _ptr(dtokens)))
-        with torch.cuda.device(dfeat.device):
-            _lib.check(self.lib.fsvit_visformer_train_backward(self.h, arr, len(tensors), _ptr(dfeat), _stream_ptr(dfeat.device)))
-        self._keep = None
 
+class VitTrainer(_Trainer):
+    """Train-mode ViT / DeiT (deit.py:61-78, 139-218): LayerNorm row statistics + DropPath - the ViT counterpart of VisformerTrainer."""
+    _fn = dict(create='fsvit_vit_trainer_create', destroy='fsvit_vit_trainer_destroy', workspace_bytes='fsvit_vit_trainer_workspace_bytes',
+               forward='fsvit_vit_train_forward', backward='fsvit_vit_train_backward')
 
-class VitTrainer:
-    """Train-mode ViT / DeiT (deit.py:61-78, 139-218): forward with LayerNorm row statistics + DropPath and saved activations, backward to all
-    parameter gradients - the ViT counterpart of VisformerTrainer, same calling convention."""
+    def _make_cfg(self, cfg):
+        return VitEngine._make_cfg(None, cfg)
 
-    def __init__(self, cfg: dict, numerics: str = None, device=None):
-        self.lib = _lib.load()
-        numerics = numerics or default_numerics()
-        if numerics not in DTYPES:
-            raise ValueError(f'unknown numerics mode {numerics!r} (bf16 | parity)')
-        if DTYPES[numerics] in EVAL_ONLY:
-            raise NotImplementedError(f"fsvit: the {numerics!r} numerics mode is an eval mode; train in 'bf16', 'bf16x2' or 'parity'")
-        self.dtype = DTYPES[numerics]
-        log_numerics_once(numerics, type(self).__name__)
-        self.device = torch.device(device if device is not None else 'cuda')
-        if self.device.type != 'cuda':
-            raise RuntimeError('VitTrainer needs a GPU device (no CPU fallback)')
-        self.cfg = dict(cfg)
-        self.out_dim = cfg['embed_dim']
-        c = VitEngine._make_cfg(None, cfg)
-        h = C.c_void_p()
-        _lib.check(self.lib.fsvit_vit_trainer_create(C.byref(c), self.dtype, C.byref(h)))
-        self.h = h
-        self._ws = None
-        self._keep = None
-        self.generation = 0
-
-    def __del__(self):
-        h, self.h = getattr(self, 'h', None), None
-        if h:
-            try:
-                self.lib.fsvit_vit_trainer_destroy(h)
-            except Exception:
-                pass
+    def _out_dim(self, cfg):
+        return cfg['embed_dim']
 
     def n_droppath_calls(self, rate: float) -> int:
         return int(self.lib.fsvit_vit_trainer_droppath_calls(self.h, float(rate)))
-
-    def forward(self, tensors: Dict[str, torch.Tensor], x: torch.Tensor, drop_path_rate: float = 0.0, masks: Optional[torch.Tensor] = None) -> torch.Tensor:
-        _require_cuda(x)
-        x = x.contiguous().float()
-        B = x.shape[0]
-        arr, keep = VisformerTrainer._table(tensors, None)
-        need = self.lib.fsvit_vit_trainer_workspace_bytes(self.h, arr, len(tensors), B, float(drop_path_rate))
-        if need == 0:
-            _lib.check(_lib.ERR_KEY if 'missing' in self.lib.fsvit_last_error().decode() else _lib.ERR_ARG)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        feat = torch.empty(B, self.out_dim, dtype=torch.float32, device=x.device)
-        if masks is not None:
-            masks = masks.contiguous().float()
-        with torch.cuda.device(x.device):
-            _lib.check(self.lib.fsvit_vit_train_forward(self.h, arr, len(tensors), _ptr(x), B, x.shape[2], x.shape[3], float(drop_path_rate), _ptr(masks),
-                                                        _ptr(feat), _ptr(self._ws), self._ws.numel(), _stream_ptr(x.device)))
-        self._keep = (x, masks)
-        self.generation += 1
-        return feat
-
-    def backward(self, tensors: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], dfeat: torch.Tensor, dtokens=None):
-        _require_cuda(dfeat)
-        if self._keep is None:
-            raise RuntimeError('fsvit: backward without a pending train-mode forward (the saved activations were already consumed)')
-        if dtokens is not None:
-            raise NotImplementedError('fsvit: the ViT trainer returns the cls feature only')
-        dfeat = dfeat.contiguous().float()
-        arr, keep = VisformerTrainer._table(tensors, grads)
-        with torch.cuda.device(dfeat.device):
-            _lib.check(self.lib.fsvit_vit_train_backward(self.h, arr, len(tensors), _ptr(dfeat), _stream_ptr(dfeat.device)))
-        self._keep = None
 
 
 class VitEngine(_EncoderEngine):

@@ -8,6 +8,7 @@ As for the Visformer, the nn.Module tree only owns parameters under the referenc
 import torch
 import torch.nn as nn
 
+from ._host import EngineHost
 from .models import register
 
 
@@ -43,7 +44,9 @@ class _PatchEmbed(nn.Module):
         self.proj = nn.Conv2d(3, embed_dim, kernel_size=patch_size, stride=patch_size)
 
 
-class VisionTransformer(nn.Module):
+class VisionTransformer(EngineHost, nn.Module):
+    _engine_cls, _trainer_cls = 'VitEngine', 'VitTrainer'
+
     def __init__(self, img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4., qkv_bias=True,
                  drop_path_rate=0., ln_eps=1e-6, numerics=None, **unused):
         super().__init__()
@@ -71,30 +74,6 @@ class VisionTransformer(nn.Module):
                 nn.init.constant_(m.bias, 0)
                 nn.init.constant_(m.weight, 1.0)
         self.drop_path_rate = float(drop_path_rate)
-        self._engine = None
-        self._engine_key = None
-        self._trainer = None
-
-    def engine(self):
-        from ..engine import VitEngine
-        dev = self.pos_embed.device
-        if dev.type != 'cuda':
-            raise RuntimeError('fsvit: the encoder lives on %s; the HIP engine needs an MI355X (no CPU fallback)' % dev)
-        from ..engine import weights_fingerprint
-        key = (weights_fingerprint(self), self.numerics, str(dev))
-        if self._engine is None or self._engine_key != key:
-            self._engine = VitEngine(self.cfg, self.state_dict(), numerics=self.numerics, device=dev)
-            self._engine_key = key
-        return self._engine
-
-    def trainer(self):
-        from ..engine import VitTrainer
-        dev = self.pos_embed.device
-        if dev.type != 'cuda':
-            raise RuntimeError('fsvit: the encoder lives on %s; the HIP trainer needs an MI355X (no CPU fallback)' % dev)
-        if self._trainer is None or self._trainer.device != dev:
-            self._trainer = VitTrainer(self.cfg, numerics=self.numerics, device=dev)
-        return self._trainer
 
     def draw_droppath_masks(self, n_img, device):
         """timm DropPath (deit.py:70,76-77): floor(keep_prob + U[0,1)) per sample, drawn per block in forward order (attention branch, then Mlp)."""

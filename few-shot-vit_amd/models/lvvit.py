@@ -8,6 +8,7 @@ built (the 96-channel stem has no weight-gradient kernel yet) and raises NotImpl
 import torch
 import torch.nn as nn
 
+from ._host import EngineHost
 from .models import register
 
 _NO_TRAIN = ('fsvit: LV-ViT (lvvit_micro_80) is built for evaluation only - training, meta-tuning and distillation of this encoder '
@@ -54,7 +55,9 @@ class _ConvBlock(nn.Module):
         self.num_patches = 25
 
 
-class LvVit(nn.Module):
+class LvVit(EngineHost, nn.Module):
+    _engine_cls = 'LvvitEngine'
+
     def __init__(self, img_size=80, embed_dim=384, depth=8, num_heads=6, mlp_ratio=3., stem_channels=96, skip_lam=2., ln_eps=1e-5,
                  numerics=None, return_map=False):
         super().__init__()
@@ -81,19 +84,6 @@ class LvVit(nn.Module):
             elif isinstance(m, nn.LayerNorm):
                 nn.init.constant_(m.bias, 0)
                 nn.init.constant_(m.weight, 1.0)
-        self._engine = None
-        self._engine_key = None
-
-    def engine(self):
-        from ..engine import LvvitEngine, weights_fingerprint
-        dev = self.pos_embed.device
-        if dev.type != 'cuda':
-            raise RuntimeError('fsvit: the encoder lives on %s; the HIP engine needs an MI355X (no CPU fallback)' % dev)
-        key = (weights_fingerprint(self), self.numerics, str(dev))
-        if self._engine is None or self._engine_key != key:
-            self._engine = LvvitEngine(self.cfg, self.state_dict(), numerics=self.numerics, device=dev)
-            self._engine_key = key
-        return self._engine
 
     def trainer(self):
         raise NotImplementedError(_NO_TRAIN)

@@ -12,6 +12,7 @@ import math
 import torch
 import torch.nn as nn
 
+from ._host import EngineHost
 from .models import register
 
 
@@ -79,9 +80,10 @@ class _PatchEmbed(nn.Module):
         self.norm = _BatchNorm(embed_dim)
 
 
-class Visformer(nn.Module):
+class Visformer(EngineHost, nn.Module):
     """Supported family: stem + BatchNorm + attn_stage='011' + spatial_conv='100' (every shipped
     Visformer factory; visformer.py:466-487).  Other combinations raise at construction."""
+    _engine_cls, _trainer_cls, _anchor = 'VisformerEngine', 'VisformerTrainer', 'pos_embed1'
 
     def __init__(self, img_size=80, init_channels=64, embed_dim=256, depth=(4, 2, 3), num_heads=6, mlp_ratio=4.,
                  group=8, drop_path_rate=0., attn_stage='011', spatial_conv='100', numerics=None, return_map=False, **unused):
@@ -115,9 +117,6 @@ class Visformer(nn.Module):
         self.norm = _BatchNorm(embed_dim * 2)
         self._init_weights()
         self.drop_path_rate = float(drop_path_rate)
-        self._engine = None
-        self._engine_key = None
-        self._trainer = None
 
     def _init_weights(self):
         """conv_init=True initialisation of the shipped factories (visformer.py:395-422)."""
@@ -132,48 +131,20 @@ class Visformer(nn.Module):
                 nn.init.constant_(m.weight, 1.0)
                 nn.init.constant_(m.bias, 0.)
 
-    # ------------------------------------------------------------------ engine management
-    def _fingerprint(self):
-        from ..engine import weights_fingerprint
-        return weights_fingerprint(self)
-
-    def engine(self):
-        """Packed HIP engine for the current weights (re-packed when any tensor changed)."""
-        from ..engine import VisformerEngine
-        dev = self.pos_embed1.device
-        if dev.type != 'cuda':
-            raise RuntimeError('fsvit: the encoder lives on %s; the HIP engine needs an MI355X (no CPU fallback)' % dev)
-        key = (self._fingerprint(), self.numerics, str(dev))
-        if self._engine is None or self._engine_key != key:
-            self._engine = VisformerEngine(self.cfg, self.state_dict(), numerics=self.numerics, device=dev)
-            self._engine_key = key
-        return self._engine
-
-    def trainer(self):
-        from ..engine import VisformerTrainer
-        dev = self.pos_embed1.device
-        if dev.type != 'cuda':
-            raise RuntimeError('fsvit: the encoder lives on %s; the HIP trainer needs an MI355X (no CPU fallback)' % dev)
-        if self._trainer is None or self._trainer.device != dev:
-            self._trainer = VisformerTrainer(self.cfg, numerics=self.numerics, device=dev)
-        return self._trainer
-
     def draw_droppath_masks(self, n_img, device):
         """The Bernoulli draws of every DropPath call with a non-zero rate, in call order:
         floor(keep_prob + rand(B)) (visformer.py:93-95)."""
-        n = self.trainer().n_droppath_calls(self.drop_path_rate)
-        if n == 0:
-            return None
-        depth = self.cfg['depth']
+        trainer = self.trainer()
         key = (str(device), self.drop_path_rate)
         if getattr(self, '_keep_key', None) != key:          # keep-probabilities per DropPath call, uploaded once (an upload per step is a stream synchronisation)
-            rates = torch.linspace(0, self.drop_path_rate, sum(depth)).tolist()
-            keep = [1.0 - r for b, r in enumerate(rates) if r > 0 for _ in range(1 if b < depth[0] else 2)]
-            self._keep_dev = torch.tensor(keep, dtype=torch.float32).to(device).unsqueeze(1)
+            keep = trainer.droppath_keep(self.drop_path_rate)        # the trainer's list is the one source of which calls exist
+            self._keep_dev = torch.tensor(keep, dtype=torch.float32).to(device).unsqueeze(1) if keep else None
             self._keep_key = key
+        if self._keep_dev is None:
+            return None
         # floor(keep_prob + rand(B)) of every call from ONE generator launch: the draws are i.i.d. uniforms either way, and the device generator's stream
         # is not the reference's (a CUDA Philox stream cannot be reproduced here); one launch + two in-place passes instead of 16 + 3 (70 us per step)
-        return torch.rand(n, n_img, device=device).add_(self._keep_dev).floor_()
+        return torch.rand(self._keep_dev.shape[0], n_img, device=device).add_(self._keep_dev).floor_()
 
     def forward(self, x, droppath_masks=None):
         """[B,3,img,img] fp32 -> [B,out_dim] pooled features (visformer.py:424-462).
