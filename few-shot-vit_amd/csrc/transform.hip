@@ -140,3 +140,176 @@ extern "C" int fsvit_image_transform_gather(const uint8_t* images_dev, int H, in
   if (rc) return fsvit_set_error(rc, "%s", "fsvit_image_transform_gather: launch failed (image too large for LDS?)");
   return 0;
 }
+
+// ---------------------------------------------------------------- train-time augment 'resize' (sun_train_teacher/datasets/mini_imagenet.py:57-63)
+//   RandomResizedCrop(80) (Pillow crop, then Pillow BILINEAR resize) -> RandomHorizontalFlip -> ToTensor -> Normalize
+// for a gathered batch: the crop box differs per image, so each workgroup builds its own image's tap tables in LDS - the same integers as
+// datasets/transforms.py:pil_bilinear_tables(w, OW) / (h, OH), in fp64 with the same association and NO contraction (an FMA changes
+// int(center - support + 0.5) at scales such as 0.6 or 1.2) - and applies them at the box offset.  The host draws the boxes and flips; nothing else is
+// uploaded per batch.  Taps are clipped to the crop, not to the source image (torchvision crops first, then resizes).
+namespace fsvit {
+
+struct RrcParams {
+  const uint8_t* images;       // [N][H][W][3]
+  const int64_t* index;        // [B]
+  const int32_t* box;          // [B][4] top, left, height, width
+  const uint8_t* flip;         // [B]
+  float* out;                  // [B][3][OH][OW]
+  int H, W, OH, OW, kh, kv;    // kh / kv: table row stride = tap count of the largest box (w = W, h = H)
+  float mean[3], stdv[3];
+};
+
+__host__ __device__ inline int rrc_ksize(int in, int out) { const int c = (in + out - 1) / out; return 2 * (c < 1 ? 1 : c) + 1; }
+
+// One row of pil_bilinear_tables(in, out): first input index, tap count, 22-bit taps.  Every double operation is one IEEE operation, in Python's order.
+__device__ void rrc_table_row(int in, int out, int o, int stride, int32_t* xmin, int32_t* cnt, int32_t* coef) {
+#pragma clang fp contract(off)
+  const double scale = (double)in / (double)out;
+  const double support = scale > 1.0 ? scale : 1.0;
+  const double inv = 1.0 / support;
+  const double center = ((double)o + 0.5) * scale;
+  int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > in ? in : hi;
+  int n = hi - lo;
+  n = n < 0 ? 0 : (n > stride ? stride : n);             // never taken for Pillow's tables (hi - lo <= ksize); keeps the row inside its LDS slot
+  double total = 0.0;
+  for (int x = lo; x < lo + n; ++x) {
+    const double a = fabs(((double)x - center + 0.5) * inv);
+    total += a < 1.0 ? 1.0 - a : 0.0;
+  }
+  for (int j = 0; j < n; ++j) {
+    const double a = fabs(((double)(lo + j) - center + 0.5) * inv);
+    double w = a < 1.0 ? 1.0 - a : 0.0;
+    if (total != 0.0) w = w / total;
+    const double v = w * (double)(1 << 22);
+    coef[(size_t)o * stride + j] = w < 0.0 ? (int)(v - 0.5) : (int)(v + 0.5);
+  }
+  xmin[o] = lo;
+  cnt[o] = n;
+}
+
+__global__ __launch_bounds__(256) void transform_rrc_gather_kernel(RrcParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int PB = 22;
+  constexpr int KMAX = 6;                                // taps kept in registers: covers every box up to 2.5 x the output size
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int rowb = p.W * 3, hrow = p.OW * 3;
+  // the box, clamped to the image: no box can read outside its image
+  int bi = p.box[4 * b], bj = p.box[4 * b + 1], bh = p.box[4 * b + 2], bw = p.box[4 * b + 3];
+  bi = bi < 0 ? 0 : (bi > p.H - 1 ? p.H - 1 : bi);
+  bj = bj < 0 ? 0 : (bj > p.W - 1 ? p.W - 1 : bj);
+  bh = bh < 1 ? 1 : (bh > p.H - bi ? p.H - bi : bh);
+  bw = bw < 1 ? 1 : (bw > p.W - bj ? p.W - bj : bw);
+  const bool flip = p.flip[b] != 0;
+  // LDS: the box's rows (full width, at the global address's 16-byte phase) | horizontal pass | Normalize table | tap tables
+  const size_t raw_pad = (((size_t)p.H * rowb + 15) & ~(size_t)15) + 16, hp_pad = ((size_t)p.H * hrow + 15) & ~(size_t)15;
+  float* lut = reinterpret_cast<float*>(smem + raw_pad + hp_pad);      // [3][256]
+  int32_t* xmin_h = reinterpret_cast<int32_t*>(lut + 768);
+  int32_t* cnt_h = xmin_h + p.OW;
+  int32_t* coef_h = cnt_h + p.OW;                         // [OW][kh]
+  int32_t* xmin_v = coef_h + (size_t)p.OW * p.kh;
+  int32_t* cnt_v = xmin_v + p.OH;
+  int32_t* coef_v = cnt_v + p.OH;                         // [OH][kv]
+  const uint8_t* src = p.images + (size_t)p.index[b] * p.H * rowb + (size_t)bi * rowb;
+  const int nbytes = bh * rowb;
+  const int mis = (int)(((uintptr_t)src) & 15);
+  unsigned char* raw = smem + mis;                        // [bh][W][3]
+  unsigned char* hp = smem + raw_pad;                     // [bh][OW][3]
+  {
+    int head = (16 - mis) & 15;
+    head = head > nbytes ? nbytes : head;
+    const int body = (nbytes - head) >> 4, tail0 = head + (body << 4);
+    const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
+    uint4* d4 = reinterpret_cast<uint4*>(raw + head);
+    for (int i = t; i < body; i += 256) d4[i] = s4[i];
+    if (t < head) raw[t] = src[t];
+    if (tail0 + t < nbytes) raw[tail0 + t] = src[tail0 + t];           // < 16 bytes
+  }
+  for (int i = t; i < 768; i += 256) {
+    const int c = i >> 8;
+    const float v = (float)(i & 255) / 255.0f;                        // ToTensor
+    lut[i] = (v - p.mean[c]) / p.stdv[c];                              // Normalize (IEEE division, as torch does)
+  }
+  for (int o = t; o < p.OW + p.OH; o += 256) {
+    if (o < p.OW) rrc_table_row(bw, p.OW, o, p.kh, xmin_h, cnt_h, coef_h);
+    else rrc_table_row(bh, p.OH, o - p.OW, p.kv, xmin_v, cnt_v, coef_v);
+  }
+  __syncthreads();
+  // horizontal pass over the box's rows: thread = (output column x, channel c)
+  for (int pc = t; pc < hrow; pc += 256) {
+    const int x = pc / 3, c = pc - 3 * x;
+    const int n = cnt_h[x];
+    const int32_t* k = coef_h + (size_t)x * p.kh;
+    const unsigned char* rp = raw + (bj + xmin_h[x]) * 3 + c;
+    unsigned char* op = hp + pc;
+    if (n <= KMAX) {
+      int kr[KMAX];
+#pragma unroll
+      for (int j = 0; j < KMAX; ++j) kr[j] = j < n ? k[j] : 0;
+      for (int r = 0; r < bh; ++r, rp += rowb, op += hrow) {
+        int acc = 1 << (PB - 1);
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j)
+          if (j < n) acc += (int)rp[3 * j] * kr[j];
+        *op = (unsigned char)clip8(acc >> PB);
+      }
+    } else {
+      for (int r = 0; r < bh; ++r, rp += rowb, op += hrow) {
+        int acc = 1 << (PB - 1);
+        for (int j = 0; j < n; ++j) acc += (int)rp[3 * j] * k[j];
+        *op = (unsigned char)clip8(acc >> PB);
+      }
+    }
+  }
+  __syncthreads();
+  // vertical pass + flip + ToTensor + Normalize, NCHW fp32: thread = (channel c, output column x), x fastest (coalesced stores); a flipped image reads
+  // the mirrored column of the resized image (the flip follows the resize in the reference's transform order)
+  float* out = p.out + (size_t)b * 3 * p.OH * p.OW;
+  for (int pc = t; pc < 3 * p.OW; pc += 256) {
+    const int c = pc / p.OW, x = pc - c * p.OW;
+    const unsigned char* hb = hp + (flip ? p.OW - 1 - x : x) * 3 + c;
+    const float* lc = lut + 256 * c;
+    float* oc = out + (size_t)c * p.OH * p.OW + x;
+    for (int y = 0; y < p.OH; ++y) {
+      const int n = cnt_v[y];
+      const int32_t* k = coef_v + (size_t)y * p.kv;
+      const unsigned char* hr = hb + xmin_v[y] * hrow;
+      int acc = 1 << (PB - 1);
+      for (int j = 0; j < n; ++j) acc += (int)hr[j * hrow] * k[j];
+      oc[(size_t)y * p.OW] = lc[clip8(acc >> PB)];
+    }
+  }
+}
+
+int launch_transform_rrc_gather(const RrcParams& p, int B, hipStream_t s) {
+  if (B <= 0) return 0;
+  const size_t lds = (((size_t)p.H * p.W * 3 + 15) & ~(size_t)15) + 16 + (((size_t)p.H * p.OW * 3 + 15) & ~(size_t)15) + 768 * sizeof(float) +
+                     ((size_t)p.OW * (2 + p.kh) + (size_t)p.OH * (2 + p.kv)) * sizeof(int32_t);
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void*)transform_rrc_gather_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(transform_rrc_gather_kernel, dim3(B), dim3(256), lds, s, p);
+  return (int)hipGetLastError();
+}
+
+}  // namespace fsvit
+
+extern "C" int fsvit_image_transform_rrc_gather(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
+                                                const uint8_t* flip_dev, int OH, int OW, const float* mean3_host, const float* std3_host,
+                                                float* out_dev, void* stream) {
+  if (!images_dev || !index_dev || !box_dev || !flip_dev || !mean3_host || !std3_host || !out_dev)
+    return fsvit_set_error(-1, "%s", "fsvit_image_transform_rrc_gather: null argument");
+  if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || B < 0)
+    return fsvit_set_error(-1, "%s", "fsvit_image_transform_rrc_gather: bad geometry");
+  fsvit::RrcParams p;
+  p.images = images_dev; p.index = index_dev; p.box = box_dev; p.flip = flip_dev; p.out = out_dev;
+  p.H = H; p.W = W; p.OH = OH; p.OW = OW;
+  p.kh = fsvit::rrc_ksize(W, OW); p.kv = fsvit::rrc_ksize(H, OH);
+  for (int c = 0; c < 3; ++c) { p.mean[c] = mean3_host[c]; p.stdv[c] = std3_host[c]; }
+  int rc = fsvit::launch_transform_rrc_gather(p, B, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "%s", "fsvit_image_transform_rrc_gather: launch failed (image too large for LDS?)");
+  return 0;
+}

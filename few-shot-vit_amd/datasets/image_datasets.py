@@ -2,7 +2,10 @@
 (test_phase/datasets/mini_imagenet.py:27-44, tiered_imagenet.py:13-50), MI355X-first: the whole split is uploaded ONCE as a
 uint8 [N,84,84,3] tensor (mini test split 254 MB; all 60 000 images 1.27 GB of the 288 GB) and episodes are gathered +
 transformed on the GPU by index (`gather`, fsvit_image_transform_gather) instead of 8 DataLoader workers running PIL.
-Only the eval transform (`augment=None`) is built; the train-time augmentations of the supervised phase are out of scope."""
+`self.transform` is what `gather` / `__getitem__` apply.  `augment=None` is the eval transform.  `augment='resize'` is the supervised phase's
+train-time augmentation (sun_train_teacher/datasets/mini_imagenet.py:50-63, tiered_imagenet.py:68-81): RandomResizedCrop(80) +
+RandomHorizontalFlip on the GPU (fsvit_image_transform_rrc_gather), with `default_transform` = that phase's Resize(80) + ToTensor +
+Normalize; `ds.transform = ds.default_transform` switches the augmentation off.  `'crop'` (padded RandomCrop) and `'cropaug'` (timm) are not built."""
 import os
 import pickle
 
@@ -10,13 +13,13 @@ import numpy as np
 import torch
 
 from .datasets import register
-from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceTransform
+from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandomResizedCrop, DeviceTransform
 
 
 class _DeviceImageDataset:
     resize, crop = (88, 88), 80
 
-    def _finish(self, data: np.ndarray, label, device):
+    def _finish(self, data: np.ndarray, label, device, augment=None):
         if data.dtype != np.uint8 or data.ndim != 4 or data.shape[-1] != 3:
             raise ValueError('expected uint8 images [N,H,W,3]')
         min_label = min(label)
@@ -25,7 +28,12 @@ class _DeviceImageDataset:
         self.device = torch.device(device if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu'))
         self.images = torch.from_numpy(np.ascontiguousarray(data))
         self._on_device = None
-        self._transform = None
+        in_hw, norm = tuple(self.images.shape[1:3]), dict(mean=getattr(self, 'mean', IMAGENET_MEAN), std=getattr(self, 'std', IMAGENET_STD))
+        if augment == 'resize':
+            self.default_transform = DeviceTransform(in_hw, (self.crop, self.crop), self.crop, self.device, **norm)     # Resize(80)
+            self.transform = DeviceRandomResizedCrop(in_hw, self.crop, self.device, **norm)
+        else:
+            self.default_transform = self.transform = DeviceTransform(in_hw, self.resize, self.crop, self.device, **norm)
 
     def __len__(self):
         return len(self.label)
@@ -35,14 +43,12 @@ class _DeviceImageDataset:
             if self.device.type != 'cuda':
                 raise RuntimeError('fsvit: the dataset transform runs on an MI355X (no CPU fallback)')
             self._on_device = self.images.to(self.device)
-            self._transform = DeviceTransform(tuple(self.images.shape[1:3]), self.resize, self.crop, self.device,
-                                              mean=getattr(self, 'mean', IMAGENET_MEAN), std=getattr(self, 'std', IMAGENET_STD))
         return self._on_device
 
     def gather(self, index) -> torch.Tensor:
         """index: LongTensor of dataset indices (one sampler batch) -> float32 [len, 3, 80, 80] on the GPU."""
         imgs = self.device_images()
-        return self._transform(imgs, torch.as_tensor(index))
+        return self.transform(imgs, torch.as_tensor(index))
 
     def __getitem__(self, i):
         return self.gather(torch.tensor([int(i)]))[0], self.label[i]
@@ -53,12 +59,12 @@ class MiniImageNet(_DeviceImageDataset):
     resize, crop = (88, 88), 80                         # Resize((88, 88)) -> CenterCrop(80), mini_imagenet.py:49-52
 
     def __init__(self, root_path, split='train', augment=None, device=None, **kwargs):
-        if augment is not None:
-            raise NotImplementedError('fsvit: only the eval transform (augment=None) is built')
+        if augment not in (None, 'resize'):
+            raise NotImplementedError("fsvit: augment=None and 'resize' are built ('crop' / 'cropaug' are not)")
         split_tag = 'train_phase_train' if split == 'train' else split
         with open(os.path.join(root_path, 'miniImageNet_category_split_{}.pickle'.format(split_tag)), 'rb') as f:
             pack = pickle.load(f, encoding='latin1')
-        self._finish(np.asarray(pack['data']), pack['labels'], device)
+        self._finish(np.asarray(pack['data']), pack['labels'], device, augment)
 
 
 @register('tiered-imagenet')
@@ -66,8 +72,8 @@ class TieredImageNet(_DeviceImageDataset):
     resize, crop = (80, 80), 80                         # Resize(80) on square images, tiered_imagenet.py:53-57
 
     def __init__(self, root_path, split='train', mini=False, augment=None, device=None, **kwargs):
-        if augment is not None:
-            raise NotImplementedError('fsvit: only the eval transform (augment=None) is built')
+        if augment not in (None, 'test', 'resize'):                     # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
+            raise NotImplementedError("fsvit: augment=None, 'test' and 'resize' are built ('crop' / 'cropaug' are not)")
         data = np.load(os.path.join(root_path, '{}_images.npz'.format(split)), allow_pickle=True)['images']
         data = data[:, :, :, ::-1]                      # BGR -> RGB, tiered_imagenet.py:21
         with open(os.path.join(root_path, '{}_labels.pkl'.format(split)), 'rb') as f:
@@ -87,4 +93,4 @@ class TieredImageNet(_DeviceImageDataset):
                     label_.append(ind[y])
                     cnt[y] += 1
             data, label = data[keep], label_
-        self._finish(np.ascontiguousarray(data), label, device)
+        self._finish(np.ascontiguousarray(data), label, device, augment)

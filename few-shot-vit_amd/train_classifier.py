@@ -6,8 +6,9 @@ with linear warm-up stepped with (epoch - 1) (:121-123,:195-196); per epoch a su
 reference's schema.  The teacher of the distillation phase (`offline.py`, key `load`) is a checkpoint of this driver.
 
 MI355X-native: encoder forward / backward on the HIP trainer, Linear head, AdamW update and the few-shot evaluation on the HIP engine;
-multi-GPU = one process per GPU with one gradient all-reduce per step and rank-sharded few-shot episodes.  Not restated: tensorboard,
-dataset visualisation, train-time augmentation.
+multi-GPU = one process per GPU with one gradient all-reduce per step and rank-sharded few-shot episodes.  `train_dataset_args: {augment: resize}`
+(RandomResizedCrop + RandomHorizontalFlip, the reference's train_classifier_mini / _tiered configs) runs on the GPU, seeded with `seed` + rank.
+Not restated: tensorboard, dataset visualisation, the `cropaug` (timm) and `crop` augmentations.
 
   python -m fewshot_vit_amd.train_classifier --config few-shot-vit_amd/configs/train_classifier_synthetic.yaml
 """
@@ -27,6 +28,8 @@ from .utils.schedulers import CosineLRScheduler
 
 
 def _gather(dataset, idx, device):
+    if hasattr(dataset, 'gather'):                                                           # device-resident datasets: one launch per batch
+        return dataset.gather(idx).to(device, non_blocking=True), torch.tensor([int(dataset.label[int(i)]) for i in idx], device=device)
     items = [dataset[int(i)] for i in idx]
     return torch.stack([it[0] for it in items]).to(device, non_blocking=True), torch.tensor([int(it[-1]) for it in items], device=device)
 
@@ -56,6 +59,8 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
         for n_shot in n_shots:
             fs_samplers.append(CategoriesSampler(fs_dataset.label, config.get('fs_batches', 200), 5, n_shot + 15, ep_per_batch=4, rank=rank,
                                                  world_size=world, shard=parallel.sampler_shard(world)))
+    if hasattr(getattr(train_dataset, 'transform', None), 'manual_seed'):                    # ranks draw different boxes; a run is repeatable
+        train_dataset.transform.manual_seed(config.get('seed', 0) + rank)
     if rank == 0:
         log('train dataset: {} (x{}), {}'.format(tuple(train_dataset[0][0].shape), len(train_dataset), train_dataset.n_classes))
 
@@ -90,7 +95,7 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     for epoch in range(1, max_epoch + 1 + 1):
         if epoch == max_epoch + 1:
             # `epoch_ex` (sun_train_teacher/train_classifier.py:141-148): ONE extra epoch over the training set under its default
-            # (un-augmented) transform.  The datasets here only have that transform, so the switch itself is a no-op.
+            # (un-augmented) transform.  A no-op for datasets built without `augment`.
             if not config.get('epoch_ex'):
                 break
             if hasattr(train_dataset, 'default_transform'):

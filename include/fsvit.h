@@ -395,6 +395,16 @@ int fsvit_image_transform_gather(const uint8_t* images_dev, int H, int W, const 
                                  const int32_t* cnt_h_dev, const int32_t* coef_h_dev, int ksize_h, const int32_t* xmin_v_dev,
                                  const int32_t* cnt_v_dev, const int32_t* coef_v_dev, int ksize_v, int crop_y0, int crop_x0, int OH, int OW,
                                  const float* mean3_host, const float* std3_host, float* out_dev, void* stream);
+/* The train-time augmentation `augment: resize` of the supervised phase (sun_train_teacher/datasets/mini_imagenet.py:57-63,
+ * tiered_imagenet.py:75-81) for a gathered batch: RandomResizedCrop(OH) -> RandomHorizontalFlip -> ToTensor -> Normalize.  The caller draws
+ * the randomness: box_dev int32 [B][4] = top i, left j, height h, width w of each image's crop, flip_dev uint8 [B] (non-zero = mirror the
+ * output columns; the flip acts on the resized image).  The crop is resized to OH x OW with Pillow's BILINEAR arithmetic, bit-exact with
+ * Image.crop(box).resize(...): each workgroup computes its box's coefficient tables itself (fp64, the integers of
+ * datasets/transforms.py:pil_bilinear_tables(w, OW) and (h, OH), taps clipped to the crop), so nothing but index, boxes and flips is uploaded
+ * per batch.  A box is clamped to the image on the device; callers validate it.  mean3 / std3 are HOST pointers to 3 floats. */
+int fsvit_image_transform_rrc_gather(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
+                                     const uint8_t* flip_dev, int OH, int OW, const float* mean3_host, const float* std3_host,
+                                     float* out_dev, void* stream);
 
 /* Operator level of the training path: attention backward (qkv, dctx -> dqkv; hd real / hdp padded head dim). */
 /* Weight gradient of a 3x3 / stride 1 / pad 1 convolution straight from the NHWC activations (no im2col, no transposed copies):
