@@ -263,6 +263,19 @@ __device__ __forceinline__ void x2_split(const u32x4 v, u32x4& s, u32x4& r) {
   }
 }
 
+// ---- host side: one element-type dispatch and one launch helper for the launchers.  `dtype` 0 = fp32, anything else = this build's 16-bit type:
+//   return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>; return launch(some_kernel<T>, grid, 256, 0, s, (const T*)x, (T*)y, n); });
+// launch() passes the arguments on with the kernel's own parameter types (a nullptr or an int literal needs no cast) and returns the launch error.
+template <typename T> struct elem_tag { using type = T; };
+template <typename E> using elem_t = typename E::type;
+template <typename F> inline int with_elem(int dtype, F&& f) { return dtype == 0 ? f(elem_tag<float>{}) : f(elem_tag<bf16>{}); }
+template <typename... KA, typename... A>
+inline int launch(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t s, A... a) {
+  hipLaunchKernelGGL(k, grid, block, lds, s, static_cast<KA>(a)...);
+  return (int)hipGetLastError();
+}
+inline int vec_width(int dtype) { return dtype == 0 ? 4 : 8; }      // elements of a 16-byte access (Elem<T>::kPerChunk of the type `dtype` names)
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -30,10 +30,7 @@ __global__ __launch_bounds__(256) void pool_affine_kernel(const T* __restrict__ 
 
 int launch_pool_affine(const void* x, const float* scale, const float* shift, float* feat, int B, int HW, int C, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
-  dim3 grid(B), block(256);
-  if (dtype == 0) hipLaunchKernelGGL(pool_affine_kernel<float>, grid, block, 0, s, (const float*)x, scale, shift, feat, HW, C);
-  else hipLaunchKernelGGL(pool_affine_kernel<bf16>, grid, block, 0, s, (const bf16*)x, scale, shift, feat, HW, C);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(pool_affine_kernel<elem_t<decltype(e)>>, B, 256, 0, s, x, scale, shift, feat, HW, C); });
 }
 
 // method: 0 = 'cos' (normalise both, dot), 1 = 'sqr' (negative squared distance to the mean prototype),

@@ -100,11 +100,11 @@ int launch_final_ln_cls(const void* tokens, const float* gamma, const float* bet
 // direct 3x3 / s1 / p1 weight gradient from NHWC activations (wgrad3x3.hip; dtype 1 = 16-bit storage, 2 = fp32 storage with two-limb arithmetic): dw [O][Ig][3][3] fp32 overwritten
 bool wgrad3x3_supported(int dtype, int O, int Ig, int groups, int W);
 size_t wgrad3x3_scratch_bytes(int O, int Ig, int groups, int M, int dtype = 1);
-// 1x1: Y[n][split * Kc_pad + c] split-K partials for wgrad_finalize_kernel (splits = wgrad1x1_splits)
+// 1x1: Y[n][split * Kc_pad + c] split-K partials for wgrad_finalize_multi_kernel (splits = wgrad1x1_splits)
 bool wgrad1x1_supported(int dtype, int N, int C);
 int wgrad1x1_splits(int N, int C, int M, int dtype = 1);
 int launch_wgrad1x1(const void* x, int xld, int C, const void* dz, int zld, int N, float* y, int M, int Kc_pad, hipStream_t s, int dtype = 1);   // dtype 2: fp32 rows, two-limb arithmetic
-// the grouped 3x3 conv itself (8 groups of 32 -> 32, 16-bit storage); w_packed = [256][Kw] rows (ky, kx, c) as launch_pack_weight writes them
+// the grouped 3x3 conv itself (8 groups of 32 -> 32, 16-bit storage); w_packed = [256][Kw] rows (ky, kx, c) as launch_pack_weight_multi writes them
 bool gconv3x3_supported(int dtype, int O, int Ig, int groups, int KH, int KW, int stride, int pad, int W);
 int launch_gconv3x3(const void* x, const void* w_packed, int Kw, void* y, int B, int H, int W, hipStream_t s, void* y2 = nullptr, const void* mul = nullptr);
 int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, float* scratch, int B, int H, int W, int O, int Ig, int groups, hipStream_t s,

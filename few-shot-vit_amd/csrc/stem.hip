@@ -154,10 +154,7 @@ int launch_stem_conv1(const float* x, void* patches, void* c1, const void* w, in
 int launch_im2col27(const float* x, void* out, int B, int H, int W, int OH, int OW, int dtype, hipStream_t s) {
   const int M = B * OH * OW;
   if (M <= 0) return 0;
-  dim3 grid((M + 255) / 256), block(256);
-  if (dtype == 0) hipLaunchKernelGGL(im2col27_kernel<float>, grid, block, 0, s, x, (float*)out, B, H, W, OH, OW);
-  else hipLaunchKernelGGL(im2col27_kernel<bf16>, grid, block, 0, s, x, (bf16*)out, B, H, W, OH, OW);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(im2col27_kernel<elem_t<decltype(e)>>, (M + 255) / 256, 256, 0, s, x, out, B, H, W, OH, OW); });
 }
 
 int launch_maxpool2_pos(const void* in, const float* pos, void* out, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
@@ -165,10 +162,7 @@ int launch_maxpool2_pos(const void* in, const float* pos, void* out, int B, int 
   if (total == 0) return 0;
   size_t nb = (total + 255) / 256;
   if (nb > 8192) nb = 8192;
-  dim3 grid((unsigned)nb), block(256);
-  if (dtype == 0) hipLaunchKernelGGL(maxpool2_pos_kernel<float>, grid, block, 0, s, (const float*)in, pos, (float*)out, B, OH, OW, C);
-  else hipLaunchKernelGGL(maxpool2_pos_kernel<bf16>, grid, block, 0, s, (const bf16*)in, pos, (bf16*)out, B, OH, OW, C);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(maxpool2_pos_kernel<elem_t<decltype(e)>>, (unsigned)nb, 256, 0, s, in, pos, out, B, OH, OW, C); });
 }
 
 }  // namespace FSVIT_NS

@@ -270,16 +270,12 @@ __global__ void add_f32_into_kernel(T* __restrict__ inout, const float* __restri
 int launch_tokens_to_f32(const void* in, const float* scale, const float* shift, float* out, size_t n, int C, int dtype, hipStream_t s) {
   if (n == 0) return 0;
   const unsigned g = (unsigned)((n + 255) / 256);
-  if (dtype == 0) hipLaunchKernelGGL(tokens_to_f32_kernel<float>, dim3(g), dim3(256), 0, s, (const float*)in, scale, shift, out, n, C);
-  else hipLaunchKernelGGL(tokens_to_f32_kernel<bf16>, dim3(g), dim3(256), 0, s, (const bf16*)in, scale, shift, out, n, C);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(tokens_to_f32_kernel<elem_t<decltype(e)>>, g, 256, 0, s, in, scale, shift, out, n, C); });
 }
 int launch_add_f32_into(void* inout, const float* add, size_t n, int dtype, hipStream_t s) {
   if (n == 0) return 0;
   const unsigned g = (unsigned)((n + 255) / 256);
-  if (dtype == 0) hipLaunchKernelGGL(add_f32_into_kernel<float>, dim3(g), dim3(256), 0, s, (float*)inout, add, n);
-  else hipLaunchKernelGGL(add_f32_into_kernel<bf16>, dim3(g), dim3(256), 0, s, (bf16*)inout, add, n);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(add_f32_into_kernel<elem_t<decltype(e)>>, g, 256, 0, s, inout, add, n); });
 }
 
 int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s) {

@@ -182,7 +182,9 @@ ConvGemmParams gemm_params(const void* x, const void* w, void* y, int B, int H, 
   return p;
 }
 
-// packed weights of one layer: recorded in the sizing pass, served from the batch in the real pass (fallback: packed here and now)
+// packed weights of one layer: recorded in the sizing pass, served from the batch in the real pass.  Every train_forward runs its own sizing pass over
+// forward + backward with the table it was given, so the walks ask for the recorded packs in the recorded order; only a backward that does not belong
+// to that forward (a second one, or one with other weight tensors) can miss - an error, the workspace holds no room for a pack of its own.
 int packed_weight(TB* t, const PackJob& job, size_t bytes, void** out) {
   if (t->tmp.dry) {
     t->jobs.push_back(job);
@@ -198,12 +200,7 @@ int packed_weight(TB* t, const PackJob& job, size_t bytes, void** out) {
       return 0;
     }
   }
-  void* pk = t->tmp.take(bytes);
-  if (!pk) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (weights)");
-  T_RUN(launch_pack_weight(job.w, pk, job.O, job.Ig, job.KH, job.KW, job.groups, job.mode, job.rows_pad, job.Kw, job.hd_rows, job.hdp_rows, job.hd_cols, job.hdp_cols,
-                           t->gdt, t->st));
-  *out = pk;
-  return 0;
+  return fsvit_set_error(FSVIT_ERR_ARG, "weight pack not recorded by the preceding train_forward (one train_backward per train_forward, same parameter tensors)");
 }
 // runs every recorded pack (call after the sizing pass, with the real arenas in place)
 int run_packs(TB* t) {

@@ -5,25 +5,22 @@
 
 namespace fsvit {
 
-// one job of the batched weight pack (same meaning as launch_pack_weight's arguments); `out` is the packed destination
+// one job of the batched weight pack (the fields: pack_weight_multi_kernel in train_kernels.hip); `out` is the packed destination
 struct PackJob { const float* w; void* out; int O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols; };
 struct PackJobs { static constexpr int MAX = 40; PackJob job[MAX]; };
 int launch_pack_weight_multi(const PackJob* jobs, int n, int dtype, hipStream_t s);
-int launch_pack_weight(const float* w, void* out, int O, int Ig, int KH, int KW, int groups, int mode, int rows_pad, int Kw, int hd_rows, int hdp_rows,
-                       int hd_cols, int hdp_cols, int dtype, hipStream_t s);
 // Deferred split-slab finalizes of a whole backward pass in one or two launches (the 38 per-layer finalize launches of a step were 10 .. 25 us
-// of latency each): kind 0 = wgrad_finalize_kernel, 1 = its 1x1 fast path, 2 = dense grouped, 3 = wgrad3x3_finalize_kernel (a = grouped flag,
-// b = njobs); the job table travels as a kernel argument, blockIdx.y = job
+// of latency each): kind 0 = split-K slabs of one group, 1 = its 1x1 fast path, 2 = dense grouped (g = groups), 3 = the direct 3x3 kernels' partials
+// (g = grouped flag, Kc_pad = njobs) - wgrad_finalize_multi_kernel; the job table travels as a kernel argument, blockIdx.y = job
 struct FinJob { const float* y; float* dw; int kind, Ng, Ig, KH, KW, g, splits, Kc_pad, hd_rows, hdp_rows, hd_cols, hdp_cols; };
 struct FinJobs { static constexpr int MAX = 48; FinJob job[MAX]; };
 int launch_wgrad_finalize_multi(const FinJob* jobs, int n, hipStream_t s);
 // DropPath scales of all calls of a step in one launch: scales[k][b] = masks[k][b] / keep[k]
 struct DropKeep { static constexpr int MAX = 64; float inv[MAX]; };
 int launch_droppath_scales(const float* masks, float* scales, int ncalls, int n_img, const float* keep, hipStream_t s);
+// one layer's finalize on its own: a one-job table (kind 1 where the layer allows the 16-byte form, else kind 0)
 int launch_wgrad_finalize(const float* y, float* dw, int Ng, int Ig, int KH, int KW, int g, int splits, int Kc_pad, int hd_rows, int hdp_rows, int hd_cols,
                           int hdp_cols, hipStream_t s);
-// grouped conv via one dense GEMM: keeps the diagonal (same-group) blocks
-int launch_wgrad_finalize_dense(const float* y, float* dw, int Ng, int Ig, int KH, int KW, int groups, int splits, int Kc_pad, hipStream_t s);
 int launch_transpose_cols(const void* in, void* out, int M, int ld, int c0, int ncols, int Mpad, int dtype, hipStream_t s);
 int launch_im2col_t(const void* x, void* out, int B, int H, int W, int ld, int c0, int C, int KH, int KW, int stride, int pad, int OH, int OW, int Mpad,
                     int dtype, hipStream_t s);

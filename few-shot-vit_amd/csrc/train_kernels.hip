@@ -60,46 +60,8 @@ __device__ __forceinline__ float frag_image_elem(const float* __restrict__ w, in
   }
   return w[(size_t)row * rs + (size_t)k * ks];
 }
-template <typename T>
-__global__ __launch_bounds__(256) void pack_weight_kernel(const float* __restrict__ w, T* __restrict__ out, int O, int Ig, int KH, int KW,
-                                                          int groups, int mode, int rows_pad, int Kw, int hd_rows, int hdp_rows,
-                                                          int hd_cols, int hdp_cols) {
-  const int Ng = O / groups;
-  const size_t total = (size_t)groups * rows_pad * Kw;
-  GS_LOOP(idx, total) {
-    const int k = (int)(idx % Kw);
-    const size_t t2 = idx / Kw;
-    const int r = (int)(t2 % rows_pad), g = (int)(t2 / rows_pad);
-    float v = 0.0f;
-    if (mode >= 3) { out[idx] = from_f32<T>(frag_image_elem(w, mode, idx, rows_pad, Kw, O, Ig)); continue; }
-    if (mode == 2) {
-      if (r < KH * KW * Ig && k < Ng) {
-        const int tap = r / Ig, ch = r % Ig;
-        v = w[(((size_t)(g * Ng + k) * Ig + ch) * KH + tap / KW) * KW + tap % KW];
-      }
-      out[idx] = from_f32<T>(v);
-      continue;
-    }
-    const int nin = mode == 0 ? Ig : Ng;            // channels per tap in the K dimension
-    // undo the head padding of the K (column) dimension: only for 1x1 layers
-    int kk = k;
-    bool ok = true;
-    if (hdp_cols != hd_cols) { const int y = k / hdp_cols, zz = k % hdp_cols; ok = zz < hd_cols; kk = y * hd_cols + zz; }
-    int rr = r;
-    if (hdp_rows != hd_rows) { const int y = r / hdp_rows, zz = r % hdp_rows; ok = ok && zz < hd_rows; rr = y * hd_rows + zz; }
-    const int nrows = mode == 0 ? Ng : Ig;
-    if (ok && rr < nrows && kk < KH * KW * nin) {
-      const int tap = kk / nin, ch = kk % nin;
-      const int ky = tap / KW, kx = tap % KW;
-      if (mode == 0) v = w[(((size_t)(g * Ng + rr) * Ig + ch) * KH + ky) * KW + kx];
-      else v = w[(((size_t)(g * Ng + ch) * Ig + rr) * KH + (KH - 1 - ky)) * KW + (KW - 1 - kx)];
-    }
-    out[idx] = from_f32<T>(v);
-  }
-}
-
 // All weight packs of a training step in one launch (74 layers x (forward | transposed for the data gradient)): the job table travels as a
-// kernel argument (<= 40 jobs of 64 bytes per launch), blockIdx.y = job.
+// kernel argument (<= 40 jobs of 64 bytes per launch), blockIdx.y = job, grid-stride over x inside the job.
 template <typename T>
 __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const PackJobs jobs) {
   const PackJob j = jobs.job[blockIdx.y];
@@ -137,75 +99,14 @@ __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const PackJobs j
   }
 }
 
-// split-K wgrad result Y[Ng][splits * Kc] (fp32, Kc = KH*KW*Ig padded to Kc_pad) of ONE group -> dW[O][Ig][KH][KW] (overwrite)
-__global__ __launch_bounds__(256) void wgrad_finalize_kernel(const float* __restrict__ y, float* __restrict__ dw, int Ng, int Ig, int KH, int KW,
-                                                             int g, int splits, int Kc_pad, int hd_rows, int hdp_rows, int hd_cols, int hdp_cols) {
-  const size_t total = (size_t)Ng * Ig * KH * KW;
-  GS_LOOP(idx, total) {
-    const int kx = (int)(idx % KW);
-    size_t t2 = idx / KW;
-    const int ky = (int)(t2 % KH); t2 /= KH;
-    const int i = (int)(t2 % Ig);
-    const int n = (int)(t2 / Ig);
-    int k = (ky * KW + kx) * Ig + i;
-    if (hdp_cols != hd_cols) k = (k / hd_cols) * hdp_cols + k % hd_cols;
-    int r = n;
-    if (hdp_rows != hd_rows) r = (n / hd_rows) * hdp_rows + n % hd_rows;
-    const float* src = y + (size_t)r * splits * Kc_pad + k;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;          // four slabs in flight (a single dependent chain of 4-byte loads ran at 0.5 TB/s)
-    int sp = 0;
-    for (; sp + 4 <= splits; sp += 4) {
-      s0 += src[(size_t)sp * Kc_pad];
-      s1 += src[(size_t)(sp + 1) * Kc_pad];
-      s2 += src[(size_t)(sp + 2) * Kc_pad];
-      s3 += src[(size_t)(sp + 3) * Kc_pad];
-    }
-    for (; sp < splits; ++sp) s0 += src[(size_t)sp * Kc_pad];
-    dw[(((size_t)(g * Ng + n) * Ig + i) * KH + ky) * KW + kx] = (s0 + s1) + (s2 + s3);
-  }
-}
-
-// The same for a plain 1x1 layer without head-dim padding (dW[n][i] = sum_sp y[n][sp * Kc_pad + i], Ig % 4 == 0): 16-byte accesses and four
-// independent partial sums per thread - the generic kernel's serial scalar loop ran at ~0.5 TB/s over the 64 MB of partials a layer has.
-__global__ __launch_bounds__(256) void wgrad_finalize_1x1_kernel(const float* __restrict__ y, float* __restrict__ dw, int Ng, int Ig, int splits, int Kc_pad) {
-  const int i4n = Ig / 4;
-  const size_t total = (size_t)Ng * i4n;
-  GS_LOOP(idx, total) {
-    const int i = (int)(idx % i4n) * 4, n = (int)(idx / i4n);
-    const float* src = y + (size_t)n * splits * Kc_pad + i;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    int sp = 0;
-    for (; sp + 4 <= splits; sp += 4) {
-      s0 += *reinterpret_cast<const f32x4*>(src + (size_t)sp * Kc_pad);
-      s1 += *reinterpret_cast<const f32x4*>(src + (size_t)(sp + 1) * Kc_pad);
-      s2 += *reinterpret_cast<const f32x4*>(src + (size_t)(sp + 2) * Kc_pad);
-      s3 += *reinterpret_cast<const f32x4*>(src + (size_t)(sp + 3) * Kc_pad);
-    }
-    for (; sp < splits; ++sp) s0 += *reinterpret_cast<const f32x4*>(src + (size_t)sp * Kc_pad);
-    *reinterpret_cast<f32x4*>(dw + (size_t)n * Ig + i) = (s0 + s1) + (s2 + s3);
-  }
-}
-
-// Grouped conv computed as ONE dense split-K GEMM (all cross-group products included, only the diagonal blocks are kept):
-// y[groups*Ng][splits * Kc_pad] with k = (ky*KW + kx) * (groups*Ig) + g*Ig + i  ->  dW[groups*Ng][Ig][KH][KW]
-__global__ __launch_bounds__(256) void wgrad_finalize_dense_kernel(const float* __restrict__ y, float* __restrict__ dw, int Ng, int Ig, int KH, int KW,
-                                                                   int groups, int splits, int Kc_pad) {
-  const size_t total = (size_t)groups * Ng * Ig * KH * KW;
-  GS_LOOP(idx, total) {
-    const int kx = (int)(idx % KW);
-    size_t t2 = idx / KW;
-    const int ky = (int)(t2 % KH); t2 /= KH;
-    const int i = (int)(t2 % Ig);
-    const int o = (int)(t2 / Ig), g = o / Ng;
-    const int k = (ky * KW + kx) * (groups * Ig) + g * Ig + i;
-    float s = 0.f;
-    for (int sp = 0; sp < splits; ++sp) s += y[(size_t)o * splits * Kc_pad + (size_t)sp * Kc_pad + k];
-    dw[idx] = s;
-  }
-}
-
-// All deferred finalizes of a backward pass: blockIdx.y = job, grid-stride over x inside the job (same arithmetic, same summation order as the
-// per-layer kernels above and wgrad3x3_finalize_kernel)
+// All deferred finalizes of a backward pass: blockIdx.y = job, grid-stride over x inside the job.  By FinJob::kind:
+//  0  split-K wgrad result y[Ng][splits * Kc_pad] (fp32, k = (ky*KW + kx) * Ig + i) of ONE group g -> dW[O][Ig][KH][KW] (overwrite), head-dim padding undone;
+//     four slabs in flight (a single dependent chain of 4-byte loads ran at 0.5 TB/s)
+//  1  the same for a plain 1x1 layer without head-dim padding (dW[n][i] = sum_sp y[n][sp * Kc_pad + i], Ig % 4 == 0, Kc_pad % 4 == 0): 16-byte accesses
+//  2  a grouped conv computed as ONE dense split-K GEMM (all cross-group products included, only the diagonal blocks are kept; g = groups):
+//     y[groups*Ng][splits * Kc_pad] with k = (ky*KW + kx) * (groups*Ig) + g*Ig + i  ->  dW[groups*Ng][Ig][KH][KW]
+//  3  the direct 3x3 kernels' partials [split][job][tap][32][32] (same arithmetic, same summation order as wgrad3x3_finalize_kernel; g = grouped flag,
+//     Kc_pad = njobs)
 __global__ __launch_bounds__(256) void wgrad_finalize_multi_kernel(const FinJobs jobs) {
   const FinJob j = jobs.job[blockIdx.y];
   const float* __restrict__ y = j.y;
@@ -770,10 +671,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rows_kernel(const T* dy, con
   }
 }
 static inline bool rows_form_ok(int C, int V) { const int lanesC = C / V; return C % V == 0 && lanesC >= 1 && lanesC <= 256 && 256 % lanesC == 0; }
-static inline unsigned rows_grid(size_t M, int C, int V, int U) {
+// blocks of the row-walking kernels: R = 256 / (C / V) rows side by side, U row steps per block, at most `cap` blocks (the kernels loop beyond it)
+static inline unsigned rows_grid(size_t M, int C, int V, int U, size_t cap) {
   const size_t R = 256 / (C / V);
   size_t nb = (M + R * U - 1) / (R * U);
-  return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb));
+  return (unsigned)(nb > cap ? cap : (nb < 1 ? 1 : nb));
 }
 
 // ------------------------------------------------------------------------------------------------ elementwise
@@ -1386,19 +1288,10 @@ __global__ __launch_bounds__(256) void fold_prenorm_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
-#define DISPATCH_T(dtype, CALL_F32, CALL_BF16) do { if ((dtype) == 0) { CALL_F32; } else { CALL_BF16; } } while (0)
+// with_elem / launch (fsvit_common.h): each launcher names its kernel and its arguments once; T = the storage type `dtype` stands for (0: fp32,
+// anything else: the 16-bit type), and launch() hands the untyped buffers over as the kernel's own pointer types.  dtype 2, where a launcher
+// takes it: fp32 in, two-limb words out - an explicit third case.
 
-int launch_pack_weight(const float* w, void* out, int O, int Ig, int KH, int KW, int groups, int mode, int rows_pad, int Kw, int hd_rows, int hdp_rows,
-                       int hd_cols, int hdp_cols, int dtype, hipStream_t s) {
-  const size_t total = (size_t)groups * rows_pad * Kw;
-  if (dtype == 2) {      // two-limb words (fp32 storage, 16-bit MFMA arithmetic)
-    hipLaunchKernelGGL(pack_weight_kernel<limbw>, dim3(gs_grid(total)), dim3(256), 0, s, w, (limbw*)out, O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols);
-    return (int)hipGetLastError();
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(pack_weight_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, w, (float*)out, O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols),
-             hipLaunchKernelGGL(pack_weight_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, w, (bf16*)out, O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols));
-  return (int)hipGetLastError();
-}
 int launch_pack_weight_multi(const PackJob* jobs, int n, int dtype, hipStream_t s) {
   for (int i0 = 0; i0 < n; i0 += PackJobs::MAX) {
     PackJobs pj;
@@ -1412,11 +1305,9 @@ int launch_pack_weight_multi(const PackJob* jobs, int n, int dtype, hipStream_t 
     unsigned gx = (unsigned)((biggest + 1023) / 1024);
     if (gx > 128) gx = 128;
     if (gx < 1) gx = 1;
-    if (dtype == 2) hipLaunchKernelGGL(pack_weight_multi_kernel<limbw>, dim3(gx, (unsigned)m), dim3(256), 0, s, pj);
-    else
-      DISPATCH_T(dtype, hipLaunchKernelGGL(pack_weight_multi_kernel<float>, dim3(gx, (unsigned)m), dim3(256), 0, s, pj),
-                 hipLaunchKernelGGL(pack_weight_multi_kernel<bf16>, dim3(gx, (unsigned)m), dim3(256), 0, s, pj));
-    const int rc = (int)hipGetLastError();
+    const dim3 grid(gx, (unsigned)m);
+    const int rc = dtype == 2 ? launch(pack_weight_multi_kernel<limbw>, grid, 256, 0, s, pj)
+                              : with_elem(dtype, [&](auto e) { return launch(pack_weight_multi_kernel<elem_t<decltype(e)>>, grid, 256, 0, s, pj); });
     if (rc) return rc;
   }
   return 0;
@@ -1435,8 +1326,7 @@ int launch_wgrad_finalize_multi(const FinJob* jobs, int n, hipStream_t s) {
     unsigned gx = (unsigned)((biggest + 255) / 256);          // blocks per job: the largest layer gets one pass, smaller jobs' surplus blocks exit at once
     if (gx > 1024) gx = 1024;
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(wgrad_finalize_multi_kernel, dim3(gx, (unsigned)m), dim3(256), 0, s, fj);
-    const int rc = (int)hipGetLastError();
+    const int rc = launch(wgrad_finalize_multi_kernel, dim3(gx, (unsigned)m), 256, 0, s, fj);
     if (rc) return rc;
   }
   return 0;
@@ -1449,283 +1339,196 @@ int launch_droppath_scales(const float* masks, float* scales, int ncalls, int n_
     for (int i = 0; i < n; ++i) k.inv[i] = 1.0f / keep[c0 + i];
     unsigned gx = (unsigned)((n_img + 255) / 256);
     if (gx > 64) gx = 64;
-    hipLaunchKernelGGL(droppath_scales_kernel, dim3(gx, (unsigned)n), dim3(256), 0, s, masks + (size_t)c0 * n_img, scales + (size_t)c0 * n_img, n_img, k);
-    const int rc = (int)hipGetLastError();
+    const int rc = launch(droppath_scales_kernel, dim3(gx, (unsigned)n), 256, 0, s, masks + (size_t)c0 * n_img, scales + (size_t)c0 * n_img, n_img, k);
     if (rc) return rc;
   }
   return 0;
 }
+// one layer on its own (the operator entry fsvit_conv1x1_wgrad): a one-job table, the 16-byte form (kind 1) where the layer allows it
 int launch_wgrad_finalize(const float* y, float* dw, int Ng, int Ig, int KH, int KW, int g, int splits, int Kc_pad, int hd_rows, int hdp_rows, int hd_cols,
                           int hdp_cols, hipStream_t s) {
-  const size_t total = (size_t)Ng * Ig * KH * KW;
-  if (KH == 1 && KW == 1 && g == 0 && hd_rows == hdp_rows && hd_cols == hdp_cols && (Ig & 3) == 0 && (Kc_pad & 3) == 0) {
-    hipLaunchKernelGGL(wgrad_finalize_1x1_kernel, dim3(gs_grid((size_t)Ng * (Ig / 4))), dim3(256), 0, s, y, dw, Ng, Ig, splits, Kc_pad);
-    return (int)hipGetLastError();
-  }
-  hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(gs_grid(total)), dim3(256), 0, s, y, dw, Ng, Ig, KH, KW, g, splits, Kc_pad, hd_rows, hdp_rows, hd_cols, hdp_cols);
-  return (int)hipGetLastError();
+  const bool fast = KH == 1 && KW == 1 && g == 0 && hd_rows == hdp_rows && hd_cols == hdp_cols && (Ig & 3) == 0 && (Kc_pad & 3) == 0;
+  const FinJob job{y, dw, fast ? 1 : 0, Ng, Ig, KH, KW, g, splits, Kc_pad, hd_rows, hdp_rows, hd_cols, hdp_cols};
+  return launch_wgrad_finalize_multi(&job, 1, s);
 }
-int launch_wgrad_finalize_dense(const float* y, float* dw, int Ng, int Ig, int KH, int KW, int groups, int splits, int Kc_pad, hipStream_t s) {
-  const size_t total = (size_t)groups * Ng * Ig * KH * KW;
-  hipLaunchKernelGGL(wgrad_finalize_dense_kernel, dim3(gs_grid(total)), dim3(256), 0, s, y, dw, Ng, Ig, KH, KW, groups, splits, Kc_pad);
-  return (int)hipGetLastError();
-}
-// dtype 2: fp32 in, two-limb words out (the weight-side operand of a `bf16x2` GEMM)
+// dtype 2: fp32 in, two-limb words out (the weight-side operand of a `bf16x2` GEMM).  The 16-byte forms run where every leading dimension and offset allows it
 int launch_transpose_cols(const void* in, void* out, int M, int ld, int c0, int ncols, int Mpad, int dtype, hipStream_t s) {
-  if (dtype == 2) {
-    if (((ld | c0 | ncols | Mpad) & 3) == 0) {
-      hipLaunchKernelGGL((transpose_cols_v4_kernel<float, limbw>), dim3((Mpad + 63) / 64, (ncols + 63) / 64), dim3(256), 0, s, (const float*)in, (limbw*)out, M, ld, c0, ncols, Mpad);
-    } else {
-      hipLaunchKernelGGL((transpose_cols_kernel<float, limbw>), dim3((Mpad + 31) / 32, (ncols + 31) / 32), dim3(256), 0, s, (const float*)in, (limbw*)out, M, ld, c0, ncols, Mpad);
-    }
-    return (int)hipGetLastError();
-  }
-  if (((ld | c0 | ncols | Mpad) & 3) == 0) {
-    dim3 g4((Mpad + 63) / 64, (ncols + 63) / 64);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(transpose_cols_v4_kernel<float>, g4, dim3(256), 0, s, (const float*)in, (float*)out, M, ld, c0, ncols, Mpad),
-               hipLaunchKernelGGL(transpose_cols_v4_kernel<bf16>, g4, dim3(256), 0, s, (const bf16*)in, (bf16*)out, M, ld, c0, ncols, Mpad));
-    return (int)hipGetLastError();
-  }
-  dim3 grid((Mpad + 31) / 32, (ncols + 31) / 32);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(transpose_cols_kernel<float>, grid, dim3(256), 0, s, (const float*)in, (float*)out, M, ld, c0, ncols, Mpad),
-             hipLaunchKernelGGL(transpose_cols_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)in, (bf16*)out, M, ld, c0, ncols, Mpad));
-  return (int)hipGetLastError();
+  const bool v4 = ((ld | c0 | ncols | Mpad) & 3) == 0;
+  const int t = v4 ? 64 : 32;
+  const auto run = [&](auto k) { return launch(k, dim3((Mpad + t - 1) / t, (ncols + t - 1) / t), 256, 0, s, in, out, M, ld, c0, ncols, Mpad); };
+  if (dtype == 2) return v4 ? run(transpose_cols_v4_kernel<float, limbw>) : run(transpose_cols_kernel<float, limbw>);
+  if (v4) return with_elem(dtype, [&](auto e) { return run(transpose_cols_v4_kernel<elem_t<decltype(e)>>); });
+  return with_elem(dtype, [&](auto e) { return run(transpose_cols_kernel<elem_t<decltype(e)>>); });
 }
 int launch_im2col_t(const void* x, void* out, int B, int H, int W, int ld, int c0, int C, int KH, int KW, int stride, int pad, int OH, int OW, int Mpad,
                     int dtype, hipStream_t s) {
-  if (dtype == 2) {
-    if (((ld | c0 | C | Mpad) & 3) == 0) {
-      hipLaunchKernelGGL((im2col_t_v4_kernel<float, limbw>), dim3((Mpad + 63) / 64, (C + 63) / 64, KH * KW), dim3(256), 0, s, (const float*)x, (limbw*)out, B, H, W, ld, c0, C, KH, KW,
-                         stride, pad, OH, OW, Mpad);
-    } else {
-      hipLaunchKernelGGL((im2col_t_kernel<float, limbw>), dim3((Mpad + 31) / 32, (C + 31) / 32, KH * KW), dim3(256), 0, s, (const float*)x, (limbw*)out, B, H, W, ld, c0, C, KH, KW, stride,
-                         pad, OH, OW, Mpad);
-    }
-    return (int)hipGetLastError();
-  }
-  if (((ld | c0 | C | Mpad) & 3) == 0) {
-    dim3 g4((Mpad + 63) / 64, (C + 63) / 64, KH * KW);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(im2col_t_v4_kernel<float>, g4, dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, ld, c0, C, KH, KW, stride, pad, OH, OW, Mpad),
-               hipLaunchKernelGGL(im2col_t_v4_kernel<bf16>, g4, dim3(256), 0, s, (const bf16*)x, (bf16*)out, B, H, W, ld, c0, C, KH, KW, stride, pad, OH, OW, Mpad));
-    return (int)hipGetLastError();
-  }
-  dim3 grid((Mpad + 31) / 32, (C + 31) / 32, KH * KW);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(im2col_t_kernel<float>, grid, dim3(256), 0, s, (const float*)x, (float*)out, B, H, W, ld, c0, C, KH, KW, stride, pad, OH, OW, Mpad),
-             hipLaunchKernelGGL(im2col_t_kernel<bf16>, grid, dim3(256), 0, s, (const bf16*)x, (bf16*)out, B, H, W, ld, c0, C, KH, KW, stride, pad, OH, OW, Mpad));
-  return (int)hipGetLastError();
+  const bool v4 = ((ld | c0 | C | Mpad) & 3) == 0;
+  const int t = v4 ? 64 : 32;
+  const auto run = [&](auto k) {
+    return launch(k, dim3((Mpad + t - 1) / t, (C + t - 1) / t, KH * KW), 256, 0, s, x, out, B, H, W, ld, c0, C, KH, KW, stride, pad, OH, OW, Mpad);
+  };
+  if (dtype == 2) return v4 ? run(im2col_t_v4_kernel<float, limbw>) : run(im2col_t_kernel<float, limbw>);
+  if (v4) return with_elem(dtype, [&](auto e) { return run(im2col_t_v4_kernel<elem_t<decltype(e)>>); });
+  return with_elem(dtype, [&](auto e) { return run(im2col_t_kernel<elem_t<decltype(e)>>); });
 }
 int launch_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * OH * OW * 4 * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(unpatch2_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)g, (float*)dx, B, OH, OW, C),
-             hipLaunchKernelGGL(unpatch2_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)g, (bf16*)dx, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(unpatch2_kernel<T>, gs_grid(total), 256, 0, s, g, dx, B, OH, OW, C); });
 }
 int bn_reduce_blocks(int M) { int nb = (M + 63) / 64; return nb > 512 ? 512 : nb; }
 int launch_bn_reduce(const void* a, const void* z, const float* mean, const float* invstd, float* partial, int M, int C, int bwd, int dtype, hipStream_t s,
                      const void* add_a, const void* add_b, const float* add_scale, int rows_per_img, const float* act_sa, const float* act_sb) {
   const int nb = bn_reduce_blocks(M);
   if (!rows_per_img) rows_per_img = 1;
-#define FSVIT_BNR(T, V) do { if (bwd) hipLaunchKernelGGL((bn_reduce_kernel<T, true, V>), dim3(nb), dim3(256), 0, s, (const T*)a, (const T*)z, mean, invstd, partial, M, C, \
-                                                         (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, 1, act_sa, act_sb); \
-                             else hipLaunchKernelGGL((bn_reduce_kernel<T, false, V>), dim3(nb), dim3(256), 0, s, (const T*)a, (const T*)z, mean, invstd, partial, M, C, \
-                                                     (const T*)add_a, (const T*)add_b, add_scale, rows_per_img, (const float*)nullptr, (const float*)nullptr); } while (0)
-  if (dtype == 0) FSVIT_BNR(float, 4);
-  else if (C % 8 == 0) FSVIT_BNR(bf16, 8);
-  else FSVIT_BNR(bf16, 4);
-#undef FSVIT_BNR
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    // kb / kf: the backward / forward instantiation at one vector width (the backward form takes no add_*, the forward form no act_*)
+    const auto run = [&](auto kb, auto kf) {
+      return bwd ? launch(kb, nb, 256, 0, s, a, z, mean, invstd, partial, M, C, nullptr, nullptr, nullptr, 1, act_sa, act_sb)
+                 : launch(kf, nb, 256, 0, s, a, z, mean, invstd, partial, M, C, add_a, add_b, add_scale, rows_per_img, nullptr, nullptr);
+    };
+    if constexpr (sizeof(T) == 2) if (C % 8 == 0) return run(bn_reduce_kernel<T, true, 8>, bn_reduce_kernel<T, false, 8>);
+    return run(bn_reduce_kernel<T, true, 4>, bn_reduce_kernel<T, false, 4>); });
 }
 int launch_fold_prenorm(const float* W, const float* sa, const float* sb, void* wf, float* bf, int N, int C, int Kw, int dtype, hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(fold_prenorm_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, W, sa, sb, (float*)wf, bf, N, C, Kw),
-             hipLaunchKernelGGL(fold_prenorm_kernel<bf16>, dim3((N + 3) / 4), dim3(256), 0, s, W, sa, sb, (bf16*)wf, bf, N, C, Kw));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(fold_prenorm_kernel<T>, (N + 3) / 4, 256, 0, s, W, sa, sb, wf, bf, N, C, Kw); });
 }
 int launch_bn_fwd_finalize_nblk(const float* partial, int nblk, int M, int C, float eps, float momentum, const float* gamma, const float* beta, float* rmean, float* rvar,
                                 float* mean, float* invstd, float* sa, float* sb, hipStream_t s) {
-  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, nblk, M, C, eps, momentum, gamma, beta, rmean, rvar, mean, invstd, sa, sb);
-  return (int)hipGetLastError();
+  return launch(bn_fwd_finalize_kernel, (C + 3) / 4, 256, 0, s, partial, nblk, M, C, eps, momentum, gamma, beta, rmean, rvar, mean, invstd, sa, sb);
 }
 int launch_bn_fwd_finalize(const float* partial, int M, int C, float eps, float momentum, const float* gamma, const float* beta, float* rmean, float* rvar,
                            float* mean, float* invstd, float* sa, float* sb, hipStream_t s) {
-  hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, bn_reduce_blocks(M), M, C, eps, momentum, gamma, beta, rmean, rvar, mean, invstd, sa, sb);
-  return (int)hipGetLastError();
+  return launch_bn_fwd_finalize_nblk(partial, bn_reduce_blocks(M), M, C, eps, momentum, gamma, beta, rmean, rvar, mean, invstd, sa, sb, s);
 }
 int launch_bn_bwd_finalize_nblk(const float* partial, int nblk, int M, int C, const float* gamma, const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb,
                                 float* cc, int frozen, hipStream_t s) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, nblk, M, C, gamma, invstd, dgamma, dbeta, ca, cb, cc, frozen);
-  return (int)hipGetLastError();
+  return launch(bn_bwd_finalize_kernel, (C + 3) / 4, 256, 0, s, partial, nblk, M, C, gamma, invstd, dgamma, dbeta, ca, cb, cc, frozen);
 }
 int launch_bn_bwd_finalize(const float* partial, int M, int C, const float* gamma, const float* invstd, float* dgamma, float* dbeta, float* ca, float* cb,
                            float* cc, int frozen, hipStream_t s) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, bn_reduce_blocks(M), M, C, gamma, invstd, dgamma, dbeta, ca, cb, cc, frozen);
-  return (int)hipGetLastError();
+  return launch_bn_bwd_finalize_nblk(partial, bn_reduce_blocks(M), M, C, gamma, invstd, dgamma, dbeta, ca, cb, cc, frozen, s);
 }
 int launch_bn_frozen_coeffs(int C, float eps, const float* gamma, const float* beta, const float* rmean, const float* rvar, float* mean, float* invstd, float* sa,
                             float* sb, hipStream_t s) {
-  hipLaunchKernelGGL(bn_frozen_coeffs_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, eps, gamma, beta, rmean, rvar, mean, invstd, sa, sb);
-  return (int)hipGetLastError();
+  return launch(bn_frozen_coeffs_kernel, (C + 255) / 256, 256, 0, s, C, eps, gamma, beta, rmean, rvar, mean, invstd, sa, sb);
 }
 int launch_bn_apply(const void* z, const float* sa, const float* sb, const void* res, void* y, size_t M, int C, int act, int dtype, hipStream_t s) {
-  if (rows_form_ok(C, dtype == 0 ? 4 : 8)) {
-    if (dtype == 0) hipLaunchKernelGGL((bn_apply_rows_kernel<float, 4, 4>), dim3(rows_grid(M, C, 4, 4)), dim3(256), 0, s, (const float*)z, sa, sb, (const float*)res, (float*)y, M, C, act);
-    else hipLaunchKernelGGL((bn_apply_rows_kernel<bf16, 8, 4>), dim3(rows_grid(M, C, 8, 4)), dim3(256), 0, s, (const bf16*)z, sa, sb, (const bf16*)res, (bf16*)y, M, C, act);
-    return (int)hipGetLastError();
-  }
-  const size_t total = M * (C / 4);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)z, sa, sb, (const float*)res, (float*)y, M, C, act),
-             hipLaunchKernelGGL(bn_apply_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)z, sa, sb, (const bf16*)res, (bf16*)y, M, C, act));
-  return (int)hipGetLastError();
+  const auto run = [&](auto k, unsigned grid) { return launch(k, grid, 256, 0, s, z, sa, sb, res, y, M, C, act); };
+  if (rows_form_ok(C, vec_width(dtype)))
+    return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+      constexpr int V = Elem<T>::kPerChunk;
+      return run(bn_apply_rows_kernel<T, V, 4>, rows_grid(M, C, V, 4, 4096)); });
+  return with_elem(dtype, [&](auto e) { return run(bn_apply_kernel<elem_t<decltype(e)>>, gs_grid(M * (C / 4))); });
 }
 int launch_bn_act_bwd(const void* dout, const void* z, const float* sa, const float* sb, const void* res, void* g, size_t M, int C, int dtype, hipStream_t s) {
-  const size_t total = M * (C / 4);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_act_bwd_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)dout, (const float*)z, sa, sb, (const float*)res, (float*)g, M, C),
-             hipLaunchKernelGGL(bn_act_bwd_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)dout, (const bf16*)z, sa, sb, (const bf16*)res, (bf16*)g, M, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(bn_act_bwd_kernel<T>, gs_grid(M * (C / 4)), 256, 0, s, dout, z, sa, sb, res, g, M, C); });
 }
 int launch_bn_bwd_apply(const void* dy, const void* z, const float* mean, const float* invstd, const float* ca, const float* cb, const float* cc, void* dz,
                         size_t M, int C, int dtype, hipStream_t s, const void* acc, const float* scale2, void* out2, size_t rows_per_img, const float* act_sa,
                         const float* act_sb) {
-  const size_t total = M * (C / 4);
   if (!rows_per_img) rows_per_img = 1;
-  if (rows_form_ok(C, dtype == 0 ? 4 : 8)) {
-    if (dtype == 0)
-      hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<float, 4, 2>), dim3(rows_grid(M, C, 4, 2)), dim3(256), 0, s, (const float*)dy, (const float*)z, mean, invstd, ca, cb, cc, (float*)dz, M, C,
-                         (const float*)acc, scale2, (float*)out2, rows_per_img, act_sa, act_sb);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_rows_kernel<bf16, 8, 2>), dim3(rows_grid(M, C, 8, 2)), dim3(256), 0, s, (const bf16*)dy, (const bf16*)z, mean, invstd, ca, cb, cc, (bf16*)dz, M, C,
-                         (const bf16*)acc, scale2, (bf16*)out2, rows_per_img, act_sa, act_sb);
-    return (int)hipGetLastError();
-  }
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)dy, (const float*)z, mean, invstd, ca, cb, cc, (float*)dz, M, C,
-                                       (const float*)acc, scale2, (float*)out2, rows_per_img, act_sa, act_sb),
-             hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)dy, (const bf16*)z, mean, invstd, ca, cb, cc, (bf16*)dz, M, C,
-                                (const bf16*)acc, scale2, (bf16*)out2, rows_per_img, act_sa, act_sb));
-  return (int)hipGetLastError();
+  const auto run = [&](auto k, unsigned grid) {
+    return launch(k, grid, 256, 0, s, dy, z, mean, invstd, ca, cb, cc, dz, M, C, acc, scale2, out2, rows_per_img, act_sa, act_sb);
+  };
+  if (rows_form_ok(C, vec_width(dtype)))
+    return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+      constexpr int V = Elem<T>::kPerChunk;
+      return run(bn_bwd_apply_rows_kernel<T, V, 2>, rows_grid(M, C, V, 2, 4096)); });
+  return with_elem(dtype, [&](auto e) { return run(bn_bwd_apply_kernel<elem_t<decltype(e)>>, gs_grid(M * (C / 4))); });
 }
 int launch_bn_pool_fwd(const void* z, const float* sa, const float* sb, const void* res, const float* pos, void* out, unsigned char* arg, int B, int OH, int OW,
                        int C, int dtype, hipStream_t s, const float* rsa, const float* rsb) {
   if (C % 8) return (int)hipErrorInvalidValue;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((bn_pool_fwd_kernel<float, 4>), dim3(gs_grid((size_t)B * OH * OW * (C / 4))), dim3(256), 0, s, (const float*)z, sa, sb, (const float*)res, pos,
-                                       (float*)out, arg, B, OH, OW, C, rsa, rsb),
-             hipLaunchKernelGGL((bn_pool_fwd_kernel<bf16, 8>), dim3(gs_grid((size_t)B * OH * OW * (C / 8))), dim3(256), 0, s, (const bf16*)z, sa, sb, (const bf16*)res, pos,
-                                (bf16*)out, arg, B, OH, OW, C, rsa, rsb));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    constexpr int V = Elem<T>::kPerChunk;
+    return launch(bn_pool_fwd_kernel<T, V>, gs_grid((size_t)B * OH * OW * (C / V)), 256, 0, s, z, sa, sb, res, pos, out, arg, B, OH, OW, C, rsa, rsb); });
 }
 // the two BatchNorm backwards behind the stem's pooled tail, from the pooled gradient (pool_bn_bwd_*_kernel)
-bool pool_bn_bwd_supported(int C, int dtype) { return rows_form_ok(C, dtype == 0 ? 4 : 8); }
-static inline unsigned pool_rows_grid(size_t npix, int C, int V) {
-  const size_t R = 256 / (C / V);
-  size_t nb = (npix + R - 1) / R;
-  return (unsigned)(nb > 512 ? 512 : (nb < 1 ? 1 : nb));
-}
-int pool_bn_bwd_blocks(int B, int OH, int OW, int C, int dtype) { return (int)pool_rows_grid((size_t)B * OH * OW, C, dtype == 0 ? 4 : 8); }
+bool pool_bn_bwd_supported(int C, int dtype) { return rows_form_ok(C, vec_width(dtype)); }
+int pool_bn_bwd_blocks(int B, int OH, int OW, int C, int dtype) { return (int)rows_grid((size_t)B * OH * OW, C, vec_width(dtype), 1, 512); }
 int launch_pool_bn_bwd_reduce(const void* dout, const unsigned char* arg, const void* z3, const void* zd, const float* mean3, const float* is3, const float* meand,
                               const float* isd, float* partial3, float* partiald, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
-  const unsigned nb = pool_rows_grid((size_t)B * OH * OW, C, dtype == 0 ? 4 : 8);
-  DISPATCH_T(dtype, hipLaunchKernelGGL((pool_bn_bwd_reduce_kernel<float, 4>), dim3(nb), dim3(256), 0, s, (const float*)dout, arg, (const float*)z3, (const float*)zd, mean3, is3,
-                                       meand, isd, partial3, partiald, B, OH, OW, C),
-             hipLaunchKernelGGL((pool_bn_bwd_reduce_kernel<bf16, 8>), dim3(nb), dim3(256), 0, s, (const bf16*)dout, arg, (const bf16*)z3, (const bf16*)zd, mean3, is3, meand,
-                                isd, partial3, partiald, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(pool_bn_bwd_reduce_kernel<T, Elem<T>::kPerChunk>, pool_bn_bwd_blocks(B, OH, OW, C, dtype), 256, 0, s, dout, arg, z3, zd, mean3, is3, meand, isd,
+                  partial3, partiald, B, OH, OW, C); });
 }
 int launch_pool_bn_bwd_apply(const void* dout, const unsigned char* arg, const void* z3, const void* zd, const float* mean3, const float* is3, const float* meand,
                              const float* isd, const float* coef3, const float* coefd, void* dz3, void* dzd, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
-  const size_t npix = (size_t)B * OH * OW;
-  const int V = dtype == 0 ? 4 : 8;
-  const size_t R = 256 / (C / V);
-  size_t nb = (npix + R - 1) / R;
-  if (nb > 8192) nb = 8192;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((pool_bn_bwd_apply_kernel<float, 4>), dim3((unsigned)nb), dim3(256), 0, s, (const float*)dout, arg, (const float*)z3, (const float*)zd, mean3,
-                                       is3, meand, isd, coef3, coefd, (float*)dz3, (float*)dzd, B, OH, OW, C),
-             hipLaunchKernelGGL((pool_bn_bwd_apply_kernel<bf16, 8>), dim3((unsigned)nb), dim3(256), 0, s, (const bf16*)dout, arg, (const bf16*)z3, (const bf16*)zd, mean3, is3,
-                                meand, isd, coef3, coefd, (bf16*)dz3, (bf16*)dzd, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    constexpr int V = Elem<T>::kPerChunk;
+    return launch(pool_bn_bwd_apply_kernel<T, V>, rows_grid((size_t)B * OH * OW, C, V, 1, 8192), 256, 0, s, dout, arg, z3, zd, mean3, is3, meand, isd,
+                  coef3, coefd, dz3, dzd, B, OH, OW, C); });
 }
 int launch_pool_act_bwd(const void* dout, const unsigned char* arg, void* g, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
   if (C % 8) return (int)hipErrorInvalidValue;
-  DISPATCH_T(dtype, hipLaunchKernelGGL((pool_act_bwd_kernel<float, 4>), dim3(gs_grid((size_t)B * OH * OW * (C / 4))), dim3(256), 0, s, (const float*)dout, arg, (float*)g, B, OH, OW, C),
-             hipLaunchKernelGGL((pool_act_bwd_kernel<bf16, 8>), dim3(gs_grid((size_t)B * OH * OW * (C / 8))), dim3(256), 0, s, (const bf16*)dout, arg, (bf16*)g, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    constexpr int V = Elem<T>::kPerChunk;
+    return launch(pool_act_bwd_kernel<T, V>, gs_grid((size_t)B * OH * OW * (C / V)), 256, 0, s, dout, arg, g, B, OH, OW, C); });
 }
 int launch_gelu_fwd(const void* z, void* h, size_t n, int dtype, hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gelu_fwd_kernel<float>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const float*)z, (float*)h, n / 4),
-             hipLaunchKernelGGL(gelu_fwd_kernel<bf16>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const bf16*)z, (bf16*)h, n / 4));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(gelu_fwd_kernel<T>, gs_grid(n / 4), 256, 0, s, z, h, n / 4); });
 }
 int launch_gelu_bwd(const void* dh, const void* z, void* dz, size_t n, int dtype, hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const float*)dh, (const float*)z, (float*)dz, n / 4),
-             hipLaunchKernelGGL(gelu_bwd_kernel<bf16>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const bf16*)dh, (const bf16*)z, (bf16*)dz, n / 4));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(gelu_bwd_kernel<T>, gs_grid(n / 4), 256, 0, s, dh, z, dz, n / 4); });
 }
 int launch_add_scaled(const void* a, const void* br, const float* scale, void* out, size_t n, size_t per_img, int dtype, hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(add_scaled_kernel<float>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const float*)a, (const float*)br, scale, (float*)out, n / 4, per_img / 4),
-             hipLaunchKernelGGL(add_scaled_kernel<bf16>, dim3(gs_grid(n / 4)), dim3(256), 0, s, (const bf16*)a, (const bf16*)br, scale, (bf16*)out, n / 4, per_img / 4));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(add_scaled_kernel<T>, gs_grid(n / 4), 256, 0, s, a, br, scale, out, n / 4, per_img / 4); });
 }
 int launch_maxpool2_idx(const void* in, const float* pos, void* out, unsigned char* arg, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * OH * OW * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_idx_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)in, pos, (float*)out, arg, B, OH, OW, C),
-             hipLaunchKernelGGL(maxpool2_idx_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)in, pos, (bf16*)out, arg, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(maxpool2_idx_kernel<T>, gs_grid(total), 256, 0, s, in, pos, out, arg, B, OH, OW, C); });
 }
 int launch_maxpool2_bwd(const void* dout, const unsigned char* arg, void* din, int B, int OH, int OW, int C, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * OH * OW * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)dout, arg, (float*)din, B, OH, OW, C),
-             hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)dout, arg, (bf16*)din, B, OH, OW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(maxpool2_bwd_kernel<T>, gs_grid(total), 256, 0, s, dout, arg, din, B, OH, OW, C); });
 }
 int launch_avgpool_bwd(const float* dfeat, void* dx, int B, int HW, int C, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * HW * C;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, dfeat, (float*)dx, B, HW, C),
-             hipLaunchKernelGGL(avgpool_bwd_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, dfeat, (bf16*)dx, B, HW, C));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(avgpool_bwd_kernel<T>, gs_grid(total), 256, 0, s, dfeat, dx, B, HW, C); });
 }
 int launch_batch_sum(const void* g, float* out, int B, size_t per_img, int dtype, hipStream_t s) {
   if (per_img % 4) return (int)hipErrorInvalidValue;
   const unsigned nb = (unsigned)((per_img / 4 + 63) / 64);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(batch_sum_kernel<float>, dim3(nb), dim3(1024), 0, s, (const float*)g, out, B, per_img),
-             hipLaunchKernelGGL(batch_sum_kernel<bf16>, dim3(nb), dim3(1024), 0, s, (const bf16*)g, out, B, per_img));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(batch_sum_kernel<T>, nb, 1024, 0, s, g, out, B, per_img); });
 }
 int launch_bcast_add(const void* x, const float* p, void* y, int B, size_t per_img, int dtype, hipStream_t s) {
   const size_t n4 = (size_t)B * per_img / 4;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(bcast_add_kernel<float>, dim3(gs_grid(n4)), dim3(256), 0, s, (const float*)x, p, (float*)y, n4, per_img / 4),
-             hipLaunchKernelGGL(bcast_add_kernel<bf16>, dim3(gs_grid(n4)), dim3(256), 0, s, (const bf16*)x, p, (bf16*)y, n4, per_img / 4));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(bcast_add_kernel<T>, gs_grid(n4), 256, 0, s, x, p, y, n4, per_img / 4); });
 }
-int launch_fill_f32(float* p, float v, size_t n, hipStream_t s) {
-  hipLaunchKernelGGL(fill_f32_kernel, dim3(gs_grid(n)), dim3(256), 0, s, p, v, n);
-  return (int)hipGetLastError();
-}
-int launch_scale_copy(const float* in, float* out, size_t n, float sc, hipStream_t s) {
-  hipLaunchKernelGGL(scale_copy_kernel, dim3(gs_grid(n)), dim3(256), 0, s, in, out, n, sc);
-  return (int)hipGetLastError();
-}
+int launch_fill_f32(float* p, float v, size_t n, hipStream_t s) { return launch(fill_f32_kernel, gs_grid(n), 256, 0, s, p, v, n); }
+int launch_scale_copy(const float* in, float* out, size_t n, float sc, hipStream_t s) { return launch(scale_copy_kernel, gs_grid(n), 256, 0, s, in, out, n, sc); }
 int launch_colsum(const void* a, float* partial, float* out, int M, int C, int dtype, hipStream_t s) {
   int rc = launch_bn_reduce(a, nullptr, nullptr, nullptr, partial, M, C, 0, dtype, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(colsum_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, partial, bn_reduce_blocks(M), C, out);
-  return (int)hipGetLastError();
+  return launch(colsum_finalize_kernel, (C + 3) / 4, 256, 0, s, partial, bn_reduce_blocks(M), C, out);
 }
 int launch_sgd_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s) {
   if (n_items <= 0 || max_numel == 0) return 0;
   size_t gx = (max_numel + 1023) / 1024;                 // 4 elements per thread at the largest tensor; smaller ones leave blocks idle
   if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(sgd_multi_kernel, dim3((unsigned)gx, (unsigned)n_items), dim3(256), 0, s, (const SgdItem*)items_dev, lr, momentum, wd, first);
-  return (int)hipGetLastError();
+  return launch(sgd_multi_kernel, dim3((unsigned)gx, (unsigned)n_items), 256, 0, s, items_dev, lr, momentum, wd, first);
 }
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s) {
   if (n == 0) return 0;
-  hipLaunchKernelGGL(sgd_kernel, dim3(gs_grid(n)), dim3(256), 0, s, p, g, buf, n, lr, momentum, wd, first);
-  return (int)hipGetLastError();
+  return launch(sgd_kernel, gs_grid(n), 256, 0, s, p, g, buf, n, lr, momentum, wd, first);
 }
 
 int launch_ln_train_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps, int dtype, hipStream_t s) {
   if (M <= 0) return 0;
   if (D % 4) return (int)hipErrorInvalidValue;
-  DISPATCH_T(dtype, hipLaunchKernelGGL(ln_train_fwd_kernel<float>, dim3((M + 3) / 4), dim3(256), 0, s, (const float*)x, gamma, beta, (float*)y, mean, rstd, M, D, eps),
-             hipLaunchKernelGGL(ln_train_fwd_kernel<bf16>, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16*)x, gamma, beta, (bf16*)y, mean, rstd, M, D, eps));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(ln_train_fwd_kernel<T>, (M + 3) / 4, 256, 0, s, x, gamma, beta, y, mean, rstd, M, D, eps); });
 }
 int ln_bwd_blocks(int M) { int nb = (M + 63) / 64; return nb > 1024 ? 1024 : (nb < 1 ? 1 : nb); }
 // partial: ln_bwd_blocks(M) * 2 * D floats; dgamma / dbeta may be null
@@ -1735,43 +1538,43 @@ int launch_ln_bwd(const void* dy, const void* x, const float* mean, const float*
   if (D % 4 || (size_t)8 * D * 4 > 64 * 1024) return (int)hipErrorInvalidValue;
   const int nb = ln_bwd_blocks(M), rpb = (M + nb - 1) / nb;
   const size_t lds = (size_t)8 * D * sizeof(float);
-  const int ng = (D + 255) / 256;
-  if (ng <= 4) {
-#define FSVIT_LNB(T, NG) hipLaunchKernelGGL((ln_bwd_rows_kernel<T, NG>), dim3(nb), dim3(256), lds, s, (const T*)dy, (const T*)x, mean, rstd, gamma, (const T*)add, (T*)dx, partial, M, D, rpb)
-    if (dtype == 0) { if (ng == 1) FSVIT_LNB(float, 1); else if (ng == 2) FSVIT_LNB(float, 2); else if (ng == 3) FSVIT_LNB(float, 3); else FSVIT_LNB(float, 4); }
-    else { if (ng == 1) FSVIT_LNB(bf16, 1); else if (ng == 2) FSVIT_LNB(bf16, 2); else if (ng == 3) FSVIT_LNB(bf16, 3); else FSVIT_LNB(bf16, 4); }
-#undef FSVIT_LNB
-  } else
-  DISPATCH_T(dtype, hipLaunchKernelGGL(ln_bwd_kernel<float>, dim3(nb), dim3(256), lds, s, (const float*)dy, (const float*)x, mean, rstd, gamma, (const float*)add, (float*)dx, partial, M, D, rpb),
-             hipLaunchKernelGGL(ln_bwd_kernel<bf16>, dim3(nb), dim3(256), lds, s, (const bf16*)dy, (const bf16*)x, mean, rstd, gamma, (const bf16*)add, (bf16*)dx, partial, M, D, rpb));
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3((D + 3) / 4), dim3(256), 0, s, partial, nb, D, dgamma, dbeta);
-  return (int)hipGetLastError();
+  const int ng = (D + 255) / 256;       // column groups of 256 lanes: up to four are held in registers
+  const auto run = [&](auto k) { return launch(k, nb, 256, lds, s, dy, x, mean, rstd, gamma, add, dx, partial, M, D, rpb); };
+  int rc;
+  if (ng <= 4)
+    rc = with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+      switch (ng) {
+        case 1: return run(ln_bwd_rows_kernel<T, 1>);
+        case 2: return run(ln_bwd_rows_kernel<T, 2>);
+        case 3: return run(ln_bwd_rows_kernel<T, 3>);
+        default: return run(ln_bwd_rows_kernel<T, 4>);
+      } });
+  else rc = with_elem(dtype, [&](auto e) { return run(ln_bwd_kernel<elem_t<decltype(e)>>); });
+  if (rc) return rc;
+  return launch(ln_param_grad_kernel, (D + 3) / 4, 256, 0, s, partial, nb, D, dgamma, dbeta);
 }
 int launch_vit_assemble(const void* zpe, const float* cls, const float* pos, void* tokens, int B, int S, int D, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * S * (D / 4);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(vit_assemble_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)zpe, cls, pos, (float*)tokens, B, S, D),
-             hipLaunchKernelGGL(vit_assemble_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)zpe, cls, pos, (bf16*)tokens, B, S, D));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(vit_assemble_kernel<T>, gs_grid(total), 256, 0, s, zpe, cls, pos, tokens, B, S, D); });
 }
 int launch_vit_patch_rows(const void* dtok, void* dzpe, int B, int S, int D, int dtype, hipStream_t s) {
   const size_t total = (size_t)B * (S - 1) * (D / 4);
-  DISPATCH_T(dtype, hipLaunchKernelGGL(vit_patch_rows_kernel<float>, dim3(gs_grid(total)), dim3(256), 0, s, (const float*)dtok, (float*)dzpe, B, S, D),
-             hipLaunchKernelGGL(vit_patch_rows_kernel<bf16>, dim3(gs_grid(total)), dim3(256), 0, s, (const bf16*)dtok, (bf16*)dzpe, B, S, D));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(vit_patch_rows_kernel<T>, gs_grid(total), 256, 0, s, dtok, dzpe, B, S, D); });
 }
 int launch_vit_cls_ln_fwd(const void* tokens, const float* gamma, const float* beta, float* feat, float* mean, float* rstd, int B, int S, int D, float eps, int dtype,
                           hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(vit_cls_ln_fwd_kernel<float>, dim3(B), dim3(64), 0, s, (const float*)tokens, gamma, beta, feat, mean, rstd, S, D, eps),
-             hipLaunchKernelGGL(vit_cls_ln_fwd_kernel<bf16>, dim3(B), dim3(64), 0, s, (const bf16*)tokens, gamma, beta, feat, mean, rstd, S, D, eps));
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(vit_cls_ln_fwd_kernel<T>, B, 64, 0, s, tokens, gamma, beta, feat, mean, rstd, S, D, eps); });
 }
 // dtok must be zeroed by the caller (only the cls rows are written); partial: B * 2 * D floats
 int launch_vit_cls_ln_bwd(const float* dfeat, const void* tokens, const float* mean, const float* rstd, const float* gamma, void* dtok, float* partial, float* dgamma,
                           float* dbeta, int B, int S, int D, int dtype, hipStream_t s) {
-  DISPATCH_T(dtype, hipLaunchKernelGGL(vit_cls_ln_bwd_kernel<float>, dim3(B), dim3(64), 0, s, dfeat, (const float*)tokens, mean, rstd, gamma, (float*)dtok, partial, S, D),
-             hipLaunchKernelGGL(vit_cls_ln_bwd_kernel<bf16>, dim3(B), dim3(64), 0, s, dfeat, (const bf16*)tokens, mean, rstd, gamma, (bf16*)dtok, partial, S, D));
-  hipLaunchKernelGGL(ln_param_grad_kernel, dim3((D + 3) / 4), dim3(256), 0, s, partial, B, D, dgamma, dbeta);
-  return (int)hipGetLastError();
+  const int rc = with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return launch(vit_cls_ln_bwd_kernel<T>, B, 64, 0, s, dfeat, tokens, mean, rstd, gamma, dtok, partial, S, D); });
+  if (rc) return rc;
+  return launch(ln_param_grad_kernel, (D + 3) / 4, 256, 0, s, partial, B, D, dgamma, dbeta);
 }
 
 }  // namespace fsvit

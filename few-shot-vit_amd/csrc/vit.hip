@@ -148,40 +148,35 @@ static unsigned grid_for(size_t total) {
 int launch_patchify(const float* x, void* out, int B, int img, int p, int Kp, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
   const size_t total = (size_t)B * (img / p) * (img / p) * (Kp / 4);
-  if (dtype == 0) hipLaunchKernelGGL(patchify_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, x, (float*)out, B, img, p, Kp);
-  else hipLaunchKernelGGL(patchify_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, s, x, (bf16*)out, B, img, p, Kp);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(patchify_kernel<elem_t<decltype(e)>>, grid_for(total), 256, 0, s, x, out, B, img, p, Kp); });
 }
 
 int launch_cls_pos(const float* cls_plus_pos0, void* tokens, int B, int S, int D, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
   const size_t total = (size_t)B * (D / 4);
-  if (dtype == 0) hipLaunchKernelGGL(cls_pos_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, cls_plus_pos0, (float*)tokens, B, S, D);
-  else hipLaunchKernelGGL(cls_pos_kernel<bf16>, dim3(grid_for(total)), dim3(256), 0, s, cls_plus_pos0, (bf16*)tokens, B, S, D);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(cls_pos_kernel<elem_t<decltype(e)>>, grid_for(total), 256, 0, s, cls_plus_pos0, tokens, B, S, D); });
 }
 
 int launch_layernorm(const void* x, void* y, int M, int D, float eps, int dtype, hipStream_t s) {
   if (M <= 0) return 0;
-  const int epl = dtype == 0 ? 4 : 8;
+  const int epl = vec_width(dtype);
   if (D % epl || D > 64 * epl * 4) return (int)hipErrorInvalidValue;
   const int lanes = (D / epl + 3) / 4;                           // lanes a row needs with 4 passes
   const int G = lanes <= 16 ? 16 : (lanes <= 32 ? 32 : 64);
   const int rows_per_wg = 4 * (64 / G);
-  dim3 grid((M + rows_per_wg - 1) / rows_per_wg), block(256);
-#define FSVIT_LN(TT, GG) hipLaunchKernelGGL((layernorm_kernel<TT, GG>), grid, block, 0, s, (const TT*)x, (TT*)y, M, D, eps)
-  if (dtype == 0) { if (G == 16) FSVIT_LN(float, 16); else if (G == 32) FSVIT_LN(float, 32); else FSVIT_LN(float, 64); }
-  else { if (G == 16) FSVIT_LN(bf16, 16); else if (G == 32) FSVIT_LN(bf16, 32); else FSVIT_LN(bf16, 64); }
-#undef FSVIT_LN
-  return (int)hipGetLastError();
+  const auto run = [&](auto k) { return launch(k, (M + rows_per_wg - 1) / rows_per_wg, 256, 0, s, x, y, M, D, eps); };
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    switch (G) {
+      case 16: return run(layernorm_kernel<T, 16>);
+      case 32: return run(layernorm_kernel<T, 32>);
+      default: return run(layernorm_kernel<T, 64>);
+    } });
 }
 
 int launch_final_ln_cls(const void* tokens, const float* gamma, const float* beta, float* feat, int B, int S, int D, float eps, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
   if (D % 4 || D > 2048) return (int)hipErrorInvalidValue;
-  if (dtype == 0) hipLaunchKernelGGL(final_ln_cls_kernel<float>, dim3(B), dim3(64), 0, s, (const float*)tokens, gamma, beta, feat, S, D, eps);
-  else hipLaunchKernelGGL(final_ln_cls_kernel<bf16>, dim3(B), dim3(64), 0, s, (const bf16*)tokens, gamma, beta, feat, S, D, eps);
-  return (int)hipGetLastError();
+  return with_elem(dtype, [&](auto e) { return launch(final_ln_cls_kernel<elem_t<decltype(e)>>, B, 64, 0, s, tokens, gamma, beta, feat, S, D, eps); });
 }
 
 }  // namespace FSVIT_NS

@@ -684,7 +684,7 @@ int launch_gconv3x3_x2(const ConvGemmParams& p, hipStream_t s) {
 
 // ---- 1x1 convolutions (conv1 / conv3 of the Mlps, qkv, proj):  Y[n][split * Kc_pad + c] = sum_{m in split} dz[m][n] * x[m][c]
 // The same transposing-read scheme without taps: a workgroup owns an NT (n) x CT (c) block (256 where the layer has >= 256 columns, else 128), its
-// 8 waves (4 x 2) NT/4 x CT/2 each (up to 32 accumulator tiles); per 64 rows it stages (NT + CT) x 128 B and issues up to 64 MFMAs per wave.  Output is the split-K partial layout wgrad_finalize_kernel already sums (it also
+// 8 waves (4 x 2) NT/4 x CT/2 each (up to 32 accumulator tiles); per 64 rows it stages (NT + CT) x 128 B and issues up to 64 MFMAs per wave.  Output is the split-K partial layout wgrad_finalize_multi_kernel (kind 0 / 1) already sums (it also
 // undoes the head-dim padding of qkv rows / proj columns).
 template <int NT, int CT>
 __global__ __launch_bounds__(512) void wgrad1x1_kernel(const bf16* __restrict__ x, int xld, int C, const bf16* __restrict__ dz, int zld, int N,

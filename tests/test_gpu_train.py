@@ -581,13 +581,32 @@ def test_conv3x3_wgrad_two_limb_vs_fp64(shape, limbs):
     assert torch.equal(got, ops.conv3x3_wgrad(*args).cpu().double())
 
 
+def _wgrad1x1_splits(M, N, C):
+    """Row splits (= partial slabs the finalize sums) of the 16-bit 1x1 weight-gradient launch: wgrad1x1_splits in csrc/wgrad3x3.hip at its default of
+    128 workgroups - 64-row chunks, blocks of 256 along a dimension of >= 256 columns, else 128."""
+    chunks = -(-M // 64)
+    tiles = -(-N // (256 if N >= 256 else 128)) * -(-C // (256 if C >= 256 else 128))
+    s = max(1, min(-(-128 // tiles), chunks))
+    cpw = -(-chunks // s)
+    return -(-chunks // cpw)
+
+
+# (64, 8, 8): ONE split - the finalize's sum is a copy; (390, 8, 8): 7 splits - its four-slab loop runs once and the tail loop three times
 @pytest.mark.gpu
-@pytest.mark.parametrize('shape', [(8000, 1024, 256), (2000, 864, 256), (2000, 512, 576), (5000, 128, 32), (777, 256, 128), (64, 1728, 512), (130, 8, 8)])
+@pytest.mark.parametrize('shape', [(8000, 1024, 256), (2000, 864, 256), (2000, 512, 576), (5000, 128, 32), (777, 256, 128), (64, 1728, 512), (130, 8, 8),
+                                   (64, 8, 8), (390, 8, 8)])
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 def test_conv1x1_wgrad_direct_vs_torch(shape, dtype):
-    """fsvit_conv1x1_wgrad vs dz^T @ x in fp32 on the same 16-bit-rounded operands (ragged M, N, C tails included)."""
+    """fsvit_conv1x1_wgrad vs dz^T @ x in fp32 on the same 16-bit-rounded operands (ragged M, N, C tails included).  The operator sums its split
+    slabs with a one-job launch of the training step's finalize kernel."""
     from fewshot_vit_amd.engine import ops
     M, N, C = shape
+    splits = _wgrad1x1_splits(M, N, C)
+    print(f'conv1x1_wgrad {shape}: {splits} splits')
+    if shape == (64, 8, 8):
+        assert splits == 1
+    if shape == (390, 8, 8):
+        assert splits == 7          # > 4 and not a multiple of 4: main loop and tail loop
     g = torch.Generator().manual_seed(M + N + C)
     x = torch.randn(M, C, generator=g).to(dtype)
     dz = (torch.randn(M, N, generator=g) * 0.1).to(dtype)
