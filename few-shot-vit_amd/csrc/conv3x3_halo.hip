@@ -30,53 +30,14 @@
 #include <stdlib.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "conv_gemm.h"
-#include "fsvit_common.h"
+#include "lds_dma.h"
 
 namespace FSVIT_NS {
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page_halo[256];
-typedef __attribute__((address_space(3))) void* lptrh_t;
-
-__device__ __forceinline__ void hdma1(const void* gsrc, unsigned lds_byte_addr) {       // one 1 KiB LDS-DMA, per-lane 64-bit source
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-__device__ __forceinline__ void hdma2s(unsigned off0, unsigned off1, const void* sbase, unsigned lds0, unsigned lds1) {   // scalar base + 32-bit offsets
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %3\n\t"
-      "s_mov_b32 m0, %5\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off0), "v"(off1), "s"(sbase), "s"(lds0), "s"(lds1)
-      : "memory");
-}
-__device__ __forceinline__ u32x4 hgload16(const void* p) {      // hidden from hipcc's waitcnt pass like the DMAs: counted by hand
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
 #define HWAIT(vm) asm volatile("s_waitcnt vmcnt(" #vm ") lgkmcnt(0)" ::: "memory")
-__device__ __forceinline__ void hbar() {
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 template <int CTRL>
 __device__ __forceinline__ float quad_xor(float v) {
@@ -95,13 +56,6 @@ constexpr int LDS_BYTES = OFF_W + NST * STAGE; // 163840 = 160 KiB
 static_assert(LDS_BYTES == 160 * 1024, "the two halo buffers and the weight ring fill the LDS exactly");
 }  // namespace halo
 
-template <int... I, typename F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
-
 // CREAL < CIN (the LV-ViT stem, CREAL = 96 on the CIN = 128 schedule): the maps hold CREAL channels (input and output pixel = CREAL * 2 bytes); halo
 // chunks past CREAL are filled from the zero page, the weights come as the zero-padded 128-channel image (ConvGemmParams::w_cpad), and outputs past
 // CREAL are neither loaded (bias / pos) nor stored.  Every CREAL-specific statement is `if constexpr (CREAL != CIN)`: the 64 / 128 instantiations
@@ -117,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int lrow = lane & 15, lq = lane >> 4;
-  const unsigned lds0 = (unsigned)(size_t)(lptrh_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   unsigned char* const wst0 = smem + OFF_W;
 
   const unsigned char* const Xb = reinterpret_cast<const unsigned char*>(p.x);
@@ -154,7 +108,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   // -> source byte offset relative to pixel (image b, row r0 - 1, column 0); padding slots and the left / right border read zeros
   auto issue_w = [&](int wk, int stage) {
     const unsigned d = lds0 + OFF_W + stage * STAGE;
-    hdma2s(offB[0], offB[1], Wb + (size_t)wk * 128, d + (2 * wave) * 1024, d + (2 * wave + 1) * 1024);
+    dma2(offB[0], offB[1], Wb + (size_t)wk * 128, d + (2 * wave) * 1024, d + (2 * wave + 1) * 1024);
   };
   // source of (halo row hr, halo column hc) of this wave's chunk plane = base + hr * x_rs + (hc - 1) * x_ps bytes: NHWC (pixel = CIN * 2 bytes, the wave's
   // chunk 16 bytes into the half) or row-chunk-planar (conv_gemm.h x_planar: a row of one chunk = W * 16 contiguous bytes)
@@ -169,7 +123,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
     const bool ok = (base != nullptr) & (s < HR * HP) & (hc >= 1) & (hc <= TW) & !(top & (hr == 0)) & !(bot & (hr == HR - 1));
     const unsigned long a = (unsigned long)base + (unsigned long)(unsigned)(hr * x_rs + (hc - 1) * x_ps);
     const unsigned long z = (unsigned long)g_zero_page_halo;
-    hdma1(reinterpret_cast<const void*>(ok ? a : z), lds0 + nb * HBUF + wave * PLANE + j * 1024);
+    dma1_lane(reinterpret_cast<const void*>(ok ? a : z), lds0 + nb * HBUF + wave * PLANE + j * 1024);
   };
   auto halo_base = [&](int tile, int h) {
     const int bb = tile / tiles_per_img, rr = (tile - bb * tiles_per_img) * TR;
@@ -203,7 +157,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   issue_w(wk_of(0), 0);
   issue_w(wk_of(1 % NKT), 1);
   HWAIT(0);
-  hbar();
+  bar();
   int st_cur = 0, st_pre = 2, q_pre = 2 % NKT;                  // ring state: stage being consumed, stage / step-in-tile being prefetched
   int buf = 0;                                                  // halo buffer of the current phase
 #define H_STAMP(acc_)
@@ -279,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
         if (TAP >= 1 && TAP <= NPIECE) { if (pre_w) HWAIT(3); else HWAIT(1); }
         else { if (pre_w) HWAIT(2); else HWAIT(0); }
         H_STAMP(ckV);
-        hbar();
+        bar();
         H_STAMP(ckW);
         // ---- region B: the 20 MFMAs of chunk 1; between them the halo piece of the next phase (address arithmetic + one LDS-DMA) and
         // the 9 fragment reads of the next tap's chunk 0
@@ -299,7 +253,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
               const int lr = lane_o & 15;
               const int fr_o = ((lr >> 3) & 1) * 2 + ((lr >> 1) & 1), fc_o = ((lr >> 2) & 1) * 2 + (lr & 1);
               const size_t pix = (size_t)(b * p.H + r0 + blk_r(i) * 4 + fr_o) * p.W + blk_c(i) * 4 + fc_o;
-              xf0[i] = hgload16(X2 + pix * p.x2_cstride + lq * 8);      // asynchronous: certified by the counted wait of the tail step
+              xf0[i] = gload16(X2 + pix * p.x2_cstride + lq * 8);      // asynchronous: certified by the counted wait of the tail step
             }
           }
         }
@@ -356,7 +310,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
         for (int j = 0; j < NT; ++j) acc[i][j] = mma_chunk<bf16>(wf0[j], xf0[i], acc[i][j]);
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      hbar();
+      bar();
       advance();
       H_STAMP(ckT);
     }

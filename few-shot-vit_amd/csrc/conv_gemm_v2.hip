@@ -19,34 +19,15 @@
 #include "conv_gemm.h"
 #include <type_traits>
 
-#include "fsvit_common.h"
+#include "lds_dma.h"
 
 namespace FSVIT_NS {
 
 __device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];
 
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// LDS-DMA issued through inline asm so hipcc's waitcnt pass does not see it: with the builtin, any
-// ordinary global load in the loop (the epilogue's bias fetch was enough) made the pass put
-// `s_waitcnt vmcnt(0)` in front of the first ds_read of EVERY k-step, i.e. drain the DMA right after
-// issuing it (cdna_hip_programming.md 5 "three .s-level traps" (b)).  Hidden from the pass, the DMA
-// is ordered by hand: dma_wait_all() before the barrier that publishes a buffer.  The compiler's own
-// counted waits for its ordinary loads stay safe: extra in-flight operations only make vmcnt(N)
-// stricter.  M0 (the LDS destination base) is written in the same statement that consumes it.
-__device__ __forceinline__ void dma16(const void* gsrc, unsigned lds_byte_addr) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_byte_addr)
-      : "memory");
-}
-// N LDS-DMAs to destinations lds_byte_addr + i * 4096 in ONE statement: M0 is saved / restored once and
+// LDS-DMA through inline asm, ordered by hand (lds_dma.h; the epilogue's bias fetch was enough to make hipcc's waitcnt
+// pass drain a builtin DMA at every k-step): dma_wait_all() before the barrier that publishes a buffer.  Single pieces
+// are dma1_lane(); N LDS-DMAs to destinations lds_byte_addr + i * 4096 in ONE statement: M0 is saved / restored once and
 // advanced with s_add (the per-DMA form spends 5 scalar instructions on M0 for every load).
 __device__ __forceinline__ void dma16x4(const void* s0, const void* s1, const void* s2, const void* s3, unsigned lds_byte_addr) {
   unsigned keep;
@@ -85,7 +66,6 @@ __device__ __forceinline__ void dma16x2(const void* s0, const void* s1, unsigned
       : "memory", "scc");
 }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(lptr_t)p; }
 
 // ---- two-limb ("x2") arithmetic on fp32 storage: every fp32 operand value v is fed to the 16-bit MFMA as the pair (hi, lo), hi = v rounded
 // to the 16-bit type, lo = (v - hi) rounded to it (v - hi is exact in fp32), interleaved along K: one 16-byte chunk = 4 fp32 values = 8
@@ -232,7 +212,7 @@ __global__ __launch_bounds__(256, MINB) void conv_gemm_v2_kernel(const ConvGemmP
       for (int i = 0; i < A_IT; ++i) {
         const T* src = (cok && rowok[i]) ? X2 + (size_t)pixnat[i] * p.x2_cstride + sc * EPC : zero;
         if constexpr (LIMBS) areg[i] = *reinterpret_cast<const u32x4*>(src);
-        else dma16(src, la + i * (32 * 128));
+        else dma1_lane(src, la + i * (32 * 128));
       }
     }
     const T* bs[B_IT];
@@ -242,7 +222,7 @@ __global__ __launch_bounds__(256, MINB) void conv_gemm_v2_kernel(const ConvGemmP
     else if constexpr (B_IT == 2) dma16x2(bs[0], bs[1], lb);
     else {
 #pragma unroll
-      for (int jj = 0; jj < B_IT; ++jj) dma16(bs[jj], lb + jj * (32 * 128));
+      for (int jj = 0; jj < B_IT; ++jj) dma1_lane(bs[jj], lb + jj * (32 * 128));
     }
   };
 

@@ -26,33 +26,11 @@
 #include "conv_gemm.h"
 #include <type_traits>
 
-#include "fsvit_common.h"
+#include "lds_dma.h"
 
 namespace FSVIT_NS {
 
-typedef __attribute__((address_space(3))) void* lptr256_t;
-
-// two 1 KiB LDS-DMAs: per-lane 32-bit byte offsets on one scalar base
-__device__ __forceinline__ void dma2(unsigned off0, unsigned off1, const void* sbase, unsigned lds0, unsigned lds1) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %3\n\t"
-      "s_mov_b32 m0, %5\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off0), "v"(off1), "s"(sbase), "s"(lds0), "s"(lds1)
-      : "memory");
-}
 #define WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-__device__ __forceinline__ void bar() {
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 constexpr int G_BM = 256, G_BN = 256, G_STAGE = 65536, G_BOFF = 32768;
 
@@ -72,7 +50,7 @@ __device__ __forceinline__ void gemm256_body(const ConvGemmParams& p, const int 
   constexpr int TMH = WM_ROWS / 32, TNH = WN_COLS / 32;        // 16-row tiles per A half / 16-column tiles per B half of a wave
   const int wm = LIMBS ? wave >> 1 : wave >> 2, wn = LIMBS ? wave & 1 : wave & 3;
   const int lrow = lane & 15, lq = lane >> 4;
-  const unsigned lds0 = (unsigned)(size_t)(lptr256_t)smem;
+  const unsigned lds0 = lds_addr(smem);
 
   // LDS read bases of this lane (row part + the two swizzled 16-byte k-chunk slots of the 128-byte row)
   const unsigned sw0 = (unsigned)((lq ^ (lrow & 7)) << 4), sw1 = (unsigned)(((4 + lq) ^ (lrow & 7)) << 4);

@@ -42,13 +42,12 @@
 
 #include <type_traits>
 
-#include "fsvit_common.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 namespace FSVIT_NS {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) void* lptrm_t;
 
 namespace {
 
@@ -57,113 +56,10 @@ constexpr int MR_NST = 4;                       // ring slots
 constexpr int mr_slot_frags(int C) { return C == 384 ? 24 : 32; }
 constexpr int MR_NW = 4;                        // waves per workgroup (one per SIMD)
 constexpr int MR_FD = 6;                        // weight fragments read ahead of the MFMAs that consume them
+constexpr int MR_LDS_MAX = 160 * 1024;          // LDS of a CU
+using yes_t = std::integral_constant<bool, true>;
+using no_t = std::integral_constant<bool, false>;
 
-// This wave's share of one ring slot: PW = 8 (6) consecutive 1 KiB LDS-DMAs, source = sbase + voff + i * 1024, destination = lds + i * 1024.
-// The immediate offset of global_load_lds moves the LDS destination together with the global source (tools/probes/
-// ldsdma_offset.hip, measured on gfx950), so a linear copy needs no address arithmetic; the 13-bit offset field covers 4 pieces.
-template <int PW> __device__ __forceinline__ void mr_dma(unsigned voff, const void* sbase, unsigned lds) {
-  static_assert(PW == 8 || PW == 6 || PW == 4 || PW == 3 || PW == 2, "pieces per wave and slot");
-  unsigned keep;
-  if constexpr (PW == 2)
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds)
-        : "memory");
-  else if constexpr (PW == 4)
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds)
-        : "memory");
-  else if constexpr (PW == 3)
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(lds)
-        : "memory");
-  else if constexpr (PW == 8)
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:2048\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:3072\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %3\n\t"
-        "global_load_lds_dwordx4 %2, %3 offset:1024\n\t"
-        "global_load_lds_dwordx4 %2, %3 offset:2048\n\t"
-        "global_load_lds_dwordx4 %2, %3 offset:3072\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "v"(voff + 4096u), "s"(sbase), "s"(lds), "s"(lds + 4096u)
-        : "memory");
-  else
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:1024\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:2048\n\t"
-        "global_load_lds_dwordx4 %1, %3 offset:3072\n\t"
-        "s_mov_b32 m0, %5\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %3\n\t"
-        "global_load_lds_dwordx4 %2, %3 offset:1024\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "v"(voff + 4096u), "s"(sbase), "s"(lds), "s"(lds + 4096u)
-        : "memory");
-}
-// One 1 KiB piece.  A VMEM instruction of 64 x 16 bytes keeps the wave's issue stage for ~64 cycles; back to back they queue behind
-// each other and hold up the MFMAs that follow, so inside the chunk loop the refill goes out one piece at a time, pieces >= 4 MFMAs apart.
-__device__ __forceinline__ void mr_dma1(unsigned voff, const void* sbase, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds)
-      : "memory");
-}
-__device__ __forceinline__ void mr_bar() {
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// x rows are loaded through inline asm: a compiler-visible global_load inside the tile loop makes hipcc's waitcnt pass carry
-// "x load pending" around the back edge and plant s_waitcnt vmcnt(15..0) between the MFMAs of the chunk loop - which drains the
-// LDS-DMA ring (issued from asm, invisible to that pass) at every step.
-__device__ __forceinline__ u32x4 mr_gload16(const void* p) {
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
 // s_waitcnt vmcnt(0) with N (a multiple of 4) asm-loaded registers threaded through, so that no use can be scheduled above the wait
 template <int N> __device__ __forceinline__ void mr_wait_loads(u32x4* a) {
   static_assert(N % 4 == 0 && N >= 4, "groups of 4");
@@ -171,12 +67,6 @@ template <int N> __device__ __forceinline__ void mr_wait_loads(u32x4* a) {
 #pragma unroll
   for (int o = 4; o < N; o += 4) asm volatile("" : "+v"(a[o]), "+v"(a[o + 1]), "+v"(a[o + 2]), "+v"(a[o + 3]) :: "memory");
 }
-__device__ __forceinline__ unsigned mr_pk2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) bf16 bf16x2_t;
-  const bf16x2_t v = {(bf16)a, (bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-
 // MFMAs are issued from inline asm with the register FILE of the accumulator spelled out: the 256 output accumulators must
 // live in AGPRs and everything else (x rows, GEMM1 accumulators, fragments) in arch VGPRs.  Left to hipcc's allocator the
 // kernel kept the outputs in VGPRs, spilled the x rows to scratch and reloaded one before every MFMA behind s_waitcnt vmcnt(0).
@@ -268,7 +158,7 @@ template <int NKS, int C> __device__ __forceinline__ void mr_layernorm_rows(u32x
     const bf16x8 v = __builtin_bit_cast(bf16x8, xr[s]);
     u32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = mr_pk2(fmaf((float)v[2 * e], rstd, nmr), fmaf((float)v[2 * e + 1], rstd, nmr));
+    for (int e = 0; e < 4; ++e) o[e] = pk2(fmaf((float)v[2 * e], rstd, nmr), fmaf((float)v[2 * e + 1], rstd, nmr));
     xr[s] = o;
   }
   static_assert(NKS % 4 == 0, "groups of 4");
@@ -276,6 +166,131 @@ template <int NKS, int C> __device__ __forceinline__ void mr_layernorm_rows(u32x
   for (int o = 0; o + 4 < NKS; o += 4) asm volatile("" : "+v"(xr[o]), "+v"(xr[o + 1]), "+v"(xr[o + 2]), "+v"(xr[o + 3]) :: "memory");
   asm volatile("s_nop 7" : "+v"(xr[NKS - 4]), "+v"(xr[NKS - 3]), "+v"(xr[NKS - 2]), "+v"(xr[NKS - 1]) :: "memory");
 }
+
+// ---- The weight ring of the rows kernels.  A kernel's weight image is a periodic sequence of n_img slot images of SLOT bytes (fragment-major, in
+// consumption order, repeated for every tile of the persistent workgroup); NST LDS slots at the start of the workgroup's LDS hold the images in
+// flight.  Every wave copies its share of an image - PW consecutive 1 KiB pieces at wave * PW KiB - by linear LDS-DMA, and the only workgroup-wide
+// synchronisation of these kernels is the ring's barrier, one per slot image:
+//     prime(n_img)            images 0 .. NST-2 go out
+//     per image n:            wait_bar()  [barrier n]  ->  issue() / issue_piece(0 .. PW-1) of image n + NST-1  ->  slot_base(): read image n
+// At NST = 4 image n is therefore issued right after barrier n-3, waited for (counted vmcnt: the PW DMAs of the newest image may stay in flight)
+// before barrier n-1, and first read after barrier n.  LDS-DMA data is ordered for a ds_read only by the ISSUING wave's counted vmcnt followed by
+// a barrier the reader passes, and the read must sit one barrier interval AFTER that wait (cdna_hip_programming.md, 8-phase template): a build of
+// mlp_rows_kernel that waited for image n right before barrier n and read it right after produced rare inf tiles in the first 2 KB of a slot,
+// coming and going with code placement.  Barrier n also certifies that every wave has finished reading the slot refilled next.  Row loads and
+// stores share the vmcnt queue with the DMAs: loads complete in order among loads, so "at most PW operations outstanding" still implies that every
+// older image has landed (stores can only make the wait longer).  A kernel drains the queue for its first row loads and passes open() once before
+// its first read; no DMA may be in flight into the LDS of a finished workgroup: drain() ends every kernel.
+template <int SLOT, int PW, int NST>
+struct WeightRing {
+  static constexpr int WSH = PW * 1024;         // a wave's share of a slot image
+  unsigned char* const smem;
+  const unsigned char* const wimg;
+  const int wave, lane;
+  const unsigned lds0, voff;                    // LDS address of slot 0; this lane's 16 bytes inside a slot image
+  int n_img = 1;                                // period of the image sequence
+  int issue_img = 0, issue_slot = 0, slot = 0;  // next image to issue, the slot it goes to; the slot read next
+  bool first = true;
+
+  __device__ __forceinline__ WeightRing(unsigned char* smem_, const unsigned char* wimg_, int wave_, int lane_)
+      : smem(smem_), wimg(wimg_), wave(wave_), lane(lane_), lds0(lds_addr(smem_)), voff((unsigned)(wave_ * WSH + lane_ * 16)) {}
+  __device__ __forceinline__ const unsigned char* src() const { return wimg + (size_t)issue_img * SLOT; }
+  __device__ __forceinline__ unsigned dst() const { return lds0 + issue_slot * SLOT + wave * WSH; }
+  __device__ __forceinline__ void advance(const int last) {
+    issue_img = issue_img == last ? 0 : issue_img + 1;
+    issue_slot = issue_slot == NST - 1 ? 0 : issue_slot + 1;
+  }
+  __device__ __forceinline__ void advance() { advance(n_img - 1); }
+  __device__ __forceinline__ void issue() {
+    const unsigned char* const s = src();
+    const unsigned d = dst();
+    const int last = n_img - 1;      // (formed ahead of the DMA statement: where hipcc had it before the ring was a struct)
+    dma_n<PW>(voff, s, d);
+    advance(last);
+  }
+  // the same refill piece by piece (0 .. PW-1 in order), each placed between MFMAs of the interval that follows wait_bar()
+  __device__ __forceinline__ void issue_piece(int piece) {
+    dma1(voff + piece * 1024, src(), dst() + piece * 1024);
+    if (piece == PW - 1) advance();
+  }
+  __device__ __forceinline__ void prime(int n_img_) {
+    n_img = n_img_;
+#pragma unroll
+    for (int i = 0; i < NST - 1; ++i) issue();
+  }
+  // all but the newest LEFT DMAs of this wave have landed, then the barrier.  LGKM: this wave's own LDS stores are complete before it, too.
+  template <bool LGKM = false, int LEFT = PW> __device__ __forceinline__ void wait_bar() {
+    if constexpr (LGKM) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(LEFT) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LEFT) : "memory");
+    bar();
+  }
+  // one barrier between a kernel's first vmcnt(0) (its row loads; the primed images landed with them) and the first read of image 0
+  __device__ __forceinline__ void open() {
+    if (first) { bar(); first = false; }
+  }
+  __device__ __forceinline__ void next_slot() { slot = slot == NST - 1 ? 0 : slot + 1; }
+  // this lane's first fragment byte of the slot read next; the ring moves on.  Opaque: an unrolled loop walks the ring with a fixed period, and
+  // hipcc otherwise hoists one address VGPR per fragment beyond the 64 KB ds_read offset field (40 registers, spills); one base per slot +
+  // immediate offsets is what is wanted.
+  __device__ __forceinline__ const unsigned char* slot_base() {
+    unsigned a = slot * SLOT + lane * 16;
+    asm volatile("" : "+v"(a));
+    const unsigned char* sp = smem + a;
+    next_slot();
+    return sp;
+  }
+  __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+};
+
+// ---- One ring slot of a row-wise GEMM chunk: SLF MFMAs of 32 token rows (xr[i]: B operands) against the slot's SLF fragments at sp (A operands),
+// fragments read FD ahead; nothing moves between the MFMAs (sched_barrier).  SW: operands swapped (A = rows, B = fragment -> D[token][channel]).
+template <bool SW, int SLF, int FD> __device__ __forceinline__ void rows_chunk(const unsigned char* sp, const u32x4* xr, f32x16& acc) {
+  u32x4 fr[FD];
+#pragma unroll
+  for (int i = 0; i < FD; ++i) fr[i] = *reinterpret_cast<const u32x4*>(sp + i * 1024);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < SLF; ++i) {
+    if constexpr (SW) mfma32_v(xr[i], fr[i % FD], acc);
+    else mfma32_v(fr[i % FD], xr[i], acc);
+    if (i + FD < SLF) fr[i % FD] = *reinterpret_cast<const u32x4*>(sp + (i + FD) * 1024);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// 16 accumulators (f32x16 or float[16]) -> the two k-steps of an MFMA operand: o[t] = accumulators 8 t .. 8 t + 7
+template <typename A> __device__ __forceinline__ void pack2(const A& acc, u32x4 (&o)[2]) {
+#pragma unroll
+  for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[tt][e] = pk2(acc[8 * tt + 2 * e], acc[8 * tt + 2 * e + 1]);
+}
+// LDS geometry of the kernels below, stated once: the weight ring first, the kernel's tables behind it.  A kernel takes its offsets from here and its
+// launcher the dynamic LDS size.
+template <int C, int HID, bool LN> struct mlp_rows_geom {
+  static constexpr int SLF = mr_slot_frags(C), SLOT = SLF * 1024;      // ring slot: SLF fragments
+  static constexpr int OFF_B1 = MR_NST * SLOT;                         // conv1 / fc1 bias [HID] in accumulator order
+  static constexpr int OFF_BP = OFF_B1 + HID * 4;                      // LN: proj bias [C], fc2 bias [C] (channel order)
+  static constexpr int OFF_GTAB = OFF_BP + (LN ? 2 * C * 4 : 0);       // GELU table of the bf16 build (fsvit_common.h gelu_tab)
+  static constexpr int LDS_BYTES = OFF_GTAB + gelu_tab::BYTES;
+  static_assert(LDS_BYTES <= MR_LDS_MAX, "LDS budget");
+};
+// ln_gemm_rows_kernel and qkv_attn_rows_kernel: ring + bias [N]
+template <int C, int SPC, int NST> struct gemm_rows_geom {
+  static constexpr int NKS = C / 16, SLF = NKS / SPC, SLOT = SLF * 1024;      // k-steps; fragments per ring slot; SPC slots per chunk
+  static constexpr int OFF_BIAS = NST * SLOT;
+  static constexpr int lds_bytes(int N) { return OFF_BIAS + N * 4; }
+  static_assert(NKS % SLF == 0 && SLF % MR_NW == 0, "whole slots");
+  static_assert(OFF_BIAS <= MR_LDS_MAX, "LDS budget of the ring (the N * 4 bytes of the bias table are a run-time term: hipFuncSetAttribute refuses an excess)");
+};
+// vit_attn_rows_kernel: ring, the packed K and V^T fragments of all row blocks of a head, bias [N]
+template <int C, int HDC> struct vit_attn_geom {
+  static constexpr int NWV = 8, NST = 3, SLF = C / 16, SLOT = SLF * 1024;
+  static constexpr int KV1 = HDC * 2 * 1024;                               // one row block's packed K (or V^T) fragments of a head
+  static constexpr int OFF_K = NST * SLOT, OFF_V = OFF_K + NWV * KV1, OFF_BIAS = OFF_V + NWV * KV1;
+  static constexpr int lds_bytes(int N) { return OFF_BIAS + N * 4; }
+  static_assert(OFF_BIAS <= MR_LDS_MAX, "LDS budget of ring + K + V^T (the N * 4 bytes of the bias table are a run-time term)");
+};
 
 }  // namespace
 
@@ -294,8 +309,9 @@ template <int C, int HID, int RB, int KC, bool LN>
 __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict__ X, bf16* __restrict__ Y, const unsigned char* __restrict__ wimg,
                                                           const float* __restrict__ b1img, const float* __restrict__ b2, const bf16* __restrict__ CTX,
                                                           const float* __restrict__ bproj, const float ln_eps, const int M, const int n_tiles) {
+  using G = mlp_rows_geom<C, HID, LN>;
   constexpr int NCT = C / 32, NKS = C / 16, NCH = HID / 32;
-  constexpr int SLF = mr_slot_frags(C), MR_SLOT = SLF * 1024;      // ring slot: SLF fragments
+  constexpr int SLF = G::SLF, MR_SLOT = G::SLOT;
   constexpr int PW = SLF / MR_NW, WSH = PW * 1024;                 // LDS-DMA pieces per wave and slot; a wave's share of a slot image
   constexpr int SL = RB * NKS;                                     // MFMA slots per group (GEMM1 or GEMM2 of one chunk): 32, or 24 at C = 384
   constexpr int PKS = KC / 16, PFR = PKS * NCT;          // proj: k-steps of 16 ctx channels, fragments in (k-step outer, c-tile inner) order
@@ -308,16 +324,15 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
   static_assert(!LN || (KC > 0 && RB == 1), "the LayerNorm variant continues from the proj prologue");
   static_assert(NCH % 2 == 0, "the hidden-chunk loop runs bodies in pairs behind a fixed head and tail: an even number of 32-wide chunks");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* const b1tab = reinterpret_cast<float*>(smem + MR_NST * MR_SLOT);
-  float* const bptab = b1tab + HID;                      // LN: proj bias, fc2 bias (channel order)
+  float* const b1tab = reinterpret_cast<float*>(smem + G::OFF_B1);
+  float* const bptab = reinterpret_cast<float*>(smem + G::OFF_BP);
   float* const b2tab = bptab + C;
-  // GELU table of the bf16 build (fsvit_common.h gelu_tab, round 6) behind the bias tables; TABC = LDS address of its centre (wave-uniform)
-  unsigned char* const gtab = smem + MR_NST * MR_SLOT + HID * 4 + (LN ? 2 * C * 4 : 0);
+  unsigned char* const gtab = smem + G::OFF_GTAB;        // tabc = LDS address of the table's centre (wave-uniform)
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 31, kh = lane >> 5;
-  const unsigned lds0 = (unsigned)(size_t)(lptrm_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   const unsigned voff = (unsigned)(wave * WSH + lane * 16);            // this lane's 16 bytes inside a slot image
   if ((int)blockIdx.x >= n_tiles) return;
 
@@ -326,18 +341,14 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
   if constexpr (LN)
     for (int i = t; i < C; i += MR_NW * 64) { bptab[i] = bproj[i]; b2tab[i] = b2[i]; }
   if constexpr (gelu_tab::ON) gelu_tab::fill(gtab, t, MR_NW * 64);
-  const unsigned tabc = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lptrm_t)gtab + 2u * gelu_tab::TN);
+  const unsigned tabc = __builtin_amdgcn_readfirstlane(lds_addr(gtab) + 2u * gelu_tab::TN);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");        // table written before the first ring barrier publishes it
 
-  // ring: slot image n (the weight image is a sequence of NCH * PPC slot images, repeated for every tile) is issued right after
-  // barrier n-3, waited for (counted vmcnt: 8 DMAs per wave and slot) before barrier n-1 and first read after barrier n: LDS-DMA
-  // data is ordered for a ds_read only by the issuing wave's counted vmcnt followed by a barrier the reader passes, and the read
-  // must sit one barrier interval AFTER that wait (cdna_hip_programming.md, 8-phase template).  A build that waited for image n
-  // right before barrier n and read it right after produced rare inf tiles in the first 2 KB of a slot, coming and going with
-  // code placement.  Barrier n also certifies that every wave has finished reading the slot refilled next.
+  // the ring, spelled out (the ordering rule is on WeightRing above; through the struct three variants of this kernel came out with instructions
+  // moved).  The weight image is a sequence of PSLOTS + NCH * PPC slot images, 8 or 6 DMAs per wave and slot.
   int issue_img = 0, issue_slot = 0;
   auto issue = [&]() {
-    mr_dma<PW>(voff, wimg + (size_t)issue_img * MR_SLOT, lds0 + issue_slot * MR_SLOT + wave * WSH);
+    dma_n<PW>(voff, wimg + (size_t)issue_img * MR_SLOT, lds0 + issue_slot * MR_SLOT + wave * WSH);
     issue_img = issue_img == PSLOTS + NCH * PPC - 1 ? 0 : issue_img + 1;
     issue_slot = issue_slot == MR_NST - 1 ? 0 : issue_slot + 1;
   };
@@ -347,7 +358,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
   bool first = true;
   auto ring_wait = [&]() {
     asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PW) : "memory");     // all but the newest slot image of this wave have landed: the image read after the NEXT barrier
-    mr_bar();
+    bar();
   };
   auto ring_sync = [&]() {
     ring_wait();
@@ -355,7 +366,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
   };
   // the same refill piece by piece (0..7 in order), each placed between MFMAs of the interval that follows ring_wait()
   auto issue1 = [&](int piece) {
-    mr_dma1(voff + piece * 1024, wimg + (size_t)issue_img * MR_SLOT, lds0 + issue_slot * MR_SLOT + wave * WSH + piece * 1024);
+    dma1(voff + piece * 1024, wimg + (size_t)issue_img * MR_SLOT, lds0 + issue_slot * MR_SLOT + wave * WSH + piece * 1024);
     if (piece == PW - 1) {
       issue_img = issue_img == PSLOTS + NCH * PPC - 1 ? 0 : issue_img + 1;
       issue_slot = issue_slot == MR_NST - 1 ? 0 : issue_slot + 1;
@@ -370,7 +381,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
     for (int q = 0; q < 2; ++q)
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        idf[q][e] = mr_pk2(ch == 16 * kh + 8 * q + 2 * e ? 1.0f : 0.0f, ch == 16 * kh + 8 * q + 2 * e + 1 ? 1.0f : 0.0f);
+        idf[q][e] = pk2(ch == 16 * kh + 8 * q + 2 * e ? 1.0f : 0.0f, ch == 16 * kh + 8 * q + 2 * e + 1 ? 1.0f : 0.0f);
   }
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     // ---- this wave's 32 RB token rows -> registers (tail rows re-read the last valid row; their results are never stored)
@@ -391,7 +402,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int s = 0; s < NKS; ++s) xr[rb][s] = mr_gload16(X + rowoff[rb] + 32 * (s >> 1) + 8 * (s & 1));
+        for (int s = 0; s < NKS; ++s) xr[rb][s] = gload16(X + rowoff[rb] + 32 * (s >> 1) + 8 * (s & 1));
       mr_wait_loads<RB * NKS>(&xr[0][0]);
     };
     f32x16 yacc[RB][NCT];
@@ -413,9 +424,9 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int ks = 0; ks < PKS; ++ks) cr[rb][ks] = mr_gload16(CTX + (size_t)mrow[rb] * KC + 16 * ks + 8 * kh);
+        for (int ks = 0; ks < PKS; ++ks) cr[rb][ks] = gload16(CTX + (size_t)mrow[rb] * KC + 16 * ks + 8 * kh);
       mr_wait_loads<RB * PKS>(&cr[0][0]);
-      if (first) { mr_bar(); first = false; }
+      if (first) { bar(); first = false; }
 #pragma unroll
       for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -462,13 +473,13 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
             for (int e = 0; e < 4; ++e) {
               float a0 = yacc[rb][ct][8 * q + 2 * e] + (float)xv[2 * e], a1 = yacc[rb][ct][8 * q + 2 * e + 1] + (float)xv[2 * e + 1];
               if constexpr (LN) { a0 += pb[2 * e]; a1 += pb[2 * e + 1]; }
-              o[e] = mr_pk2(a0, a1);
+              o[e] = pk2(a0, a1);
             }
             xr[rb][2 * ct + q] = o;
           }
     } else {
       load_x();
-      if (first) { mr_bar(); first = false; }             // one barrier between the drain above and the first reads of image 0
+      if (first) { bar(); first = false; }             // one barrier between the drain above and the first reads of image 0
     }
     if constexpr (LN) {
       // residual: yacc := x1 through the identity fragments (accumulator row n of tile ct <-> channel 16 (n>>2 & 1) + 4 (n>>3) + (n & 3), the k slot
@@ -573,7 +584,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
 #pragma unroll
       for (int h = 0; h < 2; ++h) ge[q][h] = __builtin_amdgcn_rcpf(ge[q][h]);
     };
-    auto gC = [&](int q, u32x4 (&hp)[RB][2]) { hp[q >> 3][(q >> 2) & 1][q & 3] = mr_pk2(gx[q][0] * ge[q][0], gx[q][1] * ge[q][1]); };
+    auto gC = [&](int q, u32x4 (&hp)[RB][2]) { hp[q >> 3][(q >> 2) & 1][q & 3] = pk2(gx[q][0] * ge[q][0], gx[q][1] * ge[q][1]); };
     // Pair q starts at slot st(q) = q CAD2 / 2:  RB = 2: a pair every 3.5 slots (6 issue slots per MFMA), RB = 1: every 4 (6 / 6 / 4 / 5).
     // Seven per MFMA already stretch the MFMA slot by ~20 % (mfma_valu_overlap probe); six cost ~10 %.  The stage that reads the
     // accumulator (A1) may not slip behind the restart of its chain (slot 28 for row block 0, 46 for row block 1): the last pairs of
@@ -595,7 +606,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
       for (int q = 0; q < NP; ++q) {
         if constexpr (gelu_tab::ON) {
           if (m == st_a1(q)) {
-            tc[q] = mr_pk2(hacc[q >> 3][2 * (q & 7)], hacc[q >> 3][2 * (q & 7) + 1]);
+            tc[q] = pk2(hacc[q >> 3][2 * (q & 7)], hacc[q >> 3][2 * (q & 7) + 1]);
             asm("" : "+v"(tc[q]));                           // (opaque: otherwise the sign shift converts the two floats again)
           }
           if (m == st(q) + 1) ta[q] = gelu_tab::rebase(tc[q]);
@@ -645,7 +656,7 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
             else asm volatile("s_nop 15\n\ts_nop 3" : "+v"(hacc[0]));
           }
           if (GE) gelu_slot(m, hp_cur);
-          if (G1 && m == SL - 4) bias_init(0, jn);              // after the GELU's last direct read of row block 0's accumulator              // after the GELU's last direct read of row block 0's accumulator
+          if (G1 && m == SL - 4) bias_init(0, jn);              // after the GELU's last direct read of row block 0's accumulator
           __builtin_amdgcn_sched_barrier(0);
         }
       } else if (GE) {                                     // body 0: the GELU of chunk 0 on its own
@@ -677,8 +688,6 @@ __global__ __launch_bounds__(256, 1) void mlp_rows_kernel(const bf16* __restrict
         __builtin_amdgcn_sched_barrier(0);
       }
     };
-    using yes_t = std::integral_constant<bool, true>;
-    using no_t = std::integral_constant<bool, false>;
 
     bias_init(0, 0);
     body(no_t{}, no_t{}, yes_t{}, 0, hpA, hpA);            // GEMM1(0)   (the chain of row block 1 starts from bias_init inside)
@@ -756,25 +765,24 @@ template <int C, bool LN, int SPC, int NST, bool GATHER = false>
 __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* __restrict__ X, bf16* __restrict__ Y, const unsigned char* __restrict__ wimg,
                                                               const float* __restrict__ bias, const float ln_eps, const int M, const int N,
                                                               const int n_tiles, const int gH = 0, const float* __restrict__ pos = nullptr) {
-  constexpr int NKS = C / 16, SLF = NKS / SPC;                // k-steps; fragments per ring slot; SPC slots per chunk
-  constexpr int SLOT = SLF * 1024, PW = SLF / MR_NW, WSH = PW * 1024, FD = 4, LAG = (NST - 3) * PW;
-  static_assert(NKS % SLF == 0 && SLF % MR_NW == 0, "whole slots");
+  using G = gemm_rows_geom<C, SPC, NST>;
+  constexpr int NKS = G::NKS, SLF = G::SLF, SLOT = G::SLOT, PW = SLF / MR_NW, WSH = PW * 1024, FD = 4, LAG = (NST - 3) * PW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* const btab = reinterpret_cast<float*>(smem + NST * SLOT);
+  float* const btab = reinterpret_cast<float*>(smem + G::OFF_BIAS);
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 31, kh = lane >> 5;
-  const unsigned lds0 = (unsigned)(size_t)(lptrm_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   const unsigned voff = (unsigned)(wave * WSH + lane * 16);
   const int nch = N / 32, n_img = nch * SPC;
   if ((int)blockIdx.x >= n_tiles) return;
   for (int i = t; i < N; i += MR_NW * 64) btab[i] = bias ? bias[i] : 0.0f;
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
-  // the ring of mlp_rows_kernel: image n issued after barrier n-3, waited for before barrier n-1, first read after barrier n
+  // WeightRing spelled out (through the struct the GATHER variant came out with instructions moved)
   int issue_img = 0, issue_slot = 0, slot = 0;
   auto issue = [&]() {
-    mr_dma<PW>(voff, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + wave * WSH);
+    dma_n<PW>(voff, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + wave * WSH);
     issue_img = issue_img == n_img - 1 ? 0 : issue_img + 1;
     issue_slot = issue_slot == NST - 1 ? 0 : issue_slot + 1;
   };
@@ -804,7 +812,7 @@ __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* 
       for (int s = 0; s < NKS; ++s) xr[s] = mr_gload16s(X + row * C + 32 * (s >> 1) + 16 * kh + 8 * (s & 1));
     }
     mr_wait_loads<NKS>(&xr[0]);
-    if (first) { mr_bar(); first = false; }
+    if (first) { bar(); first = false; }
     if constexpr (LN) mr_layernorm_rows<NKS, C>(xr, ln_eps);
     bf16* const yrow = Y + row * N + 16 * kh;
     u32x4 po0 = {0u, 0u, 0u, 0u}, po1 = {0u, 0u, 0u, 0u};      // LGR_SPREAD: the previous chunk's output, stored between the MFMAs of this one
@@ -814,7 +822,7 @@ __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* 
       u32x4 posv[4];
       if constexpr (GATHER) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) posv[g] = mr_gload16(posrow + j * 32 + 4 * g);
+        for (int g = 0; g < 4; ++g) posv[g] = gload16(posrow + j * 32 + 4 * g);
       }
       {
         const float* bp = btab + j * 32 + kh * 16;
@@ -828,7 +836,7 @@ __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* 
 #pragma unroll
       for (int h = 0; h < SPC; ++h) {
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LAG) : "memory");
-        mr_bar();
+        bar();
         // A 1 KB VMEM instruction holds the wave's issue stage for ~64 cycles (mlp_rows): the refill of the slot freed by this barrier goes out one
         // piece at a time, 4 MFMAs apart, and the previous chunk's two stores in the gaps of the chunk's first slot.
         const unsigned char* const dsrc = wimg + (size_t)issue_img * SLOT;
@@ -848,7 +856,7 @@ __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* 
           mfma32_v(fr[i % FD], xr[h * SLF + i], hacc);
           if (i + FD < SLF) fr[i % FD] = *reinterpret_cast<const u32x4*>(sp + (i + FD) * 1024);
           constexpr int EVERY = SLF / PW;
-          if (i % EVERY == 1 && i / EVERY < PW) mr_dma1(voff + (i / EVERY) * 1024, dsrc, ddst + (i / EVERY) * 1024);
+          if (i % EVERY == 1 && i / EVERY < PW) dma1(voff + (i / EVERY) * 1024, dsrc, ddst + (i / EVERY) * 1024);
           if (h == 0 && j > 0 && mok) {
             if (i == 3) mr_gstore16(yrow + (j - 1) * 32, po0);
             if (i == EVERY + 3) mr_gstore16(yrow + (j - 1) * 32 + 8, po1);
@@ -870,8 +878,8 @@ __global__ __launch_bounds__(256, LGR_OCC) void ln_gemm_rows_kernel(const bf16* 
       u32x4 o0, o1;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        o0[e] = mr_pk2(hacc[2 * e], hacc[2 * e + 1]);
-        o1[e] = mr_pk2(hacc[8 + 2 * e], hacc[8 + 2 * e + 1]);
+        o0[e] = pk2(hacc[2 * e], hacc[2 * e + 1]);
+        o1[e] = pk2(hacc[8 + 2 * e], hacc[8 + 2 * e + 1]);
       }
       po0 = o0;
       po1 = o1;
@@ -902,29 +910,21 @@ template <int C, int HDC>
 __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __restrict__ X, bf16* __restrict__ CTX, const unsigned char* __restrict__ wimg,
                                                                const float* __restrict__ bias, const float scale_log2e, const int B, const int S,
                                                                const int heads, const int n_tiles) {
-  constexpr int NKS = C / 16, SPC = 2, SLF = NKS / SPC, NST = 4, FD = 4;
-  constexpr int SLOT = SLF * 1024, PW = SLF / MR_NW, WSH = PW * 1024;
+  constexpr int SPC = 2, NST = 4, FD = 4;
+  using G = gemm_rows_geom<C, SPC, NST>;
+  constexpr int NKS = G::NKS, SLF = G::SLF, PW = SLF / MR_NW;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* const btab = reinterpret_cast<float*>(smem + NST * SLOT);
+  float* const btab = reinterpret_cast<float*>(smem + G::OFF_BIAS);
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 31, kh = lane >> 5;
-  const unsigned lds0 = (unsigned)(size_t)(lptrm_t)smem;
-  const unsigned voff = (unsigned)(wave * WSH + lane * 16);
+  WeightRing<G::SLOT, PW, NST> ring(smem, wimg, wave, lane);
   const int HD = HDC * 32, N = 3 * heads * HD, n_img = (N / 32) * SPC;
   if ((int)blockIdx.x >= n_tiles) return;
   for (int i = t; i < N; i += MR_NW * 64) btab[i] = bias ? bias[i] : 0.0f;
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
-  int issue_img = 0, issue_slot = 0, slot = 0;
-  auto issue = [&]() {
-    mr_dma<PW>(voff, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + wave * WSH);
-    issue_img = issue_img == n_img - 1 ? 0 : issue_img + 1;
-    issue_slot = issue_slot == NST - 1 ? 0 : issue_slot + 1;
-  };
-#pragma unroll
-  for (int i = 0; i < NST - 1; ++i) issue();
-  bool first = true;
+  ring.prime(n_img);
   const int perm = 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3);      // fragment row r <-> channel perm of its chunk (pack kernel)
 
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -935,7 +935,7 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
 #pragma unroll
     for (int s = 0; s < NKS; ++s) xr[s] = mr_gload16s(X + row * C + 32 * (s >> 1) + 16 * kh + 8 * (s & 1));
     mr_wait_loads<NKS>(&xr[0]);
-    if (first) { mr_bar(); first = false; }
+    ring.open();
     bf16* const crow = CTX + row * (size_t)(heads * HD) + 16 * kh;
 
     // one chunk of 32 output channels: NKS MFMAs over the two ring slots of its fragments.  swapped: A = x rows, B = fragment -> D[token][channel]
@@ -943,24 +943,9 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
       constexpr bool SW = decltype(swapped_)::value;
 #pragma unroll
       for (int h2 = 0; h2 < SPC; ++h2) {
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PW) : "memory");
-        mr_bar();
-        issue();
-        unsigned a = slot * SLOT + lane * 16;
-        asm volatile("" : "+v"(a));
-        const unsigned char* sp = smem + a;
-        slot = slot == NST - 1 ? 0 : slot + 1;
-        u32x4 fr[FD];
-#pragma unroll
-        for (int i = 0; i < FD; ++i) fr[i] = *reinterpret_cast<const u32x4*>(sp + i * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < SLF; ++i) {
-          if constexpr (SW) mfma32_v(xr[h2 * SLF + i], fr[i % FD], acc);
-          else mfma32_v(fr[i % FD], xr[h2 * SLF + i], acc);
-          if (i + FD < SLF) fr[i % FD] = *reinterpret_cast<const u32x4*>(sp + (i + FD) * 1024);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+        ring.wait_bar();
+        ring.issue();
+        rows_chunk<SW, SLF, FD>(ring.slot_base(), xr + h2 * SLF, acc);
       }
       asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));          // wait states MFMA -> VALU read of the accumulator
     };
@@ -973,14 +958,6 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
         for (int e = 0; e < 4; ++e) acc[4 * g + e] = b[e];
       }
     };
-    auto pack2 = [&](const f32x16& acc, u32x4 (&o)[2]) {          // accumulators 8 t .. 8 t + 7 -> k-step t of an MFMA operand
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[tt][e] = mr_pk2(acc[8 * tt + 2 * e], acc[8 * tt + 2 * e + 1]);
-    };
-    using yes_t = std::integral_constant<bool, true>;
-    using no_t = std::integral_constant<bool, false>;
 
 #pragma unroll 1
     for (int h = 0; h < heads; ++h) {
@@ -1023,11 +1000,11 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
       }
       sum += __shfl_xor(sum, 32);
       const float inv = __builtin_amdgcn_rcpf(sum);
-      u32x4 pp[2];
+      u32x4 pp[2];      // pack2(pv, pp) kept inline: keeps this kernel's softmax schedule as it was
 #pragma unroll
       for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) pp[tt][e] = mr_pk2(pv[8 * tt + 2 * e], pv[8 * tt + 2 * e + 1]);
+        for (int e = 0; e < 4; ++e) pp[tt][e] = pk2(pv[8 * tt + 2 * e], pv[8 * tt + 2 * e + 1]);
 #pragma unroll
       for (int c = 0; c < HDC; ++c) {
         f32x16 acc;
@@ -1046,8 +1023,8 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
         u32x4 o0, o1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          o0[e] = mr_pk2(oacc[2 * e] * inv, oacc[2 * e + 1] * inv);
-          o1[e] = mr_pk2(oacc[8 + 2 * e] * inv, oacc[8 + 2 * e + 1] * inv);
+          o0[e] = pk2(oacc[2 * e] * inv, oacc[2 * e + 1] * inv);
+          o1[e] = pk2(oacc[8 + 2 * e] * inv, oacc[8 + 2 * e + 1] * inv);
         }
         if (ok) {
           mr_gstore16(crow + h * HD + c * 32, o0);
@@ -1056,7 +1033,7 @@ __global__ __launch_bounds__(256, 2) void qkv_attn_rows_kernel(const bf16* __res
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ring.drain();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1077,18 +1054,18 @@ template <int C, int HDC>
 __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __restrict__ X, bf16* __restrict__ CTX, const unsigned char* __restrict__ wimg,
                                                                const float* __restrict__ bias, const float eps, const float scale_log2e, const int B,
                                                                const int S, const int heads) {
-  constexpr int NWV = 8, NKS = C / 16, SLF = NKS, NST = 3, FD = 4;
-  constexpr int SLOT = SLF * 1024, PW = SLF / NWV, WSH = PW * 1024;
-  constexpr int KV1 = HDC * 2 * 1024;                               // one row block's packed K (or V^T) fragments of a head
+  using G = vit_attn_geom<C, HDC>;
+  constexpr int NWV = G::NWV, NKS = C / 16, SLF = G::SLF, NST = G::NST, FD = 4;
+  constexpr int SLOT = G::SLOT, PW = SLF / NWV, WSH = PW * 1024, KV1 = G::KV1;
   static_assert(SLF % NWV == 0 && (PW == 3 || PW == 4 || PW == 2), "pieces per wave");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const kx = smem + NST * SLOT;
-  unsigned char* const vx = kx + NWV * KV1;
-  float* const btab = reinterpret_cast<float*>(vx + NWV * KV1);
+  unsigned char* const kx = smem + G::OFF_K;
+  unsigned char* const vx = smem + G::OFF_V;
+  float* const btab = reinterpret_cast<float*>(smem + G::OFF_BIAS);
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int r = lane & 31, kh = lane >> 5;
-  const unsigned lds0 = (unsigned)(size_t)(lptrm_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   const unsigned voff = (unsigned)(wave * WSH + lane * 16);
   const int HD = HDC * 32, N = 3 * heads * HD, n_img = N / 32;
   const int NB = (S + 31) >> 5;
@@ -1096,9 +1073,10 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
   for (int i = t; i < N; i += NWV * 64) btab[i] = bias ? bias[i] : 0.0f;
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 
+  // WeightRing spelled out (through the struct the bf16 build numbered its VGPRs differently).  NST = 3: the wait for image n sits right before barrier n
   int issue_img = 0, issue_slot = 0, slot = 0;
   auto issue = [&]() {
-    mr_dma<PW>(voff, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + wave * WSH);
+    dma_n<PW>(voff, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + wave * WSH);
     issue_img = issue_img == n_img - 1 ? 0 : issue_img + 1;
     issue_slot = issue_slot == NST - 1 ? 0 : issue_slot + 1;
   };
@@ -1126,31 +1104,21 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
     const size_t row = (size_t)img * S + (ok ? tok : S - 1);
     mr_wait_loads<NKS>(&xr[0]);
     mr_layernorm_rows<NKS, C>(xr, eps);
-    if (first) { mr_bar(); first = false; }
+    if (first) { bar(); first = false; }
     bf16* const crow = CTX + row * (size_t)(heads * HD) + 16 * kh;
 
     auto chunk = [&](auto swapped_, f32x16& acc) {
       constexpr bool SW = decltype(swapped_)::value;
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(PW) : "memory");      // (lgkmcnt: this wave's K / V fragment stores are in LDS before the barrier)
-      mr_bar();
+      bar();
       issue();
       unsigned a = slot * SLOT + lane * 16;
       asm volatile("" : "+v"(a));
       const unsigned char* sp = smem + a;
       slot = slot == NST - 1 ? 0 : slot + 1;
       if (active) {
-      u32x4 fr[FD];
-#pragma unroll
-      for (int i = 0; i < FD; ++i) fr[i] = *reinterpret_cast<const u32x4*>(sp + i * 1024);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < SLF; ++i) {
-        if constexpr (SW) mfma32_v(xr[i], fr[i % FD], acc);
-        else mfma32_v(fr[i % FD], xr[i], acc);
-        if (i + FD < SLF) fr[i % FD] = *reinterpret_cast<const u32x4*>(sp + (i + FD) * 1024);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));          // wait states MFMA -> VALU read of the accumulator
+        rows_chunk<SW, SLF, FD>(sp, xr, acc);
+        asm volatile("s_nop 15\n\ts_nop 3" : "+v"(acc));          // wait states MFMA -> VALU read of the accumulator
       }
     };
     auto bias_rows = [&](f32x16& acc, int src) {                 // D[channel][token]: lane (token, kh) holds channels 16 kh + i
@@ -1162,14 +1130,6 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
         for (int e = 0; e < 4; ++e) acc[4 * g + e] = b4[e];
       }
     };
-    auto pack2 = [&](const f32x16& acc, u32x4 (&o)[2]) {          // accumulators 8 t .. 8 t + 7 -> k-step t of an MFMA operand
-#pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o[tt][e] = mr_pk2(acc[8 * tt + 2 * e], acc[8 * tt + 2 * e + 1]);
-    };
-    using yes_t = std::integral_constant<bool, true>;
-    using no_t = std::integral_constant<bool, false>;
 
 #pragma unroll 1
     for (int h = 0; h < heads; ++h) {
@@ -1208,7 +1168,7 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
         *reinterpret_cast<u32x4*>(vmine + (c * 2 + 1) * 1024) = vp[1];
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mr_bar();                                                   // every row block's V^T (and, since the Q chunks, K) is in LDS
+      bar();                                                   // every row block's V^T (and, since the Q chunks, K) is in LDS
       if (h == heads - 1 && img + (int)gridDim.x < B) load_rows(img + gridDim.x);     // the rows are dead from here on: the next image's arrive under this head's attention
 
       // ---- attention over the key blocks (flash-style, one block's scores in registers at a time)
@@ -1276,10 +1236,7 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
         }
         lrun += xhalf_sum(sum);
         u32x4 pp[2];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pp[tt][e] = mr_pk2(pv[8 * tt + 2 * e], pv[8 * tt + 2 * e + 1]);
+        pack2(pv, pp);
         asm volatile("s_nop 7" : "+v"(pp[0]), "+v"(pp[1]), "+v"(oacc[0]), "+v"(oacc[HDC - 1]), "+v"(vf[0][0]), "+v"(vf[0][1]));     // VALU-written operands -> MFMA
 #pragma unroll
         for (int c = 0; c < HDC; ++c) {
@@ -1305,8 +1262,8 @@ __global__ __launch_bounds__(512, 1) void vit_attn_rows_kernel(const bf16* __res
         u32x4 o0, o1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          o0[e] = mr_pk2(oacc[c][2 * e] * inv, oacc[c][2 * e + 1] * inv);
-          o1[e] = mr_pk2(oacc[c][8 + 2 * e] * inv, oacc[c][8 + 2 * e + 1] * inv);
+          o0[e] = pk2(oacc[c][2 * e] * inv, oacc[c][2 * e + 1] * inv);
+          o1[e] = pk2(oacc[c][8 + 2 * e] * inv, oacc[c][8 + 2 * e + 1] * inv);
         }
         if (ok) {
           mr_gstore16(crow + h * HD + c * 32, o0);
@@ -1365,7 +1322,7 @@ int launch_qkv_attn_rows(const void* x, void* ctx, const void* wimg, const float
   if (B <= 0) return 0;
   if (C != 512 || hdp != 96 || S < 1 || S > 32) return (int)hipErrorInvalidValue;
   auto kern = qkv_attn_rows_kernel<512, 3>;
-  const int N = 3 * heads * hdp, lds = 4 * (512 / 32) * 1024 + N * 4;
+  const int N = 3 * heads * hdp, lds = gemm_rows_geom<512, 2, 4>::lds_bytes(N);
   {    // per launch: the attribute is per device
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
@@ -1386,7 +1343,7 @@ int launch_vit_attn_rows(const void* x, void* ctx, const void* wimg, const float
   if (B <= 0) return 0;
   if (C != 384 || hdp != 64 || S < 1 || S > 256) return (int)hipErrorInvalidValue;
   auto kern = vit_attn_rows_kernel<384, 2>;
-  const int N = 3 * heads * hdp, lds = 3 * (384 / 16) * 1024 + 2 * 8 * (2 * 2 * 1024) + N * 4;
+  const int N = 3 * heads * hdp, lds = vit_attn_geom<384, 2>::lds_bytes(N);
   {    // per launch: the attribute is per device
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
@@ -1407,7 +1364,7 @@ template <int C, bool LN, int SPC, int NST, bool GATHER = false>
 static int launch_gemm_rows_t(const void* x, void* y, const void* wimg, const float* bias, int M, int N, float eps, hipStream_t s, int gH = 0,
                               const float* pos = nullptr) {
   auto kern = ln_gemm_rows_kernel<C, LN, SPC, NST, GATHER>;
-  const int lds = NST * (C / 16 / SPC) * 1024 + N * 4;
+  const int lds = gemm_rows_geom<C, SPC, NST>::lds_bytes(N);
   {    // per launch: the attribute is per device
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
@@ -1514,7 +1471,7 @@ template <int C, int HID, int RB, int KC, bool LN = false>
 static int launch_mlp_rows_t(const void* x, void* y, const void* wimg, const float* b1img, const float* b2, const void* ctx, const float* bproj, float eps,
                              int M, hipStream_t s) {
   auto kern = mlp_rows_kernel<C, HID, RB, KC, LN>;
-  const int lds = MR_NST * mr_slot_frags(C) * 1024 + HID * 4 + (LN ? 2 * C * 4 : 0) + gelu_tab::BYTES;
+  const int lds = mlp_rows_geom<C, HID, LN>::LDS_BYTES;
   {    // per launch: the attribute is per DEVICE (a process-wide "done" flag skipped it on a second GPU), and the call is cheap
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;

@@ -22,12 +22,10 @@
 // q / k / v equal the bias: finite, masked as keys, never stored as queries.
 #include <stdlib.h>
 
-#include "fsvit_common.h"
+#include "lds_dma.h"
 #include "kernels.h"
 
 namespace FSVIT_NS {
-
-typedef __attribute__((address_space(3))) void* lptrq_t;
 
 namespace qa {
 constexpr int C = 256, HEADS = 6, HDP = 48;
@@ -48,40 +46,12 @@ constexpr int LDS_BYTES = OFF_B + 3 * HEADS * HDP * 4;
 static_assert(FRAGS % NW == 0, "whole pieces per wave");
 }  // namespace qa
 
-namespace {
-
-__device__ __forceinline__ void qa_dma1(unsigned voff, const void* sbase, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff), "s"(sbase), "s"(lds)
-      : "memory");
-}
-// x rows through inline asm: a compiler-visible global load in the pass loop would make hipcc's waitcnt pass drain the ring
-__device__ __forceinline__ u32x4 qa_gload16(const void* p) {
-  u32x4 v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
-__device__ __forceinline__ unsigned qa_pk2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) bf16 bf16x2_t;
-  const bf16x2_t v = {(bf16)a, (bf16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-
-}  // namespace
-
 __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __restrict__ X, bf16* __restrict__ CTX, const unsigned char* __restrict__ wimg,
                                                                const float* __restrict__ bias, const int B, const int S, const float scale) {
   using namespace qa;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float* const btab = reinterpret_cast<float*>(smem + OFF_B);
-  const unsigned lds0 = (unsigned)(size_t)(lptrq_t)smem;
+  const unsigned lds0 = lds_addr(smem);
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int sub = wave / WPI, tokbase = (wave % WPI) * (TT * 16);       // image of the pass, first token of this wave
@@ -104,7 +74,7 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
   int issue_img = 0, issue_slot = 0;
   const unsigned voff = (unsigned)(wave * PPW * 1024 + lane * 16);
   auto issue1 = [&](int piece) {
-    qa_dma1(voff + piece * 1024, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + (wave * PPW + piece) * 1024);
+    dma1(voff + piece * 1024, wimg + (size_t)issue_img * SLOT, lds0 + issue_slot * SLOT + (wave * PPW + piece) * 1024);
     if (piece == PPW - 1) {
       issue_img = issue_img == NIMG - 1 ? 0 : issue_img + 1;
       issue_slot = issue_slot == NST - 1 ? 0 : issue_slot + 1;
@@ -129,7 +99,7 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
       const bool ok = img < B && tok < S;
       const bf16* src = X + ((size_t)(img < B ? img : B - 1) * S + (tok < S ? tok : S - 1)) * C + lq * 8;
 #pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) xr[tt][ks] = ok ? qa_gload16(src + ks * 32) : zero4;
+      for (int ks = 0; ks < NKS; ++ks) xr[tt][ks] = ok ? gload16(src + ks * 32) : zero4;
     }
   };
   load_x(blockIdx.x);
@@ -198,9 +168,9 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
         for (int tt = 0; tt < TT; ++tt) {
           const int tok = tokbase + 16 * tt + m;
           if (p == 0) {
-            qf[tt][0] = u32x4{qa_pk2(acc[0][tt][0], acc[0][tt][1]), qa_pk2(acc[0][tt][2], acc[0][tt][3]),
-                              qa_pk2(acc[1][tt][0], acc[1][tt][1]), qa_pk2(acc[1][tt][2], acc[1][tt][3])};
-            qf[tt][1] = u32x4{qa_pk2(acc[2][tt][0], acc[2][tt][1]), qa_pk2(acc[2][tt][2], acc[2][tt][3]), 0u, 0u};
+            qf[tt][0] = u32x4{pk2(acc[0][tt][0], acc[0][tt][1]), pk2(acc[0][tt][2], acc[0][tt][3]),
+                              pk2(acc[1][tt][0], acc[1][tt][1]), pk2(acc[1][tt][2], acc[1][tt][3])};
+            qf[tt][1] = u32x4{pk2(acc[2][tt][0], acc[2][tt][1]), pk2(acc[2][tt][2], acc[2][tt][3]), 0u, 0u};
           } else if (tokbase + 16 * tt >= TOKK) {
             // token tile beyond the 112 key rows kept (never valid for S <= 112): no K / V^T entry
           } else if (p == 1) {      // k positions: chunk 0 = (tile 0 rows 4 lq.. | tile 1 rows 4 lq..) per lq, chunk 1 = (tile 2 rows | zeros)
@@ -209,13 +179,13 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
             // profiles/r04_mfma_pmc.txt); rows m and m + 4 now sit one column apart, the two tiles of chunk 0 go out as ONE 16-byte store
             // (conflict-free in its 8-lane groups), and the b128 reads of the score product stay conflict-free (bank sets checked in tools/lds_conflicts.py)
             const int ksw = 16 * (lq ^ ((m >> 2) & 1));
-            *reinterpret_cast<u32x4*>(Ks + tok * KS + ksw) = u32x4{qa_pk2(acc[0][tt][0], acc[0][tt][1]), qa_pk2(acc[0][tt][2], acc[0][tt][3]),
-                                                                   qa_pk2(acc[1][tt][0], acc[1][tt][1]), qa_pk2(acc[1][tt][2], acc[1][tt][3])};
-            *reinterpret_cast<u32x2*>(Ks + tok * KS + 64 + ksw) = u32x2{qa_pk2(acc[2][tt][0], acc[2][tt][1]), qa_pk2(acc[2][tt][2], acc[2][tt][3])};
+            *reinterpret_cast<u32x4*>(Ks + tok * KS + ksw) = u32x4{pk2(acc[0][tt][0], acc[0][tt][1]), pk2(acc[0][tt][2], acc[0][tt][3]),
+                                                                   pk2(acc[1][tt][0], acc[1][tt][1]), pk2(acc[1][tt][2], acc[1][tt][3])};
+            *reinterpret_cast<u32x2*>(Ks + tok * KS + 64 + ksw) = u32x2{pk2(acc[2][tt][0], acc[2][tt][1]), pk2(acc[2][tt][2], acc[2][tt][3])};
           } else {                  // rows = tokens tokbase + 16 tt + 4 lq + e of channel 16 c + m
 #pragma unroll
             for (int c = 0; c < NCT; ++c) {
-              const u32x2 o = {qa_pk2(acc[c][tt][0], acc[c][tt][1]), qa_pk2(acc[c][tt][2], acc[c][tt][3])};
+              const u32x2 o = {pk2(acc[c][tt][0], acc[c][tt][1]), pk2(acc[c][tt][2], acc[c][tt][3])};
               *reinterpret_cast<u32x2*>(Vt + (16 * c + m) * VS + (tokbase + 16 * tt + 4 * lq) * 2) = o;
             }
           }
@@ -281,9 +251,9 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
 #pragma unroll
           for (int kc = 0; kc < NPC; ++kc) {
             const bool two = 2 * kc + 1 < NKT;
-            pb[tt][kc] = u32x4{qa_pk2(sc[tt][2 * kc][0], sc[tt][2 * kc][1]), qa_pk2(sc[tt][2 * kc][2], sc[tt][2 * kc][3]),
-                               two ? qa_pk2(sc[tt][two ? 2 * kc + 1 : 0][0], sc[tt][two ? 2 * kc + 1 : 0][1]) : 0u,
-                               two ? qa_pk2(sc[tt][two ? 2 * kc + 1 : 0][2], sc[tt][two ? 2 * kc + 1 : 0][3]) : 0u};
+            pb[tt][kc] = u32x4{pk2(sc[tt][2 * kc][0], sc[tt][2 * kc][1]), pk2(sc[tt][2 * kc][2], sc[tt][2 * kc][3]),
+                               two ? pk2(sc[tt][two ? 2 * kc + 1 : 0][0], sc[tt][two ? 2 * kc + 1 : 0][1]) : 0u,
+                               two ? pk2(sc[tt][two ? 2 * kc + 1 : 0][2], sc[tt][two ? 2 * kc + 1 : 0][3]) : 0u};
           }
 #pragma unroll
         for (int dt = 0; dt < NCT; ++dt) {
@@ -302,7 +272,7 @@ __global__ __launch_bounds__(qa::NW * 64) void qkv_attn_kernel(const bf16* __res
 #pragma unroll
           for (int tt = 0; tt < TT; ++tt) {
             const f32x4 o = a[tt] * inv[tt];
-            pend[tt][dt] = u32x2{qa_pk2(o[0], o[1]), qa_pk2(o[2], o[3])};
+            pend[tt][dt] = u32x2{pk2(o[0], o[1]), pk2(o[2], o[3])};
           }
         }
       }

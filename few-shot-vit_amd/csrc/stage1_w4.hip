@@ -27,10 +27,9 @@
 // Numerics: as stage1_ring - h1 / h2 rounded to the 16-bit storage type where they are stored, everything else fp32, gelu_sig; a pixel's value
 // does not depend on its position in a chunk or a launch.
 #include <stdlib.h>
-#include <utility>
 #include <type_traits>
 
-#include "fsvit_common.h"
+#include "lds_dma.h"
 #include "kernels.h"
 
 namespace FSVIT_NS {
@@ -54,14 +53,7 @@ constexpr int LDS_BYTES = TAB + gelu_tab::BYTES;   // 155 648 (bf16) / 147 968 (
 
 typedef float f32x16w __attribute__((ext_vector_type(16)));
 
-// compile-time slot loops: the slot index is a type, every schedule test an `if constexpr` (a `#pragma unroll` loop over a body this size is
-// refused by the unroller's cost model - and the register arrays it indexes then live in scratch)
-template <int... I, typename F>
-__device__ __forceinline__ void w4_for_impl(std::integer_sequence<int, I...>, F&& f) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void w4_for(F&& f) { w4_for_impl(std::make_integer_sequence<int, N>{}, static_cast<F&&>(f)); }
+// the slot loops are static_for (lds_dma.h): the slot index is a type, every schedule test an `if constexpr`
 #define W4_IC(v) std::integral_constant<int, (v)>{}
 
 // weights in AGPRs (MFMA SrcA), accumulators in arch VGPRs (the GELU reads them)
@@ -82,11 +74,6 @@ __device__ __forceinline__ void w4_mfma_az(const u32x4& w, const u32x4& x, f32x1
 __device__ __forceinline__ void w4_bar() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ unsigned w4_pk2(float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) bf16 bf16x2_t;
-  const bf16x2_t v = {(bf16)a, (bf16)b};
-  return __builtin_bit_cast(unsigned, v);
 }
 
 // PIPE = false: the same data flow with every GELU pass run en bloc behind its MFMA phase (bring-up / reference for the slotted schedule)
@@ -269,7 +256,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
       for (int o = 0; o < 2; ++o) {
         u32x4 v;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = SC ? w4_pk2(acc3[bt][8 * o + 2 * j], acc3[bt][8 * o + 2 * j + 1]) : w4_pk2(8.0f * acc3[bt][8 * o + 2 * j], 8.0f * acc3[bt][8 * o + 2 * j + 1]);
+        for (int j = 0; j < 4; ++j) v[j] = SC ? pk2(acc3[bt][8 * o + 2 * j], acc3[bt][8 * o + 2 * j + 1]) : pk2(8.0f * acc3[bt][8 * o + 2 * j], 8.0f * acc3[bt][8 * o + 2 * j + 1]);
         if (m < M) *reinterpret_cast<u32x4*>(yl + (size_t)m * C1 + 8 * o) = v;
       }
     }
@@ -309,11 +296,11 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
 #pragma unroll
     for (int h = 0; h < 2; ++h) gu[J][k][h] = __builtin_amdgcn_rcpf(gu[J][k][h]);
   };
-  auto g_c = [&](int J, int k) { gp[J][k] = w4_pk2(gx[J][k][0] * gu[J][k][0], gx[J][k][1] * gu[J][k][1]); };
+  auto g_c = [&](int J, int k) { gp[J][k] = pk2(gx[J][k][0] * gu[J][k][0], gx[J][k][1] * gu[J][k][1]); };
   // the micro-stages of job J due at relative slot r; pair k starts at k * NUM / 4 (NUM = 7: 1.75 slots per pair, 8: 2); dst(tile, octet) = LDS address
   auto g_slot = [&](auto jt, auto numt, auto rt, const f32x16w& a0, const f32x16w& a1, auto dst) {
     constexpr int J = decltype(jt)::value, NUM = decltype(numt)::value, r = decltype(rt)::value;
-    w4_for<16>([&](auto kc) {
+    static_for<16>([&](auto kc) {
       constexpr int k = decltype(kc)::value, st = k * NUM / 4;
       if constexpr (r == st) g_a1(J, k, k < 8 ? a0 : a1);
       if constexpr (r == st + 1) g_a2(J, k);
@@ -348,13 +335,13 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
   unsigned tl[4][16], th[4][16];
   auto t_slot = [&](auto jt, auto numt, auto rt, const f32x16w& a0, const f32x16w& a1, auto dst) {
     constexpr int J = decltype(jt)::value, NUM = decltype(numt)::value, r = decltype(rt)::value;
-    w4_for<16>([&](auto kc) {
+    static_for<16>([&](auto kc) {
       constexpr int k = decltype(kc)::value, st = k * NUM / 4;
       // (stage boundaries keep a packed 16-bit result and its reader in different slots: gfx950 needs a wait state between such a pair, hipcc
       // fills it with an s_nop 0)
       if constexpr (r == st) {
         const f32x16w& a = k < 8 ? a0 : a1;
-        tc[J][k] = w4_pk2(a[2 * (k & 7)], a[2 * (k & 7) + 1]);
+        tc[J][k] = pk2(a[2 * (k & 7)], a[2 * (k & 7) + 1]);
         asm("" : "+v"(tc[J][k]));                            // (opaque: otherwise the sign shift below converts the two floats again)
       }
       if constexpr (r == st + 1) ta[J][k] = gelu_tab::rebase(tc[J][k]);
@@ -429,14 +416,14 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
   auto gelu1 = [&](long P0, int bt) {
     const int slot = (int)((P0 + 32 * bt + p) & (RING - 1)) * 16;
     auto dst = [&](int at, int o) { return h1w + (4 * at + o) * PITCH + slot; };
-    w4_for<36 + W4_TLAT>([&](auto rc) {
+    static_for<36 + W4_TLAT>([&](auto rc) {
       gelu_slot(J1{}, N8{}, N8{}, rc, acc1[0][bt], acc1[1][bt], dst);
       __builtin_amdgcn_sched_barrier(0);
     });
   };
   auto gelu2 = [&](int bt) {
     auto dst = [&](int gi, int o) { return h2w + (4 * gi + o) * H2P + 32 * bt * 16; };
-    w4_for<36 + W4_TLAT>([&](auto rc) {
+    static_for<36 + W4_TLAT>([&](auto rc) {
       gelu_slot(J3{}, N8{}, N8{}, rc, acc2[0][bt], acc2[1][bt], dst);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -472,7 +459,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
       xf[0] = *reinterpret_cast<const u32x4*>(xb + xn0);
       xf[1] = *reinterpret_cast<const u32x4*>(xb + 2 * XP + xn0);
       __builtin_amdgcn_sched_barrier(0);
-      w4_for<36>([&](auto mc) {
+      static_for<36>([&](auto mc) {
         constexpr int m = decltype(mc)::value, bt = m / 18, j = m % 18;
         if constexpr (j < 2) w4_mfma_az(wb[j], ones, acc1[j][bt]);
         else {
@@ -515,7 +502,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
 #pragma unroll
       for (int i = 0; i < W4_PF; ++i) hf[i] = *reinterpret_cast<const u32x4*>(h2b + 2 * i * H2P);
       __builtin_amdgcn_sched_barrier(0);
-      w4_for<32>([&](auto mc) {
+      static_for<32>([&](auto mc) {
         constexpr int m = decltype(mc)::value, bt = m >> 4, ks = m & 15;
         if constexpr (ks < W3A) w4_mfma(wf3[ks], hf[m % (W4_PF + 1)], acc3[bt]);
         else w4_mfma_vw(wv[ks - W3A], hf[m % (W4_PF + 1)], acc3[bt]);
@@ -532,7 +519,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
 #pragma unroll
       for (int i = 0; i < W4_PF; ++i) hf[i] = *(lds_frag_t)(size_t)(unsigned)(ta + (4 * (i & 1) + 2 * ((i >> 1) & 1)) * PITCH);
       __builtin_amdgcn_sched_barrier(0);
-      w4_for<36>([&](auto mc) {
+      static_for<36>([&](auto mc) {
         constexpr int m = decltype(mc)::value, tp = m >> 2, ks = (m >> 1) & 1, gi = m & 1;
         if constexpr (m < 2) w4_mfma_z(wf2[gi][0][0], hf[m % (W4_PF + 1)], acc2[gi][0]);
         else w4_mfma(wf2[gi][tp][ks], hf[m % (W4_PF + 1)], acc2[gi][0]);
@@ -548,7 +535,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
           const long mm = (long)(q - 1) * CH + 32 * bt + p;
           u32x4 v;
 #pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] = SC ? w4_pk2(acc3[bt][8 * o + 2 * j], acc3[bt][8 * o + 2 * j + 1]) : w4_pk2(8.0f * acc3[bt][8 * o + 2 * j], 8.0f * acc3[bt][8 * o + 2 * j + 1]);
+          for (int j = 0; j < 4; ++j) v[j] = SC ? pk2(acc3[bt][8 * o + 2 * j], acc3[bt][8 * o + 2 * j + 1]) : pk2(8.0f * acc3[bt][8 * o + 2 * j], 8.0f * acc3[bt][8 * o + 2 * j + 1]);
           if (mm < M) *reinterpret_cast<u32x4*>(yl + (size_t)mm * C1 + 8 * o) = v;
         }
         if constexpr (m == 28) tap_setup(q, 1);
@@ -565,7 +552,7 @@ __global__ __launch_bounds__(256, 1) void stage1_w4_kernel(const bf16* __restric
 #pragma unroll
       for (int i = 0; i < W4_PF; ++i) hf[i] = *(lds_frag_t)(size_t)(unsigned)(ta + (4 * (i & 1) + 2 * ((i >> 1) & 1)) * PITCH);
       __builtin_amdgcn_sched_barrier(0);
-      w4_for<36>([&](auto mc) {
+      static_for<36>([&](auto mc) {
         constexpr int m = decltype(mc)::value, tp = m >> 2, ks = (m >> 1) & 1, gi = m & 1;
         if constexpr (m < 2) w4_mfma_z(wf2[gi][0][0], hf[m % (W4_PF + 1)], acc2[gi][1]);
         else w4_mfma(wf2[gi][tp][ks], hf[m % (W4_PF + 1)], acc2[gi][1]);
