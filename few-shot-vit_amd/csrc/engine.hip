@@ -1108,7 +1108,7 @@ extern "C" int fsvit_conv3x3_wgrad(const void* x, const void* dz, float* dw, int
   if (!x || !dz || !dw) return fail(FSVIT_ERR_ARG, "null argument");
   if (dtype != FSVIT_BF16 && dtype != FSVIT_F16 && !is_x2(dtype))
     return fail(FSVIT_ERR_ARG, "fsvit_conv3x3_wgrad: bf16 / f16 activations, or fp32 activations with two-limb arithmetic (FSVIT_BF16X2 / FSVIT_F16X2)");
-  if (!K(wgrad3x3_supported)(kg(dtype), O, Ig, groups, W)) return fail(FSVIT_ERR_ARG, "fsvit_conv3x3_wgrad: built for 8 groups of 32 -> 32 channels (W <= 20) and dense 64 / 128 -> 128 (W <= 40)");
+  if (!K(wgrad3x3_supported)(kg(dtype), O, Ig, groups, W)) return fail(FSVIT_ERR_ARG, "fsvit_conv3x3_wgrad: built for 8 groups of 32 -> 32 channels (W <= 20) and dense 64 / 128 -> 128, 96 -> 96 (W <= 40)");
   hipStream_t st = (hipStream_t)stream;
   void* scratch = nullptr;
   HIP_TRY(hipMalloc(&scratch, K(wgrad3x3_scratch_bytes)(O, Ig, groups, B * H * W, kg(dtype))));

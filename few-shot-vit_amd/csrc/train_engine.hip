@@ -2,7 +2,7 @@
 // (batch-statistics BatchNorm with running-stat update, DropPath) with saved activations, and the full backward
 // to every parameter gradient.  GEMM-shaped work (forward convs, data gradients, split-K weight gradients) runs on
 // conv_gemm_v2 and the direct kernels of wgrad3x3.hip / stage1_ring.hip; everything else is train_kernels.hip / attention_bwd.hip / head.hip.
-// Both trainers (Visformer, ViT / DeiT) are a TrainerBase - parameter table, two arenas, batched weight pack, side streams, ONE step driver
+// Every trainer (Visformer, ViT / DeiT, LV-ViT) is a TrainerBase - parameter table, two arenas, batched weight pack, side streams, ONE step driver
 // (trainer_forward / trainer_backward) - plus the model's forward and backward walk, whose launch order is the product.
 #include "../../include/fsvit.h"
 
@@ -64,6 +64,8 @@ struct ConvSpec {                         // one nn.Conv2d of the model (PyTorch
   int O = 0, Ig = 0, KH = 1, KW = 1, stride = 1, pad = 0, groups = 1;
   int hd_rows = 1, hdp_rows = 1, hd_cols = 1, hdp_cols = 1;      // head-dim padding (qkv rows / proj columns)
   bool via_patches = false;               // stem conv1 / downsample: input is the 32-wide im2col row
+  bool via_rows = false;                  // weight gradient only: the input already is the [M][KH*KW*Ig] im2col (non-overlapping patches, launch_patchk)
+  bool wgrad_gemm = false;                // weight gradient on the general transposed split-K GEMM route even where a direct kernel takes the shape
   int rows_fwd() const { return (O / groups) / hd_rows * hdp_rows; }                         // padded N per group
   int kreal() const { return KH * KW * Ig; }
   int kpad_cols() const { return via_patches ? 32 : kreal() / hd_cols * hdp_cols; }         // padded K (elements)
@@ -92,6 +94,13 @@ struct TrainerBase {
   Arena save, tmp;
   int B = 0;
   float dp_rate = 0.f;
+  // BatchNorm models: eps, and the layers in eval mode inside the step (utils.freeze_bn): running statistics, no update
+  float bn_eps = 1e-5f;
+  bool freeze_bn = false;
+  // Constant factor of every residual branch (LV-ViT: 1 / skip_lam).  It lives in the per-image DropPath scales - scale = branch_scale * mask / keep, and row
+  // n_dp of the table is the constant one for the calls without a rate - never in the parameters: the branch's weight and bias gradients carry it exactly once
+  float branch_scale = 1.f;
+  int n_dp = 0;
   // batched weight pack: the sizing pass (dry arenas) records every pack of forward + backward in call order; the real forward runs them in
   // one or two launches and the real conv calls pick their packed weights up by position
   std::vector<PackJob> jobs;
@@ -129,12 +138,17 @@ struct TrainerBase {
   }
 };
 
+// The ConvBlock stem both BatchNorm models start with (stem_forward / stem_backward): its geometry and parameter names, and its saved forward state
+// pfx: "stem." | "patch_embed."; pos: the [1,C1,H1,H1] table added behind the pool, or null; wgrad_gemm: ConvSpec::wgrad_gemm of conv2 / conv3
+struct StemGeo { int C0, C1, H0, H1, img; const char* pfx; const char* pos; bool wgrad_gemm; };
+struct StemSave { void *patches, *z1, *a1, *zd, *z2, *a2, *z3; unsigned char* arg; BnSave b1, bd, b2, b3; void* x1; };
+
 struct fsvit_visformer_trainer : TrainerBase {
   fsvit_visformer_cfg cfg;
   int C0, C1, C2, C3, H0, H1, H2, H3, hid1, hid2, hid3, hd2, hdp2, hd3, hdp3, Cg;
-  bool freeze_bn = false;                 // BatchNorm layers in eval mode inside the step (utils.freeze_bn): running statistics, no update
+  StemGeo geo() const { return StemGeo{C0, C1, H0, H1, cfg.img_size, "stem.", "pos_embed1", false}; }
   // saved forward state (pointers into `save`)
-  struct Stem { void *patches, *z1, *a1, *zd, *ad, *z2, *a2, *z3, *a3; unsigned char* arg; BnSave b1, bd, b2, b3; void* x1; } stem;
+  StemSave stem;
   struct S1 { void *x, *xn, *z1, *h1, *z2, *h2; BnSave bn; const float* scale; void* out; };
   struct SA { void *x, *xn1, *qkv, *ctx, *xa, *xn2, *z1, *h; BnSave bn1, bn2; const float *s1, *s2; void* out; };
   struct PE { void *xin, *z; BnSave bn; void* out; };
@@ -149,6 +163,7 @@ struct fsvit_visformer_trainer : TrainerBase {
 // statistics, token assembly, the final norm on the cls row
 struct fsvit_vit_trainer : TrainerBase {
   fsvit_vit_cfg vcfg;
+  bool qkv_bias = true;                   // (LV-ViT: none, lvvit.py:116)
   int D = 0, S = 0, np = 0, npw = 0, K = 0, Kp = 0, hidv = 0, heads = 0, hd = 0, hdp = 0;
   struct Blk { void *x, *xn1, *qkv, *ctx, *x1, *xn2, *z1, *h; float *m1, *r1, *m2, *r2; const float *s1, *s2; };
   std::vector<Blk> blk;
@@ -157,11 +172,24 @@ struct fsvit_vit_trainer : TrainerBase {
   float *mf = nullptr, *rf = nullptr;
 };
 
+// LV-ViT (lvvit.py:413-552): the ConvBlock stem at 96 channels (stem_forward / stem_backward), a 4x4 / stride 4 projection of the pooled map into 25 patch
+// tokens, and the ViT blocks without qkv bias, every residual branch scaled by 1 / skip_lam (TrainerBase::branch_scale)
+struct fsvit_lvvit_trainer : fsvit_vit_trainer {
+  fsvit_lvvit_cfg lcfg;
+  int C0 = 0, H0 = 0, H1 = 0;
+  // FSVIT_LVVIT_WGRAD=gemm | direct (read when the handle is created): the route of the dense 96 -> 96 weight gradients, the A/B switch of
+  // tools/bench_lvvit.py --mode train
+  bool wgrad_gemm = true;
+  StemGeo geo() const { return StemGeo{C0, C0, H0, H1, lcfg.img_size, "patch_embed.", nullptr, wgrad_gemm}; }
+  StemSave stem;
+};
+
 namespace {
 
 typedef TrainerBase TB;
 typedef fsvit_visformer_trainer TR;
 typedef fsvit_vit_trainer VT;
+typedef fsvit_lvvit_trainer LT;
 
 const fsvit_param* getp(TB* t, const std::string& name) {
   auto it = t->P.find(name);
@@ -365,13 +393,15 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
   const fsvit_param* w = getp(t, c.wname);
   if (!w) return FSVIT_ERR_KEY;
   if (!w->grad && !t->save.dry) return 0;      // (the sizing pass always counts the weight-gradient scratch)
-  const int OH = c.via_patches ? H : (H + 2 * c.pad - c.KH) / c.stride + 1, OW = c.via_patches ? W : (W + 2 * c.pad - c.KW) / c.stride + 1;
+  const bool rows_in = c.via_patches || c.via_rows;                             // x holds im2col rows: H x W is the OUTPUT grid
+  const int OH = rows_in ? H : (H + 2 * c.pad - c.KH) / c.stride + 1, OW = rows_in ? W : (W + 2 * c.pad - c.KW) / c.stride + 1;
   const int M = B * OH * OW;
   const int rows = c.groups * c.rows_fwd();                                     // all output channels (padded)
-  const int Cin_tot = c.via_patches ? 32 : c.groups * (c.kpad_cols() / (c.KH * c.KW));
-  const int Kc_pad = c.via_patches ? 32 : round_up(c.KH * c.KW * Cin_tot, 4);
+  const int Cin_tot = c.via_patches ? 32 : c.via_rows ? c.kreal() : c.groups * (c.kpad_cols() / (c.KH * c.KW));
+  const int Kc_pad = c.via_patches ? 32 : c.via_rows ? round_up(c.kreal(), 4) : round_up(c.KH * c.KW * Cin_tot, 4);
   const int wdt = t->gdt == 2 ? 2 : t->dtype;          // the direct weight-gradient kernels: 16-bit rows, or fp32 rows with two-limb arithmetic
-  if (!c.via_patches && c.KH == 3 && c.KW == 3 && c.stride == 1 && c.pad == 1 && wgrad3x3_supported(wdt, c.O, c.Ig, c.groups, W)) {
+  if (!c.via_patches && c.KH == 3 && c.KW == 3 && c.stride == 1 && c.pad == 1 && !c.wgrad_gemm &&
+      wgrad3x3_supported(wdt, c.O, c.Ig, c.groups, W)) {
     // direct kernel: no transposed copies of dz / im2col(x) (wgrad3x3.hip)
     float* scratch = (float*)t->save.take(wgrad3x3_scratch_bytes(c.O, c.Ig, c.groups, M, wdt));
     if (!scratch) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (wgrad3x3)");
@@ -380,10 +410,10 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
     if (on_side) T_TRY(side_begin(t));
     T_RUN(launch_wgrad3x3(x, Cin_tot, dz, rows, w->grad, scratch, B, H, W, c.O, c.Ig, c.groups, on_side ? t->side : t->st, d, wdt));
     if (on_side) T_TRY(side_end(t, x, (size_t)M * Cin_tot * t->es, dz, (size_t)M * rows * t->es));
-    if (!t->save.dry) t->fin.push_back(FinJob{scratch, w->grad, 3, 0, c.Ig, 3, 3, c.groups == 8 ? 1 : 0, d[1], d[0], 1, 1, 1, 1});
+    if (!t->save.dry) t->fin.push_back(FinJob{scratch, w->grad, 3, 0, c.Ig, 3, 3, c.groups == 8 ? 1 : c.O == 96 ? 2 : 0, d[1], d[0], 1, 1, 1, 1});
     return 0;
   }
-  if ((c.via_patches || (c.KH == 1 && c.KW == 1 && c.stride == 1 && c.groups == 1)) && wgrad1x1_supported(wdt, rows, Cin_tot)) {
+  if ((rows_in || (c.KH == 1 && c.KW == 1 && c.stride == 1 && c.groups == 1)) && wgrad1x1_supported(wdt, rows, Cin_tot)) {
     // direct kernel on the row-major operands (x [M][Cin_tot] - or the 32-wide patch rows - and dz [M][rows]); the finalize pass is the round-1 one
     const int splits = wgrad1x1_splits(rows, Cin_tot, M, wdt);
     float* ysp = (float*)t->save.take((size_t)round_up(rows, 4) * splits * Kc_pad * 4);
@@ -411,7 +441,7 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
   T_TRY(side_guard(t, dzt, (size_t)rows * Mpad * t->es));
   T_TRY(side_guard(t, xct, (size_t)Kc_pad * Mpad * t->es));
   T_RUN(launch_transpose_cols(dz, dzt, M, rows, 0, rows, Mpad, t->dtype, t->st));
-  if (c.via_patches) T_RUN(launch_transpose_cols(x, xct, M, 32, 0, 32, Mpad, t->gdt, t->st));           // (the GEMM's weight-side operand: limb words under bf16x2)
+  if (rows_in) T_RUN(launch_transpose_cols(x, xct, M, Cin_tot, 0, Cin_tot, Mpad, t->gdt, t->st));      // (the GEMM's weight-side operand: limb words under bf16x2)
   else T_RUN(launch_im2col_t(x, xct, B, H, W, Cin_tot, 0, Cin_tot, c.KH, c.KW, c.stride, c.pad, OH, OW, Mpad, t->gdt, t->st));
   // Y[n][s*Kc_pad + k] = sum_{m in split s} dzt[n][m] * xct[k][m]
   ConvGemmParams p = gemm_params(dzt, xct, ysp, 1, rows, 1, Ks, Mpad, 1, 1, 1, 0, Kc_pad, splits * Kc_pad, Ks, Ks, splits);
@@ -442,7 +472,7 @@ int run_finalizes(TB* t) {
 // A residual add queued by the block that produced z (z = add.a + add.scale[image] * add.b, not yet computed) rides in the reduce pass.
 struct PendingAdd { const void* a = nullptr; const void* b = nullptr; const float* scale = nullptr; void* out = nullptr; size_t n = 0, per_img = 0; };
 // pre / pre_rows: partial sums of z that the producing kernel already wrote (conv_fwd's st_partial / st_rows): no reduce pass
-int bn_fwd(TR* t, const std::string& name, const void* z, int M, int C, int act, const void* res, void* y, BnSave* sv, PendingAdd* add = nullptr,
+int bn_fwd(TB* t, const std::string& name, const void* z, int M, int C, int act, const void* res, void* y, BnSave* sv, PendingAdd* add = nullptr,
            const float* pre = nullptr, int pre_rows = 0) {
   const fsvit_param *g = getp(t, name + ".weight"), *b = getp(t, name + ".bias"), *rm = getp(t, name + ".running_mean"), *rv = getp(t, name + ".running_var");
   if (!g || !b || !rm || !rv) return FSVIT_ERR_KEY;
@@ -456,14 +486,14 @@ int bn_fwd(TR* t, const std::string& name, const void* z, int M, int C, int act,
     T_RUN(launch_add_scaled(add->a, add->b, add->scale, add->out, add->n, add->per_img, t->dtype, t->st));
   }
   if (t->freeze_bn) {
-    T_RUN(launch_bn_frozen_coeffs(C, t->cfg.bn_eps, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
+    T_RUN(launch_bn_frozen_coeffs(C, t->bn_eps, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
   } else {
     if (pre && pre_rows > 0 && !fuse_add) {
-      T_RUN(launch_bn_fwd_finalize_nblk(pre, pre_rows, M, C, t->cfg.bn_eps, 0.1f, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
+      T_RUN(launch_bn_fwd_finalize_nblk(pre, pre_rows, M, C, t->bn_eps, 0.1f, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
     } else {
       if (fuse_add) T_RUN(launch_bn_reduce(z, nullptr, nullptr, nullptr, partial, M, C, 0, t->dtype, t->st, add->a, add->b, add->scale, (int)(add->per_img / C)));
       else T_RUN(launch_bn_reduce(z, nullptr, nullptr, nullptr, partial, M, C, 0, t->dtype, t->st));
-      T_RUN(launch_bn_fwd_finalize(partial, M, C, t->cfg.bn_eps, 0.1f, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
+      T_RUN(launch_bn_fwd_finalize(partial, M, C, t->bn_eps, 0.1f, g->data, b->data, rm->data, rv->data, sv->mean, sv->invstd, sv->sa, sv->sb, t->st));
     }
   }
   if (add) *add = PendingAdd{};
@@ -474,7 +504,7 @@ int bn_fwd(TR* t, const std::string& name, const void* z, int M, int C, int act,
 // dy: gradient w.r.t. the BN output (after undoing the activation) -> dz; writes dgamma / dbeta
 // acc / scale2 / out2 / rows_per_img: the fused tail of launch_bn_bwd_apply (dz = acc + ..., out2 = scale2[image] * dz)
 // act: dy is the gradient BEHIND the LeakyReLU that followed this BatchNorm (no residual); the slope is applied inside the reduce and apply passes
-int bn_bwd(TR* t, const std::string& name, const BnSave& sv, const void* dy, void* dz, const void* acc = nullptr, const float* scale2 = nullptr,
+int bn_bwd(TB* t, const std::string& name, const BnSave& sv, const void* dy, void* dz, const void* acc = nullptr, const float* scale2 = nullptr,
            void* out2 = nullptr, size_t rows_per_img = 0, bool act = false) {
   const fsvit_param *g = getp(t, name + ".weight"), *b = getp(t, name + ".bias");
   if (!g || !b) return FSVIT_ERR_KEY;
@@ -495,7 +525,7 @@ int bn_bwd(TR* t, const std::string& name, const BnSave& sv, const void* dy, voi
 }
 
 // conv_fwd of a stem layer whose kernel hands its BatchNorm the statistics of the map it stores - not asked for with frozen BatchNorm layers
-int conv_fwd_stats(TR* t, const ConvSpec& c, const void* x, int B, int H, int W, void* z, float** st_partial, int* st_rows) {
+int conv_fwd_stats(TB* t, const ConvSpec& c, const void* x, int B, int H, int W, void* z, float** st_partial, int* st_rows) {
   *st_rows = 0;
   return conv_fwd(t, c, x, B, H, W, z, nullptr, nullptr, st_partial, t->freeze_bn ? nullptr : st_rows);
 }
@@ -507,13 +537,136 @@ void* take_tmp(TB* t, size_t elems) { return t->tmp.take(elems * t->es); }
 const float* dp_scale(TB* t, int call, int block_index, int nblocks) {
   // per-block rates linspace(0, rate, depth) (visformer.py:312, deit.py:161); rate 0 -> plain residual
   const float r = nblocks > 1 ? t->dp_rate * (float)block_index / (float)(nblocks - 1) : 0.f;
-  if (r == 0.f || !t->scales) return nullptr;
+  if (!t->scales) return nullptr;
+  if (r == 0.f) return t->branch_scale != 1.f ? t->scales + (size_t)t->n_dp * t->B : nullptr;      // (the constant row of a model with a branch scale)
   return t->scales + (size_t)call * t->B;
+}
+
+// ================================================================ the ConvBlock stem (visformer.py:219-239; lvvit.py:277-317 is the same block at C0 = C1 = 96, no pos)
+struct StemSpecs { ConvSpec conv1, down, conv2, conv3; };
+StemSpecs stem_specs(const StemGeo& g) {
+  StemSpecs s;
+  const std::string p = g.pfx;
+  auto mk = [](std::string n, int O, int Ig, int stride) { ConvSpec c; c.wname = n; c.O = O; c.Ig = Ig; c.KH = c.KW = 3; c.stride = stride; c.pad = 1; return c; };
+  s.conv1 = mk(p + "conv1.weight", g.C0, 3, 2); s.conv1.via_patches = true;
+  s.down = mk(p + "downsample.0.weight", g.C1, 3, 2); s.down.via_patches = true;
+  s.conv2 = mk(p + "conv2.weight", g.C1, g.C0, 1); s.conv2.wgrad_gemm = g.wgrad_gemm;
+  s.conv3 = mk(p + "conv3.weight", g.C1, g.C1, 1); s.conv3.wgrad_gemm = g.wgrad_gemm;
+  return s;
+}
+
+// x [B][3][img][img] -> S.x1 [B * H1 * H1][C1] = MaxPool(LeakyReLU(bn3(conv3(..)) + bn_d(down(x)))) (+ pos)
+int stem_forward(TB* t, const StemGeo& g, StemSave& S, const float* x) {
+  const StemSpecs ss = stem_specs(g);
+  const std::string pfx = g.pfx;
+  const int B = t->B, dt = t->dtype, img = g.img, H0 = g.H0, H1 = g.H1;
+  hipStream_t st = t->st;
+  const size_t M0 = (size_t)B * H0 * H0, M1 = (size_t)B * H1 * H1;
+  NEED(S.patches = take_act(t, M0 * 32)); NEED(S.z1 = take_act(t, M0 * g.C0)); NEED(S.a1 = take_act(t, M0 * g.C0));
+  NEED(S.zd = take_act(t, M0 * g.C1)); NEED(S.z2 = take_act(t, M0 * g.C1)); NEED(S.a2 = take_act(t, M0 * g.C1));
+  NEED(S.z3 = take_act(t, M0 * g.C1)); NEED(S.arg = (unsigned char*)t->save.take(M1 * g.C1)); NEED(S.x1 = take_act(t, M1 * g.C1));
+  T_RUN(launch_im2col27(x, S.patches, B, img, img, H0, H0, dt, st));
+  {
+    // (the producing GEMMs hand the BatchNorm statistics of the maps they store to the finalize: no reduce pass, ConvGemmParams::stats)
+    const size_t mark = t->tmp.off;
+    float* stp = nullptr;
+    int str = 0;
+    T_TRY(conv_fwd_stats(t, ss.conv1, S.patches, B, H0, H0, S.z1, &stp, &str));
+    T_TRY(bn_fwd(t, pfx + "bn1", S.z1, (int)M0, g.C0, ACT_LRELU, nullptr, S.a1, &S.b1, nullptr, stp, str));
+    t->tmp.off = mark;
+    T_TRY(conv_fwd_stats(t, ss.down, S.patches, B, H0, H0, S.zd, &stp, &str));
+    T_TRY(bn_fwd(t, pfx + "downsample.1", S.zd, (int)M0, g.C1, ACT_NONE, nullptr, nullptr, &S.bd, nullptr, stp, str));      // statistics only: applied inside the pooling pass
+    t->tmp.off = mark;
+  }
+  {
+    // conv2 / conv3 (conv3x3_halo) hand their BatchNorm the statistics of the map they store: no reduce pass over 328 MB
+    const size_t mark = t->tmp.off;
+    float* stp = nullptr;
+    int str = 0;
+    T_TRY(conv_fwd_stats(t, ss.conv2, S.a1, B, H0, H0, S.z2, &stp, &str));
+    T_TRY(bn_fwd(t, pfx + "bn2", S.z2, (int)M0, g.C1, ACT_LRELU, nullptr, S.a2, &S.b2, nullptr, stp, str));
+    t->tmp.off = mark;
+    T_TRY(conv_fwd_stats(t, ss.conv3, S.a2, B, H0, H0, S.z3, &stp, &str));
+    T_TRY(bn_fwd(t, pfx + "bn3", S.z3, (int)M0, g.C1, ACT_LRELU, nullptr, nullptr, &S.b3, nullptr, stp, str));      // statistics only: applied inside the pooling pass below
+    t->tmp.off = mark;
+  }
+  {
+    float* pt = nullptr;
+    if (g.pos) {
+      const fsvit_param* pos = getp(t, g.pos);
+      if (!pos) return FSVIT_ERR_KEY;
+      // pos_embed is [1,C,H,W] in the checkpoint; transpose to [HW][C] in tmp
+      pt = (float*)t->tmp.take((size_t)H1 * H1 * g.C1 * 4);
+      NEED(pt);
+      T_RUN(launch_transpose_cols(pos->data, pt, g.C1, H1 * H1, 0, H1 * H1, g.C1, 0, st));   // in [C][HW] -> out [HW][C]
+    }
+    T_RUN(launch_bn_pool_fwd(S.z3, S.b3.sa, S.b3.sb, S.zd, pt, S.x1, S.arg, B, H1, H1, g.C1, dt, st, S.bd.sa, S.bd.sb));      // LeakyReLU(bn3(z3) + bn_d(zd)) -> MaxPool -> + pos
+  }
+  return 0;
+}
+
+// dx: the gradient of S.x1
+int stem_backward(TB* t, const StemGeo& g, StemSave& S, const void* dx) {
+  const StemSpecs ss = stem_specs(g);
+  const std::string pfx = g.pfx;
+  const int B = t->B, dt = t->dtype, H0 = g.H0, H1 = g.H1;
+  hipStream_t st = t->st;
+  const size_t M0 = (size_t)B * H0 * H0;
+  const fsvit_param* pos = g.pos ? getp(t, g.pos) : nullptr;
+  if (g.pos && !pos) return FSVIT_ERR_KEY;
+  if (pos && (pos->grad || t->save.dry)) {
+    float* ps = (float*)t->tmp.take((size_t)H1 * H1 * g.C1 * 4); NEED(ps);
+    T_TRY(side_guard(t, ps, (size_t)H1 * H1 * g.C1 * 4));
+    T_RUN(launch_batch_sum(dx, ps, B, (size_t)H1 * H1 * g.C1, dt, st));
+    T_RUN(launch_transpose_cols(ps, pos->grad, H1 * H1, g.C1, 0, g.C1, H1 * H1, 0, st));
+  }
+  void* da3 = take_tmp(t, M0 * g.C1); NEED(da3);
+  void* g3 = take_tmp(t, M0 * g.C1); NEED(g3);
+  T_TRY(side_guard(t, da3, M0 * g.C1 * t->es));
+  T_TRY(side_guard(t, g3, M0 * g.C1 * t->es));
+  void* da2 = nullptr;
+  if (pool_bn_bwd_supported(g.C1, dt)) {
+    // bn3 and the identity path's BatchNorm see the same gradient - the pooled gradient routed to each window's arg-max with the LeakyReLU slope;
+    // their reductions and apply passes are formed from the pooled gradient itself (train_kernels.hip pool_bn_bwd_*): da3 := dz3, g3 := dzd
+    const fsvit_param *g3w = getp(t, pfx + "bn3.weight"), *b3w = getp(t, pfx + "bn3.bias"), *gdw = getp(t, pfx + "downsample.1.weight"), *bdw = getp(t, pfx + "downsample.1.bias");
+    if (!g3w || !b3w || !gdw || !bdw) return FSVIT_ERR_KEY;
+    const int C = g.C1, nb = pool_bn_bwd_blocks(B, H1, H1, C, dt);
+    float* part = (float*)t->tmp.take((size_t)nb * 4 * C * 4); NEED(part);
+    float* coef = (float*)t->tmp.take((size_t)10 * C * 4); NEED(coef);
+    float *coef3 = coef, *coefd = coef + 3 * C, *scr = coef + 6 * C;
+    T_RUN(launch_pool_bn_bwd_reduce(dx, S.arg, S.z3, S.zd, S.b3.mean, S.b3.invstd, S.bd.mean, S.bd.invstd, part, part + (size_t)nb * 2 * C, B, H1, H1, C, dt, st));
+    T_RUN(launch_bn_bwd_finalize_nblk(part, nb, (int)M0, C, g3w->data, S.b3.invstd, g3w->grad ? g3w->grad : scr, b3w->grad ? b3w->grad : scr + C, coef3, coef3 + C,
+                                      coef3 + 2 * C, t->freeze_bn ? 1 : 0, st));
+    T_RUN(launch_bn_bwd_finalize_nblk(part + (size_t)nb * 2 * C, nb, (int)M0, C, gdw->data, S.bd.invstd, gdw->grad ? gdw->grad : scr + 2 * C, bdw->grad ? bdw->grad : scr + 3 * C,
+                                      coefd, coefd + C, coefd + 2 * C, t->freeze_bn ? 1 : 0, st));
+    T_RUN(launch_pool_bn_bwd_apply(dx, S.arg, S.z3, S.zd, S.b3.mean, S.b3.invstd, S.bd.mean, S.bd.invstd, coef3, coefd, da3, g3, B, H1, H1, C, dt, st));
+    T_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
+    da2 = take_tmp(t, M0 * g.C1); NEED(da2);
+    T_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
+    T_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, g3));
+  } else {
+    T_RUN(launch_pool_act_bwd(dx, S.arg, g3, B, H1, H1, g.C1, dt, st));                      // gradient at (bn3(z3) + identity): max-pool routing x LeakyReLU slope
+    T_TRY(bn_bwd(t, pfx + "bn3", S.b3, g3, da3));                                              // da3 := dz3
+    T_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
+    da2 = take_tmp(t, M0 * g.C1); NEED(da2);
+    T_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
+    // identity path: ad = bn_d(zd)
+    T_TRY(bn_bwd(t, pfx + "downsample.1", S.bd, g3, da3));                                     // da3 := dzd
+    T_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, da3));
+  }
+  // bn2 / bn1 are followed by a LeakyReLU: its slope rides in the BatchNorm backward's two passes (no bn_act_bwd pass, no 328 MB map)
+  T_TRY(bn_bwd(t, pfx + "bn2", S.b2, da2, da2, nullptr, nullptr, nullptr, 0, true));         // da2 := dz2 (in place)
+  T_TRY(conv_bwd_weight(t, ss.conv2, S.a1, B, H0, H0, da2));
+  void* da1 = take_tmp(t, M0 * g.C0); NEED(da1);
+  T_TRY(conv_bwd_data(t, ss.conv2, da2, B, H0, H0, da1));
+  T_TRY(bn_bwd(t, pfx + "bn1", S.b1, da1, da1, nullptr, nullptr, nullptr, 0, true));         // da1 := dz1 (in place)
+  T_TRY(conv_bwd_weight(t, ss.conv1, S.patches, B, H0, H0, da1));
+  return 0;
 }
 
 // ================================================================ specs
 struct Specs {
-  ConvSpec conv1, down, conv2, conv3, pe2, pe3;
+  ConvSpec pe2, pe3;
   std::vector<ConvSpec> s1c1, s1c2, s1c3;
   struct A { ConvSpec qkv, proj, fc1, fc2; };
   std::vector<A> s2, s3;
@@ -522,10 +675,6 @@ struct Specs {
 Specs make_specs(const TR* t) {
   Specs s;
   auto mk = [](std::string n, int O, int Ig, int k, int stride, int pad, int groups) { ConvSpec c; c.wname = n; c.O = O; c.Ig = Ig; c.KH = c.KW = k; c.stride = stride; c.pad = pad; c.groups = groups; return c; };
-  s.conv1 = mk("stem.conv1.weight", t->C0, 3, 3, 2, 1, 1); s.conv1.via_patches = true;
-  s.down = mk("stem.downsample.0.weight", t->C1, 3, 3, 2, 1, 1); s.down.via_patches = true;
-  s.conv2 = mk("stem.conv2.weight", t->C1, t->C0, 3, 1, 1, 1);
-  s.conv3 = mk("stem.conv3.weight", t->C1, t->C1, 3, 1, 1, 1);
   for (int i = 0; i < t->cfg.depth[0]; ++i) {
     const std::string p = "stage1." + std::to_string(i) + ".mlp.";
     s.s1c1.push_back(mk(p + "conv1.weight", t->hid1, t->C1, 1, 1, 0, 1));
@@ -556,51 +705,13 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
   const Specs sp = make_specs(t);
   const int B = t->B, dt = t->dtype;
   hipStream_t st = t->st;
-  const int img = t->cfg.img_size, H0 = t->H0, H1 = t->H1;
-  const size_t M0 = (size_t)B * H0 * H0, M1 = (size_t)B * H1 * H1;
+  const int H1 = t->H1;
+  const size_t M1 = (size_t)B * H1 * H1;
   const int nblk = t->cfg.depth[0] + t->cfg.depth[1] + t->cfg.depth[2];
   int dp_call = 0, blk = 0;
 
-  // ---- stem (visformer.py:219-239)
-  auto& S = t->stem;
-  NEED(S.patches = take_act(t, M0 * 32)); NEED(S.z1 = take_act(t, M0 * t->C0)); NEED(S.a1 = take_act(t, M0 * t->C0));
-  NEED(S.zd = take_act(t, M0 * t->C1)); S.ad = nullptr; NEED(S.z2 = take_act(t, M0 * t->C1)); NEED(S.a2 = take_act(t, M0 * t->C1));
-  NEED(S.z3 = take_act(t, M0 * t->C1)); S.a3 = nullptr; NEED(S.arg = (unsigned char*)t->save.take(M1 * t->C1)); NEED(S.x1 = take_act(t, M1 * t->C1));
-  T_RUN(launch_im2col27(x, S.patches, B, img, img, H0, H0, dt, st));
-  {
-    // (the producing GEMMs hand the BatchNorm statistics of the maps they store to the finalize: no reduce pass, ConvGemmParams::stats)
-    const size_t mark = t->tmp.off;
-    float* stp = nullptr;
-    int str = 0;
-    T_TRY(conv_fwd_stats(t, sp.conv1, S.patches, B, H0, H0, S.z1, &stp, &str));
-    T_TRY(bn_fwd(t, "stem.bn1", S.z1, (int)M0, t->C0, ACT_LRELU, nullptr, S.a1, &S.b1, nullptr, stp, str));
-    t->tmp.off = mark;
-    T_TRY(conv_fwd_stats(t, sp.down, S.patches, B, H0, H0, S.zd, &stp, &str));
-    T_TRY(bn_fwd(t, "stem.downsample.1", S.zd, (int)M0, t->C1, ACT_NONE, nullptr, nullptr, &S.bd, nullptr, stp, str));      // statistics only: applied inside the pooling pass
-    t->tmp.off = mark;
-  }
-  {
-    // conv2 / conv3 (conv3x3_halo) hand their BatchNorm the statistics of the map they store: no reduce pass over 328 MB
-    const size_t mark = t->tmp.off;
-    float* stp = nullptr;
-    int str = 0;
-    T_TRY(conv_fwd_stats(t, sp.conv2, S.a1, B, H0, H0, S.z2, &stp, &str));
-    T_TRY(bn_fwd(t, "stem.bn2", S.z2, (int)M0, t->C1, ACT_LRELU, nullptr, S.a2, &S.b2, nullptr, stp, str));
-    t->tmp.off = mark;
-    T_TRY(conv_fwd_stats(t, sp.conv3, S.a2, B, H0, H0, S.z3, &stp, &str));
-    T_TRY(bn_fwd(t, "stem.bn3", S.z3, (int)M0, t->C1, ACT_LRELU, nullptr, nullptr, &S.b3, nullptr, stp, str));      // statistics only: applied inside the pooling pass below
-    t->tmp.off = mark;
-  }
-  {
-    const fsvit_param* pos = getp(t, "pos_embed1");
-    if (!pos) return FSVIT_ERR_KEY;
-    // pos_embed is [1,C,H,W] in the checkpoint; transpose to [HW][C] in tmp
-    float* pt = (float*)t->tmp.take((size_t)H1 * H1 * t->C1 * 4);
-    NEED(pt);
-    T_RUN(launch_transpose_cols(pos->data, pt, t->C1, H1 * H1, 0, H1 * H1, t->C1, 0, st));   // in [C][HW] -> out [HW][C]
-    T_RUN(launch_bn_pool_fwd(S.z3, S.b3.sa, S.b3.sb, S.zd, pt, S.x1, S.arg, B, H1, H1, t->C1, dt, st, S.bd.sa, S.bd.sb));      // LeakyReLU(bn3(z3) + bn_d(zd)) -> MaxPool -> + pos
-  }
-  void* xcur = S.x1;
+  T_TRY(stem_forward(t, t->geo(), t->stem, x));
+  void* xcur = t->stem.x1;
   // residual adds in front of a BatchNorm are queued here and computed by that BatchNorm's reduce pass (bn_fwd); flush_add() launches a queued
   // add on its own where the consumer is not a BatchNorm
   PendingAdd pend;
@@ -731,8 +842,8 @@ int train_backward_impl(TB* tb, const float* dfeat) {
   const Specs sp = make_specs(t);
   const int B = t->B, dt = t->dtype;
   hipStream_t st = t->st;
-  const int H0 = t->H0, H1 = t->H1;
-  const size_t M0 = (size_t)B * H0 * H0, M1 = (size_t)B * H1 * H1, M3 = (size_t)B * t->H3 * t->H3;
+  const int H1 = t->H1;
+  const size_t M1 = (size_t)B * H1 * H1, M3 = (size_t)B * t->H3 * t->H3;
   // gradient of the residual stream, ping-pong in tmp
   void* dx = take_tmp(t, M3 * t->C3); NEED(dx);
   {
@@ -865,59 +976,7 @@ int train_backward_impl(TB* tb, const float* dfeat) {
     else T_TRY(bn_bwd(t, p + "norm2.bn", b.bn, dxn, dx, dx));
     t->tmp.off = mark;
   }
-  // ---- stem
-  {
-    auto& S = t->stem;
-    const fsvit_param* pos = getp(t, "pos_embed1");
-    if (!pos) return FSVIT_ERR_KEY;
-    if (pos->grad || t->save.dry) {
-      float* ps = (float*)t->tmp.take((size_t)H1 * H1 * t->C1 * 4); NEED(ps);
-      T_TRY(side_guard(t, ps, (size_t)H1 * H1 * t->C1 * 4));
-      T_RUN(launch_batch_sum(dx, ps, B, (size_t)H1 * H1 * t->C1, dt, st));
-      T_RUN(launch_transpose_cols(ps, pos->grad, H1 * H1, t->C1, 0, t->C1, H1 * H1, 0, st));
-    }
-    void* da3 = take_tmp(t, M0 * t->C1); NEED(da3);
-    void* g3 = take_tmp(t, M0 * t->C1); NEED(g3);
-    T_TRY(side_guard(t, da3, M0 * t->C1 * t->es));
-    T_TRY(side_guard(t, g3, M0 * t->C1 * t->es));
-    void* da2 = nullptr;
-    if (pool_bn_bwd_supported(t->C1, dt)) {
-      // bn3 and the identity path's BatchNorm see the same gradient - the pooled gradient routed to each window's arg-max with the LeakyReLU slope;
-      // their reductions and apply passes are formed from the pooled gradient itself (train_kernels.hip pool_bn_bwd_*): da3 := dz3, g3 := dzd
-      const fsvit_param *g3w = getp(t, "stem.bn3.weight"), *b3w = getp(t, "stem.bn3.bias"), *gdw = getp(t, "stem.downsample.1.weight"), *bdw = getp(t, "stem.downsample.1.bias");
-      if (!g3w || !b3w || !gdw || !bdw) return FSVIT_ERR_KEY;
-      const int C = t->C1, nb = pool_bn_bwd_blocks(B, H1, H1, C, dt);
-      float* part = (float*)t->tmp.take((size_t)nb * 4 * C * 4); NEED(part);
-      float* coef = (float*)t->tmp.take((size_t)10 * C * 4); NEED(coef);
-      float *coef3 = coef, *coefd = coef + 3 * C, *scr = coef + 6 * C;
-      T_RUN(launch_pool_bn_bwd_reduce(dx, S.arg, S.z3, S.zd, S.b3.mean, S.b3.invstd, S.bd.mean, S.bd.invstd, part, part + (size_t)nb * 2 * C, B, H1, H1, C, dt, st));
-      T_RUN(launch_bn_bwd_finalize_nblk(part, nb, (int)M0, C, g3w->data, S.b3.invstd, g3w->grad ? g3w->grad : scr, b3w->grad ? b3w->grad : scr + C, coef3, coef3 + C,
-                                        coef3 + 2 * C, t->freeze_bn ? 1 : 0, st));
-      T_RUN(launch_bn_bwd_finalize_nblk(part + (size_t)nb * 2 * C, nb, (int)M0, C, gdw->data, S.bd.invstd, gdw->grad ? gdw->grad : scr + 2 * C, bdw->grad ? bdw->grad : scr + 3 * C,
-                                        coefd, coefd + C, coefd + 2 * C, t->freeze_bn ? 1 : 0, st));
-      T_RUN(launch_pool_bn_bwd_apply(dx, S.arg, S.z3, S.zd, S.b3.mean, S.b3.invstd, S.bd.mean, S.bd.invstd, coef3, coefd, da3, g3, B, H1, H1, C, dt, st));
-      T_TRY(conv_bwd_weight(t, sp.conv3, S.a2, B, H0, H0, da3));
-      da2 = take_tmp(t, M0 * t->C1); NEED(da2);
-      T_TRY(conv_bwd_data(t, sp.conv3, da3, B, H0, H0, da2));
-      T_TRY(conv_bwd_weight(t, sp.down, S.patches, B, H0, H0, g3));
-    } else {
-      T_RUN(launch_pool_act_bwd(dx, S.arg, g3, B, H1, H1, t->C1, dt, st));                      // gradient at (bn3(z3) + identity): max-pool routing x LeakyReLU slope
-      T_TRY(bn_bwd(t, "stem.bn3", S.b3, g3, da3));                                              // da3 := dz3
-      T_TRY(conv_bwd_weight(t, sp.conv3, S.a2, B, H0, H0, da3));
-      da2 = take_tmp(t, M0 * t->C1); NEED(da2);
-      T_TRY(conv_bwd_data(t, sp.conv3, da3, B, H0, H0, da2));
-      // identity path: ad = bn_d(zd)
-      T_TRY(bn_bwd(t, "stem.downsample.1", S.bd, g3, da3));                                     // da3 := dzd
-      T_TRY(conv_bwd_weight(t, sp.down, S.patches, B, H0, H0, da3));
-    }
-    // bn2 / bn1 are followed by a LeakyReLU: its slope rides in the BatchNorm backward's two passes (no bn_act_bwd pass, no 328 MB map)
-    T_TRY(bn_bwd(t, "stem.bn2", S.b2, da2, da2, nullptr, nullptr, nullptr, 0, true));         // da2 := dz2 (in place)
-    T_TRY(conv_bwd_weight(t, sp.conv2, S.a1, B, H0, H0, da2));
-    void* da1 = take_tmp(t, M0 * t->C0); NEED(da1);
-    T_TRY(conv_bwd_data(t, sp.conv2, da2, B, H0, H0, da1));
-    T_TRY(bn_bwd(t, "stem.bn1", S.b1, da1, da1, nullptr, nullptr, nullptr, 0, true));         // da1 := dz1 (in place)
-    T_TRY(conv_bwd_weight(t, sp.conv1, S.patches, B, H0, H0, da1));
-  }
+  T_TRY(stem_backward(t, t->geo(), t->stem, dx));
   return run_finalizes(t);
 }
 
@@ -994,10 +1053,12 @@ int vit_ln_bwd(VT* t, const std::string& name, const void* dy, const void* x, co
   return 0;
 }
 
+int vit_blocks_forward(VT* t, const VSpecs& sp, void* xcur, float* feat);
+
 int vit_forward_impl(TB* tb, const float* x, float* feat) {
   VT* t = static_cast<VT*>(tb);
   const VSpecs sp = vit_specs(t);
-  const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
+  const int B = t->B, S = t->S, D = t->D, dt = t->dtype;
   const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
   hipStream_t st = t->st;
   const fsvit_param *cls = getp(t, "cls_token"), *pos = getp(t, "pos_embed"), *peb = getp(t, "patch_embed.proj.bias");
@@ -1012,14 +1073,23 @@ int vit_forward_impl(TB* tb, const float* x, float* feat) {
     T_RUN(launch_vit_assemble(zpe, cls->data, pos->data, xcur, B, S, D, dt, st));
     t->tmp.off = mark;
   }
+  return vit_blocks_forward(t, sp, xcur, feat);
+}
+
+// The pre-LN blocks (deit.py:61-78; lvvit.py:134-155 with hidden width, qkv bias, LayerNorm eps and the residual-branch scale 1 / skip_lam as parameters)
+// and the final norm on the cls row: tokens x0 [B][S][D] -> feat [B][D]
+int vit_blocks_forward(VT* t, const VSpecs& sp, void* xcur, float* feat) {
+  const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
+  const size_t M = (size_t)B * S;
+  hipStream_t st = t->st;
   t->blk.resize(t->vcfg.depth);
   const float scale = 1.0f / std::sqrt((float)t->hd);
   int dp_call = 0;
   for (int i = 0; i < t->vcfg.depth; ++i) {
     auto& b = t->blk[i];
     const std::string p = "blocks." + std::to_string(i) + ".";
-    const fsvit_param *bq = getp(t, p + "attn.qkv.bias"), *bp = getp(t, p + "attn.proj.bias"), *b1 = getp(t, p + "mlp.fc1.bias"), *b2 = getp(t, p + "mlp.fc2.bias");
-    if (!bq || !bp || !b1 || !b2) return FSVIT_ERR_KEY;
+    const fsvit_param *bq = t->qkv_bias ? getp(t, p + "attn.qkv.bias") : nullptr, *bp = getp(t, p + "attn.proj.bias"), *b1 = getp(t, p + "mlp.fc1.bias"), *b2 = getp(t, p + "mlp.fc2.bias");
+    if ((t->qkv_bias && !bq) || !bp || !b1 || !b2) return FSVIT_ERR_KEY;
     b.x = xcur;
     NEED(b.xn1 = take_act(t, M * D)); NEED(b.qkv = take_act(t, M * 3 * heads * hdp)); NEED(b.ctx = take_act(t, M * heads * hdp));
     NEED(b.x1 = take_act(t, M * D)); NEED(b.xn2 = take_act(t, M * D)); NEED(b.z1 = take_act(t, M * hid)); NEED(b.h = take_act(t, M * hid));
@@ -1028,7 +1098,7 @@ int vit_forward_impl(TB* tb, const float* x, float* feat) {
     void* zp = take_tmp(t, M * D); NEED(zp);
     T_TRY(vit_ln_fwd(t, p + "norm1", b.x, b.xn1, &b.m1, &b.r1, (int)M));
     const float* bqp = nullptr;
-    T_TRY(padded_bias(t, bq, 3 * heads * t->hd, t->hd, hdp, &bqp));
+    if (bq) T_TRY(padded_bias(t, bq, 3 * heads * t->hd, t->hd, hdp, &bqp));
     T_TRY(conv_fwd(t, sp.qkv[i], b.xn1, B, S, 1, b.qkv, bqp));
     T_RUN(launch_attention(b.qkv, b.ctx, B, S, heads, hdp, scale, t->gdt == 2 ? 2 : dt, st));
     T_TRY(conv_fwd(t, sp.proj[i], b.ctx, B, S, 1, zp, bp->data));
@@ -1053,11 +1123,10 @@ int vit_forward_impl(TB* tb, const float* x, float* feat) {
   return 0;
 }
 
-int vit_backward_impl(TB* tb, const float* dfeat) {
-  VT* t = static_cast<VT*>(tb);
-  const VSpecs sp = vit_specs(t);
+// dfeat [B][D] -> *dx_out [B][S][D] (tmp), the gradient of the tokens in front of block 0; every block and final-norm parameter gradient on the way
+int vit_blocks_backward(VT* t, const VSpecs& sp, const float* dfeat, void** dx_out) {
   const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
-  const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
+  const size_t M = (size_t)B * S;
   hipStream_t st = t->st;
   const fsvit_param *ng = getp(t, "norm.weight"), *nb = getp(t, "norm.bias");
   if (!ng || !nb) return FSVIT_ERR_KEY;
@@ -1073,8 +1142,8 @@ int vit_backward_impl(TB* tb, const float* dfeat) {
   for (int i = t->vcfg.depth - 1; i >= 0; --i) {
     auto& b = t->blk[i];
     const std::string p = "blocks." + std::to_string(i) + ".";
-    const fsvit_param *bq = getp(t, p + "attn.qkv.bias"), *bp = getp(t, p + "attn.proj.bias"), *b1 = getp(t, p + "mlp.fc1.bias"), *b2 = getp(t, p + "mlp.fc2.bias");
-    if (!bq || !bp || !b1 || !b2) return FSVIT_ERR_KEY;
+    const fsvit_param *bq = t->qkv_bias ? getp(t, p + "attn.qkv.bias") : nullptr, *bp = getp(t, p + "attn.proj.bias"), *b1 = getp(t, p + "mlp.fc1.bias"), *b2 = getp(t, p + "mlp.fc2.bias");
+    if ((t->qkv_bias && !bq) || !bp || !b1 || !b2) return FSVIT_ERR_KEY;
     const size_t mark = t->tmp.off;
     // mlp branch: out = x1 + s2 * fc2(gelu(fc1(norm2(x1))))
     void* dz2 = take_tmp(t, M * D); NEED(dz2);
@@ -1100,29 +1169,107 @@ int vit_backward_impl(TB* tb, const float* dfeat) {
     T_TRY(side_guard(t, dqkv, M * 3 * heads * hdp * t->es));
     T_RUN(launch_attention_bwd(b.qkv, dctx, dqkv, B, S, heads, t->hd, hdp, scale, dt, st));
     T_TRY(conv_bwd_weight(t, sp.qkv[i], b.xn1, B, S, 1, dqkv));
-    T_TRY(bias_grad(t, bq, dqkv, (int)M, 3 * heads * t->hd, t->hd, hdp));
+    if (bq) T_TRY(bias_grad(t, bq, dqkv, (int)M, 3 * heads * t->hd, t->hd, hdp));
     T_TRY(conv_bwd_data(t, sp.qkv[i], dqkv, B, S, 1, dxn));
     T_TRY(vit_ln_bwd(t, p + "norm1", dxn, b.x, b.m1, b.r1, dx, dx, (int)M));
     t->tmp.off = mark;
   }
-  // embedding: tokens = [cls + pos0 | conv(patches) + bias + pos]
+  *dx_out = dx;
+  return 0;
+}
+
+// embedding: tokens = [cls + pos0 | conv(patches) + bias + pos]: the gradients of pos_embed and cls_token, and *dzpe_out [B * np][D] (tmp) = the patch rows of dx
+int vit_embed_backward(VT* t, const void* dx, void** dzpe_out) {
+  const int B = t->B, S = t->S, D = t->D, dt = t->dtype;
+  hipStream_t st = t->st;
+  const fsvit_param *cls = getp(t, "cls_token"), *pos = getp(t, "pos_embed");
+  if (!cls || !pos) return FSVIT_ERR_KEY;
+  float* ps = (float*)t->tmp.take((size_t)S * D * 4); NEED(ps);
+  T_RUN(launch_batch_sum(dx, ps, B, (size_t)S * D, dt, st));
+  if (!t->tmp.dry) {
+    hipError_t e = hipSuccess;
+    if (pos->grad) e = hipMemcpyAsync(pos->grad, ps, (size_t)S * D * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && cls->grad) e = hipMemcpyAsync(cls->grad, ps, (size_t)D * 4, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return fsvit_set_error((int)e, "pos / cls gradient");
+  }
+  void* dzpe = take_tmp(t, (size_t)B * t->np * D); NEED(dzpe);
+  T_TRY(side_sync(t));
+  T_RUN(launch_vit_patch_rows(dx, dzpe, B, S, D, dt, st));
+  *dzpe_out = dzpe;
+  return 0;
+}
+
+int vit_backward_impl(TB* tb, const float* dfeat) {
+  VT* t = static_cast<VT*>(tb);
+  const VSpecs sp = vit_specs(t);
+  const int Mp = t->B * t->np;
+  const fsvit_param* peb = getp(t, "patch_embed.proj.bias");
+  if (!peb) return FSVIT_ERR_KEY;
+  void *dx = nullptr, *dzpe = nullptr;
+  T_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
+  T_TRY(vit_embed_backward(t, dx, &dzpe));
+  T_TRY(conv_bwd_weight(t, sp.pe, t->patches, Mp, 1, 1, dzpe));
+  T_TRY(bias_grad(t, peb, dzpe, Mp, t->D, 1, 1));
+  return run_finalizes(t);
+}
+
+// ================================================================ LV-ViT trainer
+// patch_embed.proj: 4x4 / stride 4 over the pooled NHWC map.  rows: the weight gradient's view - the patches do not overlap, so the im2col of the map is a
+// permutation (launch_patchk) and the layer a Linear over K = 16 C0 columns in (ky, kx, c) order
+ConvSpec lvvit_proj_spec(const LT* t, bool rows) {
+  ConvSpec c;
+  c.wname = "patch_embed.proj.weight"; c.O = t->D; c.Ig = t->C0; c.KH = c.KW = 4; c.stride = 4; c.pad = 0; c.via_rows = rows;
+  return c;
+}
+
+int lvvit_forward_impl(TB* tb, const float* x, float* feat) {
+  LT* t = static_cast<LT*>(tb);
+  VSpecs sp = vit_specs(t);
+  sp.pe = lvvit_proj_spec(t, false);
+  const int B = t->B, S = t->S, D = t->D, dt = t->dtype;
+  const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
   const fsvit_param *cls = getp(t, "cls_token"), *pos = getp(t, "pos_embed"), *peb = getp(t, "patch_embed.proj.bias");
   if (!cls || !pos || !peb) return FSVIT_ERR_KEY;
+  T_TRY(stem_forward(t, t->geo(), t->stem, x));
+  void* xcur = take_act(t, M * D); NEED(xcur);
   {
-    float* ps = (float*)t->tmp.take((size_t)S * D * 4); NEED(ps);
-    T_RUN(launch_batch_sum(dx, ps, B, (size_t)S * D, dt, st));
-    if (!t->tmp.dry) {
-      hipError_t e = hipSuccess;
-      if (pos->grad) e = hipMemcpyAsync(pos->grad, ps, (size_t)S * D * 4, hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess && cls->grad) e = hipMemcpyAsync(cls->grad, ps, (size_t)D * 4, hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) return fsvit_set_error((int)e, "pos / cls gradient");
-    }
-    void* dzpe = take_tmp(t, Mp * D); NEED(dzpe);
-    T_TRY(side_sync(t));
-    T_RUN(launch_vit_patch_rows(dx, dzpe, B, S, D, dt, st));
-    T_TRY(conv_bwd_weight(t, sp.pe, t->patches, (int)Mp, 1, 1, dzpe));
-    T_TRY(bias_grad(t, peb, dzpe, (int)Mp, D, 1, 1));
+    const size_t mark = t->tmp.off;
+    void* zpe = take_tmp(t, Mp * D); NEED(zpe);
+    T_TRY(conv_fwd(t, sp.pe, t->stem.x1, B, t->H1, t->H1, zpe, peb->data));
+    T_RUN(launch_vit_assemble(zpe, cls->data, pos->data, xcur, B, S, D, dt, t->st));
+    t->tmp.off = mark;
   }
+  return vit_blocks_forward(t, sp, xcur, feat);
+}
+
+int lvvit_backward_impl(TB* tb, const float* dfeat) {
+  LT* t = static_cast<LT*>(tb);
+  const VSpecs sp = vit_specs(t);
+  const int B = t->B, D = t->D, C0 = t->C0, H1 = t->H1, npw = t->npw, dt = t->dtype, Mp = B * t->np, Kr = 16 * C0;
+  hipStream_t st = t->st;
+  const fsvit_param *peb = getp(t, "patch_embed.proj.bias"), *w = getp(t, "patch_embed.proj.weight");
+  if (!peb || !w) return FSVIT_ERR_KEY;
+  void *dx = nullptr, *dzpe = nullptr;
+  T_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
+  T_TRY(vit_embed_backward(t, dx, &dzpe));
+  // weight gradient of the projection: wgrad1x1 over the permuted rows of the pooled map (K = 16 C0, N = D)
+  void* prow = take_tmp(t, (size_t)Mp * Kr); NEED(prow);
+  T_TRY(side_guard(t, prow, (size_t)Mp * Kr * t->es));
+  T_RUN(launch_patchk(t->stem.x1, prow, B, npw, npw, C0, 4, 1, dt, st));
+  T_TRY(conv_bwd_weight(t, lvvit_proj_spec(t, true), prow, B, npw, npw, dzpe));
+  T_TRY(bias_grad(t, peb, dzpe, Mp, D, 1, 1));
+  // data gradient: G[m][(ky,kx,c)] = dz[m] . W[:, c, ky, kx] in one GEMM, then the inverse permutation into the pooled map's gradient
+  const int bke = 128 / t->es, Kw = round_up(D, bke);
+  void* pk = nullptr;
+  T_TRY(packed_weight(t, PackJob{w->data, nullptr, D, C0, 4, 4, 1, 2, Kr, Kw, 1, 1, 1, 1}, (size_t)Kr * Kw * t->es, &pk));
+  void* G = take_tmp(t, (size_t)Mp * Kr); NEED(G);
+  ConvGemmParams p = gemm_params(dzpe, pk, G, B, npw, npw, D, D, 1, 1, 1, 0, Kr, Kr, D, Kw, 1);
+  T_TRY(side_guard(t, G, (size_t)Mp * Kr * t->es));
+  T_RUN(launch_conv_gemm(p, t->gdt, st));
+  void* dx1 = take_tmp(t, (size_t)B * H1 * H1 * C0); NEED(dx1);
+  T_TRY(side_guard(t, dx1, (size_t)B * H1 * H1 * C0 * t->es));
+  T_RUN(launch_patchk(G, dx1, B, npw, npw, C0, 4, 0, dt, st));
+  T_TRY(stem_backward(t, t->geo(), t->stem, dx1));
   return run_finalizes(t);
 }
 
@@ -1161,7 +1308,7 @@ int bn_pre_check(const TB* t, int n_img) {
 
 // the image-size messages restate the reference's asserts (visformer.py:283-284,431: "does not match"; deit.py:96-97: "doesn't match")
 void visformer_init(TR* t, const fsvit_visformer_cfg& cfg) {
-  t->cfg = cfg;
+  t->cfg = cfg; t->bn_eps = cfg.bn_eps;
   t->forward_walk = train_forward_impl; t->backward_walk = train_backward_impl; t->droppath_calls = droppath_calls; t->pre_check = bn_pre_check;
   t->img_size = cfg.img_size; t->size_fmt = "Input image size (%d*%d) does not match model (%d*%d).";
   const int D = cfg.embed_dim, kch = 64 / t->es;
@@ -1182,7 +1329,22 @@ void vit_init(VT* t, const fsvit_vit_cfg& cfg) {
   t->hidv = (int)(cfg.embed_dim * cfg.mlp_ratio); t->heads = cfg.num_heads; t->hd = cfg.embed_dim / cfg.num_heads; t->hdp = round_up(t->hd, kch);
 }
 
-// ================================================================ the step driver of both trainers
+void lvvit_init(LT* t, const fsvit_lvvit_cfg& cfg) {
+  t->lcfg = cfg; t->bn_eps = cfg.bn_eps; t->branch_scale = 1.0f / cfg.skip_lam; t->qkv_bias = false;
+  t->vcfg = fsvit_vit_cfg();
+  t->vcfg.img_size = cfg.img_size; t->vcfg.embed_dim = cfg.embed_dim; t->vcfg.depth = cfg.depth;
+  t->vcfg.num_heads = cfg.num_heads; t->vcfg.mlp_ratio = cfg.mlp_ratio; t->vcfg.ln_eps = cfg.ln_eps;
+  t->forward_walk = lvvit_forward_impl; t->backward_walk = lvvit_backward_impl; t->droppath_calls = vit_droppath_calls;      // (per-block rates as deit.py: get_dpr 'linear', lvvit.py:401-404)
+  t->img_size = cfg.img_size; t->size_fmt = "Input image size (%d*%d) doesn't match model (%d*%d).";
+  const int kch = 64 / t->es;
+  t->C0 = cfg.stem_channels; t->H0 = cfg.img_size / 2; t->H1 = cfg.img_size / 4;
+  t->D = cfg.embed_dim; t->npw = t->H1 / 4; t->np = t->npw * t->npw; t->S = t->np + 1;
+  t->K = t->Kp = 16 * t->C0;
+  if (const char* e = getenv("FSVIT_LVVIT_WGRAD")) t->wgrad_gemm = !strcmp(e, "gemm") ? true : !strcmp(e, "direct") ? false : t->wgrad_gemm;
+  t->hidv = (int)(cfg.embed_dim * cfg.mlp_ratio); t->heads = cfg.num_heads; t->hd = cfg.embed_dim / cfg.num_heads; t->hdp = round_up(t->hd, kch);
+}
+
+// ================================================================ the step driver of every trainer
 // bad_cfg: the caller's range check of *cfg (false for a null cfg); init: the model's geometry and its entries of TrainerBase
 template <class H, class Cfg>
 int trainer_create(const Cfg* cfg, int dtype, H** out, bool bad_cfg, const char* bad_cfg_msg, void (*init)(H*, const Cfg&)) {
@@ -1217,7 +1379,7 @@ int trainer_size_workspace(TB* t, int n_img, float rate, size_t* save_bytes, siz
   rc = t->backward_walk(t, nullptr);
   if (rc) return rc;
   if (t->tmp.peak > tp) tp = t->tmp.peak;
-  *save_bytes = align256(t->save.peak + t->pack_bytes + 256 + (size_t)t->droppath_calls(t, rate, nullptr) * n_img * 4 + 256);
+  *save_bytes = align256(t->save.peak + t->pack_bytes + 256 + (size_t)(t->droppath_calls(t, rate, nullptr) + (t->branch_scale != 1.f ? 1 : 0)) * n_img * 4 + 256);
   *tmp_bytes = align256(tp);
   return 0;
 }
@@ -1243,13 +1405,17 @@ int trainer_forward(TB* t, const fsvit_param* params, int n_params, const float*
   t->st = (hipStream_t)stream;
   t->save = Arena(); t->save.base = (unsigned char*)ws_dev; t->save.size = sb;
   t->tmp = Arena(); t->tmp.base = (unsigned char*)ws_dev + sb; t->tmp.size = ws_bytes - sb;
-  t->scales = nullptr;
-  if (drop_path_rate > 0.f) {                       // DropPath scale = mask / keep_prob per call (visformer.py:92-96; timm DropPath, deit.py:70,76-77)
+  t->scales = nullptr; t->n_dp = 0;
+  const bool branch = t->branch_scale != 1.f;      // (one more row: the constant scale of the calls without a rate)
+  if (drop_path_rate > 0.f || branch) {             // DropPath scale = mask / keep_prob per call (visformer.py:92-96; timm DropPath, deit.py:70,76-77)
     std::vector<float> keep;
-    const int ncalls = t->droppath_calls(t, drop_path_rate, &keep);
-    t->scales = (float*)t->save.take((size_t)ncalls * n_img * 4);
+    const int ncalls = drop_path_rate > 0.f ? t->droppath_calls(t, drop_path_rate, &keep) : 0;
+    t->scales = (float*)t->save.take((size_t)(ncalls + (branch ? 1 : 0)) * n_img * 4);
     if (!t->scales) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small");
-    T_RUN(launch_droppath_scales(masks_dev, t->scales, ncalls, n_img, keep.data(), t->st));
+    if (branch) for (float& k : keep) k /= t->branch_scale;
+    if (ncalls > 0) T_RUN(launch_droppath_scales(masks_dev, t->scales, ncalls, n_img, keep.data(), t->st));
+    if (branch) T_RUN(launch_fill_f32(t->scales + (size_t)ncalls * n_img, t->branch_scale, (size_t)n_img, t->st));
+    t->n_dp = ncalls;
   }
   T_TRY(run_packs(t));                              // every weight pack of this step (forward + data-gradient layouts) in one or two launches
   const int rc_f = t->forward_walk(t, x_nchw_dev, feat_dev);
@@ -1303,6 +1469,29 @@ extern "C" int fsvit_vit_train_forward(fsvit_vit_trainer* t, const fsvit_param* 
   return trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
 }
 extern "C" int fsvit_vit_train_backward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
+  return trainer_backward(t, params, n_params, dfeat_dev, stream);
+}
+
+extern "C" int fsvit_lvvit_trainer_create(const fsvit_lvvit_cfg* cfg, int dtype, fsvit_lvvit_trainer** out) {
+  const bool bad = cfg && (cfg->num_heads < 1 || cfg->embed_dim < 32 || cfg->embed_dim % cfg->num_heads || cfg->embed_dim % 8 || cfg->depth < 0 || cfg->stem_channels < 32 ||
+                           cfg->stem_channels % 32 || cfg->img_size != 80 || !(cfg->skip_lam > 0.f));
+  return trainer_create(cfg, dtype, out, bad, "bad LV-ViT configuration", lvvit_init);
+}
+extern "C" void fsvit_lvvit_trainer_destroy(fsvit_lvvit_trainer* t) { delete t; }
+extern "C" int fsvit_lvvit_trainer_droppath_calls(const fsvit_lvvit_trainer* t, float drop_path_rate) { return t ? vit_droppath_calls(t, drop_path_rate, nullptr) : 0; }
+extern "C" size_t fsvit_lvvit_trainer_workspace_bytes(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate) {
+  return trainer_workspace_bytes(t, params, n_params, n_img, drop_path_rate);
+}
+extern "C" int fsvit_lvvit_trainer_set_freeze_bn(fsvit_lvvit_trainer* t, int on) {
+  if (!t) return fsvit_set_error(FSVIT_ERR_ARG, "null trainer");
+  t->freeze_bn = on != 0;
+  return 0;
+}
+extern "C" int fsvit_lvvit_train_forward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
+                                         float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+  return trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
+}
+extern "C" int fsvit_lvvit_train_backward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
   return trainer_backward(t, params, n_params, dfeat_dev, stream);
 }
 

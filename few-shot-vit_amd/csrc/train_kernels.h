@@ -25,6 +25,8 @@ int launch_transpose_cols(const void* in, void* out, int M, int ld, int c0, int 
 int launch_im2col_t(const void* x, void* out, int B, int H, int W, int ld, int c0, int C, int KH, int KW, int stride, int pad, int OH, int OW, int Mpad,
                     int dtype, hipStream_t s);
 int launch_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int dtype, hipStream_t s);
+// k x k / stride k patches of an NHWC map [B][k OH][k OW][C] <-> rows [B*OH*OW][k*k*C] (k order (ky, kx, c)); gather: map -> rows, else rows -> map
+int launch_patchk(const void* src, void* dst, int B, int OH, int OW, int C, int k, int gather, int dtype, hipStream_t s);
 int bn_reduce_blocks(int M);
 // CALLERS: C / V channel lanes (V = 4, bf16 8 where C % 8 == 0) beyond 256 must be a multiple of 256 - the kernel's block barrier sits inside its per-pass
 // channel loop, a partial last pass would leave threads behind it.  Neither this launcher nor launch_colsum checks that (the fsvit_op_* entries do).

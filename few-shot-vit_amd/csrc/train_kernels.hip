@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void pack_weight_multi_kernel(const PackJobs j
 //  1  the same for a plain 1x1 layer without head-dim padding (dW[n][i] = sum_sp y[n][sp * Kc_pad + i], Ig % 4 == 0, Kc_pad % 4 == 0): 16-byte accesses
 //  2  a grouped conv computed as ONE dense split-K GEMM (all cross-group products included, only the diagonal blocks are kept; g = groups):
 //     y[groups*Ng][splits * Kc_pad] with k = (ky*KW + kx) * (groups*Ig) + g*Ig + i  ->  dW[groups*Ng][Ig][KH][KW]
-//  3  the direct 3x3 kernels' partials [split][job][tap][32][32] (same arithmetic, same summation order as wgrad3x3_finalize_kernel; g = grouped flag,
+//  3  the direct 3x3 kernels' partials [split][job][tap][32][32] (same arithmetic, same summation order as wgrad3x3_finalize_kernel; g = its job map: 0 dense, 1 grouped, 2 dense 96 -> 96,
 //     Kc_pad = njobs)
 __global__ __launch_bounds__(256) void wgrad_finalize_multi_kernel(const FinJobs jobs) {
   const FinJob j = jobs.job[blockIdx.y];
@@ -184,8 +184,8 @@ __global__ __launch_bounds__(256) void wgrad_finalize_multi_kernel(const FinJobs
       }
       for (; sp < splits; ++sp) s0 += *reinterpret_cast<const f32x4*>(y + (size_t)sp * total + idx);
       const f32x4 sv = (s0 + s1) + (s2 + s3);
-      const int o = grouped ? job * 32 + n : (job & 3) * 32 + n;
-      const int ig = grouped ? c : (job >> 3) * 64 + ((job >> 2) & 1) * 32 + c;
+      const int o = grouped == 2 ? (job % 3) * 32 + n : grouped ? job * 32 + n : (job & 3) * 32 + n;
+      const int ig = grouped == 2 ? (job / 3) * 32 + c : grouped ? c : (job >> 3) * 64 + ((job >> 2) & 1) * 32 + c;
 #pragma unroll
       for (int e = 0; e < 4; ++e) dw[((size_t)o * Ig + ig + e) * 9 + tp] = sv[e];
     }
@@ -304,6 +304,26 @@ __global__ __launch_bounds__(256) void unpatch2_kernel(const T* __restrict__ g, 
     const int oy = (int)(t2 % OH);
     const size_t b = t2 / OH;
     dx[((b * 2 * OH + 2 * oy + (tap >> 1)) * 2 * OW + 2 * ox + (tap & 1)) * C + c] = g[idx];
+  }
+}
+
+// Non-overlapping k x k / stride k patches of an NHWC map [B][k OH][k OW][C] as rows [B*OH*OW][k*k*C], k order (ky, kx, c) - the im2col of such a
+// conv is a permutation.  GATHER: map -> rows (the weight gradient's input rows); else rows -> map (the data gradient's scatter, every pixel once)
+template <typename T, bool GATHER>
+__global__ __launch_bounds__(256) void patchk_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int OH, int OW, int C, int k) {
+  const int c4n = C / 4;
+  const size_t total = (size_t)B * OH * OW * k * k * c4n;
+  GS_LOOP(idx, total) {
+    const int c = (int)(idx % c4n) * 4;
+    size_t t2 = idx / c4n;
+    const int kx = (int)(t2 % k); t2 /= k;
+    const int ky = (int)(t2 % k); t2 /= k;
+    const int ox = (int)(t2 % OW); t2 /= OW;
+    const int oy = (int)(t2 % OH);
+    const size_t b = t2 / OH;
+    const size_t map = ((b * k * OH + (size_t)k * oy + ky) * k * OW + (size_t)k * ox + kx) * C + c, row = idx * 4;
+    if (GATHER) store4<T>(dst + row, load4<T>(src + map));
+    else store4<T>(dst + map, load4<T>(src + row));
   }
 }
 
@@ -1375,6 +1395,13 @@ int launch_unpatch2(const void* g, void* dx, int B, int OH, int OW, int C, int d
   const size_t total = (size_t)B * OH * OW * 4 * C;
   return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
     return launch(unpatch2_kernel<T>, gs_grid(total), 256, 0, s, g, dx, B, OH, OW, C); });
+}
+int launch_patchk(const void* src, void* dst, int B, int OH, int OW, int C, int k, int gather, int dtype, hipStream_t s) {
+  if (C % 4 || k < 1) return (int)hipErrorInvalidValue;
+  const size_t total = (size_t)B * OH * OW * k * k * (C / 4);
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return gather ? launch(patchk_kernel<T, true>, gs_grid(total), 256, 0, s, src, dst, B, OH, OW, C, k)
+                  : launch(patchk_kernel<T, false>, gs_grid(total), 256, 0, s, src, dst, B, OH, OW, C, k); });
 }
 int bn_reduce_blocks(int M) { int nb = (M + 63) / 64; return nb > 512 ? 512 : nb; }
 int launch_bn_reduce(const void* a, const void* z, const float* mean, const float* invstd, float* partial, int M, int C, int bwd, int dtype, hipStream_t s,

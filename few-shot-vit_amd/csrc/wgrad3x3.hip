@@ -32,7 +32,8 @@ typedef short s4 __attribute__((ext_vector_type(4)));
 }  // namespace wg3
 
 // NC / CC: dz / x columns staged per workgroup.  (256, 256): grouped conv, wave j = group j.  (128, 64): dense conv, wave j = n-block j & 3,
-// c-block j >> 2 of the 64 input channels blockIdx.y * 64 ..
+// c-block j >> 2 of the 64 input channels blockIdx.y * 64 ..  (96, 32): the dense 96 -> 96 layers of the LV-ViT stem - nine 32 x 32 jobs as a
+// 3 x 3 grid: workgroup column blockIdx.y = c-block, waves 0 .. 2 = the three n-blocks (one per SIMD), waves 3 .. 7 only stage.
 template <int NC, int CC, int MAXW>
 __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ x, int xld, const bf16* __restrict__ dz, int zld, float* __restrict__ part,
                                                        int M, int H, int W, int n_chunks, int chunks_per_wg) {
@@ -41,7 +42,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
                                                                // 16-column subtiles, and with an even pitch they met on 2 of the 16 bank groups
   constexpr int ZT_BYTES = (NC / 16) * CH * 32;
   constexpr int XW_BYTES = (CC / 16) * WINP * 32;
-  constexpr int NPZ = (CH * NC / 8) / 512;                     // 16-byte units of dz per thread and chunk
+  constexpr bool D96 = NC == 96;
+  constexpr int NPZ = (CH * NC / 8 + 511) / 512;               // 16-byte units of dz per thread and chunk (96 columns: 768 units, the tail is skipped)
   constexpr int NPX = (WINP * (CC / 8) + 511) / 512;           // of the x window
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const ZT = smem;
@@ -50,7 +52,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
 
   const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
   const int j = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int nb = NC == 256 ? j : (j & 3), cb = NC == 256 ? j : (j >> 2);
+  const int nb = NC == 256 || D96 ? j : (j & 3), cb = D96 ? 0 : NC == 256 ? j : (j >> 2);
+  const bool active = !D96 || j < 3;
   const int xc0 = NC == 256 ? 0 : blockIdx.y * CC;
   const int halo = W + 1, winp = CH + 2 * halo;                // pixels actually used (<= WINP)
   const int q0 = blockIdx.x * chunks_per_wg;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int u0 = 0; u0 < NPZ; ++u0) {
       const int u = t + 512 * u0, r = u / (NC / 8), c8 = u % (NC / 8);
-      *reinterpret_cast<u32x4*>(ZT + (c8 >> 1) * (CH * 32) + r * 32 + (c8 & 1) * 16) = (okm >> u0) & 1u ? pz[u0] : u32x4{0u, 0u, 0u, 0u};
+      if (!D96 || r < CH) *reinterpret_cast<u32x4*>(ZT + (c8 >> 1) * (CH * 32) + r * 32 + (c8 & 1) * 16) = (okm >> u0) & 1u ? pz[u0] : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int u0 = 0; u0 < NPX; ++u0) {
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
     if (q + 1 < q1) gload(q + 1);
     const long m0 = (long)q * CH;
 #pragma unroll 1
-    for (int ks = 0; ks < 2; ++ks) {      // (not unrolled: with both steps' tap addresses live the grouped variant spilled 20 registers)
+    for (int ks = 0; ks < (active ? 2 : 0); ++ks) {      // (not unrolled: with both steps' tap addresses live the grouped variant spilled 20 registers)
       // dz^T fragments: rows (= K slots) ks*32 + h*16 + lq*4 + 0..3, column 16 nt + i
       u32x4 af[2];
 #pragma unroll
@@ -163,7 +166,9 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
   }
 
   // fp32 partials of this row range: [split][job][tap][n 32][c 32]; lane holds n = 16 nt + 4 lq + e, c = 16 ct + i
-  const int job = (NC == 256 ? 0 : blockIdx.y * NW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * NW;
+  constexpr int JW = D96 ? 3 : NW;                             // jobs per workgroup
+  const int job = (NC == 256 ? 0 : blockIdx.y * JW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * JW;
+  if (!active) return;
   float* out = part + ((size_t)blockIdx.x * njobs + job) * JOB;
 #pragma unroll
   for (int tp = 0; tp < 9; ++tp)
@@ -186,7 +191,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
   constexpr int ZSUB = 2 * CHX * 32, XSUB = 2 * WINP * 32;     // subtile pitches (limb rows)
   constexpr int ZT_BYTES = (NC / 16) * ZSUB;
   constexpr int XW_BYTES = (CC / 16) * XSUB;
-  constexpr int NPZ = (CHX * NC / 8) / 512;
+  constexpr bool D96 = NC == 96;
+  constexpr int NPZ = (CHX * NC / 8 + 511) / 512;
   constexpr int NPX = (WINP * (CC / 8) + 511) / 512;
   static_assert(NPZ + NPX <= 32, "validity bits");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -196,7 +202,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
 
   const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
   const int j = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int nb = NC == 256 ? j : (j & 3), cb = NC == 256 ? j : (j >> 2);
+  const int nb = NC == 256 || D96 ? j : (j & 3), cb = D96 ? 0 : NC == 256 ? j : (j >> 2);
+  const bool active = !D96 || j < 3;
   const int xc0 = NC == 256 ? 0 : blockIdx.y * CC;
   const int halo = W + 1, winp = CHX + 2 * halo;
   const int q0 = blockIdx.x * chunks_per_wg;
@@ -247,8 +254,10 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
       limbs8(pz[u0][0], pz[u0][1], lo, hi);
       const bool ok = (okm >> u0) & 1u;
       unsigned char* d = ZT + (c8 >> 1) * ZSUB + (2 * r) * 32 + (c8 & 1) * 16;
-      *reinterpret_cast<u32x4*>(d) = ok ? lo : z4;
-      *reinterpret_cast<u32x4*>(d + 32) = ok ? hi : z4;
+      if (!D96 || r < CHX) {
+        *reinterpret_cast<u32x4*>(d) = ok ? lo : z4;
+        *reinterpret_cast<u32x4*>(d + 32) = ok ? hi : z4;
+      }
     }
 #pragma unroll
     for (int u0 = 0; u0 < NPX; ++u0) {
@@ -286,7 +295,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
     if (q + 1 < q1) gload(q + 1);
     const long m0 = (long)q * CHX;
 #pragma unroll 1
-    for (int ks = 0; ks < CHX / 16; ++ks) {                      // 32 limb rows = 16 rows of dz per step (not unrolled: the tap addresses of all steps at once spill)
+    for (int ks = 0; ks < (active ? CHX / 16 : 0); ++ks) {                      // 32 limb rows = 16 rows of dz per step (not unrolled: the tap addresses of all steps at once spill)
       u32x4 af[2];
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt) {
@@ -335,7 +344,9 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
     }
   }
 
-  const int job = (NC == 256 ? 0 : blockIdx.y * NW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * NW;
+  constexpr int JW = D96 ? 3 : NW;                             // jobs per workgroup
+  const int job = (NC == 256 ? 0 : blockIdx.y * JW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * JW;
+  if (!active) return;
   float* out = part + ((size_t)blockIdx.x * njobs + job) * JOB;
 #pragma unroll
   for (int tp = 0; tp < 9; ++tp)
@@ -349,7 +360,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restric
 
 // dW[o][ig][ky][kx] (PyTorch layout, overwrite) = sum over splits, in split order.  One thread per partial element in PARTIAL order (c fastest: the
 // reads of a wave are contiguous 128-byte rows, split after split); the 4-byte scatter into the weight layout is 74 k .. 147 k stores per layer.
-// grouped: o = 32 job + n, ig = c;  dense: job = (ig / 64) * 8 + (ig % 64 / 32) * 4 + o / 32
+// grouped (1): o = 32 job + n, ig = c;  dense (0): job = (ig / 64) * 8 + (ig % 64 / 32) * 4 + o / 32;  dense 96 -> 96 (2): job = (ig / 32) * 3 + o / 32
 __global__ __launch_bounds__(256) void wgrad3x3_finalize_kernel(const float* __restrict__ part, float* __restrict__ dw, int O, int Ig, int grouped, int njobs,
                                                                 int splits) {
   // a thread owns 4 consecutive c (one 16-byte load per split slab) and keeps four slabs in flight: the one-element-per-thread loop with its
@@ -368,30 +379,30 @@ __global__ __launch_bounds__(256) void wgrad3x3_finalize_kernel(const float* __r
     }
     for (; sp < splits; ++sp) s0 += *reinterpret_cast<const f32x4*>(part + (size_t)sp * total + idx);
     const f32x4 s = (s0 + s1) + (s2 + s3);
-    const int o = grouped ? job * 32 + n : (job & 3) * 32 + n;
-    const int ig = grouped ? c : (job >> 3) * 64 + ((job >> 2) & 1) * 32 + c;
+    const int o = grouped == 2 ? (job % 3) * 32 + n : grouped ? job * 32 + n : (job & 3) * 32 + n;
+    const int ig = grouped == 2 ? (job / 3) * 32 + c : grouped ? c : (job >> 3) * 64 + ((job >> 2) & 1) * 32 + c;
 #pragma unroll
     for (int e = 0; e < 4; ++e) dw[((size_t)o * Ig + ig + e) * 9 + tp] = s[e];
   }
 }
 
 // Supported: 3x3 / stride 1 / pad 1, 16-bit storage; grouped with 32 -> 32 channels per group and 8 groups, or dense with 128 output
-// channels and 64 / 128 input channels.
+// channels and 64 / 128 input channels, or dense 96 -> 96.
 bool wgrad3x3_supported(int dtype, int O, int Ig, int groups, int W) {
   if (dtype != 1 && dtype != 2) return false;         // dtype 2: fp32 rows, two-limb arithmetic (wgrad3x3_x2_kernel)
   if (groups == 8) return O == 256 && Ig == 32 && W <= 20;
-  return groups == 1 && O == 128 && (Ig == 64 || Ig == 128) && W <= 40;
+  return groups == 1 && W <= 40 && ((O == 128 && (Ig == 64 || Ig == 128)) || (O == 96 && Ig == 96));
 }
 static int wgrad3x3_rows(int groups, int dtype) { return dtype == 2 && groups == 8 ? 32 : wg3::CH; }      // rows per stage
 static int wgrad3x3_plan(int O, int Ig, int groups, int M, int* splits, int* cpw, int* njobs, int dtype) {
   const int ch = wgrad3x3_rows(groups, dtype);
   const int n_chunks = (M + ch - 1) / ch;
-  const int gy = groups == 8 ? 1 : Ig / 64;
+  const int gy = groups == 8 ? 1 : O == 96 ? 3 : Ig / 64;   // workgroup columns
   int s = 256 / gy;                     // one workgroup per CU: fewer partials to write and sum
   if (s > n_chunks) s = n_chunks;
   *cpw = (n_chunks + s - 1) / s;
   *splits = (n_chunks + *cpw - 1) / *cpw;
-  *njobs = gy * wg3::NW;
+  *njobs = O == 96 ? 9 : gy * wg3::NW;
   return n_chunks;
 }
 size_t wgrad3x3_scratch_bytes(int O, int Ig, int groups, int M, int dtype) {
@@ -412,6 +423,12 @@ int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, 
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(kern, dim3(splits), dim3(512), lds, s, (const float*)x, xld, (const float*)dz, zld, scratch, M, H, W, n_chunks, cpw);
+  } else if (dtype == 2 && O == 96) {
+    constexpr int CHX = 64, WINP = CHX + 2 * 41 + 3, lds = (96 / 16) * 2 * CHX * 32 + (32 / 16) * 2 * WINP * 32 + 2 * WINP * 32 + 32;
+    auto kern = wgrad3x3_x2_kernel<96, 32, 40, CHX>;
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kern, dim3(splits, 3), dim3(512), lds, s, (const float*)x, xld, (const float*)dz, zld, scratch, M, H, W, n_chunks, cpw);
   } else if (dtype == 2) {
     constexpr int CHX = 64, WINP = CHX + 2 * 41 + 3, lds = (128 / 16) * 2 * CHX * 32 + (64 / 16) * 2 * WINP * 32 + 2 * WINP * 32 + 32;
     auto kern = wgrad3x3_x2_kernel<128, 64, 40, CHX>;
@@ -425,6 +442,9 @@ int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, 
       if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL((wgrad3x3_kernel<256, 256, 20>), dim3(splits), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
+  } else if (O == 96) {
+    constexpr int WINP = wg3::CH + 2 * 41 + 3, lds = (96 / 16) * wg3::CH * 32 + (32 / 16) * WINP * 32 + WINP * 32 + 32;
+    hipLaunchKernelGGL((wgrad3x3_kernel<96, 32, 40>), dim3(splits, 3), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
   } else {
     constexpr int WINP = wg3::CH + 2 * 41 + 3, lds = (128 / 16) * wg3::CH * 32 + (64 / 16) * WINP * 32 + WINP * 32 + 32;
     hipLaunchKernelGGL((wgrad3x3_kernel<128, 64, 40>), dim3(splits, Ig / 64), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
@@ -433,7 +453,7 @@ int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, 
   if (rc) return rc;
   if (defer) { defer[0] = njobs; defer[1] = splits; return 0; }
   const int total = njobs * wg3::JOB;
-  hipLaunchKernelGGL(wgrad3x3_finalize_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, s, scratch, dw, O, Ig, groups == 8 ? 1 : 0, njobs, splits);
+  hipLaunchKernelGGL(wgrad3x3_finalize_kernel, dim3((total / 4 + 255) / 256), dim3(256), 0, s, scratch, dw, O, Ig, groups == 8 ? 1 : O == 96 ? 2 : 0, njobs, splits);
   return (int)hipGetLastError();
 }
 

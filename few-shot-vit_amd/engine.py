@@ -328,6 +328,8 @@ class _Trainer:
                                                              self._ws.numel(), _stream_ptr(x.device)))
         self._keep = (x, masks)
         self.generation += 1
+        # BatchNorm running statistics were updated in place (none in a ViT's table)
+        bump_weight_generation(v for k, v in tensors.items() if k.endswith(('running_mean', 'running_var')))
         return feat
 
     def backward(self, tensors: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], dfeat: torch.Tensor, dtokens: torch.Tensor = None):
@@ -373,12 +375,6 @@ class VisformerTrainer(_Trainer):
     def n_droppath_calls(self, rate: float) -> int:
         return len(self.droppath_keep(rate))
 
-    def forward(self, tensors, x, drop_path_rate=0.0, masks=None):
-        feat = super().forward(tensors, x, drop_path_rate, masks)
-        # BatchNorm running statistics were updated in place
-        bump_weight_generation(v for k, v in tensors.items() if k.endswith(('running_mean', 'running_var')))
-        return feat
-
     def tokens(self, B: int, tokens_per_image: int) -> torch.Tensor:
         """Post-norm token map [B, T, out_dim] fp32 of the last forward (sun_meta_training/models/visformer.py:464)."""
         out = torch.empty(B, tokens_per_image, self.out_dim, dtype=torch.float32, device=self.device)
@@ -402,6 +398,30 @@ class VitTrainer(_Trainer):
         return int(self.lib.fsvit_vit_trainer_droppath_calls(self.h, float(rate)))
 
 
+class LvvitTrainer(_Trainer):
+    """Train-mode LV-ViT (lvvit.py:277-317 stem with batch-statistics BatchNorm, :134-155 blocks with the 1 / skip_lam branch scale, DropPath)."""
+    _fn = dict(create='fsvit_lvvit_trainer_create', destroy='fsvit_lvvit_trainer_destroy', workspace_bytes='fsvit_lvvit_trainer_workspace_bytes',
+               forward='fsvit_lvvit_train_forward', backward='fsvit_lvvit_train_backward')
+
+    def _make_cfg(self, cfg):
+        return LvvitEngine._make_cfg(None, cfg)
+
+    def _out_dim(self, cfg):
+        return cfg['embed_dim']
+
+    def set_freeze_bn(self, on: bool):
+        """The stem's BatchNorm layers in eval mode inside the step (utils.freeze_bn), as VisformerTrainer.set_freeze_bn."""
+        _lib.check(self.lib.fsvit_lvvit_trainer_set_freeze_bn(self.h, int(bool(on))))
+
+    def droppath_keep(self, rate: float) -> list:
+        """Keep-probability of every DropPath call with a non-zero rate, in call order: two calls per block, rates get_dpr(rate, depth, 'linear')
+        (lvvit.py:401-404)."""
+        return [1.0 - r for r in torch.linspace(0, rate, self.cfg['depth']).tolist() if r > 0 for _ in range(2)]
+
+    def n_droppath_calls(self, rate: float) -> int:
+        return int(self.lib.fsvit_lvvit_trainer_droppath_calls(self.h, float(rate)))
+
+
 class VitEngine(_EncoderEngine):
     """cfg: dict(img_size, patch_size, embed_dim, depth, num_heads[, mlp_ratio, ln_eps]) (deit.py:142-144)."""
     _fn = dict(create='fsvit_vit_create', destroy='fsvit_vit_destroy', out_dim='fsvit_vit_out_dim',
@@ -417,7 +437,7 @@ class VitEngine(_EncoderEngine):
 
 class LvvitEngine(_EncoderEngine):
     """cfg: dict(img_size, stem_channels, embed_dim, depth, num_heads[, mlp_ratio, skip_lam, ln_eps, bn_eps]) (lvvit.py:583-587);
-    eval only."""
+    the eval engine (LvvitTrainer trains)."""
     _fn = dict(create='fsvit_lvvit_create', destroy='fsvit_lvvit_destroy', out_dim='fsvit_lvvit_out_dim',
                workspace_bytes='fsvit_lvvit_workspace_bytes', forward='fsvit_lvvit_forward')
     _default_chunk = 12800      # as the other encoders; shrinks to half of the free device memory in workspace()

@@ -3,16 +3,17 @@
 
 The nn.Module tree only owns parameters and buffers under the reference's key names (`cls_token`, `pos_embed`,
 `patch_embed.{conv1,bn1,conv2,bn2,conv3,bn3,downsample.0,downsample.1,proj}.*`, `blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}.*`,
-`norm.*`; 118 entries, no qkv bias), so checkpoints saved by the reference load unchanged.  Eval runs on the HIP engine; training is not
-built (the 96-channel stem has no weight-gradient kernel yet) and raises NotImplementedError."""
+`norm.*`; 118 entries, no qkv bias), so checkpoints saved by the reference load unchanged.  Eval runs on engine.LvvitEngine, model.train() on
+engine.LvvitTrainer (fsvit_lvvit_train_forward / _backward: batch-statistics or frozen BatchNorm in the stem, DropPath, the 1 / skip_lam branch scale,
+every parameter gradient).  Neither has a CPU form: a train-mode call on host tensors raises NotImplementedError."""
 import torch
 import torch.nn as nn
 
 from ._host import EngineHost
 from .models import register
 
-_NO_TRAIN = ('fsvit: LV-ViT (lvvit_micro_80) is built for evaluation only - training, meta-tuning and distillation of this encoder '
-             'are not implemented')
+_NO_CPU_TRAIN = ('fsvit: LV-ViT (lvvit_micro_80) trains on the HIP trainer only - the training path has no CPU form, and this call has tensors on %s '
+                 '(move the model and its input to an MI355X)')
 
 
 class _Attention(nn.Module):
@@ -56,10 +57,10 @@ class _ConvBlock(nn.Module):
 
 
 class LvVit(EngineHost, nn.Module):
-    _engine_cls = 'LvvitEngine'
+    _engine_cls, _trainer_cls = 'LvvitEngine', 'LvvitTrainer'
 
     def __init__(self, img_size=80, embed_dim=384, depth=8, num_heads=6, mlp_ratio=3., stem_channels=96, skip_lam=2., ln_eps=1e-5,
-                 numerics=None, return_map=False):
+                 drop_path_rate=0., numerics=None, return_map=False):
         super().__init__()
         if img_size != 80:
             raise NotImplementedError('fsvit: LV-ViT has a fixed 5 x 5 patch grid (lvvit.py:290, num_patches = 25): img_size must be 80')
@@ -68,6 +69,7 @@ class LvVit(EngineHost, nn.Module):
         self.numerics = numerics
         self.img_size = img_size
         self.return_map = bool(return_map)
+        self.drop_path_rate = float(drop_path_rate)                          # per-block rates get_dpr(rate, depth, 'linear') (lvvit.py:401-404, :453)
         self.out_dim = self.num_features = self.embed_dim = embed_dim        # lvvit.py:432
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, 26, embed_dim))
@@ -86,24 +88,54 @@ class LvVit(EngineHost, nn.Module):
                 nn.init.constant_(m.weight, 1.0)
 
     def trainer(self):
-        raise NotImplementedError(_NO_TRAIN)
+        if self.pos_embed.device.type != 'cuda':
+            raise NotImplementedError(_NO_CPU_TRAIN % self.pos_embed.device)
+        return super().trainer()
 
-    def forward(self, x):
-        """[B,3,80,80] fp32 -> [B,embed_dim] = norm(tokens)[:, 0] (lvvit.py:529-546), eval mode on the packed engine."""
-        if self.training:
-            raise NotImplementedError(_NO_TRAIN)
+    def draw_droppath_masks(self, n_img, device):
+        """The reference's DropPath (lvvit.py drop_path): floor(keep_prob + U[0,1)) per sample, drawn per block in forward order (attention branch, then Mlp)."""
+        keep = self.trainer().droppath_keep(self.drop_path_rate)
+        if not keep:
+            return None
+        return torch.rand(len(keep), n_img, device=device).add_(torch.tensor(keep, device=device).unsqueeze(1)).floor_()
+
+    def forward(self, x, droppath_masks=None):
+        """[B,3,80,80] fp32 -> [B,embed_dim] = norm(tokens)[:, 0] (lvvit.py:529-546).  eval: packed engine; train: the HIP trainer through the autograd
+        bridge of the other encoders (`droppath_masks` overrides the random draws)."""
         if self.return_map:
             raise NotImplementedError('fsvit: LV-ViT returns the cls feature only; the (map, pooled) output of the classifier / distillation '
                                       'phase is not built (evaluate a teacher through load_encoder + meta-baseline)')
-        return self.engine().forward(x)
+        if not self.training:
+            return self.engine().forward(x)
+        if self.pos_embed.device.type != 'cuda' or not x.is_cuda:
+            raise NotImplementedError(_NO_CPU_TRAIN % (self.pos_embed.device if self.pos_embed.device.type != 'cuda' else x.device))
+        assert x.shape[-2] == self.img_size and x.shape[-1] == self.img_size, \
+            f"Input image size ({x.shape[-2]}*{x.shape[-1]}) doesn't match model ({self.img_size}*{self.img_size})."
+        bn_modes = {m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)}
+        if len(bn_modes) > 1:
+            raise NotImplementedError('fsvit: BatchNorm layers must be all in train mode or all frozen (utils.freeze_bn) inside a training step')
+        frozen = bn_modes == {False}                    # utils.freeze_bn (train_meta.py:156-157): running statistics normalise, nothing is updated
+        trainer = self.trainer()
+        trainer.set_freeze_bn(frozen)
+        from ..autograd import VisformerTrainFn
+        named = [(k, p) for k, p in self.named_parameters()]
+        names = tuple(k for k, _ in named)
+        buffers = {k: b for k, b in self.named_buffers() if not k.endswith('num_batches_tracked')}
+        masks = droppath_masks if droppath_masks is not None else self.draw_droppath_masks(x.shape[0], x.device)
+        trainer.grad_sink = getattr(self, '_grad_sink', None)       # parallel.GradBucket: gradients land in the flat all-reduce buffer
+        feat = VisformerTrainFn.apply(x, trainer, names, buffers, self.drop_path_rate, masks, *[p for _, p in named])
+        if not frozen:      # nn.BatchNorm2d counts its train-mode forwards
+            torch._foreach_add_([b for k, b in self.named_buffers() if k.endswith('num_batches_tracked')], 1)
+        return feat
 
 
 @register('lvvit_micro_80')
 def lvvit_micro_80(pretrained=False, **kwargs):
-    """lvvit.py:583-587: embed_dim 384, depth 8, 6 heads, mlp_ratio 3, skip_lam 2 (drop_path_rate / mix_token / return_dense only act in
-    training)."""
+    """lvvit.py:583-587: embed_dim 384, depth 8, 6 heads, mlp_ratio 3, skip_lam 2, drop_path_rate 0.5 (acts in training only).  mix_token /
+    return_dense are dead code in the reference (commented out): accepted and ignored."""
     if pretrained:
         raise NotImplementedError('pretrained LV-ViT weights are loaded through load_state_dict (no network here)')
-    for k in ('drop_path_rate', 'mix_token', 'return_dense'):
+    for k in ('mix_token', 'return_dense'):
         kwargs.pop(k, None)
+    kwargs.setdefault('drop_path_rate', 0.5)
     return LvVit(**kwargs)

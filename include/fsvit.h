@@ -132,7 +132,7 @@ int fsvit_vit_forward(fsvit_vit* h, const float* x_nchw_dev, int n_img, int img_
  * BatchNorm, LeakyReLU(0.1), MaxPool2d(2)), a 4x4 / stride 4 projection to embed_dim, cls token + pos_embed, pre-LN blocks
  * (qkv_bias=False, residual branches divided by skip_lam), features = norm(x)[:, 0].  Same conventions as the ViT handle;
  * state-dict keys `patch_embed.{conv1,bn1,conv2,bn2,conv3,bn3,downsample.0,downsample.1,proj}.*`, `cls_token`, `pos_embed`,
- * `blocks.N.*`, `norm.*`.  Eval only. */
+ * `blocks.N.*`, `norm.*`.  This handle is the eval engine; training runs on the fsvit_lvvit_trainer handle further down. */
 typedef struct fsvit_lvvit fsvit_lvvit;
 typedef struct fsvit_lvvit_cfg {        /* lvvit.py:583-587 */
   int img_size;                         /* 80 */
@@ -345,6 +345,23 @@ size_t fsvit_vit_trainer_workspace_bytes(fsvit_vit_trainer* t, const fsvit_param
 int fsvit_vit_train_forward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
                             float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream);
 int fsvit_vit_train_backward(fsvit_vit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream);
+
+/* ---- Train-mode LV-ViT (meta_tuning_sun_m/models/lvvit.py:277-317 ConvBlock stem, :134-155 blocks, :415-552): the third trainer on the shared step
+ * driver.  Parameters and BatchNorm running statistics under the reference's state-dict names (patch_embed.{conv1,bn1,conv2,bn2,conv3,bn3,
+ * downsample.0,downsample.1,proj}.*, cls_token, pos_embed, blocks.N.*, norm.*; no qkv bias).  BatchNorm: batch statistics with the running update, or
+ * frozen (set_freeze_bn, as fsvit_visformer_trainer_set_freeze_bn).  Every residual branch is scaled by 1 / skip_lam; the factor lives in the per-image
+ * DropPath scales, never in the parameters.  DropPath: 2 calls per block whose rate linspace(0, drop_path_rate, depth)[i] is non-zero (get_dpr 'linear'),
+ * masks_dev [calls][n_img] of 0 / 1 in forward order (fsvit_lvvit_trainer_droppath_calls).  img_size must be 80 (5 x 5 patch grid).
+ * dtype FSVIT_F32 | FSVIT_BF16 | FSVIT_BF16X2. */
+typedef struct fsvit_lvvit_trainer fsvit_lvvit_trainer;
+int fsvit_lvvit_trainer_create(const fsvit_lvvit_cfg* cfg, int dtype, fsvit_lvvit_trainer** out);
+void fsvit_lvvit_trainer_destroy(fsvit_lvvit_trainer* t);
+int fsvit_lvvit_trainer_droppath_calls(const fsvit_lvvit_trainer* t, float drop_path_rate);
+size_t fsvit_lvvit_trainer_workspace_bytes(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, int n_img, float drop_path_rate);
+int fsvit_lvvit_trainer_set_freeze_bn(fsvit_lvvit_trainer* t, int on);
+int fsvit_lvvit_train_forward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
+                              float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int fsvit_lvvit_train_backward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream);
 
 /* Backward of fsvit_proto_head, method 'cos' (meta_baseline.py:33-47): dlogits [E,Q,way] -> dfeat_shot [E,way,shot,D],
  * dfeat_query [E,Q,D], dtemp_per_episode [E] (sum it for the learnable temperature, meta_baseline.py:20-21). */

@@ -1,7 +1,11 @@
 """LV-ViT (`lvvit_micro_80`) eval throughput on one MI355X: 5-way 5-shot episodes (15 queries per class), EPISODES per launch
 (128 x 100 = 12 800 images) through meta-baseline's one C-ABI call, procedural weights, bf16 by default.  Prints episodes/s, ms per launch,
 the per-layer profile (fsvit_encoder_profile_begin / _end: HIP events around every launch of one profiled step) and the fraction of the
-dense MFMA peak.  Usage: python tools/bench_lvvit.py [--numerics bf16] [--steps 10] [--warmup 3] [--episodes 128]"""
+dense MFMA peak.  Usage: python tools/bench_lvvit.py [--numerics bf16] [--steps 10] [--warmup 3] [--episodes 128]
+
+--mode train: one meta-tuning step (forward, cross-entropy, backward) of EPISODES 5-way 1-shot 3-query episodes (default 40 = 800 images) on the
+HIP trainer, timed with HIP events.  Both weight-gradient routes of the dense 96 -> 96 stem layers are built in the same process (--routes: the
+direct kernel under FSVIT_LVVIT_WGRAD=direct, the transposed split-K GEMM under =gemm) and their steps ALTERNATE; medians per route are printed."""
 import argparse
 import json
 import os
@@ -17,13 +21,65 @@ MFMA_PEAK_TFLOPS = {'bf16': 2500.0, 'f16': 2500.0, 'parity': 157.3, 'bf16x2': 62
 GFLOP_PER_IMAGE = 1.199          # torch.utils.flop_counter on the reference model (stem 0.548, blocks 0.622, projection 0.030)
 
 
+def train_step(args):
+    import statistics
+    import torch.nn.functional as F
+    from fewshot_vit_amd.utils import few_shot as fs
+    dev = torch.device('cuda', 0)
+    way, shot, query, E = 5, 1, 3, args.episodes or 40
+    g = torch.Generator(device=dev).manual_seed(0)
+    xs = torch.randn(E, way, shot, 3, 80, 80, device=dev, generator=g)
+    xq = torch.randn(E, way * query, 3, 80, 80, device=dev, generator=g)
+    label = fs.make_nk_label(way, query, E).to(dev)
+    routes = {}
+    for route in args.routes.split(','):                    # the switch is read when the trainer handle is created (first train-mode forward)
+        os.environ['FSVIT_LVVIT_WGRAD'] = route
+        m = models.make('meta-baseline', encoder='lvvit_micro_80', encoder_args={'numerics': args.numerics})
+        m.load_state_dict(synthetic.synthetic_checkpoint_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}, calib='lvvit_micro_80'))
+        m = m.to(dev).train()
+        F.cross_entropy(m(xs, xq).view(-1, way), label).backward()
+        routes[route] = m
+    os.environ.pop('FSVIT_LVVIT_WGRAD', None)
+
+    def step(m):
+        m.zero_grad(set_to_none=True)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        loss = F.cross_entropy(m(xs, xq).view(-1, way), label)
+        loss.backward()
+        t1.record()
+        t1.synchronize()
+        assert torch.isfinite(loss)
+        return t0.elapsed_time(t1)
+
+    ms = {r: [] for r in routes}
+    for i in range(args.warmup + args.steps):
+        for r, m in routes.items():                        # A B A B ...
+            t = step(m)
+            if i >= args.warmup:
+                ms[r].append(t)
+    n_img = E * way * (shot + query)
+    for r in routes:
+        print(f'{r:7s} samples (ms): ' + ' '.join(f'{v:.2f}' for v in ms[r]))
+    med = {r: statistics.median(v) for r, v in ms.items()}
+    print(json.dumps({'metric': 'lvvit_micro_80_meta_tuning_step_ms', 'numerics': args.numerics, 'images': n_img, 'unit': 'ms',
+                      **{f'wgrad96_{r}_route_ms': round(v, 3) for r, v in med.items()}, 'samples_per_route': args.steps, 'alternated': True,
+                      'device': torch.cuda.get_device_name(dev)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--numerics', default='bf16')
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--episodes', type=int, default=128)
+    ap.add_argument('--episodes', type=int, default=None)
+    ap.add_argument('--mode', choices=['eval', 'train'], default='eval')
+    ap.add_argument('--routes', default='direct,gemm', help='--mode train: the weight-gradient routes to build and alternate (one name for a kernel trace)')
     args = ap.parse_args()
+    if args.mode == 'train':
+        return train_step(args)
+    if args.episodes is None:
+        args.episodes = 128
     dev = torch.device('cuda', 0)
     way, shot, query, E = 5, 5, 15, args.episodes
     m = models.make('meta-baseline', encoder='lvvit_micro_80', encoder_args={'numerics': args.numerics})
