@@ -154,19 +154,39 @@ struct RrcParams {
   const int64_t* index;        // [B]
   const int32_t* box;          // [B][4] top, left, height, width
   const uint8_t* flip;         // [B]
-  float* out;                  // [B][3][OH][OW]
+  void* out;                   // float [B][3][OH][OW] normalised, or (U8 epilogue) uint8 [B][OH][OW][3]
   int H, W, OH, OW, kh, kv;    // kh / kv: table row stride = tap count of the largest box (w = W, h = H)
   float mean[3], stdv[3];
 };
 
-__host__ __device__ inline int rrc_ksize(int in, int out) { const int c = (in + out - 1) / out; return 2 * (c < 1 ? 1 : c) + 1; }
+enum { RRC_BILINEAR = 0, RRC_BICUBIC = 1 };
 
-// One row of pil_bilinear_tables(in, out): first input index, tap count, 22-bit taps.  Every double operation is one IEEE operation, in Python's order.
+// ceil(support * max(in / out, 1)) * 2 + 1 with support 1 (bilinear) or 2 (bicubic)
+__host__ __device__ inline int rrc_ksize(int in, int out, int filter = RRC_BILINEAR) {
+  const int c = filter == RRC_BICUBIC ? (2 * in + out - 1) / out : (in + out - 1) / out, cmin = filter == RRC_BICUBIC ? 2 : 1;
+  return 2 * (c < cmin ? cmin : c) + 1;
+}
+
+// Resample.c bilinear_filter / bicubic_filter (a = -0.5), each double operation one IEEE operation in C's order
+template <int FILTER>
+__device__ __forceinline__ double rrc_filter(double x) {
+#pragma clang fp contract(off)
+  x = fabs(x);
+  if (FILTER == RRC_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
+  if (x < 1.0) return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1.0;
+  if (x < 2.0) return (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5;
+  return 0.0;
+}
+
+// One row of pil_resample_tables(in, out, filter): first input index, tap count, 22-bit taps.  Every double operation is one IEEE operation, in Python's
+// order.
+template <int FILTER>
 __device__ void rrc_table_row(int in, int out, int o, int stride, int32_t* xmin, int32_t* cnt, int32_t* coef) {
 #pragma clang fp contract(off)
   const double scale = (double)in / (double)out;
-  const double support = scale > 1.0 ? scale : 1.0;
-  const double inv = 1.0 / support;
+  const double fscale = scale > 1.0 ? scale : 1.0;
+  const double support = FILTER == RRC_BICUBIC ? 2.0 * fscale : fscale;
+  const double inv = 1.0 / fscale;
   const double center = ((double)o + 0.5) * scale;
   int lo = (int)(center - support + 0.5), hi = (int)(center + support + 0.5);
   lo = lo < 0 ? 0 : lo;
@@ -175,12 +195,10 @@ __device__ void rrc_table_row(int in, int out, int o, int stride, int32_t* xmin,
   n = n < 0 ? 0 : (n > stride ? stride : n);             // never taken for Pillow's tables (hi - lo <= ksize); keeps the row inside its LDS slot
   double total = 0.0;
   for (int x = lo; x < lo + n; ++x) {
-    const double a = fabs(((double)x - center + 0.5) * inv);
-    total += a < 1.0 ? 1.0 - a : 0.0;
+    total += rrc_filter<FILTER>(((double)x - center + 0.5) * inv);
   }
   for (int j = 0; j < n; ++j) {
-    const double a = fabs(((double)(lo + j) - center + 0.5) * inv);
-    double w = a < 1.0 ? 1.0 - a : 0.0;
+    double w = rrc_filter<FILTER>(((double)(lo + j) - center + 0.5) * inv);
     if (total != 0.0) w = w / total;
     const double v = w * (double)(1 << 22);
     coef[(size_t)o * stride + j] = w < 0.0 ? (int)(v - 0.5) : (int)(v + 0.5);
@@ -189,6 +207,8 @@ __device__ void rrc_table_row(int in, int out, int o, int stride, int32_t* xmin,
   cnt[o] = n;
 }
 
+// FILTER picks the tap tables; U8OUT the epilogue: the resized (and mirrored) bytes as [OH][OW][3] for the colour stage instead of the normalised planes.
+template <int FILTER, bool U8OUT>
 __global__ __launch_bounds__(256) void transform_rrc_gather_kernel(RrcParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PB = 22;
@@ -226,14 +246,15 @@ __global__ __launch_bounds__(256) void transform_rrc_gather_kernel(RrcParams p) 
     if (t < head) raw[t] = src[t];
     if (tail0 + t < nbytes) raw[tail0 + t] = src[tail0 + t];           // < 16 bytes
   }
-  for (int i = t; i < 768; i += 256) {
-    const int c = i >> 8;
-    const float v = (float)(i & 255) / 255.0f;                        // ToTensor
-    lut[i] = (v - p.mean[c]) / p.stdv[c];                              // Normalize (IEEE division, as torch does)
-  }
+  if constexpr (!U8OUT)
+    for (int i = t; i < 768; i += 256) {
+      const int c = i >> 8;
+      const float v = (float)(i & 255) / 255.0f;                      // ToTensor
+      lut[i] = (v - p.mean[c]) / p.stdv[c];                            // Normalize (IEEE division, as torch does)
+    }
   for (int o = t; o < p.OW + p.OH; o += 256) {
-    if (o < p.OW) rrc_table_row(bw, p.OW, o, p.kh, xmin_h, cnt_h, coef_h);
-    else rrc_table_row(bh, p.OH, o - p.OW, p.kv, xmin_v, cnt_v, coef_v);
+    if (o < p.OW) rrc_table_row<FILTER>(bw, p.OW, o, p.kh, xmin_h, cnt_h, coef_h);
+    else rrc_table_row<FILTER>(bh, p.OH, o - p.OW, p.kv, xmin_v, cnt_v, coef_v);
   }
   __syncthreads();
   // horizontal pass over the box's rows: thread = (output column x, channel c)
@@ -265,33 +286,42 @@ __global__ __launch_bounds__(256) void transform_rrc_gather_kernel(RrcParams p) 
   __syncthreads();
   // vertical pass + flip + ToTensor + Normalize, NCHW fp32: thread = (channel c, output column x), x fastest (coalesced stores); a flipped image reads
   // the mirrored column of the resized image (the flip follows the resize in the reference's transform order)
-  float* out = p.out + (size_t)b * 3 * p.OH * p.OW;
+  // U8OUT: thread = (output column x, channel c) with c fastest, as the bytes lie in [OH][OW][3]
   for (int pc = t; pc < 3 * p.OW; pc += 256) {
-    const int c = pc / p.OW, x = pc - c * p.OW;
+    const int c = U8OUT ? pc % 3 : pc / p.OW, x = U8OUT ? pc / 3 : pc - c * p.OW;
     const unsigned char* hb = hp + (flip ? p.OW - 1 - x : x) * 3 + c;
-    const float* lc = lut + 256 * c;
-    float* oc = out + (size_t)c * p.OH * p.OW + x;
+    [[maybe_unused]] const float* lc = nullptr;
+    [[maybe_unused]] float* oc = nullptr;
+    [[maybe_unused]] unsigned char* out8 = nullptr;
+    if constexpr (U8OUT) {
+      out8 = static_cast<unsigned char*>(p.out) + (size_t)b * 3 * p.OH * p.OW + pc;
+    } else {
+      lc = lut + 256 * c;
+      oc = static_cast<float*>(p.out) + (size_t)b * 3 * p.OH * p.OW + (size_t)c * p.OH * p.OW + x;
+    }
     for (int y = 0; y < p.OH; ++y) {
       const int n = cnt_v[y];
       const int32_t* k = coef_v + (size_t)y * p.kv;
       const unsigned char* hr = hb + xmin_v[y] * hrow;
       int acc = 1 << (PB - 1);
       for (int j = 0; j < n; ++j) acc += (int)hr[j * hrow] * k[j];
-      oc[(size_t)y * p.OW] = lc[clip8(acc >> PB)];
+      if constexpr (U8OUT) out8[(size_t)y * hrow] = (unsigned char)clip8(acc >> PB);
+      else oc[(size_t)y * p.OW] = lc[clip8(acc >> PB)];
     }
   }
 }
 
-int launch_transform_rrc_gather(const RrcParams& p, int B, hipStream_t s) {
+template <int FILTER, bool U8OUT>
+int launch_transform_rrc(const RrcParams& p, int B, hipStream_t s) {
   if (B <= 0) return 0;
   const size_t lds = (((size_t)p.H * p.W * 3 + 15) & ~(size_t)15) + 16 + (((size_t)p.H * p.OW * 3 + 15) & ~(size_t)15) + 768 * sizeof(float) +
                      ((size_t)p.OW * (2 + p.kh) + (size_t)p.OH * (2 + p.kv)) * sizeof(int32_t);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)transform_rrc_gather_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void*)transform_rrc_gather_kernel<FILTER, U8OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(transform_rrc_gather_kernel, dim3(B), dim3(256), lds, s, p);
+  hipLaunchKernelGGL((transform_rrc_gather_kernel<FILTER, U8OUT>), dim3(B), dim3(256), lds, s, p);
   return (int)hipGetLastError();
 }
 
@@ -309,7 +339,26 @@ extern "C" int fsvit_image_transform_rrc_gather(const uint8_t* images_dev, int H
   p.H = H; p.W = W; p.OH = OH; p.OW = OW;
   p.kh = fsvit::rrc_ksize(W, OW); p.kv = fsvit::rrc_ksize(H, OH);
   for (int c = 0; c < 3; ++c) { p.mean[c] = mean3_host[c]; p.stdv[c] = std3_host[c]; }
-  int rc = fsvit::launch_transform_rrc_gather(p, B, (hipStream_t)stream);
+  int rc = fsvit::launch_transform_rrc<fsvit::RRC_BILINEAR, false>(p, B, (hipStream_t)stream);
   if (rc) return fsvit_set_error(rc, "%s", "fsvit_image_transform_rrc_gather: launch failed (image too large for LDS?)");
+  return 0;
+}
+
+// The weak view of the distillation phase (sun_meta_training/datasets/mini_imagenet.py:100-102): the same crop + resize + flip with Pillow's BICUBIC
+// (or BILINEAR) taps, left as uint8 [B][OH][OW][3] for fsvit_image_strong_weak (augment.hip).  The negative bicubic taps overshoot: clip8 is live here.
+extern "C" int fsvit_image_transform_rrc_u8(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
+                                            const uint8_t* flip_dev, int OH, int OW, int filter, uint8_t* out_dev, void* stream) {
+  if (!images_dev || !index_dev || !box_dev || !flip_dev || !out_dev) return fsvit_set_error(-1, "%s", "fsvit_image_transform_rrc_u8: null argument");
+  if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || B < 0) return fsvit_set_error(-1, "%s", "fsvit_image_transform_rrc_u8: bad geometry");
+  if (filter != fsvit::RRC_BILINEAR && filter != fsvit::RRC_BICUBIC)
+    return fsvit_set_error(-1, "%s", "fsvit_image_transform_rrc_u8: filter must be 0 (bilinear) or 1 (bicubic)");
+  fsvit::RrcParams p;
+  p.images = images_dev; p.index = index_dev; p.box = box_dev; p.flip = flip_dev; p.out = out_dev;
+  p.H = H; p.W = W; p.OH = OH; p.OW = OW;
+  p.kh = fsvit::rrc_ksize(W, OW, filter); p.kv = fsvit::rrc_ksize(H, OH, filter);
+  for (int c = 0; c < 3; ++c) { p.mean[c] = 0.0f; p.stdv[c] = 1.0f; }
+  int rc = filter == fsvit::RRC_BICUBIC ? fsvit::launch_transform_rrc<fsvit::RRC_BICUBIC, true>(p, B, (hipStream_t)stream)
+                                        : fsvit::launch_transform_rrc<fsvit::RRC_BILINEAR, true>(p, B, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "%s", "fsvit_image_transform_rrc_u8: launch failed (image too large for LDS?)");
   return 0;
 }

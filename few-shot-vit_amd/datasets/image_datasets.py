@@ -5,7 +5,11 @@ transformed on the GPU by index (`gather`, fsvit_image_transform_gather) instead
 `self.transform` is what `gather` / `__getitem__` apply.  `augment=None` is the eval transform.  `augment='resize'` is the supervised phase's
 train-time augmentation (sun_train_teacher/datasets/mini_imagenet.py:50-63, tiered_imagenet.py:68-81): RandomResizedCrop(80) +
 RandomHorizontalFlip on the GPU (fsvit_image_transform_rrc_gather), with `default_transform` = that phase's Resize(80) + ToTensor +
-Normalize; `ds.transform = ds.default_transform` switches the augmentation off.  `'crop'` (padded RandomCrop) and `'cropaug'` (timm) are not built."""
+Normalize; `ds.transform = ds.default_transform` switches the augmentation off.  `augment='strongweak'` (our name: the reference keys it on
+`split == 'train'`, sun_meta_training/datasets/mini_imagenet.py:160-163, :194-204) is the distillation phase's view pair on the GPU
+(transforms.DeviceStrongWeakPair: fsvit_image_transform_rrc_u8 + fsvit_image_strong_weak): `gather_pair(index)` -> (strong, weak),
+`__getitem__` -> (strong, weak, label), `strong_prob` (default 0.5) as in the reference's constructor; the weak view's RandomApply([RandAugment], p = 0.2) is not restated.  `'crop'` (padded RandomCrop) and
+`'cropaug'` (timm) are not built."""
 import os
 import pickle
 
@@ -13,13 +17,13 @@ import numpy as np
 import torch
 
 from .datasets import register
-from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandomResizedCrop, DeviceTransform
+from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandomResizedCrop, DeviceStrongWeakPair, DeviceTransform
 
 
 class _DeviceImageDataset:
     resize, crop = (88, 88), 80
 
-    def _finish(self, data: np.ndarray, label, device, augment=None):
+    def _finish(self, data: np.ndarray, label, device, augment=None, strong_prob=0.5):
         if data.dtype != np.uint8 or data.ndim != 4 or data.shape[-1] != 3:
             raise ValueError('expected uint8 images [N,H,W,3]')
         min_label = min(label)
@@ -32,6 +36,9 @@ class _DeviceImageDataset:
         if augment == 'resize':
             self.default_transform = DeviceTransform(in_hw, (self.crop, self.crop), self.crop, self.device, **norm)     # Resize(80)
             self.transform = DeviceRandomResizedCrop(in_hw, self.crop, self.device, **norm)
+        elif augment == 'strongweak':
+            self.default_transform = DeviceTransform(in_hw, (self.crop, self.crop), self.crop, self.device, **norm)     # Resize(80)
+            self.transform = DeviceStrongWeakPair(in_hw, self.crop, self.device, strong_prob=strong_prob, **norm)
         else:
             self.default_transform = self.transform = DeviceTransform(in_hw, self.resize, self.crop, self.device, **norm)
 
@@ -47,10 +54,25 @@ class _DeviceImageDataset:
 
     def gather(self, index) -> torch.Tensor:
         """index: LongTensor of dataset indices (one sampler batch) -> float32 [len, 3, 80, 80] on the GPU."""
-        imgs = self.device_images()
-        return self.transform(imgs, torch.as_tensor(index))
+        out = self.transform(self.device_images(), torch.as_tensor(index))
+        return out[0] if isinstance(out, tuple) else out   # under 'strongweak': the strong view
+
+    @property
+    def gather_pair(self):
+        """`gather_pair(index)` -> (strong, weak), float32 [len, 3, 80, 80] each on the GPU: one launch pair for the batch.  The attribute exists
+        exactly while `self.transform` is the view-pair transform (`hasattr` is how the distillation driver asks), so it follows a replaced
+        `ds.transform` both ways."""
+        if not isinstance(self.transform, DeviceStrongWeakPair):
+            raise AttributeError("gather_pair: dataset.transform is not the 'strongweak' view pair")
+        return self._gather_pair
+
+    def _gather_pair(self, index):
+        return self.transform(self.device_images(), torch.as_tensor(index))
 
     def __getitem__(self, i):
+        if isinstance(self.transform, DeviceStrongWeakPair):
+            strong, weak = self._gather_pair(torch.tensor([int(i)]))
+            return strong[0], weak[0], self.label[i]
         return self.gather(torch.tensor([int(i)]))[0], self.label[i]
 
 
@@ -58,22 +80,22 @@ class _DeviceImageDataset:
 class MiniImageNet(_DeviceImageDataset):
     resize, crop = (88, 88), 80                         # Resize((88, 88)) -> CenterCrop(80), mini_imagenet.py:49-52
 
-    def __init__(self, root_path, split='train', augment=None, device=None, **kwargs):
-        if augment not in (None, 'resize'):
-            raise NotImplementedError("fsvit: augment=None and 'resize' are built ('crop' / 'cropaug' are not)")
+    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, **kwargs):
+        if augment not in (None, 'resize', 'strongweak'):
+            raise NotImplementedError("fsvit: augment=None, 'resize' and 'strongweak' are built ('crop' / 'cropaug' are not)")
         split_tag = 'train_phase_train' if split == 'train' else split
         with open(os.path.join(root_path, 'miniImageNet_category_split_{}.pickle'.format(split_tag)), 'rb') as f:
             pack = pickle.load(f, encoding='latin1')
-        self._finish(np.asarray(pack['data']), pack['labels'], device, augment)
+        self._finish(np.asarray(pack['data']), pack['labels'], device, augment, strong_prob)
 
 
 @register('tiered-imagenet')
 class TieredImageNet(_DeviceImageDataset):
     resize, crop = (80, 80), 80                         # Resize(80) on square images, tiered_imagenet.py:53-57
 
-    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, **kwargs):
-        if augment not in (None, 'test', 'resize'):                     # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
-            raise NotImplementedError("fsvit: augment=None, 'test' and 'resize' are built ('crop' / 'cropaug' are not)")
+    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, strong_prob=0.5, **kwargs):
+        if augment not in (None, 'test', 'resize', 'strongweak'):       # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
+            raise NotImplementedError("fsvit: augment=None, 'test', 'resize' and 'strongweak' are built ('crop' / 'cropaug' are not)")
         data = np.load(os.path.join(root_path, '{}_images.npz'.format(split)), allow_pickle=True)['images']
         data = data[:, :, :, ::-1]                      # BGR -> RGB, tiered_imagenet.py:21
         with open(os.path.join(root_path, '{}_labels.pkl'.format(split)), 'rb') as f:
@@ -93,4 +115,4 @@ class TieredImageNet(_DeviceImageDataset):
                     label_.append(ind[y])
                     cnt[y] += 1
             data, label = data[keep], label_
-        self._finish(np.ascontiguousarray(data), label, device, augment)
+        self._finish(np.ascontiguousarray(data), label, device, augment, strong_prob)

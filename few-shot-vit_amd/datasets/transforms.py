@@ -17,11 +17,31 @@ IMAGENET_MEAN = (0.485, 0.456, 0.406)        # mini_imagenet.py:43-44
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 
-def pil_bilinear_tables(in_size: int, out_size: int):
-    """-> xmin [out] int32, count [out] int32, coef [out, ksize] int32 (zero padded)."""
+def _bilinear_filter(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _bicubic_filter(x):
+    """Resample.c bicubic_filter, a = -0.5, with its association."""
+    x = abs(x)
+    if x < 1.0:
+        return ((-0.5 + 2.0) * x - (-0.5 + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * -0.5
+    return 0.0
+
+
+FILTERS = {'bilinear': (0, _bilinear_filter, 1.0), 'bicubic': (1, _bicubic_filter, 2.0)}       # name -> (kernel code, filter, support)
+
+
+def pil_resample_tables(in_size: int, out_size: int, filter: str = 'bilinear'):
+    """-> xmin [out] int32, count [out] int32, coef [out, ksize] int32 (zero padded): `precompute_coeffs` + `normalize_coeffs_8bpc` for
+    Pillow's BILINEAR (support 1) or BICUBIC (a = -0.5, support 2: negative taps, rounded with int(v - 0.5))."""
+    _, filt, fsupport = FILTERS[filter]
     scale = float(in_size) / float(out_size)
     filterscale = max(scale, 1.0)
-    support = filterscale                                    # bilinear support 1.0 * filterscale
+    support = fsupport * filterscale
     ksize = int(np.ceil(support)) * 2 + 1
     inv = 1.0 / filterscale
     xmin = np.zeros(out_size, np.int32)
@@ -34,8 +54,7 @@ def pil_bilinear_tables(in_size: int, out_size: int):
         taps = []
         total = 0.0
         for x in range(lo, hi):
-            a = abs((x - center + 0.5) * inv)               # same association as Resample.c: (x + xmin - center + 0.5) * ss
-            w = 1.0 - a if a < 1.0 else 0.0
+            w = filt((x - center + 0.5) * inv)              # same association as Resample.c: (x + xmin - center + 0.5) * ss
             taps.append(w)
             total += w
         for j, w in enumerate(taps):
@@ -45,6 +64,11 @@ def pil_bilinear_tables(in_size: int, out_size: int):
             coef[o, j] = int(v - 0.5) if w < 0 else int(v + 0.5)
         xmin[o], cnt[o] = lo, hi - lo
     return xmin, cnt, coef
+
+
+def pil_bilinear_tables(in_size: int, out_size: int):
+    """-> xmin [out] int32, count [out] int32, coef [out, ksize] int32 (zero padded)."""
+    return pil_resample_tables(in_size, out_size, 'bilinear')
 
 
 class DeviceTransform:
@@ -123,6 +147,18 @@ def random_resized_crop_boxes(n, H, W, generator, scale=(0.08, 1.0), ratio=(3. /
     return boxes.to(torch.int32).contiguous()
 
 
+def _checked_boxes(n, boxes, flips, H, W):
+    """Host validation of n crop boxes (top, left, height, width) and flips against an H x W image -> (int32 [n, 4], uint8 [n])."""
+    boxes, flips = torch.as_tensor(boxes).cpu(), torch.as_tensor(flips).cpu()
+    if boxes.dim() != 2 or tuple(boxes.shape) != (n, 4) or flips.dim() != 1 or flips.numel() != n:
+        raise ValueError(f'boxes must be [{n}, 4] and flips [{n}], got {tuple(boxes.shape)} and {tuple(flips.shape)}')
+    boxes = boxes.to(torch.int64)
+    i, j, h, w = boxes.unbind(1)
+    if n and bool(((h <= 0) | (w <= 0) | (i < 0) | (j < 0) | (i + h > H) | (j + w > W)).any()):
+        raise ValueError(f'crop box outside the {H} x {W} image or empty (rows are top, left, height, width)')
+    return boxes.to(torch.int32).contiguous(), (flips != 0).to(torch.uint8).contiguous()
+
+
 class DeviceRandomResizedCrop:
     """RandomResizedCrop(out) -> RandomHorizontalFlip -> ToTensor -> Normalize over uint8 images [N,H,W,3] resident on the GPU (the reference's
     `augment: resize`).  Boxes and flips are drawn on the host from this object's generator, or passed in; `boxes` / `flips` keep the last call's."""
@@ -142,14 +178,7 @@ class DeviceRandomResizedCrop:
         return self
 
     def _checked(self, n, boxes, flips):
-        boxes, flips = torch.as_tensor(boxes).cpu(), torch.as_tensor(flips).cpu()
-        if boxes.dim() != 2 or tuple(boxes.shape) != (n, 4) or flips.dim() != 1 or flips.numel() != n:
-            raise ValueError(f'boxes must be [{n}, 4] and flips [{n}], got {tuple(boxes.shape)} and {tuple(flips.shape)}')
-        boxes = boxes.to(torch.int64)
-        i, j, h, w = boxes.unbind(1)
-        if n and bool(((h <= 0) | (w <= 0) | (i < 0) | (j < 0) | (i + h > self.H) | (j + w > self.W)).any()):
-            raise ValueError(f'crop box outside the {self.H} x {self.W} image or empty (rows are top, left, height, width)')
-        return boxes.to(torch.int32).contiguous(), (flips != 0).to(torch.uint8).contiguous()
+        return _checked_boxes(n, boxes, flips, self.H, self.W)
 
     def __call__(self, images: torch.Tensor, index: torch.Tensor, boxes=None, flips=None) -> torch.Tensor:
         from .. import _lib
@@ -176,3 +205,194 @@ class DeviceRandomResizedCrop:
                 _ptr(images), self.H, self.W, _ptr(index), B, _ptr(boxes_dev), _ptr(flips_dev), self.out, self.out,
                 self.mean, self.std, _ptr(out), _stream_ptr(images.device)))
         return out
+
+
+# ---------------------------------------------------------------- the distillation phase's strong / weak view pair
+# (sun_meta_training/datasets/mini_imagenet.py:91-124, :194-204).  One int32 row per image tells the kernel behind fsvit_image_strong_weak what to do;
+# the three factors are float32 bit patterns.
+SW_STRONG, SW_ORDER, SW_FACTOR, SW_BLUR, SW_R, SW_WW, SW_FW, SW_SOLARIZE, SW_GRAY, SW_ERASE, SW_COLS = 0, 1, 4, 7, 8, 9, 10, 11, 12, 13, 17
+OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION = 0, 1, 2                  # values of the SW_ORDER columns; SW_FACTOR + op is that operation's factor
+_PERMS = torch.tensor([[0, 1, 2], [0, 2, 1], [1, 0, 2], [1, 2, 0], [2, 0, 1], [2, 1, 0]], dtype=torch.int32)
+
+
+def gaussian_blur_box(radius):
+    """Pillow's ImageFilter.GaussianBlur(radius) = three box blurs per axis (BoxBlur.c): -> (r, ww, fw) int64 arrays, the integer box radius and the
+    24-bit weights of the inner taps and of the two far taps, in the precisions of `_gaussian_blur_radius` and `ImagingLineBoxBlur8`."""
+    f32 = np.float32
+    rho = np.asarray(radius, np.float64).astype(f32)
+    sigma2 = (rho * rho) / f32(3)
+    L = np.sqrt(12.0 * sigma2.astype(np.float64) + 1.0).astype(f32)
+    l = np.floor((L.astype(np.float64) - 1.0) / 2.0).astype(f32)
+    a = (f32(2) * l + f32(1)) * (l * (l + f32(1)) - f32(3) * sigma2)
+    a = a / (f32(6) * (sigma2 - (l + f32(1)) * (l + f32(1))))
+    fr = l + a
+    r = fr.astype(np.int64)
+    ww = (f32(1 << 24) / (fr * f32(2) + f32(1))).astype(np.int64)
+    fw = ((1 << 24) - (2 * r + 1) * ww) // 2
+    return r, ww, fw
+
+
+def random_erase_boxes(n, H, W, generator, prob=0.25, area=(0.02, 1. / 3.), min_aspect=0.3):
+    """timm's RandomErasing box (count 1), vectorised over n -> int32 [n, 4] (top, left, h, w), h = 0 where nothing is erased: with probability
+    `prob`, up to 10 attempts of area = H*W*U(area), ratio = exp(U(log min_aspect, log 1/min_aspect)), h = round(sqrt(area*ratio)),
+    w = round(sqrt(area/ratio)); the first with w < W and h < H is taken, top and left uniform integers in [0, H-h] and [0, W-w].  The distribution,
+    not timm's stream (see random_resized_crop_boxes)."""
+    u = torch.rand(10, n, 2, generator=generator).double()
+    v = torch.rand(n, 3, generator=generator).double()                        # (apply, top, left)
+    target = H * W * (area[0] + (area[1] - area[0]) * u[..., 0])
+    lo, hi = math.log(min_aspect), math.log(1.0 / min_aspect)
+    ratio = torch.exp(lo + (hi - lo) * u[..., 1])
+    h = torch.round(torch.sqrt(target * ratio)).to(torch.int64)
+    w = torch.round(torch.sqrt(target / ratio)).to(torch.int64)
+    ok = (w < W) & (h < H) & (w > 0) & (h > 0)
+    first = ok.to(torch.int8).argmax(0, keepdim=True)
+    use = ok.any(0) & (v[:, 0] <= prob)
+    h, w = h.gather(0, first)[0], w.gather(0, first)[0]
+    top = torch.minimum((v[:, 1] * (H - h + 1)).floor().to(torch.int64), (H - h).clamp(min=0))
+    left = torch.minimum((v[:, 2] * (W - w + 1)).floor().to(torch.int64), (W - w).clamp(min=0))
+    box = torch.stack([top, left, h, w], 1)
+    return torch.where(use[:, None], box, torch.zeros_like(box)).to(torch.int32).contiguous()
+
+
+def strong_weak_table(n, generator, strong_prob=0.5, size=80):
+    """The per-image parameter rows [n, SW_COLS] int32 of the strong view: strong flag (probability strong_prob), ColorJitter(0.4, 0.4, 0.4) - the
+    order of brightness / contrast / saturation uniform over the 6 permutations, each factor U(0.6, 1.4) as float32 bits -, GaussianBlur(p = 0.5,
+    radius U(0.1, 2)) as (flag, r, ww, fw), Solarization(0.5), RandomGrayscale(0.2), and the RandomErasing(0.25) box.  Every column is drawn for every
+    image; the kernel ignores the colour columns of an image whose strong flag is 0 (the reference does not draw them then), never the erase box."""
+    u = torch.rand(n, 8, generator=generator).double()
+    perm = _PERMS[torch.randint(0, 6, (n,), generator=generator)]
+    tab = torch.zeros(n, SW_COLS, dtype=torch.int32)
+    tab[:, SW_STRONG] = (u[:, 0] <= strong_prob).to(torch.int32)
+    tab[:, SW_ORDER:SW_ORDER + 3] = perm
+    tab[:, SW_FACTOR:SW_FACTOR + 3] = (0.6 + 0.8 * u[:, 1:4]).to(torch.float32).view(torch.int32)
+    tab[:, SW_BLUR] = (u[:, 4] <= 0.5).to(torch.int32)
+    r, ww, fw = gaussian_blur_box((0.1 + 1.9 * u[:, 5]).numpy())
+    tab[:, SW_R], tab[:, SW_WW], tab[:, SW_FW] = (torch.from_numpy(np.ascontiguousarray(a)).to(torch.int32) for a in (r, ww, fw))
+    tab[:, SW_SOLARIZE] = (u[:, 6] < 0.5).to(torch.int32)
+    tab[:, SW_GRAY] = (u[:, 7] < 0.2).to(torch.int32)
+    tab[:, SW_ERASE:SW_ERASE + 4] = random_erase_boxes(n, size, size, generator)
+    return tab.contiguous()
+
+
+def _checked_table(n, table, size):
+    table = torch.as_tensor(table).cpu()
+    if table.dim() != 2 or tuple(table.shape) != (n, SW_COLS) or table.dtype != torch.int32:
+        raise ValueError(f'the parameter table must be int32 [{n}, {SW_COLS}], got {table.dtype} {tuple(table.shape)}')
+    t = table.long()
+    flags = t[:, [SW_STRONG, SW_BLUR, SW_SOLARIZE, SW_GRAY]]
+    if bool(((flags != 0) & (flags != 1)).any()):
+        raise ValueError('strong / blur / solarize / gray flags must be 0 or 1')
+    if n and not bool((t[:, SW_ORDER:SW_ORDER + 3].sort(1).values == torch.arange(3)).all()):
+        raise ValueError('the operation order must be a permutation of (0, 1, 2)')
+    f = table[:, SW_FACTOR:SW_FACTOR + 3].contiguous().view(torch.float32)
+    if not bool((torch.isfinite(f) & (f >= 0)).all()):
+        raise ValueError('colour factors must be finite and non-negative')
+    r, ww, fw = t[:, SW_R], t[:, SW_WW], t[:, SW_FW]
+    if bool(((r < 0) | (r > 3) | (ww < 1) | ((2 * r + 1) * ww > (1 << 24)) | (fw != ((1 << 24) - (2 * r + 1) * ww) // 2)).any()):
+        raise ValueError('blur box: need 0 <= r <= 3, ww >= 1, (2r+1) * ww <= 2^24 and fw = (2^24 - (2r+1) * ww) / 2')
+    top, left, h, w = t[:, SW_ERASE:SW_ERASE + 4].unbind(1)
+    if bool(((h < 0) | (w < 0) | (top < 0) | (left < 0) | (top + h > size) | (left + w > size) | ((h == 0) != (w == 0))).any()):
+        raise ValueError(f'erase box outside the {size} x {size} view (columns are top, left, height, width; height = width = 0 for none)')
+    return table.contiguous()
+
+
+class DeviceStrongWeakPair:
+    """The distillation phase's view pair over uint8 images [N,H,W,3] resident on the GPU: weak = RandomResizedCrop(out, BICUBIC) ->
+    RandomHorizontalFlip; strong = weak, or with probability strong_prob ColorJitter -> GaussianBlur -> Solarization -> RandomGrayscale of it; both
+    ToTensor + Normalize, RandomErasing('pixel') on the strong one.  Two launches per batch (fsvit_image_transform_rrc_u8, fsvit_image_strong_weak),
+    bit-exact with Pillow up to the erase noise, which the kernel generates from `seed`.  NOT restated: the weak view's RandomApply([RandAugment],
+    p = 0.2).  All parameters are drawn on the host from this object's generator, or passed in; `params` keeps the last call's
+    {'boxes', 'flips', 'table', 'seed'}, and `tf(images, index, params=tf.params)` replays it."""
+
+    def __init__(self, in_hw, out=80, device='cuda', mean=IMAGENET_MEAN, std=IMAGENET_STD, strong_prob=0.5, seed=0):
+        import ctypes as C
+        if int(out) != 80:
+            raise NotImplementedError('fsvit: the strong / weak kernel is built for 80 x 80 views')
+        self.H, self.W = in_hw
+        self.out = int(out)
+        self.device = torch.device(device)
+        self.mean = (C.c_float * 3)(*mean)
+        self.std = (C.c_float * 3)(*std)
+        self.strong_prob = float(strong_prob)
+        self.generator = torch.Generator().manual_seed(int(seed))
+        self.params = None
+
+    def manual_seed(self, seed):
+        self.generator.manual_seed(int(seed))
+        return self
+
+    def draw(self, n):
+        boxes = random_resized_crop_boxes(n, self.H, self.W, self.generator)
+        flips = torch.rand(n, generator=self.generator) < 0.5
+        table = strong_weak_table(n, self.generator, self.strong_prob, self.out)
+        seed = int(torch.randint(0, 1 << 62, (1,), generator=self.generator))
+        return {'boxes': boxes, 'flips': flips, 'table': table, 'seed': seed}
+
+    @staticmethod
+    def _checked_seed(seed):
+        seed = int(seed)
+        if not 0 <= seed < (1 << 64):
+            raise ValueError('seed must fit 64 bits')
+        return seed
+
+    def _checked(self, n, params):
+        boxes, flips = _checked_boxes(n, params['boxes'], params['flips'], self.H, self.W)
+        return boxes, flips, _checked_table(n, params['table'], self.out), self._checked_seed(params['seed'])
+
+    def _images(self, images, hw):
+        from ..engine import _require_cuda
+        _require_cuda(images)
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_contiguous():
+            raise ValueError('images must be a contiguous uint8 [N,H,W,3] tensor')
+        if tuple(images.shape[1:3]) != tuple(hw):
+            raise ValueError(f'images are {tuple(images.shape[1:3])}, expected {tuple(hw)}')
+
+    # the two launches, on arguments already validated
+    def _crop_u8(self, images, index, boxes, flips, code):
+        from .. import _lib
+        from ..engine import _ptr, _stream_ptr
+        B = index.numel()
+        index = index.to(images.device, torch.int64).contiguous()
+        boxes_dev, flips_dev = boxes.to(images.device), flips.to(images.device)
+        out = torch.empty(B, self.out, self.out, 3, dtype=torch.uint8, device=images.device)
+        with torch.cuda.device(images.device):
+            _lib.check(_lib.load().fsvit_image_transform_rrc_u8(
+                _ptr(images), self.H, self.W, _ptr(index), B, _ptr(boxes_dev), _ptr(flips_dev), self.out, self.out, code, _ptr(out),
+                _stream_ptr(images.device)))
+        return out
+
+    def _strong_weak(self, views, table, seed):
+        from .. import _lib
+        from ..engine import _ptr, _stream_ptr
+        B = views.shape[0]
+        table_dev = table.to(views.device)
+        weak = torch.empty(B, 3, self.out, self.out, dtype=torch.float32, device=views.device)
+        strong = torch.empty_like(weak)
+        with torch.cuda.device(views.device):
+            _lib.check(_lib.load().fsvit_image_strong_weak(
+                _ptr(views), B, self.out, self.out, _ptr(table_dev), SW_COLS, self.mean, self.std, seed, _ptr(weak), _ptr(strong),
+                _stream_ptr(views.device)))
+        return strong, weak
+
+    def crop_u8(self, images, index, boxes, flips, filter='bicubic'):
+        """Crop + Pillow resize (`filter`: 'bilinear' / 'bicubic') + flip -> uint8 [B, out, out, 3] on the GPU."""
+        boxes, flips = _checked_boxes(index.numel(), boxes, flips, self.H, self.W)
+        code = FILTERS[filter][0]
+        self._images(images, (self.H, self.W))
+        return self._crop_u8(images, index, boxes, flips, code)
+
+    def strong_weak(self, views, table, seed=0):
+        """uint8 weak views [B, 80, 80, 3] on the GPU + parameter table -> (strong, weak) float32 [B, 3, 80, 80]."""
+        table = _checked_table(views.shape[0] if views.dim() == 4 else -1, table, self.out)
+        seed = self._checked_seed(seed)
+        self._images(views, (self.out, self.out))
+        return self._strong_weak(views, table, seed)
+
+    def __call__(self, images: torch.Tensor, index: torch.Tensor, params=None):
+        B = index.numel()
+        if params is None:
+            params = self.draw(B)
+        boxes, flips, table, seed = self._checked(B, params)                   # once, on the host, before anything reaches the device
+        self._images(images, (self.H, self.W))
+        self.params = {'boxes': boxes, 'flips': flips.bool(), 'table': table, 'seed': seed}
+        return self._strong_weak(self._crop_u8(images, index, boxes, flips, FILTERS['bicubic'][0]), table, seed)

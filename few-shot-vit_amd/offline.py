@@ -10,8 +10,10 @@ MI355X-native: the encoder's train-mode forward / backward (both outputs of `ret
 the soft-target loss + gradient and the AdamW update are HIP kernels behind the C-ABI; cross-entropy on [B, 64] logits stays in the
 caller as in the reference.  Multi-GPU = one process per GPU (torchrun): every rank takes its slice of each batch, BatchNorm
 statistics stay per replica (as under the reference's nn.DataParallel, :222-225) and the one exchange per step is the all-reduce (mean) of
-the flattened gradients over RCCL.  Not restated: tensorboard, dataset visualisation, the strong / weak augmentation pair (the teacher
-sees the same image as the student unless the dataset returns three items), `epoch_ex`.
+the flattened gradients over RCCL.  The strong / weak augmentation pair comes from a dataset made with `augment: strongweak` (one launch pair per
+batch on the GPU, datasets/transforms.py:DeviceStrongWeakPair; the reference keys it on `split: train`); with any other dataset the teacher sees
+the same image as the student unless the dataset returns three items.  Not restated: tensorboard, dataset visualisation, the weak view's
+RandAugment, `epoch_ex`.
 
   python -m fewshot_vit_amd.offline --config few-shot-vit_amd/configs/offline_synthetic.yaml
 """
@@ -31,6 +33,10 @@ from .utils.schedulers import CosineLRScheduler
 
 
 def _gather(dataset, idx, device):
+    if hasattr(dataset, 'gather_pair'):                                                      # device-resident view pair: one launch pair per batch
+        data, weak = dataset.gather_pair(idx)
+        label = torch.tensor([int(dataset.label[int(i)]) for i in idx], device=device)
+        return data.to(device, non_blocking=True), weak.to(device, non_blocking=True), label
     items = [dataset[int(i)] for i in idx]
     data = torch.stack([it[0] for it in items]).to(device, non_blocking=True)
     weak = torch.stack([it[1] for it in items]).to(device, non_blocking=True) if len(items[0]) == 3 else data
@@ -101,6 +107,8 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     train_dataset = datasets.make(config['train_dataset'], **config['train_dataset_args'])
     val_dataset = datasets.make(config['val_dataset'], **config['val_dataset_args'])
     val_sampler = CategoriesSampler(val_dataset.label, config.get('eval_batches', 200), n_way, n_shot + n_query, ep_per_batch=ep_per_batch)
+    if hasattr(train_dataset, 'gather_pair'):                                                # ranks draw different views; a run is repeatable
+        train_dataset.transform.manual_seed(config.get('seed', 0) + rank)
     if rank == 0:
         log('train dataset: {} (x{}), {}'.format(tuple(train_dataset[0][0].shape), len(train_dataset), train_dataset.n_classes))
 

@@ -422,6 +422,22 @@ int fsvit_image_transform_gather(const uint8_t* images_dev, int H, int W, const 
 int fsvit_image_transform_rrc_gather(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
                                      const uint8_t* flip_dev, int OH, int OW, const float* mean3_host, const float* std3_host,
                                      float* out_dev, void* stream);
+/* The same crop + resize + flip left as bytes: out_dev uint8 [B,OH,OW,3], filter 0 = Pillow BILINEAR (the bytes fsvit_image_transform_rrc_gather
+ * normalises), 1 = Pillow BICUBIC (a = -0.5, support 2; negative taps, so the clip to 0..255 is live).  With filter 1 this is the weak view of the
+ * distillation phase before ToTensor (sun_meta_training/datasets/mini_imagenet.py:100-102: RandomResizedCropAndInterpolation(80, 'bicubic') ->
+ * RandomHorizontalFlip; its RandomApply([RandAugment], p = 0.2) is NOT restated). */
+int fsvit_image_transform_rrc_u8(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
+                                 const uint8_t* flip_dev, int OH, int OW, int filter, uint8_t* out_dev, void* stream);
+/* The strong / weak pair of the distillation phase (mini_imagenet.py:110-124, :194-204) from uint8 weak views views_dev [B,80,80,3] (16-byte
+ * aligned; H = W = 80 or argument error): weak_dev [B,3,80,80] = Normalize(ToTensor(view)); strong_dev [B,3,80,80] = the same of the view after,
+ * when the row's strong flag is set, ColorJitter (brightness / contrast / saturation in the row's order) -> GaussianBlur -> Solarization ->
+ * RandomGrayscale, bit-exact with Pillow; then RandomErasing('pixel'): inside the row's erase box every value is an N(0, 1) draw of a counter-based
+ * generator keyed by (seed, image slot, channel, pixel).  table_dev int32 [B, cols = 17], one row per image, the caller draws it:
+ *   0 strong flag | 1-3 operation order (0 brightness, 1 contrast, 2 saturation) | 4-6 their factors as float32 bits | 7 blur flag, 8 box radius r,
+ *   9 ww, 10 fw (Pillow's 24-bit box weights; datasets/transforms.py:gaussian_blur_box) | 11 solarize | 12 grayscale | 13-16 erase top, left,
+ *   height, width (height 0 = none).  Callers validate the rows; the kernel reads nothing outside its image whatever they hold. */
+int fsvit_image_strong_weak(const uint8_t* views_dev, int B, int H, int W, const int32_t* table_dev, int cols, const float* mean3_host,
+                            const float* std3_host, uint64_t seed, float* weak_dev, float* strong_dev, void* stream);
 
 /* Operator level of the training path: attention backward (qkv, dctx -> dqkv; hd real / hdp padded head dim). */
 /* Weight gradient of a 3x3 / stride 1 / pad 1 convolution straight from the NHWC activations (no im2col, no transposed copies):
