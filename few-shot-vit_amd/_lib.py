@@ -167,6 +167,13 @@ SIGNATURES = {
     'fsvit_op_fill_f32': (_i, [_fp, _f, _sz, _vp]),
     'fsvit_op_scale_copy': (_i, [_fp, _fp, _sz, _f, _vp]),
     'fsvit_op_fold_prenorm': (_i, [_fp, _fp, _fp, _vp, _fp, _i, _i, _i, _i, _vp]),
+    # ... and the MFMA side: weight packs, the conv launchers' training epilogues, the stage-1 ring kernels
+    'fsvit_op_pack_weight': (_i, [_fp, _vp] + [_i] * 13 + [_vp]),
+    'fsvit_op_pack_weight_multi': (_i, [C.POINTER(_fp), C.POINTER(_vp), C.POINTER(_i), _i, _i, _vp]),
+    'fsvit_op_conv_train': (_i, [_vp, _vp, _fp, _vp, _vp, _vp] + [_i] * 15 + [C.POINTER(_i), _vp]),
+    'fsvit_op_gconv3x3_train': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_stage1_block_train': (_i, [_vp, _vp, _vp, _fp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_stage1_block_dgrad': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_sampler_draw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 

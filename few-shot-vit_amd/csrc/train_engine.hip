@@ -1854,3 +1854,133 @@ extern "C" int fsvit_op_fold_prenorm(const float* W, const float* sa, const floa
   OP_RUN("fold_prenorm", launch_fold_prenorm(W, sa, sb, wf, bf, N, C, Kw, dtype, (hipStream_t)stream));
   return 0;
 }
+
+// ---------------------------------------------------------------- the MFMA side: weight packs, the conv launchers' training epilogues, the stage-1 ring kernels
+namespace {
+// what pack_weight_multi_kernel assumes of a job in modes 0 .. 2 (it guards its reads of w; rows and columns that do not fit are dropped silently)
+int op_pack_job_check(const char* fn, const PackJob& j, int i) {
+  if (!j.w || !j.out) return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: null argument", fn, i);
+  if (j.mode < 0 || j.mode > 2) return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: mode %d (0 forward | 1 transposed | 2 patch dgrad; the fragment images are not served)", fn, i, j.mode);
+  if (j.O < 1 || j.Ig < 1 || j.KH < 1 || j.KW < 1 || j.groups < 1 || j.O % j.groups || j.rows_pad < 1 || j.Kw < 1)
+    return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: O %d, Ig %d, %d x %d, groups %d, rows_pad %d, Kw %d", fn, i, j.O, j.Ig, j.KH, j.KW, j.groups, j.rows_pad, j.Kw);
+  if (j.hd_rows < 1 || j.hdp_rows < j.hd_rows || j.hd_cols < 1 || j.hdp_cols < j.hd_cols)
+    return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: head padding rows %d -> %d, columns %d -> %d", fn, i, j.hd_rows, j.hdp_rows, j.hd_cols, j.hdp_cols);
+  const int Ng = j.O / j.groups, taps = j.KH * j.KW;
+  if (j.mode == 2) {
+    if (j.hd_rows != j.hdp_rows || j.hd_cols != j.hdp_cols) return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: mode 2 has no head padding", fn, i);
+    if (j.rows_pad < taps * j.Ig || j.Kw < Ng) return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: mode 2 needs rows_pad >= %d, Kw >= %d", fn, i, taps * j.Ig, Ng);
+    return 0;
+  }
+  const int nrows = j.mode == 0 ? Ng : j.Ig, K = taps * (j.mode == 0 ? j.Ig : Ng);
+  if (nrows % j.hd_rows || K % j.hd_cols) return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: %d rows / %d columns are not whole heads of %d / %d", fn, i, nrows, K, j.hd_rows, j.hd_cols);
+  if (j.rows_pad < nrows / j.hd_rows * j.hdp_rows || j.Kw < K / j.hd_cols * j.hdp_cols)
+    return fsvit_set_error(FSVIT_ERR_ARG, "%s: job %d: needs rows_pad >= %d, Kw >= %d", fn, i, nrows / j.hd_rows * j.hdp_rows, K / j.hd_cols * j.hdp_cols);
+  return 0;
+}
+inline bool op_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + nb && pb < pa + na;
+}
+struct OpBuf { const void* p; size_t bytes; bool out; };
+// no output may overlap an input or another output
+bool op_buffers_alias(const OpBuf* b, int n) {
+  for (int i = 0; i < n; ++i)
+    for (int k = i + 1; k < n; ++k)
+      if ((b[i].out || b[k].out) && op_overlap(b[i].p, b[i].bytes, b[k].p, b[k].bytes)) return true;
+  return false;
+}
+int op_ring_shape(const char* fn, int B, int H, int W, int w2_ld, int dtype) {
+  if (dtype != FSVIT_BF16) return fsvit_set_error(FSVIT_ERR_ARG, "%s: storage dtype %d (the stage-1 ring training kernels are FSVIT_BF16 only)", fn, dtype);
+  if (B < 1 || H < 1 || W < 1 || W > 20 || (long)H * W < 16) return fsvit_set_error(FSVIT_ERR_ARG, "%s: B = %d, H = %d, W = %d (1 <= W <= 20, H * W >= 16)", fn, B, H, W);
+  if ((long)B * H * W >= (1L << 31) - 256) return fsvit_set_error(FSVIT_ERR_ARG, "%s: map too large", fn);
+  if (w2_ld != 320) return fsvit_set_error(FSVIT_ERR_ARG, "%s: w2 row length %d (the kernel reads rows of 320: 9 taps x 32 channels padded to the K slice)", fn, w2_ld);
+  return 0;
+}
+}  // namespace
+
+extern "C" int fsvit_op_pack_weight_multi(const float* const* w, void* const* out, const int* fields, int n, int dtype, void* stream) {
+  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16 && dtype != FSVIT_BF16X2)
+    OP_FAIL("fsvit_op_pack_weight_multi: dtype %d (FSVIT_F32, FSVIT_BF16 or the two-limb words FSVIT_BF16X2)", dtype);
+  if (!w || !out || !fields || n < 1) OP_FAIL("fsvit_op_pack_weight_multi: null argument or n = %d", n);
+  std::vector<PackJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const int* f = fields + (size_t)i * 12;
+    jobs[i] = PackJob{w[i], out[i], f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11]};
+    if (int rc = op_pack_job_check("fsvit_op_pack_weight_multi", jobs[i], i)) return rc;
+  }
+  OP_RUN("pack_weight_multi", launch_pack_weight_multi(jobs.data(), n, dtype == FSVIT_BF16X2 ? 2 : dtype, (hipStream_t)stream));
+  return 0;
+}
+extern "C" int fsvit_op_pack_weight(const float* w, void* out, int O, int Ig, int KH, int KW, int groups, int mode, int rows_pad, int Kw, int hd_rows, int hdp_rows,
+                                    int hd_cols, int hdp_cols, int dtype, void* stream) {
+  const int f[12] = {O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols};
+  return fsvit_op_pack_weight_multi(&w, &out, f, 1, dtype, stream);
+}
+
+extern "C" int fsvit_op_conv_train(const void* x, const void* w, const float* bias, const void* mul, void* y, void* y2, int B, int H, int W, int Cin, int x_cstride, int KH,
+                                   int KW, int stride, int pad, int N, int y_cstride, int Kw, int groups, int act, int dtype, int* route, void* stream) {
+  OP_DT("fsvit_op_conv_train");
+  if (!x || !w || !y) OP_FAIL("fsvit_op_conv_train: null argument");
+  if (act != FSVIT_ACT_NONE && act != FSVIT_ACT_GELU && act != FSVIT_ACT_MUL) OP_FAIL("fsvit_op_conv_train: act %d (none | GELU | MUL)", act);
+  if (y2 && act != FSVIT_ACT_GELU) OP_FAIL("fsvit_op_conv_train: y2 (the GELU derivative) without act = GELU");
+  if (act == FSVIT_ACT_MUL && !mul) OP_FAIL("fsvit_op_conv_train: act = MUL without mul");
+  if (mul && act != FSVIT_ACT_MUL) OP_FAIL("fsvit_op_conv_train: mul without act = MUL");
+  if (B < 1 || H < 1 || W < 1 || Cin < 1 || N < 1 || groups < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || H + 2 * pad < KH || W + 2 * pad < KW)
+    OP_FAIL("fsvit_op_conv_train: bad geometry");
+  const int es = dtype == FSVIT_F32 ? 4 : 2, epc = 16 / es, bke = 128 / es;
+  if (Cin % epc || x_cstride % epc || x_cstride < groups * Cin || N % 4 || y_cstride % 4 || y_cstride < groups * N || Kw % bke || Kw < KH * KW * Cin)
+    OP_FAIL("fsvit_op_conv_train: alignment: Cin / x_cstride %% %d, N / y_cstride %% 4, Kw %% %d and >= KH * KW * Cin", epc, bke);
+  if (KH * KW > 1 && (Cin & (Cin - 1)) && Cin % 32) OP_FAIL("fsvit_op_conv_train: a multi-tap conv needs a power-of-two Cin or a multiple of 32");
+  ConvGemmParams p = gemm_params(x, w, y, B, H, W, Cin, x_cstride, KH, KW, stride, pad, N, y_cstride, KH * KW * Cin, Kw, groups);
+  if ((long)B * p.OH * p.OW > 0x7fffffffL) OP_FAIL("fsvit_op_conv_train: map too large");
+  p.bias = bias;
+  p.act = act == FSVIT_ACT_MUL ? ACT_MUL : act;
+  p.res = mul;
+  p.y2 = y2;
+  const size_t ybytes = (size_t)p.M * y_cstride * es;
+  if (y == x || (y2 && (y2 == x || op_overlap(y, ybytes, y2, ybytes))) || (mul && op_overlap(y, ybytes, mul, ybytes)))
+    OP_FAIL("fsvit_op_conv_train: y / y2 overlap an operand");
+  if (route) *route = conv_gemm_route(p, dtype);
+  OP_RUN("conv_gemm", launch_conv_gemm(p, dtype, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_op_gconv3x3_train(const void* x, const void* w_packed, int Kw, void* y, void* y2, const void* mul, int B, int H, int W, int dtype, void* stream) {
+  if (dtype != FSVIT_BF16) OP_FAIL("fsvit_op_gconv3x3_train: storage dtype %d (FSVIT_BF16 only)", dtype);
+  if (!x || !w_packed || !y) OP_FAIL("fsvit_op_gconv3x3_train: null argument");
+  if (y2 && mul) OP_FAIL("fsvit_op_gconv3x3_train: y2 and mul together (the kernel has the GELU-derivative form or the multiplier form, not both)");
+  if (B < 1 || H < 1 || W < 1 || !gconv3x3_supported(1, 256, 32, 8, 3, 3, 1, 1, W) || Kw < 288 || (Kw & 7))
+    OP_FAIL("fsvit_op_gconv3x3_train: B = %d, H = %d, W = %d, Kw = %d (W <= 20, Kw >= 288 and a multiple of 8)", B, H, W, Kw);
+  if ((long)B * H * W > 0x7fffffffL - 64) OP_FAIL("fsvit_op_gconv3x3_train: map too large");
+  const size_t bytes = (size_t)B * H * W * 256 * 2;
+  const OpBuf bufs[] = {{x, bytes, false}, {w_packed, (size_t)256 * Kw * 2, false}, {y, bytes, true}, {y2 ? y2 : y, y2 ? bytes : 0, true}};
+  if (op_buffers_alias(bufs, 4)) OP_FAIL("fsvit_op_gconv3x3_train: y / y2 overlap an operand");
+  OP_RUN("gconv3x3", launch_gconv3x3(x, w_packed, Kw, y, B, H, W, (hipStream_t)stream, y2, mul));
+  return 0;
+}
+
+extern "C" int fsvit_op_stage1_block_train(const void* x, void* out, const void* w1f, const float* b1f, const void* w2, int w2_ld, const void* w3, void* h1, void* g1,
+                                           void* h2, void* g2, void* xn, const float* sa, const float* sb, const float* scale, int B, int H, int W, int dtype,
+                                           void* stream) {
+  if (int rc = op_ring_shape("fsvit_op_stage1_block_train", B, H, W, w2_ld, dtype)) return rc;
+  if (!x || !out || !w1f || !b1f || !w2 || !w3 || !h1 || !g1 || !h2 || !g2 || !xn || !sa || !sb) OP_FAIL("fsvit_op_stage1_block_train: null argument");
+  const size_t M = (size_t)B * H * W, m128 = M * 128 * 2, m256 = M * 256 * 2;
+  const OpBuf bufs[] = {{x, m128, false}, {w1f, 256 * 128 * 2, false}, {b1f, 256 * 4, false}, {w2, 256 * 320 * 2, false}, {w3, 128 * 256 * 2, false},
+                        {sa, 128 * 4, false}, {sb, 128 * 4, false}, {scale ? (const void*)scale : x, scale ? (size_t)B * 4 : 0, false},
+                        {out, m128, true}, {h1, m256, true}, {g1, m256, true}, {h2, m256, true}, {g2, m256, true}, {xn, m128, true}};
+  if (op_buffers_alias(bufs, 14)) OP_FAIL("fsvit_op_stage1_block_train: an output overlaps an input or another output");
+  OP_RUN("stage1_ring_block_train", launch_stage1_ring_block_train(x, out, w1f, b1f, w2, w3, h1, g1, h2, g2, xn, sa, sb, scale, nullptr, B, H, W, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_op_stage1_block_dgrad(const void* dz3, void* dxn, const void* w3t, const void* w2t, int w2_ld, const void* w1t, const void* g2, const void* g1,
+                                           void* dz2, void* dz1, int B, int H, int W, int dtype, void* stream) {
+  if (int rc = op_ring_shape("fsvit_op_stage1_block_dgrad", B, H, W, w2_ld, dtype)) return rc;
+  if (!dz3 || !dxn || !w3t || !w2t || !w1t || !g2 || !g1 || !dz2 || !dz1) OP_FAIL("fsvit_op_stage1_block_dgrad: null argument");
+  const size_t M = (size_t)B * H * W, m128 = M * 128 * 2, m256 = M * 256 * 2;
+  const OpBuf bufs[] = {{dz3, m128, false}, {w3t, 256 * 128 * 2, false}, {w2t, 256 * 320 * 2, false}, {w1t, 128 * 256 * 2, false}, {g2, m256, false}, {g1, m256, false},
+                        {dxn, m128, true}, {dz2, m256, true}, {dz1, m256, true}};
+  if (op_buffers_alias(bufs, 9)) OP_FAIL("fsvit_op_stage1_block_dgrad: an output overlaps an input or another output");
+  OP_RUN("stage1_ring_dgrad", launch_stage1_ring_dgrad(dz3, dxn, w3t, w2t, w1t, g2, g1, dz2, dz1, B, H, W, (hipStream_t)stream));
+  return 0;
+}

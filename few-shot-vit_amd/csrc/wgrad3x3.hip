@@ -552,6 +552,7 @@ bool gconv3x3_supported(int dtype, int O, int Ig, int groups, int KH, int KW, in
   return dtype == 1 && O == 256 && Ig == 32 && groups == 8 && KH == 3 && KW == 3 && stride == 1 && pad == 1 && W <= 20;
 }
 int launch_gconv3x3(const void* x, const void* w_packed, int Kw, void* y, int B, int H, int W, hipStream_t s, void* y2, const void* mul) {
+  if (y2 && mul) return (int)hipErrorInvalidValue;      // the epilogue has no GELU-times-multiplier form (mul would be ignored)
   const int M = B * H * W, n_chunks = (M + wg3::CH - 1) / wg3::CH;
   int wgs = n_chunks < 512 ? n_chunks : 512;
   const int cpw = (n_chunks + wgs - 1) / wgs;

@@ -1199,3 +1199,120 @@ class ops:
         out = torch.empty_like(x)
         ops._op(x, 'scale_copy', _ptr(x), _ptr(out), x.numel(), float(scale))
         return out
+
+    # ---- the MFMA side of the training step: weight packs, the conv launchers' training epilogues, the stage-1 ring kernels (fsvit.h)
+    ACT_NONE, ACT_GELU, ACT_MUL = 0, 1, 3
+
+    @staticmethod
+    def _pack_dt(dtype):
+        """-> (fsvit dtype code, torch dtype of the packed buffer, elements per 128-byte K slice); 'bf16x2': two-limb words in a float32-typed tensor"""
+        if dtype == 'bf16x2':
+            return _lib.BF16X2, torch.float32, 32
+        if dtype == torch.float32:
+            return _lib.F32, torch.float32, 32
+        if dtype == torch.bfloat16:
+            return _lib.BF16, torch.bfloat16, 64
+        if dtype == torch.float16:
+            return _lib.F16, torch.float16, 64          # (refused by the entry: no f16 build of the pack kernel)
+        raise TypeError(dtype)
+
+    @staticmethod
+    def pack_geometry(shape, groups, mode, bke, hd_rows=1, hdp_rows=1, hd_cols=1, hdp_cols=1):
+        """(rows_pad, Kw) as the trainer sizes a pack of a conv weight [O, Ig, KH, KW]: padded rows, padded columns rounded up to the K slice of bke elements"""
+        O, Ig, KH, KW = shape
+        Ng = O // groups
+        if mode == 2:
+            rows, K = KH * KW * Ig, Ng
+        else:
+            rows = (Ng if mode == 0 else Ig) // hd_rows * hdp_rows
+            K = KH * KW * (Ig if mode == 0 else Ng) // hd_cols * hdp_cols
+        return rows, -(-K // bke) * bke
+
+    @staticmethod
+    def pack_weight_multi(jobs, dtype):
+        """jobs: dicts(w [O,Ig,KH,KW] fp32, groups, mode[, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols]) -> the packed [groups, rows_pad, Kw] of each, in
+        ONE call of launch_pack_weight_multi (any number of jobs: the launcher walks its 40-job table)."""
+        code, tdt, bke = ops._pack_dt(dtype)
+        ws, outs, fields = [], [], []
+        for j in jobs:
+            w = j['w']
+            _require_cuda(w)
+            assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 4
+            groups, mode = int(j.get('groups', 1)), int(j['mode'])
+            hd = [int(j.get(k, 1)) for k in ('hd_rows', 'hdp_rows', 'hd_cols', 'hdp_cols')]
+            rows, Kw = ops.pack_geometry(w.shape, groups, mode, bke, *hd)
+            rows, Kw = int(j.get('rows_pad') or rows), int(j.get('Kw') or Kw)
+            out = torch.full((groups, max(rows, 1), max(Kw, 1)), float('nan'), dtype=tdt, device=w.device)
+            ws.append(w)
+            outs.append(out)
+            fields += [w.shape[0], w.shape[1], w.shape[2], w.shape[3], groups, mode, rows, Kw] + hd
+        n = len(jobs)
+        wp = (C.c_void_p * n)(*[w.data_ptr() for w in ws])
+        op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        fl = (C.c_int * (12 * n))(*fields)
+        ops._op(ws[0], 'pack_weight_multi', wp, op, fl, n, code)
+        return outs
+
+    @staticmethod
+    def pack_weight(w, groups=1, mode=0, rows_pad=None, Kw=None, hd_rows=1, hdp_rows=1, hd_cols=1, hdp_cols=1, dtype=torch.bfloat16):
+        """One job through fsvit_op_pack_weight: conv weight w [O,Ig,KH,KW] fp32 -> packed [groups, rows_pad, Kw] (mode 0 forward, 1 transposed + flipped
+        taps, 2 patch-conv data gradient); dtype torch.float32 | torch.bfloat16 | 'bf16x2'."""
+        _require_cuda(w)
+        assert w.dtype == torch.float32 and w.is_contiguous() and w.dim() == 4
+        code, tdt, bke = ops._pack_dt(dtype)
+        rows, kw = ops.pack_geometry(w.shape, groups, mode, bke, hd_rows, hdp_rows, hd_cols, hdp_cols) if mode in (0, 1, 2) else (1, 1)
+        rows, kw = int(rows_pad or rows), int(Kw or kw)
+        out = torch.full((groups, max(rows, 1), max(kw, 1)), float('nan'), dtype=tdt, device=w.device)
+        ops._op(w, 'pack_weight', _ptr(w), _ptr(out), w.shape[0], w.shape[1], w.shape[2], w.shape[3], groups, mode, rows, kw, hd_rows, hdp_rows, hd_cols,
+                hdp_cols, code)
+        return out
+
+    @staticmethod
+    def conv_train(x, w, bias, KH, KW, stride, pad, N, groups, act, with_y2=False, mul=None):
+        """launch_conv_gemm with the training epilogues: x NHWC [B,H,W,groups*Cin], w packed [groups][N][Kw] -> (y, y2 | None, route).  act ops.ACT_GELU with
+        with_y2: y = GELU(conv + bias) and y2 = the GELU derivative; act ops.ACT_MUL: y = (conv + bias) * mul.  route: 0 conv3x3_halo, 1 gemm256, 2 conv_gemm_v2."""
+        _require_cuda(x, w, bias, mul)
+        B, H, W, xc = x.shape
+        OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+        y = torch.full((B, OH, OW, groups * N), float('nan'), dtype=x.dtype, device=x.device)
+        y2 = torch.full_like(y, float('nan')) if with_y2 else None
+        route = C.c_int(-1)
+        ops._op(x, 'conv_train', _ptr(x), _ptr(w), _ptr(bias), _ptr(mul), _ptr(y), _ptr(y2), B, H, W, xc // groups, xc, KH, KW, stride, pad, N, groups * N,
+                w.shape[-1], groups, int(act), ops._dt(x), C.byref(route))
+        return y, y2, route.value
+
+    @staticmethod
+    def gconv3x3_train(x, w_packed, with_y2=False, mul=None):
+        """launch_gconv3x3 with its training epilogues: x NHWC [B,H,W,256] bf16, w_packed [256][Kw] -> (y, y2 | None); with_y2: y = GELU(conv), y2 the
+        derivative; mul: y = conv * mul."""
+        _require_cuda(x, w_packed, mul)
+        B, H, W, _ = x.shape
+        y = torch.full_like(x, float('nan'))
+        y2 = torch.full_like(x, float('nan')) if with_y2 else None
+        ops._op(x, 'gconv3x3_train', _ptr(x), _ptr(w_packed), w_packed.shape[-1], _ptr(y), _ptr(y2), _ptr(mul), B, H, W, ops._dt(x))
+        return y, y2
+
+    @staticmethod
+    def stage1_block_train(x, w1f, b1f, w2, w3, sa, sb, scale=None, out=None):
+        """launch_stage1_ring_block_train: x NHWC [B,H,W,128] bf16, w1f [256,128] / b1f [256] (ops.fold_prenorm), w2 [256,320], w3 [128,256], sa / sb [128] fp32,
+        scale [B] fp32 or None -> dict(out, h1, g1, h2, g2, xn) (maps [B,H,W,128 | 256])."""
+        _require_cuda(x, w1f, b1f, w2, w3, sa, sb, scale, out)
+        B, H, W, _ = x.shape
+        nan = lambda c: torch.full((B, H, W, c), float('nan'), dtype=x.dtype, device=x.device)
+        r = dict(out=nan(128) if out is None else out, h1=nan(256), g1=nan(256), h2=nan(256), g2=nan(256), xn=nan(128))
+        ops._op(x, 'stage1_block_train', _ptr(x), _ptr(r['out']), _ptr(w1f), _ptr(b1f), _ptr(w2), w2.shape[-1], _ptr(w3), _ptr(r['h1']), _ptr(r['g1']),
+                _ptr(r['h2']), _ptr(r['g2']), _ptr(r['xn']), _ptr(sa), _ptr(sb), _ptr(scale), B, H, W, ops._dt(x))
+        return r
+
+    @staticmethod
+    def stage1_block_dgrad(dz3, w3t, w2t, w1t, g2, g1, dxn=None):
+        """launch_stage1_ring_dgrad: dz3 NHWC [B,H,W,128] bf16, the transposed packs w3t [256,128], w2t [256,320] (tap-flipped), w1t [128,256], the saved
+        derivatives g2 / g1 [B,H,W,256] -> (dxn [B,H,W,128], dz2, dz1 [B,H,W,256])."""
+        _require_cuda(dz3, w3t, w2t, w1t, g2, g1, dxn)
+        B, H, W, _ = dz3.shape
+        nan = lambda c: torch.full((B, H, W, c), float('nan'), dtype=dz3.dtype, device=dz3.device)
+        dxn = nan(128) if dxn is None else dxn
+        dz2, dz1 = nan(256), nan(256)
+        ops._op(dz3, 'stage1_block_dgrad', _ptr(dz3), _ptr(dxn), _ptr(w3t), _ptr(w2t), w2t.shape[-1], _ptr(w1t), _ptr(g2), _ptr(g1), _ptr(dz2), _ptr(dz1),
+                B, H, W, ops._dt(dz3))
+        return dxn, dz2, dz1

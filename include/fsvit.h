@@ -31,7 +31,8 @@ extern "C" {
 #endif
 
 enum { FSVIT_F32 = 0, FSVIT_BF16 = 1, FSVIT_F16 = 2, FSVIT_BF16X2 = 3, FSVIT_F16X2 = 4 };
-enum { FSVIT_ACT_NONE = 0, FSVIT_ACT_GELU = 1, FSVIT_ACT_LRELU = 2 };
+enum { FSVIT_ACT_NONE = 0, FSVIT_ACT_GELU = 1, FSVIT_ACT_LRELU = 2,
+       FSVIT_ACT_MUL = 3 /* fsvit_op_conv_train only: y = conv(x) * mul, the data-gradient GEMM times the saved GELU derivative */ };
 enum { FSVIT_HEAD_COS = 0, FSVIT_HEAD_SQR = 1, FSVIT_HEAD_DOT = 2 };
 enum {
   FSVIT_ERR_ARG = -1,        /* bad argument / unsupported configuration        */
@@ -462,7 +463,7 @@ int fsvit_attention_backward(const void* qkv_dev, const void* dctx_dev, void* dq
 
 /* ================================================================ operator entry points (tests, tools)
  * The memory-bound kernels of the training step (train_kernels.hip), one entry per engine-level operation, so that each can be held against a
- * plain reference on its own (tests/test_gpu_train_ops.py).  No engine path calls them.  dtype = storage type of the maps: FSVIT_F32 or FSVIT_BF16
+ * plain reference on its own (tests/test_gpu_train_ops.py, tests/test_gpu_train_conv_ops.py).  No engine path calls them.  dtype = storage type of the maps: FSVIT_F32 or FSVIT_BF16
  * (the training kernels are built for these two; anything else is FSVIT_ERR_ARG).  Statistics, parameters and parameter gradients are fp32.  A shape a
  * kernel does not cover is rejected with FSVIT_ERR_ARG and a message; nothing is launched on it.  Maps are row-major [M][C] / NHWC.
  *
@@ -533,6 +534,36 @@ int fsvit_op_droppath_scales(const float* masks, float* scales, int ncalls, int 
 int fsvit_op_fill_f32(float* p, float v, size_t n, void* stream);                                   /* p[i] = v */
 int fsvit_op_scale_copy(const float* in, float* out, size_t n, float scale, void* stream);          /* out[i] = in[i] * scale */
 int fsvit_op_fold_prenorm(const float* W, const float* sa, const float* sb, void* wf, float* bf, int N, int C, int Kw, int dtype, void* stream);
+
+/* ---- the MFMA side of the training step, one launcher per entry (tests/test_gpu_train_conv_ops.py)
+ * Weight packs (launch_pack_weight_multi): PyTorch conv weight w [O][Ig][KH][KW] fp32 -> out [groups][rows_pad][Kw] in `dtype` = FSVIT_F32, FSVIT_BF16 or
+ * FSVIT_BF16X2 (the two-limb words hi << 16 | lo, 4 bytes each).  mode 0: forward rows (row = output channel of the group, k = (ky, kx, i)); 1: the
+ * transposed pack of the data gradient (row = input channel, k = (flipped tap, output channel)); 2: the non-overlapping patch conv's data gradient
+ * (row = (ky, kx, i), k = output channel).  Modes >= 3 (fragment images) are refused.  hd / hdp: head-dim padding of the rows / columns (index j ->
+ * (j / hd) * hdp + j % hd; hd == hdp: none; modes 0 / 1 only).  rows_pad and Kw must hold the padded rows / columns; everything else is zero.
+ * fields [n][12] = O, Ig, KH, KW, groups, mode, rows_pad, Kw, hd_rows, hdp_rows, hd_cols, hdp_cols per job; any n >= 1 (the launcher walks its 40-job table). */
+int fsvit_op_pack_weight(const float* w, void* out, int O, int Ig, int KH, int KW, int groups, int mode, int rows_pad, int Kw, int hd_rows, int hdp_rows,
+                         int hd_cols, int hdp_cols, int dtype, void* stream);
+int fsvit_op_pack_weight_multi(const float* const* w, void* const* out, const int* fields, int n, int dtype, void* stream);
+/* launch_conv_gemm with the training epilogues (geometry arguments as fsvit_conv_gemm; dtype FSVIT_F32 | FSVIT_BF16): act FSVIT_ACT_GELU with y2 != NULL -
+ * y = GELU(conv + bias), y2 = the GELU's derivative at the pre-activation; act FSVIT_ACT_MUL - y = (conv + bias) * mul (mul [M][y_cstride], required);
+ * FSVIT_ACT_NONE / FSVIT_ACT_GELU without y2: the plain forms.  y2 without GELU and mul without FSVIT_ACT_MUL are refused.  *route (may be NULL) receives
+ * the kernel that ran: 0 conv3x3_halo, 1 gemm256, 2 conv_gemm_v2. */
+int fsvit_op_conv_train(const void* x, const void* w, const float* bias, const void* mul, void* y, void* y2, int B, int H, int W, int Cin, int x_cstride, int KH,
+                        int KW, int stride, int pad, int N, int y_cstride, int Kw, int groups, int act, int dtype, int* route, void* stream);
+/* launch_gconv3x3 (fsvit_gconv3x3's kernel, FSVIT_BF16) with y2 != NULL: y = GELU(conv), y2 = the derivative; or mul != NULL: y = conv * mul.  The kernel has
+ * no form with both: refused. */
+int fsvit_op_gconv3x3_train(const void* x, const void* w_packed, int Kw, void* y, void* y2, const void* mul, int B, int H, int W, int dtype, void* stream);
+/* launch_stage1_ring_block_train: the training forward of a whole stage-1 block in one launch.  x, out, xn [B*H*W][128], h1 / g1 / h2 / g2 [B*H*W][256],
+ * w1f [256][128] + b1f [256] (conv1 with the BatchNorm folded, fsvit_op_fold_prenorm), w2 [256][w2_ld] (w2_ld must be 320), w3 [128][256], sa / sb [128],
+ * scale [B] or NULL.  out = x + scale[b] * conv3(h2), h1 = GELU(conv1(x)), g1 its derivative, h2 = GELU(conv2(h1)), g2, xn = sa x + sb.  FSVIT_BF16 only,
+ * 1 <= W <= 20, H * W >= 16, no output may overlap an input or another output. */
+int fsvit_op_stage1_block_train(const void* x, void* out, const void* w1f, const float* b1f, const void* w2, int w2_ld, const void* w3, void* h1, void* g1,
+                                void* h2, void* g2, void* xn, const float* sa, const float* sb, const float* scale, int B, int H, int W, int dtype, void* stream);
+/* launch_stage1_ring_dgrad: dz2 = (dz3 W3) * g2, dz1 = (grouped conv^T of dz2) * g1, dxn = dz1 W1 on the transposed packs w3t [256][128], w2t [256][w2_ld]
+ * (tap-flipped, w2_ld must be 320), w1t [128][256].  The same checks. */
+int fsvit_op_stage1_block_dgrad(const void* dz3, void* dxn, const void* w3t, const void* w2t, int w2_ld, const void* w1t, const void* g2, const void* g1,
+                                void* dz2, void* dz1, int B, int H, int W, int dtype, void* stream);
 
 /* ---------------------------------------------------------------- episode sampler (host only, no GPU)
  * The draws of `CategoriesSampler.__iter__` (test_phase/datasets/samplers.py:19-35) replayed natively on the legacy numpy generator state: per episode

@@ -10,6 +10,10 @@ through `rnd` (a function that rounds a float64 tensor to the storage type and r
 * pool_act_bwd / pool_bn_bwd_* route T(slope * dout).
 
 tests/test_train_ops_ref_cpu.py holds these references to finite differences; tests/test_gpu_train_ops.py holds the kernels to them.
+
+The MFMA side (tests/test_gpu_train_conv_ops.py): gelu_sig / gelu_sig_d (the sigmoid-form GELU of fsvit_common.h and its derivative), pack_weight (the
+packed weight layouts of pack_weight_multi_kernel, modes 0 .. 2), stage1_block_forward / stage1_block_dgrad (the stage-1 ring kernels, every stored
+map, with the kernel's own stored maps optionally standing in for the stage in front).
 """
 import torch
 import torch.nn.functional as F
@@ -147,3 +151,104 @@ def gelu_backward(dh, z):
 def unpatch2(g, B, OH, OW):
     C = g.shape[1] // 4
     return g.reshape(B, OH, OW, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, 2 * OH, 2 * OW, C)
+
+
+# ------------------------------------------------------------------------------------------------ the MFMA side
+# gelu_sig of fsvit_common.h: x * sigmoid(x * poly(x^2)) with x^2 clamped at 64; the three fp32 coefficients carry the -log2(e) of the exp2
+_GS_C2, _GS_C1, _GS_C0 = (float(torch.tensor(v, dtype=torch.float32)) for v in (1.0153755e-3, -1.0678257e-1, -2.3011138))
+_LN2 = 0.69314718055994530942
+
+
+def _gelu_sig_s(z):
+    u = (z * z).clamp(max=64.0)
+    p = (_GS_C2 * u + _GS_C1) * u + _GS_C0
+    return u, 1.0 / (1.0 + torch.exp2(z * p))
+
+
+def gelu_sig(z):
+    return z * _gelu_sig_s(z)[1]
+
+
+def gelu_sig_d(z):
+    """d/dz gelu_sig as the kernels evaluate it: s (1 + z (1 - s) q(u)), q = d/dz [z poly(z^2)] = c0 + 3 c1 u + 5 c2 u^2 (kept beyond the clamp of u,
+    where s (1 - s) < 2e-12 has long vanished)"""
+    u, s = _gelu_sig_s(z)
+    q = ((5.0 * _GS_C2 * u + 3.0 * _GS_C1) * u + _GS_C0) * -_LN2
+    return s * (1.0 + z * (1.0 - s) * q)
+
+
+def _pad_heads(t, dim, hd, hdp):
+    """index j of `dim` -> (j / hd) * hdp + j % hd, the slots hd .. hdp - 1 of every head zero"""
+    if hd == hdp:
+        return t
+    shape = list(t.shape)
+    n = shape[dim]
+    assert n % hd == 0
+    t = t.unflatten(dim, (n // hd, hd))
+    pad = [0, 0] * (t.dim() - dim - 2) + [0, hdp - hd]
+    return F.pad(t, pad).flatten(dim, dim + 1)
+
+
+def pack_weight(w, groups=1, mode=0, rows_pad=None, Kw=None, hd_rows=1, hdp_rows=1, hd_cols=1, hdp_cols=1):
+    """PyTorch conv weight w [O, Ig, KH, KW] -> packed [groups, rows_pad, Kw] (the layout comment above pack_weight_multi_kernel):
+      mode 0: row = output channel of the group, column = (ky, kx, input channel)
+      mode 1: row = input channel of the group, column = (ky, kx, output channel) of the taps rotated by 180 degrees
+      mode 2: row = (ky, kx, input channel), column = output channel
+    rows / columns head-padded hd -> hdp (modes 0 / 1), then zero-filled up to rows_pad x Kw."""
+    O, Ig, KH, KW = w.shape
+    v = w.reshape(groups, O // groups, Ig, KH, KW)
+    if mode == 0:
+        m = v.permute(0, 1, 3, 4, 2)
+    elif mode == 1:
+        m = v.flip(3, 4).permute(0, 2, 3, 4, 1)
+    elif mode == 2:
+        m = v.permute(0, 3, 4, 2, 1).flatten(1, 3)
+    else:
+        raise ValueError(mode)
+    if mode != 2:
+        m = m.flatten(2)
+        m = _pad_heads(_pad_heads(m, 1, hd_rows, hdp_rows), 2, hd_cols, hdp_cols)
+    rows_pad, Kw = rows_pad or m.shape[1], Kw or m.shape[2]
+    out = torch.zeros(groups, rows_pad, Kw, dtype=w.dtype)
+    out[:, :m.shape[1], :m.shape[2]] = m
+    return out
+
+
+def gconv(h, w, groups, transposed=False):
+    """h NHWC [B,H,W,C], w [O, Ig, 3, 3]: the 3 x 3 / pad 1 convolution, or its transpose (the gradient with respect to its input) -> NHWC"""
+    f = F.conv_transpose2d if transposed else F.conv2d
+    return f(h.permute(0, 3, 1, 2), w, None, 1, 1, groups=groups).permute(0, 2, 3, 1)
+
+
+def stage1_block_forward(x, w1f, b1f, w2, w3, sa, sb, scale, rnd, h1_stored=None, h2_stored=None):
+    """The training forward of a stage-1 block as stage1_ring.hip MODE 3 stores it.  x [B,H,W,128]; w1f [256,128] / b1f [256]: conv1 with the BatchNorm folded;
+    w2 [256,32,3,3] (8 groups); w3 [128,256]; sa / sb [128]; scale [B] or None; every operand already rounded to its storage type.  h1 / h2 are rounded (rnd)
+    where they are stored and consumed rounded.  h1_stored / h2_stored: maps (the kernel's own, read back) that stand in for this function's h1 / h2 in
+    the stages behind them.  Returns the stored maps, the pre-activations z1 / z2 / the conv3 result acc3, and for the error bounds the sums of the
+    magnitudes of each dot product's terms (abs1 / abs2 / abs3)."""
+    B = x.shape[0]
+    z1 = x @ w1f.T + b1f
+    h1, g1 = rnd(gelu_sig(z1)), rnd(gelu_sig_d(z1))
+    h1u = h1 if h1_stored is None else h1_stored
+    z2 = gconv(h1u, w2, 8)
+    h2, g2 = rnd(gelu_sig(z2)), rnd(gelu_sig_d(z2))
+    h2u = h2 if h2_stored is None else h2_stored
+    acc3 = h2u @ w3.T
+    sc = torch.ones(B, dtype=x.dtype) if scale is None else scale
+    out = rnd(x + sc[:, None, None, None] * acc3)
+    return dict(xn=rnd(x * sa + sb), z1=z1, h1=h1, g1=g1, z2=z2, h2=h2, g2=g2, acc3=acc3, out=out, abs1=x.abs() @ w1f.abs().T,
+                abs2=gconv(h1u.abs(), w2.abs(), 8), abs3=h2u.abs() @ w3.abs().T)
+
+
+def stage1_block_dgrad(dz3, w3, w2, w1, g2, g1, rnd, dz2_stored=None, dz1_stored=None):
+    """The block's data-gradient chain as stage1_ring.hip MODE 2 stores it: dz2 = T((dz3 W3) * g2), dz1 = T(conv2^T(dz2) * g1), dxn = T(dz1 W1), with w3
+    [128,256], w2 [256,32,3,3], w1 [256,128] in the FORWARD layout (the kernel reads their transposed packs).  dz2_stored / dz1_stored as above."""
+    acc2 = dz3 @ w3
+    dz2 = rnd(acc2 * g2)
+    d2 = dz2 if dz2_stored is None else dz2_stored
+    acc1 = gconv(d2, w2, 8, transposed=True)
+    dz1 = rnd(acc1 * g1)
+    d1 = dz1 if dz1_stored is None else dz1_stored
+    acc0 = d1 @ w1
+    return dict(acc2=acc2, dz2=dz2, acc1=acc1, dz1=dz1, acc0=acc0, dxn=rnd(acc0), abs2=dz3.abs() @ w3.abs(), abs1=gconv(d2.abs(), w2.abs(), 8, transposed=True),
+                abs0=d1.abs() @ w1.abs())

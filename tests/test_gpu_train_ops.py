@@ -10,8 +10,11 @@ Launchers of train_kernels.h and where they are held:
   vit_assemble, vit_patch_rows, vit_cls_ln_fwd / _bwd                       test_vit_cls_ln_and_tokens
   gelu_fwd / gelu_bwd, add_scaled, avgpool_bwd, batch_sum, bcast_add,
   colsum, unpatch2, droppath_scales, fold_prenorm                           test_elementwise, test_batch_sum, test_small_ops
- covered elsewhere: launch_sgd* (test_gpu_train: SGD), launch_attention_bwd, launch_proto_head*_bwd, launch_wgrad_finalize*, launch_pack_weight*,
- launch_transpose_cols / launch_im2col_t (the weight-gradient operator tests of test_gpu_train.py); fill_f32 / scale_copy: test_small_ops.
+ covered elsewhere: launch_sgd* (test_gpu_train: SGD), launch_attention_bwd, launch_proto_head*_bwd (their operator tests in test_gpu_train.py);
+ launch_pack_weight_multi (modes 0 / 1 / 2, head padding, two-limb words, the 40-job table), the training epilogues of launch_conv_gemm / launch_gconv3x3
+ (y2, ACT_MUL, mul) and launch_stage1_ring_block_train / launch_stage1_ring_dgrad: test_gpu_train_conv_ops.py, same conventions; fill_f32 / scale_copy:
+ test_small_ops.  Reached only through whole train steps (the golden / oracle step tests of test_gpu_train.py, no operator entry): launch_patchk,
+ launch_im2col_t, launch_transpose_cols, launch_wgrad_finalize_multi.
 Storage types: fp32 and bf16.  train_kernels.hip is a single-build source (Makefile SINGLE): there is no f16 build of these kernels, the trainers take
 fp32 / bf16 / bf16x2 only, and the entries reject f16 (test_rejections) instead of reading f16 bits as bf16.
 
