@@ -137,6 +137,7 @@ SIGNATURES = {
     'fsvit_image_transform_rrc_gather': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _vp]),
     'fsvit_image_transform_rrc_u8': (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'fsvit_image_strong_weak': (_i, [_vp, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, _fp, _fp, _vp]),
+    'fsvit_image_rand_augment': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, C.POINTER(C.c_uint8), _vp]),
     'fsvit_attention_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     # operator entry points (tests, tools): the memory-bound training kernels one by one
     'fsvit_op_bn_reduce_blocks': (_i, [_i]),

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pil_bytes.h"
+
 namespace fsvit {
 
 constexpr int SW_S = 80, SW_PIX = SW_S * SW_S;             // the view is 80 x 80 (argument error otherwise)
@@ -26,19 +28,6 @@ struct StrongWeakParams {
   float mean[3], stdv[3];
   uint32_t seed_lo, seed_hi;
 };
-
-__device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }    // Convert.c L24
-
-// Blend.c ImagingBlend(degenerate d, image x, alpha): one fp32 multiply, one fp32 add, then truncation when 0 <= alpha <= 1, else clamp to [0, 255]
-// first.  Contraction is switched off: a fused multiply-add changes the truncation (and __fmul_rn / __fadd_rn are plain operators to this compiler,
-// which it would fuse).
-__device__ __forceinline__ int blend(int d, int x, float alpha, bool clamp) {
-#pragma clang fp contract(off)
-  const float prod = alpha * (float)(x - d);
-  float t = (float)d + prod;
-  if (clamp) t = t <= 0.0f ? 0.0f : (t >= 255.0f ? 255.0f : t);
-  return (int)t;
-}
 
 // Philox-4x32-10 (Salmon et al. 2011): counter (c0..c3), key (k0, k1) -> first two output words
 __device__ __forceinline__ uint2 philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
@@ -88,18 +77,7 @@ __global__ __launch_bounds__(256) void strong_weak_kernel(StrongWeakParams p) {
   __shared__ int red[4];
   const int t = threadIdx.x, b = blockIdx.x;
   const int32_t* row = p.table + (size_t)b * SWC_COLS;
-  {                                                        // [80][80][3] bytes (19 200, a multiple of 16) -> planes
-    const uint4* s4 = reinterpret_cast<const uint4*>(p.views + (size_t)b * 3 * SW_PIX);
-    for (int i = t; i < 3 * SW_PIX / 16; i += 256) {
-      const uint4 v = s4[i];
-      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int g = 16 * i + j, pix = g / 3, c = g - 3 * pix;
-        pa[c * SW_PIX + pix] = (unsigned char)(w[j >> 2] >> (8 * (j & 3)));
-      }
-    }
-  }
+  load_planes<SW_PIX>(p.views + (size_t)b * 3 * SW_PIX, pa, t);      // [80][80][3] bytes (19 200, a multiple of 16) -> planes
   for (int i = t; i < 768; i += 256) {
     const int c = i >> 8;
     const float v = (float)(i & 255) / 255.0f;                        // ToTensor
@@ -114,27 +92,7 @@ __global__ __launch_bounds__(256) void strong_weak_kernel(StrongWeakParams p) {
     for (int s = 0; s < 3; ++s) {
       const int op = row[SWC_ORDER + s];
       if (op < 0 || op > 2) continue;
-      const float alpha = __int_as_float(row[SWC_FACTOR + op]);
-      const bool clamp = !(alpha >= 0.0f && alpha <= 1.0f);
-      if (op == 0) {                                       // ImageEnhance.Brightness: degenerate = black
-        for (int i = t; i < 3 * SW_PIX; i += 256) pa[i] = (unsigned char)blend(0, pa[i], alpha, clamp);
-      } else if (op == 1) {                                // ImageEnhance.Contrast: degenerate = int(mean(L) + 0.5), the sum exact in int32
-        int sum = 0;
-        for (int i = t; i < SW_PIX; i += 256) sum += luma(pa[i], pa[SW_PIX + i], pa[2 * SW_PIX + i]);
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-        if ((t & 63) == 0) red[t >> 6] = sum;
-        __syncthreads();
-        const int d = (int)((double)(red[0] + red[1] + red[2] + red[3]) / (double)SW_PIX + 0.5);
-        __syncthreads();
-        for (int i = t; i < 3 * SW_PIX; i += 256) pa[i] = (unsigned char)blend(d, pa[i], alpha, clamp);
-      } else {                                             // ImageEnhance.Color: degenerate = L
-        for (int i = t; i < SW_PIX; i += 256) {
-          const int r = pa[i], g = pa[SW_PIX + i], bl = pa[2 * SW_PIX + i], l = luma(r, g, bl);
-          pa[i] = (unsigned char)blend(l, r, alpha, clamp);
-          pa[SW_PIX + i] = (unsigned char)blend(l, g, alpha, clamp);
-          pa[2 * SW_PIX + i] = (unsigned char)blend(l, bl, alpha, clamp);
-        }
-      }
+      enhance_planes<SW_PIX>(pa, op, __int_as_float(row[SWC_FACTOR + op]), red, t);      // 0 brightness, 1 contrast, 2 saturation = ENH_*
     }
     if (row[SWC_BLUR] != 0) {                              // ImageFilter.GaussianBlur: three box passes along x, then three along y
       int r = row[SWC_R];

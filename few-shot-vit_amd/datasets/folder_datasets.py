@@ -10,8 +10,9 @@ cifar_fs.py:25-108) on the device-resident data path.
   torchvision's Resize on a PIL image IS `Image.resize(..., BILINEAR)`), each image once, cached as uint8 [image_size, image_size, 3];
   a batch is stacked, uploaded and normalised on the GPU.  `gather(index)` is the batch interface the drivers use.
 
-'cifar-fs' also takes `augment='strongweak'`, the distillation phase's view pair, like the pickle datasets (image_datasets.py; the kernels take any
-source size) with the CIFAR mean / std; its `augment='resize'` and every augmentation of 'image-folder' are not built.  Class order: the reference enumerates
+'cifar-fs' also takes `augment='strongweak'`, the distillation phase's view pair (with `weak_randaug`), and `augment='randaug'`, the reference's
+`cropaug` pipeline under our own name, like the pickle datasets (image_datasets.py; the kernels take any source size) with the CIFAR mean / std
+and the fill colour made from that mean; its `augment='resize'` and every augmentation of 'image-folder' are not built.  Class order: the reference enumerates
 `os.listdir` (cifar-fs) / `sorted(os.listdir)` (image-folder); listdir order is file-system dependent, so cifar-fs sorts too - class
 identity never reaches the few-shot episode (labels are re-made per episode, utils/few_shot.py:11-16)."""
 import json
@@ -39,9 +40,9 @@ class CifarFS(_DeviceImageDataset):
     resize, crop = (80, 80), 80                 # transforms.Resize(80) on square 32 x 32 images (cifar_fs.py:70-76)
     mean, std = CIFAR_MEAN, CIFAR_STD
 
-    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, **kwargs):
-        if augment not in (None, 'strongweak'):
-            raise NotImplementedError("fsvit: augment=None and 'strongweak' are built ('resize' / 'cropaug' are not)")
+    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, **kwargs):
+        if augment not in (None, 'strongweak', 'randaug'):
+            raise NotImplementedError("fsvit: augment=None, 'strongweak' and 'randaug' are built ('resize' / 'cropaug' are not)")
         sub = {'train': 'meta-train', 'val': 'meta-val', 'test': 'meta-test'}.get(split)
         if sub is None:
             raise ValueError('Unkown setname.')                              # cifar_fs.py:42
@@ -56,7 +57,7 @@ class CifarFS(_DeviceImageDataset):
         if len(shapes) != 1:
             raise ValueError(f'cifar-fs: images of different sizes {sorted(shapes)} (expected 32 x 32 everywhere)')
         self.num_class = len(set(label))
-        self._finish(np.stack(data), label, device, augment, strong_prob)
+        self._finish(np.stack(data), label, device, augment, strong_prob, weak_randaug)
 
 
 @register('image-folder')

@@ -8,8 +8,12 @@ RandomHorizontalFlip on the GPU (fsvit_image_transform_rrc_gather), with `defaul
 Normalize; `ds.transform = ds.default_transform` switches the augmentation off.  `augment='strongweak'` (our name: the reference keys it on
 `split == 'train'`, sun_meta_training/datasets/mini_imagenet.py:160-163, :194-204) is the distillation phase's view pair on the GPU
 (transforms.DeviceStrongWeakPair: fsvit_image_transform_rrc_u8 + fsvit_image_strong_weak): `gather_pair(index)` -> (strong, weak),
-`__getitem__` -> (strong, weak, label), `strong_prob` (default 0.5) as in the reference's constructor; the weak view's RandomApply([RandAugment], p = 0.2) is not restated.  `'crop'` (padded RandomCrop) and
-`'cropaug'` (timm) are not built."""
+`__getitem__` -> (strong, weak, label), `strong_prob` (default 0.5) as in the reference's constructor; `weak_randaug` (default 0.0: off; the
+reference's value is 0.2) is the probability of the weak view's RandomApply([RandAugment], p), a third launch (fsvit_image_rand_augment) between
+the two.  `augment='randaug'` is the reference's `cropaug` pipeline under our own name (timm's create_transform: bicubic RandomResizedCrop + flip
+-> RandAugment 'rand-m9-mstd0.5-inc1' -> Normalize -> RandomErasing(0.25, 'pixel'); transforms.DeviceRandAugCrop), with the `default_transform` of
+`'resize'`; the RandAugment draw restates timm's published algorithm and is not pinned against timm, so the name `'cropaug'` itself stays
+refused, as does `'crop'` (padded RandomCrop)."""
 import os
 import pickle
 
@@ -17,13 +21,13 @@ import numpy as np
 import torch
 
 from .datasets import register
-from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandomResizedCrop, DeviceStrongWeakPair, DeviceTransform
+from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandAugCrop, DeviceRandomResizedCrop, DeviceStrongWeakPair, DeviceTransform
 
 
 class _DeviceImageDataset:
     resize, crop = (88, 88), 80
 
-    def _finish(self, data: np.ndarray, label, device, augment=None, strong_prob=0.5):
+    def _finish(self, data: np.ndarray, label, device, augment=None, strong_prob=0.5, weak_randaug=0.0):
         if data.dtype != np.uint8 or data.ndim != 4 or data.shape[-1] != 3:
             raise ValueError('expected uint8 images [N,H,W,3]')
         min_label = min(label)
@@ -38,7 +42,10 @@ class _DeviceImageDataset:
             self.transform = DeviceRandomResizedCrop(in_hw, self.crop, self.device, **norm)
         elif augment == 'strongweak':
             self.default_transform = DeviceTransform(in_hw, (self.crop, self.crop), self.crop, self.device, **norm)     # Resize(80)
-            self.transform = DeviceStrongWeakPair(in_hw, self.crop, self.device, strong_prob=strong_prob, **norm)
+            self.transform = DeviceStrongWeakPair(in_hw, self.crop, self.device, strong_prob=strong_prob, weak_randaug=weak_randaug, **norm)
+        elif augment == 'randaug':
+            self.default_transform = DeviceTransform(in_hw, (self.crop, self.crop), self.crop, self.device, **norm)     # Resize(80)
+            self.transform = DeviceRandAugCrop(in_hw, self.crop, self.device, **norm)
         else:
             self.default_transform = self.transform = DeviceTransform(in_hw, self.resize, self.crop, self.device, **norm)
 
@@ -80,22 +87,22 @@ class _DeviceImageDataset:
 class MiniImageNet(_DeviceImageDataset):
     resize, crop = (88, 88), 80                         # Resize((88, 88)) -> CenterCrop(80), mini_imagenet.py:49-52
 
-    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, **kwargs):
-        if augment not in (None, 'resize', 'strongweak'):
-            raise NotImplementedError("fsvit: augment=None, 'resize' and 'strongweak' are built ('crop' / 'cropaug' are not)")
+    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, **kwargs):
+        if augment not in (None, 'resize', 'strongweak', 'randaug'):
+            raise NotImplementedError("fsvit: augment=None, 'resize', 'strongweak' and 'randaug' are built ('crop' / 'cropaug' are not)")
         split_tag = 'train_phase_train' if split == 'train' else split
         with open(os.path.join(root_path, 'miniImageNet_category_split_{}.pickle'.format(split_tag)), 'rb') as f:
             pack = pickle.load(f, encoding='latin1')
-        self._finish(np.asarray(pack['data']), pack['labels'], device, augment, strong_prob)
+        self._finish(np.asarray(pack['data']), pack['labels'], device, augment, strong_prob, weak_randaug)
 
 
 @register('tiered-imagenet')
 class TieredImageNet(_DeviceImageDataset):
     resize, crop = (80, 80), 80                         # Resize(80) on square images, tiered_imagenet.py:53-57
 
-    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, strong_prob=0.5, **kwargs):
-        if augment not in (None, 'test', 'resize', 'strongweak'):       # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
-            raise NotImplementedError("fsvit: augment=None, 'test', 'resize' and 'strongweak' are built ('crop' / 'cropaug' are not)")
+    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, **kwargs):
+        if augment not in (None, 'test', 'resize', 'strongweak', 'randaug'):       # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
+            raise NotImplementedError("fsvit: augment=None, 'test', 'resize', 'strongweak' and 'randaug' are built ('crop' / 'cropaug' are not)")
         data = np.load(os.path.join(root_path, '{}_images.npz'.format(split)), allow_pickle=True)['images']
         data = data[:, :, :, ::-1]                      # BGR -> RGB, tiered_imagenet.py:21
         with open(os.path.join(root_path, '{}_labels.pkl'.format(split)), 'rb') as f:
@@ -115,4 +122,4 @@ class TieredImageNet(_DeviceImageDataset):
                     label_.append(ind[y])
                     cnt[y] += 1
             data, label = data[keep], label_
-        self._finish(np.ascontiguousarray(data), label, device, augment, strong_prob)
+        self._finish(np.ascontiguousarray(data), label, device, augment, strong_prob, weak_randaug)

@@ -300,11 +300,14 @@ class DeviceStrongWeakPair:
     """The distillation phase's view pair over uint8 images [N,H,W,3] resident on the GPU: weak = RandomResizedCrop(out, BICUBIC) ->
     RandomHorizontalFlip; strong = weak, or with probability strong_prob ColorJitter -> GaussianBlur -> Solarization -> RandomGrayscale of it; both
     ToTensor + Normalize, RandomErasing('pixel') on the strong one.  Two launches per batch (fsvit_image_transform_rrc_u8, fsvit_image_strong_weak),
-    bit-exact with Pillow up to the erase noise, which the kernel generates from `seed`.  NOT restated: the weak view's RandomApply([RandAugment],
-    p = 0.2).  All parameters are drawn on the host from this object's generator, or passed in; `params` keeps the last call's
-    {'boxes', 'flips', 'table', 'seed'}, and `tf(images, index, params=tf.params)` replays it."""
+    bit-exact with Pillow up to the erase noise, which the kernel generates from `seed`.  `weak_randaug` is the probability of the weak view's
+    RandomApply([RandAugment 'rand-m9-mstd0.5-inc1'], p) (the reference's 0.2; rand_augment_table): above 0 a third launch
+    (fsvit_image_rand_augment) augments the drawn images in place between the two, so that strong and weak are both made from the result; at the
+    default 0.0 nothing is drawn or launched for it.  All parameters are drawn on the host from this object's generator, or passed in; `params`
+    keeps the last call's {'boxes', 'flips', 'table', 'seed'} (and 'randaug': (slots, table) when weak_randaug > 0), and
+    `tf(images, index, params=tf.params)` replays it."""
 
-    def __init__(self, in_hw, out=80, device='cuda', mean=IMAGENET_MEAN, std=IMAGENET_STD, strong_prob=0.5, seed=0):
+    def __init__(self, in_hw, out=80, device='cuda', mean=IMAGENET_MEAN, std=IMAGENET_STD, strong_prob=0.5, seed=0, weak_randaug=0.0):
         import ctypes as C
         if int(out) != 80:
             raise NotImplementedError('fsvit: the strong / weak kernel is built for 80 x 80 views')
@@ -314,6 +317,10 @@ class DeviceStrongWeakPair:
         self.mean = (C.c_float * 3)(*mean)
         self.std = (C.c_float * 3)(*std)
         self.strong_prob = float(strong_prob)
+        self.weak_randaug = float(weak_randaug)
+        if not 0.0 <= self.weak_randaug <= 1.0:
+            raise ValueError('weak_randaug is a probability')
+        self.fill = (C.c_uint8 * 3)(*fill_colour(mean))
         self.generator = torch.Generator().manual_seed(int(seed))
         self.params = None
 
@@ -326,7 +333,10 @@ class DeviceStrongWeakPair:
         flips = torch.rand(n, generator=self.generator) < 0.5
         table = strong_weak_table(n, self.generator, self.strong_prob, self.out)
         seed = int(torch.randint(0, 1 << 62, (1,), generator=self.generator))
-        return {'boxes': boxes, 'flips': flips, 'table': table, 'seed': seed}
+        params = {'boxes': boxes, 'flips': flips, 'table': table, 'seed': seed}
+        if self.weak_randaug > 0:                                               # after every other draw: at 0 the stream is the one it always was
+            params['randaug'] = rand_augment_table(n, self.generator, self.weak_randaug, self.out)
+        return params
 
     @staticmethod
     def _checked_seed(seed):
@@ -337,7 +347,8 @@ class DeviceStrongWeakPair:
 
     def _checked(self, n, params):
         boxes, flips = _checked_boxes(n, params['boxes'], params['flips'], self.H, self.W)
-        return boxes, flips, _checked_table(n, params['table'], self.out), self._checked_seed(params['seed'])
+        randaug = _checked_randaug(n, *params['randaug']) if 'randaug' in params else None
+        return boxes, flips, _checked_table(n, params['table'], self.out), self._checked_seed(params['seed']), randaug
 
     def _images(self, images, hw):
         from ..engine import _require_cuda
@@ -347,7 +358,7 @@ class DeviceStrongWeakPair:
         if tuple(images.shape[1:3]) != tuple(hw):
             raise ValueError(f'images are {tuple(images.shape[1:3])}, expected {tuple(hw)}')
 
-    # the two launches, on arguments already validated
+    # the launches, on arguments already validated
     def _crop_u8(self, images, index, boxes, flips, code):
         from .. import _lib
         from ..engine import _ptr, _stream_ptr
@@ -374,6 +385,22 @@ class DeviceStrongWeakPair:
                 _stream_ptr(views.device)))
         return strong, weak
 
+    def _rand_augment(self, views, slots, table):
+        from .. import _lib
+        from ..engine import _ptr, _stream_ptr
+        slots_dev, table_dev = slots.to(views.device), table.to(views.device)
+        with torch.cuda.device(views.device):
+            _lib.check(_lib.load().fsvit_image_rand_augment(
+                _ptr(views), views.shape[0], self.out, self.out, _ptr(slots_dev), slots.numel(), _ptr(table_dev), RA_COLS, self.fill,
+                _stream_ptr(views.device)))
+        return views
+
+    def rand_augment(self, views, slots, table):
+        """RandAugment IN PLACE on uint8 views [B, 80, 80, 3] on the GPU: image slots[k] gets the two operations of table[k] -> views."""
+        slots, table = _checked_randaug(views.shape[0] if views.dim() == 4 else -1, slots, table)
+        self._images(views, (self.out, self.out))
+        return self._rand_augment(views, slots, table)
+
     def crop_u8(self, images, index, boxes, flips, filter='bicubic'):
         """Crop + Pillow resize (`filter`: 'bilinear' / 'bicubic') + flip -> uint8 [B, out, out, 3] on the GPU."""
         boxes, flips = _checked_boxes(index.numel(), boxes, flips, self.H, self.W)
@@ -392,7 +419,187 @@ class DeviceStrongWeakPair:
         B = index.numel()
         if params is None:
             params = self.draw(B)
-        boxes, flips, table, seed = self._checked(B, params)                   # once, on the host, before anything reaches the device
+        boxes, flips, table, seed, randaug = self._checked(B, params)          # once, on the host, before anything reaches the device
         self._images(images, (self.H, self.W))
         self.params = {'boxes': boxes, 'flips': flips.bool(), 'table': table, 'seed': seed}
-        return self._strong_weak(self._crop_u8(images, index, boxes, flips, FILTERS['bicubic'][0]), table, seed)
+        views = self._crop_u8(images, index, boxes, flips, FILTERS['bicubic'][0])
+        if randaug is not None:
+            self.params['randaug'] = randaug
+            self._rand_augment(views, *randaug)
+        return self._strong_weak(views, table, seed)
+
+
+# ---------------------------------------------------------------- RandAugment: the weak view's RandomApply([rand-m9-mstd0.5-inc1], p = 0.2)
+# (sun_meta_training/datasets/mini_imagenet.py:91-108) and the classifier phase's `cropaug` (sun_train_teacher/datasets/mini_imagenet.py, timm's
+# create_transform).  One int32 row per AUGMENTED image tells the kernel behind fsvit_image_rand_augment what to do: RA_SLOTS operation slots of
+# RA_OP_COLS columns each - a device operation code, one int32 argument (a table argument, or an enhance factor as float32 bits) and six float64
+# affine coefficients as twelve int32.  timm's fifteen named operations map onto the twelve device codes here, on the host.
+RA_SLOTS, RA_OP_COLS, RA_COLS = 2, 14, 28
+RA_CODE, RA_ARG, RA_COEF = 0, 1, 2
+(RA_NONE, RA_AFFINE, RA_INVERT, RA_POSTERIZE, RA_SOLARIZE, RA_SOLARIZE_ADD, RA_AUTOCONTRAST, RA_EQUALIZE, RA_COLOR, RA_CONTRAST, RA_BRIGHTNESS,
+ RA_SHARPNESS) = range(12)
+RA_FILL = tuple(min(255, round(255 * m)) for m in IMAGENET_MEAN)       # the reference's img_mean: (124, 116, 104)
+RAND_INCREASING_OPS = ('AutoContrast', 'Equalize', 'Invert', 'Rotate', 'PosterizeIncreasing', 'SolarizeIncreasing', 'SolarizeAdd', 'ColorIncreasing',
+                       'ContrastIncreasing', 'BrightnessIncreasing', 'SharpnessIncreasing', 'ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel')
+RA_SIGNED = frozenset(('Rotate', 'ColorIncreasing', 'ContrastIncreasing', 'BrightnessIncreasing', 'SharpnessIncreasing', 'ShearX', 'ShearY',
+                       'TranslateXRel', 'TranslateYRel'))
+_RA_ENHANCE = {'ColorIncreasing': RA_COLOR, 'ContrastIncreasing': RA_CONTRAST, 'BrightnessIncreasing': RA_BRIGHTNESS,
+               'SharpnessIncreasing': RA_SHARPNESS}
+_RA_TABLE_ARG = {RA_POSTERIZE: (0, 8), RA_SOLARIZE: (0, 256), RA_SOLARIZE_ADD: (0, 255)}       # inclusive argument ranges
+
+
+def fill_colour(mean):
+    """The reference's img_mean: min(255, round(255 * mean)) per channel."""
+    return tuple(min(255, int(round(255 * float(m)))) for m in mean)
+
+
+def rotate_matrix(degrees, w, h):
+    """The six AFFINE coefficients Pillow's Image.rotate(degrees) hands to Image.transform for a w x h image (centre (w/2, h/2), no expansion), or
+    None when degrees % 360 == 0, where Image.rotate returns a copy.  (Its transpose shortcuts at 90 / 180 / 270 are out of RandAugment's +-30.)"""
+    angle = degrees % 360.0
+    if angle == 0:
+        return None
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    cx, cy = w / 2.0, h / 2.0
+    m[2], m[5] = m[0] * -cx + m[1] * -cy + m[2], m[3] * -cx + m[4] * -cy + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def rand_augment_op(name, magnitude, negate=False, size=80, translate_pct=0.45):
+    """One operation slot (int32 [RA_OP_COLS]) for timm's operation `name` of the 'increasing' set at `magnitude` (0..10): timm's level maps
+    (auto_augment.py `_*_level_to_arg`) and the matrices its PIL calls build, in Python float64."""
+    m = float(magnitude) / 10.0
+    sign = -1.0 if negate else 1.0
+    code, arg, coef = RA_NONE, 0, None
+    if name == 'AutoContrast':
+        code = RA_AUTOCONTRAST
+    elif name == 'Equalize':
+        code = RA_EQUALIZE
+    elif name == 'Invert':
+        code = RA_INVERT
+    elif name == 'Rotate':
+        coef = rotate_matrix(sign * (m * 30.0), size, size)
+    elif name == 'PosterizeIncreasing':
+        code, arg = RA_POSTERIZE, 4 - int(m * 4)
+    elif name == 'SolarizeIncreasing':
+        code, arg = RA_SOLARIZE, 256 - int(m * 256)
+    elif name == 'SolarizeAdd':
+        code, arg = RA_SOLARIZE_ADD, min(128, int(m * 110))
+    elif name in _RA_ENHANCE:
+        code = _RA_ENHANCE[name]
+        arg = int(np.asarray([max(0.1, 1.0 + sign * (m * 0.9))], np.float32).view(np.int32)[0])
+    elif name == 'ShearX':
+        coef = (1, sign * (m * 0.3), 0, 0, 1, 0)
+    elif name == 'ShearY':
+        coef = (1, 0, 0, sign * (m * 0.3), 1, 0)
+    elif name == 'TranslateXRel':
+        coef = (1, 0, sign * (m * translate_pct) * size, 0, 1, 0)
+    elif name == 'TranslateYRel':
+        coef = (1, 0, 0, 0, 1, sign * (m * translate_pct) * size)
+    else:
+        raise ValueError(f'unknown RandAugment operation {name!r}')
+    op = np.zeros(RA_OP_COLS, np.int32)
+    if coef is not None:
+        code = RA_AFFINE
+        op[RA_COEF:RA_COEF + 12] = np.asarray(coef, np.float64).view(np.int32)
+    op[RA_CODE], op[RA_ARG] = code, arg
+    return op
+
+
+def rand_augment_draw(n, generator, apply_prob, magnitude=9, magnitude_std=0.5, num_layers=RA_SLOTS):
+    """The random part of rand_augment_table, a fixed number of draws per call: 'apply' [n] (RandomApply), and per layer 'op' (index into
+    RAND_INCREASING_OPS, uniform with replacement), 'on' (each operation's own probability 0.5), 'raw' (N(magnitude, magnitude_std)),
+    'magnitude' (raw clipped to [0, 10]) and 'negate' (the sign of the signed operations)."""
+    u = torch.rand(n, 1 + 2 * num_layers, generator=generator).double()
+    op = torch.randint(0, len(RAND_INCREASING_OPS), (n, num_layers), generator=generator)
+    raw = magnitude + magnitude_std * torch.randn(n, num_layers, generator=generator).double()
+    return {'apply': u[:, 0] < apply_prob, 'op': op, 'on': u[:, 1:1 + num_layers] < 0.5, 'negate': u[:, 1 + num_layers:] < 0.5, 'raw': raw,
+            'magnitude': raw.clamp(0.0, 10.0)}
+
+
+def rand_augment_table(n, generator, apply_prob, size=80, magnitude=9, magnitude_std=0.5, num_layers=RA_SLOTS, translate_pct=0.45):
+    """-> (slots int32 [k], table int32 [k, RA_COLS]): timm's RandAugment 'rand-m9-mstd0.5-inc1' drawn for n images.  With probability `apply_prob`
+    an image is augmented: `num_layers` operations uniform WITH replacement from the 15 of RAND_INCREASING_OPS, each applied with probability 0.5 at
+    its own magnitude clip(N(magnitude, magnitude_std), 0, 10), the signed ones negated with probability 0.5.  `slots` lists, strictly increasing,
+    the images with at least one applied operation; a skipped operation is an RA_NONE slot.  The fill colour of the geometric operations is not
+    part of the table: it goes with the call (fill_colour(mean), the reference's img_mean).
+
+    timm is neither in the reference tree nor installed here, so this is timm's published algorithm (auto_augment.py: RandAugment, AugmentOp,
+    `_RAND_INCREASING_TRANSFORMS`, the `_*_level_to_arg` maps) restated and its parity is UNPINNED: no test compares it with timm itself.  As
+    elsewhere in this file the distribution is what is restated, not timm's random stream."""
+    if num_layers != RA_SLOTS:
+        raise NotImplementedError(f'fsvit: the RandAugment kernel applies {RA_SLOTS} operation slots')
+    d = rand_augment_draw(n, generator, apply_prob, magnitude, magnitude_std, num_layers)
+    listed = (d['apply'][:, None] & d['on']).any(1).nonzero()[:, 0]
+    table = np.zeros((listed.numel(), RA_COLS), np.int32)
+    op, on, mag, neg = d['op'].tolist(), d['on'].tolist(), d['magnitude'].tolist(), d['negate'].tolist()
+    for k, b in enumerate(listed.tolist()):
+        for s in range(num_layers):
+            if on[b][s]:
+                table[k, s * RA_OP_COLS:(s + 1) * RA_OP_COLS] = rand_augment_op(RAND_INCREASING_OPS[op[b][s]], mag[b][s], neg[b][s], size, translate_pct)
+    return listed.to(torch.int32).contiguous(), torch.from_numpy(table)
+
+
+def _checked_randaug(n, slots, table):
+    """Host validation of a RandAugment (slots, table) pair for a batch of n images -> (int32 [k], int32 [k, RA_COLS])."""
+    slots, table = torch.as_tensor(slots).cpu(), torch.as_tensor(table).cpu()
+    if slots.dim() != 1 or slots.dtype != torch.int32:
+        raise ValueError(f'slots must be a 1-d int32 tensor, got {slots.dtype} {tuple(slots.shape)}')
+    k = slots.numel()
+    if table.dim() != 2 or tuple(table.shape) != (k, RA_COLS) or table.dtype != torch.int32:
+        raise ValueError(f'the RandAugment table must be int32 [{k}, {RA_COLS}], got {table.dtype} {tuple(table.shape)}')
+    s = slots.long()
+    if k and (int(s[0]) < 0 or int(s[-1]) >= n or bool((s[1:] <= s[:-1]).any())):
+        raise ValueError(f'slots must be strictly increasing image indices in [0, {n})')
+    ops = table.contiguous().view(k * RA_SLOTS, RA_OP_COLS)
+    code, arg = ops[:, RA_CODE].long(), ops[:, RA_ARG]
+    if bool(((code < RA_NONE) | (code > RA_SHARPNESS)).any()):
+        raise ValueError(f'operation codes must be in [{RA_NONE}, {RA_SHARPNESS}]')
+    coef = ops[:, RA_COEF:RA_COEF + 12].contiguous().view(torch.float64)[code == RA_AFFINE]
+    if not bool(torch.isfinite(coef).all()):
+        raise ValueError('affine coefficients must be finite')
+    f = arg.contiguous().view(torch.float32)[(code >= RA_COLOR) & (code <= RA_SHARPNESS)]
+    if not bool((torch.isfinite(f) & (f >= 0)).all()):
+        raise ValueError('enhance factors must be finite and non-negative')
+    for c, (lo, hi) in _RA_TABLE_ARG.items():
+        a = arg[code == c]
+        if bool(((a < lo) | (a > hi)).any()):
+            raise ValueError(f'the argument of operation code {c} must be in [{lo}, {hi}]')
+    return slots.contiguous(), table.contiguous()
+
+
+class DeviceRandAugCrop:
+    """The classifier phase's timm pipeline (the reference's `augment: cropaug`, sun_train_teacher/datasets/mini_imagenet.py: timm's
+    create_transform with auto_augment 'rand-m9-mstd0.5-inc1', which drops its colour jitter) over uint8 images [N,H,W,3] resident on the GPU:
+    RandomResizedCrop(out, BICUBIC) -> RandomHorizontalFlip -> RandAugment (always applied) -> ToTensor -> Normalize -> RandomErasing(0.25,
+    'pixel') -> float32 [B, 3, 80, 80].  It is the view pair's three launches with the strong flag 0 everywhere: the result is the pair's `strong`
+    output (the un-jittered view, erased); its `weak` store is made and dropped.  Same `draw` / `params` / replay surface as DeviceStrongWeakPair
+    (`pair`, which does the work)."""
+
+    def __init__(self, in_hw, out=80, device='cuda', mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0):
+        self.pair = DeviceStrongWeakPair(in_hw, out, device, mean, std, strong_prob=0.0, seed=seed, weak_randaug=1.0)
+        self.H, self.W, self.out, self.device = self.pair.H, self.pair.W, self.pair.out, self.pair.device
+        self.mean, self.std, self.fill, self.generator = self.pair.mean, self.pair.std, self.pair.fill, self.pair.generator
+
+    @property
+    def params(self):
+        return self.pair.params
+
+    def manual_seed(self, seed):
+        self.pair.manual_seed(seed)
+        return self
+
+    def draw(self, n):
+        params = self.pair.draw(n)
+        params['table'][:, SW_STRONG] = 0                                       # (u <= 0 has probability 2^-24 per image)
+        return params
+
+    def __call__(self, images: torch.Tensor, index: torch.Tensor, params=None) -> torch.Tensor:
+        if params is None:
+            params = self.draw(index.numel())
+        elif 'randaug' not in params:
+            raise ValueError("params needs 'randaug': (slots, table)")
+        return self.pair(images, index, params)[0]

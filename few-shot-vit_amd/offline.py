@@ -12,8 +12,9 @@ caller as in the reference.  Multi-GPU = one process per GPU (torchrun): every r
 statistics stay per replica (as under the reference's nn.DataParallel, :222-225) and the one exchange per step is the all-reduce (mean) of
 the flattened gradients over RCCL.  The strong / weak augmentation pair comes from a dataset made with `augment: strongweak` (one launch pair per
 batch on the GPU, datasets/transforms.py:DeviceStrongWeakPair; the reference keys it on `split: train`); with any other dataset the teacher sees
-the same image as the student unless the dataset returns three items.  Not restated: tensorboard, dataset visualisation, the weak view's
-RandAugment, `epoch_ex`.
+the same image as the student unless the dataset returns three items.  `weak_randaug: 0.2` next to it switches on the weak view's
+RandomApply([RandAugment], p = 0.2) (a third launch, fsvit_image_rand_augment; timm's algorithm restated, not pinned against timm; off by
+default).  Not restated: tensorboard, dataset visualisation, `epoch_ex`.
 
   python -m fewshot_vit_amd.offline --config few-shot-vit_amd/configs/offline_synthetic.yaml
 """

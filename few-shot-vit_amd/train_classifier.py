@@ -7,8 +7,10 @@ reference's schema.  The teacher of the distillation phase (`offline.py`, key `l
 
 MI355X-native: encoder forward / backward on the HIP trainer, Linear head, AdamW update and the few-shot evaluation on the HIP engine;
 multi-GPU = one process per GPU with one gradient all-reduce per step and rank-sharded few-shot episodes.  `train_dataset_args: {augment: resize}`
-(RandomResizedCrop + RandomHorizontalFlip, the reference's train_classifier_mini / _tiered configs) runs on the GPU, seeded with `seed` + rank.
-Not restated: tensorboard, dataset visualisation, the `cropaug` (timm) and `crop` augmentations.
+(RandomResizedCrop + RandomHorizontalFlip, the reference's train_classifier_mini / _tiered configs) runs on the GPU, seeded with `seed` + rank,
+and so does `{augment: randaug}`: the reference's `cropaug` pipeline (timm's create_transform: bicubic crop + flip -> RandAugment -> Normalize
+-> RandomErasing) under our own name, because its RandAugment draw restates timm's published algorithm without timm at hand to pin it.
+Not restated: tensorboard, dataset visualisation, the `crop` augmentation; the name `cropaug` itself stays refused.
 
   python -m fewshot_vit_amd.train_classifier --config few-shot-vit_amd/configs/train_classifier_synthetic.yaml
 """

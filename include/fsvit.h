@@ -426,7 +426,7 @@ int fsvit_image_transform_rrc_gather(const uint8_t* images_dev, int H, int W, co
 /* The same crop + resize + flip left as bytes: out_dev uint8 [B,OH,OW,3], filter 0 = Pillow BILINEAR (the bytes fsvit_image_transform_rrc_gather
  * normalises), 1 = Pillow BICUBIC (a = -0.5, support 2; negative taps, so the clip to 0..255 is live).  With filter 1 this is the weak view of the
  * distillation phase before ToTensor (sun_meta_training/datasets/mini_imagenet.py:100-102: RandomResizedCropAndInterpolation(80, 'bicubic') ->
- * RandomHorizontalFlip; its RandomApply([RandAugment], p = 0.2) is NOT restated). */
+ * RandomHorizontalFlip; its RandomApply([RandAugment], p = 0.2) is fsvit_image_rand_augment below, on these bytes in place). */
 int fsvit_image_transform_rrc_u8(const uint8_t* images_dev, int H, int W, const int64_t* index_dev, int B, const int32_t* box_dev,
                                  const uint8_t* flip_dev, int OH, int OW, int filter, uint8_t* out_dev, void* stream);
 /* The strong / weak pair of the distillation phase (mini_imagenet.py:110-124, :194-204) from uint8 weak views views_dev [B,80,80,3] (16-byte
@@ -439,6 +439,19 @@ int fsvit_image_transform_rrc_u8(const uint8_t* images_dev, int H, int W, const 
  *   height, width (height 0 = none).  Callers validate the rows; the kernel reads nothing outside its image whatever they hold. */
 int fsvit_image_strong_weak(const uint8_t* views_dev, int B, int H, int W, const int32_t* table_dev, int cols, const float* mean3_host,
                             const float* std3_host, uint64_t seed, float* weak_dev, float* strong_dev, void* stream);
+/* RandAugment (timm 'rand-m9-mstd0.5-inc1') in place on uint8 views views_dev [B,80,80,3] (16-byte aligned; H = W = 80 or argument error), between
+ * fsvit_image_transform_rrc_u8 and fsvit_image_strong_weak: the weak view's RandomApply([RandAugment], p = 0.2) of the distillation phase
+ * (sun_meta_training/datasets/mini_imagenet.py:91-108) and the RandAugment stage of the classifier phase's timm pipeline.  slots_dev int32
+ * [n_slots], strictly increasing image indices in [0, B): only these images are read and written, one workgroup each (n_slots <= B; n_slots = 0
+ * returns 0 without a launch).  table_dev int32 [n_slots, cols = 28]: two operation slots of 14 columns, applied in order -
+ *   0 code | 1 argument | 2-13 six float64 coefficients a0..a5 (low word first)
+ * with the codes 0 none, 1 affine (Image.transform(AFFINE, a, BICUBIC, fillcolor = fill3_host): shear, translate, rotate), 2 invert,
+ * 3 posterize (argument = bits kept, 0..8), 4 solarize (threshold 0..256), 5 solarize-add (addend 0..255, below 128), 6 autocontrast,
+ * 7 equalize, 8 color, 9 contrast, 10 brightness, 11 sharpness (ImageEnhance; argument = the factor as float32 bits).  Bit-exact with Pillow.
+ * The caller draws and validates the rows (datasets/transforms.py: rand_augment_table); the kernel touches nothing outside the batch whatever
+ * they hold. */
+int fsvit_image_rand_augment(uint8_t* views_dev, int B, int H, int W, const int32_t* slots_dev, int n_slots, const int32_t* table_dev, int cols,
+                             const uint8_t* fill3_host, void* stream);
 
 /* Operator level of the training path: attention backward (qkv, dctx -> dqkv; hd real / hdp padded head dim). */
 /* Weight gradient of a 3x3 / stride 1 / pad 1 convolution straight from the NHWC activations (no im2col, no transposed copies):
