@@ -92,15 +92,23 @@ SIGNATURES = {
     'fsvit_adamw_step': (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _f, _i, _vp]),
     'fsvit_adamw_step_multi': (_i, [_vp, _i, _sz, _f, _f, _f, _f, _f, _i, _vp]),
     'fsvit_proj_mlp_rows': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _vp]),
+    'fsvit_proj_mlp_rows_dt': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_ln_linear_rows': (_i, [_vp, _vp, _vp, _i, _fp, _i, _i, _i, _f, _vp]),
+    'fsvit_ln_linear_rows_dt': (_i, [_vp, _vp, _vp, _i, _fp, _i, _i, _i, _f, _i, _vp]),
     'fsvit_patch_embed2x2': (_i, [_vp, _vp, _vp, _i, _fp, _fp, _i, _i, _i, _i, _vp]),
+    'fsvit_patch_embed2x2_dt': (_i, [_vp, _vp, _vp, _i, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
     'fsvit_vit_block_tail': (_i, [_vp, _vp, _vp, _vp, _i, _i, _fp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _f, _vp]),
+    'fsvit_vit_block_tail_dt': (_i, [_vp, _vp, _vp, _vp, _i, _i, _fp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _f, _i, _vp]),
     'fsvit_mlp_rows': (_i, [_vp, _vp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _vp]),
+    'fsvit_mlp_rows_dt': (_i, [_vp, _vp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_attention': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     'fsvit_qkv_attention': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    'fsvit_qkv_attention_dt': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     'fsvit_vit_ln_qkv_attention': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    'fsvit_vit_ln_qkv_attention_dt': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     'fsvit_im2col27': (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_stem_conv1': (_i, [_fp, _vp, _i, _fp, _vp, _vp, _i, _i, _i, _vp]),
+    'fsvit_stem_conv1_dt': (_i, [_fp, _vp, _i, _fp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_maxpool2_pos': (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _i, _vp]),
     'fsvit_pool_affine': (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_visformer_trainer_create': (_i, [C.POINTER(VisformerCfg), _i, C.POINTER(_vp)]),

@@ -33,6 +33,7 @@ static inline bool known_dtype(int dtype) { return dtype >= FSVIT_F32 && dtype <
 static inline int kd(int dtype) { return (dtype == FSVIT_F32 || is_x2(dtype)) ? 0 : 1; }
 static inline int kg(int dtype) { return is_x2(dtype) ? 2 : kd(dtype); }
 static inline int storage_bytes(int dtype) { return kd(dtype) == 0 ? 4 : 2; }
+static inline bool half_dtype(int dtype) { return dtype == FSVIT_BF16 || dtype == FSVIT_F16; }
 
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -1146,16 +1147,27 @@ extern "C" int fsvit_conv1x1_wgrad(const void* x, const void* dz, float* dw, int
   return 0;
 }
 
+// The row-kernel operators below exist as NAME_dt(..., dtype, stream) for the two 16-bit storage types (FSVIT_BF16 / FSVIT_F16: the fsvit / fsvit_f16
+// builds of the same kernel) and, with the signature they always had, as NAME(..., stream) = NAME_dt(..., FSVIT_BF16, stream).
 extern "C" int fsvit_mlp_rows(const void* x, void* y, const void* w1, int k1w, const float* b1, const void* w2, int k2w, const float* b2,
                               int M, int C, int hid, void* stream) {
-  return fsvit_proj_mlp_rows(x, y, nullptr, nullptr, 0, 0, w1, k1w, b1, w2, k2w, b2, M, C, hid, stream);
+  return fsvit_proj_mlp_rows_dt(x, y, nullptr, nullptr, 0, 0, w1, k1w, b1, w2, k2w, b2, M, C, hid, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_mlp_rows_dt(const void* x, void* y, const void* w1, int k1w, const float* b1, const void* w2, int k2w, const float* b2,
+                                 int M, int C, int hid, int dtype, void* stream) {
+  return fsvit_proj_mlp_rows_dt(x, y, nullptr, nullptr, 0, 0, w1, k1w, b1, w2, k2w, b2, M, C, hid, dtype, stream);
 }
 
 extern "C" int fsvit_proj_mlp_rows(const void* x, void* y, const void* ctx, const void* wp, int kpw, int KC, const void* w1, int k1w, const float* b1,
                                    const void* w2, int k2w, const float* b2, int M, int C, int hid, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_proj_mlp_rows_dt(x, y, ctx, wp, kpw, KC, w1, k1w, b1, w2, k2w, b2, M, C, hid, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_proj_mlp_rows_dt(const void* x, void* y, const void* ctx, const void* wp, int kpw, int KC, const void* w1, int k1w, const float* b1,
+                                      const void* w2, int k2w, const float* b2, int M, int C, int hid, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_mlp_rows: 16-bit storage only (bf16 / f16)");
   if (!x || !y || !w1 || !w2) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!K(mlp_rows_supported)(1, C, hid)) return fail(FSVIT_ERR_ARG, "fsvit_mlp_rows: only C = 256 / hidden = 1024 and C = 512 / hidden = 2048 (bf16) are built");
+  if (!K(mlp_rows_supported)(1, C, hid)) return fail(FSVIT_ERR_ARG, "fsvit_mlp_rows: only C = 256 / hidden = 1024 and C = 512 / hidden = 2048 are built");
   if (k1w < C || k2w < hid) return fail(FSVIT_ERR_ARG, "weight rows shorter than K");
   if (ctx && (!wp || kpw < KC || !K(mlp_rows_proj_supported)(C, hid, KC))) return fail(FSVIT_ERR_ARG, "proj fusion: (C, KC) must be (256, 288) or (512, 576)");
   if (!ctx) KC = 0;
@@ -1177,9 +1189,14 @@ extern "C" int fsvit_proj_mlp_rows(const void* x, void* y, const void* ctx, cons
 // (fold gamma / beta into w1 / b1: W1 diag(gamma), b1 + W1 beta - what the engine's packer does).  Packs the weights on every call.
 extern "C" int fsvit_vit_block_tail(const void* x, void* y, const void* ctx, const void* wp, int kpw, int KC, const float* bp, const void* w1, int k1w,
                                     const float* b1, const void* w2, int k2w, const float* b2, int M, int C, int hid, float eps, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_vit_block_tail_dt(x, y, ctx, wp, kpw, KC, bp, w1, k1w, b1, w2, k2w, b2, M, C, hid, eps, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_vit_block_tail_dt(const void* x, void* y, const void* ctx, const void* wp, int kpw, int KC, const float* bp, const void* w1, int k1w,
+                                    const float* b1, const void* w2, int k2w, const float* b2, int M, int C, int hid, float eps, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_vit_block_tail: 16-bit storage only (bf16 / f16)");
   if (!x || !y || !ctx || !wp || !bp || !w1 || !b1 || !w2 || !b2) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!K(mlp_rows_ln_supported)(1, C, hid, KC)) return fail(FSVIT_ERR_ARG, "fsvit_vit_block_tail: only C = 384 / hidden = 1536 or 1152 / KC = 384 (bf16) is built");
+  if (!K(mlp_rows_ln_supported)(1, C, hid, KC)) return fail(FSVIT_ERR_ARG, "fsvit_vit_block_tail: only C = 384 / hidden = 1536 or 1152 / KC = 384 is built");
   if (k1w < C || k2w < hid || kpw < KC) return fail(FSVIT_ERR_ARG, "weight rows shorter than K");
   hipStream_t st = (hipStream_t)stream;
   void *img = nullptr, *b1i = nullptr;
@@ -1198,11 +1215,15 @@ extern "C" int fsvit_vit_block_tail(const void* x, void* y, const void* ctx, con
 // LayerNorm + Linear on token rows as one operator (the DeiT block's norm1 + qkv, deit.py:40-47,:69): y [M][N] = b + W LN(x), LN without affine
 // (gamma / beta folded into w / b by the caller).  bf16, C = 384, N a multiple of 32.  Packs the weights on every call.
 extern "C" int fsvit_ln_linear_rows(const void* x, void* y, const void* w, int kw, const float* b, int M, int C, int N, float eps, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_ln_linear_rows_dt(x, y, w, kw, b, M, C, N, eps, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_ln_linear_rows_dt(const void* x, void* y, const void* w, int kw, const float* b, int M, int C, int N, float eps, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_ln_linear_rows: 16-bit storage only (bf16 / f16)");
   if (!x || !y || !w || (!b && C != 512)) return fail(FSVIT_ERR_ARG, "null argument");
   const bool plain = C == 512;      // the Visformer stage-3 geometry runs the same kernel without the LayerNorm (eps ignored)
   if (!(plain ? K(gemm_rows_supported)(1, C, N) : K(ln_gemm_rows_supported)(1, C, N)) || kw < C)
-    return fail(FSVIT_ERR_ARG, "fsvit_ln_linear_rows: C = 384 (LayerNorm + Linear) or 512 (Linear only), N a multiple of 32, rows of at least C weights (bf16)");
+    return fail(FSVIT_ERR_ARG, "fsvit_ln_linear_rows: C = 384 (LayerNorm + Linear) or 512 (Linear only), N a multiple of 32, rows of at least C weights");
   hipStream_t st = (hipStream_t)stream;
   void* img = nullptr;
   HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(C, N)));
@@ -1219,9 +1240,14 @@ extern "C" int fsvit_ln_linear_rows(const void* x, void* y, const void* w, int k
 // pos fp32 [(H/2)^2][N]; y [B (H/2)^2][N].  Packs the weights on every call.
 extern "C" int fsvit_patch_embed2x2(const void* x, void* y, const void* w, int kw, const float* bias, const float* pos, int B, int H, int Ci, int N,
                                     void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_patch_embed2x2_dt(x, y, w, kw, bias, pos, B, H, Ci, N, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_patch_embed2x2_dt(const void* x, void* y, const void* w, int kw, const float* bias, const float* pos, int B, int H, int Ci, int N,
+                                       int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_patch_embed2x2: 16-bit storage only (bf16 / f16)");
   if (!x || !y || !w || !pos) return fail(FSVIT_ERR_ARG, "null argument");
-  if (!K(patch_embed_rows_supported)(1, Ci, H, N) || kw < 4 * Ci) return fail(FSVIT_ERR_ARG, "fsvit_patch_embed2x2: 4 Ci = 512, even H, N a multiple of 32 (bf16)");
+  if (!K(patch_embed_rows_supported)(1, Ci, H, N) || kw < 4 * Ci) return fail(FSVIT_ERR_ARG, "fsvit_patch_embed2x2: 4 Ci = 512, even H, N a multiple of 32");
   hipStream_t st = (hipStream_t)stream;
   void* img = nullptr;
   HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(4 * Ci, N)));
@@ -1289,13 +1315,18 @@ extern "C" int fsvit_adamw_step_multi(const void* items_dev, int n_items, size_t
 
 extern "C" int fsvit_qkv_attention(const void* x, const void* wqkv, int kw, const float* bias, void* ctx, int B, int S, int C, int heads, int hdp,
                                    float scale, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_qkv_attention_dt(x, wqkv, kw, bias, ctx, B, S, C, heads, hdp, scale, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_qkv_attention_dt(const void* x, const void* wqkv, int kw, const float* bias, void* ctx, int B, int S, int C, int heads, int hdp,
+                                   float scale, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_qkv_attention: 16-bit storage only (bf16 / f16)");
   if (!x || !wqkv || !ctx) return fail(FSVIT_ERR_ARG, "null argument");
   hipStream_t st = (hipStream_t)stream;
   void* img = nullptr;
   if (C == 512) {       // the rows kernel (stage-3 geometry: head dim padded to 96, maps of at most 32 tokens)
     if (!K(qkv_attn_rows_supported)(1, C, heads, hdp, S) || kw < C)
-      return fail(FSVIT_ERR_ARG, "fsvit_qkv_attention: C = 512 needs head dim 96 (padded) and S <= 32 (bf16)");
+      return fail(FSVIT_ERR_ARG, "fsvit_qkv_attention: C = 512 needs head dim 96 (padded) and S <= 32");
     HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp)));
     int rc = K(launch_qkv_attn_rows_pack)(wqkv, kw, img, C, heads, hdp, st);
     if (rc == 0) rc = K(launch_qkv_attn_rows)(x, ctx, img, bias, B, S, C, heads, hdp, scale, st);
@@ -1305,7 +1336,7 @@ extern "C" int fsvit_qkv_attention(const void* x, const void* wqkv, int kw, cons
     return 0;
   }
   if (!K(qkv_attn_supported)(1, C, heads, hdp, S) || kw < C)
-    return fail(FSVIT_ERR_ARG, "fsvit_qkv_attention: only C = 256, 6 heads x 48 (padded), S <= 112 (bf16) is built");
+    return fail(FSVIT_ERR_ARG, "fsvit_qkv_attention: only C = 256, 6 heads x 48 (padded), S <= 112 is built");
   HIP_TRY(hipMalloc(&img, K(qkv_attn_image_bytes)()));
   int rc = K(launch_qkv_attn_pack)(wqkv, kw, img, st);
   if (rc == 0) rc = K(launch_qkv_attn)(x, ctx, img, bias, B, S, scale, st);
@@ -1317,10 +1348,15 @@ extern "C" int fsvit_qkv_attention(const void* x, const void* wqkv, int kw, cons
 
 extern "C" int fsvit_vit_ln_qkv_attention(const void* x, const void* wqkv, int kw, const float* bias, void* ctx, int B, int S, int C, int heads, int hdp,
                                           float eps, float scale, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_vit_ln_qkv_attention_dt(x, wqkv, kw, bias, ctx, B, S, C, heads, hdp, eps, scale, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_vit_ln_qkv_attention_dt(const void* x, const void* wqkv, int kw, const float* bias, void* ctx, int B, int S, int C, int heads, int hdp,
+                                          float eps, float scale, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_vit_ln_qkv_attention: 16-bit storage only (bf16 / f16)");
   if (!x || !wqkv || !ctx) return fail(FSVIT_ERR_ARG, "null argument");
   if (!K(vit_attn_rows_supported)(1, C, heads, hdp, S) || kw < C)
-    return fail(FSVIT_ERR_ARG, "fsvit_vit_ln_qkv_attention: built for C = 384, head dim 64, S <= 256 (bf16)");
+    return fail(FSVIT_ERR_ARG, "fsvit_vit_ln_qkv_attention: built for C = 384, head dim 64, S <= 256");
   hipStream_t st = (hipStream_t)stream;
   void* img = nullptr;
   HIP_TRY(hipMalloc(&img, K(ln_gemm_rows_image_bytes)(C, 3 * heads * hdp)));
@@ -1350,9 +1386,13 @@ extern "C" int fsvit_im2col27(const float* x, void* out, int B, int H, int W, in
 }
 
 extern "C" int fsvit_stem_conv1(const float* x, const void* w, int kw, const float* bias, void* patches, void* c1, int B, int H, int W, void* stream) {
-  const int kdt = FSVIT_BF16;
+  return fsvit_stem_conv1_dt(x, w, kw, bias, patches, c1, B, H, W, FSVIT_BF16, stream);
+}
+extern "C" int fsvit_stem_conv1_dt(const float* x, const void* w, int kw, const float* bias, void* patches, void* c1, int B, int H, int W, int dtype, void* stream) {
+  const int kdt = dtype;
+  if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_stem_conv1: 16-bit storage only (bf16 / f16)");
   if (!x || !w || !patches || !c1 || kw < 32) return fail(FSVIT_ERR_ARG, "bad argument");
-  if (H != W || !K(stem_conv1_supported)(1, H, 64)) return fail(FSVIT_ERR_ARG, "fsvit_stem_conv1: only 80x80 images, 64 output channels (bf16) are built");
+  if (H != W || !K(stem_conv1_supported)(1, H, 64)) return fail(FSVIT_ERR_ARG, "fsvit_stem_conv1: only 80x80 images, 64 output channels are built");
   RC_TRY(K(launch_stem_conv1)(x, patches, c1, w, kw, bias, B, (hipStream_t)stream, 0));
   return 0;
 }

@@ -451,7 +451,8 @@ class LvvitEngine(_EncoderEngine):
 
 
 class ops:
-    """Operator-level entry points (storage dtype follows the input tensors: fp32 or bf16)."""
+    """Operator-level entry points (storage dtype follows the input tensors: fp32, bf16 or fp16; the fused row operators take the two 16-bit types
+    only, activations and weights of the same one)."""
     _sgd_tables = {}
 
     @staticmethod
@@ -463,6 +464,26 @@ class ops:
         if t.dtype == torch.float16:
             return _lib.F16
         raise TypeError(t.dtype)
+
+    @staticmethod
+    def _dt16(x, *weights):
+        """Storage dtype of a fused row operator: x bf16 or fp16 (TypeError otherwise), every 16-bit tensor in `weights` of the same type."""
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError(f'16-bit activations only (torch.bfloat16 / torch.float16), got {x.dtype}')
+        for w in weights:
+            if w is not None and w.dtype != x.dtype:
+                raise TypeError(f'activations are {x.dtype} but a weight / activation operand is {w.dtype}')
+        return ops._dt(x)
+
+    @staticmethod
+    def _out(out, x, N):
+        """The [M][N] result of a row operator on x [M][.]: a fresh tensor, or the caller's `out` (contiguous, x's dtype and device; `out is x` runs the
+        Mlp operators in place, as the engines do)."""
+        if out is None:
+            return torch.empty(x.shape[0], N, device=x.device, dtype=x.dtype)
+        if out.dtype != x.dtype or out.device != x.device or tuple(out.shape) != (x.shape[0], N) or not out.is_contiguous():
+            raise ValueError(f'out must be a contiguous [{x.shape[0]}, {N}] {x.dtype} tensor on {x.device}')
+        return out
 
     @staticmethod
     def x2_limbs(w: torch.Tensor, numerics: str) -> torch.Tensor:
@@ -650,26 +671,28 @@ class ops:
                                                   float(weight_decay), int(step), _stream_ptr(dev)))
 
     @staticmethod
-    def proj_mlp_rows(x, ctx, wp, w1, b1, w2, b2=None):
+    def proj_mlp_rows(x, ctx, wp, w1, b1, w2, b2=None, out=None):
         """x [M][C], ctx [M][KC] bf16, wp [C][KpW]: x1 = x + ctx wp^T; y = x1 + W2 GELU(W1 x1 + b1) + b2  ((C, KC) = (256, 288) | (512, 576))."""
         _require_cuda(x, ctx, wp, w1, w2)
+        dt = ops._dt16(x, ctx, wp, w1, w2)
         lib = _lib.load()
-        y = torch.empty_like(x)
+        y = ops._out(out, x, x.shape[1])
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_proj_mlp_rows(_ptr(x), _ptr(y), _ptr(ctx), _ptr(wp), wp.shape[-1], ctx.shape[1], _ptr(w1), w1.shape[-1], _ptr(b1),
-                                               _ptr(w2), w2.shape[-1], _ptr(b2), x.shape[0], x.shape[1], w1.shape[0], _stream_ptr(x.device)))
+            _lib.check(lib.fsvit_proj_mlp_rows_dt(_ptr(x), _ptr(y), _ptr(ctx), _ptr(wp), wp.shape[-1], ctx.shape[1], _ptr(w1), w1.shape[-1], _ptr(b1),
+                                                  _ptr(w2), w2.shape[-1], _ptr(b2), x.shape[0], x.shape[1], w1.shape[0], dt, _stream_ptr(x.device)))
         return y
 
     @staticmethod
-    def ln_linear_rows(x, w, b, eps=1e-6):
+    def ln_linear_rows(x, w, b, eps=1e-6, out=None):
         """y = b + LN(x) w^T on bf16 rows (x [M][384], w [N][>=384], N % 32 == 0): the DeiT block's norm1 + qkv (deit.py:40-47,:69), LN without
         affine (gamma / beta folded into w / b by the caller).  x [M][512]: the same row-wise kernel without the LayerNorm (Visformer stage-3
         qkv, visformer.py:175), b may be None."""
         _require_cuda(x, w)
-        y = torch.empty(x.shape[0], w.shape[0], device=x.device, dtype=x.dtype)
+        dt = ops._dt16(x, w)
+        y = ops._out(out, x, w.shape[0])
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().fsvit_ln_linear_rows(_ptr(x), _ptr(y), _ptr(w), w.shape[-1], _ptr(b), x.shape[0], x.shape[1], w.shape[0], float(eps),
-                                                        _stream_ptr(x.device)))
+            _lib.check(_lib.load().fsvit_ln_linear_rows_dt(_ptr(x), _ptr(y), _ptr(w), w.shape[-1], _ptr(b), x.shape[0], x.shape[1], w.shape[0], float(eps),
+                                                           dt, _stream_ptr(x.device)))
         return y
 
     @staticmethod
@@ -677,35 +700,38 @@ class ops:
         """Visformer PatchEmbed (conv k2 s2 with folded BN, + pos_embed; visformer.py:266-288) on the row-wise kernel: x NHWC bf16 [B, H, H, Ci]
         (4 Ci = 512), w [N, 4 Ci] in (ky, kx, c) order, bias [N] or None, pos fp32 [(H/2)^2, N] -> [B (H/2)^2, N]."""
         _require_cuda(x, w, pos)
+        dt = ops._dt16(x, w)
         B, H, _, Ci = x.shape
         y = torch.empty(B * (H // 2) * (H // 2), w.shape[0], device=x.device, dtype=x.dtype)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().fsvit_patch_embed2x2(_ptr(x), _ptr(y), _ptr(w), w.shape[-1], _ptr(bias), _ptr(pos), B, H, Ci, w.shape[0],
-                                                        _stream_ptr(x.device)))
+            _lib.check(_lib.load().fsvit_patch_embed2x2_dt(_ptr(x), _ptr(y), _ptr(w), w.shape[-1], _ptr(bias), _ptr(pos), B, H, Ci, w.shape[0],
+                                                           dt, _stream_ptr(x.device)))
         return y
 
     @staticmethod
-    def vit_block_tail(x, ctx, wp, bp, w1, b1, w2, b2, eps=1e-6):
+    def vit_block_tail(x, ctx, wp, bp, w1, b1, w2, b2, eps=1e-6, out=None):
         """DeiT block tail (deit.py:69-72) on bf16 rows, (C, KC, hidden) = (384, 384, 1536): x1 = x + bp + ctx wp^T;
         y = x1 + b2 + W2 GELU(W1 LN(x1) + b1), LN without affine (norm2's gamma / beta folded into w1 / b1 by the caller)."""
         _require_cuda(x, ctx, wp, bp, w1, b1, w2, b2)
+        dt = ops._dt16(x, ctx, wp, w1, w2)
         lib = _lib.load()
-        y = torch.empty_like(x)
+        y = ops._out(out, x, x.shape[1])
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_vit_block_tail(_ptr(x), _ptr(y), _ptr(ctx), _ptr(wp), wp.shape[-1], ctx.shape[1], _ptr(bp), _ptr(w1), w1.shape[-1],
-                                                _ptr(b1), _ptr(w2), w2.shape[-1], _ptr(b2), x.shape[0], x.shape[1], w1.shape[0], float(eps),
-                                                _stream_ptr(x.device)))
+            _lib.check(lib.fsvit_vit_block_tail_dt(_ptr(x), _ptr(y), _ptr(ctx), _ptr(wp), wp.shape[-1], ctx.shape[1], _ptr(bp), _ptr(w1), w1.shape[-1],
+                                                   _ptr(b1), _ptr(w2), w2.shape[-1], _ptr(b2), x.shape[0], x.shape[1], w1.shape[0], float(eps),
+                                                   dt, _stream_ptr(x.device)))
         return y
 
     @staticmethod
-    def mlp_rows(x, w1, b1, w2, b2=None):
-        """x [M][C] bf16, C = 256 or 512; w1 [4C][K1w], w2 [C][K2w] packed K-major bf16; b1 [4C], b2 [C] fp32 or None.  y = x + W2 GELU(W1 x + b1) + b2."""
+    def mlp_rows(x, w1, b1, w2, b2=None, out=None):
+        """x [M][C] bf16 / fp16, C = 256 or 512; w1 [4C][K1w], w2 [C][K2w] packed K-major, same type; b1 [4C], b2 [C] fp32 or None.  y = x + W2 GELU(W1 x + b1) + b2."""
         _require_cuda(x, w1, w2)
+        dt = ops._dt16(x, w1, w2)
         lib = _lib.load()
-        y = torch.empty_like(x)
+        y = ops._out(out, x, x.shape[1])
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_mlp_rows(_ptr(x), _ptr(y), _ptr(w1), w1.shape[-1], _ptr(b1), _ptr(w2), w2.shape[-1], _ptr(b2),
-                                          x.shape[0], x.shape[1], w1.shape[0], _stream_ptr(x.device)))
+            _lib.check(lib.fsvit_mlp_rows_dt(_ptr(x), _ptr(y), _ptr(w1), w1.shape[-1], _ptr(b1), _ptr(w2), w2.shape[-1], _ptr(b2),
+                                             x.shape[0], x.shape[1], w1.shape[0], dt, _stream_ptr(x.device)))
         return y
 
     @staticmethod
@@ -720,12 +746,13 @@ class ops:
     @staticmethod
     def qkv_attention(x, wqkv, bias, B, S, heads, hdp, scale):
         """Fused qkv conv + attention core (qkv_attn.hip): x [B*S, C] bf16, wqkv [3*heads*hdp, kw] bf16 -> ctx [B*S, heads*hdp]."""
-        _require_cuda(x)
+        _require_cuda(x, wqkv)
+        dt = ops._dt16(x, wqkv)
         lib = _lib.load()
         ctx = torch.empty(B * S, heads * hdp, dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_qkv_attention(_ptr(x), _ptr(wqkv), wqkv.shape[-1], _ptr(bias), _ptr(ctx), B, S, x.shape[1], heads, hdp,
-                                               float(scale), _stream_ptr(x.device)))
+            _lib.check(lib.fsvit_qkv_attention_dt(_ptr(x), _ptr(wqkv), wqkv.shape[-1], _ptr(bias), _ptr(ctx), B, S, x.shape[1], heads, hdp,
+                                                  float(scale), dt, _stream_ptr(x.device)))
         return ctx
 
     @staticmethod
@@ -733,10 +760,11 @@ class ops:
         """norm1 + qkv Linear + attention core of a ViT block in one launch (mlp_rows.hip vit_attn_rows): x [B*S, 384] bf16, wqkv [3*heads*64, kw]
         bf16 (LayerNorm affine folded in by the caller) -> ctx [B*S, heads*64]."""
         _require_cuda(x, wqkv)
+        dt = ops._dt16(x, wqkv)
         ctx = torch.empty(B * S, heads * hdp, dtype=x.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.load().fsvit_vit_ln_qkv_attention(_ptr(x), _ptr(wqkv), wqkv.shape[-1], _ptr(bias), _ptr(ctx), B, S, x.shape[1], heads, hdp,
-                                                              float(eps), float(scale), _stream_ptr(x.device)))
+            _lib.check(_lib.load().fsvit_vit_ln_qkv_attention_dt(_ptr(x), _ptr(wqkv), wqkv.shape[-1], _ptr(bias), _ptr(ctx), B, S, x.shape[1], heads, hdp,
+                                                                 float(eps), float(scale), dt, _stream_ptr(x.device)))
         return ctx
 
     @staticmethod
@@ -753,12 +781,16 @@ class ops:
     def stem_conv1(x, w, bias):
         """im2col + stem conv1 + LeakyReLU in one pass (stem.hip): x [B,3,80,80] fp32, w [64, kw] bf16 -> (patches [B*1600,32], c1 [B*1600,64])."""
         _require_cuda(x, w)
+        if x.dtype != torch.float32:
+            raise TypeError(f'stem_conv1 reads the fp32 image, got {x.dtype}')
+        dt = ops._dt16(w)
         lib = _lib.load()
         B, _, H, W = x.shape
         patches = torch.empty(B * (H // 2) * (W // 2), 32, dtype=w.dtype, device=x.device)
         c1 = torch.empty(B * (H // 2) * (W // 2), 64, dtype=w.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_stem_conv1(_ptr(x.contiguous()), _ptr(w), w.shape[-1], _ptr(bias), _ptr(patches), _ptr(c1), B, H, W, _stream_ptr(x.device)))
+            _lib.check(lib.fsvit_stem_conv1_dt(_ptr(x.contiguous()), _ptr(w), w.shape[-1], _ptr(bias), _ptr(patches), _ptr(c1), B, H, W, dt,
+                                               _stream_ptr(x.device)))
         return patches, c1
 
     @staticmethod

@@ -247,6 +247,25 @@ int fsvit_ln_linear_rows(const void* x_dev, void* y_dev, const void* w_dev, int 
  * or NULL, pos fp32 [(H/2)^2][N]; y [B (H/2)^2][N] bf16. */
 int fsvit_patch_embed2x2(const void* x_dev, void* y_dev, const void* w_dev, int kw, const float* bias_dev, const float* pos_dev, int B, int H, int Ci,
                          int N, void* stream);
+/* The row-kernel operators with the storage type spelled out: NAME_dt(..., dtype, stream) runs the bf16 (FSVIT_BF16) or the fp16 (FSVIT_F16) build of
+ * NAME's kernel on tensors of that type; any other dtype is FSVIT_ERR_ARG.  NAME(..., stream) above / below is NAME_dt(..., FSVIT_BF16, stream). */
+int fsvit_mlp_rows_dt(const void* x_dev, void* y_dev, const void* w1_dev, int k1w, const float* b1_dev, const void* w2_dev, int k2w,
+                      const float* b2_dev, int M, int C, int hid, int dtype, void* stream);
+int fsvit_proj_mlp_rows_dt(const void* x_dev, void* y_dev, const void* ctx_dev, const void* wp_dev, int kpw, int KC, const void* w1_dev, int k1w,
+                           const float* b1_dev, const void* w2_dev, int k2w, const float* b2_dev, int M, int C, int hid, int dtype, void* stream);
+int fsvit_vit_block_tail_dt(const void* x_dev, void* y_dev, const void* ctx_dev, const void* wp_dev, int kpw, int KC, const float* bp_dev,
+                            const void* w1_dev, int k1w, const float* b1_dev, const void* w2_dev, int k2w, const float* b2_dev, int M, int C, int hid,
+                            float eps, int dtype, void* stream);
+int fsvit_ln_linear_rows_dt(const void* x_dev, void* y_dev, const void* w_dev, int kw, const float* b_dev, int M, int C, int N, float eps, int dtype,
+                            void* stream);
+int fsvit_patch_embed2x2_dt(const void* x_dev, void* y_dev, const void* w_dev, int kw, const float* bias_dev, const float* pos_dev, int B, int H, int Ci,
+                            int N, int dtype, void* stream);
+int fsvit_qkv_attention_dt(const void* x_dev, const void* wqkv_dev, int kw, const float* bias_dev, void* ctx_dev, int B, int S, int C,
+                           int heads, int hdp, float scale, int dtype, void* stream);
+int fsvit_vit_ln_qkv_attention_dt(const void* x_dev, const void* wqkv_dev, int kw, const float* bias_dev, void* ctx_dev, int B, int S, int C,
+                                  int heads, int hdp, float eps, float scale, int dtype, void* stream);
+int fsvit_stem_conv1_dt(const float* x_nchw_dev, const void* w_dev, int kw, const float* bias_dev, void* patches_dev, void* c1_dev,
+                        int B, int H, int W, int dtype, void* stream);
 /* ---------------------------------------------------------------- distillation head
  * Replaces, for sun_meta_training/offline.py: `LinearClassifier.forward` / its autograd (models/classifier.py:27-34) as used by
  * `TokenLabelOffline` (models/token_label.py:36-60) on the 25 tokens and on the pooled feature, `generate_softlabel`
