@@ -102,6 +102,7 @@ SIGNATURES = {
     'fsvit_mlp_rows': (_i, [_vp, _vp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _vp]),
     'fsvit_mlp_rows_dt': (_i, [_vp, _vp, _vp, _i, _fp, _vp, _i, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_attention': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    'fsvit_op_attention_route': (_i, [_i, _i, _i]),
     'fsvit_qkv_attention': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     'fsvit_qkv_attention_dt': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     'fsvit_vit_ln_qkv_attention': (_i, [_vp, _vp, _i, _fp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp]),
@@ -147,6 +148,7 @@ SIGNATURES = {
     'fsvit_image_strong_weak': (_i, [_vp, _i, _i, _i, _vp, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, _fp, _fp, _vp]),
     'fsvit_image_rand_augment': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, C.POINTER(C.c_uint8), _vp]),
     'fsvit_attention_backward': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    'fsvit_op_attention_bwd_route': (_i, [_i, _i, _i, _i]),
     # operator entry points (tests, tools): the memory-bound training kernels one by one
     'fsvit_op_bn_reduce_blocks': (_i, [_i]),
     'fsvit_op_ln_bwd_blocks': (_i, [_i]),

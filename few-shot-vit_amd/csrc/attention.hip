@@ -85,14 +85,18 @@ __global__ __launch_bounds__(256) void attention_kernel(const T* __restrict__ qk
 
   // ---- phase 2: scores[q][k] = scale * <Q[q], K[k]>
   const int nt = g.SP / 16;
-  const int nkc = hdp * ES / 64;
+  const int nkc = (hdp * ES + 63) / 64;               // 16-bit rows of an odd multiple of 16 (80, 112) end in a half chunk: its upper two 16-byte
+  const bool half_tail = (hdp * ES) % 64 != 0;        // slots lie past the row and enter as zeros (hdp * ES / 64 dropped the head dims 64 .. 79 of hdp = 80)
   for (int id = wave; id < nt * nt; id += 4) {
     const int qt = id / nt, kt = id - qt * nt;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     const unsigned char* qa = Qs + (qt * 16 + lrow) * g.qs + lq * 16;
     const unsigned char* ka = Ks + (kt * 16 + lrow) * g.qs + lq * 16;
-    for (int kc = 0; kc < nkc; ++kc)
-      acc = mma_chunk<T>(*reinterpret_cast<const u32x4*>(qa + kc * 64), *reinterpret_cast<const u32x4*>(ka + kc * 64), acc);
+    for (int kc = 0; kc < nkc; ++kc) {
+      const bool past = half_tail && kc + 1 == nkc && lq >= 2;
+      const u32x4 qf = past ? zero4 : *reinterpret_cast<const u32x4*>(qa + kc * 64), kf = past ? zero4 : *reinterpret_cast<const u32x4*>(ka + kc * 64);
+      acc = mma_chunk<T>(qf, kf, acc);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       *reinterpret_cast<float*>(Ss + (qt * 16 + lq * 4 + r) * g.ss + (kt * 16 + lrow) * 4) = acc[r] * scale;
@@ -321,21 +325,31 @@ __global__ __launch_bounds__(NW * 64) void attention_v2_kernel(const T* __restri
   }
 }
 
+// LDS image of attention_v2_kernel: K rows at the kernel's stride + V^T (es = bytes per stored element)
+static constexpr size_t v2_lds_bytes(int es, int nkt, int ndt) {
+  const int qsb = ndt * 16 * es + ((32 - (ndt * 16 * es) % 64 + 64) % 64);      // the kernel's K row stride
+  return (size_t)nkt * 16 * qsb + (size_t)ndt * 16 * (nkt * 16 * es + 16);
+}
+constexpr size_t kAttnLdsMax = 160 * 1024;
+
+// -1: the instantiation's image does not fit the LDS (fp32 rows, 13 key tiles, head dims 96 and 128: 164 / 217 KB) - it is not built, and
+// attention_route never names it (these shapes used to end in a bare hipErrorInvalidValue from hipFuncSetAttribute)
 template <typename T, int NKT, int NDT, int NW>
 static int launch_v2(const void* qkv, void* ctx, int B, int S, int heads, float scale, hipStream_t s) {
-  constexpr int ES = sizeof(T);
-  constexpr int QSB = NDT * 16 * ES + ((32 - (NDT * 16 * ES) % 64 + 64) % 64);      // the kernel's K row stride
-  const size_t lds = (size_t)NKT * 16 * QSB + (size_t)NDT * 16 * (NKT * 16 * ES + 16);
-  auto kern = attention_v2_kernel<T, NKT, NDT, NW>;
-  if (lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
+  constexpr size_t lds = v2_lds_bytes(sizeof(T), NKT, NDT);
+  if constexpr (lds > kAttnLdsMax) return -1;
+  else {
+    auto kern = attention_v2_kernel<T, NKT, NDT, NW>;
+    if (lds > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kern, dim3(B * heads), dim3(NW * 64), lds, s, (const T*)qkv, (T*)ctx, S, heads, scale);
+    return (int)hipGetLastError();
   }
-  hipLaunchKernelGGL(kern, dim3(B * heads), dim3(NW * 64), lds, s, (const T*)qkv, (T*)ctx, S, heads, scale);
-  return (int)hipGetLastError();
 }
 
-// returns -1 when no v2 instantiation covers the shape (caller falls back to the generic v1 kernel)
+// the instantiations of one (element type, key tiles): -1 when ndt has none (v2_has_ndt restates this list for attention_route)
 template <typename T, int NKT, int NW>
 static int dispatch_ndt(int ndt, const void* qkv, void* ctx, int B, int S, int heads, float scale, hipStream_t s) {
   switch (ndt) {
@@ -350,33 +364,46 @@ static int dispatch_ndt(int ndt, const void* qkv, void* ctx, int B, int S, int h
   }
 }
 
-static int launch_attention_v2(const void* qkv, void* ctx, int B, int S, int heads, int hdp, float scale, int dtype, hipStream_t s) {
-  const int ndt = hdp / 16;
-  if (dtype == 2) {                        // two-limb modes (fp32 storage): the float kernel's shapes on the 16-bit MFMA
-    if (S <= 32) return dispatch_ndt<f32x2l, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s);
-    if (S <= 112) return dispatch_ndt<f32x2l, 7, 4>(ndt, qkv, ctx, B, S, heads, scale, s);
-    if (S <= 208) return dispatch_ndt<f32x2l, 13, 7>(ndt, qkv, ctx, B, S, heads, scale, s);
-    return -1;
-  }
-  if (dtype == 0) {
-    if (S <= 32) return dispatch_ndt<float, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s);
 #ifndef ATT_NWF112
 #define ATT_NWF112 4
 #endif
 #ifndef ATT_NWF208
 #define ATT_NWF208 7      // 13 query tiles: 4 waves 153 ms per DeiT-S step (two-limb mode), 7: 138, 8: 141; at 7 tiles (S <= 112) the wave count does not matter
 #endif
-    if (S <= 112) return dispatch_ndt<float, 7, ATT_NWF112>(ndt, qkv, ctx, B, S, heads, scale, s);
-    if (S <= 208) return dispatch_ndt<float, 13, ATT_NWF208>(ndt, qkv, ctx, B, S, heads, scale, s);   // ViT: 196 patches + cls
-  } else {
-    if (S <= 32) return dispatch_ndt<bf16, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s);
-    if (S <= 128) return dispatch_ndt<bf16, 8, 4>(ndt, qkv, ctx, B, S, heads, scale, s);
 #ifndef ATT_NW224
 #define ATT_NW224 8      // 13 query tiles of a 197-token map over 8 waves (4: 27.9 ms per DeiT-S step, 7: 26.1, 8: 24.8)
 #endif
-    if (S <= 224) return dispatch_ndt<bf16, 14, ATT_NW224>(ndt, qkv, ctx, B, S, heads, scale, s);
-  }
-  return -1;
+
+// ---- the ONE place that chooses a kernel.  elem: 0 = float, 1 = this build's 16-bit type, 2 = f32x2l (fp32 rows, two-limb products).
+// key tiles of the v2 instantiation that holds S tokens (0: none)
+static int v2_key_tiles(int S, int elem) {
+  if (elem == 1) return S <= 32 ? 2 : S <= 128 ? 8 : S <= 224 ? 14 : 0;      // (224: ViT, 196 patches + cls)
+  return S <= 32 ? 2 : S <= 112 ? 7 : S <= 208 ? 13 : 0;
+}
+// head-dim tile counts dispatch_ndt instantiates (16-bit: 3 = head dim 48, one and a half 64-byte chunks)
+static bool v2_has_ndt(int ndt, int elem) {
+  if (ndt == 2 || ndt == 3 || ndt == 4 || ndt == 6 || ndt == 8) return true;
+  return elem != 1 && (ndt == 1 || ndt == 5);
+}
+// the v2 instantiation of (S, ndt, elem) exists and its image fits the LDS -> its key tiles, else 0
+static int v2_route(int S, int ndt, int elem) {
+  const int nkt = v2_key_tiles(S, elem);
+  return nkt && v2_has_ndt(ndt, elem) && v2_lds_bytes(elem == 1 ? 2 : 4, nkt, ndt) <= kAttnLdsMax ? nkt : 0;
+}
+static inline int attn_route_id(int family, int elem, int nkt, int ndt) { return family * 100000 + elem * 10000 + nkt * 100 + ndt; }
+
+// fsvit.h fsvit_op_attention_route: family * 100000 + elem * 10000 + NKT * 100 + NDT (family 1 = attention_v2_kernel<elem, NKT, NDT>, 2 = the generic
+// attention_kernel<elem>, NKT = NDT = 0), -1 = refused.  dtype as launch_attention takes it (0 fp32, 1 16-bit, 2 two-limb); a two-limb shape without a
+// two-limb instantiation goes where the exact-fp32 kernels take it.
+int attention_route(int S, int hdp, int dtype) {
+  if (dtype < 0 || dtype > 2 || S < 1 || hdp < 16 || hdp % 16 != 0) return -1;
+  const int ndt = hdp / 16;
+  if (dtype == 2 && v2_route(S, ndt, 2)) return attn_route_id(1, 2, v2_route(S, ndt, 2), ndt);
+  const int elem = dtype == 2 ? 0 : dtype;
+  if (v2_route(S, ndt, elem)) return attn_route_id(1, elem, v2_route(S, ndt, elem), ndt);
+  if (S > 128) return -1;                                             // the generic v1 kernel holds at most 128 tokens
+  if (attention_lds_bytes(S, hdp, elem) > kAttnLdsMax) return -1;
+  return attn_route_id(2, elem, 0, 0);
 }
 
 // Padded head dim the packer should use: the smallest multiple of 16 the attention kernels take for (hd, S, dtype).  fp32: any
@@ -393,23 +420,28 @@ int attention_padded_head_dim(int hd, int S, int dtype) {
 
 int launch_attention(const void* qkv, void* ctx, int B, int S, int heads, int hdp, float scale, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
-  if (dtype == 2) {                        // no two-limb instantiation for this shape: the exact-fp32 kernels take it
-    const int rc = launch_attention_v2(qkv, ctx, B, S, heads, hdp, scale, 2, s);
-    if (rc != -1) return rc;
-    dtype = 0;
+  const int route = attention_route(S, hdp, dtype);
+  if (route < 0) return (int)hipErrorInvalidValue;
+  const int family = route / 100000, elem = route / 10000 % 10, nkt = route / 100 % 100, ndt = route % 100;
+  if (family == 1) {                         // the table of instantiations (no condition of its own: a route without one is an error, not a fallback)
+    int rc = -1;
+    switch (elem * 100 + nkt) {
+      case 202: rc = dispatch_ndt<f32x2l, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 207: rc = dispatch_ndt<f32x2l, 7, 4>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 213: rc = dispatch_ndt<f32x2l, 13, 7>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 2: rc = dispatch_ndt<float, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 7: rc = dispatch_ndt<float, 7, ATT_NWF112>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 13: rc = dispatch_ndt<float, 13, ATT_NWF208>(ndt, qkv, ctx, B, S, heads, scale, s); break;   // ViT: 196 patches + cls
+      case 102: rc = dispatch_ndt<bf16, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 108: rc = dispatch_ndt<bf16, 8, 4>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+      case 114: rc = dispatch_ndt<bf16, 14, ATT_NW224>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+    }
+    return rc == -1 ? (int)hipErrorInvalidValue : rc;
   }
-
-  if (S < 1 || hdp % 16 != 0) return (int)hipErrorInvalidValue;
-  {
-    const int rc = launch_attention_v2(qkv, ctx, B, S, heads, hdp, scale, dtype, s);
-    if (rc != -1) return rc;
-  }
-  if (S > 128) return (int)hipErrorInvalidValue;      // the generic v1 kernel holds at most 128 tokens
-  const size_t lds = attention_lds_bytes(S, hdp, dtype);
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  const size_t lds = attention_lds_bytes(S, hdp, elem);
   dim3 grid(B * heads), block(256);
   hipError_t e;
-  if (dtype == 0) {
+  if (elem == 0) {
     e = hipFuncSetAttribute((const void*)attention_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(attention_kernel<float>, grid, block, lds, s, (const float*)qkv, (float*)ctx, S, heads, hdp, scale);

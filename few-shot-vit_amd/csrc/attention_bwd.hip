@@ -751,58 +751,79 @@ static int launch_bwd_mfma(const void* qkv, const void* dctx, void* dqkv, int B,
   return (int)hipGetLastError();
 }
 
+// ---- the ONE place that chooses a kernel (fsvit.h fsvit_op_attention_bwd_route): family * 100000 + dtype * 10000 + KT * 100 + DT, -1 = refused.
+//   family 1  attention_bwd_mfma_kernel<KT, DT, .> (bf16)      2  attention_bwd_f32mfma_kernel<KT, DT>      3  attention_bwd_f32mfma_long_kernel<13, 4, 7>
+//          4  attention_bwd_kernel<T> (FMA loops, all in LDS)   5  attention_bwd_tiled_f32_kernel<16>       (4 and 5: KT = DT = 0)
+static inline int bwd_route_id(int family, int dtype, int kt, int dt) { return family * 100000 + dtype * 10000 + kt * 100 + dt; }
+constexpr int kBwdTiledQB = 16;
+static size_t bwd_fma_lds(int S, int hd) { return ((size_t)4 * S * (hd + 1) + (size_t)2 * S * (S + 1)) * sizeof(float); }
+static size_t bwd_tiled_lds(int S, int hd) {
+  return ((size_t)2 * S * (hd + 1) + (size_t)2 * kBwdTiledQB * (hd + 1) + (size_t)2 * kBwdTiledQB * (S + 1)) * sizeof(float);
+}
+static size_t bwd_mfma_lds(int nkt, int ndt) { return (size_t)4 * nkt * 16 * (ndt * 16 * 2 + 32) + (size_t)3 * nkt * 16 * sizeof(float); }
+
+int attention_bwd_route(int S, int hd, int hdp, int dtype) {
+  if ((dtype != 0 && dtype != 1) || S < 1 || hd < 1 || hdp < hd) return -1;
+  if (dtype == 1 && hdp % 32 == 0 && S <= 224) {      // bf16: MFMA kernel
+    const int ndt = hdp / 16;
+    // (128 tokens on 4 waves: with 8 the 512-thread bound left 256 registers per wave and the kernel spilled 228 .. 928 bytes per lane; one wave per SIMD
+    //  takes accumulators in AGPRs: 311 -> 249 us at S = 100.  224: ViT, 196 patches + cls)
+    const int nkt = S <= 32 ? 2 : S <= 128 ? 8 : 14;
+    const bool built = nkt == 2 ? (ndt == 2 || ndt == 4 || ndt == 6 || ndt == 8) : nkt == 8 ? (ndt == 2 || ndt == 4 || ndt == 6) : (ndt == 2 || ndt == 4);
+    if (built && bwd_mfma_lds(nkt, ndt) <= 160 * 1024) return bwd_route_id(1, 1, nkt, ndt);
+  }
+  if (dtype == 0 && (hdp & 3) == 0) {                 // exact-fp32 MFMA kernel where the head fits the LDS (Visformer stages: 100 x 42, 25 x 85)
+    if (S <= 32 && hdp <= 48) return bwd_route_id(2, 0, 2, 3);
+    if (S <= 32 && hdp <= 96) return bwd_route_id(2, 0, 2, 6);
+    if (S <= 48 && hdp <= 64) return bwd_route_id(2, 0, 3, 4);
+    if (S <= 112 && hdp <= 48) return bwd_route_id(2, 0, 7, 3);
+    if (S <= 208 && hdp <= 64) return bwd_route_id(3, 0, 13, 4);      // ViT / DeiT: 196 patches + cls
+  }
+  if (bwd_fma_lds(S, hd) <= 160 * 1024) return bwd_route_id(4, dtype, 0, 0);
+  if (dtype == 0 && bwd_tiled_lds(S, hd) <= 160 * 1024) return bwd_route_id(5, 0, 0, 0);
+  return -1;
+}
+
 int launch_attention_bwd(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, int dtype, hipStream_t s) {
   if (B <= 0) return 0;
-  if (dtype == 1 && hdp % 32 == 0 && S <= 224) {      // bf16: MFMA kernel
-    bool ran = false;
-    int rc = 0;
-    const int ndt = hdp / 16;
-    if (S <= 32) {
-      if (ndt == 2) rc = launch_bwd_mfma<2, 2, 2>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 4) rc = launch_bwd_mfma<2, 4, 2>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 6) rc = launch_bwd_mfma<2, 6, 2>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 8) rc = launch_bwd_mfma<2, 8, 2>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-    } else if (S <= 128) {                              // (4 waves: with 8 the 512-thread bound left 256 registers per wave and the kernel spilled 228 ..
-                                                        //  928 bytes per lane; one wave per SIMD takes accumulators in AGPRs: 311 -> 249 us at S = 100)
-      if (ndt == 2) rc = launch_bwd_mfma<8, 2, 4>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 4) rc = launch_bwd_mfma<8, 4, 4>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 6) rc = launch_bwd_mfma<8, 6, 4>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-    } else {                                            // ViT: 196 patches + cls
-      if (ndt == 2) rc = launch_bwd_mfma<14, 2, 4>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-      else if (ndt == 4) rc = launch_bwd_mfma<14, 4, 4>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran);
-    }
-    if (rc || ran) return rc;
-  }
-  if (dtype == 0) {                                     // exact-fp32 MFMA kernel where the head fits the LDS (Visformer stages: 100 x 42, 25 x 85)
-    if ((hdp & 3) == 0) {
-      if (S <= 32 && hdp <= 48) return launch_bwd_f32mfma<2, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-      if (S <= 32 && hdp <= 96) return launch_bwd_f32mfma<2, 6>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-      if (S <= 48 && hdp <= 64) return launch_bwd_f32mfma<3, 4>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-      if (S <= 112 && hdp <= 48) return launch_bwd_f32mfma<7, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-      if (S <= 208 && hdp <= 64) return launch_bwd_f32mfma_long<13, 4, 7>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);      // ViT / DeiT: 196 patches + cls
-    }
-  }
-  const size_t lds = ((size_t)4 * S * (hd + 1) + (size_t)2 * S * (S + 1)) * sizeof(float);
+  const int route = attention_bwd_route(S, hd, hdp, dtype);
+  if (route < 0) return (int)hipErrorInvalidValue;
+  bool ran = false;
   hipError_t e;
-  if (lds > 160 * 1024) {
-    constexpr int QB = 16;
-    const size_t lds_t = ((size_t)2 * S * (hd + 1) + (size_t)2 * QB * (hd + 1) + (size_t)2 * QB * (S + 1)) * sizeof(float);
-    if (dtype != 0 || lds_t > 160 * 1024) return (int)hipErrorInvalidValue;
-    e = hipFuncSetAttribute((const void*)attention_bwd_tiled_f32_kernel<QB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(attention_bwd_tiled_f32_kernel<QB>, dim3(B * heads), dim3(256), lds_t, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-    return (int)hipGetLastError();
+  switch (route) {                                      // the table of instantiations: no condition of its own
+#define BWD_MFMA(KT, DT, NW) case 110000 + KT * 100 + DT: { const int rc = launch_bwd_mfma<KT, DT, NW>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran); return rc || ran ? rc : (int)hipErrorInvalidValue; }
+    BWD_MFMA(2, 2, 2) BWD_MFMA(2, 4, 2) BWD_MFMA(2, 6, 2) BWD_MFMA(2, 8, 2)
+    BWD_MFMA(8, 2, 4) BWD_MFMA(8, 4, 4) BWD_MFMA(8, 6, 4)
+    BWD_MFMA(14, 2, 4) BWD_MFMA(14, 4, 4)
+#undef BWD_MFMA
+    case 200203: return launch_bwd_f32mfma<2, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+    case 200206: return launch_bwd_f32mfma<2, 6>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+    case 200304: return launch_bwd_f32mfma<3, 4>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+    case 200703: return launch_bwd_f32mfma<7, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+    case 301304: return launch_bwd_f32mfma_long<13, 4, 7>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+    case 500000: {
+      const size_t lds_t = bwd_tiled_lds(S, hd);
+      e = hipFuncSetAttribute((const void*)attention_bwd_tiled_f32_kernel<kBwdTiledQB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(attention_bwd_tiled_f32_kernel<kBwdTiledQB>, dim3(B * heads), dim3(256), lds_t, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
+      return (int)hipGetLastError();
+    }
+    case 400000: {
+      const size_t lds = bwd_fma_lds(S, hd);
+      e = hipFuncSetAttribute((const void*)attention_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * heads), dim3(256), lds, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
+      return (int)hipGetLastError();
+    }
+    case 410000: {
+      const size_t lds = bwd_fma_lds(S, hd);
+      e = hipFuncSetAttribute((const void*)attention_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(attention_bwd_kernel<bf16>, dim3(B * heads), dim3(256), lds, s, (const bf16*)qkv, (const bf16*)dctx, (bf16*)dqkv, S, heads, hd, hdp, scale);
+      return (int)hipGetLastError();
+    }
   }
-  if (dtype == 0) {
-    e = hipFuncSetAttribute((const void*)attention_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * heads), dim3(256), lds, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-  } else {
-    e = hipFuncSetAttribute((const void*)attention_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(attention_bwd_kernel<bf16>, dim3(B * heads), dim3(256), lds, s, (const bf16*)qkv, (const bf16*)dctx, (bf16*)dqkv, S, heads, hd, hdp, scale);
-  }
-  return (int)hipGetLastError();
+  return (int)hipErrorInvalidValue;                     // a route without an instantiation is an error, never a fallback
 }
 
 }  // namespace fsvit

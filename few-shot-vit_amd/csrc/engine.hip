@@ -1368,11 +1368,20 @@ extern "C" int fsvit_vit_ln_qkv_attention_dt(const void* x, const void* wqkv, in
   return 0;
 }
 
+extern "C" int fsvit_op_attention_route(int S, int hdp, int dtype) {
+  const int kdt = dtype;
+  if (!known_dtype(dtype)) return -1;
+  return K(attention_route)(S, hdp, kg(dtype));
+}
+
 extern "C" int fsvit_attention(const void* qkv, void* ctx, int B, int S, int heads, int hdp, float scale, int dtype, void* stream) {
   const int kdt = dtype;
   if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
   if (!qkv || !ctx) return fail(FSVIT_ERR_ARG, "null argument");
-  int rc = K(launch_attention)(qkv, ctx, B, S, heads, hdp, scale, kd(dtype), (hipStream_t)stream);
+  if (B < 0 || heads < 1) return fail(FSVIT_ERR_ARG, "fsvit_attention: B = %d, heads = %d (B >= 0, heads >= 1)", B, heads);
+  if (K(attention_route)(S, hdp, kg(dtype)) < 0)
+    return fail(FSVIT_ERR_ARG, "fsvit_attention: no kernel covers S = %d, hdp = %d in dtype %d (fsvit.h)", S, hdp, dtype);
+  int rc = K(launch_attention)(qkv, ctx, B, S, heads, hdp, scale, kg(dtype), (hipStream_t)stream);      // (kg: the two-limb dtypes run the two-limb kernels, as in the engines)
   if (rc != 0) return hipfail((hipError_t)rc, "attention");
   return 0;
 }

@@ -1543,9 +1543,21 @@ extern "C" int fsvit_proto_head_ce_backward(const float* feat_shot, const float*
   return rc ? fsvit_set_error(rc, "proto_head_ce_backward") : 0;
 }
 
+extern "C" int fsvit_op_attention_bwd_route(int S, int hd, int hdp, int dtype) {
+  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16) return -1;
+  return attention_bwd_route(S, hd, hdp, dtype);
+}
+
 extern "C" int fsvit_attention_backward(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, int dtype,
                                         void* stream) {
-  if (!qkv || !dctx || !dqkv) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (dtype != FSVIT_F32 && dtype != FSVIT_BF16)      // (any other value used to run the bf16 kernel on whatever bits it was handed)
+    return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_attention_backward: storage dtype %d (built for FSVIT_F32 and FSVIT_BF16 only)", dtype);
+  if (!qkv || !dctx || !dqkv) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_attention_backward: null argument");
+  if (B < 0 || S < 1 || heads < 1 || hd < 1 || hdp < hd)
+    return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_attention_backward: B = %d, S = %d, heads = %d, hd = %d, hdp = %d (B >= 0, S, heads, hd >= 1, hdp >= hd)", B, S, heads, hd,
+                           hdp);
+  if (attention_bwd_route(S, hd, hdp, dtype) < 0)
+    return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_attention_backward: no kernel covers S = %d, hd = %d, hdp = %d in dtype %d (fsvit.h)", S, hd, hdp, dtype);
   int rc = launch_attention_bwd(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, dtype, (hipStream_t)stream);
   return rc ? fsvit_set_error(rc, "attention_bwd") : 0;
 }

@@ -79,6 +79,7 @@ int launch_sgd_multi(const void* items_dev, int n_items, size_t max_numel, float
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s);
 // attention backward (attention_bwd.hip): qkv [B*S][3*heads*hdp], dctx [B*S][heads*hdp] -> dqkv [B*S][3*heads*hdp]
 int launch_attention_bwd(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, int dtype, hipStream_t s);
+int attention_bwd_route(int S, int hd, int hdp, int dtype);      // the kernel launch_attention_bwd takes (attention_bwd.hip), -1 = refused; host only
 // prototype head backward (head.hip): dlogits [E,Q,way] -> dfeat_shot [E,way,shot,D], dfeat_query [E,Q,D], dtemp[E] (cos method).
 // up: device scalar every gradient is multiplied with (the upstream gradient of a scalar loss); ticket: zeroed device word -> dtemp[E] = sum_e dtemp[e]
 int launch_proto_head_bwd(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D, float temp,

@@ -735,12 +735,22 @@ class ops:
         return y
 
     @staticmethod
-    def attention(qkv, B, S, heads, hdp, scale):
+    def attention(qkv, B, S, heads, hdp, scale, numerics=None, out=None):
+        """qkv [B S, 3 heads hdp] (rows (q | k | v, head, channel), pad channels zero) -> ctx [B S, heads hdp].  numerics 'bf16x2' / 'f16x2': qkv fp32,
+        every product from two 16-bit limbs per operand (fsvit.h: fsvit_attention)."""
         _require_cuda(qkv)
+        if numerics is not None:
+            if numerics not in ('bf16x2', 'f16x2'):
+                raise ValueError(f"numerics: None, 'bf16x2' or 'f16x2', got {numerics!r}")
+            if qkv.dtype != torch.float32:
+                raise TypeError(f'the two-limb modes read fp32 rows, got {qkv.dtype}')
+        if tuple(qkv.shape) != (B * S, 3 * heads * hdp) or not qkv.is_contiguous():
+            raise ValueError(f'qkv must be a contiguous [{B * S}, {3 * heads * hdp}] tensor')
         lib = _lib.load()
-        ctx = torch.empty(B * S, heads * hdp, dtype=qkv.dtype, device=qkv.device)
+        ctx = ops._out(out, qkv, heads * hdp)
         with torch.cuda.device(qkv.device):
-            _lib.check(lib.fsvit_attention(_ptr(qkv), _ptr(ctx), B, S, heads, hdp, float(scale), ops._dt(qkv), _stream_ptr(qkv.device)))
+            _lib.check(lib.fsvit_attention(_ptr(qkv), _ptr(ctx), B, S, heads, hdp, float(scale), DTYPES[numerics] if numerics else ops._dt(qkv),
+                                           _stream_ptr(qkv.device)))
         return ctx
 
     @staticmethod
@@ -814,10 +824,18 @@ class ops:
         return out
 
     @staticmethod
-    def attention_backward(qkv, dctx, B, S, heads, hd, hdp, scale):
+    def attention_backward(qkv, dctx, B, S, heads, hd, hdp, scale, out=None):
+        """qkv [B S, 3 heads hdp], dctx [B S, heads hdp], both fp32 or both bf16, pad channels zero -> dqkv (dQ | dK | dV) (fsvit.h:
+        fsvit_attention_backward).  The training kernels have no fp16 build: fp16 tensors raise TypeError."""
         _require_cuda(qkv, dctx)
+        if qkv.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f'attention_backward is built for torch.float32 and torch.bfloat16, got {qkv.dtype}')
+        if dctx.dtype != qkv.dtype:
+            raise TypeError(f'qkv is {qkv.dtype} but dctx is {dctx.dtype}')
+        if tuple(qkv.shape) != (B * S, 3 * heads * hdp) or tuple(dctx.shape) != (B * S, heads * hdp) or not qkv.is_contiguous() or not dctx.is_contiguous():
+            raise ValueError(f'qkv / dctx must be contiguous [{B * S}, {3 * heads * hdp}] / [{B * S}, {heads * hdp}] tensors')
         lib = _lib.load()
-        dqkv = torch.empty_like(qkv)
+        dqkv = ops._out(out, qkv, 3 * heads * hdp)
         with torch.cuda.device(qkv.device):
             _lib.check(lib.fsvit_attention_backward(_ptr(qkv), _ptr(dctx), _ptr(dqkv), B, S, heads, hd, hdp, float(scale),
                                                     ops._dt(qkv), _stream_ptr(qkv.device)))

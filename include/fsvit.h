@@ -193,9 +193,21 @@ int fsvit_conv_gemm(const void* x_dev, const void* w_dev, const float* bias_dev,
  * + bias)) + pos [(H/2)*(W/2)][N]; BatchNorms folded into w / bias by the caller; bke = 128 bytes of K (64 bf16 / 32 fp32). */
 int fsvit_conv_stem_tail(const void* x_dev, const void* w_dev, const float* bias_dev, const float* pos_dev, const void* x2_dev, int x2_cstride,
                          int K2, void* y_dev, int B, int H, int W, int Cin, int N, int Kw, int dtype, void* stream);
-/* qkv [B*S][3*heads*hdp] -> ctx [B*S][heads*hdp] (visformer.py:183-190) */
+/* qkv [B*S][3*heads*hdp] -> ctx [B*S][heads*hdp] = softmax(scale q k^T) v per (image, head) (visformer.py:183-190).  Row layout of qkv: (q | k | v, head,
+ * channel), every head padded from its hd channels to hdp.  dtype: any of the five; FSVIT_BF16X2 / FSVIT_F16X2 take fp32 rows and form every product
+ * from two 16-bit limbs per operand (a shape without a two-limb kernel runs the exact-fp32 one).
+ * PAD CONTRACT: the kernels contract over all hdp channels, so the pad channels hd .. hdp-1 of q, k and v must be ZERO (the weight packers write them
+ * so); the pad channels of ctx are then written as exact zeros.
+ * Refused with FSVIT_ERR_ARG and a message, nothing launched: an unknown dtype, a null pointer, B < 0, heads < 1, S < 1, hdp < 16 or not a multiple of 16,
+ * and a shape no kernel covers - 16-bit: S > 224, or S > 128 where hdp / 16 is not one of 2, 3, 4, 6, 8; fp32 and two-limb: S > 208, or S > 128 where
+ * hdp / 16 is not one of 1 .. 5 (13 key tiles of fp32 rows at hdp 96 / 128 pass the 160 KB of LDS), or 113 <= S <= 128 at hdp >= 96; any type: the generic
+ * kernel's (S <= 128) LDS image past 160 KB.  B == 0 returns 0. */
 int fsvit_attention(const void* qkv_dev, void* ctx_dev, int B, int S, int heads, int hdp, float scale,
                     int dtype, void* stream);
+/* The kernel fsvit_attention takes for (S, hdp, dtype), host only, nothing launched: family * 100000 + elem * 10000 + NKT * 100 + NDT with family 1 =
+ * attention_v2_kernel<elem, NKT key tiles, NDT head-dim tiles>, 2 = the generic attention_kernel<elem> (NKT = NDT = 0); elem 0 = float, 1 = the 16-bit
+ * type, 2 = two-limb; -1 = refused.  The launcher decides by this very function (attention.hip attention_route). */
+int fsvit_op_attention_route(int S, int hdp, int dtype);
 /* Fused qkv conv + attention core of a Visformer stage-2 Attention block (visformer.py:172-190; the eval BatchNorm folded into the
  * conv as column scale + bias by the caller), bf16, Visformer-S geometry only (C = 256, 6 heads, head dim padded to 48, S <= 112):
  * x rows [B*S][C] -> ctx rows [B*S][heads*hdp].  wqkv [3*heads*hdp][kw] K-major bf16, rows ordered (q|k|v, head, z); bias fp32
@@ -490,8 +502,20 @@ int fsvit_gconv3x3(const void* x_dev, const void* w_packed_dev, int Kw, void* y_
  * LDS: the two-limb trainers' kernel); N and C multiples of 8.  (conv1 / conv3 of the Mlps, qkv, proj in train_meta.py:228-232.) */
 int fsvit_conv1x1_wgrad(const void* x_dev, const void* dz_dev, float* dw_dev, int M, int N, int C, int dtype, void* stream);
 
+/* Backward of fsvit_attention: qkv [B*S][3*heads*hdp] (the forward's input) and dctx [B*S][heads*hdp] -> dqkv [B*S][3*heads*hdp] = (dQ | dK | dV):
+ * P = softmax(scale q k^T), dV = P^T dO, dP = dO V^T, dS = scale P o (dP - rowsum(dP o P)), dQ = dS K, dK = dS^T Q.  hd = the real head dim, hdp its
+ * padded size.  dtype: FSVIT_F32 or FSVIT_BF16 only (the training kernels' two storage types; the two-limb trainers call it with FSVIT_F32).
+ * PAD CONTRACT: the pad channels hd .. hdp-1 of every head of qkv AND of dctx must be ZERO - the bf16 MFMA kernels take no hd and contract over all hdp
+ * channels; the fp32 kernels mask by hd and ignore what the input pads hold.  The pad channels of dqkv are written as exact zeros by every kernel.
+ * Refused with FSVIT_ERR_ARG and a message, nothing launched: any other dtype, a null pointer, B < 0, S < 1, heads < 1, hd < 1, hdp < hd, and a shape no
+ * kernel covers (bf16: S > 224, or a head whose fp32 image 4 S (hd + 1) + 2 S (S + 1) floats is past 160 KB where hdp / 16 has no MFMA kernel at that S -
+ * 2, 4, 6, 8 for S <= 32; 2, 4, 6 for S <= 128; 2, 4 for S <= 224; fp32: 2 (S + 16) (hd + 1) + 32 (S + 1) floats past 160 KB).  B == 0 returns 0. */
 int fsvit_attention_backward(const void* qkv_dev, const void* dctx_dev, void* dqkv_dev, int B, int S, int heads, int hd, int hdp,
                              float scale, int dtype, void* stream);
+/* The kernel fsvit_attention_backward takes, host only, nothing launched: family * 100000 + dtype * 10000 + KT * 100 + DT with family 1 =
+ * attention_bwd_mfma_kernel<KT, DT> (bf16), 2 = attention_bwd_f32mfma_kernel<KT, DT>, 3 = attention_bwd_f32mfma_long_kernel<13, 4>, 4 = attention_bwd_kernel
+ * (FMA loops, the head in LDS), 5 = attention_bwd_tiled_f32_kernel (4 and 5: KT = DT = 0); -1 = refused.  The launcher decides by this very function. */
+int fsvit_op_attention_bwd_route(int S, int hd, int hdp, int dtype);
 
 /* ================================================================ operator entry points (tests, tools)
  * The memory-bound kernels of the training step (train_kernels.hip), one entry per engine-level operation, so that each can be held against a

@@ -39,8 +39,8 @@ EPS24 = 2.0 ** -24
 
 
 def half_ulp(dtype):
-    """u: half an ulp, relative (2^-11 for fp16, 2^-8 for bf16)"""
-    return {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}[dtype]
+    """u: half an ulp, relative (2^-11 for fp16, 2^-8 for bf16; 2^-24 for the fp32 rows of the stand-alone attention kernels)"""
+    return {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8, torch.float32: 2.0 ** -24}[dtype]
 
 
 def gelu_erf(z):

@@ -10,7 +10,7 @@ Launchers of train_kernels.h and where they are held:
   vit_assemble, vit_patch_rows, vit_cls_ln_fwd / _bwd                       test_vit_cls_ln_and_tokens
   gelu_fwd / gelu_bwd, add_scaled, avgpool_bwd, batch_sum, bcast_add,
   colsum, unpatch2, droppath_scales, fold_prenorm                           test_elementwise, test_batch_sum, test_small_ops
- covered elsewhere: launch_sgd* (test_gpu_train: SGD), launch_attention_bwd, launch_proto_head*_bwd (their operator tests in test_gpu_train.py);
+ covered elsewhere: launch_sgd* (test_gpu_train: SGD), launch_attention_bwd (test_gpu_attention_ops.py), launch_proto_head*_bwd (test_gpu_train.py);
  launch_pack_weight_multi (modes 0 / 1 / 2, head padding, two-limb words, the 40-job table), the training epilogues of launch_conv_gemm / launch_gconv3x3
  (y2, ACT_MUL, mul) and launch_stage1_ring_block_train / launch_stage1_ring_dgrad: test_gpu_train_conv_ops.py, same conventions; fill_f32 / scale_copy:
  test_small_ops.  Reached only through whole train steps (the golden / oracle step tests of test_gpu_train.py, no operator entry): launch_patchk,
