@@ -67,6 +67,7 @@ SIGNATURES = {
     'fsvit_lvvit_out_dim': (_i, [_vp]),
     'fsvit_lvvit_workspace_bytes': (_sz, [_vp, _i]),
     'fsvit_lvvit_forward': (_i, [_vp, _fp, _i, _i, _i, _fp, _vp, _sz, _vp]),
+    'fsvit_lvvit_forward_map': (_i, [_vp, _fp, _i, _i, _i, _fp, _fp, _vp, _sz, _vp]),
     'fsvit_stem96_conv': (_i, [_vp, _vp, _fp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     'fsvit_encoder_set_tap': (_i, [_vp, C.c_char_p, _vp, _sz]),
     'fsvit_encoder_profile_begin': (_i, [_vp]),
@@ -130,6 +131,8 @@ SIGNATURES = {
     'fsvit_lvvit_trainer_set_freeze_bn': (_i, [_vp, _i]),
     'fsvit_lvvit_train_forward': (_i, [_vp, C.POINTER(Param), _i, _fp, _i, _i, _i, _f, _fp, _fp, _vp, _sz, _vp]),
     'fsvit_lvvit_train_backward': (_i, [_vp, C.POINTER(Param), _i, _fp, _vp]),
+    'fsvit_lvvit_train_tokens': (_i, [_vp, _fp, _vp]),
+    'fsvit_lvvit_train_set_token_grad': (_i, [_vp, _fp]),
     'fsvit_proto_head_backward': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _fp, _vp]),
     'fsvit_proto_head_backward_sqr': (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _fp, _vp]),
     'fsvit_proto_head_ce': (_i, [_fp, _fp, _vp, _i, _i, _i, _i, _i, _f, _fp, _i, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
@@ -167,6 +170,9 @@ SIGNATURES = {
     'fsvit_op_vit_patch_rows': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_op_vit_cls_ln_forward': (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _vp]),
     'fsvit_op_vit_cls_ln_backward': (_i, [_fp, _vp, _fp, _fp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_vit_map_ln_forward': (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _vp]),
+    'fsvit_op_vit_map_ln_bwd_blocks': (_i, [_i, _i]),
+    'fsvit_op_vit_map_ln_backward': (_i, [_fp, _fp, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_op_gelu': (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     'fsvit_op_add_scaled': (_i, [_vp, _vp, _fp, _vp, _sz, _sz, _i, _vp]),
     'fsvit_op_avgpool_bwd': (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),

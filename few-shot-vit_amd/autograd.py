@@ -83,6 +83,34 @@ class VisformerTrainMapFn(torch.autograd.Function):
         return (None,) * 7 + tuple(grads[k] for k in ctx.names)
 
 
+class LvvitTrainMapFn(torch.autograd.Function):
+    """(tokens, feat) = encoder(x) in train mode for LV-ViT (sun_meta_training/models/lvvit.py:552: x_local, x1), the contract of
+    VisformerTrainMapFn: tokens [B, 25, D] token-major.  Undefined gradients stay None: an output the loss does not use costs nothing in the
+    backward - without a token gradient the trainer runs its cls-only final-norm backward (what VisformerTrainFn gives, bit for bit), without a
+    feature gradient the fused kernel gets a null pointer for it."""
+
+    @staticmethod
+    def forward(ctx, x, trainer, names, buffers, drop_path_rate, masks, *params):
+        tensors = dict(zip(names, params))
+        tensors.update(buffers)
+        feat = trainer.forward(tensors, x, drop_path_rate, masks)
+        tokens = trainer.tokens(x.shape[0])
+        ctx.trainer, ctx.names, ctx.buffers, ctx.generation = trainer, names, buffers, trainer.generation
+        ctx.save_for_backward(*params)
+        ctx.set_materialize_grads(False)
+        return tokens, feat
+
+    @staticmethod
+    def backward(ctx, dtokens, dfeat):
+        _check_generation(ctx)
+        params = ctx.saved_tensors
+        tensors = dict(zip(ctx.names, params))
+        grads = {k: torch.empty_like(v) for k, v in tensors.items()}
+        tensors.update(ctx.buffers)
+        ctx.trainer.backward(tensors, grads, dfeat, dtokens)
+        return (None,) * 6 + tuple(grads[k] for k in ctx.names)
+
+
 class ProtoHeadFn(torch.autograd.Function):
     """logits = temp * cos(query, mean_shot) or -temp * |query - mean_shot|^2 (meta_baseline.py:33-47, methods 'cos' / 'sqr')."""
 

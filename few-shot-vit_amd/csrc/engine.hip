@@ -1734,6 +1734,7 @@ struct fsvit_lvvit : EngineBase {
   Layer conv2h, conv3h;        // bf16 / f16 at 96 channels: the 128-channel weight images of conv2 / conv3f for conv3x3_halo (w = nullptr: not built)
   float *pos_patch = nullptr, *cls_pos0 = nullptr, *ng = nullptr, *nb = nullptr;
   std::vector<VitBlock> blocks;
+  float* map_out = nullptr;    // fsvit_lvvit_forward_map: where the next chunk's patch rows [Bc][S - 1][D] go (advanced chunk by chunk); null: cls feature only
 };
 
 namespace {
@@ -1877,6 +1878,12 @@ int lvvit_forward_chunk(EngineBase* hb, const float* x, int Bc, float* feat, uns
   RC_TRY(tap(h, "embed", tokens, (size_t)Bc * S * D * es, first, st));
   RC_TRY(vit_blocks_forward(h, h->blocks, tokens, ws + pl.xn, ws + pl.qkv, ws + pl.ctx, ws + pl.hid, Bc, S, D, heads, h->hd, h->hdp, h->hid,
                             h->cfg.ln_eps, first, st));
+  if (h->map_out) {
+    float* map = h->map_out;
+    h->map_out += (size_t)Bc * (S - 1) * D;
+    RC_TRY(timed(h, st, "norm.map", KID_LN, 0.0, [&]() { return K(launch_final_ln_map)(tokens, h->ng, h->nb, feat, map, Bc, S, D, h->cfg.ln_eps, dt, st); }));
+    return 0;
+  }
   RC_TRY(timed(h, st, "norm.cls", KID_LN, 0.0, [&]() { return K(launch_final_ln_cls)(tokens, h->ng, h->nb, feat, Bc, S, D, h->cfg.ln_eps, dt, st); }));
   return 0;
 }
@@ -1894,4 +1901,13 @@ extern "C" size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_im
 extern "C" int fsvit_lvvit_forward(fsvit_lvvit* h, const float* x, int n_img, int img_h, int img_w, float* feat, void* ws,
                                    size_t ws_bytes, void* stream) {
   return encoder_forward(h, x, n_img, img_h, img_w, feat, ws, ws_bytes, stream);
+}
+extern "C" int fsvit_lvvit_forward_map(fsvit_lvvit* h, const float* x, int n_img, int img_h, int img_w, float* feat, float* tokens, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  if (h && n_img <= 0) return 0;
+  if (!h || !tokens) return fail(FSVIT_ERR_ARG, "null argument");
+  h->map_out = tokens;                   // every chunk writes its images' rows and moves this on
+  const int rc = encoder_forward(h, x, n_img, img_h, img_w, feat, ws, ws_bytes, stream);
+  h->map_out = nullptr;
+  return rc;
 }

@@ -97,6 +97,7 @@ int launch_patchify(const float* x_nchw, void* out, int B, int img, int p, int K
 int launch_cls_pos(const float* cls_plus_pos0, void* tokens, int B, int S, int D, int dtype, hipStream_t s);
 int launch_layernorm(const void* x, void* y, int M, int D, float eps, int dtype, hipStream_t s);
 int launch_final_ln_cls(const void* tokens, const float* gamma, const float* beta, float* feat, int B, int S, int D, float eps, int dtype, hipStream_t s);
+int launch_final_ln_map(const void* tokens, const float* gamma, const float* beta, float* feat, float* map, int B, int S, int D, float eps, int dtype, hipStream_t s);
 
 // direct 3x3 / s1 / p1 weight gradient from NHWC activations (wgrad3x3.hip; dtype 1 = 16-bit storage, 2 = fp32 storage with two-limb arithmetic): dw [O][Ig][3][3] fp32 overwritten
 bool wgrad3x3_supported(int dtype, int O, int Ig, int groups, int W);

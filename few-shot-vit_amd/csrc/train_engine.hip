@@ -170,6 +170,14 @@ struct fsvit_vit_trainer : TrainerBase {
   void* patches = nullptr;
   void* xlast = nullptr;
   float *mf = nullptr, *rf = nullptr;
+  // The final norm's patch rows as a second output (LV-ViT only: sun_meta_training/models/lvvit.py:552).  The forward reserves their row statistics,
+  // train_tokens computes the map (and the statistics) on demand, set_token_grad arms the fused backward of both outputs for one backward pass.
+  bool has_map = false;
+  bool pending = false;                   // a train_forward whose train_backward has not run yet
+  bool map_done = false;                  // train_tokens ran for the pending forward: mp / rp hold the statistics
+  float *mp = nullptr, *rp = nullptr;     // [B * (S - 1)]
+  const float *map_g = nullptr, *map_b = nullptr;      // norm.weight / norm.bias of the pending forward
+  const float* dtokens = nullptr;         // gradient of the map [B][S - 1][D] for the next backward, or null
 };
 
 // LV-ViT (lvvit.py:413-552): the ConvBlock stem at 96 channels (stem_forward / stem_backward), a 4x4 / stride 4 projection of the pooled map into 25 patch
@@ -1120,10 +1128,16 @@ int vit_blocks_forward(VT* t, const VSpecs& sp, void* xcur, float* feat) {
   t->mf = (float*)t->save.take((size_t)B * 4); t->rf = (float*)t->save.take((size_t)B * 4);
   NEED(t->mf); NEED(t->rf);
   T_RUN(launch_vit_cls_ln_fwd(t->xlast, ng->data, nb->data, feat, t->mf, t->rf, B, S, D, t->vcfg.ln_eps, dt, st));
+  if (t->has_map) {
+    t->mp = (float*)t->save.take((size_t)B * (S - 1) * 4); t->rp = (float*)t->save.take((size_t)B * (S - 1) * 4);
+    NEED(t->mp); NEED(t->rp);
+    t->map_g = ng->data; t->map_b = nb->data;
+  }
   return 0;
 }
 
-// dfeat [B][D] -> *dx_out [B][S][D] (tmp), the gradient of the tokens in front of block 0; every block and final-norm parameter gradient on the way
+// dfeat [B][D] -> *dx_out [B][S][D] (tmp), the gradient of the tokens in front of block 0; every block and final-norm parameter gradient on the way.
+// With a token-map gradient set (t->dtokens) the final norm's backward is the fused one over all rows, and dfeat may be null.
 int vit_blocks_backward(VT* t, const VSpecs& sp, const float* dfeat, void** dx_out) {
   const int B = t->B, S = t->S, D = t->D, dt = t->dtype, heads = t->heads, hdp = t->hdp, hid = t->hidv;
   const size_t M = (size_t)B * S;
@@ -1132,10 +1146,15 @@ int vit_blocks_backward(VT* t, const VSpecs& sp, const float* dfeat, void** dx_o
   if (!ng || !nb) return FSVIT_ERR_KEY;
   void* dx = take_tmp(t, M * D); NEED(dx);
   {
-    if (!t->tmp.dry) { hipError_t e = hipMemsetAsync(dx, 0, M * D * t->es, st); if (e != hipSuccess) return fsvit_set_error((int)e, "memset"); }
     const size_t mark = t->tmp.off;
-    float* partial = (float*)t->tmp.take((size_t)B * 2 * D * 4); NEED(partial);
-    T_RUN(launch_vit_cls_ln_bwd(dfeat, t->xlast, t->mf, t->rf, ng->data, dx, partial, ng->grad, nb->grad, B, S, D, dt, st));
+    const int nblk = t->has_map && vit_map_ln_bwd_blocks(B, S) > B ? vit_map_ln_bwd_blocks(B, S) : B;      // (sized for either kernel)
+    float* partial = (float*)t->tmp.take((size_t)nblk * 2 * D * 4); NEED(partial);
+    if (t->dtokens && !t->tmp.dry) {
+      T_RUN(launch_vit_map_ln_bwd(dfeat, t->dtokens, t->xlast, t->mf, t->rf, t->mp, t->rp, ng->data, dx, partial, ng->grad, nb->grad, B, S, D, dt, st));
+    } else {
+      if (!t->tmp.dry) { hipError_t e = hipMemsetAsync(dx, 0, M * D * t->es, st); if (e != hipSuccess) return fsvit_set_error((int)e, "memset"); }
+      T_RUN(launch_vit_cls_ln_bwd(dfeat, t->xlast, t->mf, t->rf, ng->data, dx, partial, ng->grad, nb->grad, B, S, D, dt, st));
+    }
     t->tmp.off = mark;
   }
   const float scale = 1.0f / std::sqrt((float)t->hd);
@@ -1330,7 +1349,7 @@ void vit_init(VT* t, const fsvit_vit_cfg& cfg) {
 }
 
 void lvvit_init(LT* t, const fsvit_lvvit_cfg& cfg) {
-  t->lcfg = cfg; t->bn_eps = cfg.bn_eps; t->branch_scale = 1.0f / cfg.skip_lam; t->qkv_bias = false;
+  t->lcfg = cfg; t->bn_eps = cfg.bn_eps; t->branch_scale = 1.0f / cfg.skip_lam; t->qkv_bias = false; t->has_map = true;
   t->vcfg = fsvit_vit_cfg();
   t->vcfg.img_size = cfg.img_size; t->vcfg.embed_dim = cfg.embed_dim; t->vcfg.depth = cfg.depth;
   t->vcfg.num_heads = cfg.num_heads; t->vcfg.mlp_ratio = cfg.mlp_ratio; t->vcfg.ln_eps = cfg.ln_eps;
@@ -1423,8 +1442,9 @@ int trainer_forward(TB* t, const fsvit_param* params, int n_params, const float*
   return rc_f;
 }
 
-int trainer_backward(TB* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
-  if (!t || !params || !dfeat_dev) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
+// dfeat_optional: the model has a second gradient source armed for this pass (LV-ViT's token map), so a null dfeat is "no gradient", not a mistake
+int trainer_backward(TB* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream, bool dfeat_optional = false) {
+  if (!t || !params || (!dfeat_dev && !dfeat_optional)) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
   if (!t->save.base || t->save.dry) return fsvit_set_error(FSVIT_ERR_ARG, "train_backward called without a preceding train_forward");
   bind_params(t, params, n_params);
   t->st = (hipStream_t)stream;
@@ -1489,10 +1509,33 @@ extern "C" int fsvit_lvvit_trainer_set_freeze_bn(fsvit_lvvit_trainer* t, int on)
 }
 extern "C" int fsvit_lvvit_train_forward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
                                          float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-  return trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
+  if (t) t->pending = t->map_done = false;
+  const int rc = trainer_forward(t, params, n_params, x_nchw_dev, n_img, img_h, img_w, drop_path_rate, masks_dev, feat_dev, ws_dev, ws_bytes, stream);
+  if (t) t->pending = rc == 0;
+  return rc;
 }
 extern "C" int fsvit_lvvit_train_backward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream) {
-  return trainer_backward(t, params, n_params, dfeat_dev, stream);
+  if (t && t->dtokens && !(t->pending && t->map_done)) {
+    t->dtokens = nullptr;
+    return fsvit_set_error(FSVIT_ERR_ARG, "train_backward: a token gradient is set, but train_tokens did not run for this forward");
+  }
+  const int rc = trainer_backward(t, params, n_params, dfeat_dev, stream, t && t->dtokens);
+  if (t) { t->dtokens = nullptr; t->pending = false; }      // the token gradient armed this pass only
+  return rc;
+}
+// ---- the patch rows of the final norm [B][25][D] fp32 of the pending train_forward, and their gradient for its train_backward (the Visformer pair's contract)
+extern "C" int fsvit_lvvit_train_tokens(fsvit_lvvit_trainer* t, float* tokens_dev, void* stream) {
+  if (!t || !tokens_dev) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (!t->pending || !t->xlast || !t->mp || !t->save.base || t->save.dry) return fsvit_set_error(FSVIT_ERR_ARG, "train_tokens called without a preceding train_forward");
+  int rc = launch_vit_map_ln_fwd(t->xlast, t->map_g, t->map_b, tokens_dev, t->mp, t->rp, t->B, t->S, t->D, t->vcfg.ln_eps, t->dtype, (hipStream_t)stream);
+  if (rc != 0) return fsvit_set_error(FSVIT_ERR_ARG, "launch failed: %d", rc);
+  t->map_done = true;
+  return 0;
+}
+extern "C" int fsvit_lvvit_train_set_token_grad(fsvit_lvvit_trainer* t, const float* dtokens_dev) {
+  if (!t) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  t->dtokens = dtokens_dev;               // consumed (and cleared) by the next fsvit_lvvit_train_backward; NULL: none
+  return 0;
 }
 
 extern "C" int fsvit_proto_head_backward(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D,
@@ -1792,6 +1835,28 @@ extern "C" int fsvit_op_vit_cls_ln_backward(const float* dfeat, const void* toke
   hipError_t e = hipMemsetAsync(dtok, 0, (size_t)B * S * D * (dtype == FSVIT_F32 ? 4 : 2), (hipStream_t)stream);
   if (e != hipSuccess) return fsvit_set_error((int)e, "fsvit_op_vit_cls_ln_backward: memset");
   OP_RUN("vit_cls_ln_bwd", launch_vit_cls_ln_bwd(dfeat, tokens, mean, rstd, gamma, dtok, partial, dgamma, dbeta, B, S, D, dtype, (hipStream_t)stream));
+  return 0;
+}
+
+// the final norm on the patch rows: map [B][S - 1][D] fp32, mean / rstd [B * (S - 1)]
+extern "C" int fsvit_op_vit_map_ln_forward(const void* tokens, const float* gamma, const float* beta, float* map, float* mean, float* rstd, int B, int S, int D, float eps,
+                                           int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_map_ln_forward");
+  if (!tokens || !gamma || !beta || !map || !mean || !rstd) OP_FAIL("fsvit_op_vit_map_ln_forward: null argument");
+  if (B < 1 || S < 2 || D < 4 || D % 4 || D > 2052) OP_FAIL("fsvit_op_vit_map_ln_forward: B = %d, S = %d, D = %d (S >= 2, D a multiple of 4 up to 2052)", B, S, D);
+  OP_RUN("vit_map_ln_fwd", launch_vit_map_ln_fwd(tokens, gamma, beta, map, mean, rstd, B, S, D, eps, dtype, (hipStream_t)stream));
+  return 0;
+}
+// the fused backward of both outputs: dfeat [B][D] (statistics mean0 / rstd0 [B]) and dmap [B][S - 1][D] (meanp / rstdp [B * (S - 1)]), either may be NULL;
+// every row of dtok is written; partial: fsvit_op_vit_map_ln_bwd_blocks(B, S) * 2 * D floats
+extern "C" int fsvit_op_vit_map_ln_bwd_blocks(int B, int S) { return B < 1 || S < 1 ? 0 : vit_map_ln_bwd_blocks(B, S); }
+extern "C" int fsvit_op_vit_map_ln_backward(const float* dfeat, const float* dmap, const void* tokens, const float* mean0, const float* rstd0, const float* meanp,
+                                            const float* rstdp, const float* gamma, void* dtok, float* partial, float* dgamma, float* dbeta, int B, int S, int D,
+                                            int dtype, void* stream) {
+  OP_DT("fsvit_op_vit_map_ln_backward");
+  if (!tokens || !gamma || !dtok || !partial || (dfeat && (!mean0 || !rstd0)) || (dmap && (!meanp || !rstdp))) OP_FAIL("fsvit_op_vit_map_ln_backward: null argument");
+  if (B < 1 || S < 2 || D < 4 || D % 4 || D > 2052) OP_FAIL("fsvit_op_vit_map_ln_backward: B = %d, S = %d, D = %d (S >= 2, D a multiple of 4 up to 2052)", B, S, D);
+  OP_RUN("vit_map_ln_bwd", launch_vit_map_ln_bwd(dfeat, dmap, tokens, mean0, rstd0, meanp, rstdp, gamma, dtok, partial, dgamma, dbeta, B, S, D, dtype, (hipStream_t)stream));
   return 0;
 }
 

@@ -100,4 +100,11 @@ int launch_vit_cls_ln_fwd(const void* tokens, const float* gamma, const float* b
                           hipStream_t s);
 int launch_vit_cls_ln_bwd(const float* dfeat, const void* tokens, const float* mean, const float* rstd, const float* gamma, void* dtok, float* partial, float* dgamma,
                           float* dbeta, int B, int S, int D, int dtype, hipStream_t s);
+// ... and on the patch rows (LV-ViT's token map): map [B][S - 1][D] fp32 with its own row statistics; the backward takes both gradient sources (either may
+// be null) and writes every row of dtok.  S >= 2, D % 4 == 0, D <= 2052; partial: vit_map_ln_bwd_blocks(B, S) * 2 * D floats
+int launch_vit_map_ln_fwd(const void* tokens, const float* gamma, const float* beta, float* map, float* mean, float* rstd, int B, int S, int D, float eps, int dtype,
+                          hipStream_t s);
+int vit_map_ln_bwd_blocks(int B, int S);
+int launch_vit_map_ln_bwd(const float* dfeat, const float* dmap, const void* tokens, const float* mean0, const float* rstd0, const float* meanp, const float* rstdp,
+                          const float* gamma, void* dtok, float* partial, float* dgamma, float* dbeta, int B, int S, int D, int dtype, hipStream_t s);
 }  // namespace fsvit

@@ -4,6 +4,7 @@
 // reuses conv_gemm_v2.  T = storage dtype of activations and activation gradients (fp32 or bf16);
 // parameters, parameter gradients, BN statistics and reductions are fp32.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "fsvit_common.h"
 #include "train_kernels.h"
@@ -1289,6 +1290,119 @@ __global__ __launch_bounds__(64) void vit_cls_ln_bwd_kernel(const float* __restr
   }
 }
 
+// The same norm on the patch rows (sun_meta_training/models/lvvit.py:552 returns norm(x)[:, 1:] next to the cls feature): map[b][i] =
+// LN(tokens[b][1 + i]) * gamma + beta, fp32, token-major, cls row left out; mean / rstd [B * (S - 1)] kept.  One wave per row, four rows per workgroup,
+// the row in registers as in ln_bwd_rows_kernel (a lane owns the channels 4 lane + 256 g .. + 3, g < NG).  The statistic is the one of
+// vit_cls_ln_fwd_kernel (E[x^2] - mean^2, clamped at 0), so all rows of an image are normalised alike.
+template <typename T, int NG>
+__global__ __launch_bounds__(256) void vit_map_ln_fwd_kernel(const T* __restrict__ tokens, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float* __restrict__ map, float* __restrict__ mean, float* __restrict__ rstd, int rows, int S,
+                                                             int D, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int b = r / (S - 1), i = r - b * (S - 1);
+  const T* xr = tokens + ((size_t)b * S + 1 + i) * D;
+  f32x4 v[NG];
+  float s = 0.f, ss = 0.f;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int d = lane * 4 + 256 * g;
+    v[g] = d < D ? load4<T>(xr + d) : f32x4{0.f, 0.f, 0.f, 0.f};
+    s += v[g][0] + v[g][1] + v[g][2] + v[g][3];
+    ss += v[g][0] * v[g][0] + v[g][1] * v[g][1] + v[g][2] * v[g][2] + v[g][3] * v[g][3];
+  }
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
+  const float mu = s / D;
+  float var = ss / D - mu * mu;
+  var = var < 0.f ? 0.f : var;
+  const float rs = 1.0f / sqrtf(var + eps);
+  if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int d = lane * 4 + 256 * g;
+    if (d < D)
+      *reinterpret_cast<f32x4*>(map + (size_t)r * D + d) =
+          (v[g] - mu) * rs * *reinterpret_cast<const f32x4*>(gamma + d) + *reinterpret_cast<const f32x4*>(beta + d);
+  }
+}
+
+// Backward of the final norm with both outputs in use: row 0 of dtok[b] is the LN backward of dfeat[b] (statistics mean0 / rstd0 [B] of
+// vit_cls_ln_fwd_kernel), row 1 + i that of dmap[b][i] (statistics meanp / rstdp [B * (S - 1)] of vit_map_ln_fwd_kernel).  A null source gives zero
+// rows and adds nothing to the sums, so dtok needs no fill in front and there is no concatenated dy.  Workgroup b owns the rows b * rows_per_blk ..,
+// each wave every 4th of them with the row in registers; partial[blk][0][d] = sum of dy, [1][d] of dy * xhat over the block's rows
+// (-> dbeta / dgamma by ln_param_grad_kernel).  The four waves' sums meet in LDS, one half at a time ([4][D] floats).
+template <typename T, int NG>
+__global__ __launch_bounds__(256) void vit_map_ln_bwd_kernel(const float* __restrict__ dfeat, const float* __restrict__ dmap, const T* __restrict__ tokens,
+                                                             const float* __restrict__ mean0, const float* __restrict__ rstd0,
+                                                             const float* __restrict__ meanp, const float* __restrict__ rstdp,
+                                                             const float* __restrict__ gamma, T* __restrict__ dtok, float* __restrict__ partial, int M, int S,
+                                                             int D, int rows_per_blk) {
+  extern __shared__ float red[];                       // [4 waves][D]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  f32x4 gam[NG], acc[2][NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int d = lane * 4 + 256 * g;
+    gam[g] = d < D ? *reinterpret_cast<const f32x4*>(gamma + d) : f32x4{0.f, 0.f, 0.f, 0.f};
+    acc[0][g] = acc[1][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const int r0 = blockIdx.x * rows_per_blk;
+  const int rend = r0 + rows_per_blk < M ? r0 + rows_per_blk : M;
+  const float invD = 1.0f / D;
+  for (int row = r0 + wave; row < rend; row += 4) {
+    const int b = row / S, s = row - b * S;
+    const int pr = b * (S - 1) + s - 1;                // the row's index among the patch rows (s > 0)
+    const float* dyr = s == 0 ? (dfeat ? dfeat + (size_t)b * D : nullptr) : (dmap ? dmap + (size_t)pr * D : nullptr);
+    T* dxr = dtok + (size_t)row * D;
+    if (!dyr) {                                        // (uniform over the wave)
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const int d = lane * 4 + 256 * g;
+        if (d < D) store4<T>(dxr + d, f32x4{0.f, 0.f, 0.f, 0.f});
+      }
+      continue;
+    }
+    const float mu = s == 0 ? mean0[b] : meanp[pr], rs = s == 0 ? rstd0[b] : rstdp[pr];
+    const T* xr = tokens + (size_t)row * D;
+    f32x4 dyv[NG], xh[NG];
+    float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int d = lane * 4 + 256 * g;
+      const bool act = d < D;
+      dyv[g] = act ? *reinterpret_cast<const f32x4*>(dyr + d) : f32x4{0.f, 0.f, 0.f, 0.f};
+      xh[g] = act ? (load4<T>(xr + d) - mu) * rs : f32x4{0.f, 0.f, 0.f, 0.f};
+      const f32x4 gg = dyv[g] * gam[g];
+      c1 += gg[0] + gg[1] + gg[2] + gg[3];
+      c2 += gg[0] * xh[g][0] + gg[1] * xh[g][1] + gg[2] * xh[g][2] + gg[3] * xh[g][3];
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { c1 += __shfl_xor(c1, o); c2 += __shfl_xor(c2, o); }
+    c1 *= invD; c2 *= invD;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int d = lane * 4 + 256 * g;
+      if (d < D) store4<T>(dxr + d, (dyv[g] * gam[g] - c1 - xh[g] * c2) * rs);
+      acc[0][g] += dyv[g];
+      acc[1][g] += dyv[g] * xh[g];
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int d = lane * 4 + 256 * g;
+      if (d < D) *reinterpret_cast<f32x4*>(red + (size_t)wave * D + d) = acc[h][g];
+    }
+    __syncthreads();
+    for (int d = threadIdx.x; d < D; d += 256)
+      partial[((size_t)blockIdx.x * 2 + h) * D + d] = red[d] + red[D + d] + red[2 * D + d] + red[3 * D + d];
+    __syncthreads();
+  }
+}
+
 // A 1x1 conv behind a pre-norm BatchNorm with the batch statistics folded in (what the eval engine's packer does with the running statistics):
 // wf[n][c] = W[n][c] * sa[c] rounded ONCE to the storage type ([N][Kw] rows, zero padded), bf[n] = sum_c W[n][c] * sb[c].  One wave per row.
 template <typename T>
@@ -1602,6 +1716,33 @@ int launch_vit_cls_ln_bwd(const float* dfeat, const void* tokens, const float* m
     return launch(vit_cls_ln_bwd_kernel<T>, B, 64, 0, s, dfeat, tokens, mean, rstd, gamma, dtok, partial, S, D); });
   if (rc) return rc;
   return launch(ln_param_grad_kernel, (D + 3) / 4, 256, 0, s, partial, B, D, dgamma, dbeta);
+}
+// the map kernels hold a row in registers: two instantiations, 2 x 256 channels (the shipped 384) and 9 x 256 (up to 2052, the widest row vit_cls_ln is held to)
+static bool vit_map_ln_shape_ok(int B, int S, int D) { return B >= 1 && S >= 2 && D >= 4 && D % 4 == 0 && D <= 2052; }
+template <typename F> static int with_map_ln_groups(int D, F&& f) {
+  return D <= 512 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 9>{});
+}
+// map [B][S - 1][D], mean / rstd [B * (S - 1)]
+int launch_vit_map_ln_fwd(const void* tokens, const float* gamma, const float* beta, float* map, float* mean, float* rstd, int B, int S, int D, float eps, int dtype,
+                          hipStream_t s) {
+  if (!vit_map_ln_shape_ok(B, S, D)) return (int)hipErrorInvalidValue;
+  const int rows = B * (S - 1);
+  return with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return with_map_ln_groups(D, [&](auto ng) {
+      return launch(vit_map_ln_fwd_kernel<T, decltype(ng)::value>, (rows + 3) / 4, 256, 0, s, tokens, gamma, beta, map, mean, rstd, rows, S, D, eps); }); });
+}
+int vit_map_ln_bwd_blocks(int B, int S) { return (B * S + 31) / 32; }      // 32 rows per workgroup, 8 per wave
+// dfeat / dmap may be null (not both is the caller's business: two nulls give a zero dtok); partial: vit_map_ln_bwd_blocks(B, S) * 2 * D floats
+int launch_vit_map_ln_bwd(const float* dfeat, const float* dmap, const void* tokens, const float* mean0, const float* rstd0, const float* meanp, const float* rstdp,
+                          const float* gamma, void* dtok, float* partial, float* dgamma, float* dbeta, int B, int S, int D, int dtype, hipStream_t s) {
+  if (!vit_map_ln_shape_ok(B, S, D)) return (int)hipErrorInvalidValue;
+  const int nb = vit_map_ln_bwd_blocks(B, S);
+  const int rc = with_elem(dtype, [&](auto e) { using T = elem_t<decltype(e)>;
+    return with_map_ln_groups(D, [&](auto ng) {
+      return launch(vit_map_ln_bwd_kernel<T, decltype(ng)::value>, nb, 256, (size_t)4 * D * sizeof(float), s, dfeat, dmap, tokens, mean0, rstd0, meanp, rstdp, gamma,
+                    dtok, partial, B * S, S, D, 32); }); });
+  if (rc) return rc;
+  return launch(ln_param_grad_kernel, (D + 3) / 4, 256, 0, s, partial, nb, D, dgamma, dbeta);
 }
 
 }  // namespace fsvit

@@ -4,7 +4,7 @@
 //  * cls_pos: token 0 of every image = cls_token + pos_embed[0] (deit.py:200-202).
 //  * layernorm: x_hat = (x - mean) / sqrt(var + eps) per token (nn.LayerNorm eps 1e-6, deit.py:66,71); gamma / beta
 //    are folded into the following Linear by the weight packer.  One wave per token.
-//  * final_ln_cls: norm(x)[:, 0] (deit.py:212-213) with explicit gamma / beta -> fp32 features.
+//  * final_ln_cls: norm(x)[:, 0] (deit.py:212-213) with explicit gamma / beta -> fp32 features; final_ln_map: the patch rows norm(x)[:, 1:] as well.
 #include "fsvit_common.h"
 #include "kernels.h"
 
@@ -105,11 +105,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
   }
 }
 
+// One row of the final norm, by one wave: out[0 .. D) = LN(xr) * gamma + beta in fp32 (two-pass variance; lane `lane` holds the 4-channel groups
+// lane + 64 i, i < 8).  Shared by the cls-only kernel and the one that also returns the patch rows, so that both give the same bits for a row.
 template <typename T>
-__global__ __launch_bounds__(64) void final_ln_cls_kernel(const T* __restrict__ tokens, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta, float* __restrict__ feat, int S, int D, float eps) {
-  const int lane = threadIdx.x, b = blockIdx.x;
-  const T* xr = tokens + (size_t)b * S * D;                        // token 0 of image b
+__device__ __forceinline__ void final_ln_row(const T* __restrict__ xr, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             float* __restrict__ out, int D, float eps, int lane) {
   f32x4 v[8];
   float s = 0.f;
   const int n4 = D / 4;
@@ -135,9 +135,28 @@ __global__ __launch_bounds__(64) void final_ln_cls_kernel(const T* __restrict__ 
     const int c = lane + 64 * i;
     if (c < n4) {
       const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c * 4), bt = *reinterpret_cast<const f32x4*>(beta + c * 4);
-      *reinterpret_cast<f32x4*>(feat + (size_t)b * D + c * 4) = (v[i] - mean) * rstd * g + bt;
+      *reinterpret_cast<f32x4*>(out + c * 4) = (v[i] - mean) * rstd * g + bt;
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void final_ln_cls_kernel(const T* __restrict__ tokens, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ feat, int S, int D, float eps) {
+  const int b = blockIdx.x;
+  final_ln_row<T>(tokens + (size_t)b * S * D, gamma, beta, feat + (size_t)b * D, D, eps, threadIdx.x);      // token 0 of image b
+}
+
+// The final norm on every row (sun_meta_training/models/lvvit.py:552: x_local, x1): row 0 of image b -> feat[b], row 1 + i -> map[b][i] ([B][S - 1][D],
+// token-major).  One wave per row, four rows per workgroup.
+template <typename T>
+__global__ __launch_bounds__(256) void final_ln_map_kernel(const T* __restrict__ tokens, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          float* __restrict__ feat, float* __restrict__ map, int rows, int S, int D, float eps) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int b = r / S, s = r - b * S;
+  float* out = s == 0 ? feat + (size_t)b * D : map + ((size_t)b * (S - 1) + s - 1) * D;
+  final_ln_row<T>(tokens + (size_t)r * D, gamma, beta, out, D, eps, threadIdx.x & 63);
 }
 
 static unsigned grid_for(size_t total) {
@@ -177,6 +196,13 @@ int launch_final_ln_cls(const void* tokens, const float* gamma, const float* bet
   if (B <= 0) return 0;
   if (D % 4 || D > 2048) return (int)hipErrorInvalidValue;
   return with_elem(dtype, [&](auto e) { return launch(final_ln_cls_kernel<elem_t<decltype(e)>>, B, 64, 0, s, tokens, gamma, beta, feat, S, D, eps); });
+}
+
+int launch_final_ln_map(const void* tokens, const float* gamma, const float* beta, float* feat, float* map, int B, int S, int D, float eps, int dtype, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (D % 4 || D > 2048 || S < 2) return (int)hipErrorInvalidValue;
+  const int rows = B * S;
+  return with_elem(dtype, [&](auto e) { return launch(final_ln_map_kernel<elem_t<decltype(e)>>, (rows + 3) / 4, 256, 0, s, tokens, gamma, beta, feat, map, rows, S, D, eps); });
 }
 
 }  // namespace FSVIT_NS

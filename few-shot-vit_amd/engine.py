@@ -252,6 +252,7 @@ class _Trainer:
     nothing is packed ahead of time."""
 
     _fn = {}          # C entry points: create / destroy / workspace_bytes / forward / backward [/ token_grad: the handle takes a token-map gradient]
+    _dfeat_optional = False     # the backward accepts dfeat=None next to a token-map gradient
 
     def _make_cfg(self, cfg: dict):
         raise NotImplementedError
@@ -334,19 +335,22 @@ class _Trainer:
 
     def backward(self, tensors: Dict[str, torch.Tensor], grads: Dict[str, torch.Tensor], dfeat: torch.Tensor, dtokens: torch.Tensor = None):
         """Overwrites grads[name] (same shapes as tensors[name]) from dfeat [B,out_dim] (+ dtokens [B,T,out_dim], the gradient of the
-        token map handed out by `tokens`, Visformer only)."""
-        _require_cuda(dfeat)
+        token map handed out by `tokens`: Visformer and LV-ViT; the LV-ViT trainer takes dfeat=None next to it)."""
+        _require_cuda(dfeat, dtokens)
         if self._keep is None:
             raise RuntimeError('fsvit: backward without a pending train-mode forward (the saved activations were already consumed)')
         if dtokens is not None and 'token_grad' not in self._fn:
             raise NotImplementedError('fsvit: the ViT trainer returns the cls feature only')
-        dfeat = dfeat.contiguous().float()
+        if dfeat is None and (dtokens is None or not self._dfeat_optional):
+            raise ValueError('fsvit: backward needs dfeat')
+        dfeat = dfeat.contiguous().float() if dfeat is not None else None
         arr, keep = self._table(tensors, grads)
         if dtokens is not None:
             dtokens = dtokens.contiguous().float()
             _lib.check(getattr(self.lib, self._fn['token_grad'])(self.h, _ptr(dtokens)))
-        with torch.cuda.device(dfeat.device):
-            _lib.check(getattr(self.lib, self._fn['backward'])(self.h, arr, len(tensors), _ptr(dfeat), _stream_ptr(dfeat.device)))
+        dev = dfeat.device if dfeat is not None else dtokens.device
+        with torch.cuda.device(dev):
+            _lib.check(getattr(self.lib, self._fn['backward'])(self.h, arr, len(tensors), _ptr(dfeat), _stream_ptr(dev)))
         self._keep = None
 
 
@@ -401,13 +405,21 @@ class VitTrainer(_Trainer):
 class LvvitTrainer(_Trainer):
     """Train-mode LV-ViT (lvvit.py:277-317 stem with batch-statistics BatchNorm, :134-155 blocks with the 1 / skip_lam branch scale, DropPath)."""
     _fn = dict(create='fsvit_lvvit_trainer_create', destroy='fsvit_lvvit_trainer_destroy', workspace_bytes='fsvit_lvvit_trainer_workspace_bytes',
-               forward='fsvit_lvvit_train_forward', backward='fsvit_lvvit_train_backward')
+               forward='fsvit_lvvit_train_forward', backward='fsvit_lvvit_train_backward', token_grad='fsvit_lvvit_train_set_token_grad')
+    _dfeat_optional = True      # with a token-map gradient the backward takes "no gradient on the cls feature" as a null pointer
 
     def _make_cfg(self, cfg):
         return LvvitEngine._make_cfg(None, cfg)
 
     def _out_dim(self, cfg):
         return cfg['embed_dim']
+
+    def tokens(self, B: int, tokens_per_image: int = 25) -> torch.Tensor:
+        """The final norm's patch rows [B, 25, out_dim] fp32 of the pending forward (sun_meta_training/models/lvvit.py:552), token-major."""
+        out = torch.empty(B, tokens_per_image, self.out_dim, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fsvit_lvvit_train_tokens(self.h, _ptr(out), _stream_ptr(self.device)))
+        return out
 
     def set_freeze_bn(self, on: bool):
         """The stem's BatchNorm layers in eval mode inside the step (utils.freeze_bn), as VisformerTrainer.set_freeze_bn."""
@@ -441,6 +453,24 @@ class LvvitEngine(_EncoderEngine):
     _fn = dict(create='fsvit_lvvit_create', destroy='fsvit_lvvit_destroy', out_dim='fsvit_lvvit_out_dim',
                workspace_bytes='fsvit_lvvit_workspace_bytes', forward='fsvit_lvvit_forward')
     _default_chunk = 12800      # as the other encoders; shrinks to half of the free device memory in workspace()
+
+    def forward_map(self, x: torch.Tensor):
+        """x [B,3,80,80] fp32 cuda -> (tokens [B,25,out_dim], feat [B,out_dim]) fp32: the final norm's patch rows, token-major, next to the cls feature
+        (sun_meta_training/models/lvvit.py:552); feat holds the bits `forward` gives.  Chunked like `forward`: any B."""
+        _require_cuda(x)
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError('expected [B,3,H,W] input')
+        x = x.contiguous().float()
+        B = x.shape[0]
+        feat = torch.empty(B, self.out_dim, dtype=torch.float32, device=x.device)
+        tokens = torch.empty(B, 25, self.out_dim, dtype=torch.float32, device=x.device)
+        if B == 0:
+            return tokens, feat
+        ws = self.workspace(B)
+        with torch.cuda.device(x.device):
+            _lib.check(self.lib.fsvit_lvvit_forward_map(self.h, _ptr(x), B, x.shape[2], x.shape[3], _ptr(feat), _ptr(tokens), _ptr(ws), ws.numel(),
+                                                        _stream_ptr(x.device)))
+        return tokens, feat
 
     def _make_cfg(self, cfg):
         c = _lib.LvvitCfg()
@@ -1160,6 +1190,29 @@ class ops:
         dgamma, dbeta, partial = ops._scratch(D, tokens.device), ops._scratch(D, tokens.device), ops._scratch(B * 2 * D, tokens.device)
         ops._op(tokens, 'vit_cls_ln_backward', _ptr(dfeat), _ptr(tokens), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dtok), _ptr(partial), _ptr(dgamma), _ptr(dbeta),
                 B, S, D, ops._dt(tokens))
+        return dtok, dgamma, dbeta
+
+    @staticmethod
+    def vit_map_ln_forward(tokens, gamma, beta, eps=1e-6):
+        """The final norm on the patch rows: tokens [B,S,D] -> (map [B,S-1,D] fp32, mean [B*(S-1)], rstd [B*(S-1)])"""
+        _require_cuda(tokens, gamma, beta)
+        B, S, D = tokens.shape
+        rows = B * max(S - 1, 0)
+        fmap = torch.empty(B, max(S - 1, 0), D, dtype=torch.float32, device=tokens.device)
+        mean, rstd = ops._scratch(max(rows, 1), tokens.device), ops._scratch(max(rows, 1), tokens.device)
+        ops._op(tokens, 'vit_map_ln_forward', _ptr(tokens), _ptr(gamma), _ptr(beta), _ptr(fmap), _ptr(mean), _ptr(rstd), B, S, D, float(eps), ops._dt(tokens))
+        return fmap, mean[:rows], rstd[:rows]
+
+    @staticmethod
+    def vit_map_ln_backward(dfeat, dmap, tokens, mean0, rstd0, meanp, rstdp, gamma):
+        """The fused backward of (feat, map): dfeat [B,D] and dmap [B,S-1,D] fp32, either may be None -> (dtok [B,S,D], dgamma, dbeta)"""
+        _require_cuda(dfeat, dmap, tokens, mean0, rstd0, meanp, rstdp, gamma)
+        B, S, D = tokens.shape
+        dtok = torch.empty_like(tokens)
+        nblk = max(_lib.load().fsvit_op_vit_map_ln_bwd_blocks(B, S), 1)
+        dgamma, dbeta, partial = ops._scratch(D, tokens.device), ops._scratch(D, tokens.device), ops._scratch(nblk * 2 * D, tokens.device)
+        ops._op(tokens, 'vit_map_ln_backward', _ptr(dfeat), _ptr(dmap), _ptr(tokens), _ptr(mean0), _ptr(rstd0), _ptr(meanp), _ptr(rstdp), _ptr(gamma), _ptr(dtok),
+                _ptr(partial), _ptr(dgamma), _ptr(dbeta), B, S, D, ops._dt(tokens))
         return dtok, dgamma, dbeta
 
     @staticmethod

@@ -4,9 +4,9 @@ state-dict keys (`classifier.linear.{weight,bias}`, `classifier_local.linear.{we
 
 The Linear layers run on the HIP kernels behind `fsvit_linear_forward / _backward` (autograd.LinearFn); CPU tensors raise
 (no fallback).  `TokenLabelOffline.forward` needs an encoder that returns `(feature map [B, D, H, W], pooled [B, D])` as the
-reference's sun_meta_training Visformer does (models/visformer.py:464): any module with that contract can be passed as
-`encoder=<module>`; wiring the HIP trainer's pre-pool map out through `visformer_micro_80` is the remaining step of SURVEY 8f.2
-(DESIGN.md 7)."""
+reference's sun_meta_training encoders do (models/visformer.py:464, models/lvvit.py:552): `visformer_micro_80` and `lvvit_micro_80` built with
+`return_map=True` (eval engine and HIP trainer both hand the map out), or any module with that contract passed as
+`encoder=<module>`."""
 import math
 
 import torch

@@ -5,7 +5,11 @@ The nn.Module tree only owns parameters and buffers under the reference's key na
 `patch_embed.{conv1,bn1,conv2,bn2,conv3,bn3,downsample.0,downsample.1,proj}.*`, `blocks.N.{norm1,attn.qkv,attn.proj,norm2,mlp.fc1,mlp.fc2}.*`,
 `norm.*`; 118 entries, no qkv bias), so checkpoints saved by the reference load unchanged.  Eval runs on engine.LvvitEngine, model.train() on
 engine.LvvitTrainer (fsvit_lvvit_train_forward / _backward: batch-statistics or frozen BatchNorm in the stem, DropPath, the 1 / skip_lam branch scale,
-every parameter gradient).  Neither has a CPU form: a train-mode call on host tensors raises NotImplementedError."""
+every parameter gradient).  Neither has a CPU form: a train-mode call on host tensors raises NotImplementedError.
+
+`return_map=True` is the encoder of the classifier / distillation phases (sun_meta_training/models/lvvit.py:529-552, which differs from the file above in
+its return line only): forward returns `(x_local [B,embed_dim,5,5], x1 [B,embed_dim])`, the final norm's patch rows next to the cls feature - eval through
+LvvitEngine.forward_map, train through autograd.LvvitTrainMapFn (fsvit_lvvit_train_tokens / fsvit_lvvit_train_set_token_grad)."""
 import torch
 import torch.nn as nn
 
@@ -100,13 +104,14 @@ class LvVit(EngineHost, nn.Module):
         return torch.rand(len(keep), n_img, device=device).add_(torch.tensor(keep, device=device).unsqueeze(1)).floor_()
 
     def forward(self, x, droppath_masks=None):
-        """[B,3,80,80] fp32 -> [B,embed_dim] = norm(tokens)[:, 0] (lvvit.py:529-546).  eval: packed engine; train: the HIP trainer through the autograd
-        bridge of the other encoders (`droppath_masks` overrides the random draws)."""
-        if self.return_map:
-            raise NotImplementedError('fsvit: LV-ViT returns the cls feature only; the (map, pooled) output of the classifier / distillation '
-                                      'phase is not built (evaluate a teacher through load_encoder + meta-baseline)')
+        """[B,3,80,80] fp32 -> [B,embed_dim] = norm(tokens)[:, 0] (lvvit.py:529-546); with return_map (x_local [B,embed_dim,5,5], x1 [B,embed_dim]), x_local
+        a view of the token-major patch rows.  eval: packed engine; train: the HIP trainer through the autograd bridge of the other encoders
+        (`droppath_masks` overrides the random draws)."""
         if not self.training:
-            return self.engine().forward(x)
+            if not self.return_map:
+                return self.engine().forward(x)
+            tokens, feat = self.engine().forward_map(x)
+            return self._as_map(tokens), feat
         if self.pos_embed.device.type != 'cuda' or not x.is_cuda:
             raise NotImplementedError(_NO_CPU_TRAIN % (self.pos_embed.device if self.pos_embed.device.type != 'cuda' else x.device))
         assert x.shape[-2] == self.img_size and x.shape[-1] == self.img_size, \
@@ -117,16 +122,25 @@ class LvVit(EngineHost, nn.Module):
         frozen = bn_modes == {False}                    # utils.freeze_bn (train_meta.py:156-157): running statistics normalise, nothing is updated
         trainer = self.trainer()
         trainer.set_freeze_bn(frozen)
-        from ..autograd import VisformerTrainFn
+        from ..autograd import LvvitTrainMapFn, VisformerTrainFn
         named = [(k, p) for k, p in self.named_parameters()]
         names = tuple(k for k, _ in named)
         buffers = {k: b for k, b in self.named_buffers() if not k.endswith('num_batches_tracked')}
         masks = droppath_masks if droppath_masks is not None else self.draw_droppath_masks(x.shape[0], x.device)
         trainer.grad_sink = getattr(self, '_grad_sink', None)       # parallel.GradBucket: gradients land in the flat all-reduce buffer
-        feat = VisformerTrainFn.apply(x, trainer, names, buffers, self.drop_path_rate, masks, *[p for _, p in named])
+        if self.return_map:
+            tokens, feat = LvvitTrainMapFn.apply(x, trainer, names, buffers, self.drop_path_rate, masks, *[p for _, p in named])
+        else:
+            feat = VisformerTrainFn.apply(x, trainer, names, buffers, self.drop_path_rate, masks, *[p for _, p in named])
         if not frozen:      # nn.BatchNorm2d counts its train-mode forwards
             torch._foreach_add_([b for k, b in self.named_buffers() if k.endswith('num_batches_tracked')], 1)
-        return feat
+        return (self._as_map(tokens), feat) if self.return_map else feat
+
+    @staticmethod
+    def _as_map(tokens):
+        """tokens [B,25,D] token-major -> the reference's x_local [B,D,5,5] (lvvit.py:550-551), as a view"""
+        B, T, D = tokens.shape
+        return tokens.permute(0, 2, 1).reshape(B, D, 5, 5)
 
 
 @register('lvvit_micro_80')

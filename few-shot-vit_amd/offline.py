@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """SUN meta-training (teacher -> student token-label distillation) driver with the reference's CLI / YAML surface
-(sun_meta_training/offline.py:78-461): supervised training of `token-label` over a Visformer encoder - global cross-entropy on the
+(sun_meta_training/offline.py:78-461): supervised training of `token-label` over a Visformer or LV-ViT encoder - global cross-entropy on the
 pooled feature + `token_label_weight`-free `0.5 *` SoftTargetCrossEntropy on the student's 25 token logits against soft labels generated
 from the frozen teacher's token logits (top-k scatter + background tokens), AdamW(lr * batch_size / 512) with a cosine schedule and
 linear warm-up stepped with (epoch - 1), few-shot `val` episodes scored by cosine prototypes on the pooled feature, checkpoints in the

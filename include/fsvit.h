@@ -152,6 +152,11 @@ int fsvit_lvvit_out_dim(const fsvit_lvvit* h);
 size_t fsvit_lvvit_workspace_bytes(const fsvit_lvvit* h, int chunk_images);
 int fsvit_lvvit_forward(fsvit_lvvit* h, const float* x_nchw_dev, int n_img, int img_h, int img_w, float* feat_dev,
                         void* ws_dev, size_t ws_bytes, void* stream);
+/* The same forward with the token map next to the cls feature (sun_meta_training/models/lvvit.py:552 returns x_local, x1): tokens_dev
+ * [n_img][25][embed_dim] fp32 = norm(x)[:, 1:], token-major (the caller's permute gives the reference's [n_img, embed_dim, 5, 5]).  Chunked like the plain
+ * forward, every chunk's rows at its image offset - any n_img; feat_dev holds the same bits as the plain forward's. */
+int fsvit_lvvit_forward_map(fsvit_lvvit* h, const float* x_nchw_dev, int n_img, int img_h, int img_w, float* feat_dev, float* tokens_dev, void* ws_dev,
+                            size_t ws_bytes, void* stream);
 
 /* LV-ViT stem conv2 (pool = 0) or conv3 + downsample tail + LeakyReLU + MaxPool2d(2) (pool = 1) at 96 channels on the dedicated kernel: x NHWC
  * [B][H][W][96] (bf16 / f16, W = 40, H a multiple of 8), w the 128-channel weight image [128][9 * 128 (+ 64)] (k = tap * 128 + c, zero past 96
@@ -394,6 +399,12 @@ int fsvit_lvvit_trainer_set_freeze_bn(fsvit_lvvit_trainer* t, int on);
 int fsvit_lvvit_train_forward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* x_nchw_dev, int n_img, int img_h, int img_w,
                               float drop_path_rate, const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream);
 int fsvit_lvvit_train_backward(fsvit_lvvit_trainer* t, const fsvit_param* params, int n_params, const float* dfeat_dev, void* stream);
+/* The token map of the pending train_forward (tokens_dev [n_img][25][embed_dim] fp32, the final norm on the patch rows) and its gradient for the
+ * train_backward of that forward - the contract of the Visformer pair above.  train_tokens is valid between a train_forward and its train_backward
+ * (FSVIT_ERR_ARG otherwise).  set_token_grad arms the next train_backward only, which then needs train_tokens to have run and accepts a NULL dfeat_dev
+ * (no gradient on the cls feature); without it the backward is the cls-only one, bit for bit. */
+int fsvit_lvvit_train_tokens(fsvit_lvvit_trainer* t, float* tokens_dev, void* stream);
+int fsvit_lvvit_train_set_token_grad(fsvit_lvvit_trainer* t, const float* dtokens_dev);
 
 /* Backward of fsvit_proto_head, method 'cos' (meta_baseline.py:33-47): dlogits [E,Q,way] -> dfeat_shot [E,way,shot,D],
  * dfeat_query [E,Q,D], dtemp_per_episode [E] (sum it for the learnable temperature, meta_baseline.py:20-21). */
@@ -574,6 +585,15 @@ int fsvit_op_vit_cls_ln_forward(const void* tokens, const float* gamma, const fl
                                 int dtype, void* stream);
 int fsvit_op_vit_cls_ln_backward(const float* dfeat, const void* tokens, const float* mean, const float* rstd, const float* gamma, void* dtok, float* partial,
                                  float* dgamma, float* dbeta, int B, int S, int D, int dtype, void* stream);
+/* The final norm on the patch rows (map [B][S - 1][D] fp32, mean / rstd [B * (S - 1)]) and the fused backward of both outputs: row 0 of dtok[b] from
+ * dfeat[b] (statistics mean0 / rstd0 [B] of the cls forward), row 1 + i from dmap[b][i] (meanp / rstdp of the map forward); a NULL source gives zero rows
+ * and adds nothing to dgamma / dbeta; every row of dtok is written.  S >= 2, D a multiple of 4 up to 2052; partial: the block count below * 2 * D floats. */
+int fsvit_op_vit_map_ln_forward(const void* tokens, const float* gamma, const float* beta, float* map, float* mean, float* rstd, int B, int S, int D, float eps,
+                                int dtype, void* stream);
+int fsvit_op_vit_map_ln_bwd_blocks(int B, int S);
+int fsvit_op_vit_map_ln_backward(const float* dfeat, const float* dmap, const void* tokens, const float* mean0, const float* rstd0, const float* meanp,
+                                 const float* rstdp, const float* gamma, void* dtok, float* partial, float* dgamma, float* dbeta, int B, int S, int D, int dtype,
+                                 void* stream);
 
 /* Elementwise / small reductions.  gelu: dh NULL -> out = gelu(z), else out = dh * gelu'(z) (erf form); add_scaled: out = a + scale[i / per_img] * br
  * (a, scale may be NULL); avgpool_bwd: dx[b][hw][c] = dfeat[b][c] / HW; batch_sum: out[i] = sum_b g[b][i]; bcast_add: y[b][i] = x[b][i] + p[i];

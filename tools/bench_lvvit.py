@@ -5,7 +5,12 @@ dense MFMA peak.  Usage: python tools/bench_lvvit.py [--numerics bf16] [--steps 
 
 --mode train: one meta-tuning step (forward, cross-entropy, backward) of EPISODES 5-way 1-shot 3-query episodes (default 40 = 800 images) on the
 HIP trainer, timed with HIP events.  Both weight-gradient routes of the dense 96 -> 96 stem layers are built in the same process (--routes: the
-direct kernel under FSVIT_LVVIT_WGRAD=direct, the transposed split-K GEMM under =gemm) and their steps ALTERNATE; medians per route are printed."""
+direct kernel under FSVIT_LVVIT_WGRAD=direct, the transposed split-K GEMM under =gemm) and their steps ALTERNATE; medians per route are printed.
+--return-map: the same step with the encoder's (token map, cls) output and a loss on both (cross-entropy on the head + mean(map * w)): what the fused
+final-norm backward and the fp32 map cost on top of the cls-only step (plus the three torch kernels of that extra loss term).
+
+--mode distill: one offline.distill_step (student forward with both outputs, frozen teacher forward, soft labels, both losses, backward, AdamW) of
+`token-label` over lvvit_micro_80 at --batch images (default 512, the reference's batch size), timed with HIP events."""
 import argparse
 import json
 import os
@@ -31,13 +36,25 @@ def train_step(args):
     xs = torch.randn(E, way, shot, 3, 80, 80, device=dev, generator=g)
     xq = torch.randn(E, way * query, 3, 80, 80, device=dev, generator=g)
     label = fs.make_nk_label(way, query, E).to(dev)
+    n_shot = E * way * shot
+    wtok = torch.randn(E * way * (shot + query), 5, 5, 384, device=dev, generator=g)
+
+    def loss_of(m):
+        if not args.return_map:
+            return F.cross_entropy(m(xs, xq).view(-1, way), label)
+        from fewshot_vit_amd.autograd import ProtoHeadFn
+        fmap, feat = m.encoder(torch.cat([xs.reshape(-1, 3, 80, 80), xq.reshape(-1, 3, 80, 80)], dim=0))      # MetaBaseline._forward_train with the map kept
+        logits = ProtoHeadFn.apply(feat[:n_shot].view(E, way, shot, -1), feat[n_shot:].view(E, way * query, -1),
+                                   m.temp if isinstance(m.temp, torch.Tensor) else torch.tensor(float(m.temp)), m.method)
+        return F.cross_entropy(logits.view(-1, way), label) + (fmap.permute(0, 2, 3, 1) * wtok).mean()      # (token-major, as token-label's heads read the map)
+
     routes = {}
     for route in args.routes.split(','):                    # the switch is read when the trainer handle is created (first train-mode forward)
         os.environ['FSVIT_LVVIT_WGRAD'] = route
-        m = models.make('meta-baseline', encoder='lvvit_micro_80', encoder_args={'numerics': args.numerics})
+        m = models.make('meta-baseline', encoder='lvvit_micro_80', encoder_args={'numerics': args.numerics, 'return_map': args.return_map})
         m.load_state_dict(synthetic.synthetic_checkpoint_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}, calib='lvvit_micro_80'))
         m = m.to(dev).train()
-        F.cross_entropy(m(xs, xq).view(-1, way), label).backward()
+        loss_of(m).backward()
         routes[route] = m
     os.environ.pop('FSVIT_LVVIT_WGRAD', None)
 
@@ -45,7 +62,7 @@ def train_step(args):
         m.zero_grad(set_to_none=True)
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        loss = F.cross_entropy(m(xs, xq).view(-1, way), label)
+        loss = loss_of(m)
         loss.backward()
         t1.record()
         t1.synchronize()
@@ -62,9 +79,44 @@ def train_step(args):
     for r in routes:
         print(f'{r:7s} samples (ms): ' + ' '.join(f'{v:.2f}' for v in ms[r]))
     med = {r: statistics.median(v) for r, v in ms.items()}
-    print(json.dumps({'metric': 'lvvit_micro_80_meta_tuning_step_ms', 'numerics': args.numerics, 'images': n_img, 'unit': 'ms',
+    print(json.dumps({'metric': 'lvvit_micro_80_meta_tuning_step_ms', 'numerics': args.numerics, 'images': n_img, 'unit': 'ms', 'return_map': args.return_map,
                       **{f'wgrad96_{r}_route_ms': round(v, 3) for r, v in med.items()}, 'samples_per_route': args.steps, 'alternated': True,
                       'device': torch.cuda.get_device_name(dev)}))
+
+
+def distill(args):
+    import statistics
+    from fewshot_vit_amd import offline
+    from fewshot_vit_amd.models.classifier import FsvitAdamW, SoftTargetCrossEntropy
+    dev = torch.device('cuda', 0)
+    B, n_classes = args.batch, 64
+    g = torch.Generator(device=dev).manual_seed(0)
+    data = torch.randn(B, 3, 80, 80, device=dev, generator=g)
+    weak = torch.randn(B, 3, 80, 80, device=dev, generator=g)
+    label = torch.randint(0, n_classes, (B,), device=dev, generator=g)
+    pair = []
+    for _ in range(2):
+        m = models.make('token-label', encoder='lvvit_micro_80', encoder_args={'numerics': args.numerics, 'return_map': True, 'drop_path_rate': 0.1},
+                        classifier='linear-classifier', classifier_args={'n_classes': n_classes})
+        esd = synthetic.synthetic_checkpoint_sd({'encoder.' + k: tuple(v.shape) for k, v in m.encoder.state_dict().items()}, calib='lvvit_micro_80')
+        m.encoder.load_state_dict({k[len('encoder.'):]: v for k, v in esd.items()})
+        pair.append(m.to(dev))
+    model, teacher = pair[0].train(), pair[1].eval()
+    opt = FsvitAdamW(model.parameters(), lr=5e-4 * B / 512, weight_decay=0.05)
+    crit = SoftTargetCrossEntropy()
+    ms = []
+    for i in range(args.warmup + args.steps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        loss, _ = offline.distill_step(model, teacher, opt, crit, data, weak, label)
+        t1.record()
+        t1.synchronize()
+        assert torch.isfinite(loss)
+        if i >= args.warmup:
+            ms.append(t0.elapsed_time(t1))
+    print('samples (ms): ' + ' '.join(f'{v:.2f}' for v in ms))
+    print(json.dumps({'metric': 'lvvit_micro_80_distill_step_ms', 'numerics': args.numerics, 'images': B, 'unit': 'ms', 'value': round(statistics.median(ms), 3),
+                      'min': round(min(ms), 3), 'max': round(max(ms), 3), 'samples': args.steps, 'device': torch.cuda.get_device_name(dev)}))
 
 
 def main():
@@ -73,11 +125,15 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--episodes', type=int, default=None)
-    ap.add_argument('--mode', choices=['eval', 'train'], default='eval')
+    ap.add_argument('--mode', choices=['eval', 'train', 'distill'], default='eval')
+    ap.add_argument('--return-map', action='store_true', help='--mode train: the encoder returns (token map, cls) and the loss uses both')
+    ap.add_argument('--batch', type=int, default=512, help='--mode distill: images per step')
     ap.add_argument('--routes', default='direct,gemm', help='--mode train: the weight-gradient routes to build and alternate (one name for a kernel trace)')
     args = ap.parse_args()
     if args.mode == 'train':
         return train_step(args)
+    if args.mode == 'distill':
+        return distill(args)
     if args.episodes is None:
         args.episodes = 128
     dev = torch.device('cuda', 0)
