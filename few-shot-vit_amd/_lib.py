@@ -191,6 +191,12 @@ SIGNATURES = {
     'fsvit_op_gconv3x3_train': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_op_stage1_block_train': (_i, [_vp, _vp, _vp, _fp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_op_stage1_block_dgrad': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    # DeepEMD head (emd_head.hip)
+    'fsvit_emd_head_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'fsvit_emd_head_forward': (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _vp, _vp, _sz, _vp]),
+    'fsvit_emd_head_backward': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _vp, _sz, _vp]),
+    'fsvit_op_emd_solve': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp]),
+    'fsvit_op_emd_solve_counts': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp, _vp]),
     'fsvit_sampler_draw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 

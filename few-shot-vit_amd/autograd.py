@@ -200,3 +200,23 @@ class SoftTargetCEFn(torch.autograd.Function):
     def backward(ctx, dloss):
         (dz,) = ctx.saved_tensors
         return dz * dloss, None
+
+
+class EmdHeadFn(torch.autograd.Function):
+    """(logits [E,Q,P], status [E,Q,P]) = DeepEMD head of proto token maps [E,P,N,C] and query token maps [E,Q,N,C]
+    (meta_tuning_sun_d/Models/models/Network.py:67-81,:109-124).  The optimal flows are saved and treated as constants in the backward
+    (`solver: opencv`, :118-120); the weight vectors carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, shot_tok, query_tok, temperature):
+        logits, flow, status = ops.emd_head_forward(shot_tok, query_tok, temperature, want_flow=True)
+        ctx.save_for_backward(shot_tok, query_tok, flow)
+        ctx.temperature = float(temperature)
+        ctx.mark_non_differentiable(status)
+        return logits, status
+
+    @staticmethod
+    def backward(ctx, dlogits, _dstatus):
+        shot_tok, query_tok, flow = ctx.saved_tensors
+        ds, dq = ops.emd_head_backward(shot_tok, query_tok, dlogits, flow, ctx.temperature)
+        return ds.view_as(shot_tok), dq.view_as(query_tok), None

@@ -1,0 +1,454 @@
+// DeepEMD head (meta_tuning_sun_d/Models/models/Network.py:48-175, emd_utils.py:65-76): a query is scored against a class by the earth mover's
+// distance between the token maps of the two images.  fp32 throughout, in every numerics mode (the token map arrives as fp32).
+//  * emd_prep_kernel: per token the channel mean, the centred vector (normalize_feature 'center', :143-146) scaled by 1 / max(|x|, 1e-8)
+//    (F.cosine_similarity's clamp: a constant token gives similarity 0), and per image the token mean of the UN-centred map
+//    (adaptive_avg_pool2d in get_weight_vector, which runs before the centring, :70-74).
+//  * emd_pair_kernel: one wavefront per (query, proto) problem, four problems per workgroup.  Cost c = 1 - cosine similarity [query node][proto node]
+//    (:151-167) and both weight vectors (:48-65, emd_utils.py:69-73) are formed in registers / LDS, the transportation problem is solved exactly in
+//    place, and logit = temperature / N * sum (1 - c) F (:118-124).  The similarity map never reaches HBM.
+//  * emd_solve_wave: successive shortest augmenting paths with node potentials, one lane per node (rows on lanes 0 .. N-1, columns on lanes 32 .. 32+N-1),
+//    from a starting dual (column minima) and a greedy starting flow on its tight arcs.
+//    Every loop has a static bound (augmentations <= 8 N, Dijkstra steps <= 2 N + 1, path trace <= N + 1); a problem that reaches one writes status 1
+//    and stops.  No block barrier anywhere: the waves of a workgroup run problems of different lengths.
+//  * emd_bwd_kernel: flows are constants (the reference's `solver: opencv` semantics, :118-120): dS = dlogit * temperature / N * F.  One workgroup per
+//    image looping over its partners, no atomics, deterministic.
+#include "fsvit_common.h"
+#include "kernels.h"
+#include "../../include/fsvit.h"
+
+namespace fsvit {
+
+constexpr int EMD_PITCH = 33;                      // N + 1 at N = 32: row scans and column scans of c / F are both bank-conflict free
+constexpr int EMD_TILE = 32 * EMD_PITCH;
+constexpr int EMD_WAVES = 4;
+constexpr float EMD_SNAP = 1e-6f;                  // residual supply / demand / reverse flow below this is zero
+constexpr float EMD_INF = 3.0e38f;
+
+// Wave-wide minimum of non-negative keys on the DPP network (no LDS crossbar round trips: this sits on the critical path of every Dijkstra step):
+// prefix minimum inside each row of 16 (row_shr 1, 2, 4, 8), lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast15), lane 31 into rows 2 / 3
+// (row_bcast31); lane 63 then holds the minimum.  Lanes a step does not reach keep EMD_INF as the incoming value.
+// (The keys are non-negative floats, never -0: their bit patterns order like unsigned integers, and the unsigned minimum with its identity as the
+// incoming value folds into one v_min_u32 with a DPP operand per step.)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned emd_dpp_min(unsigned v) {
+  const unsigned in = (unsigned)__builtin_amdgcn_update_dpp((int)0xffffffffu, (int)v, CTRL, ROW_MASK, 0xf, false);
+  return v < in ? v : in;
+}
+__device__ __forceinline__ float emd_lane_f(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+__device__ __forceinline__ int emd_lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }      // l is wave-uniform at every call
+__device__ __forceinline__ float emd_wave_min(float key) {
+  unsigned v = __builtin_bit_cast(unsigned, key);
+  v = emd_dpp_min<0x111, 0xf>(v);
+  v = emd_dpp_min<0x112, 0xf>(v);
+  v = emd_dpp_min<0x114, 0xf>(v);
+  v = emd_dpp_min<0x118, 0xf>(v);
+  v = emd_dpp_min<0x142, 0xa>(v);
+  v = emd_dpp_min<0x143, 0xc>(v);
+  return __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_readlane((int)v, 63));
+}
+
+// c, F: this wave's [32][EMD_PITCH] tiles in LDS (c zero outside N x N, F all zero); rem: this lane's supply (row lanes) or demand (column lanes).
+// Returns the status; F holds the optimal flow.  Potentials: reduced cost of the forward arc i -> j is c_ij + pu_i - pv_j, of the reverse arc
+// j -> i (present where F_ij > 0) its negative; both are clamped at 0 against fp32 rounding.
+__device__ __forceinline__ int emd_solve_wave(const float* c, float* F, const int N, float rem, const int lane, int* naug_out) {
+  const bool is_row = lane < 32;
+  const int me = lane & 31;
+  const bool valid = me < N;
+  if (!valid) rem = 0.f;
+  float pot = 0.f;
+  int status = 0, it = 0;
+  const int max_aug = 8 * N;
+  // Starting dual and flow: pv_j = min_i c_ij keeps every forward arc at a non-negative reduced cost and the arcs that attain the minimum at 0; each
+  // column in turn then hands its demand to its cheapest row while that row has supply left.  Flow sits only on arcs of reduced cost 0, which is all the
+  // searches below need; N short uniform steps save about a third of them.
+  {
+    float cmin = EMD_INF;
+    int arg = 0;
+    for (int i = 0; i < N; ++i) {
+      const float v = c[i * EMD_PITCH + me];
+      if (v < cmin) { cmin = v; arg = i; }
+    }
+    if (!is_row && valid) pot = cmin;
+    for (int j = 0; j < N; ++j) {
+      const int r = emd_lane_i(arg, 32 + j) & 31;
+      const float d = fminf(emd_lane_f(rem, r), emd_lane_f(rem, 32 + j));
+      if (d > 0.f) {
+        if (lane == 0) F[r * EMD_PITCH + j] = d;
+        if (lane == r || lane == 32 + j) {
+          const float x = rem - d;
+          rem = x < EMD_SNAP ? 0.f : x;
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  }
+  for (; it < max_aug; ++it) {
+    const unsigned long long src_mask = __ballot(is_row && rem > 0.f);
+    const unsigned long long dem_mask = __ballot(!is_row && rem > 0.f);
+    if (!src_mask || !dem_mask) break;
+    // multi-source Dijkstra from the rows with supply left, until the first column with demand left
+    float dist = (is_row && rem > 0.f) ? 0.f : EMD_INF;
+    bool vis = false;
+    int par = -1, tgt = -1;
+    float D = 0.f;
+    for (int step = 0; step <= 2 * N; ++step) {
+      const float key = (valid && !vis) ? dist : EMD_INF;
+      const float dmin = emd_wave_min(key);
+      if (!(dmin < EMD_INF)) break;
+      const unsigned long long ties = __ballot(key == dmin);
+      const unsigned long long hit = ties & dem_mask;
+      if (hit) { tgt = __ffsll((long long)hit) - 1 - 32; D = dmin; break; }
+      if (!ties) break;                                       // (a NaN key: cannot happen with finite costs; never index with ffs(0) - 1)
+      const int u = __ffsll((long long)ties) - 1;
+      if (lane == u) vis = true;
+      const bool urow = u < 32;
+      const int ui = u & 31;
+      const float pu = emd_lane_f(pot, u);
+      const int idx = urow ? ui * EMD_PITCH + me : me * EMD_PITCH + ui;      // < EMD_TILE for every lane
+      const float cv = c[idx], fv = F[idx];
+      const float rc = fmaxf((urow ? cv : -cv) + pu - pot, 0.f);
+      const float nd = dmin + rc;
+      const bool can = valid && !vis && (is_row != urow) && (urow || fv > 0.f);
+      if (can && nd < dist) { dist = nd; par = ui; }
+    }
+    if (tgt < 0) { status = 1; break; }
+    tgt &= 31;
+    if (vis) pot += dist - D;
+    // bottleneck along the path: demand left at the target, reverse flows, supply left at the source
+    int cur = tgt, src = -1;
+    float delta = emd_lane_f(rem, 32 + tgt);
+    for (int k = 0; k <= N; ++k) {
+      const int i = emd_lane_i(par, 32 + cur) & 31;
+      const int pj = emd_lane_i(par, i);
+      if (pj < 0) { src = i; delta = fminf(delta, emd_lane_f(rem, i)); break; }
+      delta = fminf(delta, F[i * EMD_PITCH + (pj & 31)]);
+      cur = pj & 31;
+    }
+    if (src < 0 || !(delta > 0.f)) { status = 1; break; }
+    cur = tgt;
+    for (int k = 0; k <= N; ++k) {
+      const int i = emd_lane_i(par, 32 + cur) & 31;
+      const int pj = emd_lane_i(par, i);
+      if (lane == 0) F[i * EMD_PITCH + cur] += delta;
+      if (pj < 0) break;
+      if (lane == 0) {
+        const float f = F[i * EMD_PITCH + (pj & 31)] - delta;
+        F[i * EMD_PITCH + (pj & 31)] = f < EMD_SNAP ? 0.f : f;
+      }
+      cur = pj & 31;
+    }
+    if (lane == src || lane == 32 + tgt) {
+      const float r = rem - delta;
+      rem = r < EMD_SNAP ? 0.f : r;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // lane 0's flow updates before the next search reads them
+  }
+  if (status == 0) {
+    const bool more = __ballot(is_row && rem > 0.f) != 0ull && __ballot(!is_row && rem > 0.f) != 0ull;
+    if (it >= max_aug && more) status = 1;                     // augmentation bound
+    float left = rem;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) left = fmaxf(left, __shfl_xor(left, o, 64));
+    if (left > 1e-3f) status = 1;                              // supply without demand (or the reverse): the weight sums differ
+  }
+  if (naug_out && lane == 0) *naug_out = it;
+  return status;
+}
+
+__global__ __launch_bounds__(64 * EMD_WAVES) void emd_solve_kernel(const float* __restrict__ cost, const float* __restrict__ w1, const float* __restrict__ w2,
+                                                                   int B, int N, float* __restrict__ flow, int* __restrict__ status, int* __restrict__ naug) {
+  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int b = blockIdx.x * EMD_WAVES + wave;
+  if (b >= B) return;
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  const float* cb = cost + (size_t)b * N * N;
+  for (int idx = lane; idx < EMD_TILE; idx += 64) {
+    const int a = idx / EMD_PITCH, bb = idx - a * EMD_PITCH;
+    c[idx] = (a < N && bb < N) ? cb[a * N + bb] : 0.f;
+    F[idx] = 0.f;
+  }
+  const int me = lane & 31;
+  float rem = 0.f;
+  if (me < N) rem = lane < 32 ? w1[(size_t)b * N + me] : w2[(size_t)b * N + me];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  const int st = emd_solve_wave(c, F, N, rem, lane, naug ? naug + b : nullptr);
+  float* fb = flow + (size_t)b * N * N;
+  for (int idx = lane; idx < EMD_TILE; idx += 64) {
+    const int a = idx / EMD_PITCH, bb = idx - a * EMD_PITCH;
+    if (a < N && bb < N) fb[a * N + bb] = F[idx];
+  }
+  if (lane == 0) status[b] = st;
+}
+
+// tok [n_img][N][C] -> xhat [n_img][N][C], pooled [n_img][C], rn [n_img][N]
+__global__ __launch_bounds__(256) void emd_prep_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok, int n_shot, int N, int C,
+                                                       float* __restrict__ xhat, float* __restrict__ pooled, float* __restrict__ rn) {
+  const int img = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float* x = img < n_shot ? shot_tok + (size_t)img * N * C : query_tok + (size_t)(img - n_shot) * N * C;
+  float* xh = xhat + (size_t)img * N * C;
+  for (int n = wave; n < N; n += 4) {
+    float s = 0.f;
+    for (int k = lane; k < C; k += 64) s += x[n * C + k];
+    const float mean = wave_sum(s) / (float)C;
+    float ss = 0.f;
+    for (int k = lane; k < C; k += 64) { const float d = x[n * C + k] - mean; ss += d * d; }
+    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-8f);
+    for (int k = lane; k < C; k += 64) xh[n * C + k] = (x[n * C + k] - mean) * inv;
+    if (lane == 0) rn[(size_t)img * N + n] = inv;
+  }
+  for (int k = threadIdx.x; k < C; k += 256) {
+    float s = 0.f;
+    for (int n = 0; n < N; ++n) s += x[n * C + k];
+    pooled[(size_t)img * C + k] = s / (float)N;
+  }
+}
+
+__global__ __launch_bounds__(64 * EMD_WAVES) void emd_pair_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok,
+                                                                  const float* __restrict__ xhat, const float* __restrict__ pooled, int E, int P, int Q,
+                                                                  int N, int C, float scale, float* __restrict__ logits, float* __restrict__ flow,
+                                                                  int* __restrict__ status) {
+  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long prob = (long long)blockIdx.x * EMD_WAVES + wave;
+  if (prob >= (long long)E * Q * P) return;
+  const int p = (int)(prob % P);
+  const long long eq = prob / P;                 // e * Q + q
+  const int e = (int)(eq / Q);
+  const size_t ip = (size_t)e * P + p, iq = (size_t)E * P + (size_t)eq;      // image indices in the workspace (protos first)
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  for (int idx = lane; idx < EMD_TILE; idx += 64) F[idx] = 0.f;
+  if (lane < 32) c[lane * EMD_PITCH + 32] = 0.f;
+  // c[a][b] = 1 - <xhat_q[a], xhat_p[b]>: lane (la, lb) of an 8 x 8 grid owns a = la + 8 r, b = lb + 8 s
+  {
+    const int la = lane >> 3, lb = lane & 7;
+    const float* xq = xhat + iq * N * C;
+    const float* xp = xhat + ip * N * C;
+    const float *qa[4], *pb[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      qa[r] = xq + (size_t)min(la + 8 * r, N - 1) * C;
+      pb[r] = xp + (size_t)min(lb + 8 * r, N - 1) * C;
+    }
+    float acc[4][4] = {};
+    for (int k = 0; k < C; k += 4) {
+      f32x4 va[4], vb[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        va[r] = *reinterpret_cast<const f32x4*>(qa[r] + k);
+        vb[r] = *reinterpret_cast<const f32x4*>(pb[r] + k);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+          acc[r][s] += va[r][0] * vb[s][0] + va[r][1] * vb[s][1] + va[r][2] * vb[s][2] + va[r][3] * vb[s][3];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int a = la + 8 * r, b = lb + 8 * s;
+        c[a * EMD_PITCH + b] = (a < N && b < N) ? 1.0f - acc[r][s] : 0.f;
+      }
+  }
+  // weights: w1[a] = relu(<query token a, pooled proto>) + 1e-3 on the row lanes, w2[b] = relu(<proto token b, pooled query>) + 1e-3 on the column lanes
+  const int me = lane & 31;
+  const bool is_row = lane < 32, valid = me < N;
+  float w = 0.f;
+  {
+    const float* tq = query_tok + (size_t)eq * N * C;
+    const float* tp = shot_tok + ip * N * C;
+    const float* gq = pooled + iq * C;
+    const float* gp = pooled + ip * C;
+    for (int n = 0; n < N; ++n) {
+      float s1 = 0.f, s2 = 0.f;
+      for (int k = lane * 4; k < C; k += 256) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(tq + (size_t)n * C + k), g = *reinterpret_cast<const f32x4*>(gp + k);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(tp + (size_t)n * C + k), h = *reinterpret_cast<const f32x4*>(gq + k);
+        s1 += a[0] * g[0] + a[1] * g[1] + a[2] * g[2] + a[3] * g[3];
+        s2 += b[0] * h[0] + b[1] * h[1] + b[2] * h[2] + b[3] * h[3];
+      }
+      s1 = wave_sum(s1);
+      s2 = wave_sum(s2);
+      if (lane == n) w = s1;
+      if (lane == 32 + n) w = s2;
+    }
+  }
+  w = valid ? fmaxf(w, 0.f) + 1e-3f : 0.f;                       // get_weight_vector (:64)
+  w = valid ? fmaxf(w, 0.f) + 1e-5f : 0.f;                       // emd_inference_opencv (emd_utils.py:69-70)
+  const float srow = wave_sum(is_row ? w : 0.f), scol = wave_sum(is_row ? 0.f : w);
+  w *= (float)N / (is_row ? srow : scol);                        // both sum to N (emd_utils.py:72-73)
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  const int st = emd_solve_wave(c, F, N, w, lane, nullptr);
+  float s = 0.f;
+  for (int idx = lane; idx < EMD_TILE; idx += 64) s += (1.0f - c[idx]) * F[idx];
+  s = wave_sum(s);
+  if (lane == 0) {
+    logits[prob] = s * scale;
+    status[prob] = st;
+  }
+  if (flow) {
+    float* fb = flow + (size_t)prob * N * N;
+    for (int idx = lane; idx < EMD_TILE; idx += 64) {
+      const int a = idx / EMD_PITCH, b = idx - a * EMD_PITCH;
+      if (a < N && b < N) fb[a * N + b] = F[idx];
+    }
+  }
+}
+
+// One workgroup per image (protos first, then queries), one wave per token.  d xhat = sum over partners and their tokens of g * F * partner xhat
+// (g = dlogit * temperature / N), then back through x / max(|x|, 1e-8): rn (d xhat - xhat <xhat, d xhat>), then through the centring: minus the channel mean.
+__global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ xhat, const float* __restrict__ rn, const float* __restrict__ dlogits,
+                                                      const float* __restrict__ flow, int E, int P, int Q, int N, int C, float scale,
+                                                      float* __restrict__ d_shot, float* __restrict__ d_query) {
+  const int img = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool is_proto = img < E * P;
+  const int e = is_proto ? img / P : (img - E * P) / Q;
+  const int self = is_proto ? img - e * P : (img - E * P) - e * Q;            // p or q
+  const int n_part = is_proto ? Q : P;
+  float* out = is_proto ? d_shot + (size_t)img * N * C : d_query + (size_t)(img - E * P) * N * C;
+  const float* xh = xhat + (size_t)img * N * C;
+  for (int n = wave; n < N; n += 4) {
+    float dot = 0.f;
+    for (int k = lane * 4; k < C; k += 256) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < n_part; ++j) {
+        const int q = is_proto ? j : self, p = is_proto ? self : j;
+        const size_t pair = ((size_t)e * Q + q) * P + p;
+        const float g = dlogits[pair] * scale;
+        const float* fp = flow + pair * N * N;
+        const float* oh = xhat + (is_proto ? (size_t)E * P + (size_t)e * Q + q : (size_t)e * P + p) * N * C;
+        for (int m = 0; m < N; ++m) {
+          const float f = is_proto ? fp[m * N + n] : fp[n * N + m];          // F[query node][proto node]
+          if (f != 0.f) acc += (g * f) * *reinterpret_cast<const f32x4*>(oh + (size_t)m * C + k);
+        }
+      }
+      const f32x4 x = *reinterpret_cast<const f32x4*>(xh + (size_t)n * C + k);
+      dot += acc[0] * x[0] + acc[1] * x[1] + acc[2] * x[2] + acc[3] * x[3];
+      *reinterpret_cast<f32x4*>(out + (size_t)n * C + k) = acc;
+    }
+    dot = wave_sum(dot);
+    const float inv = rn[(size_t)img * N + n];
+    float msum = 0.f;
+    for (int k = lane * 4; k < C; k += 256) {                   // each lane re-reads only what it wrote itself
+      const f32x4 x = *reinterpret_cast<const f32x4*>(xh + (size_t)n * C + k);
+      f32x4 v = *reinterpret_cast<f32x4*>(out + (size_t)n * C + k);
+      v = (v - x * dot) * inv;
+      msum += v[0] + v[1] + v[2] + v[3];
+      *reinterpret_cast<f32x4*>(out + (size_t)n * C + k) = v;
+    }
+    const float mean = wave_sum(msum) / (float)C;
+    for (int k = lane * 4; k < C; k += 256) {
+      f32x4 v = *reinterpret_cast<f32x4*>(out + (size_t)n * C + k);
+      *reinterpret_cast<f32x4*>(out + (size_t)n * C + k) = v - mean;
+    }
+  }
+}
+
+size_t emd_head_workspace_bytes(int E, int P, int Q, int N, int C) {
+  const size_t n_img = (size_t)E * ((size_t)P + (size_t)Q);
+  return n_img * ((size_t)N * C + (size_t)C + (size_t)N) * sizeof(float);
+}
+
+static void emd_workspace_split(void* ws, int E, int P, int Q, int N, int C, float*& xhat, float*& pooled, float*& rn) {
+  const size_t n_img = (size_t)E * ((size_t)P + (size_t)Q);
+  xhat = reinterpret_cast<float*>(ws);
+  pooled = xhat + n_img * N * C;
+  rn = pooled + n_img * C;
+}
+
+int launch_emd_solve(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* naug, hipStream_t s) {
+  if (B <= 0) return 0;
+  return launch(emd_solve_kernel, dim3((B + EMD_WAVES - 1) / EMD_WAVES), dim3(64 * EMD_WAVES), 0, s, cost, w1, w2, B, N, flow, status, naug);
+}
+
+int launch_emd_head_forward(const float* shot_tok, const float* query_tok, int E, int P, int Q, int N, int C, float temperature, float* logits, float* flow,
+                            int* status, void* ws, hipStream_t s) {
+  if (E <= 0 || P <= 0 || Q <= 0) return 0;
+  float *xhat, *pooled, *rn;
+  emd_workspace_split(ws, E, P, Q, N, C, xhat, pooled, rn);
+  int rc = launch(emd_prep_kernel, dim3(E * (P + Q)), dim3(256), 0, s, shot_tok, query_tok, E * P, N, C, xhat, pooled, rn);
+  if (rc) return rc;
+  const long long probs = (long long)E * Q * P;
+  return launch(emd_pair_kernel, dim3((unsigned)((probs + EMD_WAVES - 1) / EMD_WAVES)), dim3(64 * EMD_WAVES), 0, s, shot_tok, query_tok, xhat, pooled, E, P, Q, N,
+                C, temperature / (float)N, logits, flow, status);
+}
+
+int launch_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N, int C,
+                             float temperature, float* d_shot, float* d_query, void* ws, hipStream_t s) {
+  if (E <= 0 || P <= 0 || Q <= 0) return 0;
+  float *xhat, *pooled, *rn;
+  emd_workspace_split(ws, E, P, Q, N, C, xhat, pooled, rn);
+  int rc = launch(emd_prep_kernel, dim3(E * (P + Q)), dim3(256), 0, s, shot_tok, query_tok, E * P, N, C, xhat, pooled, rn);
+  if (rc) return rc;
+  return launch(emd_bwd_kernel, dim3(E * (P + Q)), dim3(256), 0, s, xhat, rn, dlogits, flow, E, P, Q, N, C, temperature / (float)N, d_shot, d_query);
+}
+
+}  // namespace fsvit
+
+int fsvit_set_error(int code, const char* fmt, ...);      // engine.hip (library-internal, C++ linkage)
+
+#define EMD_FAIL(...) return fsvit_set_error(FSVIT_ERR_ARG, __VA_ARGS__)
+
+static const char* emd_shape_bad(int E, int P, int Q, int N, int C) {
+  if (E < 0 || P < 0 || Q < 0) return "negative E / P / Q";
+  if (N < 1 || N > 32) return "N must be 1 .. 32 (one lane per node)";
+  if (C < 64 || C % 64) return "C must be a positive multiple of 64";
+  if ((long long)E * ((long long)P + Q) > (1ll << 24) || (long long)E * P * Q > (1ll << 28)) return "too many images / problems for one launch";
+  return nullptr;
+}
+
+extern "C" size_t fsvit_emd_head_workspace_bytes(int E, int P, int Q, int N, int C) {
+  if (emd_shape_bad(E, P, Q, N, C)) return 0;
+  return fsvit::emd_head_workspace_bytes(E, P, Q, N, C);
+}
+
+extern "C" int fsvit_emd_head_forward(const float* shot_tok, const float* query_tok, int E, int P, int Q, int N, int C, float temperature, float* logits,
+                                      float* flow_or_null, int* status, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!shot_tok || !query_tok || !logits || !status || !workspace) EMD_FAIL("fsvit_emd_head_forward: null argument");
+  if (const char* why = emd_shape_bad(E, P, Q, N, C)) EMD_FAIL("fsvit_emd_head_forward: E = %d, P = %d, Q = %d, N = %d, C = %d: %s", E, P, Q, N, C, why);
+  if (!(temperature - temperature == 0.0f)) EMD_FAIL("fsvit_emd_head_forward: temperature is not finite");
+  if (workspace_bytes < fsvit::emd_head_workspace_bytes(E, P, Q, N, C))
+    return fsvit_set_error(FSVIT_ERR_WORKSPACE, "fsvit_emd_head_forward: workspace of %zu bytes, %zu needed", workspace_bytes,
+                           fsvit::emd_head_workspace_bytes(E, P, Q, N, C));
+  int rc = fsvit::launch_emd_head_forward(shot_tok, query_tok, E, P, Q, N, C, temperature, logits, flow_or_null, status, workspace, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_head_forward: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int fsvit_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N,
+                                       int C, float temperature, float* d_shot_tok, float* d_query_tok, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  if (!shot_tok || !query_tok || !dlogits || !flow || !d_shot_tok || !d_query_tok || !workspace) EMD_FAIL("fsvit_emd_head_backward: null argument");
+  if (const char* why = emd_shape_bad(E, P, Q, N, C)) EMD_FAIL("fsvit_emd_head_backward: E = %d, P = %d, Q = %d, N = %d, C = %d: %s", E, P, Q, N, C, why);
+  if (!(temperature - temperature == 0.0f)) EMD_FAIL("fsvit_emd_head_backward: temperature is not finite");
+  if (workspace_bytes < fsvit::emd_head_workspace_bytes(E, P, Q, N, C))
+    return fsvit_set_error(FSVIT_ERR_WORKSPACE, "fsvit_emd_head_backward: workspace of %zu bytes, %zu needed", workspace_bytes,
+                           fsvit::emd_head_workspace_bytes(E, P, Q, N, C));
+  int rc = fsvit::launch_emd_head_backward(shot_tok, query_tok, dlogits, flow, E, P, Q, N, C, temperature, d_shot_tok, d_query_tok, workspace,
+                                           (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_head_backward: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static int emd_solve_entry(const char* fn, const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* naug, void* stream) {
+  if (!cost || !w1 || !w2 || !flow || !status) EMD_FAIL("%s: null argument", fn);
+  if (B < 0 || B > (1 << 28)) EMD_FAIL("%s: B = %d", fn, B);
+  if (N < 1 || N > 32) EMD_FAIL("%s: N = %d: N must be 1 .. 32 (one lane per node)", fn, N);
+  int rc = fsvit::launch_emd_solve(cost, w1, w2, B, N, flow, status, naug, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "%s: %s", fn, hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int fsvit_op_emd_solve(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, void* stream) {
+  return emd_solve_entry("fsvit_op_emd_solve", cost, w1, w2, B, N, flow, status, nullptr, stream);
+}
+
+extern "C" int fsvit_op_emd_solve_counts(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* n_augment,
+                                         void* stream) {
+  if (!n_augment) EMD_FAIL("fsvit_op_emd_solve_counts: null argument");
+  return emd_solve_entry("fsvit_op_emd_solve_counts", cost, w1, w2, B, N, flow, status, n_augment, stream);
+}

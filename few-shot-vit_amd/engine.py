@@ -1419,3 +1419,69 @@ class ops:
         ops._op(dz3, 'stage1_block_dgrad', _ptr(dz3), _ptr(dxn), _ptr(w3t), _ptr(w2t), w2t.shape[-1], _ptr(w1t), _ptr(g2), _ptr(g1), _ptr(dz2), _ptr(dz1),
                 B, H, W, ops._dt(dz3))
         return dxn, dz2, dz1
+
+    # ---- DeepEMD head (emd_head.hip): fp32 in every numerics mode
+    _emd_ws = {}
+
+    @staticmethod
+    def _emd_workspace(E, P, Q, N, Cc, dev):
+        need = _lib.load().fsvit_emd_head_workspace_bytes(E, P, Q, N, Cc)
+        ws = ops._emd_ws.get(dev)
+        if ws is None or ws.numel() < max(need, 16):
+            ws = ops._emd_ws[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        return ws
+
+    @staticmethod
+    def emd_head_forward(shot_tok, query_tok, temperature, want_flow=True):
+        """shot_tok [E,P,N,C] (the class prototypes' token maps), query_tok [E,Q,N,C] -> (logits [E,Q,P], flow [E,Q,P,N,N] or None, status [E,Q,P] int32)."""
+        _require_cuda(shot_tok, query_tok)
+        if shot_tok.dim() != 4 or query_tok.dim() != 4 or shot_tok.shape[0] != query_tok.shape[0] or shot_tok.shape[2:] != query_tok.shape[2:]:
+            raise ValueError('expected shot_tok [E,P,N,C] and query_tok [E,Q,N,C]')
+        s, q = shot_tok.detach().contiguous().float(), query_tok.detach().contiguous().float()
+        E, P, N, Cc = s.shape
+        Q = q.shape[1]
+        dev = s.device
+        logits = torch.empty(E, Q, P, dtype=torch.float32, device=dev)
+        flow = torch.empty(E, Q, P, N, N, dtype=torch.float32, device=dev) if want_flow else None
+        status = torch.empty(E, Q, P, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ws = ops._emd_workspace(E, P, Q, N, Cc, dev)
+            _lib.check(_lib.load().fsvit_emd_head_forward(_ptr(s), _ptr(q), E, P, Q, N, Cc, float(temperature), _ptr(logits), _ptr(flow), _ptr(status),
+                                                          _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        return logits, flow, status
+
+    @staticmethod
+    def emd_head_backward(shot_tok, query_tok, dlogits, flow, temperature):
+        """-> (d_shot_tok [E,P,N,C], d_query_tok [E,Q,N,C]); the flows are constants."""
+        _require_cuda(shot_tok, query_tok, dlogits, flow)
+        s, q = shot_tok.detach().contiguous().float(), query_tok.detach().contiguous().float()
+        E, P, N, Cc = s.shape
+        Q = q.shape[1]
+        dev = s.device
+        dl, fl = dlogits.contiguous().float(), flow.contiguous().float()
+        if dl.shape != (E, Q, P) or fl.shape != (E, Q, P, N, N):
+            raise ValueError('expected dlogits [E,Q,P] and flow [E,Q,P,N,N]')
+        ds, dq = torch.empty_like(s), torch.empty_like(q)
+        with torch.cuda.device(dev):
+            ws = ops._emd_workspace(E, P, Q, N, Cc, dev)
+            _lib.check(_lib.load().fsvit_emd_head_backward(_ptr(s), _ptr(q), _ptr(dl), _ptr(fl), E, P, Q, N, Cc, float(temperature), _ptr(ds), _ptr(dq),
+                                                           _ptr(ws), ws.numel(), _stream_ptr(dev)))
+        return ds, dq
+
+    @staticmethod
+    def emd_solve(cost, w1, w2, counts=False):
+        """The transport solver alone: cost [B,N,N], w1 / w2 [B,N] with equal sums -> (flow [B,N,N], status [B] int32[, augmentations [B] int32])."""
+        _require_cuda(cost, w1, w2)
+        c, a, b = cost.contiguous().float(), w1.contiguous().float(), w2.contiguous().float()
+        if c.dim() != 3 or c.shape[1] != c.shape[2] or a.shape != c.shape[:2] or b.shape != c.shape[:2]:
+            raise ValueError('expected cost [B,N,N] and w1, w2 [B,N]')
+        B, N = a.shape
+        flow = torch.empty_like(c)
+        status = torch.empty(B, dtype=torch.int32, device=c.device)
+        with torch.cuda.device(c.device):
+            if counts:
+                n_aug = torch.empty(B, dtype=torch.int32, device=c.device)
+                _lib.check(_lib.load().fsvit_op_emd_solve_counts(_ptr(c), _ptr(a), _ptr(b), B, N, _ptr(flow), _ptr(status), _ptr(n_aug), _stream_ptr(c.device)))
+                return flow, status, n_aug
+            _lib.check(_lib.load().fsvit_op_emd_solve(_ptr(c), _ptr(a), _ptr(b), B, N, _ptr(flow), _ptr(status), _stream_ptr(c.device)))
+        return flow, status

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""SUN-D evaluation driver: the reference's meta_tuning_sun_d/eval.py on the HIP DeepEMD head (models/deepemd.py, csrc/emd_head.hip).
+
+  python -m fewshot_vit_amd.eval_deepemd -way 5 -shot 1 -query 15 -test_episode 5000 -model_dir max_acc.pth
+  python -m fewshot_vit_amd.eval_deepemd -shot 5 -test_episode 600 -sfc_lr 100 -sfc_update_step 100 -sfc_bs 4
+
+Flags are the reference's (eval.py:18-50).  Differences: datasets come through this package's `datasets.make` (`-dataset`, default the synthetic
+stand-in; `-dataset_args` a YAML dict), episodes are drawn by this package's CategoriesSampler (class-major batches; SUN-D's own `randperm` sampler
+stream is not reproduced), `-episodes_per_launch` episodes go through the encoder and the head per launch - one episode's 375
+transportation problems are fewer than the GPU's SIMDs -, and the solver's status is checked once per evaluation.  Without `-model_dir` the encoder
+carries the procedural stand-in weights.  Reports the mean accuracy and its 95 % interval over episodes (eval.py:100-104)."""
+import argparse
+
+import numpy as np
+import torch
+import yaml
+
+from . import datasets, models, utils
+from .datasets.samplers import CategoriesSampler
+from .utils import few_shot as fs
+
+
+def load_params(model, path):
+    """load_model (Models/utils.py): the checkpoint's `params` with the DataParallel prefix removed, encoder keys only."""
+    sd = torch.load(path, map_location='cpu')
+    sd = sd.get('params', sd)
+    sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
+    sd = {k: v for k, v in sd.items() if k.startswith('encoder.')}
+    model.load_state_dict(sd, strict=True)
+    return model
+
+
+def build_model(args):
+    model = models.make('deepemd', encoder=args.encoder, encoder_args={'numerics': args.numerics} if args.numerics else {},
+                        temperature=args.temperature, metric=args.metric, norm=args.norm, deepemd=args.deepemd, feature_pyramid=args.feature_pyramid,
+                        solver=args.solver, sfc_lr=args.sfc_lr, sfc_update_step=int(args.sfc_update_step), sfc_bs=args.sfc_bs)
+    if args.model_dir:
+        return load_params(model, args.model_dir)
+    from . import synthetic
+    model.load_state_dict(synthetic.synthetic_checkpoint_sd({k: tuple(v.shape) for k, v in model.state_dict().items()}, calib=args.encoder))
+    return model
+
+
+def evaluate(args, log=print):
+    if args.deepemd != 'fcn':
+        raise NotImplementedError("fsvit: the patch-cropping data loaders of -deepemd grid / sampling are not built (DESIGN.md 7); the model takes patch batches")
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    device = torch.device('cuda', torch.cuda.current_device())
+    gen = torch.Generator().manual_seed(args.seed)            # the SFC permutations (torch.randperm per step and episode)
+    dataset = datasets.make(args.dataset, **args.dataset_args)
+    model = build_model(args).to(device).eval()
+    model.sfc_generator = gen
+    sampler = CategoriesSampler(dataset.label, args.test_episode, args.way, args.shot + args.query)
+    label = fs.make_nk_label(args.way, args.query).to(device)
+    accs, pending = [], []
+
+    def flush():
+        if not pending:
+            return
+        G = len(pending)
+        idx = torch.stack(list(pending)).view(-1)
+        if hasattr(dataset, 'gather'):
+            data = dataset.gather(idx)
+        else:
+            data = torch.stack([dataset[int(i)][0] for i in idx]).to(device)
+        x_shot, x_query = fs.split_shot_query(data, args.way, args.shot, args.query, ep_per_batch=G)
+        with torch.no_grad():
+            logits = model(x_shot, x_query)
+        accs.append((logits.argmax(dim=-1) == label).float().mean(dim=1))
+        pending.clear()
+
+    for idx in sampler:
+        pending.append(idx)
+        if len(pending) == args.episodes_per_launch:
+            flush()
+    flush()
+    model.check_status()                                     # the one synchronisation: raises if any transportation problem hit a loop bound
+    acc = torch.cat(accs).double().cpu().numpy() * 100.0
+    mean = float(acc.mean())
+    ci = float(utils.mean_confidence_interval(acc)) if len(acc) > 1 else float('nan')
+    log('test Acc {:.4f}'.format(mean))
+    log('Test Acc {:.4f} + {:.4f}'.format(mean, ci))
+    return dict(acc=mean, ci=ci, n=len(acc))
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument('-encoder', '--backbone', dest='encoder', default='visformer_micro_80')
+    p.add_argument('-way', type=int, default=5)
+    p.add_argument('-shot', type=int, default=1)
+    p.add_argument('-query', type=int, default=15)
+    p.add_argument('-dataset', default='synthetic-episodes')
+    p.add_argument('-dataset_args', type=yaml.safe_load, default={'split': 'test', 'noise': 1.0, 'seed': 0})
+    p.add_argument('-temperature', type=float, default=12.5)
+    p.add_argument('-metric', default='cosine')
+    p.add_argument('-norm', default='center')
+    p.add_argument('-deepemd', default='fcn', choices=['fcn', 'grid', 'sampling'])
+    p.add_argument('-feature_pyramid', default=None)
+    p.add_argument('-solver', default='opencv')
+    p.add_argument('-sfc_lr', type=float, default=100)
+    p.add_argument('-sfc_update_step', type=float, default=100)
+    p.add_argument('-sfc_bs', type=int, default=4)
+    p.add_argument('-test_episode', type=int, default=5000)
+    p.add_argument('-model_dir', default=None)
+    p.add_argument('-seed', type=int, default=1)
+    p.add_argument('-numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'])
+    p.add_argument('-episodes_per_launch', type=int, default=16)
+    args = p.parse_args(argv)
+    return evaluate(args, log=utils.log if hasattr(utils, 'log') else print)
+
+
+if __name__ == '__main__':
+    main()

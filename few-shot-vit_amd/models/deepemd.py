@@ -1,0 +1,132 @@
+"""'deepemd': the SUN-D few-shot head - a query is scored against a class by the earth mover's distance between the token maps of the
+two images (surface of meta_tuning_sun_d/Models/models/Network.py:9-204 with `solver: opencv`).
+
+The encoder is one of this package's encoders built with return_map=True; the head runs on the HIP kernels of csrc/emd_head.hip (node
+preparation, cost / weights / exact transport solver per (query, proto) pair, and the backward with the flows as constants).  State-dict keys
+are the reference's (`encoder.*`), so the `params` of a SUN-D checkpoint load.
+"""
+import torch
+import torch.nn as nn
+
+from .models import make as _make
+from .models import register
+
+MAX_NODES = 32          # one lane per node on either side of the transportation problem
+
+
+def check_status_count(count) -> None:
+    """Raise when any transportation problem reached one of the solver's loop bounds (its logit is then not an optimum).  `count` is the
+    accumulated status sum: a Python int or a tensor (reading a device tensor is the one synchronisation of an evaluation)."""
+    n = int(count.sum().item()) if isinstance(count, torch.Tensor) else int(count)
+    if n != 0:
+        raise RuntimeError(f'fsvit: {n} DeepEMD transportation problem(s) stopped at a loop bound of the solver (status 1); their logits are not optimal')
+
+
+@register('deepemd')
+class DeepEMD(nn.Module):
+
+    def __init__(self, encoder, encoder_args={}, temperature=12.5, metric='cosine', norm='center', deepemd='fcn', feature_pyramid=None,
+                 solver='opencv', form=None, sfc_lr=100., sfc_update_step=100, sfc_bs=4):
+        super().__init__()
+        if feature_pyramid is not None:
+            raise NotImplementedError('fsvit: DeepEMD feature_pyramid is not built (DESIGN.md 7)')
+        if metric != 'cosine':
+            raise NotImplementedError(f"fsvit: DeepEMD metric {metric!r}: the head is built for 'cosine'")
+        if solver != 'opencv' or form is not None:
+            raise NotImplementedError("fsvit: the DeepEMD head solves the transport LP exactly with constant flows (`solver: opencv`); qpth / form are not built")
+        if norm != 'center':
+            raise NotImplementedError(f"fsvit: DeepEMD norm {norm!r}: the node preparation kernel centres over channels ('center')")
+        if deepemd not in ('fcn', 'grid', 'sampling'):
+            raise ValueError(deepemd)
+        self.encoder = _make(encoder, **{**encoder_args, 'return_map': True})
+        self.temperature = float(temperature)
+        self.deepemd = deepemd
+        self.sfc_lr, self.sfc_update_step, self.sfc_bs = float(sfc_lr), int(sfc_update_step), int(sfc_bs)
+        self.sfc_generator = None          # torch.Generator of get_sfc's permutations inside forward (None: the global one)
+        self._status_count = None          # device int64 scalar: status sum of every head call since the last check_status()
+
+    # ---- status: accumulated on the device, read once per evaluation
+    def add_status(self, status):
+        s = status.sum(dtype=torch.int64)
+        self._status_count = s if self._status_count is None else self._status_count.to(s.device) + s
+
+    def check_status(self):
+        count, self._status_count = self._status_count, None
+        if count is not None:
+            check_status_count(count)
+
+    # ---- nodes
+    def encode(self, x, patches):
+        """[B,3,H,W] -> token map [B,N,C] (fcn); [B,n_patch,3,H,W] -> the pooled feature of every patch [B,n_patch,C] (grid / sampling, :179-187)."""
+        if patches:
+            B, n_patch = x.shape[:2]
+            _, feat = self.encoder(x.reshape(-1, *x.shape[2:]))
+            return feat.reshape(B, n_patch, -1)
+        fmap, _ = self.encoder(x)
+        return fmap.flatten(2).transpose(1, 2).contiguous()
+
+    def forward(self, x_shot, x_query):
+        """x_shot [E,way,shot,3,H,W], x_query [E,Q,3,H,W] -> logits [E,Q,way]; 'grid' / 'sampling' take one more patch axis before the image axes."""
+        patches = self.deepemd != 'fcn'
+        nd = 1 if patches else 0
+        if x_shot.dim() != 6 + nd or x_query.dim() != 5 + nd:
+            raise ValueError('expected x_shot [E,way,shot,(n_patch,)3,H,W] and x_query [E,Q,(n_patch,)3,H,W]')
+        E, way, shot = x_shot.shape[:3]
+        Q = x_query.shape[1]
+        img = x_shot.shape[3:]
+        if patches and img[0] > MAX_NODES:
+            raise NotImplementedError(f'fsvit: {img[0]} patches per image; the DeepEMD head holds at most {MAX_NODES} nodes')
+        # one encoder pass over shot + query images of all episodes (train mode: BatchNorm sees the whole batch, one forward per backward)
+        tok = self.encode(torch.cat([x_shot.reshape(-1, *img), x_query.reshape(-1, *img)], dim=0), patches)
+        if tok.shape[1] > MAX_NODES:
+            raise NotImplementedError(f'fsvit: a {tok.shape[1]}-token map; the DeepEMD head holds at most {MAX_NODES} nodes')
+        n_shot = E * way * shot
+        shot_tok = tok[:n_shot].reshape(E, way, shot, *tok.shape[1:])
+        query_tok = tok[n_shot:].reshape(E, Q, *tok.shape[1:])
+        proto = shot_tok[:, :, 0] if shot == 1 else self.get_sfc(shot_tok, generator=self.sfc_generator)
+        return self.emd_forward(proto, query_tok)
+
+    def emd_forward(self, proto, query_tok):
+        """emd_forward_1shot (:67-81): proto [E,P,N,C], query_tok [E,Q,N,C] -> logits [E,Q,P]."""
+        from ..engine import ops
+        if torch.is_grad_enabled() and (proto.requires_grad or query_tok.requires_grad):
+            from ..autograd import EmdHeadFn
+            logits, status = EmdHeadFn.apply(proto, query_tok, self.temperature)
+        else:
+            logits, _, status = ops.emd_head_forward(proto, query_tok, self.temperature, want_flow=False)
+        self.add_status(status)
+        return logits
+
+    def get_sfc(self, shot_maps, perms=None, generator=None):
+        """Structured fully connected layer (:83-107), batched over episodes: shot_maps [E,way,shot,N,C] -> SFC [E,way,N,C].  Initialised with the
+        mean over shots, then sfc_update_step epochs of SGD(lr=sfc_lr, momentum=0.9, dampening=0.9) over mini-batches of sfc_bs support images
+        (labels arange(way).repeat(shot): the support set in shot-major order), cross entropy of the EMD logits per episode.  `perms`
+        [steps, way*shot] or [steps, E, way*shot] fixes the permutation of every step (tests); otherwise a fresh torch.randperm per step and episode
+        from `generator`.  Head forward / backward are the HIP kernels; the update of the one small tensor is torch arithmetic."""
+        from ..engine import ops
+        maps = shot_maps.detach().float()
+        E, way, shot, N, Cc = maps.shape
+        dev = maps.device
+        n = way * shot
+        support = maps.permute(0, 2, 1, 3, 4).reshape(E, n, N, Cc)             # index s * way + c
+        label = torch.arange(way, device=dev).repeat(shot)
+        sfc = maps.mean(dim=2).contiguous()
+        buf = None
+        rows = torch.arange(E, device=dev)[:, None]
+        eye = torch.eye(way, device=dev)
+        for k in range(self.sfc_update_step):
+            if perms is not None:
+                perm = torch.as_tensor(perms[k]).to(dev).long()
+                perm = perm.expand(E, n) if perm.dim() == 1 else perm
+            else:
+                perm = torch.stack([torch.randperm(n, generator=generator) for _ in range(E)]).to(dev)
+            for j in range(0, n, self.sfc_bs):
+                ids = perm[:, j:j + self.sfc_bs]                               # [E, b]
+                batch = support[rows, ids].contiguous()                         # [E, b, N, C]
+                logits, flow, status = ops.emd_head_forward(sfc, batch, self.temperature)
+                self.add_status(status)
+                dlogits = (torch.softmax(logits, dim=-1) - eye[label[ids]]) / ids.shape[1]      # mean cross entropy per episode
+                grad, _ = ops.emd_head_backward(sfc, batch, dlogits, flow, self.temperature)
+                buf = grad.clone() if buf is None else buf.mul_(0.9).add_(grad, alpha=1.0 - 0.9)   # torch.optim.SGD: no dampening on the first step
+                sfc = sfc - self.sfc_lr * buf
+        return sfc

@@ -641,6 +641,28 @@ int fsvit_op_stage1_block_train(const void* x, void* out, const void* w1f, const
 int fsvit_op_stage1_block_dgrad(const void* dz3, void* dxn, const void* w3t, const void* w2t, int w2_ld, const void* w1t, const void* g2, const void* g1,
                                 void* dz2, void* dz1, int B, int H, int W, int dtype, void* stream);
 
+/* ---------------------------------------------------------------- DeepEMD head (SUN-D: meta_tuning_sun_d/Models/models/Network.py:48-175, emd_utils.py:65-76)
+ * fp32 in every numerics mode.  shot_tok [E][P][N][C] are the class prototypes' token maps (token-major), query_tok [E][Q][N][C] the queries'; N <= 32
+ * nodes, C a multiple of 64.  Per (query, proto) pair the transportation problem  min sum c F,  c = 1 - cosine similarity of the channel-centred tokens,
+ * F >= 0, row sums w1, column sums w2 (the reference's weights, both scaled to sum N)  is solved exactly (successive shortest paths, every loop bounded):
+ * logits [E][Q][P] = temperature / N * sum (1 - c) F; flow_or_null [E][Q][P][N][N] (first index the query node) is what the backward needs;
+ * status [E][Q][P] is 0, or 1 where a problem reached a loop bound (its logit is then not the optimum).  workspace: fsvit_emd_head_workspace_bytes
+ * (0 for a refused shape).  Refused with FSVIT_ERR_ARG and a message, nothing launched: a null pointer, N < 1 or N > 32, C not a multiple of 64, negative
+ * E / P / Q, a temperature that is not finite; FSVIT_ERR_WORKSPACE for a workspace that is too small.
+ * Backward: the flows are constants (the reference's `solver: opencv`), dS = dlogit * temperature / N * F, the weights carry no gradient; d_shot_tok /
+ * d_query_tok have the shapes of the token maps.  Deterministic (no atomics). */
+size_t fsvit_emd_head_workspace_bytes(int E, int P, int Q, int N, int C);
+int fsvit_emd_head_forward(const float* shot_tok_dev, const float* query_tok_dev, int E, int P, int Q, int N, int C, float temperature, float* logits_dev,
+                           float* flow_or_null_dev, int* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int fsvit_emd_head_backward(const float* shot_tok_dev, const float* query_tok_dev, const float* dlogits_dev, const float* flow_dev, int E, int P, int Q,
+                            int N, int C, float temperature, float* d_shot_tok_dev, float* d_query_tok_dev, void* workspace_dev, size_t workspace_bytes,
+                            void* stream);
+/* The solver alone, for operator tests: cost [B][N][N], w1 / w2 [B][N] already normalised (equal sums) -> flow [B][N][N], status [B]; _counts also
+ * writes the number of augmenting paths of every problem (n_augment [B]). */
+int fsvit_op_emd_solve(const float* cost_dev, const float* w1_dev, const float* w2_dev, int B, int N, float* flow_dev, int* status_dev, void* stream);
+int fsvit_op_emd_solve_counts(const float* cost_dev, const float* w1_dev, const float* w2_dev, int B, int N, float* flow_dev, int* status_dev,
+                              int* n_augment_dev, void* stream);
+
 /* ---------------------------------------------------------------- episode sampler (host only, no GPU)
  * The draws of `CategoriesSampler.__iter__` (test_phase/datasets/samplers.py:19-35) replayed natively on the legacy numpy generator state: per episode
  * `np.random.choice(n_cat, n_cls, replace=False)`, then per chosen class `np.random.choice(catlocs[c], n_per, replace=False)`.  mt_key [624] / mt_pos =
