@@ -1418,7 +1418,8 @@ extern "C" int fsvit_pool_affine(const void* x, const float* scale, const float*
                                  int dtype, void* stream) {
   const int kdt = dtype;
   if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "unknown dtype %d", dtype);
-  if (!x || !scale || !shift || !feat || C % 4) return fail(FSVIT_ERR_ARG, "bad argument");
+  if (!x || !scale || !shift || !feat || C % 4 || C < 4 || HW < 1)
+    return fail(FSVIT_ERR_ARG, "fsvit_pool_affine: null argument, C %% 4 != 0 or HW < 1 (the mean over no positions divides by zero)");
   RC_TRY(K(launch_pool_affine)(x, scale, shift, feat, B, HW, C, kd(dtype), (hipStream_t)stream));
   return 0;
 }

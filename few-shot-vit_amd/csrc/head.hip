@@ -142,7 +142,7 @@ int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const 
                          float* logits, float* acc, float* loss, float* dlogits, float* mean_out, unsigned* ticket, hipStream_t s, const float* temp_dev) {
   if (E <= 0) return 0;
   const size_t lds = ((size_t)way * D + (size_t)Q * 2) * sizeof(float);
-  if (lds > 160 * 1024 || way < 1 || shot < 1 || Q < 1) return (int)hipErrorInvalidValue;
+  if (lds > 160 * 1024 || way < 1 || shot < 1 || Q < 1 || D < 1) return (int)hipErrorInvalidValue;
   // few episodes per launch -> latency bound: 16 waves per episode (one wave per query at a time)
   hipError_t e = hipFuncSetAttribute((const void*)proto_head_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
@@ -305,6 +305,7 @@ __global__ __launch_bounds__(256) void proto_head_sqr_bwd_kernel(const float* __
 int launch_proto_head_sqr_bwd(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D, float temp,
                               float* dfeat_shot, float* dfeat_query, float* dtemp, hipStream_t s, const float* temp_dev, const float* up, unsigned* ticket) {
   if (E <= 0) return 0;
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return (int)hipErrorInvalidValue;      // (shot = 0 divides by it; way = 0 / Q = 0 leave the outputs unwritten)
   const size_t lds = ((size_t)way * D + 4) * sizeof(float);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void*)proto_head_sqr_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -316,6 +317,7 @@ int launch_proto_head_sqr_bwd(const float* feat_shot, const float* feat_query, c
 int launch_proto_head_bwd(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D, float temp,
                           float* dfeat_shot, float* dfeat_query, float* dtemp, hipStream_t s, const float* temp_dev, const float* up, unsigned* ticket) {
   if (E <= 0) return 0;
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return (int)hipErrorInvalidValue;
   const size_t lds = ((size_t)2 * way * D + way + Q + HB_NT / 64) * sizeof(float);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
   hipError_t e = hipFuncSetAttribute((const void*)proto_head_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -1541,6 +1541,7 @@ extern "C" int fsvit_lvvit_train_set_token_grad(fsvit_lvvit_trainer* t, const fl
 extern "C" int fsvit_proto_head_backward(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D,
                                          float temp, float* dfeat_shot, float* dfeat_query, float* dtemp_per_episode, void* stream) {
   if (!feat_shot || !feat_query || !dlogits || !dfeat_shot || !dfeat_query) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: way = %d, shot = %d, Q = %d, D = %d (all >= 1)", way, shot, Q, D);
   int rc = launch_proto_head_bwd(feat_shot, feat_query, dlogits, E, way, shot, Q, D, temp, dfeat_shot, dfeat_query, dtemp_per_episode, (hipStream_t)stream);
   return rc ? fsvit_set_error(rc, "proto_head_bwd") : 0;
 }
@@ -1548,6 +1549,7 @@ extern "C" int fsvit_proto_head_backward(const float* feat_shot, const float* fe
 extern "C" int fsvit_proto_head_backward_sqr(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D,
                                              float temp, float* dfeat_shot, float* dfeat_query, float* dtemp_per_episode, void* stream) {
   if (!feat_shot || !feat_query || !dlogits || !dfeat_shot || !dfeat_query) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: way = %d, shot = %d, Q = %d, D = %d (all >= 1)", way, shot, Q, D);
   int rc = launch_proto_head_sqr_bwd(feat_shot, feat_query, dlogits, E, way, shot, Q, D, temp, dfeat_shot, dfeat_query, dtemp_per_episode, (hipStream_t)stream);
   return rc ? fsvit_set_error(rc, "proto_head_sqr_bwd") : 0;
 }
@@ -1555,6 +1557,7 @@ extern "C" int fsvit_proto_head_backward_sqr(const float* feat_shot, const float
 extern "C" int fsvit_proto_head_backward_devtemp(const float* feat_shot, const float* feat_query, const float* dlogits, int E, int way, int shot, int Q, int D,
                                                  const float* temp_dev, int method, float* dfeat_shot, float* dfeat_query, float* dtemp_per_episode, void* stream) {
   if (!feat_shot || !feat_query || !dlogits || !dfeat_shot || !dfeat_query || !temp_dev) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: way = %d, shot = %d, Q = %d, D = %d (all >= 1)", way, shot, Q, D);
   if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: method 'cos' or 'sqr'");
   int rc = method == FSVIT_HEAD_COS
                ? launch_proto_head_bwd(feat_shot, feat_query, dlogits, E, way, shot, Q, D, 0.f, dfeat_shot, dfeat_query, dtemp_per_episode, (hipStream_t)stream, temp_dev)
@@ -1577,6 +1580,7 @@ extern "C" int fsvit_proto_head_ce_backward(const float* feat_shot, const float*
                                             int Q, int D, float temp, const float* temp_dev, int method, float* dfeat_shot, float* dfeat_query, float* dtemp,
                                             unsigned* ticket, void* stream) {
   if (!feat_shot || !feat_query || !dlogits || !dfeat_shot || !dfeat_query) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  if (way < 1 || shot < 1 || Q < 1 || D < 1) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: way = %d, shot = %d, Q = %d, D = %d (all >= 1)", way, shot, Q, D);
   if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR) return fsvit_set_error(FSVIT_ERR_ARG, "head backward: method 'cos' or 'sqr'");
   if (ticket && !dtemp) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_proto_head_ce_backward: the ticket sums dtemp[0 .. E) into dtemp[E]");
   int rc = method == FSVIT_HEAD_COS ? launch_proto_head_bwd(feat_shot, feat_query, dlogits, E, way, shot, Q, D, temp_dev ? 0.f : temp, dfeat_shot, dfeat_query, dtemp,

@@ -872,12 +872,19 @@ class ops:
         return dqkv
 
     @staticmethod
+    def _head_in(*ts):
+        """The head kernels read dense fp32 rows: every wrapper of the head takes any layout / floating type and hands over a contiguous fp32 copy (no copy
+        when the tensor already is one), so a permuted view, a strided slice or a float64 temperature gives the bits of its contiguous fp32 copy."""
+        return tuple(t.detach().contiguous().float() for t in ts)
+
+    @staticmethod
     def proto_head_backward(feat_shot, feat_query, dlogits, temp, method='cos'):
         """-> dfeat_shot [E,way,shot,D], dfeat_query [E,Q,D], dtemp (scalar tensor); method 'cos' or 'sqr'."""
         if method not in ('cos', 'sqr'):
             raise ValueError(method)
         _require_cuda(feat_shot, feat_query, dlogits)
         lib = _lib.load()
+        feat_shot, feat_query, dlogits = ops._head_in(feat_shot, feat_query, dlogits)
         E, way, shot, D = feat_shot.shape
         Q = feat_query.shape[1]
         dev = feat_shot.device
@@ -885,12 +892,12 @@ class ops:
         dt = torch.empty(E, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             if isinstance(temp, torch.Tensor) and temp.is_cuda:
-                _lib.check(lib.fsvit_proto_head_backward_devtemp(_ptr(feat_shot), _ptr(feat_query), _ptr(dlogits.contiguous().float()), E, way, shot, Q, D,
-                                                                 _ptr(temp.detach().float().contiguous()), _lib.HEAD_COS if method == 'cos' else _lib.HEAD_SQR,
+                _lib.check(lib.fsvit_proto_head_backward_devtemp(_ptr(feat_shot), _ptr(feat_query), _ptr(dlogits), E, way, shot, Q, D,
+                                                                 _ptr(ops._head_in(temp)[0]), _lib.HEAD_COS if method == 'cos' else _lib.HEAD_SQR,
                                                                  _ptr(ds), _ptr(dq), _ptr(dt), _stream_ptr(dev)))
             else:
                 fn = lib.fsvit_proto_head_backward if method == 'cos' else lib.fsvit_proto_head_backward_sqr
-                _lib.check(fn(_ptr(feat_shot), _ptr(feat_query), _ptr(dlogits.contiguous().float()), E, way, shot, Q, D, float(temp), _ptr(ds), _ptr(dq), _ptr(dt),
+                _lib.check(fn(_ptr(feat_shot), _ptr(feat_query), _ptr(dlogits), E, way, shot, Q, D, float(temp), _ptr(ds), _ptr(dq), _ptr(dt),
                               _stream_ptr(dev)))
         return ds, dq, dt.sum()
 
@@ -973,6 +980,7 @@ class ops:
         (of the mean CE), stats [2 + 2 E] = {loss, acc, acc per episode .., loss per episode ..}.  label: int64 [E*Q] on the device (None: make_nk_label)."""
         _require_cuda(feat_shot, feat_query)
         lib = _lib.load()
+        feat_shot, feat_query = ops._head_in(feat_shot, feat_query)
         E, way, shot, D = feat_shot.shape
         Q = feat_query.shape[1]
         dev = feat_shot.device
@@ -985,10 +993,11 @@ class ops:
                 raise ValueError('label: int64 [E*Q] on the device')
             label = label.contiguous()
         dev_temp = isinstance(temp, torch.Tensor) and temp.is_cuda
+        temp_d = ops._head_in(temp)[0] if dev_temp else None
         tk = ops._ticket(dev)
         with torch.cuda.device(dev):
             _lib.check(lib.fsvit_proto_head_ce(_ptr(feat_shot), _ptr(feat_query), _ptr(label) if label is not None else None, E, way, shot, Q, D,
-                                               0.0 if dev_temp else float(temp), _ptr(temp.detach()) if dev_temp else None, m, _ptr(logits), _ptr(dlogits),
+                                               0.0 if dev_temp else float(temp), _ptr(temp_d), m, _ptr(logits), _ptr(dlogits),
                                                _ptr(stats[2:2 + E]), _ptr(stats[2 + E:]), _ptr(stats), tk.data_ptr(), _stream_ptr(dev)))
         return logits, dlogits, stats
 
@@ -999,18 +1008,20 @@ class ops:
             raise ValueError(method)
         _require_cuda(feat_shot, feat_query, dlogits)
         lib = _lib.load()
+        feat_shot, feat_query, dlogits = ops._head_in(feat_shot, feat_query, dlogits)
         E, way, shot, D = feat_shot.shape
         Q = feat_query.shape[1]
         dev = feat_shot.device
         ds, dq = torch.empty_like(feat_shot), torch.empty_like(feat_query)
         dt = torch.empty(E + 1, dtype=torch.float32, device=dev)
         dev_temp = isinstance(temp, torch.Tensor) and temp.is_cuda
+        temp_d = ops._head_in(temp)[0] if dev_temp else None
         if dloss is not None and not (dloss.is_cuda and dloss.dtype == torch.float32 and dloss.numel() == 1):
             raise ValueError('dloss: one fp32 value on the device')
         tk = ops._ticket(dev)
         with torch.cuda.device(dev):
             _lib.check(lib.fsvit_proto_head_ce_backward(_ptr(feat_shot), _ptr(feat_query), _ptr(dlogits), _ptr(dloss) if dloss is not None else None, E, way,
-                                                        shot, Q, D, 0.0 if dev_temp else float(temp), _ptr(temp.detach()) if dev_temp else None,
+                                                        shot, Q, D, 0.0 if dev_temp else float(temp), _ptr(temp_d),
                                                         _lib.HEAD_COS if method == 'cos' else _lib.HEAD_SQR, _ptr(ds), _ptr(dq), _ptr(dt),
                                                         tk.data_ptr() + 4, _stream_ptr(dev)))
         return ds, dq, dt[E]
@@ -1020,6 +1031,7 @@ class ops:
         """feat_shot [E,way,shot,D], feat_query [E,Q,D] fp32 -> logits [E,Q,way], acc [E], loss [E]."""
         _require_cuda(feat_shot, feat_query)
         lib = _lib.load()
+        feat_shot, feat_query = ops._head_in(feat_shot, feat_query)
         E, way, shot, D = feat_shot.shape
         Q = feat_query.shape[1]
         dev = feat_shot.device
@@ -1029,11 +1041,11 @@ class ops:
         m = {'cos': _lib.HEAD_COS, 'sqr': _lib.HEAD_SQR, 'dot': _lib.HEAD_DOT}[method]
         with torch.cuda.device(dev):
             if isinstance(temp, torch.Tensor) and temp.is_cuda:      # the learnable temperature stays on the device: no .item() synchronisation per step
-                _lib.check(lib.fsvit_proto_head_devtemp(_ptr(feat_shot.contiguous().float()), _ptr(feat_query.contiguous().float()), E, way,
-                                                        shot, Q, D, _ptr(temp.detach().float().contiguous()), m, _ptr(logits), _ptr(acc), _ptr(loss),
+                _lib.check(lib.fsvit_proto_head_devtemp(_ptr(feat_shot), _ptr(feat_query), E, way,
+                                                        shot, Q, D, _ptr(ops._head_in(temp)[0]), m, _ptr(logits), _ptr(acc), _ptr(loss),
                                                         _stream_ptr(dev)))
             else:
-                _lib.check(lib.fsvit_proto_head(_ptr(feat_shot.contiguous().float()), _ptr(feat_query.contiguous().float()), E, way,
+                _lib.check(lib.fsvit_proto_head(_ptr(feat_shot), _ptr(feat_query), E, way,
                                                 shot, Q, D, float(temp), m, _ptr(logits), _ptr(acc), _ptr(loss), _stream_ptr(dev)))
         return logits, acc, loss
 

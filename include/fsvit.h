@@ -325,6 +325,7 @@ int fsvit_stem_conv1(const float* x_nchw_dev, const void* w_dev, int kw, const f
                      int B, int H, int W, void* stream);
 int fsvit_maxpool2_pos(const void* in_dev, const float* pos_dev, void* out_dev, int B, int OH, int OW, int C,
                        int dtype, void* stream);
+/* feat [B][C] fp32 = scale[c] * mean over HW of x [B][HW][C] + shift[c];  HW >= 1, C >= 4, C % 4 == 0 (FSVIT_ERR_ARG otherwise). */
 int fsvit_pool_affine(const void* x_dev, const float* scale_dev, const float* shift_dev, float* feat_dev,
                       int B, int HW, int C, int dtype, void* stream);
 
@@ -407,7 +408,8 @@ int fsvit_lvvit_train_tokens(fsvit_lvvit_trainer* t, float* tokens_dev, void* st
 int fsvit_lvvit_train_set_token_grad(fsvit_lvvit_trainer* t, const float* dtokens_dev);
 
 /* Backward of fsvit_proto_head, method 'cos' (meta_baseline.py:33-47): dlogits [E,Q,way] -> dfeat_shot [E,way,shot,D],
- * dfeat_query [E,Q,D], dtemp_per_episode [E] (sum it for the learnable temperature, meta_baseline.py:20-21). */
+ * dfeat_query [E,Q,D], dtemp_per_episode [E] (sum it for the learnable temperature, meta_baseline.py:20-21).  way, shot, Q, D >= 1 in every backward
+ * entry below (FSVIT_ERR_ARG otherwise, nothing written). */
 int fsvit_proto_head_backward(const float* feat_shot_dev, const float* feat_query_dev, const float* dlogits_dev, int E, int way,
                               int shot, int Q, int D, float temp, float* dfeat_shot_dev, float* dfeat_query_dev,
                               float* dtemp_per_episode_dev, void* stream);
