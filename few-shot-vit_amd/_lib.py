@@ -141,6 +141,9 @@ SIGNATURES = {
     'fsvit_visformer_trainer_set_freeze_bn': (_i, [_vp, _i]),
     'fsvit_sgd_step_multi': (_i, [_vp, _i, _sz, _f, _f, _f, _i, _vp]),
     'fsvit_sgd_step': (_i, [_fp, _fp, _fp, _sz, _f, _f, _f, _i, _vp]),
+    'fsvit_sgd_nesterov_step_multi': (_i, [_vp, _i, _sz, _f, _f, _f, _i, _vp]),
+    'fsvit_sgd_nesterov_step': (_i, [_fp, _fp, _fp, _sz, _f, _f, _f, _i, _vp]),
+    'fsvit_grad_nan_guard_multi': (_i, [_vp, _i, _sz, _vp, _vp]),
     'fsvit_conv1x1_wgrad': (_i, [_vp, _vp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_conv3x3_wgrad': (_i, [_vp, _vp, _fp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'fsvit_gconv3x3': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

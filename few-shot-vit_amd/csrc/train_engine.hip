@@ -1629,6 +1629,27 @@ extern "C" int fsvit_sgd_step(float* param, const float* grad, float* momentum_b
   return rc ? fsvit_set_error(rc, "sgd") : 0;
 }
 
+extern "C" int fsvit_sgd_nesterov_step_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float weight_decay,
+                                             int first_step, void* stream) {
+  if (!items_dev && n_items > 0) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_sgd_nesterov_step_multi: null table");
+  int rc = launch_sgd_nesterov_multi(items_dev, n_items, max_numel, lr, momentum, weight_decay, first_step, (hipStream_t)stream);
+  return rc ? fsvit_set_error(rc, "sgd_nesterov_multi") : 0;
+}
+
+extern "C" int fsvit_sgd_nesterov_step(float* param, const float* grad, float* momentum_buf, size_t n, float lr, float momentum, float weight_decay,
+                                       int first_step, void* stream) {
+  if (!param || !grad || !momentum_buf) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");
+  int rc = launch_sgd_nesterov(param, grad, momentum_buf, n, lr, momentum, weight_decay, first_step, (hipStream_t)stream);
+  return rc ? fsvit_set_error(rc, "sgd_nesterov") : 0;
+}
+
+extern "C" int fsvit_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int32_t* flags_dev, void* stream) {
+  if (n_items < 0) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_grad_nan_guard_multi: n_items = %d", n_items);
+  if (n_items > 0 && (!items_dev || !flags_dev)) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_grad_nan_guard_multi: null argument");
+  int rc = launch_grad_nan_guard_multi(items_dev, n_items, max_numel, flags_dev, (hipStream_t)stream);
+  return rc ? fsvit_set_error(rc, "grad_nan_guard_multi") : 0;
+}
+
 // ---- post-norm token map of the last train_forward (the `x` of `return x, pooled`, sun_meta_training/models/visformer.py:464) and its gradient
 extern "C" int fsvit_visformer_train_tokens(fsvit_visformer_trainer* t, float* tokens_dev, void* stream) {
   if (!t || !tokens_dev) return fsvit_set_error(FSVIT_ERR_ARG, "null argument");

@@ -77,6 +77,9 @@ int launch_scale_copy(const float* in, float* out, size_t n, float sc, hipStream
 int launch_colsum(const void* a, float* partial, float* out, int M, int C, int dtype, hipStream_t s);
 int launch_sgd_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s);
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s);
+int launch_sgd_nesterov_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s);
+int launch_sgd_nesterov(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s);
+int launch_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int* flags_dev, hipStream_t s);
 // attention backward (attention_bwd.hip): qkv [B*S][3*heads*hdp], dctx [B*S][heads*hdp] -> dqkv [B*S][3*heads*hdp]
 int launch_attention_bwd(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, int dtype, hipStream_t s);
 int attention_bwd_route(int S, int hd, int hdp, int dtype);      // the kernel launch_attention_bwd takes (attention_bwd.hip), -1 = refused; host only

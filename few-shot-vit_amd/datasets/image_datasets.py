@@ -13,7 +13,14 @@ reference's value is 0.2) is the probability of the weak view's RandomApply([Ran
 the two.  `augment='randaug'` is the reference's `cropaug` pipeline under our own name (timm's create_transform: bicubic RandomResizedCrop + flip
 -> RandAugment 'rand-m9-mstd0.5-inc1' -> Normalize -> RandomErasing(0.25, 'pixel'); transforms.DeviceRandAugCrop), with the `default_transform` of
 `'resize'`; the RandAugment draw restates timm's published algorithm and is not pinned against timm, so the name `'cropaug'` itself stays
-refused, as does `'crop'` (padded RandomCrop)."""
+refused, as does `'crop'` (padded RandomCrop).
+
+`patches='grid' | 'sampling'` (default None) are the SUN-D loaders (meta_tuning_sun_d/Models/dataloader/miniimagenet/{grid,sampling}): `gather` then
+returns [len, P, 3, 80, 80] and `__getitem__` [P, 3, 80, 80] (transforms.DevicePatchGrid with `patch_list`, `patch_ratio`, `patch_train`;
+transforms.DevicePatchSampler with `num_patch`).  `mean` / `std` override the normalisation statistics (default: ImageNet's; SUN-D's csv loaders
+use transforms.SUND_MEAN / SUND_STD) and `resize` the eval transform's Resize (SUN-D `fcn`: Resize([92, 92]) -> CenterCrop(80)).
+
+'synthetic-images' is a deterministic class-structured uint8 table behind the same class, for machines without the pickles."""
 import os
 import pickle
 
@@ -21,13 +28,25 @@ import numpy as np
 import torch
 
 from .datasets import register
-from .transforms import IMAGENET_MEAN, IMAGENET_STD, DeviceRandAugCrop, DeviceRandomResizedCrop, DeviceStrongWeakPair, DeviceTransform
+from .transforms import (IMAGENET_MEAN, IMAGENET_STD, DevicePatchGrid, DevicePatchSampler, DeviceRandAugCrop, DeviceRandomResizedCrop,
+                         DeviceStrongWeakPair, DeviceTransform)
 
 
 class _DeviceImageDataset:
     resize, crop = (88, 88), 80
 
-    def _finish(self, data: np.ndarray, label, device, augment=None, strong_prob=0.5, weak_randaug=0.0):
+    def _finish(self, data: np.ndarray, label, device, augment=None, strong_prob=0.5, weak_randaug=0.0, patches=None, patch_list=(2, 3),
+                patch_ratio=2.0, num_patch=9, patch_train=False, mean=None, std=None, resize=None):
+        if patches not in (None, 'grid', 'sampling'):
+            raise ValueError(f"patches={patches!r}: None, 'grid' or 'sampling'")
+        if patches is not None and augment in ('strongweak', 'randaug'):
+            raise ValueError(f'patches={patches!r} cannot be combined with augment={augment!r}')
+        if mean is not None:
+            self.mean = tuple(float(v) for v in mean)
+        if std is not None:
+            self.std = tuple(float(v) for v in std)
+        if resize is not None:
+            self.resize = (int(resize), int(resize)) if isinstance(resize, int) else tuple(int(v) for v in resize)
         if data.dtype != np.uint8 or data.ndim != 4 or data.shape[-1] != 3:
             raise ValueError('expected uint8 images [N,H,W,3]')
         min_label = min(label)
@@ -48,6 +67,10 @@ class _DeviceImageDataset:
             self.transform = DeviceRandAugCrop(in_hw, self.crop, self.device, **norm)
         else:
             self.default_transform = self.transform = DeviceTransform(in_hw, self.resize, self.crop, self.device, **norm)
+        if patches == 'grid':
+            self.transform = DevicePatchGrid(in_hw, self.crop, self.device, patch_list=patch_list, patch_ratio=patch_ratio, train=patch_train, **norm)
+        elif patches == 'sampling':
+            self.transform = DevicePatchSampler(in_hw, self.crop, self.device, num_patch=num_patch, **norm)
 
     def __len__(self):
         return len(self.label)
@@ -60,7 +83,7 @@ class _DeviceImageDataset:
         return self._on_device
 
     def gather(self, index) -> torch.Tensor:
-        """index: LongTensor of dataset indices (one sampler batch) -> float32 [len, 3, 80, 80] on the GPU."""
+        """index: LongTensor of dataset indices (one sampler batch) -> float32 [len, 3, 80, 80] on the GPU ([len, P, 3, 80, 80] with patches)."""
         out = self.transform(self.device_images(), torch.as_tensor(index))
         return out[0] if isinstance(out, tuple) else out   # under 'strongweak': the strong view
 
@@ -87,20 +110,23 @@ class _DeviceImageDataset:
 class MiniImageNet(_DeviceImageDataset):
     resize, crop = (88, 88), 80                         # Resize((88, 88)) -> CenterCrop(80), mini_imagenet.py:49-52
 
-    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, **kwargs):
+    def __init__(self, root_path, split='train', augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, patches=None, patch_list=(2, 3),
+                 patch_ratio=2.0, num_patch=9, patch_train=False, mean=None, std=None, resize=None, **kwargs):
         if augment not in (None, 'resize', 'strongweak', 'randaug'):
             raise NotImplementedError("fsvit: augment=None, 'resize', 'strongweak' and 'randaug' are built ('crop' / 'cropaug' are not)")
         split_tag = 'train_phase_train' if split == 'train' else split
         with open(os.path.join(root_path, 'miniImageNet_category_split_{}.pickle'.format(split_tag)), 'rb') as f:
             pack = pickle.load(f, encoding='latin1')
-        self._finish(np.asarray(pack['data']), pack['labels'], device, augment, strong_prob, weak_randaug)
+        self._finish(np.asarray(pack['data']), pack['labels'], device, augment, strong_prob, weak_randaug, patches, patch_list, patch_ratio, num_patch,
+                     patch_train, mean, std, resize)
 
 
 @register('tiered-imagenet')
 class TieredImageNet(_DeviceImageDataset):
     resize, crop = (80, 80), 80                         # Resize(80) on square images, tiered_imagenet.py:53-57
 
-    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, **kwargs):
+    def __init__(self, root_path, split='train', mini=False, augment=None, device=None, strong_prob=0.5, weak_randaug=0.0, patches=None,
+                 patch_list=(2, 3), patch_ratio=2.0, num_patch=9, patch_train=False, mean=None, std=None, resize=None, **kwargs):
         if augment not in (None, 'test', 'resize', 'strongweak', 'randaug'):       # 'test' = the un-augmented transform, tiered_imagenet.py:90-91
             raise NotImplementedError("fsvit: augment=None, 'test', 'resize', 'strongweak' and 'randaug' are built ('crop' / 'cropaug' are not)")
         data = np.load(os.path.join(root_path, '{}_images.npz'.format(split)), allow_pickle=True)['images']
@@ -122,4 +148,31 @@ class TieredImageNet(_DeviceImageDataset):
                     label_.append(ind[y])
                     cnt[y] += 1
             data, label = data[keep], label_
-        self._finish(np.ascontiguousarray(data), label, device, augment, strong_prob, weak_randaug)
+        self._finish(np.ascontiguousarray(data), label, device, augment, strong_prob, weak_randaug, patches, patch_list, patch_ratio, num_patch,
+                     patch_train, mean, std, resize)
+
+
+@register('synthetic-images')
+class SyntheticImages(_DeviceImageDataset):
+    """A stand-in for a miniImageNet split as RAW images: a uint8 [n_classes * n_per_class, 84, 84, 3] table, image i of class c =
+    clip(128 + 40 mu_c + noise eps_i), fixed by (seed, split, index), behind the transforms of 'mini-imagenet' - the patch modes crop raw
+    images, which 'synthetic-episodes' (finished float images) cannot offer.  The splits carry disjoint class seeds."""
+    resize, crop = (88, 88), 80
+    SPLIT_OFFSET = {'train': 0, 'train_phase_train': 0, 'val': 1, 'test': 2}
+
+    def __init__(self, root_path=None, split='test', n_classes=20, n_per_class=30, image_size=84, noise=20.0, seed=0, augment=None, device=None,
+                 strong_prob=0.5, weak_randaug=0.0, patches=None, patch_list=(2, 3), patch_ratio=2.0, num_patch=9, patch_train=False, mean=None,
+                 std=None, resize=None, **kwargs):
+        if augment not in (None, 'resize', 'strongweak', 'randaug'):
+            raise NotImplementedError("fsvit: augment=None, 'resize', 'strongweak' and 'randaug' are built ('crop' / 'cropaug' are not)")
+        if split not in self.SPLIT_OFFSET:
+            raise ValueError(split)
+        self.class_seeds = [(int(seed) * 3 + self.SPLIT_OFFSET[split]) * 100003 + c for c in range(n_classes)]      # disjoint across the splits of a seed
+        data = np.empty((n_classes * n_per_class, image_size, image_size, 3), dtype=np.uint8)
+        for c, cs in enumerate(self.class_seeds):
+            rng = np.random.Generator(np.random.PCG64(cs))
+            mu = rng.standard_normal((image_size, image_size, 3))
+            eps = rng.standard_normal((n_per_class, image_size, image_size, 3))
+            data[c * n_per_class:(c + 1) * n_per_class] = np.clip(np.rint(128.0 + 40.0 * mu[None] + float(noise) * eps), 0, 255).astype(np.uint8)
+        self._finish(data, np.repeat(np.arange(n_classes), n_per_class).tolist(), device, augment, strong_prob, weak_randaug, patches, patch_list,
+                     patch_ratio, num_patch, patch_train, mean, std, resize)

@@ -207,6 +207,103 @@ class DeviceRandomResizedCrop:
         return out
 
 
+# ---------------------------------------------------------------- SUN-D patch loaders (meta_tuning_sun_d/Models/dataloader/miniimagenet/{grid,sampling})
+# Both are "crop box -> Pillow BILINEAR resize to out x out -> optional mirror -> ToTensor -> Normalize" per patch: fsvit_image_transform_rrc_gather with
+# B * P rows (index repeated per patch, one box and one flip per row).
+SUND_MEAN = tuple(x / 255.0 for x in (125.3, 123.0, 113.9))         # the statistics of the reference's SUN-D csv loaders
+SUND_STD = tuple(x / 255.0 for x in (63.0, 62.1, 66.7))
+
+
+def grid_location(size, ratio, num_grid):
+    """get_grid_location (grid/mini_imagenet.py:78-97): the num_grid (lo, hi) extents along one axis of `size` pixels.  Even cells of
+    int(size / num_grid) pixels, enlarged about their centres to int(size / num_grid * ratio) (float64, Python's operation order), clipped."""
+    raw = int(size / num_grid)
+    enl = int(size / num_grid * ratio)
+    centre = raw // 2
+    out = []
+    for _ in range(num_grid):
+        out.append((max(0, centre - enl // 2), min(size, centre + enl // 2)))
+        centre += raw
+    return out
+
+
+def grid_boxes(H, W, ratio, num_grid):
+    """The num_grid^2 boxes (top, left, height, width) of one pyramid level (get_pyramid, :116-131): rows (h) outer, columns (w) inner."""
+    cols, rows = grid_location(W, ratio, num_grid), grid_location(H, ratio, num_grid)
+    return [(t, l, b - t, r - l) for t, b in rows for l, r in cols]
+
+
+class _DevicePatches:
+    """B images -> [B, P, 3, out, out]: one launch of the random-resized-crop gather over B * P (index, box, flip) rows."""
+
+    def __init__(self, in_hw, out, device, mean, std, seed):
+        self._rrc = DeviceRandomResizedCrop(in_hw, out, device, mean=mean, std=std, seed=seed)
+        self.H, self.W = in_hw
+        self.out = int(out)
+        self.device = self._rrc.device
+        self.generator = self._rrc.generator
+        self.boxes = self.flips = None
+
+    def manual_seed(self, seed):
+        self.generator.manual_seed(int(seed))
+        return self
+
+    def draw(self, B):
+        raise NotImplementedError
+
+    def __call__(self, images: torch.Tensor, index: torch.Tensor, boxes=None, flips=None) -> torch.Tensor:
+        """boxes int [B * P, 4] (top, left, height, width) and flips [B * P], image-major, or neither (drawn from this object's generator)."""
+        index = torch.as_tensor(index).reshape(-1)
+        B, P = index.numel(), self.n_patch
+        if (boxes is None) != (flips is None):
+            raise ValueError('pass both boxes and flips, or neither')
+        if boxes is None:
+            boxes, flips = self.draw(B)
+        out = self._rrc(images, index.repeat_interleave(P), boxes, flips)
+        self.boxes, self.flips = self._rrc.boxes, self._rrc.flips
+        return out.view(B, P, 3, self.out, self.out)
+
+
+class DevicePatchGrid(_DevicePatches):
+    """The grid patches of SUN-D (grid/mini_imagenet.py:78-148): for every level n of `patch_list`, the n x n cells of the image enlarged by a
+    ratio about their centres, each resized to out x out.  Patch order: levels in order; inside a level rows outer, columns inner.
+    train=False (val / test): ratio = patch_ratio, no flips.  train=True: one ratio = 1 + 2 u, u ~ U[0, 1), per (image, level) - the reference draws
+    once per get_pyramid call - and an independent flip with probability 0.5 per patch (the flip is inside the per-patch transform).  The
+    distribution is restated, not the stream of Python's `random` (the stance of random_resized_crop_boxes)."""
+
+    def __init__(self, in_hw, out, device, patch_list=(2, 3), patch_ratio=2.0, train=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0):
+        super().__init__(in_hw, out, device, mean, std, seed)
+        self.patch_list = tuple(int(n) for n in patch_list)
+        if not self.patch_list or min(self.patch_list) < 1:
+            raise ValueError(f'patch_list {patch_list!r}')
+        self.patch_ratio, self.train = float(patch_ratio), bool(train)
+        self.n_patch = sum(n * n for n in self.patch_list)
+
+    def draw(self, B):
+        if not self.train:
+            one = [b for n in self.patch_list for b in grid_boxes(self.H, self.W, self.patch_ratio, n)]
+            return torch.tensor(one, dtype=torch.int32).repeat(B, 1), torch.zeros(B * self.n_patch, dtype=torch.bool)
+        u = torch.rand(B, len(self.patch_list), generator=self.generator, dtype=torch.float64)
+        flips = torch.rand(B * self.n_patch, generator=self.generator) < 0.5
+        boxes = [b for i in range(B) for k, n in enumerate(self.patch_list) for b in grid_boxes(self.H, self.W, 1 + 2 * float(u[i, k]), n)]
+        return torch.tensor(boxes, dtype=torch.int32), flips
+
+
+class DevicePatchSampler(_DevicePatches):
+    """The sampled patches of SUN-D (sampling/mini_imagenet.py:41-58, the variant data_utils.set_up_datasets selects): num_patch independent
+    RandomResizedCrop(out) + RandomHorizontalFlip per image, for every split - the reference samples random patches at evaluation time too."""
+
+    def __init__(self, in_hw, out, device, num_patch=9, mean=IMAGENET_MEAN, std=IMAGENET_STD, seed=0):
+        super().__init__(in_hw, out, device, mean, std, seed)
+        self.n_patch = int(num_patch)
+        if self.n_patch < 1:
+            raise ValueError(f'num_patch {num_patch!r}')
+
+    def draw(self, B):
+        n = B * self.n_patch
+        return random_resized_crop_boxes(n, self.H, self.W, self.generator), torch.rand(n, generator=self.generator) < 0.5
+
+
 # ---------------------------------------------------------------- the distillation phase's strong / weak view pair
 # (sun_meta_training/datasets/mini_imagenet.py:91-124, :194-204).  One int32 row per image tells the kernel behind fsvit_image_strong_weak what to do;
 # the three factors are float32 bit patterns.

@@ -962,6 +962,66 @@ class ops:
             _lib.check(lib.fsvit_sgd_step(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum),
                                           float(weight_decay), int(bool(first_step)), _stream_ptr(param.device)))
 
+    _sgd_nesterov_tables = {}
+
+    @staticmethod
+    def sgd_nesterov_step_multi(params, grads, bufs, lr, momentum, weight_decay, first_step):
+        """torch.optim.SGD(nesterov=True) for a list of fp32 tensors in one launch (fsvit_sgd_nesterov_step_multi); the pointer table is cached and
+        re-uploaded only when a pointer changed (as ops.sgd_step_multi).  -> the device table."""
+        if not params:
+            return
+        _require_cuda(*params)
+        lib = _lib.load()
+        bump_weight_generation(params)
+        dev = params[0].device
+        rows = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), p.numel()) for p, g, b in zip(params, grads, bufs))
+        cached = ops._sgd_nesterov_tables.get(dev)
+        if cached is None or cached[0] != rows:
+            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
+            with torch.cuda.device(dev):
+                cached = (rows, table.to(dev, non_blocking=True), table)
+            ops._sgd_nesterov_tables[dev] = cached
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_sgd_nesterov_step_multi(_ptr(cached[1]), len(params), max(r[3] for r in rows), float(lr), float(momentum),
+                                                         float(weight_decay), int(bool(first_step)), _stream_ptr(dev)))
+        return cached[1]
+
+    @staticmethod
+    def sgd_nesterov_step(param, grad, buf, lr, momentum, weight_decay, first_step):
+        _require_cuda(param, grad, buf)
+        lib = _lib.load()
+        bump_weight_generation((param,))
+        with torch.cuda.device(param.device):
+            _lib.check(lib.fsvit_sgd_nesterov_step(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum),
+                                                   float(weight_decay), int(bool(first_step)), _stream_ptr(param.device)))
+
+    _guard_tables = {}
+
+    @staticmethod
+    def grad_nan_guard(grads, device=None):
+        """detect_grad_nan of the reference for a list of contiguous fp32 gradient tensors (fsvit_grad_nan_guard_multi): a tensor holding any NaN is
+        zeroed entirely (Inf does not count) -> int32 device tensor [len(grads)] of 0 / 1 flags.  No host synchronisation; the {pointer, numel}
+        table is cached and re-uploaded only when a pointer changed."""
+        if not grads:
+            return torch.zeros(0, dtype=torch.int32, device=device if device is not None else 'cuda')
+        _require_cuda(*grads)
+        for g in grads:
+            if g.dtype != torch.float32 or not g.is_contiguous():
+                raise ValueError('grad_nan_guard: contiguous fp32 tensors')
+        lib = _lib.load()
+        dev = grads[0].device
+        rows = tuple((g.data_ptr(), g.numel()) for g in grads)
+        cached = ops._guard_tables.get(dev)
+        if cached is None or cached[0] != rows:
+            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
+            with torch.cuda.device(dev):
+                cached = (rows, table.to(dev, non_blocking=True), table)
+            ops._guard_tables[dev] = cached
+        flags = torch.empty(len(grads), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_grad_nan_guard_multi(_ptr(cached[1]), len(grads), max(r[1] for r in rows), _ptr(flags), _stream_ptr(dev)))
+        return flags
+
     _tickets = {}
 
     @staticmethod

@@ -8,7 +8,11 @@ Flags are the reference's (eval.py:18-50).  Differences: datasets come through t
 stand-in; `-dataset_args` a YAML dict), episodes are drawn by this package's CategoriesSampler (class-major batches; SUN-D's own `randperm` sampler
 stream is not reproduced), `-episodes_per_launch` episodes go through the encoder and the head per launch - one episode's 375
 transportation problems are fewer than the GPU's SIMDs -, and the solver's status is checked once per evaluation.  Without `-model_dir` the encoder
-carries the procedural stand-in weights.  Reports the mean accuracy and its 95 % interval over episodes (eval.py:100-104)."""
+carries the procedural stand-in weights.  `-deepemd grid` / `sampling` build the dataset with the matching patch loader (`-patch_list`, `-patch_ratio`,
+`-num_patch`; they need a dataset of raw images: 'mini-imagenet', 'tiered-imagenet', 'synthetic-images') and seed its generator from `-seed`; `-set`
+overrides the split of `-dataset_args`; `-norm_stats sund` normalises with the statistics of the reference's SUN-D loaders.  `-deepemd fcn` keeps the
+dataset's own eval transform: the reference's fcn loader (Resize([92, 92]) -> CenterCrop(80)), which train_deepemd applies to its val / test splits by
+itself, is `-dataset_args '{..., resize: [92, 92]}'` here.  Reports the mean accuracy and its 95 % interval over episodes (eval.py:100-104)."""
 import argparse
 
 import numpy as np
@@ -21,13 +25,27 @@ from .utils import few_shot as fs
 
 
 def load_params(model, path):
-    """load_model (Models/utils.py): the checkpoint's `params` with the DataParallel prefix removed, encoder keys only."""
-    sd = torch.load(path, map_location='cpu')
-    sd = sd.get('params', sd)
-    sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
-    sd = {k: v for k, v in sd.items() if k.startswith('encoder.')}
-    model.load_state_dict(sd, strict=True)
-    return model
+    """load_model (Models/utils.py): the checkpoint's `model_sd` / `params` with the DataParallel prefix removed, encoder keys only."""
+    from .models.deepemd import load_encoder_params
+    return load_encoder_params(model, path)
+
+
+def patch_dataset_args(args, train=False):
+    """The dataset keywords of `-deepemd`: fcn -> whole images; grid -> the patch pyramid (random ratios / flips for the train split only);
+    sampling -> random patches for every split.  `-norm_stats sund` selects the statistics of the reference's SUN-D loaders."""
+    from .datasets.transforms import SUND_MEAN, SUND_STD
+    kw = {}
+    if args.deepemd == 'grid':
+        kw.update(patches='grid', patch_list=tuple(args.patch_list), patch_ratio=args.patch_ratio, patch_train=bool(train))
+    elif args.deepemd == 'sampling':
+        kw.update(patches='sampling', num_patch=args.num_patch)
+    if args.norm_stats == 'sund':
+        kw.update(mean=SUND_MEAN, std=SUND_STD)
+    return kw
+
+
+def parse_patch_list(text):
+    return [int(x) for x in str(text).split(',')]
 
 
 def build_model(args):
@@ -42,13 +60,20 @@ def build_model(args):
 
 
 def evaluate(args, log=print):
-    if args.deepemd != 'fcn':
-        raise NotImplementedError("fsvit: the patch-cropping data loaders of -deepemd grid / sampling are not built (DESIGN.md 7); the model takes patch batches")
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     device = torch.device('cuda', torch.cuda.current_device())
     gen = torch.Generator().manual_seed(args.seed)            # the SFC permutations (torch.randperm per step and episode)
-    dataset = datasets.make(args.dataset, **args.dataset_args)
+    dataset_args = dict(args.dataset_args)
+    if args.set is not None:
+        dataset_args['split'] = args.set
+    extra = patch_dataset_args(args)
+    if extra and args.dataset == 'synthetic-episodes':
+        raise ValueError("fsvit: 'synthetic-episodes' yields finished float images; the patch modes and -norm_stats need raw images ('synthetic-images')")
+    dataset = datasets.make(args.dataset, **{**dataset_args, **extra})
+    transform = getattr(dataset, 'transform', None)
+    if hasattr(transform, 'manual_seed'):
+        transform.manual_seed(args.seed)                      # -deepemd sampling: the random patches follow -seed, as the episodes do
     model = build_model(args).to(device).eval()
     model.sfc_generator = gen
     sampler = CategoriesSampler(dataset.label, args.test_episode, args.way, args.shot + args.query)
@@ -97,6 +122,11 @@ def main(argv=None):
     p.add_argument('-norm', default='center')
     p.add_argument('-deepemd', default='fcn', choices=['fcn', 'grid', 'sampling'])
     p.add_argument('-feature_pyramid', default=None)
+    p.add_argument('-num_patch', type=int, default=9)
+    p.add_argument('-patch_list', type=parse_patch_list, default=[2, 3])
+    p.add_argument('-patch_ratio', type=float, default=2.0)
+    p.add_argument('-set', default=None, choices=[None, 'train', 'val', 'test'])
+    p.add_argument('-norm_stats', default='imagenet', choices=['imagenet', 'sund'])
     p.add_argument('-solver', default='opencv')
     p.add_argument('-sfc_lr', type=float, default=100)
     p.add_argument('-sfc_update_step', type=float, default=100)

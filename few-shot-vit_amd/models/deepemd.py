@@ -22,6 +22,26 @@ def check_status_count(count) -> None:
         raise RuntimeError(f'fsvit: {n} DeepEMD transportation problem(s) stopped at a loop bound of the solver (status 1); their logits are not optimal')
 
 
+def encoder_state_dict(checkpoint, model_keys=None):
+    """load_model (meta_tuning_sun_d/Models/utils.py:76-99) up to the load itself: the checkpoint's `model_sd` or else `params` (or the mapping
+    itself), without `temp`, the DataParallel prefix `module.` stripped, keys of a bare pre-trained encoder prefixed with `encoder.`, and then the
+    `encoder.*` keys only (with `model_keys`: those the model has, as the reference's `k in model_dict`).  Following load_model, a checkpoint of bare
+    keys is accepted and `encoder.*` keys the model lacks are dropped silently: such a checkpoint no longer fails the strict load that
+    eval_deepemd.load_params did before this helper; a MISSING encoder key still fails it."""
+    sd = checkpoint.get('model_sd', checkpoint.get('params', checkpoint)) if isinstance(checkpoint, dict) else checkpoint
+    sd = {k: v for k, v in sd.items() if k != 'temp'}
+    sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
+    if sd and not any(k.startswith('encoder.') for k in sd):
+        sd = {'encoder.' + k: v for k, v in sd.items()}
+    return {k: v for k, v in sd.items() if k.startswith('encoder.') and (model_keys is None or k in model_keys)}
+
+
+def load_encoder_params(model, path):
+    """Load the encoder of a SUN-D / pre-training checkpoint file into a DeepEMD model (strict: every encoder key must be there)."""
+    model.load_state_dict(encoder_state_dict(torch.load(path, map_location='cpu'), set(model.state_dict().keys())), strict=True)
+    return model
+
+
 @register('deepemd')
 class DeepEMD(nn.Module):
 

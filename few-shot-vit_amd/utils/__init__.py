@@ -140,11 +140,13 @@ def mean_confidence_interval(data, confidence=0.95):
 
 
 class FsvitSGD(torch.optim.Optimizer):
-    """torch.optim.SGD(params, lr, momentum, weight_decay) semantics (no dampening / nesterov) with the update done by
-    the HIP kernel behind fsvit_sgd_step; exposes param_groups so MultiStepLR drives `lr` as in the reference."""
+    """torch.optim.SGD(params, lr, momentum, weight_decay[, nesterov]) semantics (no dampening) with the update done by the HIP kernel behind
+    fsvit_sgd_step (nesterov=True: fsvit_sgd_nesterov_step); exposes param_groups so MultiStepLR / StepLR drive `lr` as in the reference."""
 
-    def __init__(self, params, lr, momentum=0.9, weight_decay=0.):
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0., nesterov=False):
+        if nesterov and momentum <= 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=bool(nesterov)))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -163,8 +165,19 @@ class FsvitSGD(torch.optim.Optimizer):
                     raise RuntimeError('FsvitSGD: parameters must be contiguous fp32 CUDA tensors')
                 ps, gs, bs = batches[first]
                 ps.append(data.view(-1)); gs.append(p.grad.contiguous().view(-1)); bs.append(st['momentum_buffer'].view(-1))
+            step_multi = ops.sgd_nesterov_step_multi if group.get('nesterov') else ops.sgd_step_multi
             for first, (ps, gs, bs) in batches.items():
-                ops.sgd_step_multi(ps, gs, bs, group['lr'], group['momentum'], group['weight_decay'], first)      # one launch per param_group
+                step_multi(ps, gs, bs, group['lr'], group['momentum'], group['weight_decay'], first)      # one launch per param_group
+
+
+def detect_grad_nan(model):
+    """detect_grad_nan (meta_tuning_sun_d/Models/utils.py:115-118): the gradient of every parameter that holds a NaN is zeroed entirely, in one
+    table-driven pass on the device (ops.grad_nan_guard) -> device int64 scalar, the number of tensors zeroed by this call (no host read)."""
+    from ..engine import ops
+    grads = [p.grad for p in model.parameters() if p.grad is not None]
+    if not grads:
+        return torch.zeros((), dtype=torch.int64, device=next(model.parameters()).device)
+    return ops.grad_nan_guard(grads).sum(dtype=torch.int64)
 
 
 def make_optimizer(params, name, lr, weight_decay=None, milestones=None, gamma=0.1):

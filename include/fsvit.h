@@ -445,6 +445,17 @@ int fsvit_sgd_step_multi(const void* items_dev, int n_items, size_t max_numel, f
 /* torch.optim.SGD(momentum, weight_decay) update of one fp32 tensor (utils/__init__.py:127-139) */
 int fsvit_sgd_step(float* param_dev, const float* grad_dev, float* momentum_buf_dev, size_t n, float lr, float momentum,
                    float weight_decay, int first_step, void* stream);
+/* torch.optim.SGD(momentum, weight_decay, nesterov=True, dampening=0) (meta_tuning_sun_d/train_meta.py:115): d = g + wd p; buf = d on the first
+ * step, else momentum buf + d; p -= lr (d + momentum buf).  The multi form takes the table of fsvit_sgd_step_multi. */
+int fsvit_sgd_nesterov_step_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float weight_decay,
+                                  int first_step, void* stream);
+int fsvit_sgd_nesterov_step(float* param_dev, const float* grad_dev, float* momentum_buf_dev, size_t n, float lr, float momentum,
+                            float weight_decay, int first_step, void* stream);
+/* detect_grad_nan (meta_tuning_sun_d/Models/utils.py:115-118) without a host round trip.  items_dev: DEVICE array of n_items records
+ * {float* grad; size_t numel} (2 x 8 bytes each); max_numel = the largest numel; flags_dev: int32 [n_items].  In stream order: flags are
+ * cleared; flags[i] = 1 for every tensor holding a NaN (g != g: +-Inf does not count); the flagged tensors are zeroed entirely.  The flags
+ * stay on the device for the caller to sum. */
+int fsvit_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int32_t* flags_dev, void* stream);
 /* ---------------------------------------------------------------- device-resident dataset transform
  * Replaces, for a gathered batch of dataset indices, the per-image CPU pipeline of the reference's datasets
  * (test_phase/datasets/mini_imagenet.py:47-56: Resize((88,88)) -> CenterCrop(80) -> ToTensor -> Normalize;
