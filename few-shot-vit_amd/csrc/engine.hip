@@ -22,9 +22,9 @@
 
 using namespace fsvit;
 
-// Kernel-namespace dispatch: every kernel exists for the two 16-bit storage types (namespace fsvit = bf16, fsvit_f16 = fp16; see
-// fsvit_common.h).  K(fn) picks the build that matches `kdt` (a FSVIT_* dtype in scope); kd() maps the public dtype to the kernels'
-// own convention (0 = f32, 1 = the namespace's 16-bit type).
+// Kernel-namespace dispatch: every kernel that touches 16-bit activations exists for the two 16-bit storage types (namespace fsvit = bf16,
+// fsvit_f16 = fp16; see fsvit_common.h).  K(fn) picks the build that matches `kdt` (a FSVIT_* dtype in scope); kd() maps the public dtype
+// to the kernels' own convention (0 = f32, 1 = the namespace's 16-bit type).  The fp32-only heads (kernels.h, bottom) are fsvit:: alone.
 // The two-limb modes (FSVIT_BF16X2 / FSVIT_F16X2) are fp32 STORAGE (kd() = 0: every kernel but the GEMM is the fp32 path's) with the GEMM
 // arithmetic selected by kg() = 2 (conv_gemm_v2.hip: x2_split) and the weights uploaded pre-split.
 #define K(fn) ((kdt == FSVIT_F16 || kdt == FSVIT_F16X2) ? fsvit_f16::fn : fsvit::fn)
@@ -992,19 +992,17 @@ extern "C" int fsvit_visformer_last_tokens(fsvit_visformer* h, const void* ws, s
 
 extern "C" int fsvit_proto_head(const float* fs, const float* fq, int E, int way, int shot, int Q, int D, float temp,
                                 int method, float* logits, float* acc, float* loss, void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!fs || !fq || !logits) return fail(FSVIT_ERR_ARG, "null argument");
   if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
-  RC_TRY(K(launch_proto_head)(fs, fq, E, way, shot, Q, D, temp, method, logits, acc, loss, (hipStream_t)stream, nullptr));
+  RC_TRY(fsvit::launch_proto_head(fs, fq, E, way, shot, Q, D, temp, method, logits, acc, loss, (hipStream_t)stream, nullptr));
   return 0;
 }
 
 extern "C" int fsvit_proto_head_devtemp(const float* fs, const float* fq, int E, int way, int shot, int Q, int D, const float* temp_dev,
                                         int method, float* logits, float* acc, float* loss, void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!fs || !fq || !logits || !temp_dev) return fail(FSVIT_ERR_ARG, "null argument");
   if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
-  RC_TRY(K(launch_proto_head)(fs, fq, E, way, shot, Q, D, 0.f, method, logits, acc, loss, (hipStream_t)stream, temp_dev));
+  RC_TRY(fsvit::launch_proto_head(fs, fq, E, way, shot, Q, D, 0.f, method, logits, acc, loss, (hipStream_t)stream, temp_dev));
   return 0;
 }
 
@@ -1261,30 +1259,26 @@ extern "C" int fsvit_patch_embed2x2_dt(const void* x, void* y, const void* w, in
 
 // ---- distillation head (sun_meta_training/offline.py, models/token_label.py, models/classifier.py)
 extern "C" int fsvit_linear_forward(const float* x, const float* w, const float* b, float* y, int M, int N, int K, void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!x || !w || !y || (K & 3) || N <= 0 || K <= 0) return fail(FSVIT_ERR_ARG, "fsvit_linear_forward: null argument or K %% 4 != 0");
-  RC_TRY(K(launch_linear_fwd)(x, w, b, y, M, N, K, (hipStream_t)stream));
+  RC_TRY(fsvit::launch_linear_fwd(x, w, b, y, M, N, K, (hipStream_t)stream));
   return 0;
 }
 extern "C" int fsvit_linear_backward(const float* dy, const float* x, const float* w, float* dx, int accumulate_dx, float* dw, float* db,
                                      int M, int N, int K, void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!dy || (dx && !w) || (dw && !x) || N <= 0 || K <= 0) return fail(FSVIT_ERR_ARG, "fsvit_linear_backward: bad argument");
-  RC_TRY(K(launch_linear_bwd)(dy, x, w, dx, accumulate_dx, dw, db, M, N, K, (hipStream_t)stream));
+  RC_TRY(fsvit::launch_linear_bwd(dy, x, w, dx, accumulate_dx, dw, db, M, N, K, (hipStream_t)stream));
   return 0;
 }
 extern "C" int fsvit_token_softlabel(const float* teacher_logits, float* soft, int B, int T, int C, int k, int bp, double smoothing, void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!teacher_logits || !soft || T > 64 || T <= 0 || C < 2 || k < 1 || k > C || bp < 0 || bp > T)
     return fail(FSVIT_ERR_ARG, "fsvit_token_softlabel: bad argument (T <= 64, 1 <= k <= C, 0 <= bp <= T)");
-  RC_TRY(K(launch_token_softlabel)(teacher_logits, soft, B, T, C, k, bp, smoothing, (hipStream_t)stream));
+  RC_TRY(fsvit::launch_token_softlabel(teacher_logits, soft, B, T, C, k, bp, smoothing, (hipStream_t)stream));
   return 0;
 }
 extern "C" int fsvit_soft_target_ce(const float* logits, const float* target, float* row_loss, float* dlogits, int R, int C, float grad_scale,
                                     void* stream) {
-  const int kdt = FSVIT_BF16;
   if (!logits || !target || !row_loss || C <= 0) return fail(FSVIT_ERR_ARG, "fsvit_soft_target_ce: bad argument");
-  RC_TRY(K(launch_soft_target_ce)(logits, target, row_loss, dlogits, R, C, grad_scale, (hipStream_t)stream));
+  RC_TRY(fsvit::launch_soft_target_ce(logits, target, row_loss, dlogits, R, C, grad_scale, (hipStream_t)stream));
   return 0;
 }
 extern "C" int fsvit_row_normalize(const float* x, float* y, float* inv_norm, int R, int D, void* stream) {
@@ -1297,22 +1291,6 @@ extern "C" int fsvit_row_normalize_backward(const float* y, const float* inv_nor
   RC_TRY(fsvit::launch_row_normalize_bwd(y, inv_norm, dy, dx, R, D, (hipStream_t)stream));
   return 0;
 }
-extern "C" int fsvit_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                                float weight_decay, int step, void* stream) {
-  const int kdt = FSVIT_BF16;
-  if (!p || !g || !m || !v || step < 1) return fail(FSVIT_ERR_ARG, "fsvit_adamw_step: bad argument");
-  RC_TRY(K(launch_adamw)(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int fsvit_adamw_step_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                      int step, void* stream) {
-  const int kdt = FSVIT_BF16;
-  if (!items_dev || n_items < 0 || step < 1) return fail(FSVIT_ERR_ARG, "fsvit_adamw_step_multi: bad argument");
-  RC_TRY(K(launch_adamw_multi)(items_dev, n_items, max_numel, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
-  return 0;
-}
-
 extern "C" int fsvit_qkv_attention(const void* x, const void* wqkv, int kw, const float* bias, void* ctx, int B, int S, int C, int heads, int hdp,
                                    float scale, void* stream) {
   return fsvit_qkv_attention_dt(x, wqkv, kw, bias, ctx, B, S, C, heads, hdp, scale, FSVIT_BF16, stream);

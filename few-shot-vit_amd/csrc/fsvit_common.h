@@ -275,6 +275,12 @@ inline int launch(void (*k)(KA...), dim3 grid, dim3 block, size_t lds, hipStream
   return (int)hipGetLastError();
 }
 inline int vec_width(int dtype) { return dtype == 0 ? 4 : 8; }      // elements of a 16-byte access (Elem<T>::kPerChunk of the type `dtype` names)
+// grid-stride elementwise kernels (train_kernels.hip, optim.hip): one thread per element up to 32768 blocks, the loop strides beyond
+static inline unsigned gs_grid(size_t total, int per_block = 256) {
+  size_t nb = (total + per_block - 1) / per_block;
+  return (unsigned)(nb > 32768 ? 32768 : (nb < 1 ? 1 : nb));
+}
+#define GS_LOOP(idx, total) for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (total); idx += (size_t)gridDim.x * blockDim.x)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

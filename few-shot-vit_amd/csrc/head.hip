@@ -1,6 +1,4 @@
-// Episode head kernels.
-//  * pool_affine: final BatchNorm (eval, folded to scale/shift) + AdaptiveAvgPool2d(1) + flatten
-//    (test_phase/models/visformer.py:455-462): feat[b][c] = scale[c] * mean_hw x[b][hw][c] + shift[c].
+// Episode head kernels, fp32, one build (the pooled feature they read comes from pool_affine, feat_out.hip).
 //  * proto_head: MetaBaseline head (test_phase/models/meta_baseline.py:33-47) with
 //    utils.compute_logits 'dot' after F.normalize / 'sqr' (utils/__init__.py:78-101), plus the
 //    per-episode accuracy and mean cross-entropy of the eval loop (test_few_shot.py:89-90,
@@ -10,28 +8,7 @@
 #include "kernels.h"
 #include "train_kernels.h"
 
-namespace FSVIT_NS {
-
-template <typename T>
-__global__ __launch_bounds__(256) void pool_affine_kernel(const T* __restrict__ x, const float* __restrict__ scale,
-                                                          const float* __restrict__ shift, float* __restrict__ feat,
-                                                          int HW, int C) {
-  const int b = blockIdx.x;
-  const T* xb = x + (size_t)b * HW * C;
-  const float inv = 1.0f / (float)HW;
-  for (int c4 = threadIdx.x; c4 < C / 4; c4 += 256) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < HW; ++p) acc += load4<T>(xb + (size_t)p * C + c4 * 4);
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(scale + c4 * 4);
-    const f32x4 sh = *reinterpret_cast<const f32x4*>(shift + c4 * 4);
-    *reinterpret_cast<f32x4*>(feat + (size_t)b * C + c4 * 4) = acc * inv * sc + sh;
-  }
-}
-
-int launch_pool_affine(const void* x, const float* scale, const float* shift, float* feat, int B, int HW, int C, int dtype, hipStream_t s) {
-  if (B <= 0) return 0;
-  return with_elem(dtype, [&](auto e) { return launch(pool_affine_kernel<elem_t<decltype(e)>>, B, 256, 0, s, x, scale, shift, feat, HW, C); });
-}
+namespace fsvit {
 
 // method: 0 = 'cos' (normalise both, dot), 1 = 'sqr' (negative squared distance to the mean prototype),
 //         2 = 'dot' (plain dot product with the mean prototype)
@@ -326,4 +303,4 @@ int launch_proto_head_bwd(const float* feat_shot, const float* feat_query, const
   return (int)hipGetLastError();
 }
 
-}  // namespace FSVIT_NS
+}  // namespace fsvit

@@ -1,5 +1,6 @@
 // Internal launchers of the fsvit gfx950 kernels.  Every kernel source that touches 16-bit activations is compiled twice
-// (fsvit_common.h): the same declarations exist in namespace fsvit (bf16) and namespace fsvit_f16 (fp16).
+// (fsvit_common.h): the declarations of kernels_decl.inc exist in namespace fsvit (bf16) and namespace fsvit_f16 (fp16).  The fp32-only
+// heads at the bottom are built once; the training-path and optimizer launchers are in train_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "conv_gemm.h"
@@ -11,8 +12,21 @@
 #include "kernels_decl.inc"
 #undef FSVIT_DECL_NS
 
-// DeepEMD head (emd_head.hip): fp32 only, one build.  workspace = emd_head_workspace_bytes(E, P, Q, N, C); N <= 32, C a multiple of 64 (checked by the C entries)
+// ---- fp32 only, one build: namespace fsvit alone
 namespace fsvit {
+// cosine / squared-distance prototype head (head.hip; meta_baseline.py:33-47, utils/__init__.py:78-109); its backwards: train_kernels.h
+int launch_proto_head(const float* feat_shot, const float* feat_query, int E, int way, int shot, int Q, int D,
+                      float temp, int method, float* logits, float* acc, float* loss, hipStream_t s, const float* temp_dev = nullptr);
+int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const long long* labels, int E, int way, int shot, int Q, int D, float temp, int method,
+                         float* logits, float* acc, float* loss, float* dlogits, float* mean_out, unsigned* ticket, hipStream_t s, const float* temp_dev = nullptr);
+// distillation head (token_label.hip): LinearClassifier forward / backward, generate_softlabel, SoftTargetCrossEntropy, F.normalize on rows
+int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s);
+int launch_linear_bwd(const float* dy, const float* x, const float* w, float* dx, int accumulate_dx, float* dw, float* db, int M, int N, int K, hipStream_t s);
+int launch_token_softlabel(const float* lt, float* soft, int B, int T, int C, int k, int bp, double smoothing, hipStream_t s);
+int launch_soft_target_ce(const float* z, const float* tgt, float* rowloss, float* dz, int R, int C, float gscale, hipStream_t s);
+int launch_row_normalize(const float* x, float* y, float* inv, int R, int D, hipStream_t s);
+int launch_row_normalize_bwd(const float* y, const float* inv, const float* dy, float* dx, int R, int D, hipStream_t s);
+// DeepEMD head (emd_head.hip).  workspace = emd_head_workspace_bytes(E, P, Q, N, C); N <= 32, C a multiple of 64 (checked by the C entries)
 size_t emd_head_workspace_bytes(int E, int P, int Q, int N, int C);
 int launch_emd_head_forward(const float* shot_tok, const float* query_tok, int E, int P, int Q, int N, int C, float temperature, float* logits, float* flow,
                             int* status, void* ws, hipStream_t s);

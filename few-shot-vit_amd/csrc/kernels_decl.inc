@@ -16,14 +16,8 @@ int attention_route(int S, int hdp, int dtype);      // the kernel launch_attent
 size_t attention_lds_bytes(int S, int hdp, int dtype);
 int attention_padded_head_dim(int hd, int S, int dtype);      // what the weight packer pads a head to
 
-// x [B][HW][C] -> feat [B][C] fp32 = scale[c] * mean_hw(x) + shift[c]
+// x [B][HW][C] -> feat [B][C] fp32 = scale[c] * mean_hw(x) + shift[c]  (feat_out.hip)
 int launch_pool_affine(const void* x, const float* scale, const float* shift, float* feat, int B, int HW, int C, int dtype, hipStream_t s);
-
-// cosine / squared-distance prototype head (meta_baseline.py:33-47, utils/__init__.py:78-109)
-int launch_proto_head(const float* feat_shot, const float* feat_query, int E, int way, int shot, int Q, int D,
-                      float temp, int method, float* logits, float* acc, float* loss, hipStream_t s, const float* temp_dev = nullptr);
-int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const long long* labels, int E, int way, int shot, int Q, int D, float temp, int method,
-                         float* logits, float* acc, float* loss, float* dlogits, float* mean_out, unsigned* ticket, hipStream_t s, const float* temp_dev = nullptr);
 
 // fused stage-1 block; x and y must be different buffers.  stage1_ring.hip: wave = channel group and register-resident weights, on the packed layers themselves (w1 [256][128], w2 [256][320], w3 [128][256])
 bool stage1_ring_supported(int dtype, int C1, int hid, int group, int H1);
@@ -80,17 +74,9 @@ size_t qkv_attn_image_bytes();
 int launch_qkv_attn_pack(const void* w, int kw, void* img, hipStream_t s);
 int launch_qkv_attn(const void* x, void* ctx, const void* wimg, const float* bias, int B, int S, float scale, hipStream_t s);
 
-// distillation head (token_label.hip; fp32): LinearClassifier forward / backward, generate_softlabel, SoftTargetCrossEntropy, AdamW
-int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s);
-int launch_linear_bwd(const float* dy, const float* x, const float* w, float* dx, int accumulate_dx, float* dw, float* db, int M, int N, int K, hipStream_t s);
-int launch_token_softlabel(const float* lt, float* soft, int B, int T, int C, int k, int bp, double smoothing, hipStream_t s);
-int launch_soft_target_ce(const float* z, const float* tgt, float* rowloss, float* dz, int R, int C, float gscale, hipStream_t s);
+// token map plumbing (feat_out.hip): out[i] = in[i] (* scale[c] + shift[c] when scale != NULL) in fp32; inout += add
 int launch_tokens_to_f32(const void* in, const float* scale, const float* shift, float* out, size_t n, int C, int dtype, hipStream_t s);
 int launch_add_f32_into(void* inout, const float* add, size_t n, int dtype, hipStream_t s);
-int launch_row_normalize(const float* x, float* y, float* inv, int R, int D, hipStream_t s);
-int launch_row_normalize_bwd(const float* y, const float* inv, const float* dy, float* dx, int R, int D, hipStream_t s);
-int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s);
-int launch_adamw_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s);
 
 // ViT / DeiT helpers (vit.hip)
 int launch_patchify(const float* x_nchw, void* out, int B, int img, int p, int Kp, int dtype, hipStream_t s);

@@ -1,15 +1,16 @@
-// Distillation head of the SUN meta-training phase (sun_meta_training/offline.py, models/token_label.py), fp32:
+// Distillation head of the SUN meta-training phase (sun_meta_training/offline.py, models/token_label.py), fp32, one build:
 //   * LinearClassifier forward / backward (classifier.py:27-34) for the per-token head (512 -> n_classes + 1 on every one of the
 //     25 tokens) and the global head (512 -> n_classes on the pooled feature) of TokenLabelOffline (token_label.py:36-60);
 //   * generate_softlabel (offline.py:57-76): per-token top-k scatter + background-token mask of the teacher's token logits;
 //   * SoftTargetCrossEntropy (offline.py:34-45) forward + gradient in one pass;
-//   * the AdamW update the phase trains with (offline.py:233).
+//   * F.normalize on rows and its backward (the nn-classifier head).
+// The AdamW update the phase trains with (offline.py:233) is in optim.hip; the token map reaches fp32 through feat_out.hip.
 // Sizes are tiny next to the encoder (B*25 x 512 x 65 per step): these kernels are written for exactness and determinism
 // (fixed reduction orders, no atomics), not for the MFMA roofline - one wave per dot product / row.
 #include "fsvit_common.h"
 #include "kernels.h"
 
-namespace FSVIT_NS {
+namespace fsvit {
 
 // y[m][n] = x[m][:] . w[n][:] + b[n];  one workgroup per row m, wave w takes n = w, w + 4, ...; K % 4 == 0
 __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
@@ -219,65 +220,6 @@ int launch_row_normalize_bwd(const float* y, const float* inv, const float* dy, 
   return (int)hipGetLastError();
 }
 
-// torch.optim.AdamW / timm AdamW (decoupled weight decay), update number `step` (1-based)
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                             float beta1, float beta2, float eps, float wd, float bc1, float rsqrt_bc2) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gi = g[i];
-  float pi = p[i] * (1.0f - lr * wd);
-  const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-  const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-  m[i] = mi;
-  v[i] = vi;
-  const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-  p[i] = pi - (lr / bc1) * (mi / denom);
-}
-
-// the same update for a table of tensors in ONE launch (blockIdx.y = tensor; rows of 5 x 8 bytes: p, g, m, v, n): the distillation phase steps 89
-// parameter tensors, i.e. 89 launches of ~4 us and as many host calls per step (profiles/r05_distill_kernel_stats.csv)
-struct AdamwItem { float* p; const float* g; float* m; float* v; size_t n; };
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwItem* __restrict__ items, float lr, float beta1, float beta2, float eps, float wd, float bc1,
-                                                          float rsqrt_bc2) {
-  const AdamwItem it = items[blockIdx.y];
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < it.n; i += (size_t)gridDim.x * 256) {
-    const float gi = it.g[i];
-    const float pi = it.p[i] * (1.0f - lr * wd);
-    const float mi = beta1 * it.m[i] + (1.0f - beta1) * gi;
-    const float vi = beta2 * it.v[i] + (1.0f - beta2) * gi * gi;
-    it.m[i] = mi;
-    it.v[i] = vi;
-    const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-    it.p[i] = pi - (lr / bc1) * (mi / denom);
-  }
-}
-
-// token map plumbing: storage dtype <-> fp32
-template <typename T>
-__global__ void tokens_to_f32_kernel(const T* __restrict__ in, const float* __restrict__ scale, const float* __restrict__ shift, float* __restrict__ out, size_t n, int C) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int c = (int)(i % C);
-  const float v = to_f32<T>(in[i]);
-  out[i] = scale ? v * scale[c] + shift[c] : v;
-}
-template <typename T>
-__global__ void add_f32_into_kernel(T* __restrict__ inout, const float* __restrict__ add, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) inout[i] = from_f32<T>(to_f32<T>(inout[i]) + add[i]);
-}
-// out[i] = in[i] (* scale[c] + shift[c] when scale != NULL): the post-norm token map in fp32
-int launch_tokens_to_f32(const void* in, const float* scale, const float* shift, float* out, size_t n, int C, int dtype, hipStream_t s) {
-  if (n == 0) return 0;
-  const unsigned g = (unsigned)((n + 255) / 256);
-  return with_elem(dtype, [&](auto e) { return launch(tokens_to_f32_kernel<elem_t<decltype(e)>>, g, 256, 0, s, in, scale, shift, out, n, C); });
-}
-int launch_add_f32_into(void* inout, const float* add, size_t n, int dtype, hipStream_t s) {
-  if (n == 0) return 0;
-  const unsigned g = (unsigned)((n + 255) / 256);
-  return with_elem(dtype, [&](auto e) { return launch(add_f32_into_kernel<elem_t<decltype(e)>>, g, 256, 0, s, inout, add, n); });
-}
-
 int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s) {
   if (M <= 0) return 0;
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(M), dim3(256), 0, s, x, w, b, y, M, N, K);
@@ -316,22 +258,5 @@ int launch_soft_target_ce(const float* z, const float* tgt, float* rowloss, floa
   hipLaunchKernelGGL(soft_target_ce_kernel, dim3((R + 3) / 4), dim3(256), 0, s, z, tgt, rowloss, dz, R, C, gscale);
   return (int)hipGetLastError();
 }
-int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s) {
-  if (n == 0) return 0;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, lr, beta1, beta2, eps, wd, (float)bc1,
-                     (float)(1.0 / sqrt(bc2)));
-  return (int)hipGetLastError();
-}
 
-int launch_adamw_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s) {
-  if (n_items <= 0 || max_numel == 0) return 0;
-  const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-  size_t gx = (max_numel + 1023) / 1024;
-  if (gx > 256) gx = 256;
-  hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)gx, (unsigned)n_items), dim3(256), 0, s, (const AdamwItem*)items_dev, lr, beta1, beta2, eps, wd, (float)bc1,
-                     (float)(1.0 / sqrt(bc2)));
-  return (int)hipGetLastError();
-}
-
-}  // namespace FSVIT_NS
+}  // namespace fsvit

@@ -1643,6 +1643,20 @@ extern "C" int fsvit_sgd_nesterov_step(float* param, const float* grad, float* m
   return rc ? fsvit_set_error(rc, "sgd_nesterov") : 0;
 }
 
+extern "C" int fsvit_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int step, void* stream) {
+  if (!p || !g || !m || !v || step < 1) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_adamw_step: bad argument");
+  T_TRY(launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_adamw_step_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float weight_decay,
+                                      int step, void* stream) {
+  if (!items_dev || n_items < 0 || step < 1) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_adamw_step_multi: bad argument");      // (a null table is refused at n_items = 0 too)
+  T_TRY(launch_adamw_multi(items_dev, n_items, max_numel, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int fsvit_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int32_t* flags_dev, void* stream) {
   if (n_items < 0) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_grad_nan_guard_multi: n_items = %d", n_items);
   if (n_items > 0 && (!items_dev || !flags_dev)) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_grad_nan_guard_multi: null argument");

@@ -1,4 +1,5 @@
-// Launchers of the training-path kernels (train_kernels.hip, attention_bwd.hip, head_bwd in head.hip).
+// Launchers of the training-path kernels (train_kernels.hip, attention_bwd.hip, head_bwd in head.hip) and of the parameter updates (optim.hip).
+// fp32 / bf16 trainers only: one build, namespace fsvit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -75,10 +76,15 @@ int launch_fill_f32(float* p, float v, size_t n, hipStream_t s);
 int launch_scale_copy(const float* in, float* out, size_t n, float sc, hipStream_t s);
 // out[c] = sum_m a[m][c]; partial: bn_reduce_blocks(M) * 2 * C floats of scratch
 int launch_colsum(const void* a, float* partial, float* out, int M, int C, int dtype, hipStream_t s);
+// parameter updates (optim.hip), fp32.  _multi: one launch over a device table of n_items rows {p, g, buf, n} / {p, g, m, v, n} / {g, n} (8-byte
+// fields), max_numel = the longest tensor.  first: the momentum buffer is written, not read.  step: AdamW's 1-based update number.
+// grad_nan_guard: flags_dev[i] = 1 and tensor i zeroed where it holds a NaN.
 int launch_sgd_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s);
 int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s);
 int launch_sgd_nesterov_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s);
 int launch_sgd_nesterov(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s);
+int launch_adamw_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s);
+int launch_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s);
 int launch_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int* flags_dev, hipStream_t s);
 // attention backward (attention_bwd.hip): qkv [B*S][3*heads*hdp], dctx [B*S][heads*hdp] -> dqkv [B*S][3*heads*hdp]
 int launch_attention_bwd(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, int dtype, hipStream_t s);

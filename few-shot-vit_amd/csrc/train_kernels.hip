@@ -11,10 +11,6 @@
 
 namespace fsvit {
 
-static inline unsigned gs_grid(size_t total, int per_block = 256) {
-  size_t nb = (total + per_block - 1) / per_block;
-  return (unsigned)(nb > 32768 ? 32768 : (nb < 1 ? 1 : nb));
-}
 // a two-limb weight word of the `bf16x2` GEMMs (conv_gemm_v2.hip x2_split / engine.py ops.x2_limbs): upper half hi = the value rounded to bf16,
 // lower half lo = (value - hi) rounded to bf16.  As an output type of the pack / transpose kernels below (training in the two-limb mode packs
 // its weights - and the activation operand of the split-K weight-gradient GEMM - on the device every step).
@@ -28,8 +24,6 @@ template <> __device__ __forceinline__ void store4<limbw>(limbw* p, f32x4 v) {
   const u32x4 o = {from_f32<limbw>(v[0]).w, from_f32<limbw>(v[1]).w, from_f32<limbw>(v[2]).w, from_f32<limbw>(v[3]).w};
   *reinterpret_cast<u32x4*>(p) = o;
 }
-
-#define GS_LOOP(idx, total) for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < (total); idx += (size_t)gridDim.x * blockDim.x)
 
 // ------------------------------------------------------------------------------------------------ weights
 // PyTorch conv weight W[O][Ig][KH][KW] (O = groups * Ng) -> packed [groups][Npad][Kw] (see conv_gemm.h).
@@ -1041,68 +1035,6 @@ __global__ __launch_bounds__(256) void colsum_finalize_kernel(const float* __res
   out[c] = (float)s0;
 }
 
-// SGD with momentum and weight decay, torch.optim.SGD semantics (utils/__init__.py:131-132): d = g + wd*p; buf = mom*buf + d (buf = d on the
-// first step); p -= lr * buf
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t n, float lr,
-                                                  float momentum, float wd, int first) {
-  GS_LOOP(idx, n) {
-    const float d = g[idx] + wd * p[idx];
-    const float b = first ? d : momentum * buf[idx] + d;
-    buf[idx] = b;
-    p[idx] -= lr * b;
-  }
-}
-
-// the same update for a table of tensors in ONE launch (blockIdx.y = tensor): 86 parameter tensors per meta-tuning step
-struct SgdItem { float* p; const float* g; float* buf; size_t n; };
-__global__ __launch_bounds__(256) void sgd_multi_kernel(const SgdItem* __restrict__ items, float lr, float momentum, float wd, int first) {
-  const SgdItem it = items[blockIdx.y];
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < it.n; idx += (size_t)gridDim.x * 256) {
-    const float d = it.g[idx] + wd * it.p[idx];
-    const float b = first ? d : momentum * it.buf[idx] + d;
-    it.buf[idx] = b;
-    it.p[idx] -= lr * b;
-  }
-}
-
-// torch.optim.SGD(nesterov=True, dampening=0) (meta_tuning_sun_d/train_meta.py:115): d = g + wd*p; buf = mom*buf + d (buf = d on the first step);
-// p -= lr * (d + mom*buf).  Kernels of their own: sgd_kernel / sgd_multi_kernel above stay as they are.
-__device__ __forceinline__ void sgd_nesterov_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t idx, float lr,
-                                                    float momentum, float wd, int first) {
-  const float d = g[idx] + wd * p[idx];
-  const float b = first ? d : momentum * buf[idx] + d;
-  buf[idx] = b;
-  p[idx] -= lr * (d + momentum * b);
-}
-__global__ __launch_bounds__(256) void sgd_nesterov_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t n, float lr,
-                                                           float momentum, float wd, int first) {
-  GS_LOOP(idx, n) sgd_nesterov_update(p, g, buf, idx, lr, momentum, wd, first);
-}
-__global__ __launch_bounds__(256) void sgd_nesterov_multi_kernel(const SgdItem* __restrict__ items, float lr, float momentum, float wd, int first) {
-  const SgdItem it = items[blockIdx.y];
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < it.n; idx += (size_t)gridDim.x * 256)
-    sgd_nesterov_update(it.p, it.g, it.buf, idx, lr, momentum, wd, first);
-}
-
-// detect_grad_nan (meta_tuning_sun_d/Models/utils.py:115-118) for a table of gradient tensors (blockIdx.y = tensor): a tensor holding any NaN (g != g;
-// Inf does not count) is zeroed entirely.  Pass 1 flags, pass 2 zeroes the flagged tensors; the flags stay on the device.  Every wave that saw a NaN
-// stores the same 1 with a plain vector store: no atomics.
-struct GradItem { float* g; size_t n; };
-__global__ __launch_bounds__(256) void grad_nan_flag_kernel(const GradItem* __restrict__ items, int* __restrict__ flags) {
-  const GradItem it = items[blockIdx.y];
-  bool nan = false;
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < it.n; idx += (size_t)gridDim.x * 256) {
-    const float v = it.g[idx];
-    nan |= v != v;
-  }
-  if (__ballot(nan) != 0 && (threadIdx.x & 63) == 0) flags[blockIdx.y] = 1;
-}
-__global__ __launch_bounds__(256) void grad_nan_zero_kernel(const GradItem* __restrict__ items, const int* __restrict__ flags) {
-  if (flags[blockIdx.y] == 0) return;
-  const GradItem it = items[blockIdx.y];
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < it.n; idx += (size_t)gridDim.x * 256) it.g[idx] = 0.f;
-}
-
 // ------------------------------------------------------------------------------------------------ ViT / DeiT training (deit.py:61-78, 139-218)
 // nn.LayerNorm in train mode: y = (x - mean) * rstd * gamma + beta (biased variance, deit.py:68,73,170), row statistics kept for the backward.
 // One wave per row (D <= 2048), 4 rows per workgroup.
@@ -1691,38 +1623,6 @@ int launch_colsum(const void* a, float* partial, float* out, int M, int C, int d
   int rc = launch_bn_reduce(a, nullptr, nullptr, nullptr, partial, M, C, 0, dtype, s);
   if (rc) return rc;
   return launch(colsum_finalize_kernel, (C + 3) / 4, 256, 0, s, partial, bn_reduce_blocks(M), C, out);
-}
-int launch_sgd_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s) {
-  if (n_items <= 0 || max_numel == 0) return 0;
-  size_t gx = (max_numel + 1023) / 1024;                 // 4 elements per thread at the largest tensor; smaller ones leave blocks idle
-  if (gx > 256) gx = 256;
-  return launch(sgd_multi_kernel, dim3((unsigned)gx, (unsigned)n_items), 256, 0, s, items_dev, lr, momentum, wd, first);
-}
-int launch_sgd(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s) {
-  if (n == 0) return 0;
-  return launch(sgd_kernel, gs_grid(n), 256, 0, s, p, g, buf, n, lr, momentum, wd, first);
-}
-
-static unsigned multi_grid_x(size_t max_numel) {          // as launch_sgd_multi: 4 elements per thread at the largest tensor, 256 blocks at most
-  const size_t gx = (max_numel + 1023) / 1024;
-  return (unsigned)(gx > 256 ? 256 : gx);
-}
-int launch_sgd_nesterov_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float momentum, float wd, int first, hipStream_t s) {
-  if (n_items <= 0 || max_numel == 0) return 0;
-  return launch(sgd_nesterov_multi_kernel, dim3(multi_grid_x(max_numel), (unsigned)n_items), 256, 0, s, items_dev, lr, momentum, wd, first);
-}
-int launch_sgd_nesterov(float* p, const float* g, float* buf, size_t n, float lr, float momentum, float wd, int first, hipStream_t s) {
-  if (n == 0) return 0;
-  return launch(sgd_nesterov_kernel, gs_grid(n), 256, 0, s, p, g, buf, n, lr, momentum, wd, first);
-}
-int launch_grad_nan_guard_multi(const void* items_dev, int n_items, size_t max_numel, int* flags_dev, hipStream_t s) {
-  if (n_items <= 0) return 0;
-  int rc = (int)hipMemsetAsync(flags_dev, 0, (size_t)n_items * sizeof(int), s);
-  if (rc || max_numel == 0) return rc;
-  const dim3 grid(multi_grid_x(max_numel), (unsigned)n_items);
-  rc = launch(grad_nan_flag_kernel, grid, 256, 0, s, items_dev, flags_dev);
-  if (rc) return rc;
-  return launch(grad_nan_zero_kernel, grid, 256, 0, s, items_dev, (const int*)flags_dev);
 }
 
 int launch_ln_train_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int D, float eps, int dtype, hipStream_t s) {

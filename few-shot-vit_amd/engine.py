@@ -483,7 +483,6 @@ class LvvitEngine(_EncoderEngine):
 class ops:
     """Operator-level entry points (storage dtype follows the input tensors: fp32, bf16 or fp16; the fused row operators take the two 16-bit types
     only, activations and weights of the same one)."""
-    _sgd_tables = {}
 
     @staticmethod
     def _dt(t):
@@ -676,12 +675,9 @@ class ops:
             _lib.check(_lib.load().fsvit_adamw_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
                                                     float(weight_decay), int(step), _stream_ptr(p.device)))
 
-    _adamw_tables = {}
-
     @staticmethod
     def adamw_step_multi(params, grads, ms, vs, lr, beta1, beta2, eps, weight_decay, step):
-        """One launch for a list of fp32 tensors at the same update number (fsvit_adamw_step_multi); the pointer table is cached per device and re-uploaded
-        only when a pointer changed (as ops.sgd_step_multi)."""
+        """One launch for a list of fp32 tensors at the same update number (fsvit_adamw_step_multi).  -> the device table (ops._ptr_table)."""
         if not params:
             return
         _require_cuda(*params)
@@ -689,16 +685,11 @@ class ops:
         bump_weight_generation(params)
         dev = params[0].device
         rows = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, g, m, v in zip(params, grads, ms, vs))
-        key = (dev, len(rows))
-        cached = ops._adamw_tables.get(key)
-        if cached is None or cached[0] != rows:
-            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
-            with torch.cuda.device(dev):
-                cached = (rows, table.to(dev, non_blocking=True), table)
-            ops._adamw_tables[key] = cached
+        table = ops._ptr_table('adamw', dev, rows)
         with torch.cuda.device(dev):
-            _lib.check(lib.fsvit_adamw_step_multi(_ptr(cached[1]), len(rows), max(r[4] for r in rows), float(lr), float(beta1), float(beta2), float(eps),
+            _lib.check(lib.fsvit_adamw_step_multi(_ptr(table), len(rows), max(r[4] for r in rows), float(lr), float(beta1), float(beta2), float(eps),
                                                   float(weight_decay), int(step), _stream_ptr(dev)))
+        return table
 
     @staticmethod
     def proj_mlp_rows(x, ctx, wp, w1, b1, w2, b2=None, out=None):
@@ -930,9 +921,25 @@ class ops:
             _lib.check(lib.fsvit_conv3x3_wgrad(_ptr(x_nhwc), _ptr(dz), _ptr(dw), B, H, W, O, Ig, groups, dt, _stream_ptr(x_nhwc.device)))
         return dw
 
+    _ptr_tables = {}
+
     @staticmethod
-    def sgd_step_multi(params, grads, bufs, lr, momentum, weight_decay, first_step):
-        """One launch for a list of fp32 tensors (fsvit_sgd_step_multi): the pointer table is built on the host and copied with the stream."""
+    def _ptr_table(kind, dev, rows):
+        """The int64 device table of a multi-tensor launch (rows of pointers and a length, the item layouts of csrc/optim.hip), cached per
+        (kind, device, number of rows).  Pinned allocation + upload only when a pointer changed: with parallel.GradBucket or
+        zero_grad(set_to_none=False) the gradients keep their addresses and a step uploads nothing (hipHostMalloc per step stalled the host
+        behind the whole backward).  The same tensor object is returned while `rows` is unchanged; the pinned host copy lives with the entry."""
+        key = (kind, dev, len(rows))
+        cached = ops._ptr_tables.get(key)
+        if cached is None or cached[0] != rows:
+            host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+            with torch.cuda.device(dev):
+                cached = (rows, host.to(dev, non_blocking=True), host)
+            ops._ptr_tables[key] = cached
+        return cached[1]
+
+    @staticmethod
+    def _sgd_multi(entry, params, grads, bufs, lr, momentum, weight_decay, first_step):
         if not params:
             return
         _require_cuda(*params)
@@ -940,68 +947,44 @@ class ops:
         bump_weight_generation(params)
         dev = params[0].device
         rows = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), p.numel()) for p, g, b in zip(params, grads, bufs))
-        cached = ops._sgd_tables.get(dev)
-        if cached is None or cached[0] != rows:
-            # (pinned allocation + upload only when a pointer changed: with parallel.GradBucket or zero_grad(set_to_none=False) the gradients keep
-            # their addresses and a step uploads nothing; hipHostMalloc per step stalled the host behind the whole backward)
-            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
-            with torch.cuda.device(dev):
-                cached = (rows, table.to(dev, non_blocking=True), table)
-            ops._sgd_tables[dev] = cached
+        table = ops._ptr_table(entry, dev, rows)
         with torch.cuda.device(dev):
-            _lib.check(lib.fsvit_sgd_step_multi(_ptr(cached[1]), len(params), max(r[3] for r in rows), float(lr), float(momentum),
-                                                float(weight_decay), int(bool(first_step)), _stream_ptr(dev)))
-        return cached[1]
+            _lib.check(getattr(lib, entry)(_ptr(table), len(params), max(r[3] for r in rows), float(lr), float(momentum), float(weight_decay),
+                                           int(bool(first_step)), _stream_ptr(dev)))
+        return table
+
+    @staticmethod
+    def _sgd_single(entry, param, grad, buf, lr, momentum, weight_decay, first_step):
+        _require_cuda(param, grad, buf)
+        lib = _lib.load()
+        bump_weight_generation((param,))
+        with torch.cuda.device(param.device):
+            _lib.check(getattr(lib, entry)(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum), float(weight_decay),
+                                           int(bool(first_step)), _stream_ptr(param.device)))
+
+    @staticmethod
+    def sgd_step_multi(params, grads, bufs, lr, momentum, weight_decay, first_step):
+        """torch.optim.SGD with momentum for a list of fp32 tensors in one launch (fsvit_sgd_step_multi).  -> the device table (ops._ptr_table)."""
+        return ops._sgd_multi('fsvit_sgd_step_multi', params, grads, bufs, lr, momentum, weight_decay, first_step)
 
     @staticmethod
     def sgd_step(param, grad, buf, lr, momentum, weight_decay, first_step):
-        _require_cuda(param, grad, buf)
-        lib = _lib.load()
-        bump_weight_generation((param,))
-        with torch.cuda.device(param.device):
-            _lib.check(lib.fsvit_sgd_step(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum),
-                                          float(weight_decay), int(bool(first_step)), _stream_ptr(param.device)))
-
-    _sgd_nesterov_tables = {}
+        ops._sgd_single('fsvit_sgd_step', param, grad, buf, lr, momentum, weight_decay, first_step)
 
     @staticmethod
     def sgd_nesterov_step_multi(params, grads, bufs, lr, momentum, weight_decay, first_step):
-        """torch.optim.SGD(nesterov=True) for a list of fp32 tensors in one launch (fsvit_sgd_nesterov_step_multi); the pointer table is cached and
-        re-uploaded only when a pointer changed (as ops.sgd_step_multi).  -> the device table."""
-        if not params:
-            return
-        _require_cuda(*params)
-        lib = _lib.load()
-        bump_weight_generation(params)
-        dev = params[0].device
-        rows = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), p.numel()) for p, g, b in zip(params, grads, bufs))
-        cached = ops._sgd_nesterov_tables.get(dev)
-        if cached is None or cached[0] != rows:
-            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
-            with torch.cuda.device(dev):
-                cached = (rows, table.to(dev, non_blocking=True), table)
-            ops._sgd_nesterov_tables[dev] = cached
-        with torch.cuda.device(dev):
-            _lib.check(lib.fsvit_sgd_nesterov_step_multi(_ptr(cached[1]), len(params), max(r[3] for r in rows), float(lr), float(momentum),
-                                                         float(weight_decay), int(bool(first_step)), _stream_ptr(dev)))
-        return cached[1]
+        """torch.optim.SGD(nesterov=True) for a list of fp32 tensors in one launch (fsvit_sgd_nesterov_step_multi).  -> the device table."""
+        return ops._sgd_multi('fsvit_sgd_nesterov_step_multi', params, grads, bufs, lr, momentum, weight_decay, first_step)
 
     @staticmethod
     def sgd_nesterov_step(param, grad, buf, lr, momentum, weight_decay, first_step):
-        _require_cuda(param, grad, buf)
-        lib = _lib.load()
-        bump_weight_generation((param,))
-        with torch.cuda.device(param.device):
-            _lib.check(lib.fsvit_sgd_nesterov_step(_ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum),
-                                                   float(weight_decay), int(bool(first_step)), _stream_ptr(param.device)))
-
-    _guard_tables = {}
+        ops._sgd_single('fsvit_sgd_nesterov_step', param, grad, buf, lr, momentum, weight_decay, first_step)
 
     @staticmethod
     def grad_nan_guard(grads, device=None):
         """detect_grad_nan of the reference for a list of contiguous fp32 gradient tensors (fsvit_grad_nan_guard_multi): a tensor holding any NaN is
         zeroed entirely (Inf does not count) -> int32 device tensor [len(grads)] of 0 / 1 flags.  No host synchronisation; the {pointer, numel}
-        table is cached and re-uploaded only when a pointer changed."""
+        table is cached (ops._ptr_table)."""
         if not grads:
             return torch.zeros(0, dtype=torch.int32, device=device if device is not None else 'cuda')
         _require_cuda(*grads)
@@ -1011,15 +994,10 @@ class ops:
         lib = _lib.load()
         dev = grads[0].device
         rows = tuple((g.data_ptr(), g.numel()) for g in grads)
-        cached = ops._guard_tables.get(dev)
-        if cached is None or cached[0] != rows:
-            table = torch.tensor(rows, dtype=torch.int64).pin_memory()
-            with torch.cuda.device(dev):
-                cached = (rows, table.to(dev, non_blocking=True), table)
-            ops._guard_tables[dev] = cached
+        table = ops._ptr_table('guard', dev, rows)
         flags = torch.empty(len(grads), dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(lib.fsvit_grad_nan_guard_multi(_ptr(cached[1]), len(grads), max(r[1] for r in rows), _ptr(flags), _stream_ptr(dev)))
+            _lib.check(lib.fsvit_grad_nan_guard_multi(_ptr(table), len(grads), max(r[1] for r in rows), _ptr(flags), _stream_ptr(dev)))
         return flags
 
     _tickets = {}

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """SUN-D meta-tuning driver: the loop of the reference's meta_tuning_sun_d/train_meta.py:95-277 on the HIP DeepEMD head (models/deepemd.py,
-csrc/emd_head.hip), the HIP encoder trainer, the Nesterov SGD kernel and the on-device NaN-gradient guard (csrc/train_kernels.hip).
+csrc/emd_head.hip), the HIP encoder trainer, the Nesterov SGD kernel and the on-device NaN-gradient guard (csrc/optim.hip).
 
   python -m fewshot_vit_amd.train_deepemd -dataset mini-imagenet -dataset_args '{root_path: ./materials/mini-imagenet}' -deepemd grid \\
       -pretrain_dir sun_m/max-va.pth -way 5 -shot 1 -query 15 -norm_stats sund

@@ -1,6 +1,6 @@
-"""float64 references of the episode head (head.hip), the distillation losses / linear head / row normalisation (token_label.hip) and the SGD / AdamW
-updates (train_kernels.hip, token_label.hip), written from the formulas in the kernels' header comments, and the first-order fp32 allowances the tests
-gate the kernels with (tests/head_cases.py; the derivations are written out in the header of tests/test_gpu_head_ops.py).
+"""float64 references of pool_affine (feat_out.hip), the episode head (head.hip), the distillation losses / linear head / row normalisation
+(token_label.hip) and the SGD / AdamW updates (optim.hip), written from the formulas in the kernels' header comments, and the first-order fp32
+allowances the tests gate the kernels with (tests/head_cases.py; the derivations are written out in the header of tests/test_gpu_head_ops.py).
 
 Every function takes float64 tensors holding fp32-representable values and returns float64.  The allowance functions return, per output element, a bound
 `a` on |fp32 kernel - float64 result| that is built from float64 quantities only:

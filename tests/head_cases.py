@@ -1,6 +1,6 @@
-"""Cases, input builders, references and gates of the episode head (head.hip), the distillation head (token_label.hip: linear, soft labels, soft-target CE,
-row normalisation, AdamW) and the SGD pair (train_kernels.hip), shared by test_head_ops_ref_cpu.py (the references alone, no GPU) and
-test_gpu_head_ops.py (the kernels).  All inputs come from seeded generators and are rounded to fp32 (pool_affine: to its storage type) before the
+"""Cases, input builders, references and gates of pool_affine (feat_out.hip), the episode head (head.hip), the distillation head (token_label.hip: linear,
+soft labels, soft-target CE, row normalisation) and the SGD / AdamW updates (optim.hip), shared by test_head_ops_ref_cpu.py (the references alone,
+no GPU) and test_gpu_head_ops.py (the kernels).  All inputs come from seeded generators and are rounded to fp32 (pool_affine: to its storage type) before the
 float64 reference of oracle/head_ops_oracle.py sees them.
 
 Gate (fp32 storage, the form of tests/attention_cases.py): |got - A| <= a + u |A|, u = 2^-24, A the float64 result from the fp32 inputs, a the first-order

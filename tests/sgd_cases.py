@@ -1,5 +1,5 @@
 """float64 restatement of torch.optim.SGD(nesterov=True, dampening=0) and its first-order fp32 allowance, shared by test_sgd_nesterov_ref_cpu.py
-(torch's own fp32 optimizer against it, no GPU) and test_gpu_sgd_nesterov.py (the kernels of train_kernels.hip).  In the style of
+(torch's own fp32 optimizer against it, no GPU) and test_gpu_sgd_nesterov.py (the kernels of optim.hip).  In the style of
 oracle.head_ops_oracle.sgd; gate as tests/head_cases.py: |got - A| <= a + u |A|.
 
   d = g + wd p                         a_d   = u |wd p| + u |d|

@@ -1,6 +1,6 @@
-"""The kernels that produce the numbers users read - few-shot accuracy, the losses, the parameter updates: head.hip (pool_affine, proto_head and its fused
-cross entropy, both head backwards), token_label.hip (linear forward / backward, token soft labels, soft-target CE, row_normalize, AdamW) and the SGD
-pair of train_kernels.hip - against the float64 references of oracle/head_ops_oracle.py, through the ops.* entry points, over the tables of
+"""The kernels that produce the numbers users read - few-shot accuracy, the losses, the parameter updates: feat_out.hip (pool_affine), head.hip (proto_head
+and its fused cross entropy, both head backwards), token_label.hip (linear forward / backward, token soft labels, soft-target CE, row_normalize) and the
+SGD and AdamW updates of optim.hip - against the float64 references of oracle/head_ops_oracle.py, through the ops.* entry points, over the tables of
 tests/head_cases.py (the edges each case reaches are written next to it there).
 
 Every case asserts, in this order: the output is finite; three launches are bit-identical; PAD canary elements behind every output buffer are untouched
@@ -56,6 +56,7 @@ import pytest
 import torch
 
 import head_cases as hc
+import sgd_cases
 from oracle import head_ops_oracle as ho
 
 pytestmark = pytest.mark.gpu
@@ -617,8 +618,8 @@ def test_multi_tensor_step_and_table_cache(kind):
 
     def multi(ts, gs, step):
         if kind == 'adamw':
-            ops.adamw_step_multi([t['p'][0] for t in ts], gs, [t['m'][0] for t in ts], [t['v'][0] for t in ts], h['lr'], h['beta1'], h['beta2'], h['eps'], h['wd'], step)
-            return ops._adamw_tables[(ts[0]['p'][0].device, len(ts))][1]
+            return ops.adamw_step_multi([t['p'][0] for t in ts], gs, [t['m'][0] for t in ts], [t['v'][0] for t in ts], h['lr'], h['beta1'], h['beta2'], h['eps'],
+                                        h['wd'], step)
         return ops.sgd_step_multi([t['p'][0] for t in ts], gs, [t['buf'][0] for t in ts], 0.05, 0.9, 5e-4, step == 1)
 
     def agree(a, b):
@@ -658,3 +659,41 @@ def test_multi_tensor_step_and_table_cache(kind):
     # and the result of the three steps against float64 for the longest tensor's last step is what test_sgd_step / test_adamw_step gate: here the
     # multi kernel inherits those gates through bit equality
     print(f'{kind}_step_multi lengths {hc.MULTI_LENGTHS}: equal to the single-tensor kernel over 3 steps, table cached / re-uploaded')
+
+
+GS_CAP = 32768 * 256                   # gs_grid: one thread per element up to here, the grid-stride loop of a single-tensor kernel strides beyond
+
+
+@pytest.mark.parametrize('kind', ('sgd', 'nesterov', 'adamw'))
+def test_single_tensor_step_past_the_grid_cap(kind):
+    """n = 32768 * 256 + 5, the smallest length at which a single-tensor launch strides: the single kernel equals the multi kernel (a one-row table,
+    256 blocks striding 32 769 times) bit for bit on every output, nothing is written behind the buffers, and the last 261 elements - the last block
+    and the 5 elements only the second stride reaches - are inside the float64 gates of test_sgd_step / test_adamw_step / test_gpu_sgd_nesterov.py.
+    Inputs are drawn on the device (AdamW: the state after one update, update number 2)."""
+    ops = _ops()
+    h = hc.ADAMW_HYPER
+    n, last = GS_CAP + 5, 261
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(8388613)
+    draw = lambda scale: scale * torch.randn(n, generator=gen, device=DEV)
+    src = dict(p=draw(1.0), g=draw(0.1))
+    if kind == 'adamw':
+        g0 = draw(0.1)
+        src.update(m=(1.0 - h['beta1']) * g0, v=(1.0 - h['beta2']) * g0 * g0)
+        keys, a = ('p', 'm', 'v'), (h['lr'], h['beta1'], h['beta2'], h['eps'], h['wd'], 2)
+        single, multi = ops.adamw_step, ops.adamw_step_multi
+    else:
+        src.update(buf=draw(0.1))
+        keys, a = ('p', 'buf'), (0.05, 0.9, 5e-4, False)
+        single, multi = (ops.sgd_step, ops.sgd_step_multi) if kind == 'sgd' else (ops.sgd_nesterov_step, ops.sgd_nesterov_step_multi)
+    one, many = {k: _tail(src[k]) for k in keys}, {k: _tail(src[k]) for k in keys}
+    single(one['p'][0], src['g'], *[one[k][0] for k in keys[1:]], *a)
+    multi([many['p'][0]], [src['g']], *[[many[k][0]] for k in keys[1:]], *a)
+    _tails_ok(*[t[k][1] for t in (one, many) for k in keys])
+    for k in keys:
+        assert torch.equal(one[k][0], many[k][0]), k
+    _finite(*[one[k][0] for k in keys])
+    x = {k: v[n - last:].cpu().double() for k, v in src.items()}
+    ref = {'sgd': ho.sgd, 'nesterov': sgd_cases.sgd_nesterov, 'adamw': ho.adamw}[kind]
+    r = ref(x['p'], x['g'], *[x[k] for k in keys[1:]], *a)
+    _report(f'{kind}_step n={n}, last {last}', {k: hc.ratio(one[k][0][n - last:].cpu(), r[k], r['a_' + k]) for k in keys})

@@ -1,4 +1,4 @@
-"""The Nesterov SGD kernels of train_kernels.hip (fsvit_sgd_nesterov_step, fsvit_sgd_nesterov_step_multi) and FsvitSGD(nesterov=True) against the
+"""The Nesterov SGD kernels of optim.hip (fsvit_sgd_nesterov_step, fsvit_sgd_nesterov_step_multi) and FsvitSGD(nesterov=True) against the
 float64 restatement and allowance of tests/sgd_cases.py (proven on the CPU against torch.optim.SGD by test_sgd_nesterov_ref_cpu.py).  Each case asserts:
 canary elements behind every parameter / state buffer are untouched; three launches are bit-identical; |got - A| <= a + u |A| for p and buf."""
 import pytest

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Launch-by-launch timeline of the LAST step in a rocprofv3 kernel trace (rocpd SQLite): start offset, duration, gap to the previous kernel.
-A step ends with the kernel whose name contains <end_marker> (default: sgd_multi_kernel = the optimizer launch of bench.py --mode train).
+A step ends with the kernel whose name contains <end_marker> (default: optim_multi_kernel<fsvit::SgdUpdate<false> = the optimizer launch of bench.py --mode train).
     python tools/rocpd_timeline.py gpurun_out/prof/x_results.db [end_marker] > profiles/rNN_train_timeline.txt"""
 import sqlite3
 import sys
@@ -10,7 +10,7 @@ from rocpd_stats import short
 
 def main():
     db = sqlite3.connect(sys.argv[1])
-    marker = sys.argv[2] if len(sys.argv) > 2 else 'sgd_multi_kernel'
+    marker = sys.argv[2] if len(sys.argv) > 2 else 'optim_multi_kernel<fsvit::SgdUpdate<false>'
     cols = [r[1] for r in db.execute('pragma table_info(kernels)')]
     name_col = 'name' if 'name' in cols else 'kernel_name'
     rows = db.execute(f'select {name_col}, start, end from kernels order by start').fetchall()
