@@ -16,7 +16,17 @@
 //     leaves the image - no im2col, no padded copy;
 //   * split over row chunks across workgroups: fp32 partials [split][job][tap][32][32], summed in fixed order by wgrad3x3_finalize_kernel
 //     into the PyTorch weight layout (deterministic, like the round-1 path).
+// Two forms of every kernel here, one body each (wg3::Form<X2>):
+//   * 16-bit rows (the `bf16` / `f16` build): a 16-byte load is 8 values = one 16-byte LDS unit, a K step of 32 rows is one MFMA per tile;
+//   * two-limb arithmetic on fp32 rows (`bf16x2` / `f16x2`, X2): the limb split happens on the way into LDS.  Row m of a chunk becomes TWO
+//     16-bit rows, 2 m = lo(m, :) and 2 m + 1 = hi(m, :) (x2_split: hi = the leading bits, lo = the rounded remainder), so the transposing
+//     read hands every lane 32-bit words (lo, hi) of ONE value - the k-slot order of conv_gemm_v2's two-limb arithmetic.  The subtile pitch
+//     doubles, a tap shifts by 2 rows per pixel, and a K step of 32 limb rows = 16 rows is two MFMAs per tile: (a, b with its halves
+//     swapped) sums the cross terms, (a, b) lo lo + hi hi.  No transposed / limb-packed copies of dz and x in HBM (round 3 route:
+//     transpose_cols + im2col_t + a limb GEMM, 12 ms of the 57 ms step in transposes alone).
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "conv_gemm.h"
 #include "fsvit_common.h"
@@ -29,42 +39,140 @@ constexpr int NW = 8;            // waves = (n-block, c-block) jobs per workgrou
 constexpr int CH = 64;           // rows per stage = 2 MFMA K steps
 constexpr int JOB = 9 * 32 * 32; // fp32 partials per job
 typedef short s4 __attribute__((ext_vector_type(4)));
+
+// 8 fp32 values -> their 8 lo limbs and 8 hi limbs, packed in column order
+__device__ __forceinline__ void limbs8(const u32x4 a, const u32x4 b, u32x4& lo, u32x4& hi) {
+  u32x4 sa, sb, r_;
+  x2_split(a, sa, r_);
+  x2_split(b, sb, r_);
+  lo = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x05040100u), __builtin_amdgcn_perm(sa[3], sa[2], 0x05040100u),
+             __builtin_amdgcn_perm(sb[1], sb[0], 0x05040100u), __builtin_amdgcn_perm(sb[3], sb[2], 0x05040100u)};
+  hi = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x07060302u), __builtin_amdgcn_perm(sa[3], sa[2], 0x07060302u),
+             __builtin_amdgcn_perm(sb[1], sb[0], 0x07060302u), __builtin_amdgcn_perm(sb[3], sb[2], 0x07060302u)};
+}
+// the transposing read at LDS byte address `addr`
+__device__ __forceinline__ u32x2 tr(unsigned addr) {
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(size_t)addr));
+}
+// an MFMA operand: rows 0..3 (r1) and 4..7 (r2) of this lane's K slots
+__device__ __forceinline__ u32x4 frag(u32x2 r1, u32x2 r2) { return u32x4{r1[0], r1[1], r2[0], r2[1]}; }
+__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) void*)p; }
+
+// Everything the two forms differ in.  A unit = 8 consecutive values of a row = 16 bytes of an LDS row.
+template <bool X2>
+struct Form {
+  using T = std::conditional_t<X2, float, bf16>;   // source element
+  static constexpr int REGS = X2 ? 2 : 1;          // 16-byte registers per unit
+  static constexpr int LR = X2 ? 2 : 1;            // LDS rows per source row
+
+  static __device__ __forceinline__ void load_unit(const T* p, u32x4 (&v)[REGS]) {
+    v[0] = *reinterpret_cast<const u32x4*>(p);
+    if constexpr (X2) v[1] = *reinterpret_cast<const u32x4*>(p + 4);
+  }
+  // the unit, or zeros unless bit `bit` of `okm` is set, into its LDS row at d; two-limb: the lo limbs there, the hi limbs one row (32 B) further
+  // (the bit is tested here, behind the limb split, where the two-limb copies tested it)
+  static __device__ __forceinline__ void store_unit(const u32x4 (&v)[REGS], unsigned okm, int bit, unsigned char* d) {
+    if constexpr (X2) {
+      const u32x4 z4 = {0u, 0u, 0u, 0u};
+      u32x4 lo, hi;
+      limbs8(v[0], v[1], lo, hi);
+      const bool ok = (okm >> bit) & 1u;
+      *reinterpret_cast<u32x4*>(d) = ok ? lo : z4;
+      *reinterpret_cast<u32x4*>(d + 32) = ok ? hi : z4;
+    } else {
+      *reinterpret_cast<u32x4*>(d) = (okm >> bit) & 1u ? v[0] : u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+  // ... unconditionally (wgrad1x1: its loads already zeroed what lies outside)
+  static __device__ __forceinline__ void store_unit(const u32x4 (&v)[REGS], unsigned char* d) {
+    if constexpr (X2) {
+      u32x4 lo, hi;
+      limbs8(v[0], v[1], lo, hi);
+      *reinterpret_cast<u32x4*>(d) = lo;
+      *reinterpret_cast<u32x4*>(d + 32) = hi;
+    } else {
+      *reinterpret_cast<u32x4*>(d) = v[0];
+    }
+  }
+  static __device__ __forceinline__ u32x4 swap_halves(u32x4 b) {
+    u32x4 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = __builtin_amdgcn_alignbit(b[e], b[e], 16);
+    return r;
+  }
+  // one K step of a tile; two-limb: the cross terms (b with its halves swapped) first, hi hi + lo lo last (as conv_gemm_v2)
+  static __device__ __forceinline__ f32x4 mma_step(u32x4 af, u32x4 bf, f32x4 acc) {
+    if constexpr (X2) acc = mma_chunk<bf16>(af, swap_halves(bf), acc);
+    return mma_chunk<bf16>(af, bf, acc);
+  }
+};
+
+// LDS layout of wgrad3x3_kernel (byte offsets), shared with its launcher
+template <int NC, int CC, int MAXW, int ROWS, bool X2>
+struct Geom3x3 {
+  static constexpr int LR = Form<X2>::LR;
+  static constexpr int WINP = ROWS + 2 * (MAXW + 1) + 3;      // pixels of the x window (W <= MAXW), rounded up to an ODD count: the staging stores walk the
+                                                              // 16-column subtiles, and with an even pitch they met on 2 of the 16 bank groups
+  static constexpr int ZSUB = LR * ROWS * 32, XSUB = LR * WINP * 32;      // subtile pitches
+  static constexpr int ZT_BYTES = (NC / 16) * ZSUB, XW_BYTES = (CC / 16) * XSUB;
+  static constexpr int ZERO = ZT_BYTES + XW_BYTES;            // a zero row (32 B) here and another one subtile pitch further (the c-tile offset is an immediate)
+  static constexpr int lds_bytes = ZERO + XSUB + 32;
+};
+// ... and of wgrad1x1_kernel.  Subtile pitch + 32 bytes: the staging stores of a lane group hit 4 .. 8 DIFFERENT 16-column subtiles at the same row - with
+// a pitch of 0 mod 256 bytes they all landed on the same banks (SQ_LDS_BANK_CONFLICT 54 % of this kernel's LDS cycles, profiles/r03_train_mfma_pmc.txt)
+template <int NT, int CT, bool X2>
+struct Geom1x1 {
+  static constexpr int SUB = Form<X2>::LR * CH * 32 + 32;
+  static constexpr int ZT_BYTES = (NT / 16) * SUB;
+  static constexpr int lds_bytes = ZT_BYTES + (CT / 16) * SUB;
+};
+
+// 512 threads with `lds` bytes of dynamic LDS.  The limit is raised per launch: the attribute is per DEVICE (a process-wide "done" flag skipped it
+// on a second GPU), and the call is host-only and cheap
+template <typename... P, typename... A>
+static int launch(void (*kern)(P...), int lds, dim3 grid, hipStream_t s, A... a) {
+  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, a...);
+  return (int)hipGetLastError();
+}
 }  // namespace wg3
 
 // NC / CC: dz / x columns staged per workgroup.  (256, 256): grouped conv, wave j = group j.  (128, 64): dense conv, wave j = n-block j & 3,
 // c-block j >> 2 of the 64 input channels blockIdx.y * 64 ..  (96, 32): the dense 96 -> 96 layers of the LV-ViT stem - nine 32 x 32 jobs as a
 // 3 x 3 grid: workgroup column blockIdx.y = c-block, waves 0 .. 2 = the three n-blocks (one per SIMD), waves 3 .. 7 only stage.
-template <int NC, int CC, int MAXW>
-__global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ x, int xld, const bf16* __restrict__ dz, int zld, float* __restrict__ part,
-                                                       int M, int H, int W, int n_chunks, int chunks_per_wg) {
+// ROWS = rows per stage: 64, and 32 for the grouped two-limb form (its 256-column window would not fit twice).
+template <int NC, int CC, int MAXW, int ROWS, bool X2>
+__global__ __launch_bounds__(512) void wgrad3x3_kernel(const typename wg3::Form<X2>::T* __restrict__ x, int xld, const typename wg3::Form<X2>::T* __restrict__ dz,
+                                                       int zld, float* __restrict__ part, int M, int H, int W, int n_chunks, int chunks_per_wg) {
   using namespace wg3;
-  constexpr int WINP = CH + 2 * (MAXW + 1) + 3;               // pixels of the x window (W <= MAXW), rounded up to an ODD count: the staging stores walk the
-                                                               // 16-column subtiles, and with an even pitch they met on 2 of the 16 bank groups
-  constexpr int ZT_BYTES = (NC / 16) * CH * 32;
-  constexpr int XW_BYTES = (CC / 16) * WINP * 32;
+  using F = Form<X2>;
+  using G = Geom3x3<NC, CC, MAXW, ROWS, X2>;
+  constexpr int LR = F::LR, WINP = G::WINP, ZSUB = G::ZSUB, XSUB = G::XSUB;
   constexpr bool D96 = NC == 96;
-  constexpr int NPZ = (CH * NC / 8 + 511) / 512;               // 16-byte units of dz per thread and chunk (96 columns: 768 units, the tail is skipped)
+  constexpr int NPZ = (ROWS * NC / 8 + 511) / 512;             // units of dz per thread and chunk (96 columns: 768 units, the tail is skipped)
   constexpr int NPX = (WINP * (CC / 8) + 511) / 512;           // of the x window
+  static_assert(NPZ + NPX <= 32, "validity bits");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const ZT = smem;
-  unsigned char* const XW = smem + ZT_BYTES;
-  unsigned char* const ZERO = smem + ZT_BYTES + XW_BYTES;      // a zero row (32 B) here and another one subtile pitch further (the c-tile offset is an immediate)
+  unsigned char* const XW = smem + G::ZT_BYTES;
+  unsigned char* const ZERO = smem + G::ZERO;
 
   const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
   const int j = __builtin_amdgcn_readfirstlane(t >> 6);
   const int nb = NC == 256 || D96 ? j : (j & 3), cb = D96 ? 0 : NC == 256 ? j : (j >> 2);
   const bool active = !D96 || j < 3;
   const int xc0 = NC == 256 ? 0 : blockIdx.y * CC;
-  const int halo = W + 1, winp = CH + 2 * halo;                // pixels actually used (<= WINP)
+  const int halo = W + 1, winp = ROWS + 2 * halo;              // pixels actually used (<= WINP)
   const int q0 = blockIdx.x * chunks_per_wg;
   int q1 = q0 + chunks_per_wg; q1 = q1 < n_chunks ? q1 : n_chunks;
 
-  if (t < 8) { reinterpret_cast<unsigned*>(ZERO)[t] = 0u; reinterpret_cast<unsigned*>(ZERO + WINP * 32)[t] = 0u; }   // one zero row (32 B) each
+  if (t < 8) { reinterpret_cast<unsigned*>(ZERO)[t] = 0u; reinterpret_cast<unsigned*>(ZERO + XSUB)[t] = 0u; }   // one zero row (32 B) each
 
-  u32x4 pz[NPZ], px[NPX];
+  u32x4 pz[NPZ][F::REGS], px[NPX][F::REGS];
   unsigned okm = 0;                                            // validity bits of pz / px (rows past the end / outside the window read a clamped row)
   auto gload = [&](int q) {                                    // chunk q -> registers
-    const long m0 = (long)q * CH;
+    const long m0 = (long)q * ROWS;
     // UNCONDITIONAL loads on clamped rows, the validity kept as a bit and applied by lstore(): a per-lane `ok ? load : 0` compiles to an exec-masked
     // branch (or a select right behind the load) with its own vmcnt wait, i.e. the chunk's 11 loads went out one latency after the other
     okm = 0;
@@ -72,7 +180,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
     for (int u0 = 0; u0 < NPZ; ++u0) {
       const int u = t + 512 * u0, r = u / (NC / 8), c8 = u % (NC / 8);
       const long m = m0 + r;
-      pz[u0] = *reinterpret_cast<const u32x4*>(dz + (size_t)(m < M ? m : M - 1) * zld + c8 * 8);
+      F::load_unit(dz + (size_t)(m < M ? m : M - 1) * zld + c8 * 8, pz[u0]);
       okm |= m < M ? 1u << u0 : 0u;
     }
 #pragma unroll
@@ -80,7 +188,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
       const int u = t + 512 * u0, p = u / (CC / 8), c8 = u % (CC / 8);
       const long m = m0 - halo + p;
       const bool ok = p < winp && m >= 0 && m < M;
-      px[u0] = *reinterpret_cast<const u32x4*>(x + (size_t)(ok ? m : 0) * xld + xc0 + c8 * 8);
+      F::load_unit(x + (size_t)(ok ? m : 0) * xld + xc0 + c8 * 8, px[u0]);
       okm |= ok ? 1u << (NPZ + u0) : 0u;
     }
   };
@@ -88,12 +196,12 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int u0 = 0; u0 < NPZ; ++u0) {
       const int u = t + 512 * u0, r = u / (NC / 8), c8 = u % (NC / 8);
-      if (!D96 || r < CH) *reinterpret_cast<u32x4*>(ZT + (c8 >> 1) * (CH * 32) + r * 32 + (c8 & 1) * 16) = (okm >> u0) & 1u ? pz[u0] : u32x4{0u, 0u, 0u, 0u};
+      if (!D96 || r < ROWS) F::store_unit(pz[u0], okm, u0, ZT + (c8 >> 1) * ZSUB + (LR * r) * 32 + (c8 & 1) * 16);
     }
 #pragma unroll
     for (int u0 = 0; u0 < NPX; ++u0) {
       const int u = t + 512 * u0, p = u / (CC / 8), c8 = u % (CC / 8);
-      if (p < WINP) *reinterpret_cast<u32x4*>(XW + (c8 >> 1) * (WINP * 32) + p * 32 + (c8 & 1) * 16) = (okm >> (NPZ + u0)) & 1u ? px[u0] : u32x4{0u, 0u, 0u, 0u};
+      if (p < WINP) F::store_unit(px[u0], okm, NPZ + u0, XW + (c8 >> 1) * XSUB + (LR * p) * 32 + (c8 & 1) * 16);
     }
   };
 
@@ -103,12 +211,9 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
 #pragma unroll
     for (int a = 0; a < 4; ++a) acc[tp][a >> 1][a & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const unsigned zt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZT + (nb * 2) * (CH * 32) + (lq * 4 + (i >> 2)) * 32 + (i & 3) * 8;
-  const unsigned xw_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)XW + (cb * 2) * (WINP * 32) + (i & 3) * 8;
-  const unsigned zero_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZERO + (i & 3) * 8;
-  auto tr = [&](unsigned addr) -> u32x2 {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(size_t)addr));
-  };
+  const unsigned zt_lane = lds_addr(ZT) + (nb * 2) * ZSUB + (lq * 4 + (i >> 2)) * 32 + (i & 3) * 8;
+  const unsigned xw_lane = lds_addr(XW) + (cb * 2) * XSUB + (i & 3) * 8;
+  const unsigned zero_lane = lds_addr(ZERO) + (i & 3) * 8;
   const int HW = H * W;
 
   if (q0 < q1) gload(q0);
@@ -117,33 +222,30 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
     lstore();
     __syncthreads();
     if (q + 1 < q1) gload(q + 1);
-    const long m0 = (long)q * CH;
+    const long m0 = (long)q * ROWS;
 #pragma unroll 1
-    for (int ks = 0; ks < (active ? 2 : 0); ++ks) {      // (not unrolled: with both steps' tap addresses live the grouped variant spilled 20 registers)
-      // dz^T fragments: rows (= K slots) ks*32 + h*16 + lq*4 + 0..3, column 16 nt + i
+    for (int ks = 0; ks < (active ? LR * ROWS / 32 : 0); ++ks) {      // 32 LDS rows per step (not unrolled: with both steps' tap addresses live the grouped variant spilled 20 registers)
+      // dz^T fragments: LDS rows (= K slots) ks*32 + h*16 + lq*4 + 0..3, column 16 nt + i
       u32x4 af[2];
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const u32x2 r1 = tr(zt_lane + nt * (CH * 32) + ks * 1024), r2 = tr(zt_lane + nt * (CH * 32) + ks * 1024 + 512);
-        af[nt] = u32x4{r1[0], r1[1], r2[0], r2[1]};
-      }
-      // this lane SUPPLIES the addresses of rows ks*32 + h*16 + lq*4 + (i >> 2), h = 0, 1
+      for (int nt = 0; nt < 2; ++nt) af[nt] = frag(tr(zt_lane + nt * ZSUB + ks * 1024), tr(zt_lane + nt * ZSUB + ks * 1024 + 512));
+      // this lane SUPPLIES the addresses of LDS rows lr = ks*32 + h*16 + lq*4 + (i >> 2), h = 0, 1: row rr = lr / LR of the chunk (two-limb: limb = lr's low bit)
       int oy[2], ox[2];
       unsigned rowa[2];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
-        const int rr = ks * 32 + h * 16 + lq * 4 + (i >> 2);
+        const int lr = ks * 32 + h * 16 + lq * 4 + (i >> 2), rr = lr >> (LR - 1);
         const int m = (int)m0 + rr;
         const int rem = m % HW;
         oy[h] = rem / W; ox[h] = rem - oy[h] * W;
         if (m >= M) oy[h] = -4;                                 // rows past the end: every tap invalid (their dz rows are zero anyway)
-        rowa[h] = xw_lane + (rr + halo) * 32;
+        rowa[h] = xw_lane + (lr + LR * halo) * 32;
       }
-      // per tap: its 4 transposing reads first, then its 4 MFMAs (hipcc had put every MFMA PAIR behind its own two reads and an lgkmcnt(0))
+      // per tap: its 4 transposing reads first, then its MFMAs (hipcc had put every MFMA PAIR behind its own two reads and an lgkmcnt(0))
 #pragma unroll
       for (int tp = 0; tp < 9; ++tp) {
         const int dy = tp / 3 - 1, dx = tp % 3 - 1;
-        const int shift = (dy * W + dx) * 32;
+        const int shift = (dy * W + dx) * (LR * 32);
         unsigned ad[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -152,198 +254,17 @@ __global__ __launch_bounds__(512) void wgrad3x3_kernel(const bf16* __restrict__ 
         }
         u32x4 bf[2];
 #pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          const u32x2 r1 = tr(ad[0] + ct * (WINP * 32)), r2 = tr(ad[1] + ct * (WINP * 32));
-          bf[ct] = u32x4{r1[0], r1[1], r2[0], r2[1]};
-        }
+        for (int ct = 0; ct < 2; ++ct) bf[ct] = frag(tr(ad[0] + ct * XSUB), tr(ad[1] + ct * XSUB));
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
-          acc[tp][0][ct] = mma_chunk<bf16>(af[0], bf[ct], acc[tp][0][ct]);
-          acc[tp][1][ct] = mma_chunk<bf16>(af[1], bf[ct], acc[tp][1][ct]);
+          acc[tp][0][ct] = F::mma_step(af[0], bf[ct], acc[tp][0][ct]);
+          acc[tp][1][ct] = F::mma_step(af[1], bf[ct], acc[tp][1][ct]);
         }
       }
     }
   }
 
   // fp32 partials of this row range: [split][job][tap][n 32][c 32]; lane holds n = 16 nt + 4 lq + e, c = 16 ct + i
-  constexpr int JW = D96 ? 3 : NW;                             // jobs per workgroup
-  const int job = (NC == 256 ? 0 : blockIdx.y * JW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * JW;
-  if (!active) return;
-  float* out = part + ((size_t)blockIdx.x * njobs + job) * JOB;
-#pragma unroll
-  for (int tp = 0; tp < 9; ++tp)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[(tp * 32 + nt * 16 + lq * 4 + e) * 32 + ct * 16 + i] = acc[tp][nt][ct][e];
-}
-
-// ---- the same kernel for the two-limb trainers (fp32 activations, `bf16x2` / `f16x2`): a row of dz / a pixel of x becomes two 16-bit LDS rows
-// (2 r = its lo limbs, 2 r + 1 = its hi limbs; see wgrad1x1_x2_kernel), a tap shifts by 2 rows per pixel, and a 16-row K step is two MFMAs per
-// accumulator tile.  CHX = rows per stage: 64 for the dense layers, 32 for the grouped one (its 256-column window would not fit twice).
-template <int NC, int CC, int MAXW, int CHX>
-__global__ __launch_bounds__(512) void wgrad3x3_x2_kernel(const float* __restrict__ x, int xld, const float* __restrict__ dz, int zld, float* __restrict__ part,
-                                                          int M, int H, int W, int n_chunks, int chunks_per_wg) {
-  using namespace wg3;
-  constexpr int WINP = CHX + 2 * (MAXW + 1) + 3;
-  constexpr int ZSUB = 2 * CHX * 32, XSUB = 2 * WINP * 32;     // subtile pitches (limb rows)
-  constexpr int ZT_BYTES = (NC / 16) * ZSUB;
-  constexpr int XW_BYTES = (CC / 16) * XSUB;
-  constexpr bool D96 = NC == 96;
-  constexpr int NPZ = (CHX * NC / 8 + 511) / 512;
-  constexpr int NPX = (WINP * (CC / 8) + 511) / 512;
-  static_assert(NPZ + NPX <= 32, "validity bits");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const ZT = smem;
-  unsigned char* const XW = smem + ZT_BYTES;
-  unsigned char* const ZERO = smem + ZT_BYTES + XW_BYTES;      // a zero row (32 B) here and another one subtile pitch further
-
-  const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
-  const int j = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int nb = NC == 256 || D96 ? j : (j & 3), cb = D96 ? 0 : NC == 256 ? j : (j >> 2);
-  const bool active = !D96 || j < 3;
-  const int xc0 = NC == 256 ? 0 : blockIdx.y * CC;
-  const int halo = W + 1, winp = CHX + 2 * halo;
-  const int q0 = blockIdx.x * chunks_per_wg;
-  int q1 = q0 + chunks_per_wg; q1 = q1 < n_chunks ? q1 : n_chunks;
-
-  if (t < 8) { reinterpret_cast<unsigned*>(ZERO)[t] = 0u; reinterpret_cast<unsigned*>(ZERO + XSUB)[t] = 0u; }
-
-  u32x4 pz[NPZ][2], px[NPX][2];
-  unsigned okm = 0;
-  auto gload = [&](int q) {
-    const long m0 = (long)q * CHX;
-    okm = 0;
-#pragma unroll
-    for (int u0 = 0; u0 < NPZ; ++u0) {
-      const int u = t + 512 * u0, r = u / (NC / 8), c8 = u % (NC / 8);
-      const long m = m0 + r;
-      const float* src = dz + (size_t)(m < M ? m : M - 1) * zld + c8 * 8;
-      pz[u0][0] = *reinterpret_cast<const u32x4*>(src);
-      pz[u0][1] = *reinterpret_cast<const u32x4*>(src + 4);
-      okm |= m < M ? 1u << u0 : 0u;
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < NPX; ++u0) {
-      const int u = t + 512 * u0, p = u / (CC / 8), c8 = u % (CC / 8);
-      const long m = m0 - halo + p;
-      const bool ok = p < winp && m >= 0 && m < M;
-      const float* src = x + (size_t)(ok ? m : 0) * xld + xc0 + c8 * 8;
-      px[u0][0] = *reinterpret_cast<const u32x4*>(src);
-      px[u0][1] = *reinterpret_cast<const u32x4*>(src + 4);
-      okm |= ok ? 1u << (NPZ + u0) : 0u;
-    }
-  };
-  auto limbs8 = [&](const u32x4 a, const u32x4 b, u32x4& lo, u32x4& hi) {
-    u32x4 sa, sb, r_;
-    x2_split(a, sa, r_);
-    x2_split(b, sb, r_);
-    lo = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x05040100u), __builtin_amdgcn_perm(sa[3], sa[2], 0x05040100u),
-               __builtin_amdgcn_perm(sb[1], sb[0], 0x05040100u), __builtin_amdgcn_perm(sb[3], sb[2], 0x05040100u)};
-    hi = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x07060302u), __builtin_amdgcn_perm(sa[3], sa[2], 0x07060302u),
-               __builtin_amdgcn_perm(sb[1], sb[0], 0x07060302u), __builtin_amdgcn_perm(sb[3], sb[2], 0x07060302u)};
-  };
-  auto lstore = [&]() {
-    const u32x4 z4 = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int u0 = 0; u0 < NPZ; ++u0) {
-      const int u = t + 512 * u0, r = u / (NC / 8), c8 = u % (NC / 8);
-      u32x4 lo, hi;
-      limbs8(pz[u0][0], pz[u0][1], lo, hi);
-      const bool ok = (okm >> u0) & 1u;
-      unsigned char* d = ZT + (c8 >> 1) * ZSUB + (2 * r) * 32 + (c8 & 1) * 16;
-      if (!D96 || r < CHX) {
-        *reinterpret_cast<u32x4*>(d) = ok ? lo : z4;
-        *reinterpret_cast<u32x4*>(d + 32) = ok ? hi : z4;
-      }
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < NPX; ++u0) {
-      const int u = t + 512 * u0, p = u / (CC / 8), c8 = u % (CC / 8);
-      if (p < WINP) {
-        u32x4 lo, hi;
-        limbs8(px[u0][0], px[u0][1], lo, hi);
-        const bool ok = (okm >> (NPZ + u0)) & 1u;
-        unsigned char* d = XW + (c8 >> 1) * XSUB + (2 * p) * 32 + (c8 & 1) * 16;
-        *reinterpret_cast<u32x4*>(d) = ok ? lo : z4;
-        *reinterpret_cast<u32x4*>(d + 32) = ok ? hi : z4;
-      }
-    }
-  };
-
-  f32x4 acc[9][2][2];
-#pragma unroll
-  for (int tp = 0; tp < 9; ++tp)
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[tp][a >> 1][a & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const unsigned zt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZT + (nb * 2) * ZSUB + (lq * 4 + (i >> 2)) * 32 + (i & 3) * 8;
-  const unsigned xw_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)XW + (cb * 2) * XSUB + (i & 3) * 8;
-  const unsigned zero_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZERO + (i & 3) * 8;
-  auto tr = [&](unsigned addr) -> u32x2 {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(size_t)addr));
-  };
-  const int HW = H * W;
-
-  if (q0 < q1) gload(q0);
-  for (int q = q0; q < q1; ++q) {
-    __syncthreads();
-    lstore();
-    __syncthreads();
-    if (q + 1 < q1) gload(q + 1);
-    const long m0 = (long)q * CHX;
-#pragma unroll 1
-    for (int ks = 0; ks < (active ? CHX / 16 : 0); ++ks) {                      // 32 limb rows = 16 rows of dz per step (not unrolled: the tap addresses of all steps at once spill)
-      u32x4 af[2];
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const u32x2 r1 = tr(zt_lane + nt * ZSUB + ks * 1024), r2 = tr(zt_lane + nt * ZSUB + ks * 1024 + 512);
-        af[nt] = u32x4{r1[0], r1[1], r2[0], r2[1]};
-      }
-      // this lane SUPPLIES the addresses of limb rows ks*32 + h*16 + lq*4 + (i >> 2), h = 0, 1: row rr = that >> 1 of the chunk, limb = its low bit
-      int oy[2], ox[2];
-      unsigned rowa[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int lr = ks * 32 + h * 16 + lq * 4 + (i >> 2), rr = lr >> 1;
-        const int m = (int)m0 + rr;
-        const int rem = m % HW;
-        oy[h] = rem / W; ox[h] = rem - oy[h] * W;
-        if (m >= M) oy[h] = -4;
-        rowa[h] = xw_lane + (lr + 2 * halo) * 32;
-      }
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) {
-        const int dy = tp / 3 - 1, dx = tp % 3 - 1;
-        const int shift = (dy * W + dx) * 64;
-        unsigned ad[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const bool ok = (unsigned)(oy[h] + dy) < (unsigned)H && (unsigned)(ox[h] + dx) < (unsigned)W;
-          ad[h] = ok ? rowa[h] + shift : zero_lane;
-        }
-        u32x4 bf[2];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          const u32x2 r1 = tr(ad[0] + ct * XSUB), r2 = tr(ad[1] + ct * XSUB);
-          bf[ct] = u32x4{r1[0], r1[1], r2[0], r2[1]};
-        }
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          u32x4 br;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) br[e] = __builtin_amdgcn_alignbit(bf[ct][e], bf[ct][e], 16);
-          acc[tp][0][ct] = mma_chunk<bf16>(af[0], br, acc[tp][0][ct]);
-          acc[tp][1][ct] = mma_chunk<bf16>(af[1], br, acc[tp][1][ct]);
-          acc[tp][0][ct] = mma_chunk<bf16>(af[0], bf[ct], acc[tp][0][ct]);
-          acc[tp][1][ct] = mma_chunk<bf16>(af[1], bf[ct], acc[tp][1][ct]);
-        }
-      }
-    }
-  }
-
   constexpr int JW = D96 ? 3 : NW;                             // jobs per workgroup
   const int job = (NC == 256 ? 0 : blockIdx.y * JW) + j, njobs = (NC == 256 ? 1 : gridDim.y) * JW;
   if (!active) return;
@@ -389,7 +310,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_finalize_kernel(const float* __r
 // Supported: 3x3 / stride 1 / pad 1, 16-bit storage; grouped with 32 -> 32 channels per group and 8 groups, or dense with 128 output
 // channels and 64 / 128 input channels, or dense 96 -> 96.
 bool wgrad3x3_supported(int dtype, int O, int Ig, int groups, int W) {
-  if (dtype != 1 && dtype != 2) return false;         // dtype 2: fp32 rows, two-limb arithmetic (wgrad3x3_x2_kernel)
+  if (dtype != 1 && dtype != 2) return false;         // dtype 2: fp32 rows, two-limb arithmetic (the X2 form)
   if (groups == 8) return O == 256 && Ig == 32 && W <= 20;
   return groups == 1 && W <= 40 && ((O == 128 && (Ig == 64 || Ig == 128)) || (O == 96 && Ig == 96));
 }
@@ -410,6 +331,11 @@ size_t wgrad3x3_scratch_bytes(int O, int Ig, int groups, int M, int dtype) {
   wgrad3x3_plan(O, Ig, groups, M, &splits, &cpw, &njobs, dtype);
   return (size_t)splits * njobs * wg3::JOB * sizeof(float);
 }
+template <int NC, int CC, int MAXW, int ROWS, bool X2, typename... A>
+static int run_wgrad3x3(dim3 grid, hipStream_t s, const void* x, int xld, const void* dz, A... a) {
+  using T = typename wg3::Form<X2>::T;
+  return wg3::launch(wgrad3x3_kernel<NC, CC, MAXW, ROWS, X2>, wg3::Geom3x3<NC, CC, MAXW, ROWS, X2>::lds_bytes, grid, s, (const T*)x, xld, (const T*)dz, a...);
+}
 // defer != nullptr: the split slabs are left in `scratch` for a later batched finalize (train_kernels.hip wgrad_finalize_multi, kind 3) and
 // defer[0..1] = {njobs, splits}
 int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, float* scratch, int B, int H, int W, int O, int Ig, int groups, hipStream_t s,
@@ -417,39 +343,13 @@ int launch_wgrad3x3(const void* x, int xld, const void* dz, int zld, float* dw, 
   const int M = B * H * W;
   int splits, cpw, njobs;
   const int n_chunks = wgrad3x3_plan(O, Ig, groups, M, &splits, &cpw, &njobs, dtype);
-  if (dtype == 2 && groups == 8) {
-    constexpr int CHX = 32, WINP = CHX + 2 * 21 + 3, lds = (256 / 16) * 2 * CHX * 32 + (256 / 16) * 2 * WINP * 32 + 2 * WINP * 32 + 32;
-    auto kern = wgrad3x3_x2_kernel<256, 256, 20, CHX>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(splits), dim3(512), lds, s, (const float*)x, xld, (const float*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  } else if (dtype == 2 && O == 96) {
-    constexpr int CHX = 64, WINP = CHX + 2 * 41 + 3, lds = (96 / 16) * 2 * CHX * 32 + (32 / 16) * 2 * WINP * 32 + 2 * WINP * 32 + 32;
-    auto kern = wgrad3x3_x2_kernel<96, 32, 40, CHX>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(splits, 3), dim3(512), lds, s, (const float*)x, xld, (const float*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  } else if (dtype == 2) {
-    constexpr int CHX = 64, WINP = CHX + 2 * 41 + 3, lds = (128 / 16) * 2 * CHX * 32 + (64 / 16) * 2 * WINP * 32 + 2 * WINP * 32 + 32;
-    auto kern = wgrad3x3_x2_kernel<128, 64, 40, CHX>;
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3(splits, Ig / 64), dim3(512), lds, s, (const float*)x, xld, (const float*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  } else if (groups == 8) {
-    constexpr int WINP = wg3::CH + 2 * 21 + 3, lds = (256 / 16) * wg3::CH * 32 + (256 / 16) * WINP * 32 + WINP * 32 + 32;
-    {    // per launch: the attribute is per DEVICE (a process-wide "done" flag skipped it on a second GPU), and the call is cheap
-      hipError_t e = hipFuncSetAttribute((const void*)wgrad3x3_kernel<256, 256, 20>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((wgrad3x3_kernel<256, 256, 20>), dim3(splits), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  } else if (O == 96) {
-    constexpr int WINP = wg3::CH + 2 * 41 + 3, lds = (96 / 16) * wg3::CH * 32 + (32 / 16) * WINP * 32 + WINP * 32 + 32;
-    hipLaunchKernelGGL((wgrad3x3_kernel<96, 32, 40>), dim3(splits, 3), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  } else {
-    constexpr int WINP = wg3::CH + 2 * 41 + 3, lds = (128 / 16) * wg3::CH * 32 + (64 / 16) * WINP * 32 + WINP * 32 + 32;
-    hipLaunchKernelGGL((wgrad3x3_kernel<128, 64, 40>), dim3(splits, Ig / 64), dim3(512), lds, s, (const bf16*)x, xld, (const bf16*)dz, zld, scratch, M, H, W, n_chunks, cpw);
-  }
-  int rc = (int)hipGetLastError();
+  auto run = [&](auto x2) {      // the three block shapes of wgrad3x3_supported, rows per stage as wgrad3x3_rows
+    constexpr bool X2 = decltype(x2)::value;
+    if (groups == 8) return run_wgrad3x3<256, 256, 20, X2 ? 32 : 64, X2>(dim3(splits), s, x, xld, dz, zld, scratch, M, H, W, n_chunks, cpw);
+    if (O == 96) return run_wgrad3x3<96, 32, 40, 64, X2>(dim3(splits, 3), s, x, xld, dz, zld, scratch, M, H, W, n_chunks, cpw);
+    return run_wgrad3x3<128, 64, 40, 64, X2>(dim3(splits, Ig / 64), s, x, xld, dz, zld, scratch, M, H, W, n_chunks, cpw);
+  };
+  int rc = dtype == 2 ? run(std::true_type{}) : run(std::false_type{});
   if (rc) return rc;
   if (defer) { defer[0] = njobs; defer[1] = splits; return 0; }
   const int total = njobs * wg3::JOB;
@@ -707,20 +607,19 @@ int launch_gconv3x3_x2(const ConvGemmParams& p, hipStream_t s) {
 // The same transposing-read scheme without taps: a workgroup owns an NT (n) x CT (c) block (256 where the layer has >= 256 columns, else 128), its
 // 8 waves (4 x 2) NT/4 x CT/2 each (up to 32 accumulator tiles); per 64 rows it stages (NT + CT) x 128 B and issues up to 64 MFMAs per wave.  Output is the split-K partial layout wgrad_finalize_multi_kernel (kind 0 / 1) already sums (it also
 // undoes the head-dim padding of qkv rows / proj columns).
-template <int NT, int CT>
-__global__ __launch_bounds__(512) void wgrad1x1_kernel(const bf16* __restrict__ x, int xld, int C, const bf16* __restrict__ dz, int zld, int N,
-                                                       float* __restrict__ y, int M, int n_chunks, int chunks_per_wg, int splits, int Kc_pad) {
+template <int NT, int CT, bool X2>
+__global__ __launch_bounds__(512) void wgrad1x1_kernel(const typename wg3::Form<X2>::T* __restrict__ x, int xld, int C, const typename wg3::Form<X2>::T* __restrict__ dz,
+                                                       int zld, int N, float* __restrict__ y, int M, int n_chunks, int chunks_per_wg, int splits, int Kc_pad) {
   using namespace wg3;
+  using F = Form<X2>;
+  using G = Geom1x1<NT, CT, X2>;
   constexpr int WN = NT / 4, WC = CT / 2;                          // a wave's block: 4 x 2 waves
   constexpr int TN = WN / 16, TC = WC / 16;
-  // subtile pitch 2048 + 32 bytes: the staging stores of a lane group hit 4 .. 8 DIFFERENT 16-column subtiles at the same row - with a pitch
-  // of 0 mod 256 bytes they all landed on the same banks (SQ_LDS_BANK_CONFLICT 54 % of this kernel's LDS cycles, profiles/r03_train_mfma_pmc.txt)
-  constexpr int SUB = CH * 32 + 32;
-  constexpr int ZT_BYTES = (NT / 16) * SUB, XT_BYTES = (CT / 16) * SUB;
+  constexpr int LR = F::LR, SUB = G::SUB;
   constexpr int NPZ = (CH * NT / 8) / 512, NPX = (CH * CT / 8) / 512;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const ZT = smem;
-  unsigned char* const XT = smem + ZT_BYTES;
+  unsigned char* const XT = smem + G::ZT_BYTES;
   const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
   const int j = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wn = j & 3, wc = j >> 2;
@@ -728,43 +627,56 @@ __global__ __launch_bounds__(512) void wgrad1x1_kernel(const bf16* __restrict__ 
   const int q0 = blockIdx.x * chunks_per_wg;
   int q1 = q0 + chunks_per_wg; q1 = q1 < n_chunks ? q1 : n_chunks;
 
-  u32x4 pz[NPZ], px[NPX];
+  u32x4 pz[NPZ][F::REGS], px[NPX][F::REGS];
+  const u32x4 zero4 = {0u, 0u, 0u, 0u};
+  // per-lane `ok ? load : 0`, each form as it was: the 16-bit one on the unclamped address, the two-limb one on a clamped address
   auto gload = [&](int q) {
     const long m0 = (long)q * CH;
 #pragma unroll
     for (int u0 = 0; u0 < NPZ; ++u0) {
       const int u = t + 512 * u0, r = u / (NT / 8), c8 = u % (NT / 8);
       const long m = m0 + r;
-      pz[u0] = (m < M && n0 + c8 * 8 < N) ? *reinterpret_cast<const u32x4*>(dz + (size_t)m * zld + n0 + c8 * 8) : u32x4{0u, 0u, 0u, 0u};
+      if constexpr (X2) {
+        const bool ok = m < M && n0 + c8 * 8 < N;
+        const float* src = dz + (size_t)(ok ? m : 0) * zld + (ok ? n0 + c8 * 8 : 0);
+        pz[u0][0] = ok ? *reinterpret_cast<const u32x4*>(src) : zero4;
+        pz[u0][1] = ok ? *reinterpret_cast<const u32x4*>(src + 4) : zero4;
+      } else {
+        pz[u0][0] = (m < M && n0 + c8 * 8 < N) ? *reinterpret_cast<const u32x4*>(dz + (size_t)m * zld + n0 + c8 * 8) : u32x4{0u, 0u, 0u, 0u};
+      }
     }
 #pragma unroll
     for (int u0 = 0; u0 < NPX; ++u0) {
       const int u = t + 512 * u0, r = u / (CT / 8), c8 = u % (CT / 8);
       const long m = m0 + r;
-      px[u0] = (m < M && c0 + c8 * 8 < C) ? *reinterpret_cast<const u32x4*>(x + (size_t)m * xld + c0 + c8 * 8) : u32x4{0u, 0u, 0u, 0u};
+      if constexpr (X2) {
+        const bool ok = m < M && c0 + c8 * 8 < C;
+        const float* src = x + (size_t)(ok ? m : 0) * xld + (ok ? c0 + c8 * 8 : 0);
+        px[u0][0] = ok ? *reinterpret_cast<const u32x4*>(src) : zero4;
+        px[u0][1] = ok ? *reinterpret_cast<const u32x4*>(src + 4) : zero4;
+      } else {
+        px[u0][0] = (m < M && c0 + c8 * 8 < C) ? *reinterpret_cast<const u32x4*>(x + (size_t)m * xld + c0 + c8 * 8) : u32x4{0u, 0u, 0u, 0u};
+      }
     }
   };
   auto lstore = [&]() {
 #pragma unroll
     for (int u0 = 0; u0 < NPZ; ++u0) {
       const int u = t + 512 * u0, r = u / (NT / 8), c8 = u % (NT / 8);
-      *reinterpret_cast<u32x4*>(ZT + (c8 >> 1) * SUB + r * 32 + (c8 & 1) * 16) = pz[u0];
+      F::store_unit(pz[u0], ZT + (c8 >> 1) * SUB + (LR * r) * 32 + (c8 & 1) * 16);
     }
 #pragma unroll
     for (int u0 = 0; u0 < NPX; ++u0) {
       const int u = t + 512 * u0, r = u / (CT / 8), c8 = u % (CT / 8);
-      *reinterpret_cast<u32x4*>(XT + (c8 >> 1) * SUB + r * 32 + (c8 & 1) * 16) = px[u0];
+      F::store_unit(px[u0], XT + (c8 >> 1) * SUB + (LR * r) * 32 + (c8 & 1) * 16);
     }
   };
   f32x4 acc[TN][TC];
 #pragma unroll
   for (int a = 0; a < TN * TC; ++a) acc[a / TC][a % TC] = f32x4{0.f, 0.f, 0.f, 0.f};
   const unsigned lane_off = (lq * 4 + (i >> 2)) * 32 + (i & 3) * 8;
-  const unsigned zt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZT + (wn * TN) * SUB + lane_off;
-  const unsigned xt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)XT + (wc * TC) * SUB + lane_off;
-  auto tr = [&](unsigned addr) -> u32x2 {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(size_t)addr));
-  };
+  const unsigned zt_lane = lds_addr(ZT) + (wn * TN) * SUB + lane_off;
+  const unsigned xt_lane = lds_addr(XT) + (wc * TC) * SUB + lane_off;
 
   if (q0 < q1) gload(q0);
   for (int q = q0; q < q1; ++q) {
@@ -773,155 +685,19 @@ __global__ __launch_bounds__(512) void wgrad1x1_kernel(const bf16* __restrict__ 
     __syncthreads();
     if (q + 1 < q1) gload(q + 1);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
+    for (int ks = 0; ks < 2 * LR; ++ks) {                          // 32 LDS rows per step
       u32x4 af[TN];
 #pragma unroll
-      for (int k4 = 0; k4 < TN; ++k4) {
-        const u32x2 a1 = tr(zt_lane + k4 * SUB + ks * 1024), a2 = tr(zt_lane + k4 * SUB + ks * 1024 + 512);
-        af[k4] = u32x4{a1[0], a1[1], a2[0], a2[1]};
-      }
+      for (int k4 = 0; k4 < TN; ++k4) af[k4] = frag(tr(zt_lane + k4 * SUB + ks * 1024), tr(zt_lane + k4 * SUB + ks * 1024 + 512));
 #pragma unroll
       for (int ct = 0; ct < TC; ++ct) {
-        const u32x2 b1 = tr(xt_lane + ct * SUB + ks * 1024), b2 = tr(xt_lane + ct * SUB + ks * 1024 + 512);
-        const u32x4 bf = {b1[0], b1[1], b2[0], b2[1]};
+        const u32x4 bf = frag(tr(xt_lane + ct * SUB + ks * 1024), tr(xt_lane + ct * SUB + ks * 1024 + 512));
 #pragma unroll
-        for (int nt = 0; nt < TN; ++nt) acc[nt][ct] = mma_chunk<bf16>(af[nt], bf, acc[nt][ct]);
+        for (int nt = 0; nt < TN; ++nt) acc[nt][ct] = F::mma_step(af[nt], bf, acc[nt][ct]);
       }
     }
   }
   // partials: lane holds n = n0 + WN wn + 16 nt + 4 lq + e, c = c0 + WC wc + 16 ct + i
-  const size_t ldy = (size_t)splits * Kc_pad;
-#pragma unroll
-  for (int nt = 0; nt < TN; ++nt)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int n = n0 + wn * WN + nt * 16 + lq * 4 + e;
-      if (n < N) {
-#pragma unroll
-        for (int ct = 0; ct < TC; ++ct) {
-          const int c = c0 + wc * WC + ct * 16 + i;
-          if (c < C) y[(size_t)n * ldy + (size_t)blockIdx.x * Kc_pad + c] = acc[nt][ct][e];
-        }
-      }
-    }
-}
-
-// ---- the same for the two-limb trainers (`bf16x2` / `f16x2`: fp32 storage).  x and dz are fp32 rows; the limb split happens on the way into LDS:
-// row m of a chunk becomes TWO 16-bit rows, 2 m = lo(m, :) and 2 m + 1 = hi(m, :) (x2_split: hi = the leading bits, lo = the rounded remainder), so the
-// transposing read hands every lane 32-bit words (lo, hi) of ONE value - the k-slot order of conv_gemm_v2's two-limb arithmetic - and a 16-value k step is
-// two MFMAs: (a, b) sums lo lo + hi hi, (a, b with its halves swapped) the cross terms.  No transposed / limb-packed copies of dz and x in HBM
-// (round 3 route: transpose_cols + im2col_t + a limb GEMM, 12 ms of the 57 ms step in transposes alone).
-template <int NT, int CT>
-__global__ __launch_bounds__(512) void wgrad1x1_x2_kernel(const float* __restrict__ x, int xld, int C, const float* __restrict__ dz, int zld, int N,
-                                                          float* __restrict__ y, int M, int n_chunks, int chunks_per_wg, int splits, int Kc_pad) {
-  using namespace wg3;
-  constexpr int WN = NT / 4, WC = CT / 2;
-  constexpr int TN = WN / 16, TC = WC / 16;
-  constexpr int SUB = 2 * CH * 32 + 32;                            // a 16-column subtile of 2 CH limb rows (+ 32: see wgrad1x1_kernel)
-  constexpr int ZT_BYTES = (NT / 16) * SUB;
-  constexpr int NPZ = (CH * NT / 8) / 512, NPX = (CH * CT / 8) / 512;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned char* const ZT = smem;
-  unsigned char* const XT = smem + ZT_BYTES;
-  const int t = threadIdx.x, lane = t & 63, i = lane & 15, lq = lane >> 4;
-  const int j = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wn = j & 3, wc = j >> 2;
-  const int n0 = blockIdx.y * NT, c0 = blockIdx.z * CT;
-  const int q0 = blockIdx.x * chunks_per_wg;
-  int q1 = q0 + chunks_per_wg; q1 = q1 < n_chunks ? q1 : n_chunks;
-
-  u32x4 pz[NPZ][2], px[NPX][2];
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
-  auto gload = [&](int q) {
-    const long m0 = (long)q * CH;
-#pragma unroll
-    for (int u0 = 0; u0 < NPZ; ++u0) {
-      const int u = t + 512 * u0, r = u / (NT / 8), c8 = u % (NT / 8);
-      const long m = m0 + r;
-      const bool ok = m < M && n0 + c8 * 8 < N;
-      const float* src = dz + (size_t)(ok ? m : 0) * zld + (ok ? n0 + c8 * 8 : 0);
-      pz[u0][0] = ok ? *reinterpret_cast<const u32x4*>(src) : zero4;
-      pz[u0][1] = ok ? *reinterpret_cast<const u32x4*>(src + 4) : zero4;
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < NPX; ++u0) {
-      const int u = t + 512 * u0, r = u / (CT / 8), c8 = u % (CT / 8);
-      const long m = m0 + r;
-      const bool ok = m < M && c0 + c8 * 8 < C;
-      const float* src = x + (size_t)(ok ? m : 0) * xld + (ok ? c0 + c8 * 8 : 0);
-      px[u0][0] = ok ? *reinterpret_cast<const u32x4*>(src) : zero4;
-      px[u0][1] = ok ? *reinterpret_cast<const u32x4*>(src + 4) : zero4;
-    }
-  };
-  // 8 fp32 values -> their 8 lo limbs and 8 hi limbs, packed in column order
-  auto limbs8 = [&](const u32x4 a, const u32x4 b, u32x4& lo, u32x4& hi) {
-    u32x4 sa, sb, r_;
-    x2_split(a, sa, r_);
-    x2_split(b, sb, r_);
-    lo = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x05040100u), __builtin_amdgcn_perm(sa[3], sa[2], 0x05040100u),
-               __builtin_amdgcn_perm(sb[1], sb[0], 0x05040100u), __builtin_amdgcn_perm(sb[3], sb[2], 0x05040100u)};
-    hi = u32x4{__builtin_amdgcn_perm(sa[1], sa[0], 0x07060302u), __builtin_amdgcn_perm(sa[3], sa[2], 0x07060302u),
-               __builtin_amdgcn_perm(sb[1], sb[0], 0x07060302u), __builtin_amdgcn_perm(sb[3], sb[2], 0x07060302u)};
-  };
-  auto lstore = [&]() {
-#pragma unroll
-    for (int u0 = 0; u0 < NPZ; ++u0) {
-      const int u = t + 512 * u0, r = u / (NT / 8), c8 = u % (NT / 8);
-      u32x4 lo, hi;
-      limbs8(pz[u0][0], pz[u0][1], lo, hi);
-      unsigned char* d = ZT + (c8 >> 1) * SUB + (2 * r) * 32 + (c8 & 1) * 16;
-      *reinterpret_cast<u32x4*>(d) = lo;
-      *reinterpret_cast<u32x4*>(d + 32) = hi;
-    }
-#pragma unroll
-    for (int u0 = 0; u0 < NPX; ++u0) {
-      const int u = t + 512 * u0, r = u / (CT / 8), c8 = u % (CT / 8);
-      u32x4 lo, hi;
-      limbs8(px[u0][0], px[u0][1], lo, hi);
-      unsigned char* d = XT + (c8 >> 1) * SUB + (2 * r) * 32 + (c8 & 1) * 16;
-      *reinterpret_cast<u32x4*>(d) = lo;
-      *reinterpret_cast<u32x4*>(d + 32) = hi;
-    }
-  };
-  f32x4 acc[TN][TC];
-#pragma unroll
-  for (int a = 0; a < TN * TC; ++a) acc[a / TC][a % TC] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const unsigned lane_off = (lq * 4 + (i >> 2)) * 32 + (i & 3) * 8;
-  const unsigned zt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)ZT + (wn * TN) * SUB + lane_off;
-  const unsigned xt_lane = (unsigned)(size_t)(__attribute__((address_space(3))) void*)XT + (wc * TC) * SUB + lane_off;
-  auto tr = [&](unsigned addr) -> u32x2 {
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4*)(size_t)addr));
-  };
-
-  if (q0 < q1) gload(q0);
-  for (int q = q0; q < q1; ++q) {
-    __syncthreads();
-    lstore();
-    __syncthreads();
-    if (q + 1 < q1) gload(q + 1);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {                               // 32 limb rows = 16 fp32 rows per step
-      u32x4 af[TN];
-#pragma unroll
-      for (int k4 = 0; k4 < TN; ++k4) {
-        const u32x2 a1 = tr(zt_lane + k4 * SUB + ks * 1024), a2 = tr(zt_lane + k4 * SUB + ks * 1024 + 512);
-        af[k4] = u32x4{a1[0], a1[1], a2[0], a2[1]};
-      }
-#pragma unroll
-      for (int ct = 0; ct < TC; ++ct) {
-        const u32x2 b1 = tr(xt_lane + ct * SUB + ks * 1024), b2 = tr(xt_lane + ct * SUB + ks * 1024 + 512);
-        const u32x4 bf = {b1[0], b1[1], b2[0], b2[1]};
-        u32x4 br;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) br[e] = __builtin_amdgcn_alignbit(bf[e], bf[e], 16);
-#pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-          acc[nt][ct] = mma_chunk<bf16>(af[nt], br, acc[nt][ct]);      // the cross terms first, hi hi + lo lo last (as conv_gemm_v2)
-          acc[nt][ct] = mma_chunk<bf16>(af[nt], bf, acc[nt][ct]);
-        }
-      }
-    }
-  }
   const size_t ldy = (size_t)splits * Kc_pad;
 #pragma unroll
   for (int nt = 0; nt < TN; ++nt)
@@ -957,6 +733,11 @@ int wgrad1x1_splits(int N, int C, int M, int dtype) {
   const int cpw = (n_chunks + s - 1) / s;
   return (n_chunks + cpw - 1) / cpw;
 }
+template <int NT, int CT, bool X2, typename... A>
+static int run_wgrad1x1(dim3 grid, hipStream_t s, const void* x, int xld, int C, const void* dz, A... a) {
+  using T = typename wg3::Form<X2>::T;
+  return wg3::launch(wgrad1x1_kernel<NT, CT, X2>, wg3::Geom1x1<NT, CT, X2>::lds_bytes, grid, s, (const T*)x, xld, C, (const T*)dz, a...);
+}
 int launch_wgrad1x1(const void* x, int xld, int C, const void* dz, int zld, int N, float* y, int M, int Kc_pad, hipStream_t s, int dtype) {
   int NT, CT;
   wgrad1x1_tile(N, C, &NT, &CT, dtype);
@@ -964,26 +745,20 @@ int launch_wgrad1x1(const void* x, int xld, int C, const void* dz, int zld, int 
   const int splits = wgrad1x1_splits(N, C, M, dtype);
   const int cpw = (n_chunks + splits - 1) / splits;
   const dim3 grid(splits, (N + NT - 1) / NT, (C + CT - 1) / CT);
-#define WG1_LAUNCH(A, B) do { const int lds = ((A) / 16 + (B) / 16) * (wg3::CH * 32 + 32);                                                                  \
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad1x1_kernel<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                            \
-    if (e != hipSuccess) return (int)e;                                                                                                                  \
-    hipLaunchKernelGGL((wgrad1x1_kernel<A, B>), grid, dim3(512), lds, s, (const bf16*)x, xld, C, (const bf16*)dz, zld, N, y, M, n_chunks, cpw, splits, Kc_pad); } while (0)
-#define WG1X_LAUNCH(A, B) do { const int lds = ((A) / 16 + (B) / 16) * (2 * wg3::CH * 32 + 32);                                                             \
-    hipError_t e = hipFuncSetAttribute((const void*)wgrad1x1_x2_kernel<A, B>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);                         \
-    if (e != hipSuccess) return (int)e;                                                                                                                  \
-    hipLaunchKernelGGL((wgrad1x1_x2_kernel<A, B>), grid, dim3(512), lds, s, (const float*)x, xld, C, (const float*)dz, zld, N, y, M, n_chunks, cpw, splits, Kc_pad); } while (0)
-  if (dtype == 2) {
-    if (NT == 256) WG1X_LAUNCH(256, 128);
-    else if (CT == 256) WG1X_LAUNCH(128, 256);
-    else WG1X_LAUNCH(128, 128);
-    return (int)hipGetLastError();
+  auto run = [&](auto x2, auto nt, auto ct) {
+    return run_wgrad1x1<decltype(nt)::value, decltype(ct)::value, decltype(x2)::value>(grid, s, x, xld, C, dz, zld, N, y, M, n_chunks, cpw, splits, Kc_pad);
+  };
+  using B128 = std::integral_constant<int, 128>;
+  using B256 = std::integral_constant<int, 256>;
+  if (dtype == 2) {      // no 256 x 256 two-limb block (wgrad1x1_tile)
+    if (NT == 256) return run(std::true_type{}, B256{}, B128{});
+    if (CT == 256) return run(std::true_type{}, B128{}, B256{});
+    return run(std::true_type{}, B128{}, B128{});
   }
-  if (NT == 256 && CT == 256) WG1_LAUNCH(256, 256);
-  else if (NT == 256) WG1_LAUNCH(256, 128);
-  else if (CT == 256) WG1_LAUNCH(128, 256);
-  else WG1_LAUNCH(128, 128);
-#undef WG1_LAUNCH
-  return (int)hipGetLastError();
+  if (NT == 256 && CT == 256) return run(std::false_type{}, B256{}, B256{});
+  if (NT == 256) return run(std::false_type{}, B256{}, B128{});
+  if (CT == 256) return run(std::false_type{}, B128{}, B256{});
+  return run(std::false_type{}, B128{}, B128{});
 }
 
 }  // namespace FSVIT_NS

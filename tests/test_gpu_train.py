@@ -591,10 +591,11 @@ def _wgrad1x1_splits(M, N, C):
     return -(-chunks // cpw)
 
 
-# (64, 8, 8): ONE split - the finalize's sum is a copy; (390, 8, 8): 7 splits - its four-slab loop runs once and the tail loop three times
+# (64, 8, 8): ONE split - the finalize's sum is a copy; (390, 8, 8): 7 splits - its four-slab loop runs once and the tail loop three times;
+# (130, 8, 256): the 128 x 256 block (N < 256 <= C, e.g. the stage-1 conv3 gradient) - every other shape with C >= 256 has N >= 256 as well
 @pytest.mark.gpu
 @pytest.mark.parametrize('shape', [(8000, 1024, 256), (2000, 864, 256), (2000, 512, 576), (5000, 128, 32), (777, 256, 128), (64, 1728, 512), (130, 8, 8),
-                                   (64, 8, 8), (390, 8, 8)])
+                                   (64, 8, 8), (390, 8, 8), (130, 8, 256)])
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 def test_conv1x1_wgrad_direct_vs_torch(shape, dtype):
     """fsvit_conv1x1_wgrad vs dz^T @ x in fp32 on the same 16-bit-rounded operands (ragged M, N, C tails included).  The operator sums its split
@@ -618,7 +619,8 @@ def test_conv1x1_wgrad_direct_vs_torch(shape, dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('shape', [(8000, 1024, 256), (2000, 864, 256), (2000, 512, 576), (5000, 128, 32), (777, 256, 128), (64, 1728, 512), (130, 8, 8)])
+@pytest.mark.parametrize('shape', [(8000, 1024, 256), (2000, 864, 256), (2000, 512, 576), (5000, 128, 32), (777, 256, 128), (64, 1728, 512), (130, 8, 8),
+                                   (130, 8, 256)])
 @pytest.mark.parametrize('limbs', ['bf16', 'f16'])
 def test_conv1x1_wgrad_two_limb_vs_fp64(shape, limbs):
     """fsvit_conv1x1_wgrad on fp32 rows (FSVIT_BF16X2 / FSVIT_F16X2: the limb split at LDS staging, two MFMAs per 16 values) vs dz^T @ x in fp64 on
