@@ -200,6 +200,8 @@ SIGNATURES = {
     'fsvit_emd_head_backward': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _vp, _sz, _vp]),
     'fsvit_op_emd_solve': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp]),
     'fsvit_op_emd_solve_counts': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp, _vp]),
+    'fsvit_emd_sfc_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'fsvit_emd_sfc_steps': (_i, [_fp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _vp, _vp, _sz, _vp]),
     'fsvit_sampler_draw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 

@@ -12,6 +12,9 @@
 //    and stops.  No block barrier anywhere: the waves of a workgroup run problems of different lengths.
 //  * emd_bwd_kernel: flows are constants (the reference's `solver: opencv` semantics, :118-120): dS = dlogit * temperature / N * F.  One workgroup per
 //    image looping over its partners, no atomics, deterministic.
+//  * emd_sfc_kernel: the 5-shot SFC fine-tune (get_sfc, :83-107) as one on-device loop, one workgroup per episode: per mini-batch update the SFC's
+//    nodes, the problems of the mini-batch (emd_pair_wave, the body emd_pair_kernel runs too), dlogits, the backward onto the SFC and the momentum
+//    update, separated by block barriers that every wave reaches.  Opt-in (DeepEMD(sfc_fused=True)); the default route calls the kernels above.
 #include "fsvit_common.h"
 #include "kernels.h"
 #include "../../include/fsvit.h"
@@ -182,6 +185,24 @@ __global__ __launch_bounds__(64 * EMD_WAVES) void emd_solve_kernel(const float* 
   if (lane == 0) status[b] = st;
 }
 
+// One token on one wave: x [C] -> xh [C] = (x - channel mean) / max(|x - mean|, 1e-8); returns the inverse norm.
+__device__ __forceinline__ float emd_prep_token(const float* x, float* xh, const int C, const int lane) {
+  float s = 0.f;
+  for (int k = lane; k < C; k += 64) s += x[k];
+  const float mean = wave_sum(s) / (float)C;
+  float ss = 0.f;
+  for (int k = lane; k < C; k += 64) { const float d = x[k] - mean; ss += d * d; }
+  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-8f);
+  for (int k = lane; k < C; k += 64) xh[k] = (x[k] - mean) * inv;
+  return inv;
+}
+// Channel k of the token mean of the un-centred map x [N][C]
+__device__ __forceinline__ float emd_prep_pooled(const float* x, const int N, const int C, const int k) {
+  float s = 0.f;
+  for (int n = 0; n < N; ++n) s += x[n * C + k];
+  return s / (float)N;
+}
+
 // tok [n_img][N][C] -> xhat [n_img][N][C], pooled [n_img][C], rn [n_img][N]
 __global__ __launch_bounds__(256) void emd_prep_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok, int n_shot, int N, int C,
                                                        float* __restrict__ xhat, float* __restrict__ pooled, float* __restrict__ rn) {
@@ -189,43 +210,22 @@ __global__ __launch_bounds__(256) void emd_prep_kernel(const float* __restrict__
   const float* x = img < n_shot ? shot_tok + (size_t)img * N * C : query_tok + (size_t)(img - n_shot) * N * C;
   float* xh = xhat + (size_t)img * N * C;
   for (int n = wave; n < N; n += 4) {
-    float s = 0.f;
-    for (int k = lane; k < C; k += 64) s += x[n * C + k];
-    const float mean = wave_sum(s) / (float)C;
-    float ss = 0.f;
-    for (int k = lane; k < C; k += 64) { const float d = x[n * C + k] - mean; ss += d * d; }
-    const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-8f);
-    for (int k = lane; k < C; k += 64) xh[n * C + k] = (x[n * C + k] - mean) * inv;
+    const float inv = emd_prep_token(x + n * C, xh + n * C, C, lane);
     if (lane == 0) rn[(size_t)img * N + n] = inv;
   }
-  for (int k = threadIdx.x; k < C; k += 256) {
-    float s = 0.f;
-    for (int n = 0; n < N; ++n) s += x[n * C + k];
-    pooled[(size_t)img * C + k] = s / (float)N;
-  }
+  for (int k = threadIdx.x; k < C; k += 256) pooled[(size_t)img * C + k] = emd_prep_pooled(x, N, C, k);
 }
 
-__global__ __launch_bounds__(64 * EMD_WAVES) void emd_pair_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok,
-                                                                  const float* __restrict__ xhat, const float* __restrict__ pooled, int E, int P, int Q,
-                                                                  int N, int C, float scale, float* __restrict__ logits, float* __restrict__ flow,
-                                                                  int* __restrict__ status) {
-  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long long prob = (long long)blockIdx.x * EMD_WAVES + wave;
-  if (prob >= (long long)E * Q * P) return;
-  const int p = (int)(prob % P);
-  const long long eq = prob / P;                 // e * Q + q
-  const int e = (int)(eq / Q);
-  const size_t ip = (size_t)e * P + p, iq = (size_t)E * P + (size_t)eq;      // image indices in the workspace (protos first)
-  float* c = lds[wave][0];
-  float* F = lds[wave][1];
+// One (query image, proto image) problem on one wave.  tq / tp: the token maps [N][C], xq / xp: their prepared nodes, gq / gp: their token means [C];
+// c, F: this wave's LDS tiles.  Builds the cost tile and both weight vectors, solves, and returns sum (1 - c) F (the logit before its scale); F holds the
+// flow, st the solver's status.
+__device__ __forceinline__ float emd_pair_wave(const float* tq, const float* tp, const float* xq, const float* xp, const float* gq, const float* gp,
+                                               const int N, const int C, float* c, float* F, const int lane, int& st) {
   for (int idx = lane; idx < EMD_TILE; idx += 64) F[idx] = 0.f;
   if (lane < 32) c[lane * EMD_PITCH + 32] = 0.f;
   // c[a][b] = 1 - <xhat_q[a], xhat_p[b]>: lane (la, lb) of an 8 x 8 grid owns a = la + 8 r, b = lb + 8 s
   {
     const int la = lane >> 3, lb = lane & 7;
-    const float* xq = xhat + iq * N * C;
-    const float* xp = xhat + ip * N * C;
     const float *qa[4], *pb[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -258,45 +258,58 @@ __global__ __launch_bounds__(64 * EMD_WAVES) void emd_pair_kernel(const float* _
   const int me = lane & 31;
   const bool is_row = lane < 32, valid = me < N;
   float w = 0.f;
-  {
-    const float* tq = query_tok + (size_t)eq * N * C;
-    const float* tp = shot_tok + ip * N * C;
-    const float* gq = pooled + iq * C;
-    const float* gp = pooled + ip * C;
-    for (int n = 0; n < N; ++n) {
-      float s1 = 0.f, s2 = 0.f;
-      for (int k = lane * 4; k < C; k += 256) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(tq + (size_t)n * C + k), g = *reinterpret_cast<const f32x4*>(gp + k);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(tp + (size_t)n * C + k), h = *reinterpret_cast<const f32x4*>(gq + k);
-        s1 += a[0] * g[0] + a[1] * g[1] + a[2] * g[2] + a[3] * g[3];
-        s2 += b[0] * h[0] + b[1] * h[1] + b[2] * h[2] + b[3] * h[3];
-      }
-      s1 = wave_sum(s1);
-      s2 = wave_sum(s2);
-      if (lane == n) w = s1;
-      if (lane == 32 + n) w = s2;
+  for (int n = 0; n < N; ++n) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = lane * 4; k < C; k += 256) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(tq + (size_t)n * C + k), g = *reinterpret_cast<const f32x4*>(gp + k);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(tp + (size_t)n * C + k), h = *reinterpret_cast<const f32x4*>(gq + k);
+      s1 += a[0] * g[0] + a[1] * g[1] + a[2] * g[2] + a[3] * g[3];
+      s2 += b[0] * h[0] + b[1] * h[1] + b[2] * h[2] + b[3] * h[3];
     }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if (lane == n) w = s1;
+    if (lane == 32 + n) w = s2;
   }
   w = valid ? fmaxf(w, 0.f) + 1e-3f : 0.f;                       // get_weight_vector (:64)
   w = valid ? fmaxf(w, 0.f) + 1e-5f : 0.f;                       // emd_inference_opencv (emd_utils.py:69-70)
   const float srow = wave_sum(is_row ? w : 0.f), scol = wave_sum(is_row ? 0.f : w);
   w *= (float)N / (is_row ? srow : scol);                        // both sum to N (emd_utils.py:72-73)
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  const int st = emd_solve_wave(c, F, N, w, lane, nullptr);
+  st = emd_solve_wave(c, F, N, w, lane, nullptr);
   float s = 0.f;
   for (int idx = lane; idx < EMD_TILE; idx += 64) s += (1.0f - c[idx]) * F[idx];
-  s = wave_sum(s);
+  return wave_sum(s);
+}
+// F (this wave's LDS tile) -> fb [N][N], two rows per pass
+__device__ __forceinline__ void emd_store_flow(const float* F, float* fb, const int N, const int lane) {
+  const int b = lane & 31;
+  for (int a = lane >> 5; a < N; a += 2)
+    if (b < N) fb[a * N + b] = F[a * EMD_PITCH + b];
+}
+
+__global__ __launch_bounds__(64 * EMD_WAVES) void emd_pair_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok,
+                                                                  const float* __restrict__ xhat, const float* __restrict__ pooled, int E, int P, int Q,
+                                                                  int N, int C, float scale, float* __restrict__ logits, float* __restrict__ flow,
+                                                                  int* __restrict__ status) {
+  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long prob = (long long)blockIdx.x * EMD_WAVES + wave;
+  if (prob >= (long long)E * Q * P) return;
+  const int p = (int)(prob % P);
+  const long long eq = prob / P;                 // e * Q + q
+  const int e = (int)(eq / Q);
+  const size_t ip = (size_t)e * P + p, iq = (size_t)E * P + (size_t)eq;      // image indices in the workspace (protos first)
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  int st;
+  const float s = emd_pair_wave(query_tok + (size_t)eq * N * C, shot_tok + ip * N * C, xhat + iq * N * C, xhat + ip * N * C, pooled + iq * C, pooled + ip * C, N, C,
+                                c, F, lane, st);
   if (lane == 0) {
     logits[prob] = s * scale;
     status[prob] = st;
   }
-  if (flow) {
-    float* fb = flow + (size_t)prob * N * N;
-    for (int idx = lane; idx < EMD_TILE; idx += 64) {
-      const int a = idx / EMD_PITCH, b = idx - a * EMD_PITCH;
-      if (a < N && b < N) fb[a * N + b] = F[idx];
-    }
-  }
+  if (flow) emd_store_flow(F, flow + (size_t)prob * N * N, N, lane);
 }
 
 // One workgroup per image (protos first, then queries), one wave per token.  d xhat = sum over partners and their tokens of g * F * partner xhat
@@ -346,6 +359,194 @@ __global__ __launch_bounds__(256) void emd_bwd_kernel(const float* __restrict__ 
       *reinterpret_cast<f32x4*>(out + (size_t)n * C + k) = v - mean;
     }
   }
+}
+
+// ---- the 5-shot SFC fine-tune (Network.py:83-107) on the device.  One workgroup owns one episode for n_steps mini-batch updates: the mini-batch's
+// support images are the queries of the head, the SFC's `way` maps its protos.  Per step four phases, each closed by a block barrier that every wave
+// reaches (no wave returns early, no barrier sits under a condition): prepare the SFC's nodes; one problem per (slot, class) and wave, EMD_SFC_WAVES at a
+// time, each wave at most ceil(problems / EMD_SFC_WAVES) (emd_pair_wave: the arithmetic of emd_pair_kernel), flows and logits to the episode's workspace; dlogits; the backward onto the SFC (one wave per
+// SFC token, fixed summation order, no atomics) with torch.optim.SGD's update of that token in place.  Nothing is handed between workgroups.
+#ifndef FSVIT_EMD_SFC_WAVES
+#define FSVIT_EMD_SFC_WAVES 16                     // 16 x 2 tiles = 135 KB of LDS, <= 128 VGPRs per lane (DESIGN.md 4f has the measurement against 8)
+#endif
+constexpr int EMD_SFC_WAVES = FSVIT_EMD_SFC_WAVES;
+
+// An episode's workspace, in floats.  The arrays read 16 bytes at a time come first (each a multiple of 64 floats long); `stride` is a multiple of 4.
+struct EmdSfcLayout {
+  size_t sup_xhat, sfc_xhat, grad, sup_pool, sfc_pool, sfc_rn, flow, logit, dl, stride;
+  __host__ __device__ EmdSfcLayout(int way, int n, int bs, int N, int C) {
+    const size_t NC = (size_t)N * C;
+    sup_xhat = 0;                                    // [n][N][C]    prepared nodes of the support images (constant over the fine-tune)
+    sfc_xhat = sup_xhat + (size_t)n * NC;            // [way][N][C]  prepared nodes of the SFC, this step
+    grad = sfc_xhat + (size_t)way * NC;              // [way][N][C]  d xhat, then d sfc
+    sup_pool = grad + (size_t)way * NC;              // [n][C]       token means of the un-centred support maps
+    sfc_pool = sup_pool + (size_t)n * C;             // [way][C]
+    sfc_rn = sfc_pool + (size_t)way * C;             // [way][N]     inverse norms of the SFC's centred tokens
+    flow = sfc_rn + (size_t)way * N;                 // [bs][way][N][N]
+    logit = flow + (size_t)bs * way * N * N;         // [bs][way]
+    dl = logit + (size_t)bs * way;                   // [bs][way]    dlogit * temperature / N
+    stride = (dl + (size_t)bs * way + 3) & ~(size_t)3;
+  }
+};
+
+// support [E][n][N][C], label [n], ids [n_steps][E][bs]; sfc, buf [E][way][N][C] in / out; status_count [E] in / out.  E = gridDim.x.
+// (sfc, buf and the workspace carry no __restrict__: waves of the workgroup hand them to one another across the barriers.)
+__global__ __launch_bounds__(64 * EMD_SFC_WAVES) void emd_sfc_kernel(const float* __restrict__ support, const int* __restrict__ label,
+                                                                     const int* __restrict__ ids, int n_steps, int first, int way, int n, int bs, int N, int C,
+                                                                     float scale, float lr, float momentum, float gmul, float* sfc_all, float* buf_all,
+                                                                     int* status_count, float* ws_all) {
+  __shared__ float lds[EMD_SFC_WAVES][2][EMD_TILE];
+  __shared__ int bad[EMD_SFC_WAVES];
+  __shared__ int next_prob;                                        // phase 2's problem counter
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;      // wave-uniform values stay in scalar registers
+  const int e = blockIdx.x, E = gridDim.x;
+  const int NC = N * C;                                            // the entry bounds an episode's workspace, so every index below, by 2^31
+  const EmdSfcLayout L(way, n, bs, N, C);
+  const float* sup = support + (size_t)e * n * NC;
+  float* sfc = sfc_all + (size_t)e * way * NC;
+  float* buf = buf_all + (size_t)e * way * NC;
+  float* ws = ws_all + (size_t)e * L.stride;
+  float *sup_xhat = ws + L.sup_xhat, *sfc_xhat = ws + L.sfc_xhat, *grad = ws + L.grad, *sup_pool = ws + L.sup_pool, *sfc_pool = ws + L.sfc_pool;
+  float *sfc_rn = ws + L.sfc_rn, *flow = ws + L.flow, *logit = ws + L.logit, *dl = ws + L.dl;
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  const int probs = bs * way, rounds = (probs + EMD_SFC_WAVES - 1) / EMD_SFC_WAVES;
+  int nbad = 0;
+  // the support images' nodes and token means: once per launch
+  for (int i = wave; i < n * N; i += EMD_SFC_WAVES) emd_prep_token(sup + (size_t)i * C, sup_xhat + (size_t)i * C, C, lane);
+  for (int i = tid; i < n * C; i += 64 * EMD_SFC_WAVES) {
+    const int img = i / C;
+    sup_pool[i] = emd_prep_pooled(sup + (size_t)img * NC, N, C, i - img * C);
+  }
+  for (int t = 0; t < n_steps; ++t) {
+    const int* slot = ids + ((size_t)t * E + e) * bs;             // a slot outside [0, n) is empty: skipped, never an address
+    // The lane index of phases 1, 3 and 4 is re-made opaque every step: otherwise their per-lane addresses are hoisted out of the step loop, live across
+    // the solver of phase 2 (which needs all 128 registers of a 16-wave workgroup), and spilled.
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    const int tl = wave * 64 + ln;
+    // 1. the SFC's nodes
+    for (int i = wave; i < way * N; i += EMD_SFC_WAVES) {
+      const float inv = emd_prep_token(sfc + (size_t)i * C, sfc_xhat + (size_t)i * C, C, ln);
+      if (ln == 0) sfc_rn[i] = inv;
+    }
+    for (int i = tl; i < way * C; i += 64 * EMD_SFC_WAVES) {
+      const int p = i / C;
+      sfc_pool[i] = emd_prep_pooled(sfc + (size_t)p * NC, N, C, i - p * C);
+    }
+    if (tl == 0) next_prob = 0;
+    __syncthreads();
+    // 2. problem (slot q, class p) = q * way + p.  A wave that is done takes the next problem off a counter in LDS, at most `rounds` of them (enough for
+    // all: EMD_SFC_WAVES * rounds >= probs), so the problems of the last round go to the waves whose first solves were short.  Which wave solves
+    // which problem changes nothing: every result goes to the problem's own place in the workspace.  No wave waits for another here.
+    for (int r = 0; r < rounds; ++r) {
+      int prob = 0;
+      if (ln == 0) prob = atomicAdd(&next_prob, 1);
+      prob = __builtin_amdgcn_readfirstlane(prob);
+      if (prob >= probs) break;
+      const int q = prob / way, p = prob - q * way;
+      const int id = __builtin_amdgcn_readfirstlane(slot[q]);
+      if (id >= 0 && id < n) {
+        int st, lp = ln;
+        asm volatile("" : "+v"(lp));                              // (and per problem, as in emd_pair_kernel: the tile's row offsets are not kept either)
+        const float s = emd_pair_wave(sup + (size_t)id * NC, sfc + (size_t)p * NC, sup_xhat + (size_t)id * NC, sfc_xhat + (size_t)p * NC,
+                                      sup_pool + (size_t)id * C, sfc_pool + (size_t)p * C, N, C, c, F, lp, st);
+        nbad += st;                                               // a problem at a loop bound still leaves a finite logit and a flow
+        if (lp == 0) logit[prob] = s * scale;
+        emd_store_flow(F, flow + (size_t)prob * N * N, N, lp);
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");    // the tiles are reused by this wave's next problem
+      }
+    }
+    __syncthreads();
+    // 3. dl = (softmax(logits over way) - onehot(label)) / (slots in use) * temperature / N
+    int b = 0;
+    for (int q = 0; q < bs; ++q) b += (slot[q] >= 0 && slot[q] < n) ? 1 : 0;
+    for (int q = tl; q < bs; q += 64 * EMD_SFC_WAVES) {
+      const int id = slot[q];
+      if (id >= 0 && id < n) {
+        const int lab = label[id];
+        const float* lg = logit + (size_t)q * way;
+        float mx = lg[0], sum = 0.f;
+        for (int p = 1; p < way; ++p) mx = fmaxf(mx, lg[p]);
+        for (int p = 0; p < way; ++p) sum += expf(lg[p] - mx);
+        for (int p = 0; p < way; ++p) dl[(size_t)q * way + p] = (expf(lg[p] - mx) / sum - (p == lab ? 1.0f : 0.f)) / (float)b * scale;
+      }
+    }
+    __syncthreads();
+    // 4. backward onto the SFC and the update, token (p, nn) = i on one wave: d xhat = sum over slots and their tokens of dl * F[m][nn] * xhat_q[m], then
+    // rn (d xhat - xhat <xhat, d xhat>), minus the channel mean (emd_bwd_kernel's proto side); buf = grad on the first update of a fine-tune, else
+    // momentum * buf + (1 - dampening) * grad; sfc -= lr * buf
+    const bool start = first != 0 && t == 0;
+    for (int i = wave; i < way * N; i += EMD_SFC_WAVES) {
+      const int p = i / N, nn = i - p * N;
+      const float* xh = sfc_xhat + (size_t)i * C;
+      float* gr = grad + (size_t)i * C;
+      float dot = 0.f;
+      for (int k0 = 0; k0 < C; k0 += 256) {                       // (a uniform trip count: every lane takes part in the ballots below)
+        const int k = k0 + ln * 4;
+        const bool on = k < C;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < bs; ++q) {
+          const int id = slot[q];
+          if (id < 0 || id >= n) continue;
+          const float g = dl[(size_t)q * way + p];
+          const float* oh = sup_xhat + (size_t)id * NC;
+          // column nn of F[support node][SFC node], one support node per lane; a flow has at most 2 N - 1 non-zero entries, so a column has few:
+          // they are taken in ascending m (a fixed summation order)
+          const float fcol = ln < N ? flow[((size_t)q * way + p) * N * N + ln * N + nn] : 0.f;
+          unsigned long long mask = __ballot(fcol != 0.f);
+          for (int j = 0; j < N && mask; ++j) {
+            const int m = __ffsll((long long)mask) - 1;            // < N: only lanes below N can be set
+            mask &= mask - 1;
+            const float f = emd_lane_f(fcol, m);
+            if (on) acc += (g * f) * *reinterpret_cast<const f32x4*>(oh + (size_t)m * C + k);
+          }
+        }
+        if (on) {
+          const f32x4 x = *reinterpret_cast<const f32x4*>(xh + k);
+          dot += acc[0] * x[0] + acc[1] * x[1] + acc[2] * x[2] + acc[3] * x[3];
+          *reinterpret_cast<f32x4*>(gr + k) = acc;
+        }
+      }
+      dot = wave_sum(dot);
+      const float inv = sfc_rn[i];
+      float msum = 0.f;
+      for (int k = ln * 4; k < C; k += 256) {                   // each lane re-reads only what it wrote itself
+        const f32x4 x = *reinterpret_cast<const f32x4*>(xh + k);
+        f32x4 v = *reinterpret_cast<f32x4*>(gr + k);
+        v = (v - x * dot) * inv;
+        msum += v[0] + v[1] + v[2] + v[3];
+        *reinterpret_cast<f32x4*>(gr + k) = v;
+      }
+      const float mean = wave_sum(msum) / (float)C;
+      for (int k = ln * 4; k < C; k += 256) {
+        const f32x4 g = *reinterpret_cast<f32x4*>(gr + k) - mean;
+        f32x4 m = g;
+        if (!start) m = *reinterpret_cast<f32x4*>(buf + (size_t)i * C + k) * momentum + g * gmul;
+        *reinterpret_cast<f32x4*>(buf + (size_t)i * C + k) = m;
+        *reinterpret_cast<f32x4*>(sfc + (size_t)i * C + k) = *reinterpret_cast<f32x4*>(sfc + (size_t)i * C + k) - m * lr;
+      }
+    }
+    __syncthreads();
+  }
+  if (lane == 0) bad[wave] = nbad;
+  __syncthreads();
+  if (tid == 0) {
+    int s = 0;
+    for (int w = 0; w < EMD_SFC_WAVES; ++w) s += bad[w];
+    status_count[e] += s;
+  }
+}
+
+size_t emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C) {
+  return (size_t)E * EmdSfcLayout(way, n, bs, N, C).stride * sizeof(float);
+}
+
+int launch_emd_sfc_steps(const float* support, const int* label, const int* ids, int n_steps, int first, int E, int way, int n, int bs, int N, int C,
+                         float temperature, float lr, float momentum, float dampening, float* sfc, float* buf, int* status_count, void* ws, hipStream_t s) {
+  if (E <= 0 || n_steps <= 0) return 0;
+  return launch(emd_sfc_kernel, dim3(E), dim3(64 * EMD_SFC_WAVES), 0, s, support, label, ids, n_steps, first, way, n, bs, N, C, temperature / (float)N, lr,
+                momentum, 1.0f - dampening, sfc, buf, status_count, reinterpret_cast<float*>(ws));
 }
 
 size_t emd_head_workspace_bytes(int E, int P, int Q, int N, int C) {
@@ -431,6 +632,40 @@ extern "C" int fsvit_emd_head_backward(const float* shot_tok, const float* query
   int rc = fsvit::launch_emd_head_backward(shot_tok, query_tok, dlogits, flow, E, P, Q, N, C, temperature, d_shot_tok, d_query_tok, workspace,
                                            (hipStream_t)stream);
   if (rc) return fsvit_set_error(rc, "fsvit_emd_head_backward: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+static const char* emd_sfc_shape_bad(int E, int way, int n, int bs, int N, int C) {
+  if (E < 0 || E > 65535) return "E must be 0 .. 65535 (one workgroup per episode)";
+  if (way < 1 || n < 1 || bs < 1) return "way, n and bs must be at least 1";
+  if (N < 1 || N > 32) return "N must be 1 .. 32 (one lane per node)";
+  if (C < 64 || C % 64) return "C must be a positive multiple of 64";
+  // ((n + 2 way) N C + (n + way) C + way N + bs way (N N + 2) floats per episode, in floating point so that the test itself cannot wrap)
+  const double per = ((double)n + 2.0 * way) * N * C + ((double)n + way) * C + (double)way * N + (double)bs * way * (N * N + 2);
+  if (per > 2147483000.0) return "an episode's workspace exceeds 2^31 floats";
+  return nullptr;
+}
+
+extern "C" size_t fsvit_emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C) {
+  if (emd_sfc_shape_bad(E, way, n, bs, N, C)) return 0;
+  return fsvit::emd_sfc_workspace_bytes(E, way, n, bs, N, C);
+}
+
+extern "C" int fsvit_emd_sfc_steps(const float* support, const int* label, const int* ids, int n_steps, int first, int E, int way, int n, int bs, int N, int C,
+                                   float temperature, float lr, float momentum, float dampening, float* sfc, float* buf, int* status_count, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!support || !label || !ids || !sfc || !buf || !status_count || !workspace) EMD_FAIL("fsvit_emd_sfc_steps: null argument");
+  if (const char* why = emd_sfc_shape_bad(E, way, n, bs, N, C))
+    EMD_FAIL("fsvit_emd_sfc_steps: E = %d, way = %d, n = %d, bs = %d, N = %d, C = %d: %s", E, way, n, bs, N, C, why);
+  if (n_steps < 0) EMD_FAIL("fsvit_emd_sfc_steps: n_steps = %d", n_steps);
+  for (const float v : {temperature, lr, momentum, dampening})
+    if (!(v - v == 0.0f)) EMD_FAIL("fsvit_emd_sfc_steps: temperature, lr, momentum or dampening is not finite");
+  const size_t need = fsvit::emd_sfc_workspace_bytes(E, way, n, bs, N, C);
+  if (workspace_bytes < need)
+    return fsvit_set_error(FSVIT_ERR_WORKSPACE, "fsvit_emd_sfc_steps: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  int rc = fsvit::launch_emd_sfc_steps(support, label, ids, n_steps, first, E, way, n, bs, N, C, temperature, lr, momentum, dampening, sfc, buf, status_count,
+                                       workspace, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_sfc_steps: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 

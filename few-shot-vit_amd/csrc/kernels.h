@@ -33,4 +33,8 @@ int launch_emd_head_forward(const float* shot_tok, const float* query_tok, int E
 int launch_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N, int C,
                              float temperature, float* d_shot, float* d_query, void* ws, hipStream_t s);
 int launch_emd_solve(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* naug, hipStream_t s);
+// The 5-shot SFC fine-tune on the device, one workgroup per episode.  workspace = emd_sfc_workspace_bytes(E, way, n, bs, N, C)
+size_t emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C);
+int launch_emd_sfc_steps(const float* support, const int* label, const int* ids, int n_steps, int first, int E, int way, int n, int bs, int N, int C,
+                         float temperature, float lr, float momentum, float dampening, float* sfc, float* buf, int* status_count, void* ws, hipStream_t s);
 }  // namespace fsvit

@@ -1518,6 +1518,56 @@ class ops:
                                                            _ptr(ws), ws.numel(), _stream_ptr(dev)))
         return ds, dq
 
+    _emd_sfc_ws = {}
+
+    @staticmethod
+    def emd_sfc_steps(support, label, ids, sfc, buf=None, status_count=None, *, temperature, lr, momentum=0.9, dampening=0.9, first=True):
+        """Mini-batch updates of the 5-shot SFC fine-tune in one launch, one workgroup per episode (fsvit_emd_sfc_steps): support [E,n,N,C] (the support
+        maps, shot-major), label [n], ids a CPU int tensor [steps,E,bs] of support indices (-1: an empty slot of a partial batch; models.deepemd.
+        sfc_step_table), sfc [E,way,N,C] float32 contiguous on the device, updated IN PLACE, as are buf (the momentum buffer; None: a fresh one, which
+        needs first=True) and status_count [E] int32 (None: zeros).  first: step 0 of this call is the first update of the fine-tune (buf = grad).
+        -> (sfc, buf, status_count)."""
+        _require_cuda(support, label, sfc, buf, status_count)
+        if not isinstance(ids, torch.Tensor) or ids.device.type != 'cpu' or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 3:
+            raise ValueError('expected ids as a CPU int32 / int64 tensor [steps,E,bs]')
+        if support.dim() != 4 or sfc.dim() != 4 or sfc.shape[0] != support.shape[0] or sfc.shape[2:] != support.shape[2:]:
+            raise ValueError('expected support [E,n,N,C] and sfc [E,way,N,C]')
+        E, n, N, Cc = support.shape
+        way = sfc.shape[1]
+        steps, bs = ids.shape[0], ids.shape[2]
+        if ids.shape[1] != E or label.shape != (n,):
+            raise ValueError('expected ids [steps,E,bs] and label [n]')
+        if ids.numel() and (int(ids.min()) < -1 or int(ids.max()) >= n):
+            raise ValueError(f'ids must lie in [-1, {n}): found {int(ids.min())} .. {int(ids.max())}')
+        if sfc.dtype != torch.float32 or not sfc.is_contiguous():
+            raise ValueError('sfc must be a contiguous float32 tensor (it is updated in place)')
+        if buf is None:
+            if not first:
+                raise ValueError('first=False needs the buf of the earlier steps')
+            buf = torch.zeros_like(sfc)
+        if buf.shape != sfc.shape or buf.dtype != torch.float32 or not buf.is_contiguous():
+            raise ValueError('buf must be a contiguous float32 tensor of the shape of sfc')
+        dev = sfc.device
+        if status_count is None:
+            status_count = torch.zeros(E, dtype=torch.int32, device=dev)
+        if status_count.shape != (E,) or status_count.dtype != torch.int32:
+            raise ValueError('status_count must be int32 [E]')
+        if E == 0 or steps == 0:
+            return sfc, buf, status_count
+        s = support.detach().contiguous().float()
+        lab = label.to(device=dev, dtype=torch.int32).contiguous()
+        table = ids.to(torch.int32).contiguous().to(dev)
+        with torch.cuda.device(dev):
+            lib = _lib.load()
+            need = lib.fsvit_emd_sfc_workspace_bytes(E, way, n, bs, N, Cc)
+            ws = ops._emd_sfc_ws.get(dev)
+            if ws is None or ws.numel() < max(need, 16):
+                ws = ops._emd_sfc_ws[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            _lib.check(lib.fsvit_emd_sfc_steps(_ptr(s), _ptr(lab), _ptr(table), steps, int(bool(first)), E, way, n, bs, N, Cc, float(temperature), float(lr),
+                                               float(momentum), float(dampening), _ptr(sfc), _ptr(buf), _ptr(status_count), _ptr(ws), ws.numel(),
+                                               _stream_ptr(dev)))
+        return sfc, buf, status_count
+
     @staticmethod
     def emd_solve(cost, w1, w2, counts=False):
         """The transport solver alone: cost [B,N,N], w1 / w2 [B,N] with equal sums -> (flow [B,N,N], status [B] int32[, augmentations [B] int32])."""

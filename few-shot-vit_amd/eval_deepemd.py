@@ -51,7 +51,7 @@ def parse_patch_list(text):
 def build_model(args):
     model = models.make('deepemd', encoder=args.encoder, encoder_args={'numerics': args.numerics} if args.numerics else {},
                         temperature=args.temperature, metric=args.metric, norm=args.norm, deepemd=args.deepemd, feature_pyramid=args.feature_pyramid,
-                        solver=args.solver, sfc_lr=args.sfc_lr, sfc_update_step=int(args.sfc_update_step), sfc_bs=args.sfc_bs)
+                        solver=args.solver, sfc_lr=args.sfc_lr, sfc_update_step=int(args.sfc_update_step), sfc_bs=args.sfc_bs, sfc_fused=args.sfc_fused)
     if args.model_dir:
         return load_params(model, args.model_dir)
     from . import synthetic
@@ -131,6 +131,7 @@ def main(argv=None):
     p.add_argument('-sfc_lr', type=float, default=100)
     p.add_argument('-sfc_update_step', type=float, default=100)
     p.add_argument('-sfc_bs', type=int, default=4)
+    p.add_argument('-sfc_fused', action='store_true', help='5-shot: run the SFC fine-tune as one on-device loop per episode (emd_sfc_kernel)')
     p.add_argument('-test_episode', type=int, default=5000)
     p.add_argument('-model_dir', default=None)
     p.add_argument('-seed', type=int, default=1)

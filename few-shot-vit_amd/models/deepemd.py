@@ -2,7 +2,8 @@
 two images (surface of meta_tuning_sun_d/Models/models/Network.py:9-204 with `solver: opencv`).
 
 The encoder is one of this package's encoders built with return_map=True; the head runs on the HIP kernels of csrc/emd_head.hip (node
-preparation, cost / weights / exact transport solver per (query, proto) pair, and the backward with the flows as constants).  State-dict keys
+preparation, cost / weights / exact transport solver per (query, proto) pair, the backward with the flows as constants, and - with
+`sfc_fused=True` - the 5-shot SFC fine-tune as one on-device loop per episode).  State-dict keys
 are the reference's (`encoder.*`), so the `params` of a SUN-D checkpoint load.
 """
 import torch
@@ -42,11 +43,26 @@ def load_encoder_params(model, path):
     return model
 
 
+SFC_CHUNK = 100        # mini-batch updates per launch of the fused SFC fine-tune (DESIGN.md 4f has the launch time)
+
+
+def sfc_step_table(perms, bs):
+    """The mini-batches of get_sfc in its loop order, for ops.emd_sfc_steps: perms [steps, E, n] (one permutation of the n support images per update
+    step and episode) -> a CPU int32 table [steps * ceil(n / bs), E, bs]; row k * ceil(n / bs) + j holds perms[k, :, j * bs:(j + 1) * bs], and the
+    slots a partial last batch leaves empty hold -1.  Pure torch, runs on the CPU."""
+    perms = torch.as_tensor(perms).to('cpu', torch.int32)
+    steps, E, n = perms.shape
+    per = -(-n // bs)
+    table = torch.full((steps, E, per * bs), -1, dtype=torch.int32)
+    table[:, :, :n] = perms
+    return table.reshape(steps, E, per, bs).permute(0, 2, 1, 3).reshape(steps * per, E, bs).contiguous()
+
+
 @register('deepemd')
 class DeepEMD(nn.Module):
 
     def __init__(self, encoder, encoder_args={}, temperature=12.5, metric='cosine', norm='center', deepemd='fcn', feature_pyramid=None,
-                 solver='opencv', form=None, sfc_lr=100., sfc_update_step=100, sfc_bs=4):
+                 solver='opencv', form=None, sfc_lr=100., sfc_update_step=100, sfc_bs=4, sfc_fused=False):
         super().__init__()
         if feature_pyramid is not None:
             raise NotImplementedError('fsvit: DeepEMD feature_pyramid is not built (DESIGN.md 7)')
@@ -62,6 +78,7 @@ class DeepEMD(nn.Module):
         self.temperature = float(temperature)
         self.deepemd = deepemd
         self.sfc_lr, self.sfc_update_step, self.sfc_bs = float(sfc_lr), int(sfc_update_step), int(sfc_bs)
+        self.sfc_fused = bool(sfc_fused)   # get_sfc as one on-device loop (emd_sfc_kernel) instead of one head forward / backward pair per mini-batch
         self.sfc_generator = None          # torch.Generator of get_sfc's permutations inside forward (None: the global one)
         self._status_count = None          # device int64 scalar: status sum of every head call since the last check_status()
 
@@ -117,12 +134,15 @@ class DeepEMD(nn.Module):
         self.add_status(status)
         return logits
 
-    def get_sfc(self, shot_maps, perms=None, generator=None):
+    def get_sfc(self, shot_maps, perms=None, generator=None, fused=None, chunk=None):
         """Structured fully connected layer (:83-107), batched over episodes: shot_maps [E,way,shot,N,C] -> SFC [E,way,N,C].  Initialised with the
         mean over shots, then sfc_update_step epochs of SGD(lr=sfc_lr, momentum=0.9, dampening=0.9) over mini-batches of sfc_bs support images
         (labels arange(way).repeat(shot): the support set in shot-major order), cross entropy of the EMD logits per episode.  `perms`
         [steps, way*shot] or [steps, E, way*shot] fixes the permutation of every step (tests); otherwise a fresh torch.randperm per step and episode
-        from `generator`.  Head forward / backward are the HIP kernels; the update of the one small tensor is torch arithmetic."""
+        from `generator`.  Head forward / backward are the HIP kernels; the update of the one small tensor is torch arithmetic.
+        `fused` (None: self.sfc_fused) keeps the whole loop on the device instead, one workgroup per episode (emd_sfc_kernel), in launches of at most
+        `chunk` (None: SFC_CHUNK) mini-batch updates; the permutations are drawn by the same calls in the same order, so both routes see the same
+        mini-batches for one generator state."""
         from ..engine import ops
         maps = shot_maps.detach().float()
         E, way, shot, N, Cc = maps.shape
@@ -131,6 +151,25 @@ class DeepEMD(nn.Module):
         support = maps.permute(0, 2, 1, 3, 4).reshape(E, n, N, Cc)             # index s * way + c
         label = torch.arange(way, device=dev).repeat(shot)
         sfc = maps.mean(dim=2).contiguous()
+        if (self.sfc_fused if fused is None else fused):
+            if perms is not None:
+                drawn = [torch.as_tensor(perms[k]).cpu() for k in range(self.sfc_update_step)]
+                drawn = [p.expand(E, n) if p.dim() == 1 else p for p in drawn]
+            else:
+                drawn = [torch.stack([torch.randperm(n, generator=generator) for _ in range(E)]).cpu() for _ in range(self.sfc_update_step)]
+            if not drawn:
+                return sfc
+            table = sfc_step_table(torch.stack(drawn), self.sfc_bs)
+            chunk = SFC_CHUNK if chunk is None else int(chunk)
+            if chunk < 1:
+                raise ValueError('chunk must be at least 1')
+            support = support.contiguous()
+            buf = count = None
+            for i in range(0, table.shape[0], chunk):
+                sfc, buf, count = ops.emd_sfc_steps(support, label, table[i:i + chunk], sfc, buf, count, temperature=self.temperature, lr=self.sfc_lr,
+                                                    momentum=0.9, dampening=0.9, first=i == 0)
+            self.add_status(count)
+            return sfc
         buf = None
         rows = torch.arange(E, device=dev)[:, None]
         eye = torch.eye(way, device=dev)

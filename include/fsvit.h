@@ -675,6 +675,23 @@ int fsvit_emd_head_backward(const float* shot_tok_dev, const float* query_tok_de
 int fsvit_op_emd_solve(const float* cost_dev, const float* w1_dev, const float* w2_dev, int B, int N, float* flow_dev, int* status_dev, void* stream);
 int fsvit_op_emd_solve_counts(const float* cost_dev, const float* w1_dev, const float* w2_dev, int B, int N, float* flow_dev, int* status_dev,
                               int* n_augment_dev, void* stream);
+/* The 5-shot structured-FC fine-tune (Network.py:83-107, get_sfc) kept on the device: one workgroup per episode runs n_steps consecutive mini-batch
+ * updates of sfc [E][way][N][C] (in / out; the caller initialises it with the shot mean) against the support maps support [E][n][N][C] (n = way * shot
+ * images, label [n] their classes).  ids [n_steps][E][bs] holds the support images of every mini-batch: an index in [0, n), or -1 for an empty slot
+ * (a partial last batch); a slot outside [0, n) is skipped and never used as an address.  Per step: the head's forward of every (slot, class) pair
+ * (the arithmetic of fsvit_emd_head_forward with the mini-batch as the queries), dlogits = (softmax - onehot(label)) / (slots in use), the head's
+ * backward onto sfc with the flows as constants, then torch.optim.SGD's update: buf = grad on the first update of a fine-tune (`first` != 0 and
+ * step 0 of this call), else buf = momentum * buf + (1 - dampening) * grad; sfc -= lr * buf.  buf [E][way][N][C] in / out.  sfc and buf persist
+ * between calls, so a fine-tune may be cut into several calls (first = 0 from the second on) with identical results.  status_count [E] in / out:
+ * the number of problems that reached a loop bound of the solver is ADDED.  No atomics, deterministic.  workspace:
+ * fsvit_emd_sfc_workspace_bytes (0 for a refused shape).  Refused with FSVIT_ERR_ARG and a message, nothing launched: a null pointer, N < 1 or
+ * N > 32, C not a positive multiple of 64, way / n / bs < 1, n_steps < 0, E < 0 or E > 65535, shapes whose workspace per episode exceeds 2^31 - 1
+ * floats, a temperature / lr / momentum / dampening that is not finite; FSVIT_ERR_WORKSPACE for a workspace that is too small.  n_steps = 0 or E = 0
+ * is a no-op. */
+size_t fsvit_emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C);
+int fsvit_emd_sfc_steps(const float* support_dev, const int* label_dev, const int* ids_dev, int n_steps, int first, int E, int way, int n, int bs, int N,
+                        int C, float temperature, float lr, float momentum, float dampening, float* sfc_dev, float* buf_dev, int* status_count_dev,
+                        void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------- episode sampler (host only, no GPU)
  * The draws of `CategoriesSampler.__iter__` (test_phase/datasets/samplers.py:19-35) replayed natively on the legacy numpy generator state: per episode

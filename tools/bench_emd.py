@@ -4,9 +4,13 @@ episodes with the procedural checkpoint.  Prints one JSON line per figure:
     float64 HiGHS oracle's CPU time on a sample of the same problems (an oracle, not the reference's cv2.EMD);
   * episodes/s of the whole DeepEMD eval step (encoder + head);
   * episodes/s of the 5-shot SFC path at the reference's eval settings (sfc_lr 100, 100 update steps, mini-batches of 4) on the token maps;
+  * with --sfc-fused, that 5-shot leg both ways in this process - the host loop and the on-device loop (DeepEMD.get_sfc(fused=True), emd_sfc_kernel) -
+    at --sfc-episodes and at --sfc-episodes-large, and the arg-max agreement of the two routes' final logits on the same permutations (reported, not
+    asserted: at sfc_lr 100 the two trajectories need not agree to rounding);
   * the histogram of augmenting paths per problem.
 Every GPU figure: --warmup untimed runs, then the median of --steps runs timed with HIP events.
-Usage: python tools/bench_emd.py [--episodes 1,16,64] [--steps 10] [--warmup 3] [--numerics bf16] [--sfc-episodes 16] [--sfc-steps 100] [--oracle-problems 40]"""
+Usage: python tools/bench_emd.py [--episodes 1,16,64] [--steps 10] [--warmup 3] [--numerics bf16] [--sfc-episodes 16] [--sfc-steps 100] [--oracle-problems 40]
+                                 [--sfc-fused [--sfc-episodes-large 64]]"""
 import argparse
 import json
 import os
@@ -61,6 +65,8 @@ def main():
     ap.add_argument('--sfc-episodes', type=int, default=16)
     ap.add_argument('--sfc-steps', type=int, default=100)
     ap.add_argument('--oracle-problems', type=int, default=40)
+    ap.add_argument('--sfc-fused', action='store_true')
+    ap.add_argument('--sfc-episodes-large', type=int, default=64)
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     name = torch.cuda.get_device_name(dev)
@@ -69,7 +75,8 @@ def main():
     m.load_state_dict(synthetic.synthetic_checkpoint_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}))
     m = m.to(dev).eval()
     sizes = [int(e) for e in args.episodes.split(',')]
-    E_max = max(sizes + [args.sfc_episodes])
+    sfc_sizes = [args.sfc_episodes, args.sfc_episodes_large] if args.sfc_fused else [args.sfc_episodes]
+    E_max = max(sizes + sfc_sizes)
     x5 = synthetic.synthetic_episodes(0, E_max, WAY, 5, QUERY).to(dev)
     xs5, xq = fs.split_shot_query(x5, WAY, 5, QUERY, ep_per_batch=E_max)
     with torch.no_grad():
@@ -121,15 +128,32 @@ def main():
         print(json.dumps({'metric': 'deepemd_eval_step_1shot_episodes_per_s', 'numerics': args.numerics, 'episodes_per_launch': E, 'value': round(E / (med * 1e-3), 1),
                           'unit': 'episodes/s', 'ms_per_launch': round(med, 3), 'min_ms': round(lo, 3), 'max_ms': round(hi, 3), 'samples': args.steps, 'device': name}))
 
-    # 3. the 5-shot SFC path on the token maps: get_sfc (sfc_update_step x ceil(25 / 4) head forward + backward pairs) + the final head
-    E = args.sfc_episodes
-    s5, q = shot5_tok[:E].contiguous(), query_tok[:E].contiguous()
-    g = torch.Generator().manual_seed(0)
-    med, lo, hi = timed(lambda: m.emd_forward(m.get_sfc(s5, generator=g), q), 1, max(3, args.steps // 3))
-    m.check_status()
-    print(json.dumps({'metric': 'deepemd_5shot_sfc_episodes_per_s', 'episodes_per_launch': E, 'sfc_update_step': args.sfc_steps, 'sfc_bs': 4, 'sfc_lr': 100.0,
-                      'value': round(E / (med * 1e-3), 2), 'unit': 'episodes/s', 'ms_per_launch': round(med, 1), 'min_ms': round(lo, 1), 'max_ms': round(hi, 1),
-                      'device': name}))
+    # 3. the 5-shot SFC path on the token maps: get_sfc (sfc_update_step x ceil(25 / 4) head forward + backward pairs, or the same mini-batch updates
+    # in launches of the fused kernel) + the final head
+    from fewshot_vit_amd.models.deepemd import SFC_CHUNK
+    for E in sfc_sizes:
+        s5, q = shot5_tok[:E].contiguous(), query_tok[:E].contiguous()
+        final = {}
+        for fused in ((False, True) if args.sfc_fused else (False,)):
+            g = torch.Generator().manual_seed(0)
+            med, lo, hi = timed(lambda: m.emd_forward(m.get_sfc(s5, generator=g, fused=fused), q), 1, max(3, args.steps // 3))
+            m.check_status()
+            rec = {'metric': 'deepemd_5shot_sfc_fused_episodes_per_s' if fused else 'deepemd_5shot_sfc_episodes_per_s', 'episodes_per_launch': E,
+                   'sfc_update_step': args.sfc_steps, 'sfc_bs': 4, 'sfc_lr': 100.0, 'value': round(E / (med * 1e-3), 2), 'unit': 'episodes/s',
+                   'ms_per_launch': round(med, 1), 'min_ms': round(lo, 1), 'max_ms': round(hi, 1), 'device': name}
+            if fused:
+                updates = args.sfc_steps * ((WAY * 5 + 3) // 4)
+                launches = (updates + SFC_CHUNK - 1) // SFC_CHUNK
+                rec.update({'updates_per_kernel_launch': SFC_CHUNK, 'kernel_launches': launches, 'ms_per_kernel_launch_at_most': round(med / launches, 1)})
+            print(json.dumps(rec))
+            if args.sfc_fused:
+                final[fused] = m.emd_forward(m.get_sfc(s5, generator=torch.Generator().manual_seed(1), fused=fused), q)
+                m.check_status()
+        if args.sfc_fused:
+            same = (final[True].argmax(-1) == final[False].argmax(-1)).float().mean().item()
+            print(json.dumps({'metric': 'deepemd_5shot_sfc_fused_vs_unfused_argmax_agreement', 'episodes': E, 'queries': int(final[True].shape[0] * final[True].shape[1]),
+                              'value': round(same, 4), 'max_abs_logit_difference': round((final[True] - final[False]).abs().max().item(), 4),
+                              'note': 'same permutations on both routes; reported, not asserted'}))
 
 
 if __name__ == '__main__':
