@@ -1006,6 +1006,52 @@ extern "C" int fsvit_proto_head_devtemp(const float* fs, const float* fq, int E,
   return 0;
 }
 
+// ---- prototype bank (proto_bank.hip): limits as fsvit.h states them
+static int proto_bank_dims(const char* what, int way, int D) {
+  if (way < 1 || way > 65536) return fail(FSVIT_ERR_ARG, "%s: way = %d is outside [1, 65536]", what, way);
+  if (D < 1 || D > 8192) return fail(FSVIT_ERR_ARG, "%s: D = %d is outside [1, 8192]", what, D);
+  return 0;
+}
+
+extern "C" int fsvit_proto_bank_accumulate(const float* feat, const void* label, int label_is_int64, int S, int way, int D, float* sum, int* count,
+                                           int* invalid, void* stream) {
+  if (!feat || !label || !sum || !count || !invalid) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_accumulate: null argument");
+  if (S < 0) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_accumulate: S = %d", S);
+  RC_TRY(proto_bank_dims("fsvit_proto_bank_accumulate", way, D));
+  RC_TRY(fsvit::launch_proto_bank_accumulate(feat, label, label_is_int64, S, way, D, sum, count, invalid, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_proto_bank_finalize(const float* sum, const int* count, int way, int D, int method, float* proto, int* empty, void* stream) {
+  if (!sum || !count || !proto || !empty) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_finalize: null argument");
+  if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
+  RC_TRY(proto_bank_dims("fsvit_proto_bank_finalize", way, D));
+  RC_TRY(fsvit::launch_proto_bank_finalize(sum, count, way, D, method, proto, empty, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_proto_bank_logits(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev,
+                                       int method, float* logits, int* pred, void* stream) {
+  if (!query || !proto || !logits) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_logits: null argument");
+  if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
+  if (Q < 0) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_logits: Q = %d", Q);
+  RC_TRY(proto_bank_dims("fsvit_proto_bank_logits", way, D));
+  if (D % 4) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_logits: D = %d is not a multiple of 4", D);
+  if (((uintptr_t)query | (uintptr_t)proto) & 15) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_logits: query / proto must be 16-byte aligned");
+  if (!temp_dev && !std::isfinite(temp)) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_logits: the temperature is not finite");
+  RC_TRY(fsvit::launch_proto_bank_logits(query, proto, empty, Q, way, D, temp_dev ? 0.f : temp, temp_dev, method, logits, pred, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int fsvit_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, void* stream) {
+  if (!feat_shot || !feat_query || !auc) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc: null argument");
+  if (E < 0 || shot < 1) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc: E = %d, shot = %d", E, shot);
+  if (Q < 2 || Q > 4096 || Q % 2) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc: Q = %d must be even and in [2, 4096] (positives first, as many negatives)", Q);
+  RC_TRY(proto_bank_dims("fsvit_proto_auc", 1, D));
+  RC_TRY(fsvit::launch_proto_auc(feat_shot, feat_query, E, shot, Q, D, auc, score, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int fsvit_meta_baseline_forward(void* hv, const float* x_shot, const float* x_query, int E, int way,
                                            int shot, int Q, int img_h, int img_w, float temp, int method, float* logits,
                                            float* acc, float* loss, float* feat, void* ws, size_t ws_bytes, void* stream) {

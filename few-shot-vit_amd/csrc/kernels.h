@@ -19,6 +19,13 @@ int launch_proto_head(const float* feat_shot, const float* feat_query, int E, in
                       float temp, int method, float* logits, float* acc, float* loss, hipStream_t s, const float* temp_dev = nullptr);
 int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const long long* labels, int E, int way, int shot, int Q, int D, float temp, int method,
                          float* logits, float* acc, float* loss, float* dlogits, float* mean_out, unsigned* ticket, hipStream_t s, const float* temp_dev = nullptr);
+// prototype bank over a labelled support set and the single-prototype ROC-AUC of --sauc (proto_bank.hip); limits: the fsvit_proto_bank_* entries of fsvit.h
+int launch_proto_bank_accumulate(const float* feat, const void* label, int label_is_int64, int S, int way, int D, float* sum, int* count, int* invalid,
+                                 hipStream_t s);
+int launch_proto_bank_finalize(const float* sum, const int* count, int way, int D, int method, float* proto, int* empty, hipStream_t s);
+int launch_proto_bank_logits(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev, int method,
+                             float* logits, int* pred, hipStream_t s);
+int launch_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, hipStream_t s);
 // distillation head (token_label.hip): LinearClassifier forward / backward, generate_softlabel, SoftTargetCrossEntropy, F.normalize on rows
 int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s);
 int launch_linear_bwd(const float* dy, const float* x, const float* w, float* dx, int accumulate_dx, float* dw, float* db, int M, int N, int K, hipStream_t s);

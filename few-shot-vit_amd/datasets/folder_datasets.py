@@ -68,9 +68,6 @@ class ImageFolder:
     def __init__(self, root_path, image_size=224, box_size=256, device=None, **kwargs):
         if kwargs.get('augment'):
             raise NotImplementedError('fsvit: only the eval transform (no augment) is built')
-        if box_size is None:
-            box_size = image_size
-        self.image_size, self.box_size = int(image_size), int(box_size)
         classes = sorted(os.listdir(root_path))
         if kwargs.get('split'):
             path = kwargs.get('split_file')
@@ -78,19 +75,35 @@ class ImageFolder:
                 path = os.path.join(os.path.dirname(root_path.rstrip('/')), 'split.json')
             with open(path, 'r') as f:
                 classes = sorted(json.load(f)[kwargs['split']])
-        self.filepaths, self.label = [], []
+        filepaths, label = [], []
         for i, c in enumerate(classes):
             for filename in sorted(os.listdir(os.path.join(root_path, c))):
-                self.filepaths.append(os.path.join(root_path, c, filename))
-                self.label.append(i)
-        self.n_classes = max(self.label) + 1
+                filepaths.append(os.path.join(root_path, c, filename))
+                label.append(i)
+        if not label:
+            raise ValueError(f'image-folder: no images under {root_path}')
+        self._setup(filepaths, label, image_size, box_size, device, kwargs.get('cache_bytes', 8 << 30))
+
+    @classmethod
+    def from_files(cls, filepaths, label, image_size=224, box_size=256, device=None, cache_bytes=8 << 30):
+        """The same decoding, cache and on-device eval transform over an explicit file list (one label per file; the list may be empty)."""
+        self = cls.__new__(cls)
+        self._setup(list(filepaths), list(label), image_size, box_size, device, cache_bytes)
+        return self
+
+    def _setup(self, filepaths, label, image_size, box_size, device, cache_bytes):
+        if box_size is None:
+            box_size = image_size
+        self.image_size, self.box_size = int(image_size), int(box_size)
+        self.filepaths, self.label = filepaths, label
+        self.n_classes = max(self.label) + 1 if self.label else 0
         self.device = torch.device(device if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu'))
         # decoded-image cache, bounded in bytes (LRU): a tieredImageNet-sized split at 224 px is 150 KB per image - 30 ... 67 GB if every
         # image ever touched stayed resident, per rank.  `cache_bytes` (default 8 GiB; 0 disables) caps it.
         from collections import OrderedDict
         self._cache = OrderedDict()
         self._cache_bytes = 0
-        self._cache_limit = int(kwargs.get('cache_bytes', 8 << 30))
+        self._cache_limit = int(cache_bytes)
         self._mean = torch.tensor(IMAGENET_MEAN).view(1, 3, 1, 1)
         self._std = torch.tensor(IMAGENET_STD).view(1, 3, 1, 1)
 

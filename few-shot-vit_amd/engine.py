@@ -1087,6 +1087,94 @@ class ops:
                                                 shot, Q, D, float(temp), m, _ptr(logits), _ptr(acc), _ptr(loss), _stream_ptr(dev)))
         return logits, acc, loss
 
+    # ---- prototype bank over a labelled support set (proto_bank.hip; limits in fsvit.h) and the single-prototype ROC-AUC of --sauc
+    _HEAD_METHOD = {'cos': _lib.HEAD_COS, 'sqr': _lib.HEAD_SQR, 'dot': _lib.HEAD_DOT}
+
+    @staticmethod
+    def _bank_state(sum_, count, invalid, way, D):
+        for t, shape, dt in ((sum_, (way, D), torch.float32), (count, (way,), torch.int32), (invalid, (1,), torch.int32)):
+            if t is None:
+                continue
+            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f'bank state: expected a contiguous {dt} tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}')
+
+    @staticmethod
+    def proto_bank_accumulate(feat, labels, sum_, count, invalid):
+        """feat [S,D], labels [S] (int32 / int64) added into the bank state in place: sum_ [way,D] fp32, count [way] int32, invalid [1] int32 (the number of
+        labels outside [0, way); they add nothing else).  Rows of a class are added in ascending index on top of the stored sum."""
+        _require_cuda(feat, labels, sum_, count, invalid)
+        lib = _lib.load()
+        feat, = ops._head_in(feat)
+        if feat.dim() != 2 or sum_.dim() != 2:
+            raise ValueError('expected feat [S,D] and sum [way,D]')
+        way, D = sum_.shape
+        ops._bank_state(sum_, count, invalid, way, D)
+        if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != feat.shape[0] or feat.shape[1] != D:
+            raise ValueError('expected labels [S] int32 / int64 for feat [S,D] and sum [way,D]')
+        labels = labels.contiguous()
+        with torch.cuda.device(feat.device):
+            _lib.check(lib.fsvit_proto_bank_accumulate(_ptr(feat), _ptr(labels), int(labels.dtype == torch.int64), feat.shape[0], way, D, _ptr(sum_),
+                                                       _ptr(count), _ptr(invalid), _stream_ptr(feat.device)))
+
+    @staticmethod
+    def proto_bank_finalize(sum_, count, method='cos'):
+        """-> proto [way,D] fp32 (the class means; 'cos': F.normalize of them), empty [way] int32 (1 where count == 0: zero prototype)."""
+        _require_cuda(sum_, count)
+        lib = _lib.load()
+        if sum_.dim() != 2:
+            raise ValueError('expected sum [way,D]')
+        way, D = sum_.shape
+        ops._bank_state(sum_, count, None, way, D)
+        proto = torch.empty(way, D, dtype=torch.float32, device=sum_.device)
+        empty = torch.empty(way, dtype=torch.int32, device=sum_.device)
+        with torch.cuda.device(sum_.device):
+            _lib.check(lib.fsvit_proto_bank_finalize(_ptr(sum_), _ptr(count), way, D, ops._HEAD_METHOD[method], _ptr(proto), _ptr(empty),
+                                                     _stream_ptr(sum_.device)))
+        return proto, empty
+
+    @staticmethod
+    def proto_bank_logits(query, proto, empty, temp, method='cos', want_pred=True):
+        """query [Q,D], proto [way,D] / empty [way] of proto_bank_finalize (empty None: no class is) -> logits [Q,way] fp32, pred [Q] int32 (the first
+        maximum; None without want_pred).  temp: a Python number or a device scalar read where it lives."""
+        _require_cuda(query, proto, empty)
+        lib = _lib.load()
+        query, proto = ops._head_in(query, proto)
+        if query.dim() != 2 or proto.dim() != 2 or query.shape[1] != proto.shape[1]:
+            raise ValueError('expected query [Q,D] and proto [way,D]')
+        Q, D = query.shape
+        way = proto.shape[0]
+        if empty is not None:
+            if empty.dtype != torch.int32 or tuple(empty.shape) != (way,):
+                raise ValueError('empty: int32 [way]')
+            empty = empty.contiguous()
+        dev = query.device
+        logits = torch.empty(Q, way, dtype=torch.float32, device=dev)
+        pred = torch.empty(Q, dtype=torch.int32, device=dev) if want_pred else None
+        dev_temp = isinstance(temp, torch.Tensor) and temp.is_cuda
+        temp_d = ops._head_in(temp)[0] if dev_temp else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_proto_bank_logits(_ptr(query), _ptr(proto), _ptr(empty), Q, way, D, 0.0 if dev_temp else float(temp), _ptr(temp_d),
+                                                   ops._HEAD_METHOD[method], _ptr(logits), _ptr(pred), _stream_ptr(dev)))
+        return logits, pred
+
+    @staticmethod
+    def proto_auc(feat_shot, feat_query, want_score=False):
+        """feat_shot [E,shot,D] (the shots of class 0), feat_query [E,Q,D] with the first Q / 2 queries positive -> auc [E] fp32: roc_auc_score of the cosine
+        scores against the normalised mean shot (test_few_shot.py --sauc); with want_score also score [E,Q]."""
+        _require_cuda(feat_shot, feat_query)
+        lib = _lib.load()
+        feat_shot, feat_query = ops._head_in(feat_shot, feat_query)
+        if feat_shot.dim() != 3 or feat_query.dim() != 3 or feat_shot.shape[0] != feat_query.shape[0] or feat_shot.shape[2] != feat_query.shape[2]:
+            raise ValueError('expected feat_shot [E,shot,D] and feat_query [E,Q,D]')
+        E, shot, D = feat_shot.shape
+        Q = feat_query.shape[1]
+        dev = feat_shot.device
+        auc = torch.empty(E, dtype=torch.float32, device=dev)
+        score = torch.empty(E, Q, dtype=torch.float32, device=dev) if want_score else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_proto_auc(_ptr(feat_shot), _ptr(feat_query), E, shot, Q, D, _ptr(auc), _ptr(score), _stream_ptr(dev)))
+        return (auc, score) if want_score else auc
+
     # ---- operator entry points of the memory-bound training kernels (fsvit_op_*: tests, tools).  Maps are [M, C] / NHWC tensors in the storage
     # dtype (fp32 or bf16), statistics / parameters fp32; outputs and the kernels' `partial` scratch are allocated here.
     @staticmethod

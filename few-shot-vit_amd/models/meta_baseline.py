@@ -63,6 +63,43 @@ class MetaBaseline(nn.Module):
             raise ValueError(self.method)
         return self._forward_train(x_shot, x_query, label)
 
+    # ---- a labelled support set of any shape: encode once into a PrototypeBank, query many times (eval mode only)
+    def _encode_eval(self, x, what):
+        if self.training:
+            raise RuntimeError(f'MetaBaseline.{what} is an eval-mode entry: call model.eval() first')
+        if self.method not in ('cos', 'sqr'):
+            raise ValueError(self.method)
+        if x.dim() != 4:
+            raise ValueError(f'{what}: expected images [N,3,H,W]')
+        if not x.is_cuda:
+            raise RuntimeError('fsvit: MetaBaseline.%s got images on %s; the HIP engine needs an MI355X (no CPU fallback)' % (what, x.device))
+        # the engine's own chunks; its output is the pooled feature also for encoders whose module forward returns (map, feat)
+        return self.encoder.engine().forward(x)
+
+    def fit(self, x_support, y_support, n_classes=None, bank=None):
+        """x_support [S,3,H,W], y_support [S] integer labels -> PrototypeBank holding them.  `bank`: extend this one instead of making one; otherwise
+        `n_classes` (None: int(y_support.max()) + 1, one device read) sizes a new bank with the model's method."""
+        from .proto_bank import PrototypeBank
+        feat = self._encode_eval(x_support, 'fit')
+        y = y_support.to(feat.device)
+        if y.dim() != 1 or y.shape[0] != feat.shape[0]:
+            raise ValueError('fit: expected one label per support image')
+        if bank is None:
+            if n_classes is None:
+                n_classes = int(y.max()) + 1
+            bank = PrototypeBank(n_classes, feat.shape[1], self.method, feat.device)
+        elif bank.method != self.method or bank.dim != feat.shape[1]:
+            raise ValueError(f'fit: the bank is {bank.method!r} x {bank.dim}, the model {self.method!r} x {feat.shape[1]}')
+        return bank.add(feat, y)
+
+    def predict(self, bank, x_query):
+        """x_query [Q,3,H,W] -> logits [Q, bank.n_classes] with the model's temperature (read on the device when it is a parameter) and method"""
+        feat = self._encode_eval(x_query, 'predict')
+        if bank.method != self.method:
+            raise ValueError(f'predict: the bank was built for {bank.method!r}, the model scores with {self.method!r}')
+        temp = self.temp.detach() if isinstance(self.temp, torch.Tensor) else float(self.temp)
+        return bank.logits(feat, temp)
+
     def _forward_eval(self, x_shot, x_query):
         engine = self.encoder.engine()
         temp = float(self.temp.detach()) if isinstance(self.temp, torch.Tensor) else float(self.temp)

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Classify your own images with a trained checkpoint: a labelled support folder becomes a PrototypeBank, a query folder is scored against it.
+
+  python -m fewshot_vit_amd.predict --load ckpt.pth --support support/ --query query/ --out preds.csv
+
+`--support DIR` holds one sub-folder per class with any number of images each; classes are numbered in sorted folder order.  `--query DIR` is a
+flat folder of images or class sub-folders of the same names (then the accuracy is printed).  Images are decoded and transformed as by the
+'image-folder' dataset (Resize(box) -> CenterCrop(size) with Pillow, normalisation on the device).  `--save-bank F` stores the bank (class sums,
+counts, method, class names); `--load-bank F` restores one, and together with `--support` extends it with further examples of the same classes
+without re-encoding the earlier ones.  The CSV has one row per query image: file, pred_class (the class number), logit_0 .. logit_{way-1}."""
+import argparse
+import csv
+import os
+
+import torch
+
+from . import models
+from .datasets.folder_datasets import ImageFolder
+from .models.proto_bank import PrototypeBank
+
+
+def _listdir(path):
+    return sorted(n for n in os.listdir(path) if not n.startswith('.'))
+
+
+def class_folders(root):
+    """sorted sub-folder names of root ([] when it is a flat folder of files)"""
+    return [n for n in _listdir(root) if os.path.isdir(os.path.join(root, n))]
+
+
+def list_labelled(root, classes):
+    """-> (paths, labels) of root/<class>/<file> with labels indexing `classes`; a folder that is not in `classes` is an error"""
+    paths, labels = [], []
+    for c in class_folders(root):
+        if c not in classes:
+            raise ValueError(f'{root}: class folder {c!r} is not one of the bank\'s classes {classes}')
+        for n in _listdir(os.path.join(root, c)):
+            paths.append(os.path.join(root, c, n))
+            labels.append(classes.index(c))
+    return paths, labels
+
+
+def encode_files(model, paths, image_size, box_size, device, batch=1024):
+    """features [len(paths), out_dim] of the files through the eval engine, `batch` images decoded and uploaded at a time"""
+    ds = ImageFolder.from_files(paths, [0] * len(paths), image_size, box_size, device, cache_bytes=0)      # every file is read once
+    engine = model.encoder.engine()
+    out = torch.empty(len(paths), engine.out_dim, dtype=torch.float32, device=device)
+    for i in range(0, len(paths), batch):
+        engine.forward(ds.gather(list(range(i, min(i + batch, len(paths))))), out=out[i:i + batch])
+    return out
+
+
+def load_model(path, method=None, numerics=None):
+    model = models.load(torch.load(path, map_location='cpu'))
+    if method is not None:
+        model.method = method
+    if numerics is not None:
+        model.encoder.numerics = numerics
+    return model
+
+
+def make_parser():
+    p = argparse.ArgumentParser(prog='python -m fewshot_vit_amd.predict', description=__doc__.split('\n\n')[0])
+    p.add_argument('--load', required=True, metavar='CKPT', help="a 'meta-baseline' checkpoint (the training drivers' schema)")
+    p.add_argument('--support', metavar='DIR', help='labelled support set: one sub-folder per class')
+    p.add_argument('--query', metavar='DIR', help='images to classify: a flat folder, or class sub-folders (prints the accuracy)')
+    p.add_argument('--method', choices=['cos', 'sqr'], default=None, help="default: the checkpoint's")
+    p.add_argument('--numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'], help="default: FSVIT_NUMERICS or 'bf16'")
+    p.add_argument('--out', metavar='preds.csv', help='file,pred_class,logit_0.. per query image')
+    p.add_argument('--save-bank', metavar='F', help='store the prototype bank after --support was added')
+    p.add_argument('--load-bank', metavar='F', help='start from a stored bank; with --support: extend it')
+    p.add_argument('--image-size', type=int, default=None, help="default: the encoder's input size")
+    p.add_argument('--box-size', type=int, default=None, help='Resize target before the centre crop (default: image size * 8 / 7, the 256 -> 224 ratio)')
+    return p
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
+    if not args.support and not args.load_bank:
+        raise SystemExit('predict: give --support DIR, --load-bank F or both')
+    if not torch.cuda.is_available():
+        raise RuntimeError('fsvit: predict needs an MI355X (no CPU fallback)')
+    device = torch.device('cuda', torch.cuda.current_device())
+    model = load_model(args.load, args.method, args.numerics).to(device).eval()
+    size = args.image_size or model.encoder.cfg['img_size']
+    box = args.box_size or (size * 8) // 7
+    bank, classes = None, None
+    if args.load_bank:
+        saved = torch.load(args.load_bank, map_location='cpu')
+        classes = list(saved['classes'])
+        bank = PrototypeBank.from_state_dict(saved['bank'], device)
+        if bank.method != model.method:
+            raise ValueError(f'{args.load_bank} was built for {bank.method!r}, the model scores with {model.method!r}')
+    if args.support:
+        if classes is None:
+            classes = class_folders(args.support)
+            if not classes:
+                raise ValueError(f'{args.support}: no class sub-folders')
+        paths, labels = list_labelled(args.support, classes)
+        feat = encode_files(model, paths, size, box, device)
+        if bank is None:
+            bank = PrototypeBank(len(classes), feat.shape[1], model.method, device)
+        bank.add(feat, torch.tensor(labels, dtype=torch.int64, device=device)).check()
+    print('bank: {} classes, {} support images ({})'.format(len(classes), int(bank.counts.sum()), bank.method))
+    if args.save_bank:
+        torch.save({'bank': {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in bank.state_dict().items()}, 'classes': classes}, args.save_bank)
+    out = {'bank': bank, 'classes': classes}
+    if args.query:
+        sub = class_folders(args.query)
+        if sub:
+            paths, truth = list_labelled(args.query, classes)
+        else:
+            paths, truth = [os.path.join(args.query, n) for n in _listdir(args.query)], None
+        feat = encode_files(model, paths, size, box, device)
+        temp = model.temp.detach() if isinstance(model.temp, torch.Tensor) else float(model.temp)
+        pred, logits = bank.predict(feat, temp)
+        pred, logits = pred.cpu(), logits.cpu()
+        out.update(files=paths, pred=pred, logits=logits)
+        if truth is not None:
+            out['acc'] = float((pred == torch.tensor(truth)).double().mean()) if paths else float('nan')
+            print('accuracy: {:.2f} % over {} images'.format(out['acc'] * 100, len(paths)))
+        if args.out:
+            with open(args.out, 'w', newline='') as f:
+                w = csv.writer(f)
+                w.writerow(['file', 'pred_class'] + [f'logit_{c}' for c in range(len(classes))])
+                for p, c, row in zip(paths, pred.tolist(), logits.tolist()):
+                    w.writerow([p, c] + [repr(v) for v in row])
+    return out
+
+
+if __name__ == '__main__':
+    main()

@@ -186,6 +186,31 @@ int fsvit_meta_baseline_forward(void* encoder /* fsvit_visformer*, fsvit_vit* or
                                 float* logits_dev, float* acc_dev, float* loss_dev, float* feat_dev,
                                 void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- prototype bank: a labelled support set, encoded once and queried many times
+ * The head above re-forms the prototypes of one rectangular episode on every call.  These four entries serve a support set with any number of
+ * examples per class, filled in any number of calls, and any number of classes (proto_bank.hip).  All tensors fp32 and dense; `method` as above.
+ * Shared refusals (FSVIT_ERR_ARG, nothing launched): a NULL pointer that is not marked optional, way < 1 or way > 65536, D < 1 or D > 8192.
+ *
+ * Accumulate: feat_dev [S,D], label_dev [S] (int64 when label_is_int64, else int32) -> sum_dev [way,D] +=, count_dev [way] +=, *invalid_dev += the number
+ * of labels outside [0, way), which contribute nothing else.  The caller zeroes the three outputs once.  A class's rows are added in ascending support
+ * index on top of the stored sum: deterministic, and two calls over a split give the bits of one chain.  S == 0 is a no-op, S < 0 refused. */
+int fsvit_proto_bank_accumulate(const float* feat_dev, const void* label_dev, int label_is_int64, int S, int way, int D, float* sum_dev, int* count_dev,
+                                int* invalid_dev, void* stream);
+/* Finalize: proto_dev [way,D] = sum / count, for FSVIT_HEAD_COS followed by F.normalize with its 1e-12 clamp (meta_baseline.py:37-38);
+ * empty_dev [way] = 1 and a zero prototype row where count == 0, else 0. */
+int fsvit_proto_bank_finalize(const float* sum_dev, const int* count_dev, int way, int D, int method, float* proto_dev, int* empty_dev, void* stream);
+/* Logits: utils.compute_logits (utils/__init__.py:78-101) of query_dev [Q,D] against proto_dev [way,D] as fsvit_proto_bank_finalize wrote it ->
+ * logits_dev [Q,way]; COS normalises the query rows (1e-12 clamp), SQR is the negative squared distance, DOT the plain product, each times the
+ * temperature: *temp_dev (device) when temp_dev != NULL, else `temp`, which must be finite.  The device value is not checked (reading it would be a host
+ * synchronisation): a NaN or inf there goes into the logits, as with fsvit_proto_head_devtemp.  Classes flagged in empty_dev (NULL = none) score -inf.
+ * pred_dev [Q] (optional) = the first maximum of each row.  Limits: D a multiple of 4, query_dev and proto_dev 16-byte aligned.  Q == 0 is a no-op. */
+int fsvit_proto_bank_logits(const float* query_dev, const float* proto_dev, const int* empty_dev, int Q, int way, int D, float temp, const float* temp_dev,
+                            int method, float* logits_dev, int* pred_dev, void* stream);
+/* `--sauc` of the reference's test_few_shot.py (meta_tuning_sun_m/test_few_shot.py:95-112): feat_shot_dev [E,shot,D] (the shots of class 0),
+ * feat_query_dev [E,Q,D], the first Q / 2 queries positive -> auc_dev [E] = roc_auc_score of the cosine scores against the normalised mean shot
+ * = (#{pos > neg} + #{pos == neg} / 2) / (Q / 2)^2; score_dev [E,Q] optional.  Limits: shot >= 1, Q even, 2 <= Q <= 4096.  E == 0 is a no-op. */
+int fsvit_proto_auc(const float* feat_shot_dev, const float* feat_query_dev, int E, int shot, int Q, int D, float* auc_dev, float* score_dev, void* stream);
+
 /* ---------------------------------------------------------------- operator level (tests, reuse)
  * Implicit-GEMM conv with fused epilogue; see few-shot-vit_amd/csrc/conv_gemm.h for the layout.
  * x NHWC [B,H,W,x_cstride]; w [groups][N][Kw] K-major (ky,kx,c); y NHWC [B,OH,OW,y_cstride]. */

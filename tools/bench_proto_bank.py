@@ -1,0 +1,80 @@
+"""Prototype bank (csrc/proto_bank.hip) on one MI355X: the share of a `MetaBaseline.predict` call that the logits kernel takes.
+Prints one JSON line per figure:
+  * proto_bank_logits at Q queries of D = 512 against `way` prototypes, per method, with the FMA rate it amounts to;
+  * proto_bank_accumulate + finalize of a support set of --support rows into the same number of classes;
+  * the encoder forward (visformer_micro_80, procedural checkpoint) of the same Q images, the other part of the predict call.
+Every figure: --warmup untimed runs, then the median of --steps runs timed with HIP events.
+Usage: python tools/bench_proto_bank.py [--queries 12800] [--ways 64,1024] [--dim 512] [--support 5120] [--steps 20] [--warmup 3] [--numerics bf16] [--no-encoder]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from fewshot_vit_amd import models, synthetic     # noqa: E402
+from fewshot_vit_amd.engine import ops            # noqa: E402
+
+
+def timed(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    ms = []
+    for _ in range(steps):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        fn()
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--queries', type=int, default=12800)
+    ap.add_argument('--ways', default='64,1024')
+    ap.add_argument('--dim', type=int, default=512)
+    ap.add_argument('--support', type=int, default=5120)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--numerics', default='bf16')
+    ap.add_argument('--no-encoder', action='store_true')
+    args = ap.parse_args()
+    dev = torch.device('cuda', 0)
+    name = torch.cuda.get_device_name(dev)
+    Q, D = args.queries, args.dim
+    g = torch.Generator().manual_seed(0)
+    query = torch.randn(Q, D, generator=g).to(dev)
+    for way in (int(w) for w in args.ways.split(',')):
+        feat = torch.randn(args.support, D, generator=g).to(dev)
+        labels = torch.randint(0, way, (args.support,), generator=g).to(dev)
+        s = torch.zeros(way, D, dtype=torch.float32, device=dev)
+        c = torch.zeros(way, dtype=torch.int32, device=dev)
+        inv = torch.zeros(1, dtype=torch.int32, device=dev)
+        med, lo, hi = timed(lambda: ops.proto_bank_accumulate(feat, labels, s, c, inv), args.warmup, args.steps)
+        fmed, _, _ = timed(lambda: ops.proto_bank_finalize(s, c, 'cos'), args.warmup, args.steps)
+        print(json.dumps({'metric': 'proto_bank_accumulate_ms', 'support': args.support, 'way': way, 'D': D, 'value': round(med, 4), 'min_ms': round(lo, 4),
+                          'max_ms': round(hi, 4), 'finalize_ms': round(fmed, 4), 'samples': args.steps, 'device': name}))
+        for method in ('cos', 'sqr'):
+            proto, empty = ops.proto_bank_finalize(s, c, method)
+            med, lo, hi = timed(lambda: ops.proto_bank_logits(query, proto, empty, 10.0, method), args.warmup, args.steps)
+            print(json.dumps({'metric': 'proto_bank_logits_ms', 'method': method, 'Q': Q, 'way': way, 'D': D, 'value': round(med, 4), 'min_ms': round(lo, 4),
+                              'max_ms': round(hi, 4), 'tfma_per_s': round(Q * way * D / (med * 1e-3) / 1e12, 2), 'samples': args.steps, 'device': name,
+                              'note': 'includes the wrapper (output allocation); fma = one q * p (cos) or (q - p)^2 (sqr) term'}))
+    if not args.no_encoder:
+        m = models.make('meta-baseline', encoder='visformer_micro_80', encoder_args={'numerics': args.numerics})
+        m.load_state_dict(synthetic.synthetic_checkpoint_sd({k: tuple(v.shape) for k, v in m.state_dict().items()}))
+        engine = m.to(dev).eval().encoder.engine()
+        x = torch.randn(Q, 3, 80, 80, generator=g).to(dev)
+        out = torch.empty(Q, engine.out_dim, dtype=torch.float32, device=dev)
+        med, lo, hi = timed(lambda: engine.forward(x, out=out), args.warmup, max(3, args.steps // 2))
+        print(json.dumps({'metric': 'encoder_forward_ms', 'encoder': 'visformer_micro_80', 'numerics': args.numerics, 'images': Q, 'value': round(med, 3),
+                          'min_ms': round(lo, 3), 'max_ms': round(hi, 3), 'device': name}))
+
+
+if __name__ == '__main__':
+    main()
