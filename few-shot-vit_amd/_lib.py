@@ -78,7 +78,9 @@ SIGNATURES = {
     'fsvit_proto_bank_accumulate': (_i, [_fp, _vp, _i, _i, _i, _i, _fp, _vp, _vp, _vp]),
     'fsvit_proto_bank_finalize': (_i, [_fp, _vp, _i, _i, _i, _fp, _vp, _vp]),
     'fsvit_proto_bank_logits': (_i, [_fp, _fp, _vp, _i, _i, _i, _f, _fp, _i, _fp, _vp, _vp]),
-    'fsvit_proto_auc': (_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _vp]),
+    'fsvit_proto_bank_topk_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'fsvit_proto_bank_topk': (_i, [_fp, _fp, _vp, _i, _i, _i, _f, _fp, _i, _i, _i, _fp, _vp, _fp, _vp, _sz, _vp]),
+    'fsvit_proto_auc':(_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _vp]),
     'fsvit_meta_baseline_forward': (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _i, _fp, _fp, _fp, _fp,
                                          _vp, _sz, _vp]),
     'fsvit_conv_gemm': (_i, [_vp, _vp, _fp, _vp, _fp, _vp] + [_i] * 15 + [_i, _vp]),

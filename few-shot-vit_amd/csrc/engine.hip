@@ -1043,6 +1043,46 @@ extern "C" int fsvit_proto_bank_logits(const float* query, const float* proto, c
   return 0;
 }
 
+// n_split of fsvit_proto_bank_topk when the caller passes 0 (the rule is stated in fsvit.h); 0 when the arguments admit none
+static int proto_bank_topk_split(int Q, int way, int n_split) {
+  if (Q < 0 || way < 1 || way > 65536 || n_split < 0) return 0;
+  const int n_seg = (way + 1023) / 1024;
+  if (n_split > n_seg) return 0;
+  if (n_split) return n_split;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  const int q_tiles = Q > 0 ? (Q + 63) / 64 : 1;
+  const int want = (cus + q_tiles - 1) / q_tiles;
+  return want < 1 ? 1 : (want > n_seg ? n_seg : want);
+}
+
+extern "C" size_t fsvit_proto_bank_topk_workspace_bytes(int Q, int way, int K, int n_split) {
+  const int ns = proto_bank_topk_split(Q, way, n_split);
+  if (!ns || K < 1 || K > 32) return 0;
+  return fsvit::proto_bank_topk_workspace_bytes(Q, way, K, ns);
+}
+
+extern "C" int fsvit_proto_bank_topk(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev,
+                                     int method, int K, int n_split, float* values, int* indices, float* lse, void* ws, size_t ws_bytes, void* stream) {
+  if (!query || !proto || !values || !indices) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: null argument");
+  if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
+  if (Q < 0) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: Q = %d", Q);
+  RC_TRY(proto_bank_dims("fsvit_proto_bank_topk", way, D));
+  if (D % 4) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: D = %d is not a multiple of 4", D);
+  if (((uintptr_t)query | (uintptr_t)proto) & 15) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: query / proto must be 16-byte aligned");
+  if (!temp_dev && !std::isfinite(temp)) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: the temperature is not finite");
+  if (K < 1 || K > 32) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: K = %d is outside [1, 32]", K);
+  const int ns = proto_bank_topk_split(Q, way, n_split);
+  if (!ns) return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: n_split = %d is outside [0, %d] (one split per 1024 classes at most)", n_split, (way + 1023) / 1024);
+  const size_t need = fsvit::proto_bank_topk_workspace_bytes(Q, way, K, ns);
+  if (Q == 0) return 0;                                        // nothing to score: the workspace of 0 bytes may be null
+  if (!ws || ((uintptr_t)ws & 3) || ws_bytes < need)
+    return fail(FSVIT_ERR_ARG, "fsvit_proto_bank_topk: the workspace is null, misaligned or smaller than the %zu bytes of fsvit_proto_bank_topk_workspace_bytes", need);
+  RC_TRY(fsvit::launch_proto_bank_topk(query, proto, empty, Q, way, D, temp_dev ? 0.f : temp, temp_dev, method, K, ns, values, indices, lse, ws,
+                                       (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int fsvit_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, void* stream) {
   if (!feat_shot || !feat_query || !auc) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc: null argument");
   if (E < 0 || shot < 1) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc: E = %d, shot = %d", E, shot);

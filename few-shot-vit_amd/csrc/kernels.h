@@ -25,6 +25,10 @@ int launch_proto_bank_accumulate(const float* feat, const void* label, int label
 int launch_proto_bank_finalize(const float* sum, const int* count, int way, int D, int method, float* proto, int* empty, hipStream_t s);
 int launch_proto_bank_logits(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev, int method,
                              float* logits, int* pred, hipStream_t s);
+// top-k + log-sum-exp per row on a (query tile, class split) grid; 1 <= K <= 32, 1 <= n_split <= ceil(way / 1024), workspace = proto_bank_topk_workspace_bytes
+size_t proto_bank_topk_workspace_bytes(int Q, int way, int K, int n_split);
+int launch_proto_bank_topk(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev, int method, int K,
+                           int n_split, float* values, int* indices, float* lse, void* ws, hipStream_t s);
 int launch_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, hipStream_t s);
 // distillation head (token_label.hip): LinearClassifier forward / backward, generate_softlabel, SoftTargetCrossEntropy, F.normalize on rows
 int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s);

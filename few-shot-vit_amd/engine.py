@@ -1158,6 +1158,48 @@ class ops:
         return logits, pred
 
     @staticmethod
+    def check_topk_k(k, what):
+        """the list length of proto_bank_topk: an int in [1, 32]; the argument alone decides, so callers check it before they look at a device"""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 32:
+            raise ValueError(f'{what}: k = {k!r} is outside [1, 32]')
+
+    @staticmethod
+    def proto_bank_topk(query, proto, empty, temp, method='cos', k=5, n_split=0, want_lse=True):
+        """The k best classes of every row of proto_bank_logits(query, proto, empty, temp, method) without the [Q,way] matrix -> (values [Q,k] fp32,
+        indices [Q,k] int32, lse [Q] fp32 or None): the head of a stable descending sort of the row (ties: the lower class; ranks beyond `way`: -inf, -1)
+        and the row's log-sum-exp over the non-empty classes.  1 <= k <= 32; n_split: how many workgroups share the class axis of a query tile
+        (0: chosen from Q, way and the CU count, fsvit.h) - the results do not depend on it."""
+        ops.check_topk_k(k, 'proto_bank_topk')
+        if isinstance(n_split, bool) or not isinstance(n_split, int) or n_split < 0:
+            raise ValueError(f'proto_bank_topk: n_split = {n_split!r} (0: the library chooses)')
+        _require_cuda(query, proto, empty)
+        lib = _lib.load()
+        query, proto = ops._head_in(query, proto)
+        if query.dim() != 2 or proto.dim() != 2 or query.shape[1] != proto.shape[1]:
+            raise ValueError('expected query [Q,D] and proto [way,D]')
+        Q, D = query.shape
+        way = proto.shape[0]
+        if empty is not None:
+            if empty.dtype != torch.int32 or tuple(empty.shape) != (way,):
+                raise ValueError('empty: int32 [way]')
+            empty = empty.contiguous()
+        dev = query.device
+        values = torch.empty(Q, k, dtype=torch.float32, device=dev)
+        indices = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        lse = torch.empty(Q, dtype=torch.float32, device=dev) if want_lse else None
+        dev_temp = isinstance(temp, torch.Tensor) and temp.is_cuda
+        temp_d = ops._head_in(temp)[0] if dev_temp else None
+        if Q == 0:                                               # nothing to score (an empty tensor has no address to hand over)
+            return values, indices, lse
+        with torch.cuda.device(dev):
+            ws_bytes = int(lib.fsvit_proto_bank_topk_workspace_bytes(Q, way, k, n_split))      # 0 for arguments the call below refuses with its message
+            ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=dev)
+            _lib.check(lib.fsvit_proto_bank_topk(_ptr(query), _ptr(proto), _ptr(empty), Q, way, D, 0.0 if dev_temp else float(temp), _ptr(temp_d),
+                                                 ops._HEAD_METHOD[method], k, n_split, _ptr(values), _ptr(indices), _ptr(lse), _ptr(ws), ws_bytes,
+                                                 _stream_ptr(dev)))
+        return values, indices, lse
+
+    @staticmethod
     def proto_auc(feat_shot, feat_query, want_score=False):
         """feat_shot [E,shot,D] (the shots of class 0), feat_query [E,Q,D] with the first Q / 2 queries positive -> auc [E] fp32: roc_auc_score of the cosine
         scores against the normalised mean shot (test_few_shot.py --sauc); with want_score also score [E,Q]."""

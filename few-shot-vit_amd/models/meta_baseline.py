@@ -100,6 +100,17 @@ class MetaBaseline(nn.Module):
         temp = self.temp.detach() if isinstance(self.temp, torch.Tensor) else float(self.temp)
         return bank.logits(feat, temp)
 
+    def predict_topk(self, bank, x_query, k):
+        """x_query [Q,3,H,W] -> (classes [Q,k] int64, logits [Q,k], prob [Q,k]) of PrototypeBank.topk: the head of a stable descending sort of
+        predict(bank, x_query)'s rows and the softmax probabilities of those classes, without the [Q, bank.n_classes] matrix.  1 <= k <= 32."""
+        from ..engine import ops
+        ops.check_topk_k(k, 'predict_topk')
+        feat = self._encode_eval(x_query, 'predict_topk')
+        if bank.method != self.method:
+            raise ValueError(f'predict_topk: the bank was built for {bank.method!r}, the model scores with {self.method!r}')
+        temp = self.temp.detach() if isinstance(self.temp, torch.Tensor) else float(self.temp)
+        return bank.topk(feat, k, temp)
+
     def _forward_eval(self, x_shot, x_query):
         engine = self.encoder.engine()
         temp = float(self.temp.detach()) if isinstance(self.temp, torch.Tensor) else float(self.temp)

@@ -58,6 +58,18 @@ class PrototypeBank:
         logits, pred = ops.proto_bank_logits(feat, proto, empty, temp, self.method)
         return pred.long(), logits
 
+    def topk(self, feat, k, temp=1.0):
+        """feat [Q,dim] -> (classes [Q,k] int64, logits [Q,k], prob [Q,k]): the k best classes of every row of logits(feat, temp) in the order of a
+        stable descending sort (ties: the lower class) and their softmax probabilities over all classes with examples, prob = exp(logit - lse); the
+        [Q,n_classes] matrix is never formed.  1 <= k <= 32.  An empty class scores -inf with prob 0; where k exceeds n_classes the tail holds class
+        -1, logit -inf, prob 0."""
+        ops.check_topk_k(k, 'PrototypeBank.topk')
+        _require_cuda(feat)
+        proto, empty = self._finalized()
+        values, indices, lse = ops.proto_bank_topk(feat, proto, empty, temp, self.method, k)
+        prob = torch.where(torch.isneginf(values), torch.zeros_like(values), torch.exp(values - lse[:, None]))
+        return indices.long(), values, prob
+
     def check(self):
         """One synchronisation, when the caller asks: raises if any label handed to add() was outside [0, n_classes)."""
         n = int(self.invalid.item())

@@ -7,7 +7,10 @@
 flat folder of images or class sub-folders of the same names (then the accuracy is printed).  Images are decoded and transformed as by the
 'image-folder' dataset (Resize(box) -> CenterCrop(size) with Pillow, normalisation on the device).  `--save-bank F` stores the bank (class sums,
 counts, method, class names); `--load-bank F` restores one, and together with `--support` extends it with further examples of the same classes
-without re-encoding the earlier ones.  The CSV has one row per query image: file, pred_class (the class number), logit_0 .. logit_{way-1}."""
+without re-encoding the earlier ones.  The CSV has one row per query image: file, pred_class (the class number), logit_0 .. logit_{way-1}.
+With `--topk K` (1 <= K <= 32) only the K best classes of every image are formed - the full logits are neither computed nor stored, which is what a
+bank of tens of thousands of classes needs - and the row is file, pred_class, pred_name, then class_i, name_i, logit_i, prob_i for i = 0 .. K-1 in
+descending order (ties: the lower class); prob is the softmax probability over all classes; a rank beyond the number of classes holds class -1."""
 import argparse
 import csv
 import os
@@ -66,7 +69,8 @@ def make_parser():
     p.add_argument('--query', metavar='DIR', help='images to classify: a flat folder, or class sub-folders (prints the accuracy)')
     p.add_argument('--method', choices=['cos', 'sqr'], default=None, help="default: the checkpoint's")
     p.add_argument('--numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'], help="default: FSVIT_NUMERICS or 'bf16'")
-    p.add_argument('--out', metavar='preds.csv', help='file,pred_class,logit_0.. per query image')
+    p.add_argument('--out', metavar='preds.csv', help='file,pred_class,logit_0.. per query image (with --topk: file,pred_class,pred_name,class_0,name_0,logit_0,prob_0,..)')
+    p.add_argument('--topk', type=int, default=None, metavar='K', help='keep only the K best classes per image, 1..32, with their probabilities: no full logits')
     p.add_argument('--save-bank', metavar='F', help='store the prototype bank after --support was added')
     p.add_argument('--load-bank', metavar='F', help='start from a stored bank; with --support: extend it')
     p.add_argument('--image-size', type=int, default=None, help="default: the encoder's input size")
@@ -78,6 +82,8 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     if not args.support and not args.load_bank:
         raise SystemExit('predict: give --support DIR, --load-bank F or both')
+    if args.topk is not None and not 1 <= args.topk <= 32:
+        raise SystemExit('predict: --topk K needs 1 <= K <= 32')
     if not torch.cuda.is_available():
         raise RuntimeError('fsvit: predict needs an MI355X (no CPU fallback)')
     device = torch.device('cuda', torch.cuda.current_device())
@@ -113,18 +119,29 @@ def main(argv=None):
             paths, truth = [os.path.join(args.query, n) for n in _listdir(args.query)], None
         feat = encode_files(model, paths, size, box, device)
         temp = model.temp.detach() if isinstance(model.temp, torch.Tensor) else float(model.temp)
-        pred, logits = bank.predict(feat, temp)
-        pred, logits = pred.cpu(), logits.cpu()
-        out.update(files=paths, pred=pred, logits=logits)
+        if args.topk is not None:
+            top_c, top_l, top_p = (t.cpu() for t in bank.topk(feat, args.topk, temp))
+            pred = top_c[:, 0]
+            out.update(files=paths, pred=pred, topk_classes=top_c, topk_logits=top_l, topk_prob=top_p)
+        else:
+            pred, logits = bank.predict(feat, temp)
+            pred, logits = pred.cpu(), logits.cpu()
+            out.update(files=paths, pred=pred, logits=logits)
         if truth is not None:
             out['acc'] = float((pred == torch.tensor(truth)).double().mean()) if paths else float('nan')
             print('accuracy: {:.2f} % over {} images'.format(out['acc'] * 100, len(paths)))
         if args.out:
             with open(args.out, 'w', newline='') as f:
                 w = csv.writer(f)
-                w.writerow(['file', 'pred_class'] + [f'logit_{c}' for c in range(len(classes))])
-                for p, c, row in zip(paths, pred.tolist(), logits.tolist()):
-                    w.writerow([p, c] + [repr(v) for v in row])
+                if args.topk is not None:
+                    name = lambda c: classes[c] if c >= 0 else ''
+                    w.writerow(['file', 'pred_class', 'pred_name'] + [f'{h}_{i}' for i in range(args.topk) for h in ('class', 'name', 'logit', 'prob')])
+                    for p, cs, ls, ps in zip(paths, top_c.tolist(), top_l.tolist(), top_p.tolist()):
+                        w.writerow([p, cs[0], name(cs[0])] + [x for c, l, pr in zip(cs, ls, ps) for x in (c, name(c), repr(l), repr(pr))])
+                else:
+                    w.writerow(['file', 'pred_class'] + [f'logit_{c}' for c in range(len(classes))])
+                    for p, c, row in zip(paths, pred.tolist(), logits.tolist()):
+                        w.writerow([p, c] + [repr(v) for v in row])
     return out
 
 

@@ -206,6 +206,22 @@ int fsvit_proto_bank_finalize(const float* sum_dev, const int* count_dev, int wa
  * pred_dev [Q] (optional) = the first maximum of each row.  Limits: D a multiple of 4, query_dev and proto_dev 16-byte aligned.  Q == 0 is a no-op. */
 int fsvit_proto_bank_logits(const float* query_dev, const float* proto_dev, const int* empty_dev, int Q, int way, int D, float temp, const float* temp_dev,
                             int method, float* logits_dev, int* pred_dev, void* stream);
+/* Top-k: the K best classes of every row of the matrix fsvit_proto_bank_logits would write, their logits and the row's log-sum-exp, without that
+ * matrix.  values_dev [Q,K] fp32 and indices_dev [Q,K] int32 are the first K entries of a stable descending sort of the row (larger logit first, then
+ * the lower class; every logit carries the bits fsvit_proto_bank_logits gives it); an empty class takes part with -inf, ranks beyond `way` hold
+ * (-inf, -1).  lse_dev [Q] (optional) = log sum exp over the non-empty classes, -inf for a row that has none.  The class axis is cut into segments of
+ * 1024 classes, n_seg = ceil(way / 1024), and the grid is ceil(Q / 64) x n_split workgroups, each over a contiguous run of whole segments; a second
+ * launch merges the n_split lists per row and folds the per-segment sums in ascending segment order.  values / indices are the same bits for every
+ * n_split, and lse_dev[q] depends on (way, D, method, temperature, row q) alone - not on n_split, Q or the other rows.
+ * n_split == 0 lets the library choose: min(n_seg, max(1, ceil(CUs / ceil(Q / 64)))) with the CU count of the current device - the fewest splits
+ * that give every CU a workgroup, as far as the bank has segments for it.
+ * Limits and refusals: those of fsvit_proto_bank_logits, and 1 <= K <= 32, 0 <= n_split <= n_seg, workspace_dev non-NULL, 4-byte aligned and of at
+ * least fsvit_proto_bank_topk_workspace_bytes(Q, way, K, n_split) bytes (the same n_split; 0 bytes are returned for arguments the call would refuse).
+ * Q == 0 is a no-op that touches no output.  Inputs are finite by contract: a NaN logit has no place in the order. */
+size_t fsvit_proto_bank_topk_workspace_bytes(int Q, int way, int K, int n_split);
+int fsvit_proto_bank_topk(const float* query_dev, const float* proto_dev, const int* empty_dev, int Q, int way, int D, float temp, const float* temp_dev,
+                          int method, int K, int n_split /* 0: the library chooses */, float* values_dev, int* indices_dev, float* lse_dev /* may be NULL */,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
 /* `--sauc` of the reference's test_few_shot.py (meta_tuning_sun_m/test_few_shot.py:95-112): feat_shot_dev [E,shot,D] (the shots of class 0),
  * feat_query_dev [E,Q,D], the first Q / 2 queries positive -> auc_dev [E] = roc_auc_score of the cosine scores against the normalised mean shot
  * = (#{pos > neg} + #{pos == neg} / 2) / (Q / 2)^2; score_dev [E,Q] optional.  Limits: shot >= 1, Q even, 2 <= Q <= 4096.  E == 0 is a no-op. */
