@@ -75,6 +75,7 @@ SIGNATURES = {
     'fsvit_kernel_name': (C.c_char_p, [_i, _i]),
     'fsvit_proto_head': (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _i, _fp, _fp, _fp, _vp]),
     'fsvit_proto_head_devtemp': (_i, [_fp, _fp, _i, _i, _i, _i, _i, _fp, _i, _fp, _fp, _fp, _vp]),
+    'fsvit_proto_head_gather': (_i, [_fp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _fp, _i, _fp, _fp, _fp, _vp, _vp]),
     'fsvit_proto_bank_accumulate': (_i, [_fp, _vp, _i, _i, _i, _i, _fp, _vp, _vp, _vp]),
     'fsvit_proto_bank_finalize': (_i, [_fp, _vp, _i, _i, _i, _fp, _vp, _vp]),
     'fsvit_proto_bank_logits': (_i, [_fp, _fp, _vp, _i, _i, _i, _f, _fp, _i, _fp, _vp, _vp]),

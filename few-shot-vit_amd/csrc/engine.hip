@@ -1006,6 +1006,20 @@ extern "C" int fsvit_proto_head_devtemp(const float* fs, const float* fq, int E,
   return 0;
 }
 
+extern "C" int fsvit_proto_head_gather(const float* table, int N, int D, const void* idx, int idx_is_int64, int E, int way, int shot, int n_query, float temp,
+                                       const float* temp_dev, int method, float* logits, float* acc, float* loss, int* invalid, void* stream) {
+  if (!table || !idx || !logits || !invalid) return fail(FSVIT_ERR_ARG, "fsvit_proto_head_gather: null argument");
+  if (method != FSVIT_HEAD_COS && method != FSVIT_HEAD_SQR && method != FSVIT_HEAD_DOT) return fail(FSVIT_ERR_ARG, "unknown head method %d", method);
+  if (E < 0 || N < 1 || D < 1 || way < 1 || shot < 1 || n_query < 1)
+    return fail(FSVIT_ERR_ARG, "fsvit_proto_head_gather: E = %d, N = %d, D = %d, way = %d, shot = %d, n_query = %d", E, N, D, way, shot, n_query);
+  const size_t lds = ((size_t)way * D + (size_t)way * n_query * 2) * sizeof(float);
+  if (lds > 160 * 1024)
+    return fail(FSVIT_ERR_ARG, "fsvit_proto_head_gather: way = %d prototypes of D = %d with %d queries per class need %zu bytes of LDS (limit 163840)", way, D, n_query, lds);
+  RC_TRY(fsvit::launch_proto_head_gather(table, N, D, idx, idx_is_int64, E, way, shot, n_query, temp_dev ? 0.f : temp, method, logits, acc, loss, invalid,
+                                         (hipStream_t)stream, temp_dev));
+  return 0;
+}
+
 // ---- prototype bank (proto_bank.hip): limits as fsvit.h states them
 static int proto_bank_dims(const char* what, int way, int D) {
   if (way < 1 || way > 65536) return fail(FSVIT_ERR_ARG, "%s: way = %d is outside [1, 65536]", what, way);

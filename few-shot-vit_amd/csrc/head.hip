@@ -4,6 +4,8 @@
 //    per-episode accuracy and mean cross-entropy of the eval loop (test_few_shot.py:89-90,
 //    utils/__init__.py:104-109) so the host needs no per-episode device sync.
 //    One workgroup per episode; wavefront reductions (DPP/shuffle) for norms and dots.
+//  * proto_head_gather: the same head over rows of a feature table [N][D] addressed by an index table [E][way][shot + n_query] (feature_table.py: every
+//    image is encoded once, the episodes read their rows through the sampler's indices); one device body serves both kernels.
 #include "fsvit_common.h"
 #include "kernels.h"
 #include "train_kernels.h"
@@ -12,30 +14,28 @@ namespace fsvit {
 
 // method: 0 = 'cos' (normalise both, dot), 1 = 'sqr' (negative squared distance to the mean prototype),
 //         2 = 'dot' (plain dot product with the mean prototype)
-template <int NT>
-__global__ __launch_bounds__(NT) void proto_head_kernel(const float* __restrict__ feat_shot, const float* __restrict__ feat_query,
-                                                         int way, int shot, int Q, int D, float temp, int method,
-                                                         float* __restrict__ logits, float* __restrict__ acc, float* __restrict__ loss,
-                                                         const float* __restrict__ temp_dev, const long long* __restrict__ labels = nullptr,
-                                                         float* __restrict__ dlogits = nullptr, float* __restrict__ mean_out = nullptr,
-                                                         unsigned* __restrict__ ticket = nullptr) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (temp_dev) temp = *temp_dev;                             // the learnable temperature read where it lives (no host round trip per step)
+// The arithmetic of one episode, shared by the kernels below: shot_row(c, k) / query_row(q) give the address of a feature row [D] of episode
+// blockIdx.x - contiguous rows in proto_head_kernel, rows of a feature table in proto_head_gather_kernel; everything after the address is the same
+// instruction sequence, so the two kernels give the same bits for the same rows.  smem: [way][D] + [Q][2] floats.
+template <int NT, typename ShotRow, typename QueryRow>
+__device__ __forceinline__ void proto_head_body(ShotRow shot_row, QueryRow query_row, unsigned char* smem, int way, int shot, int Q, int D, float temp, int method,
+                                                float* __restrict__ logits, float* __restrict__ acc, float* __restrict__ loss,
+                                                const long long* __restrict__ labels, float* __restrict__ dlogits, float* __restrict__ mean_out,
+                                                unsigned* __restrict__ ticket) {
   float* proto = reinterpret_cast<float*>(smem);              // [way][D]
   float* qstat = proto + (size_t)way * D;                     // [Q][2]: correct flag, nll
   const int e = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const float* fs = feat_shot + (size_t)e * way * shot * D;
-  const float* fq = feat_query + (size_t)e * Q * D;
 
   // prototypes: mean over shots (meta_baseline.py:37 / :42)
   constexpr int NWV = NT / 64;
   for (int i = t; i < way * D; i += NT) {
     const int c = i / D, d = i - c * D;
     float s = 0.f;
-    for (int k = 0; k < shot; ++k) s += fs[((size_t)c * shot + k) * D + d];
+    for (int k = 0; k < shot; ++k) s += shot_row(c, k)[d];
     proto[i] = s / (float)shot;
   }
+  // qstat is first written after this barrier: proto_head_gather_kernel keeps its bad-slot count in qstat's first word until every thread has passed here
   __syncthreads();
   if (method == 0) {                                          // F.normalize(proto), eps 1e-12 (:38)
     for (int c = wave; c < way; c += NWV) {
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(NT) void proto_head_kernel(const float* __restrict_
   }
   const int per = Q / way;                                    // queries per class (make_nk_label, few_shot.py:13-16)
   for (int q = wave; q < Q; q += NWV) {
-    const float* x = fq + (size_t)q * D;
+    const float* x = query_row(q);
     float inv = 1.0f;
     if (method == 0) {
       float ss = 0.f;
@@ -108,6 +108,61 @@ __global__ __launch_bounds__(NT) void proto_head_kernel(const float* __restrict_
   }
 }
 
+template <int NT>
+__global__ __launch_bounds__(NT) void proto_head_kernel(const float* __restrict__ feat_shot, const float* __restrict__ feat_query,
+                                                         int way, int shot, int Q, int D, float temp, int method,
+                                                         float* __restrict__ logits, float* __restrict__ acc, float* __restrict__ loss,
+                                                         const float* __restrict__ temp_dev, const long long* __restrict__ labels = nullptr,
+                                                         float* __restrict__ dlogits = nullptr, float* __restrict__ mean_out = nullptr,
+                                                         unsigned* __restrict__ ticket = nullptr) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (temp_dev) temp = *temp_dev;                             // the learnable temperature read where it lives (no host round trip per step)
+  const float* fs = feat_shot + (size_t)blockIdx.x * way * shot * D;
+  const float* fq = feat_query + (size_t)blockIdx.x * Q * D;
+  proto_head_body<NT>([=](int c, int k) { return fs + ((size_t)c * shot + k) * D; }, [=](int q) { return fq + (size_t)q * D; }, smem, way, shot, Q, D, temp,
+                      method, logits, acc, loss, labels, dlogits, mean_out, ticket);
+}
+
+// The same head over rows gathered from a feature table [N][D]: idx [E][way][shot + n_query] holds slot numbers in the sampler's class-major order, the
+// first `shot` of a class its shots (fs.split_shot_query), query q = c * n_query + j the entry idx[e][c][shot + j].  A slot outside [0, N) never
+// becomes an address: its row is read from slot 0, *invalid is raised by one per such entry (integer adds, any order) and the episode's logits, acc and
+// loss are written as NaN.
+template <int NT, typename L>
+__global__ __launch_bounds__(NT) void proto_head_gather_kernel(const float* __restrict__ table, const L* __restrict__ idx, int N, int way, int shot, int n_query,
+                                                                int D, float temp, int method, float* __restrict__ logits, float* __restrict__ acc,
+                                                                float* __restrict__ loss, const float* __restrict__ temp_dev, int* __restrict__ invalid) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (temp_dev) temp = *temp_dev;
+  const int e = blockIdx.x, t = threadIdx.x, Q = way * n_query, per_class = shot + n_query, n_idx = way * per_class;
+  const L* ei = idx + (size_t)e * n_idx;
+  // the count of this episode's bad slots borrows the first word of the body's [Q][2] scratch: every thread has read it back before the body's first
+  // barrier, and the body writes that scratch only after it
+  int* n_bad = reinterpret_cast<int*>(reinterpret_cast<float*>(smem) + (size_t)way * D);
+  if (t == 0) *n_bad = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = t; i < n_idx; i += NT) mine += (ei[i] < (L)0 || ei[i] >= (L)N);
+  if (mine) atomicAdd(n_bad, mine);
+  __syncthreads();
+  const int bad = *n_bad;
+  auto row = [=](int i) {
+    const L s = ei[i];
+    return table + (size_t)((s < (L)0 || s >= (L)N) ? (L)0 : s) * D;
+  };
+  proto_head_body<NT>([=](int c, int k) { return row(c * per_class + k); },
+                      [=](int q) { const int c = q / n_query; return row(c * per_class + shot + (q - c * n_query)); }, smem, way, shot, Q, D, temp, method,
+                      logits, acc, loss, nullptr, nullptr, nullptr, nullptr);
+  if (!bad) return;                                           // (uniform over the workgroup)
+  __syncthreads();                                            // the body's own stores to this episode's outputs come first
+  const float nan = __builtin_nanf("");
+  for (int i = t; i < Q * way; i += NT) logits[(size_t)e * Q * way + i] = nan;
+  if (t == 0) {
+    if (acc) acc[e] = nan;
+    if (loss) loss[e] = nan;
+    atomicAdd(invalid, bad);
+  }
+}
+
 int launch_proto_head(const float* feat_shot, const float* feat_query, int E, int way, int shot, int Q, int D,
                       float temp, int method, float* logits, float* acc, float* loss, hipStream_t s, const float* temp_dev) {
   return launch_proto_head_ce(feat_shot, feat_query, nullptr, E, way, shot, Q, D, temp, method, logits, acc, loss, nullptr, nullptr, nullptr, s, temp_dev);
@@ -125,6 +180,25 @@ int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const 
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(proto_head_kernel<1024>, dim3(E), dim3(1024), lds, s, feat_shot, feat_query, way, shot, Q, D, temp, method,
                      logits, acc, loss, temp_dev, labels, dlogits, mean_out, ticket);
+  return (int)hipGetLastError();
+}
+
+// the episode head over rows of a feature table (fsvit_proto_head_gather): the geometry and the LDS bound of launch_proto_head_ce with Q = way * n_query
+int launch_proto_head_gather(const float* table, int N, int D, const void* idx, int idx_is_int64, int E, int way, int shot, int n_query, float temp, int method,
+                             float* logits, float* acc, float* loss, int* invalid, hipStream_t s, const float* temp_dev) {
+  if (E <= 0) return 0;
+  if (N < 1 || way < 1 || shot < 1 || n_query < 1 || D < 1) return (int)hipErrorInvalidValue;
+  const size_t lds = ((size_t)way * D + (size_t)way * n_query * 2) * sizeof(float);
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  const void* fn = idx_is_int64 ? (const void*)proto_head_gather_kernel<1024, long long> : (const void*)proto_head_gather_kernel<1024, int>;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return (int)e;
+  if (idx_is_int64)
+    hipLaunchKernelGGL((proto_head_gather_kernel<1024, long long>), dim3(E), dim3(1024), lds, s, table, (const long long*)idx, N, way, shot, n_query, D, temp,
+                       method, logits, acc, loss, temp_dev, invalid);
+  else
+    hipLaunchKernelGGL((proto_head_gather_kernel<1024, int>), dim3(E), dim3(1024), lds, s, table, (const int*)idx, N, way, shot, n_query, D, temp, method,
+                       logits, acc, loss, temp_dev, invalid);
   return (int)hipGetLastError();
 }
 

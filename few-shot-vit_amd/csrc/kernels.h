@@ -19,6 +19,9 @@ int launch_proto_head(const float* feat_shot, const float* feat_query, int E, in
                       float temp, int method, float* logits, float* acc, float* loss, hipStream_t s, const float* temp_dev = nullptr);
 int launch_proto_head_ce(const float* feat_shot, const float* feat_query, const long long* labels, int E, int way, int shot, int Q, int D, float temp, int method,
                          float* logits, float* acc, float* loss, float* dlogits, float* mean_out, unsigned* ticket, hipStream_t s, const float* temp_dev = nullptr);
+// the same head over rows of a feature table [N][D] addressed by idx [E][way][shot + n_query] (int32 / int64 slots); limits: fsvit_proto_head_gather of fsvit.h
+int launch_proto_head_gather(const float* table, int N, int D, const void* idx, int idx_is_int64, int E, int way, int shot, int n_query, float temp, int method,
+                             float* logits, float* acc, float* loss, int* invalid, hipStream_t s, const float* temp_dev = nullptr);
 // prototype bank over a labelled support set and the single-prototype ROC-AUC of --sauc (proto_bank.hip); limits: the fsvit_proto_bank_* entries of fsvit.h
 int launch_proto_bank_accumulate(const float* feat, const void* label, int label_is_int64, int S, int way, int D, float* sum, int* count, int* invalid,
                                  hipStream_t s);

@@ -1087,6 +1087,36 @@ class ops:
                                                 shot, Q, D, float(temp), m, _ptr(logits), _ptr(acc), _ptr(loss), _stream_ptr(dev)))
         return logits, acc, loss
 
+    @staticmethod
+    def proto_head_gather(table, idx, shot, temp, invalid, method='cos'):
+        """The head of `proto_head` over rows of a feature table: table [N,D] fp32, idx [E,way,shot+n_query] (int32 / int64) slot numbers in the sampler's
+        class-major order -> logits [E,way*n_query,way], acc [E], loss [E]; for the same rows the bits of `proto_head`.  invalid [1] int32 is raised by
+        one per slot outside [0, N); such an episode's outputs are NaN.  Limits: fsvit_proto_head_gather (fsvit.h)."""
+        _require_cuda(table, idx, invalid)
+        lib = _lib.load()
+        table, = ops._head_in(table)
+        if table.dim() != 2 or idx.dim() != 3 or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError('expected table [N,D] and idx [E,way,shot+n_query] int32 / int64')
+        if invalid.dtype != torch.int32 or invalid.numel() != 1:
+            raise ValueError('invalid: one int32')
+        idx = idx.contiguous()
+        N, D = table.shape
+        E, way, per_class = idx.shape
+        n_query = per_class - int(shot)
+        dev = table.device
+        logits = torch.empty(E, way * max(n_query, 0), way, dtype=torch.float32, device=dev)
+        acc = torch.empty(E, dtype=torch.float32, device=dev)
+        loss = torch.empty(E, dtype=torch.float32, device=dev)
+        dev_temp = isinstance(temp, torch.Tensor) and temp.is_cuda
+        temp_d = ops._head_in(temp)[0] if dev_temp else None
+        if E == 0:
+            return logits, acc, loss
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_proto_head_gather(_ptr(table), N, D, _ptr(idx), int(idx.dtype == torch.int64), E, way, int(shot), n_query,
+                                                   0.0 if dev_temp else float(temp), _ptr(temp_d), ops._HEAD_METHOD[method], _ptr(logits), _ptr(acc),
+                                                   _ptr(loss), _ptr(invalid), _stream_ptr(dev)))
+        return logits, acc, loss
+
     # ---- prototype bank over a labelled support set (proto_bank.hip; limits in fsvit.h) and the single-prototype ROC-AUC of --sauc
     _HEAD_METHOD = {'cos': _lib.HEAD_COS, 'sqr': _lib.HEAD_SQR, 'dot': _lib.HEAD_DOT}
 

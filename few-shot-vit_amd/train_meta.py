@@ -12,6 +12,9 @@ MI355X-native differences:
     and keeps its slice of the batch's EPISODE axis (what DataParallel scatters, train_meta.py:131-132), BatchNorm
     statistics stay per replica as they do under DataParallel, and the one exchange per step is an all-reduce (mean) of
     the flattened gradients over RCCL (parallel.allreduce_mean_grads);
+  * `eval_feature_cache: true` (YAML key, default false): the tval / val loops take their logits from a feature_table.FeatureTable per eval
+    dataset - every image the epoch's episodes touch is encoded once, the head reads its rows through the index table (fsvit_proto_head_gather);
+    the tables are emptied after each epoch's training steps, loss and accuracy are formed by the same lines from the same logits;
   * tensorboard / dataset visualisation are not restated (not on the path).
 
   python -m fewshot_vit_amd.train_meta --config few-shot-vit_amd/configs/train_meta_synthetic.yaml
@@ -135,6 +138,7 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     timer_used, timer_epoch = utils.Timer(), utils.Timer()
     aves_keys = ['tl', 'ta', 'tvl', 'tva', 'vl', 'va']
     trlog = {k: [] for k in aves_keys}
+    tables = {}                                                 # eval_feature_cache: one FeatureTable per eval dataset
 
     for epoch in range(1, max_epoch + 1):
         timer_epoch.s()
@@ -156,17 +160,32 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
         _sig = -1
         for nm, ds, sampler in evals:
             name_l, name_a = ('tvl', 'tva') if nm == 'tval' else ('vl', 'va')
+            table = None
+            if config.get('eval_feature_cache'):
+                if nm not in tables:
+                    from .feature_table import FeatureTable
+                    tables[nm] = FeatureTable.for_dataset(model, ds)
+                table = tables[nm]
+                table.reset()                                   # the training steps above changed the weights
+                temp = model.temp.detach() if isinstance(model.temp, torch.Tensor) else float(model.temp)
             np.random.seed(0)
             sums = torch.zeros(3, dtype=torch.float64, device=device)     # sum loss, sum acc, n batches
             for idx in sampler:
-                data = _batch(ds, idx, device)
-                x_shot, x_query = fs.split_shot_query(data, n_way, n_shot, n_query, ep_per_batch=4)
                 label = fs.make_nk_label(n_way, n_query, ep_per_batch=4).to(device)
                 with torch.no_grad():
-                    logits = model(x_shot, x_query).view(-1, n_way)
+                    if table is not None:
+                        logits = table.episodes(idx, n_way, n_shot, n_query, temp, model.method)[0].view(-1, n_way)
+                    else:
+                        data = _batch(ds, idx, device)
+                        x_shot, x_query = fs.split_shot_query(data, n_way, n_shot, n_query, ep_per_batch=4)
+                        logits = model(x_shot, x_query).view(-1, n_way)
                     sums += torch.stack([F.cross_entropy(logits, label).double(), (logits.argmax(1) == label).double().mean(),
                                          torch.ones((), dtype=torch.float64, device=device)])
                 _sig = int(ds.label[int(idx[-1])])
+            if table is not None:
+                table.check()
+                if rank == 0:
+                    log('epoch {}, {} feature cache: {} images encoded for {} requested'.format(epoch, nm, table.n_encoded, table.n_requests))
             if world > 1:
                 torch.distributed.all_reduce(sums)
             if float(sums[2]) > 0:

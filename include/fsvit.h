@@ -178,6 +178,18 @@ int fsvit_proto_head(const float* feat_shot_dev, const float* feat_query_dev, in
 int fsvit_proto_head_devtemp(const float* feat_shot_dev, const float* feat_query_dev, int E, int way, int shot, int Q, int D,
                              const float* temp_dev, int method, float* logits_dev, float* acc_dev, float* loss_dev, void* stream);
 
+/* The same head over rows gathered from a feature table (one encoder feature per image, kept across episodes): table_dev [N,D] fp32, idx_dev
+ * [E,way,shot+n_query] slot numbers into it (int64 when idx_is_int64, else int32) in the sampler's class-major order - the first `shot` entries of a class
+ * are its shots (fs.split_shot_query), query q = c * n_query + j is idx[e][c][shot + j], labels follow make_nk_label -> logits_dev [E,way*n_query,way];
+ * acc_dev / loss_dev [E] may be NULL.  The temperature is *temp_dev (device) when temp_dev != NULL, else `temp`.  For the same rows the outputs carry the
+ * bits of fsvit_proto_head (one device body serves both kernels); they do not depend on E or on the other episodes.
+ * A slot outside [0, N) never becomes an address: the row is read from slot 0, the episode's acc, loss and logits block are written as NaN and
+ * *invalid_dev (an int the caller zeroes once) is raised by one per such entry.
+ * Limits and refusals (FSVIT_ERR_ARG, nothing launched): those of fsvit_proto_head - (way * D + 2 * way * n_query) * 4 bytes of LDS <= 160 KiB, i.e.
+ * way <= 79 at D = 512 - and N >= 1, shot >= 1, n_query >= 1, non-NULL table / idx / logits / invalid.  E == 0 is a no-op. */
+int fsvit_proto_head_gather(const float* table_dev, int N, int D, const void* idx_dev, int idx_is_int64, int E, int way, int shot, int n_query, float temp,
+                            const float* temp_dev, int method, float* logits_dev, float* acc_dev, float* loss_dev, int* invalid_dev, void* stream);
+
 /* Whole `MetaBaseline.forward(x_shot, x_query)` (meta_baseline.py:24-47) in eval mode:
  * x_shot_dev [E,way,shot,3,H,W], x_query_dev [E,Q,3,H,W] fp32 -> logits_dev [E,Q,way].
  * feat_dev: scratch [(E*way*shot + E*Q), out_dim] fp32. */
