@@ -5,11 +5,14 @@
 // zero-padded to `hdp` by the weight packer (channel = x*heads*hdp + y*hdp + z), NHWC rows
 // [B*S][3*heads*hdp]; output rows [B*S][heads*hdp] feed the proj GEMM ('b (y z) h w').
 //
-// v1 structure: one 256-thread workgroup per (image, head).  Q, K (row-major) and V^T are staged
-// in LDS, q k^T runs on MFMA into an fp32 score matrix in LDS, a wave-parallel softmax rewrites it
-// in place as P (storage dtype), and V^T P^T runs on MFMA so each lane stores 4 consecutive
-// head-dim values of one token.  S <= 128 tokens (Visformer: 100 and 25).
-#include "fsvit_common.h"
+// One workgroup per (image, head) in both kernels; attention_route picks one (route family in brackets):
+//   [1] attention_v2_kernel<T, NKT, NDT, NW>   register-resident softmax, S <= 224 (16-bit) / 208 (fp32 rows), head dims with an instantiation
+//                                              whose K and V^T images fit the LDS; T = float, this build's 16-bit type, or f32x2l (two-limb products)
+//   [2] attention_kernel<T>                    the generic kernel for the other head dims, S <= 128: Q, K (row-major) and V^T are staged in
+//       LDS, q k^T runs on MFMA into an fp32 score matrix in LDS, a wave-parallel softmax rewrites it in place as P (storage dtype), and
+//       V^T P^T runs on MFMA so each lane stores 4 consecutive head-dim values of one token.
+// The transposing fragment read, the bf16x8 pack, the launch sequence and the route id are shared with attention_bwd.hip: attention_tile.h.
+#include "attention_tile.h"
 #include "kernels.h"
 
 namespace FSVIT_NS {
@@ -254,7 +257,8 @@ __global__ __launch_bounds__(NW * 64) void attention_v2_kernel(const T* __restri
       sc[kt] = acc;                      // keys kt*16 + lq*4 + r  x  query lrow
     }
     // bf16 storage: P is rounded to bf16 anyway, so exp runs on the hardware exp2 (v_exp_f32) with log2(e) folded
-    // into the score scale; the fp32 parity path keeps expf.
+    // into the score scale; the fp32 parity path keeps expf.  (The block is tile_softmax of attention_tile.h written out: as a call it costs
+    // registers in this kernel, see there.)
     constexpr bool FAST_EXP = ES == 2;
     const float sscale = FAST_EXP ? scale * 1.44269504088896340736f : scale;
     float m = -INFINITY;
@@ -306,19 +310,11 @@ __global__ __launch_bounds__(NW * 64) void attention_v2_kernel(const T* __restri
           acc = mma_chunk<T>(vf, __builtin_bit_cast(u32x4, sc[kt]), acc);
         }
       } else {
-        // lane (i = lrow, lq) supplies the address of columns 4 (i & 3) .. of key row 32 kc + 4 lq + (i >> 2) (+ 16) and receives keys
-        // 32 kc + 4 lq + 0..3 (+ 16) of column i: the K-slot order the packed P fragment below has (tools/probes/tr_read_probe.hip)
-        const unsigned vaddr = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Vt + dt * (SKP * 32) + (lq * 4 + (lrow >> 2)) * 32 + (lrow & 3) * 8;
-        typedef short s4v __attribute__((ext_vector_type(4)));
+        // V subtile dt is a row-major image of 32-byte rows: this lane's tr_read_a address in its key rows 0 .. 31; 32 keys further = 1024 bytes
+        const unsigned vaddr = lds_addr(Vt) + dt * (SKP * 32) + (lq * 4 + (lrow >> 2)) * 32 + (lrow & 3) * 8;
 #pragma unroll
-        for (int kc = 0; kc < NKT / 2; ++kc) {
-          const u32x2 v0 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(size_t)(vaddr + kc * 1024)));
-          const u32x2 v1 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(size_t)(vaddr + kc * 1024 + 512)));
-          const u32x4 vf = {v0[0], v0[1], v1[0], v1[1]};
-          const bf16x8 pb = {(bf16)sc[2 * kc][0], (bf16)sc[2 * kc][1], (bf16)sc[2 * kc][2], (bf16)sc[2 * kc][3],
-                             (bf16)sc[2 * kc + 1][0], (bf16)sc[2 * kc + 1][1], (bf16)sc[2 * kc + 1][2], (bf16)sc[2 * kc + 1][3]};
-          acc = mma_chunk<T>(vf, __builtin_bit_cast(u32x4, pb), acc);
-        }
+        for (int kc = 0; kc < NKT / 2; ++kc)
+          acc = mma_chunk<T>(tr_read_a(vaddr + kc * 1024, 32), pack_bf16x8(sc[2 * kc], sc[2 * kc + 1]), acc);
       }
       if (q < S) store4<T>(obase + (size_t)q * heads * HDP + dt * 16 + lq * 4, acc * inv);
     }
@@ -330,7 +326,6 @@ static constexpr size_t v2_lds_bytes(int es, int nkt, int ndt) {
   const int qsb = ndt * 16 * es + ((32 - (ndt * 16 * es) % 64 + 64) % 64);      // the kernel's K row stride
   return (size_t)nkt * 16 * qsb + (size_t)ndt * 16 * (nkt * 16 * es + 16);
 }
-constexpr size_t kAttnLdsMax = 160 * 1024;
 
 // -1: the instantiation's image does not fit the LDS (fp32 rows, 13 key tiles, head dims 96 and 128: 164 / 217 KB) - it is not built, and
 // attention_route never names it (these shapes used to end in a bare hipErrorInvalidValue from hipFuncSetAttribute)
@@ -338,15 +333,7 @@ template <typename T, int NKT, int NDT, int NW>
 static int launch_v2(const void* qkv, void* ctx, int B, int S, int heads, float scale, hipStream_t s) {
   constexpr size_t lds = v2_lds_bytes(sizeof(T), NKT, NDT);
   if constexpr (lds > kAttnLdsMax) return -1;
-  else {
-    auto kern = attention_v2_kernel<T, NKT, NDT, NW>;
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(kern, dim3(B * heads), dim3(NW * 64), lds, s, (const T*)qkv, (T*)ctx, S, heads, scale);
-    return (int)hipGetLastError();
-  }
+  else return launch_head(attention_v2_kernel<T, NKT, NDT, NW>, lds, B * heads, NW * 64, s, qkv, ctx, S, heads, scale);
 }
 
 // the instantiations of one (element type, key tiles): -1 when ndt has none (v2_has_ndt restates this list for attention_route)
@@ -390,7 +377,6 @@ static int v2_route(int S, int ndt, int elem) {
   const int nkt = v2_key_tiles(S, elem);
   return nkt && v2_has_ndt(ndt, elem) && v2_lds_bytes(elem == 1 ? 2 : 4, nkt, ndt) <= kAttnLdsMax ? nkt : 0;
 }
-static inline int attn_route_id(int family, int elem, int nkt, int ndt) { return family * 100000 + elem * 10000 + nkt * 100 + ndt; }
 
 // fsvit.h fsvit_op_attention_route: family * 100000 + elem * 10000 + NKT * 100 + NDT (family 1 = attention_v2_kernel<elem, NKT, NDT>, 2 = the generic
 // attention_kernel<elem>, NKT = NDT = 0), -1 = refused.  dtype as launch_attention takes it (0 fp32, 1 16-bit, 2 two-limb); a two-limb shape without a
@@ -398,12 +384,12 @@ static inline int attn_route_id(int family, int elem, int nkt, int ndt) { return
 int attention_route(int S, int hdp, int dtype) {
   if (dtype < 0 || dtype > 2 || S < 1 || hdp < 16 || hdp % 16 != 0) return -1;
   const int ndt = hdp / 16;
-  if (dtype == 2 && v2_route(S, ndt, 2)) return attn_route_id(1, 2, v2_route(S, ndt, 2), ndt);
+  if (dtype == 2 && v2_route(S, ndt, 2)) return route_id(1, 2, v2_route(S, ndt, 2), ndt);
   const int elem = dtype == 2 ? 0 : dtype;
-  if (v2_route(S, ndt, elem)) return attn_route_id(1, elem, v2_route(S, ndt, elem), ndt);
+  if (v2_route(S, ndt, elem)) return route_id(1, elem, v2_route(S, ndt, elem), ndt);
   if (S > 128) return -1;                                             // the generic v1 kernel holds at most 128 tokens
   if (attention_lds_bytes(S, hdp, elem) > kAttnLdsMax) return -1;
-  return attn_route_id(2, elem, 0, 0);
+  return route_id(2, elem, 0, 0);
 }
 
 // Padded head dim the packer should use: the smallest multiple of 16 the attention kernels take for (hd, S, dtype).  fp32: any
@@ -422,35 +408,25 @@ int launch_attention(const void* qkv, void* ctx, int B, int S, int heads, int hd
   if (B <= 0) return 0;
   const int route = attention_route(S, hdp, dtype);
   if (route < 0) return (int)hipErrorInvalidValue;
-  const int family = route / 100000, elem = route / 10000 % 10, nkt = route / 100 % 100, ndt = route % 100;
-  if (family == 1) {                         // the table of instantiations (no condition of its own: a route without one is an error, not a fallback)
+  const AttnRoute r = route_decode(route);
+  if (r.family == 1) {                         // the table of instantiations (no condition of its own: a route without one is an error, not a fallback)
     int rc = -1;
-    switch (elem * 100 + nkt) {
-      case 202: rc = dispatch_ndt<f32x2l, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 207: rc = dispatch_ndt<f32x2l, 7, 4>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 213: rc = dispatch_ndt<f32x2l, 13, 7>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 2: rc = dispatch_ndt<float, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 7: rc = dispatch_ndt<float, 7, ATT_NWF112>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 13: rc = dispatch_ndt<float, 13, ATT_NWF208>(ndt, qkv, ctx, B, S, heads, scale, s); break;   // ViT: 196 patches + cls
-      case 102: rc = dispatch_ndt<bf16, 2, 2>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 108: rc = dispatch_ndt<bf16, 8, 4>(ndt, qkv, ctx, B, S, heads, scale, s); break;
-      case 114: rc = dispatch_ndt<bf16, 14, ATT_NW224>(ndt, qkv, ctx, B, S, heads, scale, s); break;
+    switch (r.elem * 100 + r.kt) {
+      case 202: rc = dispatch_ndt<f32x2l, 2, 2>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 207: rc = dispatch_ndt<f32x2l, 7, 4>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 213: rc = dispatch_ndt<f32x2l, 13, 7>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 2: rc = dispatch_ndt<float, 2, 2>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 7: rc = dispatch_ndt<float, 7, ATT_NWF112>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 13: rc = dispatch_ndt<float, 13, ATT_NWF208>(r.dt, qkv, ctx, B, S, heads, scale, s); break;   // ViT: 196 patches + cls
+      case 102: rc = dispatch_ndt<bf16, 2, 2>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 108: rc = dispatch_ndt<bf16, 8, 4>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
+      case 114: rc = dispatch_ndt<bf16, 14, ATT_NW224>(r.dt, qkv, ctx, B, S, heads, scale, s); break;
     }
     return rc == -1 ? (int)hipErrorInvalidValue : rc;
   }
-  const size_t lds = attention_lds_bytes(S, hdp, elem);
-  dim3 grid(B * heads), block(256);
-  hipError_t e;
-  if (elem == 0) {
-    e = hipFuncSetAttribute((const void*)attention_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(attention_kernel<float>, grid, block, lds, s, (const float*)qkv, (float*)ctx, S, heads, hdp, scale);
-  } else {
-    e = hipFuncSetAttribute((const void*)attention_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(attention_kernel<bf16>, grid, block, lds, s, (const bf16*)qkv, (bf16*)ctx, S, heads, hdp, scale);
-  }
-  return (int)hipGetLastError();
+  return with_elem(r.elem, [&](auto e) {
+    return launch_head(attention_kernel<elem_t<decltype(e)>>, attention_lds_bytes(S, hdp, r.elem), B * heads, 256, s, qkv, ctx, S, heads, hdp, scale);
+  });
 }
 
 }  // namespace FSVIT_NS

@@ -1,9 +1,14 @@
-// Attention backward for the Visformer training step (backward of test_phase/models/visformer.py:183-190):
+// Attention backward for the training steps (backward of test_phase/models/visformer.py:183-190 and of the ViT / DeiT blocks):
 // given q, k, v (the qkv GEMM output, head dim padded to hdp) and d(ctx), recompute P = softmax(scale q k^T) and form
 //   dV = P^T dO,  dP = dO V^T,  dS = scale * P o (dP - rowsum(dP o P)),  dQ = dS K,  dK = dS^T Q.
-// Attention is 1.2 % of the step's FLOPs: v1 keeps everything of one (image, head) in LDS as fp32 and
-// uses plain FMA loops (fp32 in both numerics modes); an MFMA version is queued behind the GEMM-shaped backward work.
-#include "fsvit_common.h"
+// One workgroup per (image, head) in every kernel.  attention_bwd_route picks the kernel (route family in brackets); the blocks they share -
+// register softmax, dS, staging, fp32 epilogue, transposing fragment read, the FMA loops, the launch sequence - are attention_tile.h.
+//   [1] attention_bwd_mfma_kernel<KT, DT, NW>          bf16 MFMA, S <= 224, hdp a multiple of 32: the whole head row-major in LDS, two passes
+//   [2] attention_bwd_f32mfma_kernel<KT, DT>           exact fp32 MFMA where Q, K, V, dO and one [S][S] matrix fit the LDS (Visformer stages)
+//   [3] attention_bwd_f32mfma_long_kernel<13, 4, 7>    exact fp32 MFMA, S <= 208 x hdp <= 64 (ViT / DeiT): two matrices resident at a time, two passes
+//   [4] attention_bwd_kernel<T>                        FMA loops, everything in LDS as fp32: the shapes without an MFMA instantiation, both dtypes
+//   [5] attention_bwd_tiled_f32_kernel<16>             FMA loops, fp32, K / V resident and the queries in blocks of 16: what [4] cannot hold
+#include "attention_tile.h"
 #include "train_kernels.h"
 
 #include <cstdlib>
@@ -35,28 +40,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const T* __restrict_
     dO[i * ld + d] = to_f32<T>(dob[(size_t)i * heads * hdp + d]);
   }
   __syncthreads();
-  // scores and dP
-  for (int idx = t; idx < S * S; idx += 256) {
-    const int i = idx / S, j = idx - i * S;
-    float s = 0.f, dp = 0.f;
-    for (int d = 0; d < hd; ++d) { s += Q[i * ld + d] * K[j * ld + d]; dp += dO[i * ld + d] * V[j * ld + d]; }
-    P[i * ls + j] = s * scale;
-    dP[i * ls + j] = dp;
-  }
+  fma_scores_dp(Q, dO, K, V, P, dP, S, S, hd, ld, ls, scale, t);
   __syncthreads();
-  // row softmax + dS (one wave per row)
-  for (int i = wave; i < S; i += 4) {
-    float m = -INFINITY;
-    for (int j = lane; j < S; j += 64) m = fmaxf(m, P[i * ls + j]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int j = lane; j < S; j += 64) { const float e = expf(P[i * ls + j] - m); P[i * ls + j] = e; sum += e; }
-    const float inv = 1.0f / wave_sum(sum);
-    float dot = 0.f;
-    for (int j = lane; j < S; j += 64) { const float p = P[i * ls + j] * inv; P[i * ls + j] = p; dot += p * dP[i * ls + j]; }
-    dot = wave_sum(dot);
-    for (int j = lane; j < S; j += 64) dP[i * ls + j] = scale * P[i * ls + j] * (dP[i * ls + j] - dot);
-  }
+  fma_softmax_ds(P, dP, S, S, S, ls, scale, lane, wave);
   __syncthreads();
   T* dq = dqkv + (size_t)b * S * rowlen + h * hdp;
   for (int idx = t; idx < S * hdp; idx += 256) {
@@ -115,26 +101,9 @@ __global__ __launch_bounds__(256) void attention_bwd_tiled_f32_kernel(const floa
       dO[i * ld + d] = i < nq ? dob[(size_t)(q0 + i) * heads * hdp + d] : 0.f;
     }
     __syncthreads();
-    for (int idx = t; idx < QB * S; idx += 256) {
-      const int i = idx / S, j = idx - i * S;
-      float sc = 0.f, dp = 0.f;
-      for (int d = 0; d < hd; ++d) { sc += Q[i * ld + d] * K[j * ld + d]; dp += dO[i * ld + d] * V[j * ld + d]; }
-      P[i * ls + j] = sc * scale;
-      dS[i * ls + j] = dp;
-    }
+    fma_scores_dp(Q, dO, K, V, P, dS, QB, S, hd, ld, ls, scale, t);
     __syncthreads();
-    for (int i = wave; i < QB; i += 4) {
-      float m = -INFINITY;
-      for (int j = lane; j < S; j += 64) m = fmaxf(m, P[i * ls + j]);
-      m = wave_max(m);
-      float sum = 0.f;
-      for (int j = lane; j < S; j += 64) { const float e = expf(P[i * ls + j] - m); P[i * ls + j] = e; sum += e; }
-      const float inv = i < nq ? 1.0f / wave_sum(sum) : 0.f;                 // rows past the end: P = dS = 0
-      float dot = 0.f;
-      for (int j = lane; j < S; j += 64) { const float p = P[i * ls + j] * inv; P[i * ls + j] = p; dot += p * dS[i * ls + j]; }
-      dot = wave_sum(dot);
-      for (int j = lane; j < S; j += 64) dS[i * ls + j] = scale * P[i * ls + j] * (dS[i * ls + j] - dot);
-    }
+    fma_softmax_ds(P, dS, QB, nq, S, ls, scale, lane, wave);
     __syncthreads();
     for (int idx = t; idx < nq * hdp; idx += 256) {            // dQ of this block
       const int i = idx / hdp, d = idx - i * hdp;
@@ -180,6 +149,7 @@ __global__ __launch_bounds__(KT * 64) void attention_bwd_f32mfma_kernel(const fl
   const float* dob = dctx + (size_t)b * S * heads * hdp + h * hdp;
   float* dq = dqkv + (size_t)b * S * rowlen + h * hdp;
   {   // 16-byte global loads (hdp % 4 == 0: the launcher checks), ALL in flight before the first LDS store: unconditional on clamped coordinates
+      // (this and stage2 of the long kernel are one block for four and for two matrices; as a shared function it costs registers in both, attention_tile.h)
     constexpr int NIT = (SP * (HD / 4) + NT - 1) / NT;
     f32x4 vq[NIT], vk[NIT], vv[NIT], vo[NIT];
 #pragma unroll
@@ -224,32 +194,9 @@ __global__ __launch_bounds__(KT * 64) void attention_bwd_f32mfma_kernel(const fl
       dp[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(V[(kt * 16 + lrow) * LD + k0 + lq], bo, dp[kt], 0, 0, 0);
     }
   }
-  float m = -INFINITY;
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = kt * 16 + 4 * lq + r < S ? sc[kt][r] * scale : -INFINITY;
-      sc[kt][r] = v;
-      m = fmaxf(m, v);
-    }
-  m = fmaxf(m, __shfl_xor(m, 16, 64));
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { const float e = expf(sc[kt][r] - m); sc[kt][r] = e; sum += e; }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-  float dot = 0.f;
-#pragma unroll
-  for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { const float pr = sc[kt][r] * inv; sc[kt][r] = pr; dot += pr * dp[kt][r]; }
-  dot += __shfl_xor(dot, 16, 64);
-  dot += __shfl_xor(dot, 32, 64);
+  float m, inv, dot;
+  tile_softmax<KT, false>(sc, S, scale, lq, m, inv);
+  tile_normalise_dot<KT>(sc, dp, inv, dot);
   float* PSq = PS + (qb * 16 + lrow) * PP;
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) *reinterpret_cast<f32x4*>(PSq + kt * 16 + 4 * lq) = sc[kt];
@@ -266,21 +213,11 @@ __global__ __launch_bounds__(KT * 64) void attention_bwd_f32mfma_kernel(const fl
       for (int dt = 0; dt < DT; ++dt) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(X[(k0 + lq) * LD + dt * 16 + lrow], bp, acc[dt], 0, 0, 0);
     }
     const int key = kb * 16 + lrow;
-    if (key < S) {
-      float* r0 = dq + (size_t)key * rowlen + which * heads * hdp;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int d = dt * 16 + 4 * lq;
-        if (d + 3 < hdp) *reinterpret_cast<f32x4*>(r0 + d) = acc[dt];         // (columns hd .. hdp: the operand is zero there -> exact zeros)
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (d + r < hdp) r0[d + r] = acc[dt][r];
-      }
-    }
+    if (key < S) store_rows_f32<DT>(acc, dq + (size_t)key * rowlen + which * heads * hdp, hdp, lq);      // (columns hd .. hdp: the operand is zero there -> exact zeros)
   };
   key_block_product(dO, 2);
   __syncthreads();
-  // ---- C: dS over P
+  // ---- C: dS over P (tile_ds written out: as a call it costs <7, 3> two VGPRs, attention_tile.h)
 #pragma unroll
   for (int kt = 0; kt < KT; ++kt) {
     f32x4 ds;
@@ -302,30 +239,18 @@ __global__ __launch_bounds__(KT * 64) void attention_bwd_f32mfma_kernel(const fl
       for (int dt = 0; dt < DT; ++dt) acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(K[(k0 + lq) * LD + dt * 16 + lrow], bs, acc[dt], 0, 0, 0);
     }
     const int qrow = qb * 16 + lrow;
-    if (qrow < S) {
-      float* r0 = dq + (size_t)qrow * rowlen;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int d = dt * 16 + 4 * lq;
-        if (d + 3 < hdp) *reinterpret_cast<f32x4*>(r0 + d) = acc[dt];
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (d + r < hdp) r0[d + r] = acc[dt][r];
-      }
-    }
+    if (qrow < S) store_rows_f32<DT>(acc, dq + (size_t)qrow * rowlen, hdp, lq);
   }
 }
 
+// LDS image of attention_bwd_f32mfma_kernel: Q, K, V, dO [SP][HD + 1] and P / dS [SP][SP + 4]
+static constexpr size_t bwd_f32mfma_lds(int kt, int dt) { return ((size_t)4 * kt * 16 * (dt * 16 + 1) + (size_t)kt * 16 * (kt * 16 + 4)) * sizeof(float); }
+
 template <int KT, int DT>
 static int launch_bwd_f32mfma(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, hipStream_t s) {
-  constexpr int SP = KT * 16, LD = DT * 16 + 1, PP = SP + 4;
-  const size_t lds = ((size_t)4 * SP * LD + (size_t)SP * PP) * sizeof(float);
+  static_assert(bwd_f32mfma_lds(KT, DT) <= kAttnLdsMax, "attention_bwd_f32mfma_kernel<KT, DT>: the image does not fit the LDS");
   if ((hdp & 3) || hdp > DT * 16) return (int)hipErrorInvalidValue;
-  auto kern = attention_bwd_f32mfma_kernel<KT, DT>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(B * heads), dim3(KT * 64), lds, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-  return (int)hipGetLastError();
+  return launch_head(attention_bwd_f32mfma_kernel<KT, DT>, bwd_f32mfma_lds(KT, DT), B * heads, KT * 64, s, qkv, dctx, dqkv, S, heads, hd, hdp, scale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -411,38 +336,12 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_f32mfma_long_kernel(con
       }
       __builtin_amdgcn_sched_barrier(0);               // (keeps hipcc from hoisting every fragment read of the 416-MFMA block to its top: 98 spilled VGPRs)
     }
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = kt * 16 + 4 * lq + r < S ? sc[kt][r] * scale : -INFINITY;
-        sc[kt][r] = v;
-        m = fmaxf(m, v);
-      }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float e = expf(sc[kt][r] - m); sc[kt][r] = e; sum += e; }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
-    float dot = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { const float pr = sc[kt][r] * inv; sc[kt][r] = pr; dot += pr * dp[kt][r]; }
-    dot += __shfl_xor(dot, 16, 64);
-    dot += __shfl_xor(dot, 32, 64);
+    float m, inv, dot;
+    tile_softmax<KT, false>(sc, S, scale, lq, m, inv);
+    tile_normalise_dot<KT>(sc, dp, inv, dot);
     const int qrow = qb * 16 + lrow;
     if (lq == 0) { st_m[qrow] = m; st_i[qrow] = qrow < S ? inv : 0.f; st_d[qrow] = dot; }      // (queries past the end: P = 0 in pass 2)
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sc[kt][r] = scale * sc[kt][r] * (dp[kt][r] - dot);           // dS
+    tile_ds<KT>(sc, dp, dot, scale);
     // dQ^T[d][q] = sum_key K[key][d] dS[q][key]: step (kt, r) sums the keys 16 kt + 4 lq + r
     f32x4 acc[DT];
 #pragma unroll
@@ -456,16 +355,7 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_f32mfma_long_kernel(con
           acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[(kt * 16 + 4 * lq + r) * LD + dt * 16 + lrow], sc[kt][r], acc[dt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (qrow < S) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int d = dt * 16 + 4 * lq;
-        if (d + 3 < hdp) *reinterpret_cast<f32x4*>(dq + (size_t)qrow * rowlen + d) = acc[dt];   // (columns hd .. hdp: K is zero there -> exact zeros)
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (d + r < hdp) dq[(size_t)qrow * rowlen + d + r] = acc[dt][r];
-      }
-    }
+    if (qrow < S) store_rows_f32<DT>(acc, dq + (size_t)qrow * rowlen, hdp, lq);      // (columns hd .. hdp: K is zero there -> exact zeros)
   }
   __syncthreads();
   // ---------------- pass 2
@@ -506,28 +396,20 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_f32mfma_long_kernel(con
     const int key = kb * 16 + lrow;
     if (key < S) {
       float* rk = dq + (size_t)key * rowlen + heads * hdp;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const int d = dt * 16 + 4 * lq;
-        if (d + 3 < hdp) { *reinterpret_cast<f32x4*>(rk + d) = accK[dt]; *reinterpret_cast<f32x4*>(rk + heads * hdp + d) = accV[dt]; }
-        else
-#pragma unroll
-          for (int r = 0; r < 4; ++r) if (d + r < hdp) { rk[d + r] = accK[dt][r]; rk[heads * hdp + d + r] = accV[dt][r]; }
-      }
+      store_rows_f32<DT>(accK, rk, hdp, lq);
+      store_rows_f32<DT>(accV, rk + heads * hdp, hdp, lq);
     }
   }
 }
 
+// LDS image of attention_bwd_f32mfma_long_kernel: two matrices [SP][HD + 1] and the three per-query statistics
+static constexpr size_t bwd_f32mfma_long_lds(int kt, int dt) { return ((size_t)2 * kt * 16 * (dt * 16 + 1) + (size_t)3 * kt * 16) * sizeof(float); }
+
 template <int KT, int DT, int NW>
 static int launch_bwd_f32mfma_long(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, int hd, int hdp, float scale, hipStream_t s) {
-  constexpr int SP = KT * 16, LD = DT * 16 + 1;
-  const size_t lds = ((size_t)2 * SP * LD + (size_t)3 * SP) * sizeof(float);
+  static_assert(bwd_f32mfma_long_lds(KT, DT) <= kAttnLdsMax, "attention_bwd_f32mfma_long_kernel<KT, DT, .>: the image does not fit the LDS");
   if ((hdp & 3) || hdp > DT * 16) return (int)hipErrorInvalidValue;
-  auto kern = attention_bwd_f32mfma_long_kernel<KT, DT, NW>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(B * heads), dim3(NW * 64), lds, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-  return (int)hipGetLastError();
+  return launch_head(attention_bwd_f32mfma_long_kernel<KT, DT, NW>, bwd_f32mfma_long_lds(KT, DT), B * heads, NW * 64, s, qkv, dctx, dqkv, S, heads, hd, hdp, scale);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -548,7 +430,6 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
   constexpr int HDP = NDT * 16, SKP = NKT * 16;
   constexpr int RS = HDP * 2 + 32;             // row-major row stride (bytes): 32 mod 64 - the conflict-free pitch for b128 reads whose 16-lane groups mix rows of two lq (round 6: 244 -> 233 us at the stage-2 shape; an odd multiple of 16 - 144 before - reads 2-way)
   constexpr int NKC = HDP / 32;                // 32-element MFMA chunks along the head dim
-  constexpr int CPR = HDP / 8;                 // 16-byte chunks per row
   unsigned char* const Qr = smem;
   unsigned char* const Kr = Qr + SKP * RS;
   unsigned char* const Vr = Kr + SKP * RS;
@@ -564,46 +445,18 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
   const bf16* base = qkv + (size_t)b * S * rowlen + h * HDP;
   const bf16* dob = dctx + (size_t)b * S * heads * HDP + h * HDP;
   bf16* dbase = dqkv + (size_t)b * S * rowlen + h * HDP;
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
-  {   // all staging loads of the head in flight at once: UNCONDITIONAL on clamped rows (rows >= S are zeroed at the LDS store).  The loop form - `if (row
-      // < S) { 4 loads }`, 4 stores, next iteration - waited for each iteration's loads before issuing the next ones: 4 HBM latencies per head.
-    constexpr int NIT = (SKP * CPR + NW * 64 - 1) / (NW * 64);
-    u32x4 q[NIT], k[NIT], v[NIT], o[NIT];
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = t + it * NW * 64, row = idx / CPR, ch = idx - row * CPR;
-      const int rc = row < S ? row : S - 1;
-      const bf16* src = base + (size_t)rc * rowlen + ch * 8;
-      q[it] = *reinterpret_cast<const u32x4*>(src);
-      k[it] = *reinterpret_cast<const u32x4*>(src + heads * HDP);
-      v[it] = *reinterpret_cast<const u32x4*>(src + 2 * heads * HDP);
-      o[it] = *reinterpret_cast<const u32x4*>(dob + (size_t)rc * heads * HDP + ch * 8);
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int idx = t + it * NW * 64, row = idx / CPR, ch = idx - row * CPR;
-      if (idx < SKP * CPR) {
-        const bool ok = row < S;
-        *reinterpret_cast<u32x4*>(Qr + row * RS + ch * 16) = ok ? q[it] : zero4;
-        *reinterpret_cast<u32x4*>(Kr + row * RS + ch * 16) = ok ? k[it] : zero4;
-        *reinterpret_cast<u32x4*>(Vr + row * RS + ch * 16) = ok ? v[it] : zero4;
-        *reinterpret_cast<u32x4*>(Or + row * RS + ch * 16) = ok ? o[it] : zero4;
-      }
-    }
+  {   // all staging loads of the head in flight at once
+    const bf16* const src[4] = {base, base + heads * HDP, base + 2 * heads * HDP, dob};
+    const size_t stride[4] = {(size_t)rowlen, (size_t)rowlen, (size_t)rowlen, (size_t)heads * HDP};
+    unsigned char* const img[4] = {Qr, Kr, Vr, Or};
+    stage_rows_b16<4, SKP, HDP, RS, NW * 64>(src, stride, img, S, t);
   }
   __syncthreads();
 
   const float sscale = scale * 1.44269504088896340736f;        // exp2 domain, exactly as the forward kernel
-  // A fragment (16 columns c0 .. c0 + 15 as MFMA rows, K slots = rows r0 + 4 lq + j and r0 + 16 + 4 lq + j) of a row-major image: this lane
-  // supplies the address of columns 4 (lrow & 3) .. of row r0 + 4 lq + (lrow >> 2) and receives rows r0 + 4 lq + 0..3 of column c0 + lrow
-  typedef short s4t __attribute__((ext_vector_type(4)));
-  auto trA = [&](const unsigned char* img, int r0, int c0) -> u32x4 {
-    const unsigned a = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)img + (r0 + lq * 4 + (lrow >> 2)) * RS + (c0 + (lrow & 3) * 4) * 2;
-    const u32x2 v0 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4t*)(size_t)a));
-    const u32x2 v1 = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4t*)(size_t)(a + 16 * RS)));
-    return u32x4{v0[0], v0[1], v1[0], v1[1]};
-  };
+  // rows r0 .. r0 + 31 x columns c0 .. c0 + 15 of a row-major image as the A fragment of a product over its rows
+  auto trA = [&](const unsigned char* img, int r0, int c0) { return tr_read_a(lds_addr(img) + (r0 + lq * 4 + (lrow >> 2)) * RS + (c0 + (lrow & 3) * 4) * 2, RS); };
   const int nt = (S + 15) / 16;
 
   // ------------------------------------------------------------------ pass 1: dQ + per-query statistics
@@ -632,53 +485,19 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
       sc[kt] = a0;                       // keys kt*16 + lq*4 + r  x  query lrow
       dp[kt] = a1;
     }
-    float m = -INFINITY;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const bool ok = kt * 16 + lq * 4 + r < S;
-        sc[kt][r] = ok ? sc[kt][r] * sscale : -INFINITY;
-        m = fmaxf(m, sc[kt][r]);
-      }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float e = __builtin_amdgcn_exp2f(sc[kt][r] - m);
-        sc[kt][r] = e;
-        sum += e;
-      }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 1.0f / sum;
-    float D = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { sc[kt][r] *= inv; D += sc[kt][r] * dp[kt][r]; }
-    D += __shfl_xor(D, 16, 64);
-    D += __shfl_xor(D, 32, 64);
+    float m, inv, D;
+    tile_softmax<NKT, true>(sc, S, sscale, lq, m, inv);
+    tile_normalise_dot<NKT>(sc, dp, inv, D);
     const bool qok = q < S;
     if (lq == 0) { st_m[q] = m; st_inv[q] = qok ? inv : 0.f; st_D[q] = D; }
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sc[kt][r] = scale * sc[kt][r] * (dp[kt][r] - D);       // dS
+    tile_ds<NKT>(sc, dp, D, scale);
     // dQ^T[d][q] = sum_key K^T[d][key] * dS[q][key]
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kc = 0; kc < NKT / 2; ++kc) {
-        const u32x4 kf = trA(Kr, 32 * kc, dt * 16);
-        const bf16x8 sb = {(bf16)sc[2 * kc][0], (bf16)sc[2 * kc][1], (bf16)sc[2 * kc][2], (bf16)sc[2 * kc][3],
-                           (bf16)sc[2 * kc + 1][0], (bf16)sc[2 * kc + 1][1], (bf16)sc[2 * kc + 1][2], (bf16)sc[2 * kc + 1][3]};
-        acc = mma_chunk<bf16>(kf, __builtin_bit_cast(u32x4, sb), acc);
-      }
+      for (int kc = 0; kc < NKT / 2; ++kc)
+        acc = mma_chunk<bf16>(trA(Kr, 32 * kc, dt * 16), pack_bf16x8(sc[2 * kc], sc[2 * kc + 1]), acc);
       if (qok) store4<bf16>(dbase + (size_t)q * rowlen + dt * 16 + lq * 4, acc);
     }
   }
@@ -699,7 +518,7 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
     for (int dt = 0; dt < NDT; ++dt) { accK[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; accV[dt] = accK[dt]; }
 #pragma unroll
     for (int qc = 0; qc < NKT / 2; ++qc) {
-      bf16x8 pb, sb;
+      f32x4 P[2], dS[2];
 #pragma unroll
       for (int half = 0; half < 2; ++half) {
         const int it = 2 * qc + half;
@@ -716,14 +535,15 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float pr = kok ? __builtin_amdgcn_exp2f(a0[r] * sscale - m4[r]) * i4[r] : 0.f;
-          pb[half * 4 + r] = (bf16)pr;
-          sb[half * 4 + r] = (bf16)(scale * pr * (a1[r] - D4[r]));
+          P[half][r] = pr;
+          dS[half][r] = scale * pr * (a1[r] - D4[r]);
         }
       }
+      const u32x4 pb = pack_bf16x8(P[0], P[1]), sb = pack_bf16x8(dS[0], dS[1]);
 #pragma unroll
       for (int dt = 0; dt < NDT; ++dt) {
-        accV[dt] = mma_chunk<bf16>(trA(Or, 32 * qc, dt * 16), __builtin_bit_cast(u32x4, pb), accV[dt]);
-        accK[dt] = mma_chunk<bf16>(trA(Qr, 32 * qc, dt * 16), __builtin_bit_cast(u32x4, sb), accK[dt]);
+        accV[dt] = mma_chunk<bf16>(trA(Or, 32 * qc, dt * 16), pb, accV[dt]);
+        accK[dt] = mma_chunk<bf16>(trA(Qr, 32 * qc, dt * 16), sb, accK[dt]);
       }
     }
     if (kok) {
@@ -737,30 +557,23 @@ __global__ __launch_bounds__(NW * 64) void attention_bwd_mfma_kernel(const bf16*
   }
 }
 
+// LDS image of attention_bwd_mfma_kernel: Q, K, V, dO [SKP] rows at the kernel's stride and the three per-query statistics
+static constexpr size_t bwd_mfma_lds(int nkt, int ndt) { return (size_t)4 * nkt * 16 * (ndt * 16 * 2 + 32) + (size_t)3 * nkt * 16 * sizeof(float); }
+
 template <int NKT, int NDT, int NW>
-static int launch_bwd_mfma(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, float scale, hipStream_t s, bool* ran) {
-  constexpr int HDP = NDT * 16, SKP = NKT * 16;
-  const size_t lds = (size_t)4 * SKP * (HDP * 2 + 32) + (size_t)3 * SKP * sizeof(float);
-  *ran = false;
-  if (lds > 160 * 1024) return 0;
-  auto kern = attention_bwd_mfma_kernel<NKT, NDT, NW>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(kern, dim3(B * heads), dim3(NW * 64), lds, s, (const bf16*)qkv, (const bf16*)dctx, (bf16*)dqkv, S, heads, scale);
-  *ran = true;
-  return (int)hipGetLastError();
+static int launch_bwd_mfma(const void* qkv, const void* dctx, void* dqkv, int B, int S, int heads, float scale, hipStream_t s) {
+  static_assert(bwd_mfma_lds(NKT, NDT) <= kAttnLdsMax, "attention_bwd_mfma_kernel<NKT, NDT, .>: the image does not fit the LDS");
+  return launch_head(attention_bwd_mfma_kernel<NKT, NDT, NW>, bwd_mfma_lds(NKT, NDT), B * heads, NW * 64, s, qkv, dctx, dqkv, S, heads, scale);
 }
 
 // ---- the ONE place that chooses a kernel (fsvit.h fsvit_op_attention_bwd_route): family * 100000 + dtype * 10000 + KT * 100 + DT, -1 = refused.
 //   family 1  attention_bwd_mfma_kernel<KT, DT, .> (bf16)      2  attention_bwd_f32mfma_kernel<KT, DT>      3  attention_bwd_f32mfma_long_kernel<13, 4, 7>
 //          4  attention_bwd_kernel<T> (FMA loops, all in LDS)   5  attention_bwd_tiled_f32_kernel<16>       (4 and 5: KT = DT = 0)
-static inline int bwd_route_id(int family, int dtype, int kt, int dt) { return family * 100000 + dtype * 10000 + kt * 100 + dt; }
 constexpr int kBwdTiledQB = 16;
-static size_t bwd_fma_lds(int S, int hd) { return ((size_t)4 * S * (hd + 1) + (size_t)2 * S * (S + 1)) * sizeof(float); }
-static size_t bwd_tiled_lds(int S, int hd) {
+static constexpr size_t bwd_fma_lds(int S, int hd) { return ((size_t)4 * S * (hd + 1) + (size_t)2 * S * (S + 1)) * sizeof(float); }
+static constexpr size_t bwd_tiled_lds(int S, int hd) {
   return ((size_t)2 * S * (hd + 1) + (size_t)2 * kBwdTiledQB * (hd + 1) + (size_t)2 * kBwdTiledQB * (S + 1)) * sizeof(float);
 }
-static size_t bwd_mfma_lds(int nkt, int ndt) { return (size_t)4 * nkt * 16 * (ndt * 16 * 2 + 32) + (size_t)3 * nkt * 16 * sizeof(float); }
 
 int attention_bwd_route(int S, int hd, int hdp, int dtype) {
   if ((dtype != 0 && dtype != 1) || S < 1 || hd < 1 || hdp < hd) return -1;
@@ -770,17 +583,17 @@ int attention_bwd_route(int S, int hd, int hdp, int dtype) {
     //  takes accumulators in AGPRs: 311 -> 249 us at S = 100.  224: ViT, 196 patches + cls)
     const int nkt = S <= 32 ? 2 : S <= 128 ? 8 : 14;
     const bool built = nkt == 2 ? (ndt == 2 || ndt == 4 || ndt == 6 || ndt == 8) : nkt == 8 ? (ndt == 2 || ndt == 4 || ndt == 6) : (ndt == 2 || ndt == 4);
-    if (built && bwd_mfma_lds(nkt, ndt) <= 160 * 1024) return bwd_route_id(1, 1, nkt, ndt);
+    if (built && bwd_mfma_lds(nkt, ndt) <= kAttnLdsMax) return route_id(1, 1, nkt, ndt);
   }
   if (dtype == 0 && (hdp & 3) == 0) {                 // exact-fp32 MFMA kernel where the head fits the LDS (Visformer stages: 100 x 42, 25 x 85)
-    if (S <= 32 && hdp <= 48) return bwd_route_id(2, 0, 2, 3);
-    if (S <= 32 && hdp <= 96) return bwd_route_id(2, 0, 2, 6);
-    if (S <= 48 && hdp <= 64) return bwd_route_id(2, 0, 3, 4);
-    if (S <= 112 && hdp <= 48) return bwd_route_id(2, 0, 7, 3);
-    if (S <= 208 && hdp <= 64) return bwd_route_id(3, 0, 13, 4);      // ViT / DeiT: 196 patches + cls
+    if (S <= 32 && hdp <= 48) return route_id(2, 0, 2, 3);
+    if (S <= 32 && hdp <= 96) return route_id(2, 0, 2, 6);
+    if (S <= 48 && hdp <= 64) return route_id(2, 0, 3, 4);
+    if (S <= 112 && hdp <= 48) return route_id(2, 0, 7, 3);
+    if (S <= 208 && hdp <= 64) return route_id(3, 0, 13, 4);      // ViT / DeiT: 196 patches + cls
   }
-  if (bwd_fma_lds(S, hd) <= 160 * 1024) return bwd_route_id(4, dtype, 0, 0);
-  if (dtype == 0 && bwd_tiled_lds(S, hd) <= 160 * 1024) return bwd_route_id(5, 0, 0, 0);
+  if (bwd_fma_lds(S, hd) <= kAttnLdsMax) return route_id(4, dtype, 0, 0);
+  if (dtype == 0 && bwd_tiled_lds(S, hd) <= kAttnLdsMax) return route_id(5, 0, 0, 0);
   return -1;
 }
 
@@ -788,40 +601,33 @@ int launch_attention_bwd(const void* qkv, const void* dctx, void* dqkv, int B, i
   if (B <= 0) return 0;
   const int route = attention_bwd_route(S, hd, hdp, dtype);
   if (route < 0) return (int)hipErrorInvalidValue;
-  bool ran = false;
-  hipError_t e;
-  switch (route) {                                      // the table of instantiations: no condition of its own
-#define BWD_MFMA(KT, DT, NW) case 110000 + KT * 100 + DT: { const int rc = launch_bwd_mfma<KT, DT, NW>(qkv, dctx, dqkv, B, S, heads, scale, s, &ran); return rc || ran ? rc : (int)hipErrorInvalidValue; }
-    BWD_MFMA(2, 2, 2) BWD_MFMA(2, 4, 2) BWD_MFMA(2, 6, 2) BWD_MFMA(2, 8, 2)
-    BWD_MFMA(8, 2, 4) BWD_MFMA(8, 4, 4) BWD_MFMA(8, 6, 4)
-    BWD_MFMA(14, 2, 4) BWD_MFMA(14, 4, 4)
+  const AttnRoute r = route_decode(route);
+  switch (r.family) {                                   // the table of instantiations: no condition of its own
+    case 1:
+      switch (r.kt * 100 + r.dt) {
+#define BWD_MFMA(KT, DT, NW) case KT * 100 + DT: return launch_bwd_mfma<KT, DT, NW>(qkv, dctx, dqkv, B, S, heads, scale, s);
+        BWD_MFMA(2, 2, 2) BWD_MFMA(2, 4, 2) BWD_MFMA(2, 6, 2) BWD_MFMA(2, 8, 2)
+        BWD_MFMA(8, 2, 4) BWD_MFMA(8, 4, 4) BWD_MFMA(8, 6, 4)
+        BWD_MFMA(14, 2, 4) BWD_MFMA(14, 4, 4)
 #undef BWD_MFMA
-    case 200203: return launch_bwd_f32mfma<2, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-    case 200206: return launch_bwd_f32mfma<2, 6>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-    case 200304: return launch_bwd_f32mfma<3, 4>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-    case 200703: return launch_bwd_f32mfma<7, 3>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-    case 301304: return launch_bwd_f32mfma_long<13, 4, 7>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
-    case 500000: {
-      const size_t lds_t = bwd_tiled_lds(S, hd);
-      e = hipFuncSetAttribute((const void*)attention_bwd_tiled_f32_kernel<kBwdTiledQB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(attention_bwd_tiled_f32_kernel<kBwdTiledQB>, dim3(B * heads), dim3(256), lds_t, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-      return (int)hipGetLastError();
-    }
-    case 400000: {
-      const size_t lds = bwd_fma_lds(S, hd);
-      e = hipFuncSetAttribute((const void*)attention_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * heads), dim3(256), lds, s, (const float*)qkv, (const float*)dctx, (float*)dqkv, S, heads, hd, hdp, scale);
-      return (int)hipGetLastError();
-    }
-    case 410000: {
-      const size_t lds = bwd_fma_lds(S, hd);
-      e = hipFuncSetAttribute((const void*)attention_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(attention_bwd_kernel<bf16>, dim3(B * heads), dim3(256), lds, s, (const bf16*)qkv, (const bf16*)dctx, (bf16*)dqkv, S, heads, hd, hdp, scale);
-      return (int)hipGetLastError();
-    }
+      }
+      break;
+    case 2:
+      switch (r.kt * 100 + r.dt) {
+#define BWD_F32(KT, DT) case KT * 100 + DT: return launch_bwd_f32mfma<KT, DT>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+        BWD_F32(2, 3) BWD_F32(2, 6) BWD_F32(3, 4) BWD_F32(7, 3)
+#undef BWD_F32
+      }
+      break;
+    case 3:
+      if (r.kt == 13 && r.dt == 4) return launch_bwd_f32mfma_long<13, 4, 7>(qkv, dctx, dqkv, B, S, heads, hd, hdp, scale, s);
+      break;
+    case 4:
+      return with_elem(r.elem, [&](auto e) {
+        return launch_head(attention_bwd_kernel<elem_t<decltype(e)>>, bwd_fma_lds(S, hd), B * heads, 256, s, qkv, dctx, dqkv, S, heads, hd, hdp, scale);
+      });
+    case 5:
+      return launch_head(attention_bwd_tiled_f32_kernel<kBwdTiledQB>, bwd_tiled_lds(S, hd), B * heads, 256, s, qkv, dctx, dqkv, S, heads, hd, hdp, scale);
   }
   return (int)hipErrorInvalidValue;                     // a route without an instantiation is an error, never a fallback
 }
