@@ -54,16 +54,34 @@ constexpr int NST = 3, STAGE = 16384;          // weight ring
 constexpr int OFF_W = 2 * HBUF;
 constexpr int LDS_BYTES = OFF_W + NST * STAGE; // 163840 = 160 KiB
 static_assert(LDS_BYTES == 160 * 1024, "the two halo buffers and the weight ring fill the LDS exactly");
+// C1F (stem conv2 with conv1 built on-chip, see the kernel): ONE c1 halo buffer; where the second one was, two raw-image windows, the conv1 weight
+// fragments and its bias.  A window is 3 channels x 21 rows x 80 fp32 = 1260 16-byte slots = 20 LDS-DMA pieces, fetched as 3 per wave (24: the last
+// four are dummies from the zero page into the window's own padding, so that every wave counts the same number of operations).
+constexpr int IMG = 80, RAW_ROWS = 2 * HR + 1;   // raw image side; raw rows 2 r0 - 3 ... 2 r0 + 17 under the c1 halo rows r0 - 1 ... r0 + 8
+constexpr int RAW_Q4 = IMG / 4, RAW_SLOTS = 3 * RAW_ROWS * RAW_Q4;
+constexpr int RAW_NP = 3, RAWW = 8 * RAW_NP * 1024;
+constexpr int OFF_RAW = HBUF, OFF_C1W = OFF_RAW + 2 * RAWW, OFF_C1B = OFF_C1W + 4 * 64 * 16;
+constexpr int C1_MT = HR * TW / 16;              // 25 m-tiles of 16 consecutive pixels of the 10 x 40 c1 halo
+static_assert(RAW_SLOTS <= 8 * RAW_NP * 64 && OFF_C1B + 4 * 4 * 16 <= OFF_W && HR * TW % 16 == 0, "the C1F regions sit between the c1 buffer and the weight ring");
 }  // namespace halo
 
 // CREAL < CIN (the LV-ViT stem, CREAL = 96 on the CIN = 128 schedule): the maps hold CREAL channels (input and output pixel = CREAL * 2 bytes); halo
 // chunks past CREAL are filled from the zero page, the weights come as the zero-padded 128-channel image (ConvGemmParams::w_cpad), and outputs past
 // CREAL are neither loaded (bias / pos) nor stored.  Every CREAL-specific statement is `if constexpr (CREAL != CIN)`: the 64 / 128 instantiations
 // compile to what they were.
-template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN>
+//
+// C1F (stem conv2 of the eval engine, CIN = 64): the input map c1 = LeakyReLU(bn1(conv1(image))) never exists in HBM.  The workgroup fetches the RAW
+// fp32 window under the NEXT tile's c1 halo with the piece mechanism (3 pieces per wave instead of 7) while the K loop runs, and between two tiles -
+// behind the tap-8 barrier, after which nobody reads the c1 buffer any more - the 8 waves build the 10 x 40 x 64 c1 halo from it with the statements
+// of stem_conv1_kernel (same taps, same rounding, same four MFMAs per 16 pixels, same LeakyReLU: bit-identical c1) and write it as 16-byte chunks into
+// the chunk-planar buffer.  c1 rows outside the image are written as zeros (conv2's padding, not LeakyReLU(bias)); halo columns -1 / 40 are zeroed once.
+// The packed B operand of the 8 interior rows is also the im2col patch row conv3's tail needs: stored to p.c1f_patches, the layout of stem_conv1_kernel.
+template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN, bool C1F = false>
 __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmParams p, const int n_tiles) {
   using namespace halo;
+  static_assert(!C1F || (CIN == 64 && CREAL == 64 && !FUSE_TAIL && !STATS), "conv1 is fused into the plain 64-channel instantiation only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NP = C1F ? RAW_NP : NPIECE;                     // pieces a wave issues per phase
   constexpr int NH = CIN / 64;                                  // phases (64-channel halves) per tile
   constexpr int NKM = 9 * NH, NKT = NKM + (FUSE_TAIL ? 1 : 0);  // weight K tiles per output tile (64 k each; the tail tile uses 32)
   constexpr int MT = 5, NT = 4;
@@ -133,6 +151,99 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
     return Xb + (long)(bb * p.H + rr - 1) * x_rs + (p.x_planar ? (h * 8 + wave) * p.W * 16 : h * 128 + wave * 16);
   };
 
+  // ---- C1F: piece j of this wave (window piece 8 j + wave) of the raw window of the tile whose image starts at `base` and whose first output row is
+  // nr0, into window nwin.  Slot s = (channel c, window row r, float4 q4) <- raw row 2 nr0 - 3 + r; rows outside the image, the slots past the window
+  // and base == nullptr (no next tile) read the zero page
+  auto issue_raw = [&](int j, int lane_o, const unsigned char* base, int nr0, int nwin) {
+    const int pi = j * 8 + wave;
+    const int s = pi * 64 + lane_o, c = s / (RAW_ROWS * RAW_Q4), rem = s - c * (RAW_ROWS * RAW_Q4), r = rem / RAW_Q4, q4 = rem - r * RAW_Q4;
+    const int iy = 2 * nr0 - 3 + r;
+    const bool ok = (base != nullptr) & (s < RAW_SLOTS) & (iy >= 0) & (iy < IMG);
+    const unsigned long a = (unsigned long)base + (unsigned long)(unsigned)(((c * IMG + iy) * IMG + q4 * 4) * 4);
+    const unsigned long z = (unsigned long)g_zero_page_halo;
+    dma1_lane(reinterpret_cast<const void*>(ok ? a : z), lds0 + OFF_RAW + nwin * RAWW + pi * 1024);
+  };
+  auto raw_base = [&](int tile) {           // images [0, c1f_split) of the launch come from c1f_raw, the rest from c1f_raw2
+    const int bb = tile / tiles_per_img;
+    const float* im = bb < p.c1f_split ? p.c1f_raw + (size_t)bb * 3 * IMG * IMG : p.c1f_raw2 + (size_t)(bb - p.c1f_split) * 3 * IMG * IMG;
+    return reinterpret_cast<const unsigned char*>(im);
+  };
+  // ---- C1F: the c1 halo of the tile (image b_, first output row r0_) from raw window win_ into the c1 buffer; the statements of stem_conv1_kernel
+  auto c1_phase = [&](int win_, int b_, int r0_) {
+    int lane_c = lane;
+    asm volatile("" : "+v"(lane_c));                             // see the phase loop: nothing of this is carried through the K loop
+    const int m = lane_c & 15, lqc = lane_c >> 4;
+    const float* wnd = reinterpret_cast<const float*>(smem + OFF_RAW + win_ * RAWW);
+    bf16* const P = reinterpret_cast<bf16*>(p.c1f_patches);
+    u32x4 wf[4];
+    f32x4 bv[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      wf[ct] = *reinterpret_cast<const u32x4*>(smem + OFF_C1W + (ct * 64 + lane_c) * 16);
+      bv[ct] = *reinterpret_cast<const f32x4*>(smem + OFF_C1B + (ct * 4 + lqc) * 16);
+    }
+    // this lane's taps: k = 8 lq + j = (ky * 3 + kx) * 3 + c -> float offset from (window row 2 hr, column 2 ox - 1).  Every tap is READ (k >= 27 at
+    // offset 0; kx == 0 of column 0 one float in front of the row - inside the LDS either way) and the rounded pair is masked instead: vmask keeps the
+    // halves of the real taps, lmask also drops the kx == 0 taps (column -1 of the image) - one select + one AND per packed register, not per tap
+    int koff[8];
+    unsigned vmask[4], lmask[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      unsigned vm = 0u, lm = 0u;
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int k = 8 * lqc + 2 * w + u, tap = k / 3, c = k - 3 * tap, ky = tap / 3, kx = tap - 3 * ky;
+        koff[2 * w + u] = k < 27 ? (c * RAW_ROWS + ky) * IMG + kx : 0;
+        vm |= k < 27 ? 0xffffu << (16 * u) : 0u;
+        lm |= (k < 27 && kx != 0) ? 0xffffu << (16 * u) : 0u;
+      }
+      vmask[w] = vm;
+      lmask[w] = lm;
+    }
+    // the wave's m-tiles wave, wave + 8, wave + 16 (and 24 on wave 0): all gathers first
+    constexpr int NMT = (C1_MT + 7) / 8;
+    u32x4 pf[NMT];
+    int hr_[NMT], ox_[NMT];
+#pragma unroll
+    for (int it = 0; it < NMT; ++it) {
+      if (wave + 8 * it >= C1_MT) break;                         // (wave-uniform)
+      const int tl = wave + 8 * it;
+      const int pix = tl * 16 + m, hr = pix / TW, ox = pix - hr * TW;
+      const float* org = wnd + (2 * hr * IMG + 2 * ox - 1);
+      hr_[it] = hr;
+      ox_[it] = ox;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) pf[it][w] = pk2(org[koff[2 * w]], org[koff[2 * w + 1]]) & (ox == 0 ? lmask[w] : vmask[w]);
+    }
+#pragma unroll
+    for (int it = 0; it < NMT; ++it) {
+      if (wave + 8 * it >= C1_MT) break;                         // (wave-uniform)
+      const int hr = hr_[it], ox = ox_[it], row = r0_ + hr - 1;  // row: c1 row of the image
+      const bool row_ok = (row >= 0) & (row < p.H);
+#pragma unroll
+      for (int pp = 0; pp < 2; ++pp) {
+        const f32x4 a0 = mma_chunk<bf16>(wf[2 * pp], pf[it], bv[2 * pp]), a1 = mma_chunk<bf16>(wf[2 * pp + 1], pf[it], bv[2 * pp + 1]);
+        bf16x8 o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                            // LeakyReLU(0.1) = max(v, 0.1 v)
+          o[q] = (bf16)fmaxf(a0[q], 0.1f * a0[q]);
+          o[4 + q] = (bf16)fmaxf(a1[q], 0.1f * a1[q]);
+        }
+        u32x4 ob = __builtin_bit_cast(u32x4, o);
+        if (!row_ok) ob = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(smem + (4 * pp + lqc) * PLANE + (hr * HP + ox + 1) * 16) = ob;
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < NMT; ++it) {                           // the patch rows of the 8 interior rows
+      if (wave + 8 * it >= C1_MT) break;
+      const int hr = hr_[it];
+      if (hr >= 1 && hr <= TR) *reinterpret_cast<u32x4*>(P + ((size_t)(b_ * p.H + r0_ + hr - 1) * TW + ox_[it]) * 32 + 8 * lqc) = pf[it];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // this wave's chunks are in the buffer before anyone passes the barrier
+    bar();
+  };
+
   f32x4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
@@ -148,7 +259,25 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   auto wk_of = [&](int q) { return q >= NKM ? NKM : (NH == 2 ? (q >= 9 ? (q - 9) * 2 + 1 : q * 2) : q); };
 
   // ---- prologue: whole halo of (tile, half 0) into buffer 0, weight K tiles of steps 0 and 1
-  {
+  if constexpr (C1F) {
+    // raw window of the first tile into window 0; meanwhile the c1 buffer is zeroed (its halo columns -1 / 40 are never written again) and the conv1
+    // A fragments (stem_conv1_kernel's row order) and bias go to LDS, lane-major: the phase reads them back with four ds_read_b128
+    const int r00 = (tix % tiles_per_img) * TR;
+    const unsigned char* b0 = raw_base(tix);
+#pragma unroll
+    for (int j = 0; j < RAW_NP; ++j) issue_raw(j, lane, b0, r00, 0);
+    for (int i = t; i < HBUF / 16; i += 512) *reinterpret_cast<u32x4*>(smem + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    if (wave == 0) {
+      const bf16* w1 = reinterpret_cast<const bf16*>(p.c1f_w);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+        *reinterpret_cast<u32x4*>(smem + OFF_C1W + (ct * 64 + lane) * 16) =
+            *reinterpret_cast<const u32x4*>(w1 + (size_t)(32 * (ct >> 1) + 8 * (lrow >> 2) + 4 * (ct & 1) + (lrow & 3)) * p.c1f_kw + 8 * lq);
+      if (lane < 16)
+        *reinterpret_cast<f32x4*>(smem + OFF_C1B + lane * 16) =
+            p.c1f_bias ? *reinterpret_cast<const f32x4*>(p.c1f_bias + 32 * (lane >> 3) + 8 * (lane & 3) + 4 * ((lane >> 2) & 1)) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  } else {
     const int r00 = (tix % tiles_per_img) * TR;
     const unsigned char* b0 = halo_base(tix, 0);
 #pragma unroll
@@ -158,6 +287,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
   issue_w(wk_of(1 % NKT), 1);
   HWAIT(0);
   bar();
+  [[maybe_unused]] int win = 0;                                 // C1F: raw window of the current tile
+  if constexpr (C1F) c1_phase(0, tix / tiles_per_img, (tix % tiles_per_img) * TR);
   int st_cur = 0, st_pre = 2, q_pre = 2 % NKT;                  // ring state: stage being consumed, stage / step-in-tile being prefetched
   int buf = 0;                                                  // halo buffer of the current phase
 #define H_STAMP(acc_)
@@ -179,7 +310,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
     for (int h = 0; h < NH; ++h) {
       // the phase after this one: the other half of this tile, or half 0 of the next tile, or none (dummy pieces)
       const int n_tix = h + 1 < NH ? tix : (has_next ? tnext : -1), n_h = h + 1 < NH ? h + 1 : 0;
-      const unsigned char* nbase = n_tix >= 0 ? halo_base(n_tix, n_h) : nullptr;
+      const unsigned char* nbase;
+      if constexpr (C1F) nbase = n_tix >= 0 ? raw_base(n_tix) : nullptr;
+      else nbase = n_tix >= 0 ? halo_base(n_tix, n_h) : nullptr;
       const int n_r0 = n_tix >= 0 ? (n_tix % tiles_per_img) * TR : 0;
       const bool n_top = n_r0 == 0, n_bot = n_r0 + TR == p.H;
       // Register pressure: everything derived from the lane index for the pieces / the tail loads / the epilogue is loop-invariant, and
@@ -230,14 +363,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
         // every halo piece of the next phase.  Younger: the halo piece issued behind the previous step's barrier (taps 1..7) and the
         // two weight DMAs just issued.  lgkmcnt(0): this wave's reads of the current weight stage are complete before anyone may
         // overwrite it.
-        if (TAP >= 1 && TAP <= NPIECE) { if (pre_w) HWAIT(3); else HWAIT(1); }
+        if (TAP >= 1 && TAP <= NP) { if (pre_w) HWAIT(3); else HWAIT(1); }
         else { if (pre_w) HWAIT(2); else HWAIT(0); }
         H_STAMP(ckV);
         bar();
         H_STAMP(ckW);
         // ---- region B: the 20 MFMAs of chunk 1; between them the halo piece of the next phase (address arithmetic + one LDS-DMA) and
         // the 9 fragment reads of the next tap's chunk 0
-        if constexpr (TAP < NPIECE) issue_piece(TAP, lane_o, nbase, n_top, n_bot, buf ^ 1);
+        if constexpr (TAP < NP) {
+          if constexpr (C1F) issue_raw(TAP, lane_o, nbase, n_r0, win ^ 1);
+          else issue_piece(TAP, lane_o, nbase, n_top, n_bot, buf ^ 1);
+        }
         const int st_next = st_cur == NST - 1 ? 0 : st_cur + 1;
         if constexpr (TAP < 8) {                                                     // chunk 0 of the next tap
           const unsigned char* wb = wst0 + st_next * STAGE + b_rd;
@@ -261,7 +397,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
         for (int i = 0; i < MT; ++i)
 #pragma unroll
           for (int j = 0; j < NT; ++j) acc[i][j] = mma_chunk<bf16>(wf1[j], xf1[i], acc[i][j]);
-        if constexpr (TAP < NPIECE) {
+        if constexpr (TAP < NP) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                       // 1 MFMA
@@ -285,9 +421,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
         H_STAMP(ckB);
         advance();
       });
-      buf ^= 1;
+      if constexpr (!C1F) {                  // (C1F: one c1 buffer, rebuilt between the tiles)
+        buf ^= 1;
 #pragma unroll
-      for (int i = 0; i < MT; ++i) xb[i] = buf ? xb[i] + (unsigned)HBUF : xb[i] - (unsigned)HBUF;
+        for (int i = 0; i < MT; ++i) xb[i] = buf ? xb[i] + (unsigned)HBUF : xb[i] - (unsigned)HBUF;
+      }
     }
 
     if constexpr (FUSE_TAIL) {   // tail K tile: 32 im2col taps of the downsample conv, one k-chunk
@@ -430,6 +568,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(const ConvGemmPara
     H_STAMP(ckE);
     if (!has_next) break;
     tix = tnext;
+    if constexpr (C1F) {   // every wave is past the tap-8 barrier: the last read of the c1 buffer is over and the next tile's window has landed
+      win ^= 1;
+      c1_phase(win, tix / tiles_per_img, (tix - (tix / tiles_per_img) * tiles_per_img) * TR);
+    }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // no DMA (dummy pieces) may be in flight into the LDS of a finished workgroup
   if constexpr (STATS) {
@@ -479,6 +621,11 @@ bool conv3x3_halo_eligible(const ConvGemmParams& p, int dtype) {
   return (p.Cin == 64 || p.Cin == 128) && !p.x2 && !p.pos && p.Kw == p.K;
 }
 
+// conv2 of the eval stem with conv1 built inside the kernel (C1F): the planar 64 -> 128 layer on 40 x 40 maps of 80 x 80 images
+bool conv3x3_halo_c1f_supported(const ConvGemmParams& p, int dtype) {
+  return conv3x3_halo_eligible(p, dtype) && p.Cin == 64 && p.H == halo::IMG / 2 && !p.stats && !p.pool2 && !p.w_cpad && p.x_planar;
+}
+
 static inline int halo_grid(const ConvGemmParams& p) { const int n_tiles = p.B * (p.H / halo::TR); return n_tiles < 256 ? n_tiles : 256; }
 // (the statistics rows = the persistent grid: one partial per workgroup)
 int conv3x3_halo_stats_rows(const ConvGemmParams& p, int dtype) {
@@ -488,10 +635,10 @@ int conv3x3_halo_stats_rows(const ConvGemmParams& p, int dtype) {
   return conv3x3_halo_eligible(q, dtype) ? halo_grid(p) : 0;
 }
 
-template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN>
+template <int CIN, bool FUSE_TAIL, bool STATS = false, int CREAL = CIN, bool C1F = false>
 static int launch_halo_t(const ConvGemmParams& p, hipStream_t stream) {
   const int n_tiles = p.B * (p.H / halo::TR);
-  auto kern = conv3x3_halo_kernel<CIN, FUSE_TAIL, STATS, CREAL>;
+  auto kern = conv3x3_halo_kernel<CIN, FUSE_TAIL, STATS, CREAL, C1F>;
   hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, halo::LDS_BYTES);
   if (e != hipSuccess) return (int)e;
   const int grid = n_tiles < 256 ? n_tiles : 256;
@@ -500,6 +647,7 @@ static int launch_halo_t(const ConvGemmParams& p, hipStream_t stream) {
 }
 
 int launch_conv3x3_halo(const ConvGemmParams& p, hipStream_t stream) {
+  if (p.c1f_raw) return conv3x3_halo_c1f_supported(p, 1) ? launch_halo_t<64, false, false, 64, true>(p, stream) : (int)hipErrorInvalidValue;
   if (p.w_cpad) return p.pool2 ? launch_halo_t<128, true, false, 96>(p, stream) : launch_halo_t<128, false, false, 96>(p, stream);
   if (p.pool2) return launch_halo_t<128, true>(p, stream);
   if (p.stats) return p.Cin == 64 ? launch_halo_t<64, false, true>(p, stream) : launch_halo_t<128, false, true>(p, stream);

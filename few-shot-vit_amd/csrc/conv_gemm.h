@@ -76,6 +76,16 @@ struct ConvGemmParams {
   // conv3x3_halo only (the LV-ViT stem, Cin = N = 96): w_cpad == 128 -> the weight rows are the 128-channel image of the layer: 128 rows (rows >= N
   // zero), k = tap * 128 + c with c >= Cin zero, the tail slice behind the 9 * 128 main columns.  0: the standard packing above.
   int w_cpad = 0;
+  // conv3x3_halo only (conv2 of the eval engine's stem, conv3x3_halo_c1f_supported): c1f_raw != nullptr -> the kernel never reads x.  It builds its input map
+  // c1 = LeakyReLU(conv1(image) + bias) on-chip from the raw NCHW fp32 images - images [0, c1f_split) of the launch from c1f_raw, the rest from c1f_raw2 -
+  // with the packed conv1 weights c1f_w (row length c1f_kw) / c1f_bias, and stores the im2col patch rows [B * H * W][32] to c1f_patches on the way.
+  const float* c1f_raw = nullptr;
+  const float* c1f_raw2 = nullptr;
+  int c1f_split = 0;
+  void* c1f_patches = nullptr;
+  const void* c1f_w = nullptr;
+  const float* c1f_bias = nullptr;
+  int c1f_kw = 0;
 };
 
 }  // namespace fsvit_types
@@ -95,6 +105,7 @@ struct ConvGemmParams {
   /* conv3x3_halo.hip: 3x3 / stride 1 conv with the input tile + halo resident in LDS (stem conv2 / conv3 geometry) */      \
   bool conv3x3_halo_eligible(const ConvGemmParams& p, int dtype);                                                          \
   int launch_conv3x3_halo(const ConvGemmParams& p, hipStream_t stream);                                                    \
+  bool conv3x3_halo_c1f_supported(const ConvGemmParams& p, int dtype); /* conv2 of the stem can build conv1's map on-chip */  \
   int conv_stats_rows(const ConvGemmParams& p, int dtype); /* partial rows `stats` receives from this layer's kernel, 0 = none */ \
   int conv3x3_halo_stats_rows(const ConvGemmParams& p, int dtype);                                                           \
   int conv_gemm_v2_config(const ConvGemmParams& p); /* which tile configuration launch_conv_gemm_v2 picks */               \

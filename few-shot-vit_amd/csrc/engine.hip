@@ -172,6 +172,7 @@ struct fsvit_visformer : EngineBase {
   std::vector<Block1> s1;
   std::vector<BlockA> s2, s3;
   float *fscale = nullptr, *fshift = nullptr;
+  bool stem_fuse_c1 = true;            // FSVIT_STEM_FUSE_C1 (read at create): the planar stem builds conv1's map inside the conv2 kernel
 };
 
 namespace {
@@ -394,6 +395,10 @@ int build(fsvit_visformer* h, const SD& sd) {
   if (!is_pow2(h->C0) || !is_pow2(h->C1) || !is_pow2(h->C2) || !is_pow2(Cg))
     return fail(FSVIT_ERR_ARG, "multi-tap conv input channels must be powers of two");
   if (h->H2 * h->H2 > 128) return fail(FSVIT_ERR_ARG, "attention supports at most 128 tokens (img_size <= 88)");
+
+  // FSVIT_STEM_FUSE_C1=0 (read once per build): the planar stem keeps stem_conv1 and the c1 map in HBM - the A/B switch of tests/test_gpu_stem_fused_c1.py
+  const char* fuse_env = getenv("FSVIT_STEM_FUSE_C1");
+  h->stem_fuse_c1 = !(fuse_env && fuse_env[0] == '0');
 
   std::vector<double> nob;
   WRound wr;                                    // weight-rounding bias correction: the 16-bit modes only (the two-limb modes carry 16+ bits)
@@ -727,7 +732,8 @@ int timed(EngineBase* h, hipStream_t st, const char* layer, int kernel, double f
   return 0;
 }
 
-// images per slice of the dedicated stem (forward_chunk): swept 1600 / 3200 / 6400 / 12 800 on one box - 29.14 / 29.06 / 29.24 / 29.26 ms per 12 800-image step
+// images per slice of the dedicated stem (forward_chunk): swept 1600 / 3200 / 6400 / 12 800 on one box - 29.14 / 29.06 / 29.24 / 29.26 ms per 12 800-image step;
+// again with conv1 inside the conv2 kernel (medians of three interleaved rounds): 28.02 / 27.87 / 27.85 / 27.88 - 3200 and up within the run-to-run spread, 3200 stays
 static constexpr int stem_slice_images() { return 3200; }
 
 int run_gemm(EngineBase* h, hipStream_t st, const char* layer, const Layer& L, const ConvGemmParams& p, double n_true, double k_true) {
@@ -771,9 +777,11 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
     const size_t s_pat = (size_t)h->H0 * h->H0 * 32 * es, s_c1 = (size_t)h->H0 * h->H0 * h->C0 * es, s_c2 = (size_t)h->H0 * h->H0 * h->C1 * es,
                  s_x1 = (size_t)h->H1 * h->H1 * h->C1 * es;
     const double fl1 = 2.0 * 27.0 * h->C0 * h->H0 * h->H0;
+    // conv1 inside the conv2 kernel (conv3x3_halo.hip, C1F): no stem_conv1 launch, c1 is never written; conv2 stores the patch rows for conv3's tail
+    const bool fuse_c1 = h->stem_fuse_c1 && K(conv3x3_halo_c1f_supported)(p2, kg(kdt)) && img == 80;
     for (int g0 = 0; g0 < Bc; g0 += S) {
       const int g1 = g0 + S < Bc ? g0 + S : Bc;
-      for (int part = 0; part < 2; ++part) {               // images [g0, g1) of cat([shot, query]): [0, B1) from x, [B1, Bc) from xsrc2
+      for (int part = 0; part < 2 && !fuse_c1; ++part) {   // images [g0, g1) of cat([shot, query]): [0, B1) from x, [B1, Bc) from xsrc2
         const int a = part == 0 ? g0 : (g0 > B1 ? g0 : B1), b = part == 0 ? (g1 < B1 ? g1 : B1) : g1;
         if (a >= b) continue;
         const float* src = part == 0 ? x + (size_t)a * 3 * img * img : xsrc2 + (size_t)(a - B1) * 3 * img * img;
@@ -784,6 +792,15 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
       q2.x = (const unsigned char*)c1 + g0 * s_c1; q2.y = (unsigned char*)c2 + g0 * s_c2; q2.B = g1 - g0; q2.M = (g1 - g0) * q2.OH * q2.OW;
       q3.x = (const unsigned char*)c2 + g0 * s_c2; q3.x2 = (const unsigned char*)patches + g0 * s_pat; q3.y = (unsigned char*)x1 + g0 * s_x1;
       q3.B = g1 - g0; q3.M = (g1 - g0) * q3.OH * q3.OW;
+      if (fuse_c1) {                                       // images [g0, g1) of cat([shot, query]): the first c1f_split of them from x, the rest from xsrc2
+        const size_t isz = (size_t)3 * img * img;
+        q2.c1f_raw = g0 < B1 ? x + g0 * isz : xsrc2 + (size_t)(g0 - B1) * isz;
+        q2.c1f_split = g0 < B1 ? (g1 < B1 ? g1 : B1) - g0 : g1 - g0;
+        q2.c1f_raw2 = xsrc2;
+        q2.c1f_patches = (unsigned char*)patches + g0 * s_pat;
+        q2.c1f_w = h->conv1.w; q2.c1f_kw = h->conv1.Kw; q2.c1f_bias = h->conv1.bias;
+        RC_TRY(timed(h, st, "stem.conv2", KID_HALO, 2.0 * (double)q2.M * h->C1 * 9.0 * h->C0 + fl1 * (g1 - g0), [&]() { return K(launch_conv_gemm)(q2, kg(kdt), st); }));
+      } else
       RC_TRY(run_gemm(h, st, "stem.conv2", h->conv2, q2, h->C1, 9.0 * h->C0));
       RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, q3, h->C1, 9.0 * h->C1 + 27.0));
     }
