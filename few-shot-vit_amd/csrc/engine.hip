@@ -1,6 +1,10 @@
-// fsvit engine: state-dict packing (eval BatchNorm folding, K-major weight layout, head-dim
-// padding), the Visformer eval forward as a fixed chain of kernel launches on one HIP stream, and
-// the extern "C" boundary declared in include/fsvit.h.
+// fsvit eval engines and the C boundary declared in include/fsvit.h.  In file order:
+//  - state-dict packing: eval BatchNorm folding, K-major weight layout, head-dim padding, the weight-rounding bias correction;
+//  - EvalStem: the ConvBlock stem that Visformer and LV-ViT share - one packer, one scratch layout, one slice loop over its four routes;
+//  - the Visformer eval forward: a fixed chain of kernel launches on one HIP stream, its workspace laid out by an Arena that runs dry for
+//    fsvit_*_workspace_bytes and for real inside a chunk;
+//  - the handle plumbing of every encoder (create / workspace_bytes / chunked forward), the operator entry points, the profiler;
+//  - the ViT / DeiT and LV-ViT encoders on the same plumbing.
 #include "../../include/fsvit.h"
 
 #include <hip/hip_runtime.h>
@@ -17,53 +21,21 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
 using namespace fsvit;
 
-// Kernel-namespace dispatch: every kernel that touches 16-bit activations exists for the two 16-bit storage types (namespace fsvit = bf16,
-// fsvit_f16 = fp16; see fsvit_common.h).  K(fn) picks the build that matches `kdt` (a FSVIT_* dtype in scope); kd() maps the public dtype
-// to the kernels' own convention (0 = f32, 1 = the namespace's 16-bit type).  The fp32-only heads (kernels.h, bottom) are fsvit:: alone.
-// The two-limb modes (FSVIT_BF16X2 / FSVIT_F16X2) are fp32 STORAGE (kd() = 0: every kernel but the GEMM is the fp32 path's) with the GEMM
-// arithmetic selected by kg() = 2 (conv_gemm_v2.hip: x2_split) and the weights uploaded pre-split.
-#define K(fn) ((kdt == FSVIT_F16 || kdt == FSVIT_F16X2) ? fsvit_f16::fn : fsvit::fn)
-static inline bool is_x2(int dtype) { return dtype == FSVIT_BF16X2 || dtype == FSVIT_F16X2; }
-static inline bool known_dtype(int dtype) { return dtype >= FSVIT_F32 && dtype <= FSVIT_F16X2; }
-static inline int kd(int dtype) { return (dtype == FSVIT_F32 || is_x2(dtype)) ? 0 : 1; }
-static inline int kg(int dtype) { return is_x2(dtype) ? 2 : kd(dtype); }
-static inline int storage_bytes(int dtype) { return kd(dtype) == 0 ? 4 : 2; }
-static inline bool half_dtype(int dtype) { return dtype == FSVIT_BF16 || dtype == FSVIT_F16; }
-
 // ------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+int fsvit_set_error(int code, const char* fmt, ...) {      // host_common.h: every error of engine.hip and train_engine.hip ends here
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-int fsvit_set_error(int code, const char* fmt, ...) {      // shared with train_engine.hip
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-  return code;
-}
-static int hipfail(hipError_t e, const char* what) {
-  return fail((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    hipError_t _e = (expr);                             \
-    if (_e != hipSuccess) return hipfail(_e, #expr);    \
-  } while (0)
-#define RC_TRY(expr)                                                              \
-  do {                                                                            \
-    int _rc = (expr);                                                             \
-    if (_rc != 0) return _rc > 0 ? hipfail((hipError_t)_rc, #expr) : _rc;         \
-  } while (0)
 
 extern "C" const char* fsvit_last_error(void) { return g_err; }
 extern "C" const char* fsvit_version(void) { return "fsvit 0.1.0 gfx950"; }
@@ -113,9 +85,6 @@ static inline uint32_t x2_limbs(float w, bool f16) {
   }
   return ((uint32_t)hi << 16) | lo;
 }
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-static inline bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-static inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 struct Layer {
   void* w = nullptr;      // [groups][N][Kw] storage dtype
@@ -134,6 +103,30 @@ struct BlockA {
   void* qa_img = nullptr;      // qkv_attn.hip: fragment-major image of the qkv conv (null: qkv GEMM + attention launches)
   void* qr_img = nullptr;      // mlp_rows.hip gemm_rows: fragment-major image of the qkv conv (row-wise GEMM instead of the 256-tile one)
   void* qar_img = nullptr;     // mlp_rows.hip qkv_attn_rows: head-major image of the qkv conv (qkv + attention in one launch, maps of <= 32 tokens)
+};
+
+// images per slice of the dedicated stem (stem_forward): swept 1600 / 3200 / 6400 / 12 800 on one box - 29.14 / 29.06 / 29.24 / 29.26 ms per 12 800-image step;
+// again with conv1 inside the conv2 kernel (medians of three interleaved rounds): 28.02 / 27.87 / 27.85 / 27.88 - 3200 and up within the run-to-run spread, 3200 stays
+static constexpr int stem_slice_images() { return 3200; }
+
+// The ConvBlock stem of Visformer (visformer.py:202-239) and LV-ViT (lvvit.py:277-318), packed by pack_stem and run by stem_forward:
+// conv1 s2 -> conv2 -> conv3 + downsample identity (eval BatchNorm folded, LeakyReLU(0.1)) -> MaxPool2d(2) [+ pos].  Everything that
+// decides which kernels run is fixed when the handle is created.
+enum StemRoute {
+  STEM_GENERAL,        // conv2 / conv3 wherever launch_conv_gemm routes them, NHWC maps: other image sizes, geometries and numerics modes
+  STEM_HALO_NHWC,      // conv2 / conv3 on conv3x3_halo's 96-channel instantiation over the 128-padded images conv2h / conv3h (ConvGemmParams::w_cpad)
+  STEM_PLANAR,         // stem_conv1 -> conv3x3_halo -> conv3x3_halo + tail, c1 / c2 row-chunk-planar (conv_gemm.h x_planar)
+  STEM_PLANAR_C1F      // STEM_PLANAR with conv1 built inside the conv2 kernel (conv3x3_halo.hip, C1F): no stem_conv1 launch, c1 is never written
+};
+struct EvalStem {
+  Layer conv1, conv2, conv3f;  // conv3f: conv3 + bn3 with the downsample conv + bn_d folded in as a tail K slice
+  Layer conv2h, conv3h;        // STEM_HALO_NHWC only: the 128-channel weight images of conv2 / conv3f (biases shared with them)
+  int C0 = 0, C1 = 0;          // channels of conv1's map, of conv2's / conv3's
+  int H0 = 0, H1 = 0, img = 0; // side of the conv maps (img / 2), of the pooled map (img / 4), of the image
+  const float* pos = nullptr;  // [H1 * H1][C1] added behind the pool, or null
+  StemRoute route = STEM_GENERAL;
+  bool conv1_direct = false;   // conv1 is stem_conv1 (im2col rows + conv1 + bn1 + LeakyReLU in one pass over the image), not im2col27 + a K = 32 GEMM
+  int slice = 0;               // images per pass of the slice loop (stem_forward); 0: the whole chunk in one pass
 };
 
 struct Tap { void* dst; size_t bytes; };
@@ -166,13 +159,13 @@ struct fsvit_visformer : EngineBase {
   int H0 = 0, H1 = 0, H2 = 0, H3 = 0;
   int hid1 = 0, hid2 = 0, hid3 = 0;
   int hd2 = 0, hdp2 = 0, hd3 = 0, hdp3 = 0;
-  Layer conv1, conv2, conv3f, pe2, pe3;   // conv3f: conv3 + bn3 with the downsample conv + bn_d folded in as a tail K slice
+  EvalStem stem;
+  Layer pe2, pe3;
   void* pe_img[2] = {nullptr, nullptr};                // mlp_rows.hip: fragment-major image of patch_embed2 / 3 for the row-wise kernel (null: conv_gemm)
-  float *pos1 = nullptr, *pos2 = nullptr, *pos3 = nullptr;
+  float *pos2 = nullptr, *pos3 = nullptr;      // (pos_embed1 is the stem's)
   std::vector<Block1> s1;
   std::vector<BlockA> s2, s3;
   float *fscale = nullptr, *fshift = nullptr;
-  bool stem_fuse_c1 = true;            // FSVIT_STEM_FUSE_C1 (read at create): the planar stem builds conv1's map inside the conv2 kernel
 };
 
 namespace {
@@ -372,6 +365,132 @@ int pack_pos(EngineBase* h, const float* pos, int C, int HW, float** out) {
   return 0;
 }
 
+// A [C] state-dict entry as doubles (zeros when missing: the caller has checked the key through bn_affine).
+std::vector<double> sd_vec(const SD& sd, const std::string& name, int C, bool absolute) {
+  const float* p = sd.get(name, {C});
+  std::vector<double> v(C, 0.0);
+  for (int c = 0; p && c < C; ++c) v[c] = absolute ? std::fabs((double)p[c]) : (double)p[c];
+  return v;
+}
+
+ConvGemmParams conv_params(const Layer& L, const void* x, void* y, int B, int H, int W, int Cin, int x_cstride,
+                           int KH, int KW, int stride, int pad, int y_cstride, int act,
+                           const void* res, int res_first, const float* pos) {
+  ConvGemmParams p;
+  p.x = x; p.w = L.w; p.bias = L.bias; p.res = res; p.pos = pos; p.y = y;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.x_cstride = x_cstride;
+  p.OH = (H + 2 * pad - KH) / stride + 1; p.OW = (W + 2 * pad - KW) / stride + 1;
+  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
+  p.N = L.N; p.y_cstride = y_cstride; p.K = L.K; p.Kw = L.Kw; p.M = B * p.OH * p.OW;
+  p.groups = L.groups; p.act = act; p.res_first = res_first; p.log2Cin = ilog2(Cin);
+  p.x2 = nullptr; p.x2_cstride = 0; p.K2 = 0; p.pool2 = 0; p.y_rpi = 0; p.y_row0 = 0;
+  p.w_gstride = 0; p.w_rstride = 0; p.out_f32 = 0; p.y2 = nullptr; p.stats = nullptr;
+  return p;
+}
+
+// conv2 and conv3 (+ downsample tail + LeakyReLU + MaxPool2d [+ pos]) of a stem for n images: c1 -> c2 -> out, the tail over the im2col rows `patches`
+void stem_conv_params(const EvalStem& s, bool planar, const void* c1, void* c2, const void* patches, void* out, int n, ConvGemmParams* p2, ConvGemmParams* p3) {
+  const bool halo = s.route == STEM_HALO_NHWC;
+  *p2 = conv_params(halo ? s.conv2h : s.conv2, c1, c2, n, s.H0, s.H0, s.C0, s.C0, 3, 3, 1, 1, s.C1, ACT_LRELU, nullptr, 0, nullptr);
+  *p3 = conv_params(halo ? s.conv3h : s.conv3f, c2, out, n, s.H0, s.H0, s.C1, s.C1, 3, 3, 1, 1, s.C1, ACT_LRELU, nullptr, 0, s.pos);
+  p3->x2 = patches; p3->x2_cstride = 32; p3->K2 = 32; p3->pool2 = 1;
+  // the two maps between the dedicated kernels are row-chunk-planar: the halo fetch of the consumer then reads row segments instead of 16 bytes of every 128-byte line
+  p2->x_planar = p2->y_planar = p3->x_planar = planar ? 1 : 0;
+  if (halo) p2->w_cpad = p3->w_cpad = 128;
+}
+
+// Packs <pfx>conv1 / conv2 / conv3 / downsample with their BatchNorms folded (conv -> BN as per-output-channel scale + shift) into `s` and fixes its
+// route.  pos: the packed position table added behind the pool, or null.  wr: the weight-rounding correction (null: none - LV-ViT).
+// direct_conv1: stem_conv1 may stand in for im2col27 + GEMM where it is built.  general_slice: EvalStem::slice of STEM_GENERAL (the other routes run in
+// slices of stem_slice_images()).
+int pack_stem(EngineBase* h, const SD& sd, const std::string& pfx, int C0, int C1, int img, double eps, const float* pos, const WRound* wr,
+              bool direct_conv1, int general_slice, EvalStem* out) {
+  EvalStem& s = *out;
+  const int kdt = h->dtype;
+  s.C0 = C0; s.C1 = C1; s.img = img; s.H0 = img / 2; s.H1 = img / 4; s.pos = pos;
+  const float* w1 = sd.get(pfx + "conv1.weight", {C0, 3, 3, 3});
+  const float* wd = sd.get(pfx + "downsample.0.weight", {C1, 3, 3, 3});
+  const float* w2 = sd.get(pfx + "conv2.weight", {C1, C0, 3, 3});
+  const float* w3 = sd.get(pfx + "conv3.weight", {C1, C1, 3, 3});
+  Affine b1 = bn_affine(sd, pfx + "bn1", C0, eps), b2 = bn_affine(sd, pfx + "bn2", C1, eps);
+  Affine b3 = bn_affine(sd, pfx + "bn3", C1, eps), bd = bn_affine(sd, pfx + "downsample.1", C1, eps);
+  if (!w1 || !wd || !w2 || !w3 || !b1.ok || !b2.ok || !b3.ok || !bd.ok) return FSVIT_ERR_KEY;
+  // conv1 (and the downsample taps inside conv3f) consume the 32-wide im2col rows: K columns 0..26 = (ky,kx,c), 27..31 = 0
+  std::vector<int> cm(27);
+  for (int k = 0; k < 27; ++k) cm[k] = k;
+  // operand means: the normalised image 0 (no correction for conv1 / downsample); conv2 / conv3 read LeakyReLU(BN(z)), z_c ~ N(beta_c, gamma_c^2)
+  const bool fix = wr && wr->on;
+  std::vector<double> m2(C0), m3(C1);
+  if (wr) {
+    const std::vector<double> be1 = sd_vec(sd, pfx + "bn1.bias", C0, false), ga1 = sd_vec(sd, pfx + "bn1.weight", C0, true);
+    const std::vector<double> be2 = sd_vec(sd, pfx + "bn2.bias", C1, false), ga2 = sd_vec(sd, pfx + "bn2.weight", C1, true);
+    for (int c = 0; c < C0; ++c) m2[c] = lrelu_mean(be1[c], ga1[c]);
+    for (int c = 0; c < C1; ++c) m3[c] = lrelu_mean(be2[c], ga2[c]);
+  }
+  const std::vector<double> tf0 = tap_fraction(s.H0, 1, 3, 1);
+  RC_TRY(pack_layer(h, &s.conv1, w1, C0, 3, 3, 3, 1, &b1.s, nullptr, b1.t, true, nullptr, 0, &cm, 32));
+  RC_TRY(pack_layer(h, &s.conv2, w2, C1, C0, 3, 3, 1, &b2.s, nullptr, b2.t, true, nullptr, 0, nullptr, 0, wr, &m2, tf0.data()));
+  // Row image of a BN-scaled 3 x 3 conv: `rows` rows of Kw columns, k = tap * cstride + c (zeros elsewhere); tail: behind the Kmain main columns one
+  // K slice of bn_d-scaled downsample taps over the im2col rows
+  auto conv_image = [&](const float* w, int Cin, const std::vector<double>& scale, int cstride, int rows, int Kmain, int Kw, bool tail) {
+    std::vector<float> pk((size_t)rows * Kw, 0.0f);
+    for (int o = 0; o < C1; ++o) {
+      for (int c = 0; c < Cin; ++c)
+        for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + t9 * cstride + c] = (float)((double)w[((size_t)o * Cin + c) * 9 + t9] * scale[o]);
+      for (int c = 0; tail && c < 3; ++c)
+        for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + Kmain + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
+    }
+    return pk;
+  };
+  {  // conv3f rows = [ bn3-scaled conv3 (K = 9*C1, padded to the K slice) | one tail slice: bn_d-scaled downsample taps ]
+    const int bke = 128 / h->es, K = 9 * C1, Kmain = round_up(K, bke), Kw = Kmain + bke;
+    std::vector<float> pb(C1);
+    for (int o = 0; o < C1; ++o) {
+      double bias = b3.t[o] + bd.t[o];
+      if (wr) {
+        double corr = 0.0;
+        for (int c = 0; fix && c < C1; ++c)
+          for (int t9 = 0; t9 < 9; ++t9) {
+            const double v = (double)w3[((size_t)o * C1 + c) * 9 + t9] * b3.s[o];
+            corr -= (wr->rounded(v) - v) * tf0[t9] * m3[c];
+          }
+        bias += corr;
+      }
+      pb[o] = (float)bias;
+    }
+    s.conv3f.N = C1; s.conv3f.K = K; s.conv3f.Kw = Kw; s.conv3f.groups = 1;
+    RC_TRY(upload(h, conv_image(w3, C1, b3.s, C1, C1, Kmain, Kw, true), true, &s.conv3f.w));
+    void* bdev; RC_TRY(upload(h, pb, false, &bdev)); s.conv3f.bias = (float*)bdev;
+  }
+  // ---- the route.  Two switches, each read once per build: FSVIT_LVVIT_STEM=gemm keeps the 96-channel convs on conv_gemm_v2 (the A/B switch of
+  // tools/bench_lvvit.py); FSVIT_STEM_FUSE_C1=0 keeps stem_conv1 and the c1 map in HBM on the planar route (tests/test_gpu_stem_fused_c1.py)
+  const char* stem_env = getenv("FSVIT_LVVIT_STEM");
+  const char* fuse_env = getenv("FSVIT_STEM_FUSE_C1");
+  s.route = STEM_GENERAL; s.slice = general_slice;
+  s.conv1_direct = direct_conv1 && K(stem_conv1_supported)(kd(kdt), img, C0);
+  if (kd(kdt) == 1 && C0 == 96 && C1 == 96 && !(stem_env && strcmp(stem_env, "gemm") == 0)) {
+    // conv3x3_halo's images (ConvGemmParams::w_cpad = 128): 128 rows, k = tap * 128 + c, zeros past the 96 channels / rows; conv3's tail slice of
+    // downsample taps behind the 9 * 128 main columns.  Same folded values as conv2 / conv3f (the bias tables are shared: 96 entries).
+    s.route = STEM_HALO_NHWC; s.slice = stem_slice_images();
+    for (int which = 0; which < 2; ++which) {
+      Layer& L = which ? s.conv3h : s.conv2h;
+      L.N = C1; L.K = 9 * C0; L.Kw = 9 * 128 + (which ? 64 : 0); L.groups = 1; L.bias = which ? s.conv3f.bias : s.conv2.bias;
+      RC_TRY(upload(h, conv_image(which ? w3 : w2, C0, which ? b3.s : b2.s, 128, 128, 9 * 128, L.Kw, which == 1), true, &L.w));
+    }
+  } else if (s.conv1_direct) {
+    // the whole stem on its dedicated kernels where both halo convs are built for the geometry (the probe stands in for the im2col rows of the tail)
+    static const char probe = 0;
+    ConvGemmParams p2, p3;
+    stem_conv_params(s, false, nullptr, nullptr, &probe, nullptr, 1, &p2, &p3);
+    if (K(conv_gemm_route)(p2, kg(kdt)) == 0 && K(conv_gemm_route)(p3, kg(kdt)) == 0) {
+      s.route = STEM_PLANAR; s.slice = stem_slice_images();
+      stem_conv_params(s, true, nullptr, nullptr, &probe, nullptr, 1, &p2, &p3);
+      if (!(fuse_env && fuse_env[0] == '0') && K(conv3x3_halo_c1f_supported)(p2, kg(kdt)) && img == 80) s.route = STEM_PLANAR_C1F;
+    }
+  }
+  return 0;
+}
+
 int build(fsvit_visformer* h, const SD& sd) {
   const int kdt = h->dtype;
   const fsvit_visformer_cfg& cf = h->cfg;
@@ -396,10 +515,6 @@ int build(fsvit_visformer* h, const SD& sd) {
     return fail(FSVIT_ERR_ARG, "multi-tap conv input channels must be powers of two");
   if (h->H2 * h->H2 > 128) return fail(FSVIT_ERR_ARG, "attention supports at most 128 tokens (img_size <= 88)");
 
-  // FSVIT_STEM_FUSE_C1=0 (read once per build): the planar stem keeps stem_conv1 and the c1 map in HBM - the A/B switch of tests/test_gpu_stem_fused_c1.py
-  const char* fuse_env = getenv("FSVIT_STEM_FUSE_C1");
-  h->stem_fuse_c1 = !(fuse_env && fuse_env[0] == '0');
-
   std::vector<double> nob;
   WRound wr;                                    // weight-rounding bias correction: the 16-bit modes only (the two-limb modes carry 16+ bits)
   // FSVIT_WROUND=0 (read once per build): the plain 16-bit images without the correction - the ablation switch of the one eval route whose effect
@@ -408,64 +523,18 @@ int build(fsvit_visformer* h, const SD& sd) {
   wr.on = (kdt == FSVIT_BF16 || kdt == FSVIT_F16) && !(wr_env && wr_env[0] == '0');
   wr.f16 = kdt == FSVIT_F16;
   if (wr.on) wr.cst.assign(h->C1, 0.0);
-  auto vec = [&](const std::string& name, int C, bool absolute) {      // a [C] state-dict entry as doubles (checked by bn_affine before)
-    const float* p = sd.get(name, {C});
-    std::vector<double> v(C, 0.0);
-    for (int c = 0; p && c < C; ++c) v[c] = absolute ? std::fabs((double)p[c]) : (double)p[c];
-    return v;
-  };
-  // ---- stem (visformer.py:202-239): conv -> BN folded as per-output-channel scale + shift
-  {
-    const float* w1 = sd.get("stem.conv1.weight", {h->C0, 3, 3, 3});
-    const float* wd = sd.get("stem.downsample.0.weight", {h->C1, 3, 3, 3});
-    const float* w2 = sd.get("stem.conv2.weight", {h->C1, h->C0, 3, 3});
-    const float* w3 = sd.get("stem.conv3.weight", {h->C1, h->C1, 3, 3});
-    Affine b1 = bn_affine(sd, "stem.bn1", h->C0, eps), b2 = bn_affine(sd, "stem.bn2", h->C1, eps);
-    Affine b3 = bn_affine(sd, "stem.bn3", h->C1, eps), bd = bn_affine(sd, "stem.downsample.1", h->C1, eps);
-    if (!w1 || !wd || !w2 || !w3 || !b1.ok || !b2.ok || !b3.ok || !bd.ok) return FSVIT_ERR_KEY;
-    // conv1 (and the downsample taps inside conv3f) consume the 32-wide im2col rows: K columns 0..26 = (ky,kx,c), 27..31 = 0
-    std::vector<int> cm(27);
-    for (int k = 0; k < 27; ++k) cm[k] = k;
-    // operand means: the normalised image 0 (no correction for conv1 / downsample); conv2 / conv3 read LeakyReLU(BN(z)), z_c ~ N(beta_c, gamma_c^2)
-    std::vector<double> m2(h->C0), m3(h->C1);
-    {
-      const std::vector<double> be1 = vec("stem.bn1.bias", h->C0, false), ga1 = vec("stem.bn1.weight", h->C0, true);
-      const std::vector<double> be2 = vec("stem.bn2.bias", h->C1, false), ga2 = vec("stem.bn2.weight", h->C1, true);
-      for (int c = 0; c < h->C0; ++c) m2[c] = lrelu_mean(be1[c], ga1[c]);
-      for (int c = 0; c < h->C1; ++c) m3[c] = lrelu_mean(be2[c], ga2[c]);
-    }
-    const std::vector<double> tf0 = tap_fraction(h->H0, 1, 3, 1);
-    RC_TRY(pack_layer(h, &h->conv1, w1, h->C0, 3, 3, 3, 1, &b1.s, nullptr, b1.t, true, nullptr, 0, &cm, 32));
-    RC_TRY(pack_layer(h, &h->conv2, w2, h->C1, h->C0, 3, 3, 1, &b2.s, nullptr, b2.t, true, nullptr, 0, nullptr, 0, &wr, &m2, tf0.data()));
-    {  // conv3f rows = [ bn3-scaled conv3 (K = 9*C1, padded to the K slice) | one tail slice: bn_d-scaled downsample taps ]
-      const int bke = 128 / h->es, K = 9 * h->C1, Kmain = round_up(K, bke), Kw = Kmain + bke;
-      std::vector<float> pk((size_t)h->C1 * Kw, 0.0f), pb(h->C1);
-      for (int o = 0; o < h->C1; ++o) {
-        double corr = 0.0;
-        for (int c = 0; c < h->C1; ++c)
-          for (int t9 = 0; t9 < 9; ++t9) {
-            const double v = (double)w3[((size_t)o * h->C1 + c) * 9 + t9] * b3.s[o];
-            pk[(size_t)o * Kw + t9 * h->C1 + c] = (float)v;
-            if (wr.on) corr -= (wr.rounded(v) - v) * tf0[t9] * m3[c];
-          }
-        for (int c = 0; c < 3; ++c)
-          for (int t9 = 0; t9 < 9; ++t9)
-            pk[(size_t)o * Kw + Kmain + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
-        pb[o] = (float)(b3.t[o] + bd.t[o] + corr);
-      }
-      h->conv3f.N = h->C1; h->conv3f.K = K; h->conv3f.Kw = Kw; h->conv3f.groups = 1;
-      RC_TRY(upload(h, pk, true, &h->conv3f.w));
-      void* bdev; RC_TRY(upload(h, pb, false, &bdev)); h->conv3f.bias = (float*)bdev;
-    }
-  }
+  auto vec = [&](const std::string& name, int C, bool absolute) { return sd_vec(sd, name, C, absolute); };
   {
     const float* p1 = sd.get("pos_embed1", {1, h->C1, h->H1, h->H1});
     const float* p2 = sd.get("pos_embed2", {1, h->C2, h->H2, h->H2});
     const float* p3 = sd.get("pos_embed3", {1, h->C3, h->H3, h->H3});
     if (!p1 || !p2 || !p3) return FSVIT_ERR_KEY;
-    RC_TRY(pack_pos(h, p1, h->C1, h->H1 * h->H1, &h->pos1));
+    float* pos1;
+    RC_TRY(pack_pos(h, p1, h->C1, h->H1 * h->H1, &pos1));
     RC_TRY(pack_pos(h, p2, h->C2, h->H2 * h->H2, &h->pos2));
     RC_TRY(pack_pos(h, p3, h->C3, h->H3 * h->H3, &h->pos3));
+    // ---- stem (visformer.py:202-239): sliced on the dedicated routes only - the general route launches once per chunk
+    RC_TRY(pack_stem(h, sd, "stem.", h->C0, h->C1, cf.img_size, eps, pos1, &wr, true, 0, &h->stem));
   }
   // ---- stage 1 (Block with attn_disabled, spatial_conv; visformer.py:241-263, Mlp :127-163)
   // WRound: estimated mean of the residual stream where the next PatchEmbed reads it.  Seeded with zeros (a stage without blocks hands on "no
@@ -644,66 +713,6 @@ int build(fsvit_visformer* h, const SD& sd) {
   return 0;
 }
 
-// ---- workspace plan for a chunk of Bc images
-struct Plan {
-  size_t patches, c1, c2;                // stem scratch
-  size_t ha, hb;                         // stage-1 hidden
-  size_t qkv, ctx, hid;                  // stage-2/3 scratch
-  size_t x1, x1b, x2, x3;                // residual streams (x1b: ping-pong partner for the fused stage-1 block)
-  size_t total;
-};
-
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-Plan make_plan(const fsvit_visformer* h, size_t Bc) {
-  Plan p;
-  const size_t es = h->es, P0 = (size_t)h->H0 * h->H0, P1 = (size_t)h->H1 * h->H1, P2 = (size_t)h->H2 * h->H2, P3 = (size_t)h->H3 * h->H3;
-  const int heads = h->cfg.num_heads;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  p.x1 = take(Bc * P1 * h->C1 * es);
-  p.x1b = take(Bc * P1 * h->C1 * es);
-  p.x2 = take(Bc * P2 * h->C2 * es);
-  p.x3 = take(Bc * P3 * h->C3 * es);
-  const size_t scratch0 = off;
-  // stem
-  p.patches = take(Bc * P0 * 32 * es);
-  p.c1 = take(Bc * P0 * h->C0 * es);
-  p.c2 = take(Bc * P0 * h->C1 * es);
-  size_t hi = off;
-  // stage 1 (reuses the stem scratch)
-  off = scratch0;
-  p.ha = take(Bc * P1 * h->hid1 * es);
-  p.hb = take(Bc * P1 * h->hid1 * es);
-  if (off > hi) hi = off;
-  // stage 2 / 3 (same offsets, sized for the larger)
-  off = scratch0;
-  size_t q2 = Bc * P2 * 3 * heads * h->hdp2 * es, q3 = Bc * P3 * 3 * heads * h->hdp3 * es;
-  size_t c2 = Bc * P2 * heads * h->hdp2 * es, c3 = Bc * P3 * heads * h->hdp3 * es;
-  size_t h2 = Bc * P2 * h->hid2 * es, h3 = Bc * P3 * h->hid3 * es;
-  p.qkv = take(q2 > q3 ? q2 : q3);
-  p.ctx = take(c2 > c3 ? c2 : c3);
-  p.hid = take(h2 > h3 ? h2 : h3);
-  if (off > hi) hi = off;
-  p.total = hi;
-  return p;
-}
-
-ConvGemmParams conv_params(const Layer& L, const void* x, void* y, int B, int H, int W, int Cin, int x_cstride,
-                           int KH, int KW, int stride, int pad, int y_cstride, int act,
-                           const void* res, int res_first, const float* pos) {
-  ConvGemmParams p;
-  p.x = x; p.w = L.w; p.bias = L.bias; p.res = res; p.pos = pos; p.y = y;
-  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.x_cstride = x_cstride;
-  p.OH = (H + 2 * pad - KH) / stride + 1; p.OW = (W + 2 * pad - KW) / stride + 1;
-  p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad;
-  p.N = L.N; p.y_cstride = y_cstride; p.K = L.K; p.Kw = L.Kw; p.M = B * p.OH * p.OW;
-  p.groups = L.groups; p.act = act; p.res_first = res_first; p.log2Cin = ilog2(Cin);
-  p.x2 = nullptr; p.x2_cstride = 0; p.K2 = 0; p.pool2 = 0; p.y_rpi = 0; p.y_row0 = 0;
-  p.w_gstride = 0; p.w_rstride = 0; p.out_f32 = 0; p.y2 = nullptr; p.stats = nullptr;
-  return p;
-}
-
 int tap(EngineBase* h, const std::string& name, const void* src, size_t bytes, bool first, hipStream_t st) {
   if (!first || h->taps.empty()) return 0;
   auto it = h->taps.find(name);
@@ -714,8 +723,11 @@ int tap(EngineBase* h, const std::string& name, const void* src, size_t bytes, b
 }
 
 // kernel ids reported by the profiler (names in fsvit_kernel_name)
-enum { KID_GEMM256 = 0, KID_GEMM64 = 1, KID_GEMM32 = 2, KID_IM2COL = 3, KID_MAXPOOL = 4, KID_ATTN = 5, KID_POOL = 6, KID_HEAD = 7, KID_STAGE1 = 8, KID_GEMM128 = 9, KID_HALO = 12, KID_MLPROWS = 13, KID_QKVATTN = 15, KID_STEMCONV1 = 16, KID_GCONV_X2 = 14, KID_STAGE1RING = 17, KID_LNGEMM = 18, KID_QKVATTNROWS = 19, KID_VITATTNROWS = 20 };
-
+enum {
+  KID_GEMM256 = 0, KID_GEMM64 = 1, KID_GEMM32 = 2, KID_IM2COL = 3, KID_MAXPOOL = 4, KID_ATTN = 5, KID_POOL = 6, KID_HEAD = 7, KID_STAGE1 = 8, KID_GEMM128 = 9,
+  KID_PATCHIFY = 10, KID_LN = 11, KID_HALO = 12, KID_MLPROWS = 13, KID_GCONV_X2 = 14, KID_QKVATTN = 15, KID_STEMCONV1 = 16, KID_STAGE1RING = 17, KID_LNGEMM = 18,
+  KID_QKVATTNROWS = 19, KID_VITATTNROWS = 20
+};
 
 // Runs one launch; in profiling mode brackets it with HIP events on the same stream.
 template <typename F>
@@ -732,10 +744,6 @@ int timed(EngineBase* h, hipStream_t st, const char* layer, int kernel, double f
   return 0;
 }
 
-// images per slice of the dedicated stem (forward_chunk): swept 1600 / 3200 / 6400 / 12 800 on one box - 29.14 / 29.06 / 29.24 / 29.26 ms per 12 800-image step;
-// again with conv1 inside the conv2 kernel (medians of three interleaved rounds): 28.02 / 27.87 / 27.85 / 27.88 - 3200 and up within the run-to-run spread, 3200 stays
-static constexpr int stem_slice_images() { return 3200; }
-
 int run_gemm(EngineBase* h, hipStream_t st, const char* layer, const Layer& L, const ConvGemmParams& p, double n_true, double k_true) {
   const int kdt = h->dtype;
   const double flops = 2.0 * (double)p.M * n_true * k_true * (double)p.groups;     // algorithmic: unpadded N and K
@@ -745,85 +753,140 @@ int run_gemm(EngineBase* h, hipStream_t st, const char* layer, const Layer& L, c
   return timed(h, st, layer, kid, flops, [&]() { return K(launch_conv_gemm)(p, kg(kdt), st); });
 }
 
-// xsrc2 != nullptr: images [0, B1) come from x, images [B1, Bc) from xsrc2 (the shot and query tensors of one MetaBaseline call: one
-// pass over cat([shot, query]) as the reference does, meta_baseline.py:29-32, without materialising the concatenation)
+// ---- the stem driver
+// The images of a chunk: [0, B1) from x, the rest from x2 (the shot and query tensors of one MetaBaseline call: one pass over cat([shot, query]) as the
+// reference does, meta_baseline.py:29-32, without materialising the concatenation); x2 == nullptr: one tensor
+struct ImageSrc { const float* x; const float* x2; int B1; size_t isz; };   // isz: floats per image
+struct ImageRun { const float* src; int a, n; };                            // images [a, a + n) of the chunk, contiguous from src
+// the runs of cat(x[0:B1], x2) that intersect [a, b): one or two, the second (if any) starts at x2
+int image_runs(const ImageSrc& in, int a, int b, ImageRun out[2]) {
+  const int B1 = in.x2 ? in.B1 : b;
+  int n = 0;
+  if (a < B1) out[n++] = ImageRun{in.x + (size_t)a * in.isz, a, (b < B1 ? b : B1) - a};
+  if (b > B1) { const int a2 = a > B1 ? a : B1; out[n++] = ImageRun{in.x2 + (size_t)(a2 - B1) * in.isz, a2, b - a2}; }
+  return n;
+}
+
+// Scratch of ONE slice (at most s.slice images of a chunk of Bc): every slice overwrites the previous one's - in order on one stream, each map is produced
+// and consumed within its slice.  c1: not on STEM_PLANAR_C1F, which never writes it.  pooled: for a caller that consumes the pooled map slice by slice.
+struct StemScratch { void *patches = nullptr, *c1 = nullptr, *c2 = nullptr, *pooled = nullptr; };
+StemScratch stem_scratch(const EvalStem& s, size_t es, size_t Bc, bool pooled, Arena& a) {
+  const size_t n = s.slice && (size_t)s.slice < Bc ? (size_t)s.slice : Bc, P0 = (size_t)s.H0 * s.H0;
+  StemScratch sc;
+  sc.patches = a.take(n * P0 * 32 * es);
+  if (s.route != STEM_PLANAR_C1F) sc.c1 = a.take(n * P0 * s.C0 * es);
+  sc.c2 = a.take(n * P0 * s.C1 * es);
+  if (pooled) sc.pooled = a.take(n * s.H1 * s.H1 * s.C1 * es);
+  return sc;
+}
+
+// The stem of a chunk of Bc images in slices of s.slice.  The dedicated routes run sliced because the two halo convs take ~10 % less per image at
+// 1600 ... 3200-image launches than at 12 800 (measured per launch size, profiles/r06_*; their halo fetch is bound by HBM latency, and a slice's maps are
+// produced and consumed within a few ms), while every later kernel wants the whole chunk.  Per slice [g0, g0 + n): out_of(g0) is where its pooled map
+// [n][H1][H1][C1] goes, after(g0, n, pooled map) runs behind it.
+template <class Out, class After>
+int stem_forward(EngineBase* h, const EvalStem& s, const StemScratch& sc, const ImageSrc& in, int Bc, hipStream_t st, Out&& out_of, After&& after) {
+  const int kdt = h->dtype, dt = kd(kdt);
+  const size_t s_pat = (size_t)s.H0 * s.H0 * 32 * h->es, s_c1 = (size_t)s.H0 * s.H0 * s.C0 * h->es;
+  const double fl1 = 2.0 * 27.0 * s.C0 * s.H0 * s.H0;
+  const bool planar = s.route == STEM_PLANAR || s.route == STEM_PLANAR_C1F, c1f = s.route == STEM_PLANAR_C1F, halo = s.route == STEM_HALO_NHWC;
+  const int S = s.slice ? s.slice : Bc;
+  for (int g0 = 0; g0 < Bc; g0 += S) {
+    const int n = Bc - g0 < S ? Bc - g0 : S;
+    ImageRun runs[2];
+    const int n_runs = image_runs(in, g0, g0 + n, runs);
+    for (int r = 0; r < n_runs && !c1f; ++r) {      // the im2col rows (and, direct, conv1's map) of each run, at the run's place in the slice
+      const ImageRun& run = runs[r];
+      void* pat = (unsigned char*)sc.patches + (run.a - g0) * s_pat;
+      if (s.conv1_direct)
+        RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * run.n, [&]() {
+          return K(launch_stem_conv1)(run.src, pat, (unsigned char*)sc.c1 + (run.a - g0) * s_c1, s.conv1.w, s.conv1.Kw, s.conv1.bias, run.n, st, planar ? 1 : 0); }));
+      else
+        RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() { return K(launch_im2col27)(run.src, pat, run.n, s.img, s.img, s.H0, s.H0, dt, st); }));
+    }
+    if (!c1f && !s.conv1_direct)
+      RC_TRY(run_gemm(h, st, "stem.conv1", s.conv1, conv_params(s.conv1, sc.patches, sc.c1, n, s.H0, s.H0, 32, 32, 1, 1, 1, 0, s.C0, ACT_LRELU, nullptr, 0, nullptr), s.C0, 27));
+    void* out = out_of(g0);
+    ConvGemmParams p2, p3;
+    stem_conv_params(s, planar, sc.c1, sc.c2, sc.patches, out, n, &p2, &p3);
+    if (c1f) {      // conv1 inside the conv2 kernel: it reads the raw images of the slice's runs and stores the patch rows for conv3's tail
+      p2.c1f_raw = runs[0].src; p2.c1f_split = runs[0].n; p2.c1f_raw2 = in.x2;
+      p2.c1f_patches = sc.patches;
+      p2.c1f_w = s.conv1.w; p2.c1f_kw = s.conv1.Kw; p2.c1f_bias = s.conv1.bias;
+      RC_TRY(timed(h, st, "stem.conv2", KID_HALO, 2.0 * (double)p2.M * s.C1 * 9.0 * s.C0 + fl1 * n, [&]() { return K(launch_conv_gemm)(p2, kg(kdt), st); }));
+    } else
+      RC_TRY(run_gemm(h, st, "stem.conv2", halo ? s.conv2h : s.conv2, p2, s.C1, 9.0 * s.C0));
+    RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", halo ? s.conv3h : s.conv3f, p3, s.C1, 9.0 * s.C1 + 27.0));
+    RC_TRY(after(g0, n, out));
+  }
+  return 0;
+}
+
+// ---- Visformer: workspace of a chunk of Bc images.  The residual streams live for the whole chunk; behind them ONE region that the stem scratch of a
+// slice, the stage-1 hidden maps and the stage-2 / 3 scratch (sized for the larger stage) take in turn.
+struct Plan {
+  void *x1, *x1b, *x2, *x3;              // residual streams (x1b: ping-pong partner for the fused stage-1 block)
+  StemScratch stem;
+  void *ha, *hb;                         // stage-1 hidden
+  void *qkv, *ctx, *hid;                 // stage-2/3 scratch
+};
+
+Plan visformer_layout(const fsvit_visformer* h, size_t Bc, Arena& a) {
+  Plan p;
+  const size_t es = h->es, P1 = (size_t)h->H1 * h->H1, P2 = (size_t)h->H2 * h->H2, P3 = (size_t)h->H3 * h->H3;
+  const int heads = h->cfg.num_heads;
+  p.x1 = a.take(Bc * P1 * h->C1 * es);
+  p.x1b = a.take(Bc * P1 * h->C1 * es);
+  p.x2 = a.take(Bc * P2 * h->C2 * es);
+  p.x3 = a.take(Bc * P3 * h->C3 * es);
+  const size_t scratch0 = a.mark();
+  p.stem = stem_scratch(h->stem, es, Bc, false, a);
+  a.rewind(scratch0);
+  p.ha = a.take(Bc * P1 * h->hid1 * es);
+  p.hb = a.take(Bc * P1 * h->hid1 * es);
+  a.rewind(scratch0);
+  size_t q2 = Bc * P2 * 3 * heads * h->hdp2 * es, q3 = Bc * P3 * 3 * heads * h->hdp3 * es;
+  size_t c2 = Bc * P2 * heads * h->hdp2 * es, c3 = Bc * P3 * heads * h->hdp3 * es;
+  size_t h2 = Bc * P2 * h->hid2 * es, h3 = Bc * P3 * h->hid3 * es;
+  p.qkv = a.take(q2 > q3 ? q2 : q3);
+  p.ctx = a.take(c2 > c3 ? c2 : c3);
+  p.hid = a.take(h2 > h3 ? h2 : h3);
+  return p;
+}
+
+// What fsvit_*_workspace_bytes answers: the high-water mark of the encoder's layout run dry.  Monotone in Bc (every buffer grows with Bc or with
+// min(Bc, slice)), which the chunk search of encoder_forward relies on.
+template <class H, class P>
+size_t layout_bytes(P (*layout)(const H*, size_t, Arena&), const EngineBase* h, size_t Bc) {
+  Arena a;
+  a.dry = true;
+  layout(static_cast<const H*>(h), Bc, a);
+  return a.peak;
+}
+// The arena of a chunk whose size the caller has already held against layout_bytes.
+Arena chunk_arena(const void* ws) {
+  Arena a;
+  a.base = (unsigned char*)ws; a.size = SIZE_MAX;
+  return a;
+}
+
+// xsrc2 != nullptr: images [0, B1) come from x, images [B1, Bc) from xsrc2 (ImageSrc)
 int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st,
                   const float* xsrc2 = nullptr, int B1 = 0) {
-  const Plan pl = make_plan(h, Bc);
+  Arena arena = chunk_arena(ws);
+  const Plan pl = visformer_layout(h, Bc, arena);
   const int kdt = h->dtype, dt = kd(kdt);
   const size_t es = h->es;
   const int heads = h->cfg.num_heads;
-  void *patches = ws + pl.patches, *c1 = ws + pl.c1, *c2 = ws + pl.c2;
-  void *x1 = ws + pl.x1, *x1b = ws + pl.x1b, *x2 = ws + pl.x2, *x3 = ws + pl.x3, *ha = ws + pl.ha, *hb = ws + pl.hb;
-  void *qkv = ws + pl.qkv, *ctx = ws + pl.ctx, *hid = ws + pl.hid;
-  const int img = h->cfg.img_size;
+  void *x1 = pl.x1, *x1b = pl.x1b, *x2 = pl.x2, *x3 = pl.x3, *ha = pl.ha, *hb = pl.hb;
+  void *qkv = pl.qkv, *ctx = pl.ctx, *hid = pl.hid;
 
-  // stem: conv1 over the im2col rows, conv2, conv3 + bn3 + (downsample conv + bn_d as a tail K slice over the im2col rows) + LeakyReLU + MaxPool2d(2) + pos_embed1
+  // stem: every slice pools into its rows of x1
   h->prof_last = nullptr;
-  if (!xsrc2) B1 = Bc;
-  const bool conv1_fused = K(stem_conv1_supported)(dt, img, h->C0);      // im2col + conv1 + bn1 + LeakyReLU in one pass over the image
-  // When the whole stem runs on its dedicated kernels (stem_conv1 -> conv3x3_halo -> conv3x3_halo + tail) the two intermediate maps c1 / c2 are
-  // stored row-chunk-planar (conv_gemm.h x_planar): the halo fetch of the consumer then reads row segments instead of 16 bytes of every 128-byte line
-  ConvGemmParams p2 = conv_params(h->conv2, c1, c2, Bc, h->H0, h->H0, h->C0, h->C0, 3, 3, 1, 1, h->C1, ACT_LRELU, nullptr, 0, nullptr);
-  ConvGemmParams p3 = conv_params(h->conv3f, c2, x1, Bc, h->H0, h->H0, h->C1, h->C1, 3, 3, 1, 1, h->C1, ACT_LRELU, nullptr, 0, h->pos1);
-  p3.x2 = patches; p3.x2_cstride = 32; p3.K2 = 32; p3.pool2 = 1;
-  const bool planar = conv1_fused && K(conv_gemm_route)(p2, kg(kdt)) == 0 && K(conv_gemm_route)(p3, kg(kdt)) == 0;
-  p2.x_planar = p2.y_planar = p3.x_planar = planar ? 1 : 0;
-  if (planar) {
-    // The dedicated stem runs in SLICES of the chunk (stem_conv1 -> conv2 -> conv3 + tail per slice of STEM_SLICE images): the two halo convs take
-    // ~10 % less per image at 1600 ... 3200-image launches than at 12 800 (measured per launch size, profiles/r06_*; their halo fetch is bound by HBM
-    // latency, and a slice's maps are produced and consumed within a few ms), while every later kernel wants the whole chunk.
-    const int S = stem_slice_images();
-    const size_t s_pat = (size_t)h->H0 * h->H0 * 32 * es, s_c1 = (size_t)h->H0 * h->H0 * h->C0 * es, s_c2 = (size_t)h->H0 * h->H0 * h->C1 * es,
-                 s_x1 = (size_t)h->H1 * h->H1 * h->C1 * es;
-    const double fl1 = 2.0 * 27.0 * h->C0 * h->H0 * h->H0;
-    // conv1 inside the conv2 kernel (conv3x3_halo.hip, C1F): no stem_conv1 launch, c1 is never written; conv2 stores the patch rows for conv3's tail
-    const bool fuse_c1 = h->stem_fuse_c1 && K(conv3x3_halo_c1f_supported)(p2, kg(kdt)) && img == 80;
-    for (int g0 = 0; g0 < Bc; g0 += S) {
-      const int g1 = g0 + S < Bc ? g0 + S : Bc;
-      for (int part = 0; part < 2 && !fuse_c1; ++part) {   // images [g0, g1) of cat([shot, query]): [0, B1) from x, [B1, Bc) from xsrc2
-        const int a = part == 0 ? g0 : (g0 > B1 ? g0 : B1), b = part == 0 ? (g1 < B1 ? g1 : B1) : g1;
-        if (a >= b) continue;
-        const float* src = part == 0 ? x + (size_t)a * 3 * img * img : xsrc2 + (size_t)(a - B1) * 3 * img * img;
-        RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * (b - a), [&]() {
-          return K(launch_stem_conv1)(src, (unsigned char*)patches + a * s_pat, (unsigned char*)c1 + a * s_c1, h->conv1.w, h->conv1.Kw, h->conv1.bias, b - a, st, 1); }));
-      }
-      ConvGemmParams q2 = p2, q3 = p3;
-      q2.x = (const unsigned char*)c1 + g0 * s_c1; q2.y = (unsigned char*)c2 + g0 * s_c2; q2.B = g1 - g0; q2.M = (g1 - g0) * q2.OH * q2.OW;
-      q3.x = (const unsigned char*)c2 + g0 * s_c2; q3.x2 = (const unsigned char*)patches + g0 * s_pat; q3.y = (unsigned char*)x1 + g0 * s_x1;
-      q3.B = g1 - g0; q3.M = (g1 - g0) * q3.OH * q3.OW;
-      if (fuse_c1) {                                       // images [g0, g1) of cat([shot, query]): the first c1f_split of them from x, the rest from xsrc2
-        const size_t isz = (size_t)3 * img * img;
-        q2.c1f_raw = g0 < B1 ? x + g0 * isz : xsrc2 + (size_t)(g0 - B1) * isz;
-        q2.c1f_split = g0 < B1 ? (g1 < B1 ? g1 : B1) - g0 : g1 - g0;
-        q2.c1f_raw2 = xsrc2;
-        q2.c1f_patches = (unsigned char*)patches + g0 * s_pat;
-        q2.c1f_w = h->conv1.w; q2.c1f_kw = h->conv1.Kw; q2.c1f_bias = h->conv1.bias;
-        RC_TRY(timed(h, st, "stem.conv2", KID_HALO, 2.0 * (double)q2.M * h->C1 * 9.0 * h->C0 + fl1 * (g1 - g0), [&]() { return K(launch_conv_gemm)(q2, kg(kdt), st); }));
-      } else
-      RC_TRY(run_gemm(h, st, "stem.conv2", h->conv2, q2, h->C1, 9.0 * h->C0));
-      RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, q3, h->C1, 9.0 * h->C1 + 27.0));
-    }
-  } else {      // the general route: other image sizes, geometries and numerics modes
-    if (conv1_fused) {
-      const double fl1 = 2.0 * 27.0 * h->C0 * h->H0 * h->H0;
-      RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * B1, [&]() {
-        return K(launch_stem_conv1)(x, patches, c1, h->conv1.w, h->conv1.Kw, h->conv1.bias, B1, st, 0); }));
-      if (Bc > B1)
-        RC_TRY(timed(h, st, "stem.im2col+conv1", KID_STEMCONV1, fl1 * (Bc - B1), [&]() {
-          return K(launch_stem_conv1)(xsrc2, (unsigned char*)patches + (size_t)B1 * h->H0 * h->H0 * 32 * es, (unsigned char*)c1 + (size_t)B1 * h->H0 * h->H0 * h->C0 * es,
-                                   h->conv1.w, h->conv1.Kw, h->conv1.bias, Bc - B1, st, 0); }));
-    } else {
-      RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() { return K(launch_im2col27)(x, patches, B1, img, img, h->H0, h->H0, dt, st); }));
-      if (Bc > B1)
-        RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() {
-          return K(launch_im2col27)(xsrc2, (unsigned char*)patches + (size_t)B1 * h->H0 * h->H0 * 32 * es, Bc - B1, img, img, h->H0, h->H0, dt, st); }));
-      RC_TRY(run_gemm(h, st, "stem.conv1", h->conv1, conv_params(h->conv1, patches, c1, Bc, h->H0, h->H0, 32, 32, 1, 1, 1, 0, h->C0, ACT_LRELU, nullptr, 0, nullptr), h->C0, 27));
-    }
-    RC_TRY(run_gemm(h, st, "stem.conv2", h->conv2, p2, h->C1, 9.0 * h->C0));
-    RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", h->conv3f, p3, h->C1, 9.0 * h->C1 + 27.0));
-  }
-  RC_TRY(tap(h, "stem", x1, (size_t)Bc * h->H1 * h->H1 * h->C1 * es, first, st));
+  const size_t s_x1 = (size_t)h->H1 * h->H1 * h->C1 * es;
+  RC_TRY(stem_forward(h, h->stem, pl.stem, ImageSrc{x, xsrc2, B1, (size_t)3 * h->stem.img * h->stem.img}, Bc, st,
+                      [&](int g0) { return (void*)((unsigned char*)x1 + g0 * s_x1); }, [](int, int, void*) { return 0; }));
+  RC_TRY(tap(h, "stem", x1, (size_t)Bc * s_x1, first, st));
 
   // stage 1: x += conv3(GELU(conv2_g(GELU(conv1(BN(x))))))
   const int Cg = h->hid1 / h->cfg.group;
@@ -902,7 +965,7 @@ int forward_chunk(fsvit_visformer* h, const float* x, int Bc, float* feat, unsig
   return 0;
 }
 
-size_t visformer_plan_bytes(const EngineBase* h, size_t Bc) { return make_plan(static_cast<const fsvit_visformer*>(h), Bc).total; }
+size_t visformer_plan_bytes(const EngineBase* h, size_t Bc) { return layout_bytes(visformer_layout, h, Bc); }
 int visformer_chunk(EngineBase* h, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
   return forward_chunk(static_cast<fsvit_visformer*>(h), x, Bc, feat, ws, first, st);
 }
@@ -1000,9 +1063,9 @@ extern "C" int fsvit_visformer_forward(fsvit_visformer* h, const float* x, int n
 extern "C" int fsvit_visformer_last_tokens(fsvit_visformer* h, const void* ws, size_t ws_bytes, int n_img, float* tokens, void* stream) {
   const int kdt = h ? h->dtype : FSVIT_BF16;
   if (!h || !ws || !tokens || n_img <= 0) return fail(FSVIT_ERR_ARG, "bad argument");
-  const Plan pl = make_plan(h, (size_t)n_img);
-  if (pl.total > ws_bytes) return fail(FSVIT_ERR_WORKSPACE, "last_tokens: the forward of %d images did not fit one chunk of this workspace", n_img);
-  RC_TRY(K(launch_tokens_to_f32)((const unsigned char*)ws + pl.x3, h->fscale, h->fshift, tokens, (size_t)n_img * h->H3 * h->H3 * h->C3, h->C3, kd(kdt),
+  if (visformer_plan_bytes(h, (size_t)n_img) > ws_bytes) return fail(FSVIT_ERR_WORKSPACE, "last_tokens: the forward of %d images did not fit one chunk of this workspace", n_img);
+  Arena arena = chunk_arena(ws);
+  RC_TRY(K(launch_tokens_to_f32)(visformer_layout(h, (size_t)n_img, arena).x3, h->fscale, h->fshift, tokens, (size_t)n_img * h->H3 * h->H3 * h->C3, h->C3, kd(kdt),
                               (hipStream_t)stream));
   return 0;
 }
@@ -1137,7 +1200,7 @@ extern "C" int fsvit_meta_baseline_forward(void* hv, const float* x_shot, const 
       fsvit_visformer* h = static_cast<fsvit_visformer*>(eb);
       if (img_h != h->cfg.img_size || img_w != h->cfg.img_size)
         return fail(FSVIT_ERR_IMG_SIZE, SIZE_FMT_VISFORMER, img_h, img_w, h->cfg.img_size, h->cfg.img_size);
-      if (ws && ((uintptr_t)ws & 255) == 0 && make_plan(h, (size_t)ns + nq).total <= ws_bytes) {
+      if (ws && ((uintptr_t)ws & 255) == 0 && visformer_plan_bytes(h, (size_t)ns + nq) <= ws_bytes) {
         int rc1 = forward_chunk(h, x_shot, ns + nq, feat, (unsigned char*)ws, true, (hipStream_t)stream, x_query, ns);
         if (rc1 != 0) return rc1;
         return fsvit_proto_head(feat, feat + (size_t)ns * D, E, way, shot, Q, D, temp, method, logits, acc, loss, stream);
@@ -1719,24 +1782,19 @@ int build_vit(fsvit_vit* h, const SD& sd) {
   return pack_vit_blocks(h, sd, cf.depth, D, heads, h->hd, h->hdp, h->hid, h->S, true, 1.0, &h->blocks);
 }
 
-struct VitPlan { size_t patches, tokens, xn, qkv, ctx, hid, total; };
+struct VitPlan { void *patches, *tokens, *xn, *qkv, *ctx, *hid; };
 
-VitPlan make_vit_plan(const fsvit_vit* h, size_t Bc) {
+VitPlan vit_layout(const fsvit_vit* h, size_t Bc, Arena& a) {
   VitPlan p;
   const size_t es = h->es;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  p.tokens = take(Bc * h->S * h->D * es);
-  p.xn = take(Bc * h->S * h->D * es);
-  p.qkv = take(Bc * h->S * 3 * h->cfg.num_heads * h->hdp * es);
-  p.ctx = take(Bc * h->S * h->cfg.num_heads * h->hdp * es);
+  p.tokens = a.take(Bc * h->S * h->D * es);
+  p.xn = a.take(Bc * h->S * h->D * es);
+  p.qkv = a.take(Bc * h->S * 3 * h->cfg.num_heads * h->hdp * es);
+  p.ctx = a.take(Bc * h->S * h->cfg.num_heads * h->hdp * es);
   const size_t pb = Bc * h->np * h->Kp * es, hb = Bc * h->S * h->hid * es;      // patches are dead once the tokens exist
-  p.patches = p.hid = take(pb > hb ? pb : hb);
-  p.total = off;
+  p.patches = p.hid = a.take(pb > hb ? pb : hb);
   return p;
 }
-
-enum { KID_PATCHIFY = 10, KID_LN = 11 };
 
 // The encoder blocks of a pre-LN ViT (DeiT, LV-ViT) on the token rows `tokens` [Bc * S][D], in place; taps blocks.<i>.
 int vit_blocks_forward(EngineBase* h, const std::vector<VitBlock>& blocks, void* tokens, void* xn, void* qkv, void* ctx, void* hid, int Bc, int S,
@@ -1779,14 +1837,15 @@ int vit_blocks_forward(EngineBase* h, const std::vector<VitBlock>& blocks, void*
   return 0;
 }
 
-size_t vit_plan_bytes(const EngineBase* h, size_t Bc) { return make_vit_plan(static_cast<const fsvit_vit*>(h), Bc).total; }
+size_t vit_plan_bytes(const EngineBase* h, size_t Bc) { return layout_bytes(vit_layout, h, Bc); }
 
 int vit_forward_chunk(EngineBase* hb, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
   fsvit_vit* h = static_cast<fsvit_vit*>(hb);
-  const VitPlan pl = make_vit_plan(h, Bc);
+  Arena arena = chunk_arena(ws);
+  const VitPlan pl = vit_layout(h, Bc, arena);
   const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, heads = h->cfg.num_heads, hdp = h->hdp;
   const size_t es = h->es;
-  void *patches = ws + pl.patches, *tokens = ws + pl.tokens, *xn = ws + pl.xn, *qkv = ws + pl.qkv, *ctx = ws + pl.ctx, *hid = ws + pl.hid;
+  void *patches = pl.patches, *tokens = pl.tokens, *xn = pl.xn, *qkv = pl.qkv, *ctx = pl.ctx, *hid = pl.hid;
   const int M = Bc * S;
   h->prof_last = nullptr;
   RC_TRY(timed(h, st, "patch_embed.patchify", KID_PATCHIFY, 0.0, [&]() { return K(launch_patchify)(x, patches, Bc, h->cfg.img_size, h->cfg.patch_size, h->Kp, dt, st); }));
@@ -1820,14 +1879,15 @@ extern "C" int fsvit_vit_forward(fsvit_vit* h, const float* x, int n_img, int im
 // meta_tuning_sun_m/models/lvvit.py:277-318, :413-546 (factory lvvit_micro_80, :583).  The stem is the Visformer ConvBlock at stem_channels
 // (conv1 s2 | conv2 | conv3 + downsample identity, eval BatchNorm folded, LeakyReLU(0.1), MaxPool2d(2)) followed by a 4 x 4 / stride 4 Conv2d
 // projection to embed_dim; cls token + pos_embed; pre-LN blocks with skip_lam; features = norm(x)[:, 0].
-// Stem route: im2col27 + a K = 32 GEMM for conv1; conv2 and conv3 (+ downsample as the tail K slice over the same im2col rows + LeakyReLU +
-// MaxPool2d) on conv_gemm_v2 (a 96-channel map is no power of two: the tap is found per K chunk by division); the projection is the same
-// implicit GEMM as a 4 x 4 / stride 4 conv over the pooled NHWC map, writing token rows 1..np of every image with bias + pos_embed[1:].
+// Stem (EvalStem): im2col27 + a K = 32 GEMM for conv1; conv2 and conv3 (+ downsample as the tail K slice over the same im2col rows + LeakyReLU +
+// MaxPool2d) on the dedicated conv3x3_halo instantiation in bf16 / f16 at 96 channels (STEM_HALO_NHWC), on conv_gemm_v2 otherwise (a 96-channel map is
+// no power of two: the tap is found per K chunk by division); the projection is the same implicit GEMM as a 4 x 4 / stride 4 conv over the pooled
+// NHWC map of a slice, writing token rows 1..np of every image with bias + pos_embed[1:].
 struct fsvit_lvvit : EngineBase {
   fsvit_lvvit_cfg cfg;
-  int C0 = 0, D = 0, H0 = 0, H1 = 0, npw = 0, np = 0, S = 0, hd = 0, hdp = 0, hid = 0;
-  Layer conv1, conv2, conv3f, pe;
-  Layer conv2h, conv3h;        // bf16 / f16 at 96 channels: the 128-channel weight images of conv2 / conv3f for conv3x3_halo (w = nullptr: not built)
+  int C0 = 0, D = 0, H1 = 0, npw = 0, np = 0, S = 0, hd = 0, hdp = 0, hid = 0;
+  EvalStem stem;
+  Layer pe;
   float *pos_patch = nullptr, *cls_pos0 = nullptr, *ng = nullptr, *nb = nullptr;
   std::vector<VitBlock> blocks;
   float* map_out = nullptr;    // fsvit_lvvit_forward_map: where the next chunk's patch rows [Bc][S - 1][D] go (advanced chunk by chunk); null: cls feature only
@@ -1844,63 +1904,17 @@ int build_lvvit(fsvit_lvvit* h, const SD& sd) {
   if (D % heads || D % 32) return fail(FSVIT_ERR_ARG, "unsupported LV-ViT geometry");
   if (!(cf.skip_lam > 0.0f)) return fail(FSVIT_ERR_ARG, "skip_lam must be positive");
   h->C0 = C0; h->D = h->out_dim = D;
-  h->H0 = cf.img_size / 2; h->H1 = cf.img_size / 4; h->npw = h->H1 / 4; h->np = h->npw * h->npw; h->S = h->np + 1;
+  h->H1 = cf.img_size / 4; h->npw = h->H1 / 4; h->np = h->npw * h->npw; h->S = h->np + 1;
   h->hd = D / heads; h->hdp = round_up(h->hd, kch); h->hid = (int)(D * cf.mlp_ratio);
   if (h->hid % 32) return fail(FSVIT_ERR_ARG, "hidden width must be a multiple of 32");
   if (h->S > (h->es == 4 ? 208 : 224)) return fail(FSVIT_ERR_ARG, "attention supports at most %d tokens", h->es == 4 ? 208 : 224);
-  const double eps = cf.bn_eps;
-  {   // ---- stem: BatchNorm folded exactly as build() folds the Visformer stem's
-    const float* w1 = sd.get("patch_embed.conv1.weight", {C0, 3, 3, 3});
-    const float* wd = sd.get("patch_embed.downsample.0.weight", {C0, 3, 3, 3});
-    const float* w2 = sd.get("patch_embed.conv2.weight", {C0, C0, 3, 3});
-    const float* w3 = sd.get("patch_embed.conv3.weight", {C0, C0, 3, 3});
+  {   // ---- stem (no position table, no weight-rounding correction, conv1 always im2col27 + GEMM, every route sliced) and the 4 x 4 projection
     const float* wp = sd.get("patch_embed.proj.weight", {D, C0, 4, 4});
     const float* bp = sd.get("patch_embed.proj.bias", {D});
-    Affine b1 = bn_affine(sd, "patch_embed.bn1", C0, eps), b2 = bn_affine(sd, "patch_embed.bn2", C0, eps);
-    Affine b3 = bn_affine(sd, "patch_embed.bn3", C0, eps), bd = bn_affine(sd, "patch_embed.downsample.1", C0, eps);
-    if (!w1 || !wd || !w2 || !w3 || !wp || !bp || !b1.ok || !b2.ok || !b3.ok || !bd.ok) return FSVIT_ERR_KEY;
-    std::vector<int> cm(27);
-    for (int k = 0; k < 27; ++k) cm[k] = k;
-    RC_TRY(pack_layer(h, &h->conv1, w1, C0, 3, 3, 3, 1, &b1.s, nullptr, b1.t, true, nullptr, 0, &cm, 32));
-    RC_TRY(pack_layer(h, &h->conv2, w2, C0, C0, 3, 3, 1, &b2.s, nullptr, b2.t, true, nullptr, 0, nullptr, 0));
-    {  // conv3f rows = [ bn3-scaled conv3 (K = 9*C0, padded to the K slice) | one tail slice: bn_d-scaled downsample taps ]
-      const int bke = 128 / h->es, K = 9 * C0, Kmain = round_up(K, bke), Kw = Kmain + bke;
-      std::vector<float> pk((size_t)C0 * Kw, 0.0f), pb(C0);
-      for (int o = 0; o < C0; ++o) {
-        for (int c = 0; c < C0; ++c)
-          for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + t9 * C0 + c] = (float)((double)w3[((size_t)o * C0 + c) * 9 + t9] * b3.s[o]);
-        for (int c = 0; c < 3; ++c)
-          for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + Kmain + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
-        pb[o] = (float)(b3.t[o] + bd.t[o]);
-      }
-      h->conv3f.N = C0; h->conv3f.K = K; h->conv3f.Kw = Kw; h->conv3f.groups = 1;
-      RC_TRY(upload(h, pk, true, &h->conv3f.w));
-      void* bdev; RC_TRY(upload(h, pb, false, &bdev)); h->conv3f.bias = (float*)bdev;
-    }
+    if (!wp || !bp) return FSVIT_ERR_KEY;
+    RC_TRY(pack_stem(h, sd, "patch_embed.", C0, C0, cf.img_size, cf.bn_eps, nullptr, nullptr, false, stem_slice_images(), &h->stem));
     std::vector<double> bias(bp, bp + D);
     RC_TRY(pack_layer(h, &h->pe, wp, D, C0, 4, 4, 1, nullptr, nullptr, bias, true, nullptr, 0, nullptr, 0));   // K = (ky, kx, c): 16 taps of C0
-    // FSVIT_LVVIT_STEM=gemm (read once per build): conv2 / conv3 stay on conv_gemm_v2 - the A/B switch of tools/bench_lvvit.py
-    const char* stem_env = getenv("FSVIT_LVVIT_STEM");
-    if (kd(h->dtype) == 1 && C0 == 96 && !(stem_env && strcmp(stem_env, "gemm") == 0)) {
-      // conv3x3_halo's images (ConvGemmParams::w_cpad = 128): 128 rows, k = tap * 128 + c, zeros past the 96 channels / rows; conv3's tail slice of
-      // downsample taps behind the 9 * 128 main columns.  Same folded values as conv2 / conv3f (the bias tables are shared: 96 entries).
-      for (int which = 0; which < 2; ++which) {
-        const int Kw = 9 * 128 + (which ? 64 : 0);
-        std::vector<float> pk((size_t)128 * Kw, 0.0f);
-        for (int o = 0; o < C0; ++o) {
-          const double so = which ? b3.s[o] : b2.s[o];
-          const float* w = which ? w3 : w2;
-          for (int c = 0; c < C0; ++c)
-            for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + t9 * 128 + c] = (float)((double)w[((size_t)o * C0 + c) * 9 + t9] * so);
-          if (which)
-            for (int c = 0; c < 3; ++c)
-              for (int t9 = 0; t9 < 9; ++t9) pk[(size_t)o * Kw + 9 * 128 + t9 * 3 + c] = (float)((double)wd[((size_t)o * 3 + c) * 9 + t9] * bd.s[o]);
-        }
-        Layer& L = which ? h->conv3h : h->conv2h;
-        L.N = C0; L.K = 9 * C0; L.Kw = Kw; L.groups = 1; L.bias = which ? h->conv3f.bias : h->conv2.bias;
-        RC_TRY(upload(h, pk, true, &L.w));
-      }
-    }
   }
   {
     const float* cls = sd.get("cls_token", {1, 1, D});
@@ -1914,65 +1928,45 @@ int build_lvvit(fsvit_lvvit* h, const SD& sd) {
 }
 
 // Workspace of a chunk of Bc images: the token rows, then ONE region shared by the stem scratch of a slice (im2col rows, conv1 / conv2 maps and
-// the pooled map of at most stem_slice_images() images - sized per slice, not per chunk) and the block scratch of the whole chunk.
-struct LvvitPlan { size_t tokens, patches, c1, c2, p1, xn, qkv, ctx, hid, total; int slice; };
+// the pooled map) and the block scratch of the whole chunk.
+struct LvvitPlan { void* tokens; StemScratch stem; void *xn, *qkv, *ctx, *hid; };
 
-LvvitPlan make_lvvit_plan(const fsvit_lvvit* h, size_t Bc) {
+LvvitPlan lvvit_layout(const fsvit_lvvit* h, size_t Bc, Arena& a) {
   LvvitPlan p;
-  const size_t es = h->es, P0 = (size_t)h->H0 * h->H0, P1 = (size_t)h->H1 * h->H1, heads = h->cfg.num_heads;
-  const size_t Ss = Bc < (size_t)stem_slice_images() ? Bc : (size_t)stem_slice_images();
-  p.slice = (int)Ss;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align256(bytes); return o; };
-  p.tokens = take(Bc * h->S * h->D * es);
-  const size_t scratch0 = off;
-  p.patches = take(Ss * P0 * 32 * es);
-  p.c1 = take(Ss * P0 * h->C0 * es);
-  p.c2 = take(Ss * P0 * h->C0 * es);
-  p.p1 = take(Ss * P1 * h->C0 * es);
-  size_t hi = off;
-  off = scratch0;
-  p.xn = take(Bc * h->S * h->D * es);
-  p.qkv = take(Bc * h->S * 3 * heads * h->hdp * es);
-  p.ctx = take(Bc * h->S * heads * h->hdp * es);
-  p.hid = take(Bc * h->S * h->hid * es);
-  p.total = off > hi ? off : hi;
+  const size_t es = h->es, heads = h->cfg.num_heads;
+  p.tokens = a.take(Bc * h->S * h->D * es);
+  const size_t scratch0 = a.mark();
+  p.stem = stem_scratch(h->stem, es, Bc, true, a);
+  a.rewind(scratch0);
+  p.xn = a.take(Bc * h->S * h->D * es);
+  p.qkv = a.take(Bc * h->S * 3 * heads * h->hdp * es);
+  p.ctx = a.take(Bc * h->S * heads * h->hdp * es);
+  p.hid = a.take(Bc * h->S * h->hid * es);
   return p;
 }
 
-size_t lvvit_plan_bytes(const EngineBase* h, size_t Bc) { return make_lvvit_plan(static_cast<const fsvit_lvvit*>(h), Bc).total; }
+size_t lvvit_plan_bytes(const EngineBase* h, size_t Bc) { return layout_bytes(lvvit_layout, h, Bc); }
 
 int lvvit_forward_chunk(EngineBase* hb, const float* x, int Bc, float* feat, unsigned char* ws, bool first, hipStream_t st) {
   fsvit_lvvit* h = static_cast<fsvit_lvvit*>(hb);
-  const LvvitPlan pl = make_lvvit_plan(h, Bc);
-  const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, C0 = h->C0, heads = h->cfg.num_heads, img = h->cfg.img_size;
+  Arena arena = chunk_arena(ws);
+  const LvvitPlan pl = lvvit_layout(h, Bc, arena);
+  const int kdt = h->dtype, dt = kd(kdt), D = h->D, S = h->S, C0 = h->C0, heads = h->cfg.num_heads;
   const size_t es = h->es;
-  void *tokens = ws + pl.tokens, *patches = ws + pl.patches, *c1 = ws + pl.c1, *c2 = ws + pl.c2, *p1 = ws + pl.p1;
+  void* tokens = pl.tokens;
   h->prof_last = nullptr;
-  for (int g0 = 0; g0 < Bc; g0 += pl.slice) {
-    const int n = Bc - g0 < pl.slice ? Bc - g0 : pl.slice;
-    const float* src = x + (size_t)g0 * 3 * img * img;
-    RC_TRY(timed(h, st, "stem.im2col", KID_IM2COL, 0.0, [&]() { return K(launch_im2col27)(src, patches, n, img, img, h->H0, h->H0, dt, st); }));
-    RC_TRY(run_gemm(h, st, "stem.conv1", h->conv1, conv_params(h->conv1, patches, c1, n, h->H0, h->H0, 32, 32, 1, 1, 1, 0, C0, ACT_LRELU, nullptr, 0, nullptr), C0, 27));
-    // conv2 and conv3 (+ downsample tail + LeakyReLU + MaxPool2d): the dedicated conv3x3_halo instantiation in bf16 / f16, conv_gemm_v2 otherwise
-    const bool halo = h->conv2h.w && h->conv3h.w;
-    const Layer& L2 = halo ? h->conv2h : h->conv2;
-    const Layer& L3 = halo ? h->conv3h : h->conv3f;
-    ConvGemmParams p2 = conv_params(L2, c1, c2, n, h->H0, h->H0, C0, C0, 3, 3, 1, 1, C0, ACT_LRELU, nullptr, 0, nullptr);
-    ConvGemmParams p3 = conv_params(L3, c2, p1, n, h->H0, h->H0, C0, C0, 3, 3, 1, 1, C0, ACT_LRELU, nullptr, 0, nullptr);
-    p3.x2 = patches; p3.x2_cstride = 32; p3.K2 = 32; p3.pool2 = 1;
-    if (halo) p2.w_cpad = p3.w_cpad = 128;
-    RC_TRY(run_gemm(h, st, "stem.conv2", L2, p2, C0, 9.0 * C0));
-    RC_TRY(run_gemm(h, st, "stem.conv3+down+pool", L3, p3, C0, 9.0 * C0 + 27.0));
+  // stem: every slice pools into the slice's own map, which the 4 x 4 projection turns into the token rows of its images
+  RC_TRY(stem_forward(h, h->stem, pl.stem, ImageSrc{x, nullptr, Bc, (size_t)3 * h->stem.img * h->stem.img}, Bc, st, [&](int) { return pl.stem.pooled; },
+                      [&](int g0, int n, void* p1) {
     if (g0 == 0) RC_TRY(tap(h, "stem", p1, (size_t)n * h->H1 * h->H1 * C0 * es, first, st));
     ConvGemmParams pp = conv_params(h->pe, p1, (unsigned char*)tokens + (size_t)g0 * S * D * es, n, h->H1, h->H1, C0, C0, 4, 4, 4, 0, D, ACT_NONE, nullptr, 0,
                                     h->pos_patch);
     pp.y_rpi = S; pp.y_row0 = 1;                                 // patch token i of image b -> row b*S + 1 + i
-    RC_TRY(run_gemm(h, st, "patch_embed.proj", h->pe, pp, D, 16.0 * C0));
-  }
+    return run_gemm(h, st, "patch_embed.proj", h->pe, pp, D, 16.0 * C0);
+  }));
   RC_TRY(timed(h, st, "cls_token", KID_PATCHIFY, 0.0, [&]() { return K(launch_cls_pos)(h->cls_pos0, tokens, Bc, S, D, dt, st); }));
   RC_TRY(tap(h, "embed", tokens, (size_t)Bc * S * D * es, first, st));
-  RC_TRY(vit_blocks_forward(h, h->blocks, tokens, ws + pl.xn, ws + pl.qkv, ws + pl.ctx, ws + pl.hid, Bc, S, D, heads, h->hd, h->hdp, h->hid,
+  RC_TRY(vit_blocks_forward(h, h->blocks, tokens, pl.xn, pl.qkv, pl.ctx, pl.hid, Bc, S, D, heads, h->hd, h->hdp, h->hid,
                             h->cfg.ln_eps, first, st));
   if (h->map_out) {
     float* map = h->map_out;

@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,47 +16,19 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "kernels.h"
 #include "train_kernels.h"
 
 using namespace fsvit;
 
-extern "C" const char* fsvit_last_error(void);
-int fsvit_set_error(int code, const char* fmt, ...);      // engine.hip
-
-#define T_TRY(expr)                                                                     \
-  do {                                                                                  \
-    int _rc = (expr);                                                                   \
-    if (_rc != 0) return _rc > 0 ? fsvit_set_error(_rc, "%s: %s", #expr, hipGetErrorString((hipError_t)_rc)) : _rc; \
-  } while (0)
-
 // launches are skipped in the sizing pass (dry arenas hand out fake addresses)
-#define T_RUN(expr)                                                                     \
-  do {                                                                                  \
-    if (!t->save.dry) {                                                                 \
-      int _rc = (expr);                                                                 \
-      if (_rc != 0) return _rc > 0 ? fsvit_set_error(_rc, "%s: %s", #expr, hipGetErrorString((hipError_t)_rc)) : _rc; \
-    }                                                                                   \
+#define T_RUN(expr)                                   \
+  do {                                                \
+    if (!t->save.dry) RC_TRY_AS(expr, #expr);         \
   } while (0)
 
 namespace {
-
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-struct Arena {
-  unsigned char* base = nullptr;
-  size_t size = 0, off = 0, peak = 0;
-  bool dry = false;                       // dry run: only measure
-  void* take(size_t bytes) {
-    size_t o = off;
-    off += align256(bytes);
-    if (off > peak) peak = off;
-    if (dry) return (void*)(uintptr_t)(o + 256);
-    return off <= size ? base + o : nullptr;
-  }
-};
 
 struct ConvSpec {                         // one nn.Conv2d of the model (PyTorch layout weight [O][Ig][KH][KW])
   std::string wname;
@@ -271,7 +242,7 @@ int conv_fwd(TB* t, const ConvSpec& c, const void* x, int B, int H, int W, void*
   if (!w) return FSVIT_ERR_KEY;
   const int bke = 128 / t->es, Ng = c.rows_fwd(), K = c.kpad_cols(), Kw = round_up(K, bke);
   void* pk = nullptr;
-  T_TRY(packed_weight(t, PackJob{w->data, nullptr, c.O, c.Ig, c.KH, c.KW, c.groups, 0, Ng, Kw, c.hd_rows, c.hdp_rows, c.hd_cols, c.hdp_cols},
+  RC_TRY(packed_weight(t, PackJob{w->data, nullptr, c.O, c.Ig, c.KH, c.KW, c.groups, 0, Ng, Kw, c.hd_rows, c.hdp_rows, c.hd_cols, c.hdp_cols},
                       (size_t)c.groups * Ng * Kw * t->es, &pk));
   if (!bias && !c.via_patches && gconv3x3_supported(t->dtype, c.O, c.Ig, c.groups, c.KH, c.KW, c.stride, c.pad, W)) {
     T_RUN(launch_gconv3x3(x, pk, Kw, z, B, H, W, t->st, gp));      // wave = group, weights in registers (wgrad3x3.hip)
@@ -317,9 +288,9 @@ int conv_bwd_data(TB* t, const ConvSpec& c, const void* dz, int B, int OH, int O
   const int K = c.KH * c.KW * Ng_pad, Kw = round_up(K, bke);
   // rows = input channels (padded like the forward K columns), K = output channels (padded like the forward rows)
   void* pk = nullptr;
-  T_TRY(packed_weight(t, PackJob{w->data, nullptr, c.O, c.Ig, c.KH, c.KW, c.groups, 1, Ig_pad, Kw, c.hd_cols, c.hdp_cols, c.hd_rows, c.hdp_rows},
+  RC_TRY(packed_weight(t, PackJob{w->data, nullptr, c.O, c.Ig, c.KH, c.KW, c.groups, 1, Ig_pad, Kw, c.hd_cols, c.hdp_cols, c.hd_rows, c.hdp_rows},
                       (size_t)c.groups * Ig_pad * Kw * t->es, &pk));
-  T_TRY(side_guard(t, dx, (size_t)B * OH * OW * c.groups * Ig_pad * t->es));
+  RC_TRY(side_guard(t, dx, (size_t)B * OH * OW * c.groups * Ig_pad * t->es));
   if (gconv3x3_supported(t->dtype, c.O, c.Ig, c.groups, c.KH, c.KW, c.stride, c.pad, OW) && Ng_pad == 32 && Ig_pad == 32) {
     T_RUN(launch_gconv3x3(dz, pk, Kw, dx, B, OH, OW, t->st, nullptr, mul));      // the same kernel on the transposed, tap-flipped pack
     return 0;
@@ -335,22 +306,22 @@ int side_begin(TB* t) {                       // the side stream may start once 
   if (!t->sides[0]) {
     static const int n = [] { const char* e = getenv("FSVIT_SIDE_STREAMS"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > TB::MAX_SIDE ? TB::MAX_SIDE : v); }();
     t->n_side = n;
-    for (int i = 0; i < n; ++i) T_TRY((int)hipStreamCreateWithFlags(&t->sides[i], hipStreamNonBlocking));
-    T_TRY((int)hipEventCreateWithFlags(&t->ev_a, hipEventDisableTiming));
+    for (int i = 0; i < n; ++i) RC_TRY((int)hipStreamCreateWithFlags(&t->sides[i], hipStreamNonBlocking));
+    RC_TRY((int)hipEventCreateWithFlags(&t->ev_a, hipEventDisableTiming));
   }
   t->side = t->sides[t->side_seq % t->n_side];
-  T_TRY((int)hipEventRecord(t->ev_a, t->st));
-  T_TRY((int)hipStreamWaitEvent(t->side, t->ev_a, 0));
+  RC_TRY((int)hipEventRecord(t->ev_a, t->st));
+  RC_TRY((int)hipStreamWaitEvent(t->side, t->ev_a, 0));
   return 0;
 }
 // behind a side launch: its completion event, and the byte ranges it reads
 int side_end(TB* t, const void* p0, size_t b0, const void* p1, size_t b1) {
   if ((int)t->ev_done.size() <= t->side_seq) {
     hipEvent_t e = nullptr;
-    T_TRY((int)hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    RC_TRY((int)hipEventCreateWithFlags(&e, hipEventDisableTiming));
     t->ev_done.push_back(e);
   }
-  T_TRY((int)hipEventRecord(t->ev_done[t->side_seq], t->side));
+  RC_TRY((int)hipEventRecord(t->ev_done[t->side_seq], t->side));
   t->pend.push_back(TB::Range{(const unsigned char*)p0, (const unsigned char*)p0 + b0, t->side_seq});
   t->pend.push_back(TB::Range{(const unsigned char*)p1, (const unsigned char*)p1 + b1, t->side_seq});
   ++t->side_seq;
@@ -361,7 +332,7 @@ int side_wait(TB* t, int seq) {
   for (int q = 0; q < t->n_side; ++q) {        // per side stream: its youngest launch <= seq (the stream runs in order), unless already waited for
     const int i = seq - ((seq - q) % t->n_side + t->n_side) % t->n_side;
     if (i >= 0 && i > t->side_waited[q]) {
-      T_TRY((int)hipStreamWaitEvent(t->st, t->ev_done[i], 0));
+      RC_TRY((int)hipStreamWaitEvent(t->st, t->ev_done[i], 0));
       t->side_waited[q] = i;
     }
   }
@@ -373,7 +344,7 @@ int side_wait(TB* t, int seq) {
 }
 int side_sync(TB* t) {                        // ... for every side launch so far
   if (t->save.dry || t->side_seq == 0) { t->pend.clear(); return 0; }
-  T_TRY(side_wait(t, t->side_seq - 1));
+  RC_TRY(side_wait(t, t->side_seq - 1));
   t->pend.clear();
   return 0;
 }
@@ -415,9 +386,9 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
     if (!scratch) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (wgrad3x3)");
     int d[2] = {0, 0};
     const bool on_side = t->side_on && !t->save.dry;
-    if (on_side) T_TRY(side_begin(t));
+    if (on_side) RC_TRY(side_begin(t));
     T_RUN(launch_wgrad3x3(x, Cin_tot, dz, rows, w->grad, scratch, B, H, W, c.O, c.Ig, c.groups, on_side ? t->side : t->st, d, wdt));
-    if (on_side) T_TRY(side_end(t, x, (size_t)M * Cin_tot * t->es, dz, (size_t)M * rows * t->es));
+    if (on_side) RC_TRY(side_end(t, x, (size_t)M * Cin_tot * t->es, dz, (size_t)M * rows * t->es));
     if (!t->save.dry) t->fin.push_back(FinJob{scratch, w->grad, 3, 0, c.Ig, 3, 3, c.groups == 8 ? 1 : c.O == 96 ? 2 : 0, d[1], d[0], 1, 1, 1, 1});
     return 0;
   }
@@ -427,9 +398,9 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
     float* ysp = (float*)t->save.take((size_t)round_up(rows, 4) * splits * Kc_pad * 4);
     if (!ysp) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (wgrad1x1)");
     const bool on_side = t->side_on && !t->save.dry;
-    if (on_side) T_TRY(side_begin(t));
+    if (on_side) RC_TRY(side_begin(t));
     T_RUN(launch_wgrad1x1(x, Cin_tot, Cin_tot, dz, rows, rows, ysp, M, Kc_pad, on_side ? t->side : t->st, wdt));
-    if (on_side) T_TRY(side_end(t, x, (size_t)M * Cin_tot * t->es, dz, (size_t)M * rows * t->es));
+    if (on_side) RC_TRY(side_end(t, x, (size_t)M * Cin_tot * t->es, dz, (size_t)M * rows * t->es));
     const int KHf = c.via_patches ? 3 : c.KH, KWf = c.via_patches ? 3 : c.KW;
     const bool fast = KHf == 1 && KWf == 1 && c.hd_rows == c.hdp_rows && c.hd_cols == c.hdp_cols && (c.Ig & 3) == 0 && (Kc_pad & 3) == 0;
     if (!t->save.dry) t->fin.push_back(FinJob{ysp, w->grad, fast ? 1 : 0, c.O, c.Ig, KHf, KWf, 0, splits, Kc_pad, c.hd_rows, c.hdp_rows, c.hd_cols, c.hdp_cols});
@@ -446,8 +417,8 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
   void* dzt = t->tmp.take((size_t)rows * Mpad * t->es);
   void* xct = t->tmp.take((size_t)Kc_pad * Mpad * t->es);
   if (!dzt || !xct || !ysp) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace too small (wgrad)");
-  T_TRY(side_guard(t, dzt, (size_t)rows * Mpad * t->es));
-  T_TRY(side_guard(t, xct, (size_t)Kc_pad * Mpad * t->es));
+  RC_TRY(side_guard(t, dzt, (size_t)rows * Mpad * t->es));
+  RC_TRY(side_guard(t, xct, (size_t)Kc_pad * Mpad * t->es));
   T_RUN(launch_transpose_cols(dz, dzt, M, rows, 0, rows, Mpad, t->dtype, t->st));
   if (rows_in) T_RUN(launch_transpose_cols(x, xct, M, Cin_tot, 0, Cin_tot, Mpad, t->gdt, t->st));      // (the GEMM's weight-side operand: limb words under bf16x2)
   else T_RUN(launch_im2col_t(x, xct, B, H, W, Cin_tot, 0, Cin_tot, c.KH, c.KW, c.stride, c.pad, OH, OW, Mpad, t->gdt, t->st));
@@ -469,7 +440,7 @@ int conv_bwd_weight(TB* t, const ConvSpec& c, const void* x, int B, int H, int W
 
 // every deferred split-slab finalize of this backward pass (one or two launches)
 int run_finalizes(TB* t) {
-  T_TRY(side_sync(t));
+  RC_TRY(side_sync(t));
   if (t->save.dry || t->fin.empty()) return 0;
   T_RUN(launch_wgrad_finalize_multi(t->fin.data(), (int)t->fin.size(), t->st));
   t->fin.clear();
@@ -524,8 +495,8 @@ int bn_bwd(TB* t, const std::string& name, const BnSave& sv, const void* dy, voi
   float* dbeta = b->grad ? b->grad : coef + 4 * sv.C;
   T_RUN(launch_bn_reduce(dy, sv.z, sv.mean, sv.invstd, partial, sv.M, sv.C, 1, t->dtype, t->st, nullptr, nullptr, nullptr, 0, act ? sv.sa : nullptr, act ? sv.sb : nullptr));
   T_RUN(launch_bn_bwd_finalize(partial, sv.M, sv.C, g->data, sv.invstd, dgamma, dbeta, coef, coef + sv.C, coef + 2 * sv.C, t->freeze_bn ? 1 : 0, t->st));
-  T_TRY(side_guard(t, dz, (size_t)sv.M * sv.C * t->es));
-  if (out2) T_TRY(side_guard(t, out2, (size_t)sv.M * sv.C * t->es));
+  RC_TRY(side_guard(t, dz, (size_t)sv.M * sv.C * t->es));
+  if (out2) RC_TRY(side_guard(t, out2, (size_t)sv.M * sv.C * t->es));
   T_RUN(launch_bn_bwd_apply(dy, sv.z, sv.mean, sv.invstd, coef, coef + sv.C, coef + 2 * sv.C, dz, (size_t)sv.M, sv.C, t->dtype, t->st, acc, scale2, out2, rows_per_img,
                             act ? sv.sa : nullptr, act ? sv.sb : nullptr));
   t->tmp.off = mark;
@@ -579,11 +550,11 @@ int stem_forward(TB* t, const StemGeo& g, StemSave& S, const float* x) {
     const size_t mark = t->tmp.off;
     float* stp = nullptr;
     int str = 0;
-    T_TRY(conv_fwd_stats(t, ss.conv1, S.patches, B, H0, H0, S.z1, &stp, &str));
-    T_TRY(bn_fwd(t, pfx + "bn1", S.z1, (int)M0, g.C0, ACT_LRELU, nullptr, S.a1, &S.b1, nullptr, stp, str));
+    RC_TRY(conv_fwd_stats(t, ss.conv1, S.patches, B, H0, H0, S.z1, &stp, &str));
+    RC_TRY(bn_fwd(t, pfx + "bn1", S.z1, (int)M0, g.C0, ACT_LRELU, nullptr, S.a1, &S.b1, nullptr, stp, str));
     t->tmp.off = mark;
-    T_TRY(conv_fwd_stats(t, ss.down, S.patches, B, H0, H0, S.zd, &stp, &str));
-    T_TRY(bn_fwd(t, pfx + "downsample.1", S.zd, (int)M0, g.C1, ACT_NONE, nullptr, nullptr, &S.bd, nullptr, stp, str));      // statistics only: applied inside the pooling pass
+    RC_TRY(conv_fwd_stats(t, ss.down, S.patches, B, H0, H0, S.zd, &stp, &str));
+    RC_TRY(bn_fwd(t, pfx + "downsample.1", S.zd, (int)M0, g.C1, ACT_NONE, nullptr, nullptr, &S.bd, nullptr, stp, str));      // statistics only: applied inside the pooling pass
     t->tmp.off = mark;
   }
   {
@@ -591,11 +562,11 @@ int stem_forward(TB* t, const StemGeo& g, StemSave& S, const float* x) {
     const size_t mark = t->tmp.off;
     float* stp = nullptr;
     int str = 0;
-    T_TRY(conv_fwd_stats(t, ss.conv2, S.a1, B, H0, H0, S.z2, &stp, &str));
-    T_TRY(bn_fwd(t, pfx + "bn2", S.z2, (int)M0, g.C1, ACT_LRELU, nullptr, S.a2, &S.b2, nullptr, stp, str));
+    RC_TRY(conv_fwd_stats(t, ss.conv2, S.a1, B, H0, H0, S.z2, &stp, &str));
+    RC_TRY(bn_fwd(t, pfx + "bn2", S.z2, (int)M0, g.C1, ACT_LRELU, nullptr, S.a2, &S.b2, nullptr, stp, str));
     t->tmp.off = mark;
-    T_TRY(conv_fwd_stats(t, ss.conv3, S.a2, B, H0, H0, S.z3, &stp, &str));
-    T_TRY(bn_fwd(t, pfx + "bn3", S.z3, (int)M0, g.C1, ACT_LRELU, nullptr, nullptr, &S.b3, nullptr, stp, str));      // statistics only: applied inside the pooling pass below
+    RC_TRY(conv_fwd_stats(t, ss.conv3, S.a2, B, H0, H0, S.z3, &stp, &str));
+    RC_TRY(bn_fwd(t, pfx + "bn3", S.z3, (int)M0, g.C1, ACT_LRELU, nullptr, nullptr, &S.b3, nullptr, stp, str));      // statistics only: applied inside the pooling pass below
     t->tmp.off = mark;
   }
   {
@@ -624,14 +595,14 @@ int stem_backward(TB* t, const StemGeo& g, StemSave& S, const void* dx) {
   if (g.pos && !pos) return FSVIT_ERR_KEY;
   if (pos && (pos->grad || t->save.dry)) {
     float* ps = (float*)t->tmp.take((size_t)H1 * H1 * g.C1 * 4); NEED(ps);
-    T_TRY(side_guard(t, ps, (size_t)H1 * H1 * g.C1 * 4));
+    RC_TRY(side_guard(t, ps, (size_t)H1 * H1 * g.C1 * 4));
     T_RUN(launch_batch_sum(dx, ps, B, (size_t)H1 * H1 * g.C1, dt, st));
     T_RUN(launch_transpose_cols(ps, pos->grad, H1 * H1, g.C1, 0, g.C1, H1 * H1, 0, st));
   }
   void* da3 = take_tmp(t, M0 * g.C1); NEED(da3);
   void* g3 = take_tmp(t, M0 * g.C1); NEED(g3);
-  T_TRY(side_guard(t, da3, M0 * g.C1 * t->es));
-  T_TRY(side_guard(t, g3, M0 * g.C1 * t->es));
+  RC_TRY(side_guard(t, da3, M0 * g.C1 * t->es));
+  RC_TRY(side_guard(t, g3, M0 * g.C1 * t->es));
   void* da2 = nullptr;
   if (pool_bn_bwd_supported(g.C1, dt)) {
     // bn3 and the identity path's BatchNorm see the same gradient - the pooled gradient routed to each window's arg-max with the LeakyReLU slope;
@@ -648,27 +619,27 @@ int stem_backward(TB* t, const StemGeo& g, StemSave& S, const void* dx) {
     T_RUN(launch_bn_bwd_finalize_nblk(part + (size_t)nb * 2 * C, nb, (int)M0, C, gdw->data, S.bd.invstd, gdw->grad ? gdw->grad : scr + 2 * C, bdw->grad ? bdw->grad : scr + 3 * C,
                                       coefd, coefd + C, coefd + 2 * C, t->freeze_bn ? 1 : 0, st));
     T_RUN(launch_pool_bn_bwd_apply(dx, S.arg, S.z3, S.zd, S.b3.mean, S.b3.invstd, S.bd.mean, S.bd.invstd, coef3, coefd, da3, g3, B, H1, H1, C, dt, st));
-    T_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
+    RC_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
     da2 = take_tmp(t, M0 * g.C1); NEED(da2);
-    T_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
-    T_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, g3));
+    RC_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
+    RC_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, g3));
   } else {
     T_RUN(launch_pool_act_bwd(dx, S.arg, g3, B, H1, H1, g.C1, dt, st));                      // gradient at (bn3(z3) + identity): max-pool routing x LeakyReLU slope
-    T_TRY(bn_bwd(t, pfx + "bn3", S.b3, g3, da3));                                              // da3 := dz3
-    T_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
+    RC_TRY(bn_bwd(t, pfx + "bn3", S.b3, g3, da3));                                              // da3 := dz3
+    RC_TRY(conv_bwd_weight(t, ss.conv3, S.a2, B, H0, H0, da3));
     da2 = take_tmp(t, M0 * g.C1); NEED(da2);
-    T_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
+    RC_TRY(conv_bwd_data(t, ss.conv3, da3, B, H0, H0, da2));
     // identity path: ad = bn_d(zd)
-    T_TRY(bn_bwd(t, pfx + "downsample.1", S.bd, g3, da3));                                     // da3 := dzd
-    T_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, da3));
+    RC_TRY(bn_bwd(t, pfx + "downsample.1", S.bd, g3, da3));                                     // da3 := dzd
+    RC_TRY(conv_bwd_weight(t, ss.down, S.patches, B, H0, H0, da3));
   }
   // bn2 / bn1 are followed by a LeakyReLU: its slope rides in the BatchNorm backward's two passes (no bn_act_bwd pass, no 328 MB map)
-  T_TRY(bn_bwd(t, pfx + "bn2", S.b2, da2, da2, nullptr, nullptr, nullptr, 0, true));         // da2 := dz2 (in place)
-  T_TRY(conv_bwd_weight(t, ss.conv2, S.a1, B, H0, H0, da2));
+  RC_TRY(bn_bwd(t, pfx + "bn2", S.b2, da2, da2, nullptr, nullptr, nullptr, 0, true));         // da2 := dz2 (in place)
+  RC_TRY(conv_bwd_weight(t, ss.conv2, S.a1, B, H0, H0, da2));
   void* da1 = take_tmp(t, M0 * g.C0); NEED(da1);
-  T_TRY(conv_bwd_data(t, ss.conv2, da2, B, H0, H0, da1));
-  T_TRY(bn_bwd(t, pfx + "bn1", S.b1, da1, da1, nullptr, nullptr, nullptr, 0, true));         // da1 := dz1 (in place)
-  T_TRY(conv_bwd_weight(t, ss.conv1, S.patches, B, H0, H0, da1));
+  RC_TRY(conv_bwd_data(t, ss.conv2, da2, B, H0, H0, da1));
+  RC_TRY(bn_bwd(t, pfx + "bn1", S.b1, da1, da1, nullptr, nullptr, nullptr, 0, true));         // da1 := dz1 (in place)
+  RC_TRY(conv_bwd_weight(t, ss.conv1, S.patches, B, H0, H0, da1));
   return 0;
 }
 
@@ -718,7 +689,7 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
   const int nblk = t->cfg.depth[0] + t->cfg.depth[1] + t->cfg.depth[2];
   int dp_call = 0, blk = 0;
 
-  T_TRY(stem_forward(t, t->geo(), t->stem, x));
+  RC_TRY(stem_forward(t, t->geo(), t->stem, x));
   void* xcur = t->stem.x1;
   // residual adds in front of a BatchNorm are queued here and computed by that BatchNorm's reduce pass (bn_fwd); flush_add() launches a queued
   // add on its own where the consumer is not a BatchNorm
@@ -746,7 +717,7 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
     NEED(b.z2 = take_act(t, M1 * t->hid1)); NEED(b.h2 = take_act(t, M1 * t->hid1)); NEED(b.out = take_act(t, M1 * t->C1));
     const size_t mark = t->tmp.off;
     if (block_fused) {
-      T_TRY(bn_fwd(t, p + "norm2.bn", b.x, (int)M1, t->C1, ACT_NONE, nullptr, nullptr, &b.bn));   // statistics only
+      RC_TRY(bn_fwd(t, p + "norm2.bn", b.x, (int)M1, t->C1, ACT_NONE, nullptr, nullptr, &b.bn));   // statistics only
       const fsvit_param* w1 = getp(t, sp.s1c1[i].wname);
       if (!w1) return FSVIT_ERR_KEY;
       void* w1f = t->tmp.take((size_t)t->hid1 * t->C1 * t->es); NEED(w1f);
@@ -754,8 +725,8 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
       T_RUN(launch_fold_prenorm(w1->data, b.bn.sa, b.bn.sb, w1f, b1f, t->hid1, t->C1, t->C1, dt, st));
       void *pk2 = nullptr, *pk3 = nullptr;
       int kw2 = 0;
-      T_TRY(conv_pack_fwd(t, sp.s1c2[i], &pk2, &kw2));
-      T_TRY(conv_pack_fwd(t, sp.s1c3[i], &pk3));
+      RC_TRY(conv_pack_fwd(t, sp.s1c2[i], &pk2, &kw2));
+      RC_TRY(conv_pack_fwd(t, sp.s1c3[i], &pk3));
       if (kw2 != 320) return fsvit_set_error(FSVIT_ERR_ARG, "stage-1 grouped conv pack: Kw %d", kw2);
       b.scale = dp_scale(t, dp_call, blk, nblk);
       if (t->dp_rate * blk > 0.f) ++dp_call;
@@ -765,17 +736,17 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
       continue;
     }
     void* z3 = take_tmp(t, M1 * t->C1); NEED(z3);
-    T_TRY(bn_fwd(t, p + "norm2.bn", b.x, (int)M1, t->C1, ACT_NONE, nullptr, b.xn, &b.bn, &pend));
+    RC_TRY(bn_fwd(t, p + "norm2.bn", b.x, (int)M1, t->C1, ACT_NONE, nullptr, b.xn, &b.bn, &pend));
     // (z1 / z2 hold the GELU DERIVATIVES at the pre-activations, written next to h1 / h2 by the conv epilogues)
-    T_TRY(conv_fwd(t, sp.s1c1[i], b.xn, B, H1, H1, b.h1, nullptr, b.z1));
-    T_TRY(conv_fwd(t, sp.s1c2[i], b.h1, B, H1, H1, b.h2, nullptr, b.z2));
-    T_TRY(conv_fwd(t, sp.s1c3[i], b.h2, B, H1, H1, z3, nullptr));
+    RC_TRY(conv_fwd(t, sp.s1c1[i], b.xn, B, H1, H1, b.h1, nullptr, b.z1));
+    RC_TRY(conv_fwd(t, sp.s1c2[i], b.h1, B, H1, H1, b.h2, nullptr, b.z2));
+    RC_TRY(conv_fwd(t, sp.s1c3[i], b.h2, B, H1, H1, z3, nullptr));
     b.scale = dp_scale(t, dp_call, blk, nblk);
     if (t->dp_rate * blk > 0.f) ++dp_call;
     // b.out = b.x + scale * z3: queued for the next block's BatchNorm reduce pass (z3 must outlive this block's tmp scope: it is the first
     // allocation after `mark` in every block, and the next block's BatchNorm runs before anything else is written there)
     pend = PendingAdd{b.x, z3, b.scale, b.out, M1 * t->C1, (size_t)H1 * H1 * t->C1};
-    if (i + 1 == t->cfg.depth[0]) T_TRY(flush_add());
+    if (i + 1 == t->cfg.depth[0]) RC_TRY(flush_add());
     t->tmp.off = mark;
     xcur = b.out;
   }
@@ -794,9 +765,9 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
       const fsvit_param *bias = getp(t, pn + "proj.bias"), *pos = getp(t, "pos_embed" + std::to_string(sg));
       if (!bias || !pos) return FSVIT_ERR_KEY;
       const size_t mark = t->tmp.off;
-      T_TRY(conv_fwd(t, sg == 2 ? sp.pe2 : sp.pe3, pe.xin, B, Hi, Hi, pe.z, bias->data));
+      RC_TRY(conv_fwd(t, sg == 2 ? sp.pe2 : sp.pe3, pe.xin, B, Hi, Hi, pe.z, bias->data));
       void* y = take_tmp(t, M * C); NEED(y);
-      T_TRY(bn_fwd(t, pn + "norm.bn", pe.z, (int)M, C, ACT_NONE, nullptr, y, &pe.bn));
+      RC_TRY(bn_fwd(t, pn + "norm.bn", pe.z, (int)M, C, ACT_NONE, nullptr, y, &pe.bn));
       float* pt = (float*)t->tmp.take((size_t)Ho * Ho * C * 4); NEED(pt);
       T_RUN(launch_transpose_cols(pos->data, pt, C, Ho * Ho, 0, Ho * Ho, C, 0, st));
       T_RUN(launch_bcast_add(y, pt, pe.out, B, (size_t)Ho * Ho * C, dt, st));
@@ -816,22 +787,22 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
       NEED(b.out = take_act(t, M * C));
       const size_t mark = t->tmp.off;
       void* zp = take_tmp(t, M * C); NEED(zp);
-      T_TRY(bn_fwd(t, p + "norm1.bn", b.x, (int)M, C, ACT_NONE, nullptr, b.xn1, &b.bn1, &pend));
-      T_TRY(conv_fwd(t, cs.qkv, b.xn1, B, Ho, Ho, b.qkv, nullptr));
+      RC_TRY(bn_fwd(t, p + "norm1.bn", b.x, (int)M, C, ACT_NONE, nullptr, b.xn1, &b.bn1, &pend));
+      RC_TRY(conv_fwd(t, cs.qkv, b.xn1, B, Ho, Ho, b.qkv, nullptr));
       T_RUN(launch_attention(b.qkv, b.ctx, B, Ho * Ho, heads, hdp, scale, t->gdt == 2 ? 2 : dt, st));
-      T_TRY(conv_fwd(t, cs.proj, b.ctx, B, Ho, Ho, zp, nullptr));
+      RC_TRY(conv_fwd(t, cs.proj, b.ctx, B, Ho, Ho, zp, nullptr));
       b.s1 = dp_scale(t, dp_call, blk, nblk);
       if (t->dp_rate * blk > 0.f) ++dp_call;
       pend = PendingAdd{b.x, zp, b.s1, b.xa, M * C, (size_t)Ho * Ho * C};                       // b.xa = b.x + s1 * zp inside norm2's reduce pass
-      T_TRY(bn_fwd(t, p + "norm2.bn", b.xa, (int)M, C, ACT_NONE, nullptr, b.xn2, &b.bn2, &pend));
-      T_TRY(conv_fwd(t, cs.fc1, b.xn2, B, Ho, Ho, b.h, nullptr, b.z1));                        // b.z1 = GELU'(fc1(xn2))
-      T_TRY(conv_fwd(t, cs.fc2, b.h, B, Ho, Ho, zp, nullptr));
+      RC_TRY(bn_fwd(t, p + "norm2.bn", b.xa, (int)M, C, ACT_NONE, nullptr, b.xn2, &b.bn2, &pend));
+      RC_TRY(conv_fwd(t, cs.fc1, b.xn2, B, Ho, Ho, b.h, nullptr, b.z1));                        // b.z1 = GELU'(fc1(xn2))
+      RC_TRY(conv_fwd(t, cs.fc2, b.h, B, Ho, Ho, zp, nullptr));
       b.s2 = dp_scale(t, dp_call, blk, nblk);
       if (t->dp_rate * blk > 0.f) ++dp_call;
       // b.out = b.xa + s2 * zp: queued for the next block's norm1 (zp is the first tmp allocation of every block of the stage and is
       // rewritten only by that block's proj conv, after norm1); the stage's last block adds now
       pend = PendingAdd{b.xa, zp, b.s2, b.out, M * C, (size_t)Ho * Ho * C};
-      if (i + 1 == t->cfg.depth[sg - 1]) T_TRY(flush_add());
+      if (i + 1 == t->cfg.depth[sg - 1]) RC_TRY(flush_add());
       t->tmp.off = mark;
       xcur = b.out;
     }
@@ -839,7 +810,7 @@ int train_forward_impl(TB* tb, const float* x, float* feat) {
   // ---- final norm + pool (visformer.py:455-462)
   const size_t M3 = (size_t)B * t->H3 * t->H3;
   // the normalised map is only ever averaged: feat = sa * mean_hw(x) + sb in the pooling pass (no apply pass, no stored map)
-  T_TRY(bn_fwd(t, "norm.bn", xcur, (int)M3, t->C3, ACT_NONE, nullptr, nullptr, &t->bnf));
+  RC_TRY(bn_fwd(t, "norm.bn", xcur, (int)M3, t->C3, ACT_NONE, nullptr, nullptr, &t->bnf));
   T_RUN(launch_pool_affine(xcur, t->bnf.sa, t->bnf.sb, feat, B, t->H3 * t->H3, t->C3, dt, st));
   return 0;
 }
@@ -861,7 +832,7 @@ int train_backward_impl(TB* tb, const float* dfeat) {
       T_RUN(launch_add_f32_into(dxn, t->dtokens, M3 * t->C3, dt, st));
       t->dtokens = nullptr;
     }
-    T_TRY(bn_bwd(t, "norm.bn", t->bnf, dxn, dx));
+    RC_TRY(bn_bwd(t, "norm.bn", t->bnf, dxn, dx));
   }
   for (int sg = 3; sg >= 2; --sg) {
     const int Ci = sg == 2 ? t->C1 : t->C2, C = sg == 2 ? t->C2 : t->C3, Hi = sg == 2 ? t->H1 : t->H2, Ho = sg == 2 ? t->H2 : t->H3;
@@ -878,28 +849,28 @@ int train_backward_impl(TB* tb, const float* dfeat) {
       // (dz2 sits at the same tmp offset in every block of the stage: the drop-path-scaled copy of dx each branch starts from is written by
       // the fused tail of the preceding BatchNorm backward, only the stage's first block launches the copy itself)
       void* dz2 = take_tmp(t, M * C); NEED(dz2);
-      if (i == (int)blocks.size() - 1) { T_TRY(side_guard(t, dz2, M * C * t->es)); T_RUN(launch_add_scaled(nullptr, dx, b.s2, dz2, M * C, (size_t)Ho * Ho * C, dt, st)); }
-      T_TRY(conv_bwd_weight(t, cs.fc2, b.h, B, Ho, Ho, dz2));
+      if (i == (int)blocks.size() - 1) { RC_TRY(side_guard(t, dz2, M * C * t->es)); T_RUN(launch_add_scaled(nullptr, dx, b.s2, dz2, M * C, (size_t)Ho * Ho * C, dt, st)); }
+      RC_TRY(conv_bwd_weight(t, cs.fc2, b.h, B, Ho, Ho, dz2));
       // (round 5's row-wise Mlp kernel - forward and data gradient in one launch each - was a draw against these gemm256 launches for two rounds and is
       // retired: tools/probes/variants/mlp_train/)
       void* dh = take_tmp(t, M * hid); NEED(dh);
-      T_TRY(conv_bwd_data(t, cs.fc2, dz2, B, Ho, Ho, dh, b.z1));                               // dh := dz1 (x GELU' in the epilogue)
-      T_TRY(conv_bwd_weight(t, cs.fc1, b.xn2, B, Ho, Ho, dh));
+      RC_TRY(conv_bwd_data(t, cs.fc2, dz2, B, Ho, Ho, dh, b.z1));                               // dh := dz1 (x GELU' in the epilogue)
+      RC_TRY(conv_bwd_weight(t, cs.fc1, b.xn2, B, Ho, Ho, dh));
       void* dxn2 = take_tmp(t, M * C); NEED(dxn2);
-      T_TRY(conv_bwd_data(t, cs.fc1, dh, B, Ho, Ho, dxn2));
+      RC_TRY(conv_bwd_data(t, cs.fc1, dh, B, Ho, Ho, dxn2));
       // dx := d(xa) total = dx + norm2 backward;  attention branch:  xa = x + s1 * proj(attn(qkv(bn1(x)))):  dz2 := dzp = s1 * dx
-      T_TRY(bn_bwd(t, p + "norm2.bn", b.bn2, dxn2, dx, dx, b.s1, dz2, (size_t)Ho * Ho));
-      T_TRY(conv_bwd_weight(t, cs.proj, b.ctx, B, Ho, Ho, dz2));
+      RC_TRY(bn_bwd(t, p + "norm2.bn", b.bn2, dxn2, dx, dx, b.s1, dz2, (size_t)Ho * Ho));
+      RC_TRY(conv_bwd_weight(t, cs.proj, b.ctx, B, Ho, Ho, dz2));
       void* dctx = take_tmp(t, M * heads * hdp); NEED(dctx);
-      T_TRY(conv_bwd_data(t, cs.proj, dz2, B, Ho, Ho, dctx));
+      RC_TRY(conv_bwd_data(t, cs.proj, dz2, B, Ho, Ho, dctx));
       void* dqkv = take_tmp(t, M * 3 * heads * hdp); NEED(dqkv);
-      T_TRY(side_guard(t, dqkv, M * 3 * heads * hdp * t->es));
+      RC_TRY(side_guard(t, dqkv, M * 3 * heads * hdp * t->es));
       T_RUN(launch_attention_bwd(b.qkv, dctx, dqkv, B, Ho * Ho, heads, hd, hdp, scale, dt, st));
-      T_TRY(conv_bwd_weight(t, cs.qkv, b.xn1, B, Ho, Ho, dqkv));
-      T_TRY(conv_bwd_data(t, cs.qkv, dqkv, B, Ho, Ho, dxn2));                                 // dxn2 := d(xn1)
+      RC_TRY(conv_bwd_weight(t, cs.qkv, b.xn1, B, Ho, Ho, dqkv));
+      RC_TRY(conv_bwd_data(t, cs.qkv, dqkv, B, Ho, Ho, dxn2));                                 // dxn2 := d(xn1)
       // dx += norm1 backward; the next block (i - 1) of the stage starts from dz2 = s2' * dx
-      if (i > 0) T_TRY(bn_bwd(t, p + "norm1.bn", b.bn1, dxn2, dx, dx, blocks[i - 1].s2, dz2, (size_t)Ho * Ho));
-      else T_TRY(bn_bwd(t, p + "norm1.bn", b.bn1, dxn2, dx, dx));
+      if (i > 0) RC_TRY(bn_bwd(t, p + "norm1.bn", b.bn1, dxn2, dx, dx, blocks[i - 1].s2, dz2, (size_t)Ho * Ho));
+      else RC_TRY(bn_bwd(t, p + "norm1.bn", b.bn1, dxn2, dx, dx));
       t->tmp.off = mark;
     }
     // patch embed:  out = bn(conv_k2s2(xin) + bias) + pos
@@ -912,34 +883,34 @@ int train_backward_impl(TB* tb, const float* dfeat) {
       if (!bias || !pos) return FSVIT_ERR_KEY;
       if (pos->grad || t->save.dry) {
         float* ps = (float*)t->tmp.take((size_t)Ho * Ho * C * 4); NEED(ps);
-        T_TRY(side_guard(t, ps, (size_t)Ho * Ho * C * 4));
+        RC_TRY(side_guard(t, ps, (size_t)Ho * Ho * C * 4));
         T_RUN(launch_batch_sum(dx, ps, B, (size_t)Ho * Ho * C, dt, st));
         T_RUN(launch_transpose_cols(ps, pos->grad, Ho * Ho, C, 0, C, Ho * Ho, 0, st));         // [HW][C] -> [C][HW]
       }
       void* dz = take_tmp(t, M * C); NEED(dz);
-      T_TRY(bn_bwd(t, pn + "norm.bn", pe.bn, dx, dz));
+      RC_TRY(bn_bwd(t, pn + "norm.bn", pe.bn, dx, dz));
       if (bias->grad || t->save.dry) {
         float* partial = (float*)t->tmp.take((size_t)bn_reduce_blocks((int)M) * 2 * C * 4); NEED(partial);
-        T_TRY(side_guard(t, partial, (size_t)bn_reduce_blocks((int)M) * 2 * C * 4));
+        RC_TRY(side_guard(t, partial, (size_t)bn_reduce_blocks((int)M) * 2 * C * 4));
         T_RUN(launch_colsum(dz, partial, bias->grad, (int)M, C, dt, st));
       }
-      T_TRY(conv_bwd_weight(t, pc, pe.xin, B, Hi, Hi, dz));
+      RC_TRY(conv_bwd_weight(t, pc, pe.xin, B, Hi, Hi, dz));
       // data gradient of the non-overlapping k2s2 conv: G[m][(ky,kx,c)] = dz[m] . W[:, c, ky, kx], scattered to the input grid
       const fsvit_param* w = getp(t, pc.wname);
       const int bke = 128 / t->es, Kw = round_up(C, bke);
       void* pk = nullptr;
-      T_TRY(packed_weight(t, PackJob{w->data, nullptr, C, Ci, 2, 2, 1, 2, 4 * Ci, Kw, 1, 1, 1, 1}, (size_t)4 * Ci * Kw * t->es, &pk));
+      RC_TRY(packed_weight(t, PackJob{w->data, nullptr, C, Ci, 2, 2, 1, 2, 4 * Ci, Kw, 1, 1, 1, 1}, (size_t)4 * Ci * Kw * t->es, &pk));
       void* G = take_tmp(t, M * 4 * Ci); NEED(G);
       ConvGemmParams p = gemm_params(dz, pk, G, B, Ho, Ho, C, C, 1, 1, 1, 0, 4 * Ci, 4 * Ci, C, Kw, 1);
-      T_TRY(side_guard(t, G, M * 4 * Ci * t->es));
+      RC_TRY(side_guard(t, G, M * 4 * Ci * t->es));
       T_RUN(launch_conv_gemm(p, t->gdt, st));
       void* dxi = take_tmp(t, Mi * Ci); NEED(dxi);
-      T_TRY(side_guard(t, dxi, Mi * Ci * t->es));
+      RC_TRY(side_guard(t, dxi, Mi * Ci * t->es));
       T_RUN(launch_unpatch2(G, dxi, B, Ho, Ho, Ci, dt, st));
       // the new residual-stream gradient lives at the start of tmp: move it there
       t->tmp.off = 0;
       dx = take_tmp(t, Mi * Ci);
-      T_TRY(side_sync(t));                    // (the start of tmp held this stage's gradient buffers)
+      RC_TRY(side_sync(t));                    // (the start of tmp held this stage's gradient buffers)
       T_RUN((int)hipMemcpyAsync(dx, dxi, Mi * Ci * t->es, hipMemcpyDeviceToDevice, st));
     }
   }
@@ -949,42 +920,42 @@ int train_backward_impl(TB* tb, const float* dfeat) {
     const std::string p = "stage1." + std::to_string(i) + ".";
     const size_t mark = t->tmp.off;
     void* dz3 = take_tmp(t, M1 * t->C1); NEED(dz3);
-    if (i == (int)t->s1.size() - 1) { T_TRY(side_guard(t, dz3, M1 * t->C1 * t->es)); T_RUN(launch_add_scaled(nullptr, dx, b.scale, dz3, M1 * t->C1, (size_t)H1 * H1 * t->C1, dt, st)); }
+    if (i == (int)t->s1.size() - 1) { RC_TRY(side_guard(t, dz3, M1 * t->C1 * t->es)); T_RUN(launch_add_scaled(nullptr, dx, b.scale, dz3, M1 * t->C1, (size_t)H1 * H1 * t->C1, dt, st)); }
     void* dxn = dz3;                                                                           // d(xn): in place over dz3 on the three-launch route
     if (stage1_ring_supported(t->gdt, t->C1, t->hid1, t->cfg.group, H1)) {
       // the block's data-gradient chain dz3 -> dz2 -> dz1 -> d(xn) in ONE kernel (stage1_ring.hip MODE 2), then the three weight gradients
       void *pk3 = nullptr, *pk2 = nullptr, *pk1 = nullptr;
       int kw2 = 0;
-      T_TRY(conv_pack_bwd(t, sp.s1c3[i], &pk3));
-      T_TRY(conv_pack_bwd(t, sp.s1c2[i], &pk2, &kw2));
-      T_TRY(conv_pack_bwd(t, sp.s1c1[i], &pk1));
+      RC_TRY(conv_pack_bwd(t, sp.s1c3[i], &pk3));
+      RC_TRY(conv_pack_bwd(t, sp.s1c2[i], &pk2, &kw2));
+      RC_TRY(conv_pack_bwd(t, sp.s1c1[i], &pk1));
       if (kw2 != 320) return fsvit_set_error(FSVIT_ERR_ARG, "stage-1 grouped conv dgrad pack: Kw %d", kw2);
       void* dh2 = take_tmp(t, M1 * t->hid1); NEED(dh2);
       void* dh1 = take_tmp(t, M1 * t->hid1); NEED(dh1);
       dxn = take_tmp(t, M1 * t->C1); NEED(dxn);
-      T_TRY(side_guard(t, dh2, M1 * t->hid1 * t->es));
-      T_TRY(side_guard(t, dh1, M1 * t->hid1 * t->es));
-      T_TRY(side_guard(t, dxn, M1 * t->C1 * t->es));
+      RC_TRY(side_guard(t, dh2, M1 * t->hid1 * t->es));
+      RC_TRY(side_guard(t, dh1, M1 * t->hid1 * t->es));
+      RC_TRY(side_guard(t, dxn, M1 * t->C1 * t->es));
       T_RUN(launch_stage1_ring_dgrad(dz3, dxn, pk3, pk2, pk1, b.z2, b.z1, dh2, dh1, B, H1, H1, st));
-      T_TRY(conv_bwd_weight(t, sp.s1c3[i], b.h2, B, H1, H1, dz3));
-      T_TRY(conv_bwd_weight(t, sp.s1c2[i], b.h1, B, H1, H1, dh2));
-      T_TRY(conv_bwd_weight(t, sp.s1c1[i], b.xn, B, H1, H1, dh1));
+      RC_TRY(conv_bwd_weight(t, sp.s1c3[i], b.h2, B, H1, H1, dz3));
+      RC_TRY(conv_bwd_weight(t, sp.s1c2[i], b.h1, B, H1, H1, dh2));
+      RC_TRY(conv_bwd_weight(t, sp.s1c1[i], b.xn, B, H1, H1, dh1));
     } else {
-      T_TRY(conv_bwd_weight(t, sp.s1c3[i], b.h2, B, H1, H1, dz3));
+      RC_TRY(conv_bwd_weight(t, sp.s1c3[i], b.h2, B, H1, H1, dz3));
       void* dh2 = take_tmp(t, M1 * t->hid1); NEED(dh2);
-      T_TRY(conv_bwd_data(t, sp.s1c3[i], dz3, B, H1, H1, dh2, b.z2));                           // x GELU'(z2) in the epilogue
-      T_TRY(conv_bwd_weight(t, sp.s1c2[i], b.h1, B, H1, H1, dh2));
+      RC_TRY(conv_bwd_data(t, sp.s1c3[i], dz3, B, H1, H1, dh2, b.z2));                           // x GELU'(z2) in the epilogue
+      RC_TRY(conv_bwd_weight(t, sp.s1c2[i], b.h1, B, H1, H1, dh2));
       void* dh1 = take_tmp(t, M1 * t->hid1); NEED(dh1);
-      T_TRY(conv_bwd_data(t, sp.s1c2[i], dh2, B, H1, H1, dh1, b.z1));                           // x GELU'(z1) in the epilogue
-      T_TRY(conv_bwd_weight(t, sp.s1c1[i], b.xn, B, H1, H1, dh1));
-      T_TRY(conv_bwd_data(t, sp.s1c1[i], dh1, B, H1, H1, dz3));                                  // dz3 := d(xn)
+      RC_TRY(conv_bwd_data(t, sp.s1c2[i], dh2, B, H1, H1, dh1, b.z1));                           // x GELU'(z1) in the epilogue
+      RC_TRY(conv_bwd_weight(t, sp.s1c1[i], b.xn, B, H1, H1, dh1));
+      RC_TRY(conv_bwd_data(t, sp.s1c1[i], dh1, B, H1, H1, dz3));                                  // dz3 := d(xn)
     }
     // dx += norm2 backward (read from d(xn)); the next block's dz3 = scale' * dx goes to dz3's buffer
-    if (i > 0) T_TRY(bn_bwd(t, p + "norm2.bn", b.bn, dxn, dx, dx, t->s1[i - 1].scale, dz3, (size_t)H1 * H1));
-    else T_TRY(bn_bwd(t, p + "norm2.bn", b.bn, dxn, dx, dx));
+    if (i > 0) RC_TRY(bn_bwd(t, p + "norm2.bn", b.bn, dxn, dx, dx, t->s1[i - 1].scale, dz3, (size_t)H1 * H1));
+    else RC_TRY(bn_bwd(t, p + "norm2.bn", b.bn, dxn, dx, dx));
     t->tmp.off = mark;
   }
-  T_TRY(stem_backward(t, t->geo(), t->stem, dx));
+  RC_TRY(stem_backward(t, t->geo(), t->stem, dx));
   return run_finalizes(t);
 }
 
@@ -1077,7 +1048,7 @@ int vit_forward_impl(TB* tb, const float* x, float* feat) {
   {
     const size_t mark = t->tmp.off;
     void* zpe = take_tmp(t, Mp * D); NEED(zpe);
-    T_TRY(conv_fwd(t, sp.pe, t->patches, (int)Mp, 1, 1, zpe, peb->data));
+    RC_TRY(conv_fwd(t, sp.pe, t->patches, (int)Mp, 1, 1, zpe, peb->data));
     T_RUN(launch_vit_assemble(zpe, cls->data, pos->data, xcur, B, S, D, dt, st));
     t->tmp.off = mark;
   }
@@ -1104,18 +1075,18 @@ int vit_blocks_forward(VT* t, const VSpecs& sp, void* xcur, float* feat) {
     void* xout = take_act(t, M * D); NEED(xout);
     const size_t mark = t->tmp.off;
     void* zp = take_tmp(t, M * D); NEED(zp);
-    T_TRY(vit_ln_fwd(t, p + "norm1", b.x, b.xn1, &b.m1, &b.r1, (int)M));
+    RC_TRY(vit_ln_fwd(t, p + "norm1", b.x, b.xn1, &b.m1, &b.r1, (int)M));
     const float* bqp = nullptr;
-    if (bq) T_TRY(padded_bias(t, bq, 3 * heads * t->hd, t->hd, hdp, &bqp));
-    T_TRY(conv_fwd(t, sp.qkv[i], b.xn1, B, S, 1, b.qkv, bqp));
+    if (bq) RC_TRY(padded_bias(t, bq, 3 * heads * t->hd, t->hd, hdp, &bqp));
+    RC_TRY(conv_fwd(t, sp.qkv[i], b.xn1, B, S, 1, b.qkv, bqp));
     T_RUN(launch_attention(b.qkv, b.ctx, B, S, heads, hdp, scale, t->gdt == 2 ? 2 : dt, st));
-    T_TRY(conv_fwd(t, sp.proj[i], b.ctx, B, S, 1, zp, bp->data));
+    RC_TRY(conv_fwd(t, sp.proj[i], b.ctx, B, S, 1, zp, bp->data));
     b.s1 = dp_scale(t, dp_call, i, t->vcfg.depth);
     if (t->dp_rate * i > 0.f) ++dp_call;
     T_RUN(launch_add_scaled(b.x, zp, b.s1, b.x1, M * D, (size_t)S * D, dt, st));
-    T_TRY(vit_ln_fwd(t, p + "norm2", b.x1, b.xn2, &b.m2, &b.r2, (int)M));
-    T_TRY(conv_fwd(t, sp.fc1[i], b.xn2, B, S, 1, b.h, b1->data, b.z1));                       // b.z1 = GELU'(fc1(xn2) + b1)
-    T_TRY(conv_fwd(t, sp.fc2[i], b.h, B, S, 1, zp, b2->data));
+    RC_TRY(vit_ln_fwd(t, p + "norm2", b.x1, b.xn2, &b.m2, &b.r2, (int)M));
+    RC_TRY(conv_fwd(t, sp.fc1[i], b.xn2, B, S, 1, b.h, b1->data, b.z1));                       // b.z1 = GELU'(fc1(xn2) + b1)
+    RC_TRY(conv_fwd(t, sp.fc2[i], b.h, B, S, 1, zp, b2->data));
     b.s2 = dp_scale(t, dp_call, i, t->vcfg.depth);
     if (t->dp_rate * i > 0.f) ++dp_call;
     T_RUN(launch_add_scaled(b.x1, zp, b.s2, xout, M * D, (size_t)S * D, dt, st));
@@ -1166,31 +1137,31 @@ int vit_blocks_backward(VT* t, const VSpecs& sp, const float* dfeat, void** dx_o
     const size_t mark = t->tmp.off;
     // mlp branch: out = x1 + s2 * fc2(gelu(fc1(norm2(x1))))
     void* dz2 = take_tmp(t, M * D); NEED(dz2);
-    T_TRY(side_guard(t, dz2, M * D * t->es));
+    RC_TRY(side_guard(t, dz2, M * D * t->es));
     T_RUN(launch_add_scaled(nullptr, dx, b.s2, dz2, M * D, (size_t)S * D, dt, st));
-    T_TRY(conv_bwd_weight(t, sp.fc2[i], b.h, B, S, 1, dz2));
-    T_TRY(bias_grad(t, b2, dz2, (int)M, D, 1, 1));
+    RC_TRY(conv_bwd_weight(t, sp.fc2[i], b.h, B, S, 1, dz2));
+    RC_TRY(bias_grad(t, b2, dz2, (int)M, D, 1, 1));
     void* dh = take_tmp(t, M * hid); NEED(dh);
-    T_TRY(conv_bwd_data(t, sp.fc2[i], dz2, B, S, 1, dh, b.z1));
-    T_TRY(conv_bwd_weight(t, sp.fc1[i], b.xn2, B, S, 1, dh));
-    T_TRY(bias_grad(t, b1, dh, (int)M, hid, 1, 1));
+    RC_TRY(conv_bwd_data(t, sp.fc2[i], dz2, B, S, 1, dh, b.z1));
+    RC_TRY(conv_bwd_weight(t, sp.fc1[i], b.xn2, B, S, 1, dh));
+    RC_TRY(bias_grad(t, b1, dh, (int)M, hid, 1, 1));
     void* dxn = take_tmp(t, M * D); NEED(dxn);
-    T_TRY(conv_bwd_data(t, sp.fc1[i], dh, B, S, 1, dxn));
-    T_TRY(vit_ln_bwd(t, p + "norm2", dxn, b.x1, b.m2, b.r2, dx, dx, (int)M));                // dx := d(x1) total
+    RC_TRY(conv_bwd_data(t, sp.fc1[i], dh, B, S, 1, dxn));
+    RC_TRY(vit_ln_bwd(t, p + "norm2", dxn, b.x1, b.m2, b.r2, dx, dx, (int)M));                // dx := d(x1) total
     // attention branch: x1 = x + s1 * proj(attn(qkv(norm1(x))))
-    T_TRY(side_guard(t, dz2, M * D * t->es));
+    RC_TRY(side_guard(t, dz2, M * D * t->es));
     T_RUN(launch_add_scaled(nullptr, dx, b.s1, dz2, M * D, (size_t)S * D, dt, st));
-    T_TRY(conv_bwd_weight(t, sp.proj[i], b.ctx, B, S, 1, dz2));
-    T_TRY(bias_grad(t, bp, dz2, (int)M, D, 1, 1));
+    RC_TRY(conv_bwd_weight(t, sp.proj[i], b.ctx, B, S, 1, dz2));
+    RC_TRY(bias_grad(t, bp, dz2, (int)M, D, 1, 1));
     void* dctx = take_tmp(t, M * heads * hdp); NEED(dctx);
-    T_TRY(conv_bwd_data(t, sp.proj[i], dz2, B, S, 1, dctx));
+    RC_TRY(conv_bwd_data(t, sp.proj[i], dz2, B, S, 1, dctx));
     void* dqkv = take_tmp(t, M * 3 * heads * hdp); NEED(dqkv);
-    T_TRY(side_guard(t, dqkv, M * 3 * heads * hdp * t->es));
+    RC_TRY(side_guard(t, dqkv, M * 3 * heads * hdp * t->es));
     T_RUN(launch_attention_bwd(b.qkv, dctx, dqkv, B, S, heads, t->hd, hdp, scale, dt, st));
-    T_TRY(conv_bwd_weight(t, sp.qkv[i], b.xn1, B, S, 1, dqkv));
-    if (bq) T_TRY(bias_grad(t, bq, dqkv, (int)M, 3 * heads * t->hd, t->hd, hdp));
-    T_TRY(conv_bwd_data(t, sp.qkv[i], dqkv, B, S, 1, dxn));
-    T_TRY(vit_ln_bwd(t, p + "norm1", dxn, b.x, b.m1, b.r1, dx, dx, (int)M));
+    RC_TRY(conv_bwd_weight(t, sp.qkv[i], b.xn1, B, S, 1, dqkv));
+    if (bq) RC_TRY(bias_grad(t, bq, dqkv, (int)M, 3 * heads * t->hd, t->hd, hdp));
+    RC_TRY(conv_bwd_data(t, sp.qkv[i], dqkv, B, S, 1, dxn));
+    RC_TRY(vit_ln_bwd(t, p + "norm1", dxn, b.x, b.m1, b.r1, dx, dx, (int)M));
     t->tmp.off = mark;
   }
   *dx_out = dx;
@@ -1212,7 +1183,7 @@ int vit_embed_backward(VT* t, const void* dx, void** dzpe_out) {
     if (e != hipSuccess) return fsvit_set_error((int)e, "pos / cls gradient");
   }
   void* dzpe = take_tmp(t, (size_t)B * t->np * D); NEED(dzpe);
-  T_TRY(side_sync(t));
+  RC_TRY(side_sync(t));
   T_RUN(launch_vit_patch_rows(dx, dzpe, B, S, D, dt, st));
   *dzpe_out = dzpe;
   return 0;
@@ -1225,10 +1196,10 @@ int vit_backward_impl(TB* tb, const float* dfeat) {
   const fsvit_param* peb = getp(t, "patch_embed.proj.bias");
   if (!peb) return FSVIT_ERR_KEY;
   void *dx = nullptr, *dzpe = nullptr;
-  T_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
-  T_TRY(vit_embed_backward(t, dx, &dzpe));
-  T_TRY(conv_bwd_weight(t, sp.pe, t->patches, Mp, 1, 1, dzpe));
-  T_TRY(bias_grad(t, peb, dzpe, Mp, t->D, 1, 1));
+  RC_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
+  RC_TRY(vit_embed_backward(t, dx, &dzpe));
+  RC_TRY(conv_bwd_weight(t, sp.pe, t->patches, Mp, 1, 1, dzpe));
+  RC_TRY(bias_grad(t, peb, dzpe, Mp, t->D, 1, 1));
   return run_finalizes(t);
 }
 
@@ -1249,12 +1220,12 @@ int lvvit_forward_impl(TB* tb, const float* x, float* feat) {
   const size_t M = (size_t)B * S, Mp = (size_t)B * t->np;
   const fsvit_param *cls = getp(t, "cls_token"), *pos = getp(t, "pos_embed"), *peb = getp(t, "patch_embed.proj.bias");
   if (!cls || !pos || !peb) return FSVIT_ERR_KEY;
-  T_TRY(stem_forward(t, t->geo(), t->stem, x));
+  RC_TRY(stem_forward(t, t->geo(), t->stem, x));
   void* xcur = take_act(t, M * D); NEED(xcur);
   {
     const size_t mark = t->tmp.off;
     void* zpe = take_tmp(t, Mp * D); NEED(zpe);
-    T_TRY(conv_fwd(t, sp.pe, t->stem.x1, B, t->H1, t->H1, zpe, peb->data));
+    RC_TRY(conv_fwd(t, sp.pe, t->stem.x1, B, t->H1, t->H1, zpe, peb->data));
     T_RUN(launch_vit_assemble(zpe, cls->data, pos->data, xcur, B, S, D, dt, t->st));
     t->tmp.off = mark;
   }
@@ -1269,26 +1240,26 @@ int lvvit_backward_impl(TB* tb, const float* dfeat) {
   const fsvit_param *peb = getp(t, "patch_embed.proj.bias"), *w = getp(t, "patch_embed.proj.weight");
   if (!peb || !w) return FSVIT_ERR_KEY;
   void *dx = nullptr, *dzpe = nullptr;
-  T_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
-  T_TRY(vit_embed_backward(t, dx, &dzpe));
+  RC_TRY(vit_blocks_backward(t, sp, dfeat, &dx));
+  RC_TRY(vit_embed_backward(t, dx, &dzpe));
   // weight gradient of the projection: wgrad1x1 over the permuted rows of the pooled map (K = 16 C0, N = D)
   void* prow = take_tmp(t, (size_t)Mp * Kr); NEED(prow);
-  T_TRY(side_guard(t, prow, (size_t)Mp * Kr * t->es));
+  RC_TRY(side_guard(t, prow, (size_t)Mp * Kr * t->es));
   T_RUN(launch_patchk(t->stem.x1, prow, B, npw, npw, C0, 4, 1, dt, st));
-  T_TRY(conv_bwd_weight(t, lvvit_proj_spec(t, true), prow, B, npw, npw, dzpe));
-  T_TRY(bias_grad(t, peb, dzpe, Mp, D, 1, 1));
+  RC_TRY(conv_bwd_weight(t, lvvit_proj_spec(t, true), prow, B, npw, npw, dzpe));
+  RC_TRY(bias_grad(t, peb, dzpe, Mp, D, 1, 1));
   // data gradient: G[m][(ky,kx,c)] = dz[m] . W[:, c, ky, kx] in one GEMM, then the inverse permutation into the pooled map's gradient
   const int bke = 128 / t->es, Kw = round_up(D, bke);
   void* pk = nullptr;
-  T_TRY(packed_weight(t, PackJob{w->data, nullptr, D, C0, 4, 4, 1, 2, Kr, Kw, 1, 1, 1, 1}, (size_t)Kr * Kw * t->es, &pk));
+  RC_TRY(packed_weight(t, PackJob{w->data, nullptr, D, C0, 4, 4, 1, 2, Kr, Kw, 1, 1, 1, 1}, (size_t)Kr * Kw * t->es, &pk));
   void* G = take_tmp(t, (size_t)Mp * Kr); NEED(G);
   ConvGemmParams p = gemm_params(dzpe, pk, G, B, npw, npw, D, D, 1, 1, 1, 0, Kr, Kr, D, Kw, 1);
-  T_TRY(side_guard(t, G, (size_t)Mp * Kr * t->es));
+  RC_TRY(side_guard(t, G, (size_t)Mp * Kr * t->es));
   T_RUN(launch_conv_gemm(p, t->gdt, st));
   void* dx1 = take_tmp(t, (size_t)B * H1 * H1 * C0); NEED(dx1);
-  T_TRY(side_guard(t, dx1, (size_t)B * H1 * H1 * C0 * t->es));
+  RC_TRY(side_guard(t, dx1, (size_t)B * H1 * H1 * C0 * t->es));
   T_RUN(launch_patchk(G, dx1, B, npw, npw, C0, 4, 0, dt, st));
-  T_TRY(stem_backward(t, t->geo(), t->stem, dx1));
+  RC_TRY(stem_backward(t, t->geo(), t->stem, dx1));
   return run_finalizes(t);
 }
 
@@ -1415,11 +1386,11 @@ int trainer_forward(TB* t, const fsvit_param* params, int n_params, const float*
                     const float* masks_dev, float* feat_dev, void* ws_dev, size_t ws_bytes, void* stream) {
   if (!t || !params || !x_nchw_dev || !feat_dev || !ws_dev || n_img <= 0) return fsvit_set_error(FSVIT_ERR_ARG, "bad argument");
   if (img_h != t->img_size || img_w != t->img_size) return fsvit_set_error(FSVIT_ERR_IMG_SIZE, t->size_fmt, img_h, img_w, t->img_size, t->img_size);
-  if (t->pre_check) T_TRY(t->pre_check(t, n_img));
+  if (t->pre_check) RC_TRY(t->pre_check(t, n_img));
   if (drop_path_rate > 0.f && !masks_dev) return fsvit_set_error(FSVIT_ERR_ARG, "DropPath masks required when drop_path_rate > 0");
   bind_params(t, params, n_params);
   size_t sb = 0, tb = 0;
-  T_TRY(trainer_size_workspace(t, n_img, drop_path_rate, &sb, &tb));
+  RC_TRY(trainer_size_workspace(t, n_img, drop_path_rate, &sb, &tb));
   if (ws_bytes < sb + tb) return fsvit_set_error(FSVIT_ERR_WORKSPACE, "training workspace of %zu bytes is too small (need %zu)", ws_bytes, sb + tb);
   t->st = (hipStream_t)stream;
   t->save = Arena(); t->save.base = (unsigned char*)ws_dev; t->save.size = sb;
@@ -1436,7 +1407,7 @@ int trainer_forward(TB* t, const fsvit_param* params, int n_params, const float*
     if (branch) T_RUN(launch_fill_f32(t->scales + (size_t)ncalls * n_img, t->branch_scale, (size_t)n_img, t->st));
     t->n_dp = ncalls;
   }
-  T_TRY(run_packs(t));                              // every weight pack of this step (forward + data-gradient layouts) in one or two launches
+  RC_TRY(run_packs(t));                              // every weight pack of this step (forward + data-gradient layouts) in one or two launches
   const int rc_f = t->forward_walk(t, x_nchw_dev, feat_dev);
   t->save_after_forward = t->save.off;
   return rc_f;
@@ -1646,14 +1617,14 @@ extern "C" int fsvit_sgd_nesterov_step(float* param, const float* grad, float* m
 extern "C" int fsvit_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, void* stream) {
   if (!p || !g || !m || !v || step < 1) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_adamw_step: bad argument");
-  T_TRY(launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
+  RC_TRY(launch_adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
   return 0;
 }
 
 extern "C" int fsvit_adamw_step_multi(const void* items_dev, int n_items, size_t max_numel, float lr, float beta1, float beta2, float eps, float weight_decay,
                                       int step, void* stream) {
   if (!items_dev || n_items < 0 || step < 1) return fsvit_set_error(FSVIT_ERR_ARG, "fsvit_adamw_step_multi: bad argument");      // (a null table is refused at n_items = 0 too)
-  T_TRY(launch_adamw_multi(items_dev, n_items, max_numel, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
+  RC_TRY(launch_adamw_multi(items_dev, n_items, max_numel, lr, beta1, beta2, eps, weight_decay, step, (hipStream_t)stream));
   return 0;
 }
 
