@@ -205,6 +205,9 @@ SIGNATURES = {
     'fsvit_emd_head_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'fsvit_emd_head_forward': (_i, [_fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _vp, _vp, _sz, _vp]),
     'fsvit_emd_head_backward': (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _f, _fp, _fp, _vp, _sz, _vp]),
+    'fsvit_emd_table_prep': (_i, [_fp, _i, _i, _i, _fp, _fp, _vp]),
+    'fsvit_emd_head_gather_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'fsvit_emd_head_gather': (_i, [_fp, _fp, _fp, _i, _vp, _vp, _i, _fp, _i, _i, _i, _i, _i, _f, _fp, _vp, _vp, _vp, _sz, _vp]),
     'fsvit_op_emd_solve': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp]),
     'fsvit_op_emd_solve_counts': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp, _vp]),
     'fsvit_emd_sfc_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),

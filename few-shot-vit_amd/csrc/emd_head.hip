@@ -6,6 +6,8 @@
 //  * emd_pair_kernel: one wavefront per (query, proto) problem, four problems per workgroup.  Cost c = 1 - cosine similarity [query node][proto node]
 //    (:151-167) and both weight vectors (:48-65, emd_utils.py:69-73) are formed in registers / LDS, the transportation problem is solved exactly in
 //    place, and logit = temperature / N * sum (1 - c) F (:118-124).  The similarity map never reaches HBM.
+//  * emd_gather_kernel: the same problems (emd_pair_wave) over rows of a token-map table addressed by slot numbers (feature_table.TokenTable: every
+//    image is encoded and prepared once, fsvit_emd_table_prep); the class side is a table row (1-shot) or a dense per-episode map (the 5-shot SFC).
 //  * emd_solve_wave: successive shortest augmenting paths with node potentials, one lane per node (rows on lanes 0 .. N-1, columns on lanes 32 .. 32+N-1),
 //    from a starting dual (column minima) and a greedy starting flow on its tight arcs.
 //    Every loop has a static bound (augmentations <= 8 N, Dijkstra steps <= 2 N + 1, path trace <= N + 1); a problem that reaches one writes status 1
@@ -203,7 +205,7 @@ __device__ __forceinline__ float emd_prep_pooled(const float* x, const int N, co
   return s / (float)N;
 }
 
-// tok [n_img][N][C] -> xhat [n_img][N][C], pooled [n_img][C], rn [n_img][N]
+// tok [n_img][N][C] -> xhat [n_img][N][C], pooled [n_img][C], rn [n_img][N] (rn may be null: only the backward reads it)
 __global__ __launch_bounds__(256) void emd_prep_kernel(const float* __restrict__ shot_tok, const float* __restrict__ query_tok, int n_shot, int N, int C,
                                                        float* __restrict__ xhat, float* __restrict__ pooled, float* __restrict__ rn) {
   const int img = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -211,7 +213,7 @@ __global__ __launch_bounds__(256) void emd_prep_kernel(const float* __restrict__
   float* xh = xhat + (size_t)img * N * C;
   for (int n = wave; n < N; n += 4) {
     const float inv = emd_prep_token(x + n * C, xh + n * C, C, lane);
-    if (lane == 0) rn[(size_t)img * N + n] = inv;
+    if (rn && lane == 0) rn[(size_t)img * N + n] = inv;
   }
   for (int k = threadIdx.x; k < C; k += 256) pooled[(size_t)img * C + k] = emd_prep_pooled(x, N, C, k);
 }
@@ -310,6 +312,51 @@ __global__ __launch_bounds__(64 * EMD_WAVES) void emd_pair_kernel(const float* _
     status[prob] = st;
   }
   if (flow) emd_store_flow(F, flow + (size_t)prob * N * N, N, lane);
+}
+
+// The problems of emd_pair_kernel over rows of a token-map table (tok / xhat [n_slots][N][C], pooled [n_slots][C], prepared once per image by
+// fsvit_emd_table_prep): query (e, q) is the table row query_slots[e][q]; the class side is the row proto_slots[e][p], or - with proto_slots null - the
+// dense map proto_tok[e][p] with its nodes in pxhat / ppool [E * P] (prepared by this launch).  A slot outside [0, n_slots) never becomes an address:
+// the problems it takes part in write a NaN logit and status 0 and read nothing, and *invalid is raised by one per such entry of either slot array
+// (by the problem at p == 0 for a query entry, at q == 0 for a proto entry; integer adds, any order).
+template <typename L>
+__global__ __launch_bounds__(64 * EMD_WAVES) void emd_gather_kernel(const float* __restrict__ tok, const float* __restrict__ xhat, const float* __restrict__ pooled,
+                                                                    int n_slots, const L* __restrict__ query_slots, const L* __restrict__ proto_slots,
+                                                                    const float* __restrict__ proto_tok, const float* __restrict__ pxhat,
+                                                                    const float* __restrict__ ppool, int E, int P, int Q, int N, int C, float scale,
+                                                                    float* __restrict__ logits, int* __restrict__ status, int* __restrict__ invalid) {
+  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long prob = (long long)blockIdx.x * EMD_WAVES + wave;
+  if (prob >= (long long)E * Q * P) return;
+  const int p = (int)(prob % P);
+  const long long eq = prob / P;                 // e * Q + q
+  const int e = (int)(eq / Q);
+  const int q = (int)(eq - (long long)e * Q);
+  const size_t ip = (size_t)e * P + p;
+  const L qs = query_slots[eq], ps = proto_slots ? proto_slots[ip] : (L)0;
+  const bool qbad = qs < (L)0 || qs >= (L)n_slots, pbad = ps < (L)0 || ps >= (L)n_slots;      // wave-uniform
+  if (qbad || pbad) {
+    if (lane == 0) {
+      logits[prob] = __builtin_nanf("");
+      status[prob] = 0;
+      const int n_bad = (qbad && p == 0 ? 1 : 0) + (pbad && q == 0 ? 1 : 0);
+      if (n_bad) atomicAdd(invalid, n_bad);
+    }
+    return;                                      // (no barrier in this kernel: the other waves of the workgroup go on)
+  }
+  const size_t NC = (size_t)N * C;
+  const float* tp = proto_slots ? tok + (size_t)ps * NC : proto_tok + ip * NC;
+  const float* xp = proto_slots ? xhat + (size_t)ps * NC : pxhat + ip * NC;
+  const float* gp = proto_slots ? pooled + (size_t)ps * C : ppool + ip * C;
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  int st;
+  const float s = emd_pair_wave(tok + (size_t)qs * NC, tp, xhat + (size_t)qs * NC, xp, pooled + (size_t)qs * C, gp, N, C, c, F, lane, st);
+  if (lane == 0) {
+    logits[prob] = s * scale;
+    status[prob] = st;
+  }
 }
 
 // One workgroup per image (protos first, then queries), one wave per token.  d xhat = sum over partners and their tokens of g * F * partner xhat
@@ -578,6 +625,41 @@ int launch_emd_head_forward(const float* shot_tok, const float* query_tok, int E
                 C, temperature / (float)N, logits, flow, status);
 }
 
+// Nodes and token means of n_img table rows: emd_prep_kernel over one array of maps, no rn (the table route is forward-only)
+int launch_emd_table_prep(const float* tok, int n_img, int N, int C, float* xhat, float* pooled, hipStream_t s) {
+  if (n_img <= 0) return 0;
+  return launch(emd_prep_kernel, dim3(n_img), dim3(256), 0, s, tok, (const float*)nullptr, n_img, N, C, xhat, pooled, (float*)nullptr);
+}
+
+// the dense-prototype form keeps the E * P prepared prototypes in the workspace: the layout of the dense head's with no queries
+size_t emd_head_gather_workspace_bytes(int E, int P, int N, int C) { return emd_head_workspace_bytes(E, P, 0, N, C); }
+
+template <typename L>
+static int launch_emd_gather_as(const float* tok, const float* xhat, const float* pooled, int n_slots, const void* query_slots, const void* proto_slots,
+                                const float* proto_tok, const float* pxhat, const float* ppool, int E, int P, int Q, int N, int C, float scale, float* logits,
+                                int* status, int* invalid, hipStream_t s) {
+  const long long probs = (long long)E * Q * P;
+  return launch(emd_gather_kernel<L>, dim3((unsigned)((probs + EMD_WAVES - 1) / EMD_WAVES)), dim3(64 * EMD_WAVES), 0, s, tok, xhat, pooled, n_slots,
+                (const L*)query_slots, (const L*)proto_slots, proto_tok, pxhat, ppool, E, P, Q, N, C, scale, logits, status, invalid);
+}
+
+int launch_emd_head_gather(const float* tok, const float* xhat, const float* pooled, int n_slots, const void* query_slots, const void* proto_slots,
+                           int slots_are_int64, const float* proto_tok, int E, int P, int Q, int N, int C, float temperature, float* logits, int* status,
+                           int* invalid, void* ws, hipStream_t s) {
+  if (E <= 0 || P <= 0 || Q <= 0) return 0;
+  float *pxhat = nullptr, *ppool = nullptr, *rn = nullptr;
+  if (proto_tok) {
+    emd_workspace_split(ws, E, P, 0, N, C, pxhat, ppool, rn);
+    int rc = launch(emd_prep_kernel, dim3(E * P), dim3(256), 0, s, proto_tok, (const float*)nullptr, E * P, N, C, pxhat, ppool, rn);
+    if (rc) return rc;
+  }
+  const float scale = temperature / (float)N;
+  return slots_are_int64 ? launch_emd_gather_as<long long>(tok, xhat, pooled, n_slots, query_slots, proto_slots, proto_tok, pxhat, ppool, E, P, Q, N, C, scale,
+                                                           logits, status, invalid, s)
+                         : launch_emd_gather_as<int>(tok, xhat, pooled, n_slots, query_slots, proto_slots, proto_tok, pxhat, ppool, E, P, Q, N, C, scale, logits,
+                                                     status, invalid, s);
+}
+
 int launch_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N, int C,
                              float temperature, float* d_shot, float* d_query, void* ws, hipStream_t s) {
   if (E <= 0 || P <= 0 || Q <= 0) return 0;
@@ -632,6 +714,40 @@ extern "C" int fsvit_emd_head_backward(const float* shot_tok, const float* query
   int rc = fsvit::launch_emd_head_backward(shot_tok, query_tok, dlogits, flow, E, P, Q, N, C, temperature, d_shot_tok, d_query_tok, workspace,
                                            (hipStream_t)stream);
   if (rc) return fsvit_set_error(rc, "fsvit_emd_head_backward: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int fsvit_emd_table_prep(const float* tok, int n_img, int N, int C, float* xhat, float* pooled, void* stream) {
+  if (!tok || !xhat || !pooled) EMD_FAIL("fsvit_emd_table_prep: null argument");
+  if (const char* why = emd_shape_bad(1, n_img, 0, N, C)) EMD_FAIL("fsvit_emd_table_prep: n_img = %d, N = %d, C = %d: %s", n_img, N, C, why);
+  int rc = fsvit::launch_emd_table_prep(tok, n_img, N, C, xhat, pooled, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_table_prep: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" size_t fsvit_emd_head_gather_workspace_bytes(int E, int P, int N, int C) {
+  if (emd_shape_bad(E, P, 0, N, C)) return 0;
+  return fsvit::emd_head_gather_workspace_bytes(E, P, N, C);
+}
+
+extern "C" int fsvit_emd_head_gather(const float* tok, const float* xhat, const float* pooled, int n_slots, const void* query_slots,
+                                     const void* proto_slots_or_null, int slots_are_int64, const float* proto_tok_or_null, int E, int P, int Q, int N, int C,
+                                     float temperature, float* logits, int* status, int* invalid, void* workspace_or_null, size_t workspace_bytes,
+                                     void* stream) {
+  if (!tok || !xhat || !pooled || !query_slots || !logits || !status || !invalid) EMD_FAIL("fsvit_emd_head_gather: null argument");
+  if (!proto_slots_or_null == !proto_tok_or_null) EMD_FAIL("fsvit_emd_head_gather: exactly one of proto_slots and proto_tok must be given");
+  if (n_slots < 1) EMD_FAIL("fsvit_emd_head_gather: n_slots = %d", n_slots);
+  if (const char* why = emd_shape_bad(E, P, Q, N, C)) EMD_FAIL("fsvit_emd_head_gather: E = %d, P = %d, Q = %d, N = %d, C = %d: %s", E, P, Q, N, C, why);
+  if (!(temperature - temperature == 0.0f)) EMD_FAIL("fsvit_emd_head_gather: temperature is not finite");
+  if (proto_tok_or_null) {
+    const size_t need = fsvit::emd_head_gather_workspace_bytes(E, P, N, C);
+    if (!workspace_or_null || workspace_bytes < need)
+      return fsvit_set_error(FSVIT_ERR_WORKSPACE, "fsvit_emd_head_gather: workspace of %zu bytes, %zu needed", workspace_or_null ? workspace_bytes : (size_t)0,
+                             need);
+  }
+  int rc = fsvit::launch_emd_head_gather(tok, xhat, pooled, n_slots, query_slots, proto_slots_or_null, slots_are_int64, proto_tok_or_null, E, P, Q, N, C,
+                                         temperature, logits, status, invalid, workspace_or_null, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_head_gather: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 

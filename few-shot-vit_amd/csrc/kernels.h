@@ -46,6 +46,12 @@ int launch_emd_head_forward(const float* shot_tok, const float* query_tok, int E
                             int* status, void* ws, hipStream_t s);
 int launch_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N, int C,
                              float temperature, float* d_shot, float* d_query, void* ws, hipStream_t s);
+// the head's forward over rows of a token-map table (limits: fsvit_emd_head_gather of fsvit.h); ws is read in the dense-prototype form only
+int launch_emd_table_prep(const float* tok, int n_img, int N, int C, float* xhat, float* pooled, hipStream_t s);
+size_t emd_head_gather_workspace_bytes(int E, int P, int N, int C);
+int launch_emd_head_gather(const float* tok, const float* xhat, const float* pooled, int n_slots, const void* query_slots, const void* proto_slots,
+                           int slots_are_int64, const float* proto_tok, int E, int P, int Q, int N, int C, float temperature, float* logits, int* status,
+                           int* invalid, void* ws, hipStream_t s);
 int launch_emd_solve(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* naug, hipStream_t s);
 // The 5-shot SFC fine-tune on the device, one workgroup per episode.  workspace = emd_sfc_workspace_bytes(E, way, n, bs, N, C)
 size_t emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C);

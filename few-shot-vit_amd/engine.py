@@ -1678,6 +1678,70 @@ class ops:
                                                            _ptr(ws), ws.numel(), _stream_ptr(dev)))
         return ds, dq
 
+    @staticmethod
+    def emd_table_prep(tok, xhat, pooled):
+        """Rows of a token-map table: tok [n,N,C] fp32 -> xhat [n,N,C], pooled [n,C] written IN PLACE (contiguous fp32; views of the table's arrays): the
+        nodes and token means `emd_head_forward` prepares for the same maps (fsvit_emd_table_prep)."""
+        _require_cuda(tok, xhat, pooled)
+        if tok.dim() != 3 or xhat.shape != tok.shape or pooled.shape != (tok.shape[0], tok.shape[2]):
+            raise ValueError('expected tok [n,N,C], xhat [n,N,C] and pooled [n,C]')
+        for t in (tok, xhat, pooled):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError('tok, xhat and pooled must be contiguous float32 tensors (xhat and pooled are written in place)')
+        n, N, Cc = tok.shape
+        if n:
+            with torch.cuda.device(tok.device):
+                _lib.check(_lib.load().fsvit_emd_table_prep(_ptr(tok), n, N, Cc, _ptr(xhat), _ptr(pooled), _stream_ptr(tok.device)))
+        return xhat, pooled
+
+    @staticmethod
+    def emd_head_gather(tok, xhat, pooled, query_slots, temperature, invalid, proto_slots=None, proto_tok=None):
+        """The head of `emd_head_forward` over rows of a token-map table: tok / xhat [n_slots,N,C], pooled [n_slots,C] fp32 (emd_table_prep),
+        query_slots [E,Q] and either proto_slots [E,P] (int32 / int64 slot numbers, one dtype for both) or a dense proto_tok [E,P,N,C] ->
+        (logits [E,Q,P], status [E,Q,P] int32); for the same maps the bits of `emd_head_forward`.  invalid [1] int32 is raised by one per slot outside
+        [0, n_slots); the problems of such a slot are NaN with status 0.  Limits: fsvit_emd_head_gather (fsvit.h)."""
+        _require_cuda(tok, xhat, pooled, query_slots, invalid, proto_slots, proto_tok)
+        if (proto_slots is None) == (proto_tok is None):
+            raise ValueError('emd_head_gather: exactly one of proto_slots and proto_tok')
+        if tok.dim() != 3 or xhat.shape != tok.shape or pooled.shape != (tok.shape[0], tok.shape[2]):
+            raise ValueError('expected tok [n_slots,N,C], xhat [n_slots,N,C] and pooled [n_slots,C]')
+        for t in (tok, xhat, pooled):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError('tok, xhat and pooled must be contiguous float32 tensors')
+        if query_slots.dim() != 2 or query_slots.dtype not in (torch.int32, torch.int64):
+            raise ValueError('expected query_slots [E,Q] int32 / int64')
+        if invalid.dtype != torch.int32 or invalid.numel() != 1:
+            raise ValueError('invalid: one int32')
+        n_slots, N, Cc = tok.shape
+        E, Q = query_slots.shape
+        qs = query_slots.contiguous()
+        ps = pt = None
+        if proto_slots is not None:
+            if proto_slots.dim() != 2 or proto_slots.shape[0] != E or proto_slots.dtype != qs.dtype:
+                raise ValueError('expected proto_slots [E,P] of the dtype of query_slots')
+            ps = proto_slots.contiguous()
+            P = ps.shape[1]
+        else:
+            if proto_tok.dim() != 4 or proto_tok.shape[0] != E or tuple(proto_tok.shape[2:]) != (N, Cc):
+                raise ValueError('expected proto_tok [E,P,N,C] with the N and C of the table')
+            pt = proto_tok.detach().contiguous().float()
+            P = pt.shape[1]
+        dev = tok.device
+        logits = torch.empty(E, Q, P, dtype=torch.float32, device=dev)
+        status = torch.empty(E, Q, P, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            lib = _lib.load()
+            ws = None
+            if pt is not None:
+                need = lib.fsvit_emd_head_gather_workspace_bytes(E, P, N, Cc)
+                ws = ops._emd_ws.get(dev)
+                if ws is None or ws.numel() < max(need, 16):
+                    ws = ops._emd_ws[dev] = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            _lib.check(lib.fsvit_emd_head_gather(_ptr(tok), _ptr(xhat), _ptr(pooled), n_slots, _ptr(qs), _ptr(ps), int(qs.dtype == torch.int64), _ptr(pt),
+                                                 E, P, Q, N, Cc, float(temperature), _ptr(logits), _ptr(status), _ptr(invalid), _ptr(ws),
+                                                 0 if ws is None else ws.numel(), _stream_ptr(dev)))
+        return logits, status
+
     _emd_sfc_ws = {}
 
     @staticmethod

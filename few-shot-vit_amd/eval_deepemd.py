@@ -12,7 +12,8 @@ carries the procedural stand-in weights.  `-deepemd grid` / `sampling` build the
 `-num_patch`; they need a dataset of raw images: 'mini-imagenet', 'tiered-imagenet', 'synthetic-images') and seed its generator from `-seed`; `-set`
 overrides the split of `-dataset_args`; `-norm_stats sund` normalises with the statistics of the reference's SUN-D loaders.  `-deepemd fcn` keeps the
 dataset's own eval transform: the reference's fcn loader (Resize([92, 92]) -> CenterCrop(80)), which train_deepemd applies to its val / test splits by
-itself, is `-dataset_args '{..., resize: [92, 92]}'` here.  Reports the mean accuracy and its 95 % interval over episodes (eval.py:100-104)."""
+itself, is `-dataset_args '{..., resize: [92, 92]}'` here.  `-feature_cache` (off by default; fcn and grid) encodes every image once into a
+`feature_table.TokenTable` and lets the head read its rows by slot number (fsvit_emd_head_gather): the same accuracies, bit for bit.  Reports the mean accuracy and its 95 % interval over episodes (eval.py:100-104)."""
 import argparse
 
 import numpy as np
@@ -59,7 +60,13 @@ def build_model(args):
     return model
 
 
-def evaluate(args, log=print):
+def evaluate(args, log=print, collect=None):
+    """-> dict(acc, ci, n).  `collect`, when a list, receives the per-episode accuracies (per cent, float64, in episode order).  With `-feature_cache`
+    every image is encoded once into a feature_table.TokenTable and the head reads its rows through slot numbers - the same accuracies from
+    `n_encoded` encoder passes instead of `n_requests` (both are then added to the dict)."""
+    feature_cache = bool(getattr(args, 'feature_cache', False))
+    if feature_cache and args.deepemd == 'sampling':
+        raise ValueError('fsvit: -feature_cache needs one node set per image; -deepemd sampling draws random patches at every visit (use fcn or grid)')
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     device = torch.device('cuda', torch.cuda.current_device())
@@ -79,12 +86,22 @@ def evaluate(args, log=print):
     sampler = CategoriesSampler(dataset.label, args.test_episode, args.way, args.shot + args.query)
     label = fs.make_nk_label(args.way, args.query).to(device)
     accs, pending = [], []
+    table = None
+    if feature_cache:
+        from .feature_table import TokenTable
+        table = TokenTable.for_dataset(model, dataset)
 
     def flush():
         if not pending:
             return
         G = len(pending)
         idx = torch.stack(list(pending)).view(-1)
+        if table is not None:
+            with torch.no_grad():
+                logits = table.logits(idx, args.way, args.shot, args.query, model)
+            accs.append((logits.argmax(dim=-1) == label).float().mean(dim=1))
+            pending.clear()
+            return
         if hasattr(dataset, 'gather'):
             data = dataset.gather(idx)
         else:
@@ -101,15 +118,22 @@ def evaluate(args, log=print):
             flush()
     flush()
     model.check_status()                                     # the one synchronisation: raises if any transportation problem hit a loop bound
+    if table is not None:
+        table.check()
     acc = torch.cat(accs).double().cpu().numpy() * 100.0
+    if collect is not None:
+        collect.extend(acc.tolist())
     mean = float(acc.mean())
     ci = float(utils.mean_confidence_interval(acc)) if len(acc) > 1 else float('nan')
     log('test Acc {:.4f}'.format(mean))
     log('Test Acc {:.4f} + {:.4f}'.format(mean, ci))
-    return dict(acc=mean, ci=ci, n=len(acc))
+    out = dict(acc=mean, ci=ci, n=len(acc))
+    if table is not None:
+        out.update(n_encoded=table.n_encoded, n_requests=table.n_requests)
+    return out
 
 
-def main(argv=None):
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('-encoder', '--backbone', dest='encoder', default='visformer_micro_80')
     p.add_argument('-way', type=int, default=5)
@@ -137,8 +161,13 @@ def main(argv=None):
     p.add_argument('-seed', type=int, default=1)
     p.add_argument('-numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'])
     p.add_argument('-episodes_per_launch', type=int, default=16)
-    args = p.parse_args(argv)
-    return evaluate(args, log=utils.log if hasattr(utils, 'log') else print)
+    p.add_argument('-feature_cache', action='store_true',
+                   help='encode every image once into a token-map table (fcn, grid); the head reads its rows by slot number - same accuracies')
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    return evaluate(parse_args(argv), log=utils.log if hasattr(utils, 'log') else print)
 
 
 if __name__ == '__main__':

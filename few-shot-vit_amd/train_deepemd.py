@@ -16,6 +16,8 @@ the reference's fcn loader: RandomResizedCrop(80) + flip for the train split, Re
 `resize` keys in `-dataset_args` win; other datasets keep their own transform); grid -> the patch pyramid, random ratios and flips for the train split only;
 sampling -> random patches for every split.  Without `-random_val_task` the index stream, the patch generator and the SFC permutations of the
 validation pass are re-seeded every epoch, so the validation set is fixed (the reference materialises its val loader once).
+`-eval_feature_cache` (off by default; fcn and grid) runs the validation and test passes from a `feature_table.TokenTable` per split, emptied before
+every pass because the weights have moved: every image a pass draws is encoded once, the figures are the same; the training step is untouched.
 
 Differences from the reference: a single process on a single GPU (no DataParallel); datasets come through this package's `datasets.make`
 (`-dataset`, `-dataset_args` a YAML dict; `-set` names the validation split) and episodes from this package's CategoriesSampler (class-major
@@ -128,10 +130,13 @@ def train_epoch(model, optimizer, dataset, args, epoch, device):
     return tl, ta, int(zeroed.item())
 
 
-def evaluate(model, dataset, args, n_episode, device, seed=None):
+def evaluate(model, dataset, args, n_episode, device, seed=None, table=None):
     """n_episode episodes under model.eval(), episodes_per_launch per launch -> (mean loss, per-episode accuracies in [0, 1] as a numpy array).
-    `seed` fixes the index stream, the dataset's patch generator and the SFC permutations."""
+    `seed` fixes the index stream, the dataset's patch generator and the SFC permutations.  `table` (a feature_table.TokenTable over `dataset`,
+    -eval_feature_cache) is reset - the weights have changed since the last pass - and every image the pass draws is encoded once; same figures."""
     model.eval()
+    if table is not None:
+        table.reset()
     if seed is not None:
         np.random.seed(seed)
         _seed_dataset(dataset, seed)
@@ -143,11 +148,14 @@ def evaluate(model, dataset, args, n_episode, device, seed=None):
         if not pending:
             return
         G = len(pending)
-        data = _gather(dataset, torch.stack(list(pending)).view(-1), device)
-        x_shot, x_query = fs.split_shot_query(data, args.way, args.shot, args.query, ep_per_batch=G)
+        idx = torch.stack(list(pending)).view(-1)
         label = fs.make_nk_label(args.way, args.query, ep_per_batch=G).to(device)
         with torch.no_grad():
-            logits = model(x_shot, x_query).view(-1, args.way)
+            if table is not None:
+                logits = table.logits(idx, args.way, args.shot, args.query, model).view(-1, args.way)
+            else:
+                x_shot, x_query = fs.split_shot_query(_gather(dataset, idx, device), args.way, args.shot, args.query, ep_per_batch=G)
+                logits = model(x_shot, x_query).view(-1, args.way)
         losses.append(F.cross_entropy(logits, label, reduction='none').view(G, -1).mean(dim=1))
         accs.append((logits.argmax(dim=1) == label).float().view(G, -1).mean(dim=1))
         pending.clear()
@@ -158,7 +166,21 @@ def evaluate(model, dataset, args, n_episode, device, seed=None):
             flush()
     flush()
     model.check_status()
+    if table is not None:
+        table.check()
     return float(torch.cat(losses).double().mean().item()), torch.cat(accs).double().cpu().numpy()
+
+
+def make_eval_table(model, dataset, args):
+    """-eval_feature_cache: a token-map table over a val / test split (None without the flag); `evaluate` resets it before every pass."""
+    if not getattr(args, 'eval_feature_cache', False):
+        return None
+    from .feature_table import TokenTable
+    was_training = model.training
+    try:
+        return TokenTable.for_dataset(model.eval(), dataset)
+    finally:
+        model.train(was_training)
 
 
 def save_path_of(args):
@@ -167,6 +189,8 @@ def save_path_of(args):
 
 
 def run(args, log=print):
+    if getattr(args, 'eval_feature_cache', False) and args.deepemd == 'sampling':
+        raise ValueError('fsvit: -eval_feature_cache needs one node set per image; -deepemd sampling draws random patches at every visit (use fcn or grid)')
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
     device = torch.device('cuda', torch.cuda.current_device())
@@ -177,6 +201,7 @@ def run(args, log=print):
     trainset, valset = make_dataset(args, 'train', train=True), make_dataset(args, args.set)
     _seed_dataset(trainset, args.seed)
     _seed_dataset(valset, args.seed)
+    val_table = make_eval_table(model, valset, args)
     if not args.random_val_task:
         log('fix val set for all epochs')
     optimizer, lr_scheduler = make_optimizer(model, args)
@@ -191,7 +216,8 @@ def run(args, log=print):
         timer.s()
         lr = optimizer.param_groups[0]['lr']
         tl, ta, zeroed = train_epoch(model, optimizer, trainset, args, epoch, device)
-        vl, va = evaluate(model, valset, args, args.val_episode, device, seed=None if args.random_val_task else args.seed)
+        vl, va = evaluate(model, valset, args, args.val_episode, device, seed=None if args.random_val_task else args.seed,
+                          table=val_table)
         va = float(va.mean())
         log('epo {}, lr {:.6g}, train loss={:.4f} acc={:.4f}, val loss={:.4f} acc={:.4f}, nan-gradient tensors zeroed {}'.format(
             epoch, lr, tl, ta, vl, va, zeroed))
@@ -213,7 +239,8 @@ def run(args, log=print):
     # Test phase (train_meta.py:237-277)
     testset = make_dataset(args, 'test')
     model.load_state_dict(torch.load(os.path.join(save_path, 'max_acc.pth'), map_location='cpu')['params'])
-    _, acc = evaluate(model, testset, args, args.test_episode, device, seed=args.seed)
+    test_table = make_eval_table(model, testset, args)
+    _, acc = evaluate(model, testset, args, args.test_episode, device, seed=args.seed, table=test_table)
     m, pm = compute_confidence_interval(acc * 100.0)
     result_list.append('Val Best Epoch {},\nbest val Acc {:.4f}, \nbest est Acc {:.4f}'.format(trlog['max_acc_epoch'], trlog['max_acc'], m))
     result_list.append('Test Acc {:.4f} + {:.4f}'.format(m, pm))
@@ -221,7 +248,10 @@ def run(args, log=print):
     log(result_list[-1])
     with open(os.path.join(save_path, 'results.txt'), 'w') as f:
         f.write('\n'.join(result_list) + '\n')
-    return dict(max_acc=trlog['max_acc'], max_acc_epoch=trlog['max_acc_epoch'], test_acc=m, test_ci=pm, save_path=save_path)
+    out = dict(max_acc=trlog['max_acc'], max_acc_epoch=trlog['max_acc_epoch'], test_acc=m, test_ci=pm, save_path=save_path)
+    if val_table is not None:                          # the counters of the last pass over each split (every pass starts from an empty table)
+        out['eval_cache'] = {name: dict(n_encoded=t.n_encoded, n_requests=t.n_requests) for name, t in (('val', val_table), ('test', test_table))}
+    return out
 
 
 def parse_args(argv=None):
@@ -260,6 +290,8 @@ def parse_args(argv=None):
     p.add_argument('-numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'])
     p.add_argument('-norm_stats', default='imagenet', choices=['imagenet', 'sund'])
     p.add_argument('-episodes_per_launch', type=int, default=16, help='validation / test episodes per launch (training runs one per forward)')
+    p.add_argument('-eval_feature_cache', action='store_true',
+                   help='validation / test: encode every image of a pass once into a token-map table (fcn, grid) - same figures')
     p.add_argument('-save_root', default='checkpoint')
     return p.parse_args(argv)
 

@@ -723,6 +723,23 @@ int fsvit_emd_head_forward(const float* shot_tok_dev, const float* query_tok_dev
 int fsvit_emd_head_backward(const float* shot_tok_dev, const float* query_tok_dev, const float* dlogits_dev, const float* flow_dev, int E, int P, int Q,
                             int N, int C, float temperature, float* d_shot_tok_dev, float* d_query_tok_dev, void* workspace_dev, size_t workspace_bytes,
                             void* stream);
+/* The head's forward over a token-map table (feature_table.TokenTable): every image is encoded and prepared once, the episodes address its rows.
+ * fsvit_emd_table_prep fills rows of the table: tok [n_img][N][C] -> xhat [n_img][N][C] (the channel-centred, L2-normalised nodes) and pooled [n_img][C]
+ * (the token mean of the un-centred map) - the values fsvit_emd_head_forward prepares for the same map, whatever launch it sits in.
+ * fsvit_emd_head_gather: query (e, q) is the table row query_slots[e][q]; the class side is either the table row proto_slots[e][p] (1-shot) or the dense
+ * map proto_tok[e][p] of [E][P][N][C] (the 5-shot SFC, prepared into the workspace by this call) - exactly one of the two is non-NULL.  Slots are int32, or
+ * int64 with slots_are_int64 != 0.  logits / status [E][Q][P] are, for the same maps, the bits of fsvit_emd_head_forward.  A slot outside [0, n_slots) is
+ * detected before any table read and never becomes an address: *invalid_dev (an int the caller zeroes once) is raised by one per such entry, and the
+ * problems the entry takes part in get a NaN logit and status 0.  workspace: fsvit_emd_head_gather_workspace_bytes (0 for a refused shape), needed by the
+ * dense-prototype form only (the slot form accepts NULL).  Refused with FSVIT_ERR_ARG and a message, nothing launched: a null pointer, both or neither
+ * of proto_slots / proto_tok, n_slots < 1, the shape limits of fsvit_emd_head_forward (N 1 .. 32, C a positive multiple of 64, the problem counts), a
+ * temperature that is not finite; FSVIT_ERR_WORKSPACE for a workspace that is too small.  E, P or Q == 0 is a no-op. */
+int fsvit_emd_table_prep(const float* tok_dev, int n_img, int N, int C, float* xhat_dev, float* pooled_dev, void* stream);
+size_t fsvit_emd_head_gather_workspace_bytes(int E, int P, int N, int C);
+int fsvit_emd_head_gather(const float* tok_dev, const float* xhat_dev, const float* pooled_dev, int n_slots, const void* query_slots_dev,
+                          const void* proto_slots_or_null_dev, int slots_are_int64, const float* proto_tok_or_null_dev, int E, int P, int Q, int N, int C,
+                          float temperature, float* logits_dev, int* status_dev, int* invalid_dev, void* workspace_or_null_dev, size_t workspace_bytes,
+                          void* stream);
 /* The solver alone, for operator tests: cost [B][N][N], w1 / w2 [B][N] already normalised (equal sums) -> flow [B][N][N], status [B]; _counts also
  * writes the number of augmenting paths of every problem (n_augment [B]). */
 int fsvit_op_emd_solve(const float* cost_dev, const float* w1_dev, const float* w2_dev, int B, int N, float* flow_dev, int* status_dev, void* stream);
