@@ -82,6 +82,7 @@ SIGNATURES = {
     'fsvit_proto_bank_topk_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'fsvit_proto_bank_topk': (_i, [_fp, _fp, _vp, _i, _i, _i, _f, _fp, _i, _i, _i, _fp, _vp, _fp, _vp, _sz, _vp]),
     'fsvit_proto_auc':(_i, [_fp, _fp, _i, _i, _i, _i, _fp, _fp, _vp]),
+    'fsvit_proto_auc_gather': (_i, [_fp, _i, _i, _vp, _vp, _i, _i, _i, _i, _fp, _fp, _vp, _vp]),
     'fsvit_meta_baseline_forward': (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _i, _fp, _fp, _fp, _fp,
                                          _vp, _sz, _vp]),
     'fsvit_conv_gemm': (_i, [_vp, _vp, _fp, _vp, _fp, _vp] + [_i] * 15 + [_i, _vp]),

@@ -1186,6 +1186,17 @@ extern "C" int fsvit_proto_auc(const float* feat_shot, const float* feat_query, 
   return 0;
 }
 
+extern "C" int fsvit_proto_auc_gather(const float* table, int N, int D, const void* shot_slots, const void* query_slots, int idx_is_int64, int E, int shot,
+                                      int Q, float* auc, float* score, int* invalid, void* stream) {
+  if (!table || !shot_slots || !query_slots || !auc || !invalid) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc_gather: null argument");
+  if (E < 0 || N < 1 || shot < 1) return fail(FSVIT_ERR_ARG, "fsvit_proto_auc_gather: E = %d, N = %d, shot = %d", E, N, shot);
+  if (Q < 2 || Q > 4096 || Q % 2)
+    return fail(FSVIT_ERR_ARG, "fsvit_proto_auc_gather: Q = %d must be even and in [2, 4096] (positives first, as many negatives)", Q);
+  RC_TRY(proto_bank_dims("fsvit_proto_auc_gather", 1, D));
+  RC_TRY(fsvit::launch_proto_auc_gather(table, N, D, shot_slots, query_slots, idx_is_int64, E, shot, Q, auc, score, invalid, (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int fsvit_meta_baseline_forward(void* hv, const float* x_shot, const float* x_query, int E, int way,
                                            int shot, int Q, int img_h, int img_w, float temp, int method, float* logits,
                                            float* acc, float* loss, float* feat, void* ws, size_t ws_bytes, void* stream) {

@@ -33,6 +33,9 @@ size_t proto_bank_topk_workspace_bytes(int Q, int way, int K, int n_split);
 int launch_proto_bank_topk(const float* query, const float* proto, const int* empty, int Q, int way, int D, float temp, const float* temp_dev, int method, int K,
                            int n_split, float* values, int* indices, float* lse, void* ws, hipStream_t s);
 int launch_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, hipStream_t s);
+// the same reduction over rows of a feature table [N][D]: shot_slots [E][shot], query_slots [E][Q] (int32 / int64 slots); limits: fsvit_proto_auc_gather of fsvit.h
+int launch_proto_auc_gather(const float* table, int N, int D, const void* shot_slots, const void* query_slots, int idx_is_int64, int E, int shot, int Q,
+                            float* auc, float* score, int* invalid, hipStream_t s);
 // distillation head (token_label.hip): LinearClassifier forward / backward, generate_softlabel, SoftTargetCrossEntropy, F.normalize on rows
 int launch_linear_fwd(const float* x, const float* w, const float* b, float* y, int M, int N, int K, hipStream_t s);
 int launch_linear_bwd(const float* dy, const float* x, const float* w, float* dx, int accumulate_dx, float* dw, float* db, int M, int N, int K, hipStream_t s);

@@ -13,6 +13,8 @@
 //    list in the 16 lanes that own the row, one (max, sum) pair per row and segment, then one wave per row merges the splits.  Bits do not depend on the split.
 //  * proto_auc: the --sauc reduction (meta_tuning_sun_m/test_few_shot.py:95-112): per episode, cosine scores of the queries against the single
 //    prototype of class 0 and their ROC-AUC as the pair count (#{pos > neg} + #{pos == neg} / 2) / (n_pos n_neg).  One workgroup per episode.
+//  * proto_auc_gather: the same reduction over rows of a feature table [N][D] addressed by slot numbers (feature_table.py: every image is encoded
+//    once); one device body serves both kernels.
 #include "fsvit_common.h"
 #include "kernels.h"
 
@@ -435,19 +437,19 @@ int launch_proto_bank_topk(const float* query, const float* proto, const int* em
 }
 
 // ---- --sauc: LDS = proto [D] | score [Q]
-__global__ __launch_bounds__(256) void proto_auc_kernel(const float* __restrict__ feat_shot, const float* __restrict__ feat_query, int shot, int Q, int D,
-                                                        float* __restrict__ auc, float* __restrict__ score) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int pairs2;                                       // 2 #{pos > neg} + #{pos == neg}
+// The arithmetic of one episode, shared by the two kernels below: shot_row(k) / query_row(q) give the address of a feature row [D] of episode blockIdx.x -
+// contiguous rows in proto_auc_kernel, rows of a feature table in proto_auc_gather_kernel; everything after the address is the same instruction
+// sequence, so the two kernels give the same bits for the same rows.  smem: [D] + [Q] floats; pairs2: one int of LDS, 2 #{pos > neg} + #{pos == neg}.
+template <typename ShotRow, typename QueryRow>
+__device__ __forceinline__ void proto_auc_body(ShotRow shot_row, QueryRow query_row, unsigned char* smem, int* pairs2, int shot, int Q, int D,
+                                               float* __restrict__ auc, float* __restrict__ score) {
   float* proto = reinterpret_cast<float*>(smem);               // [D]
   float* sc = proto + D;                                       // [Q]
   const int e = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const float* fs = feat_shot + (size_t)e * shot * D;
-  const float* fq = feat_query + (size_t)e * Q * D;
-  if (t == 0) pairs2 = 0;
+  if (t == 0) *pairs2 = 0;
   for (int d = t; d < D; d += 256) {
     float s = 0.f;
-    for (int k = 0; k < shot; ++k) s += fs[(size_t)k * D + d];
+    for (int k = 0; k < shot; ++k) s += shot_row(k)[d];
     proto[d] = s / (float)shot;
   }
   __syncthreads();
@@ -455,7 +457,7 @@ __global__ __launch_bounds__(256) void proto_auc_kernel(const float* __restrict_
   for (int d = lane; d < D; d += 64) ss += proto[d] * proto[d];
   const float pinv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
   for (int q = wave; q < Q; q += 4) {
-    const float* x = fq + (size_t)q * D;
+    const float* x = query_row(q);
     float qq = 0.f, qp = 0.f;
     for (int d = lane; d < D; d += 64) { qq += x[d] * x[d]; qp += x[d] * (proto[d] * pinv); }
     const float v = wave_sum(qp) * (1.0f / fmaxf(sqrtf(wave_sum(qq)), 1e-12f));
@@ -471,17 +473,78 @@ __global__ __launch_bounds__(256) void proto_auc_kernel(const float* __restrict_
     const float p = sc[i / k], n = sc[k + i % k];
     mine += p > n ? 2 : (p == n ? 1 : 0);
   }
-  if (mine) atomicAdd(&pairs2, mine);
+  if (mine) atomicAdd(pairs2, mine);
   __syncthreads();
-  if (t == 0) auc[e] = (float)pairs2 / (2.0f * (float)k * (float)k);
+  if (t == 0) auc[e] = (float)*pairs2 / (2.0f * (float)k * (float)k);
 }
+
+__global__ __launch_bounds__(256) void proto_auc_kernel(const float* __restrict__ feat_shot, const float* __restrict__ feat_query, int shot, int Q, int D,
+                                                        float* __restrict__ auc, float* __restrict__ score) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int pairs2;
+  const float* fs = feat_shot + (size_t)blockIdx.x * shot * D;
+  const float* fq = feat_query + (size_t)blockIdx.x * Q * D;
+  proto_auc_body([=](int k) { return fs + (size_t)k * D; }, [=](int q) { return fq + (size_t)q * D; }, smem, &pairs2, shot, Q, D, auc, score);
+}
+
+// The same reduction over rows gathered from a feature table [N][D]: shot_slots [E][shot] (the shots of class 0), query_slots [E][Q] (positives first).
+// A slot outside [0, N) never becomes an address: its row is read from slot 0, *invalid is raised by one per such entry (integer adds, any order) and
+// the episode's auc and score are written as NaN.
+template <typename L>
+__global__ __launch_bounds__(256) void proto_auc_gather_kernel(const float* __restrict__ table, const L* __restrict__ shot_slots,
+                                                               const L* __restrict__ query_slots, int N, int shot, int Q, int D, float* __restrict__ auc,
+                                                               float* __restrict__ score, int* __restrict__ invalid) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  __shared__ int pairs2, n_bad;
+  const int e = blockIdx.x, t = threadIdx.x;
+  const L* es = shot_slots + (size_t)e * shot;
+  const L* eq = query_slots + (size_t)e * Q;
+  if (t == 0) n_bad = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int i = t; i < shot; i += 256) mine += (es[i] < (L)0 || es[i] >= (L)N);
+  for (int i = t; i < Q; i += 256) mine += (eq[i] < (L)0 || eq[i] >= (L)N);
+  if (mine) atomicAdd(&n_bad, mine);
+  __syncthreads();
+  const int bad = n_bad;
+  auto row = [=](const L* slots, int i) {
+    const L s = slots[i];
+    return table + (size_t)((s < (L)0 || s >= (L)N) ? (L)0 : s) * D;
+  };
+  proto_auc_body([=](int k) { return row(es, k); }, [=](int q) { return row(eq, q); }, smem, &pairs2, shot, Q, D, auc, score);
+  if (!bad) return;                                            // (uniform over the workgroup)
+  __syncthreads();                                             // the body's own stores to this episode's outputs come first
+  const float nan = __builtin_nanf("");
+  if (score)
+    for (int i = t; i < Q; i += 256) score[(size_t)e * Q + i] = nan;
+  if (t == 0) {
+    auc[e] = nan;
+    atomicAdd(invalid, bad);
+  }
+}
+
+// Q <= 4096: the pair count 2 (Q / 2)^2 stays below 2^24, exact in fp32; with D <= 8192 the LDS is at most 48 KB
+static bool proto_auc_dims(int shot, int Q, int D) { return shot >= 1 && Q >= 2 && Q % 2 == 0 && Q <= 4096 && D >= 1 && D <= 8192; }
 
 int launch_proto_auc(const float* feat_shot, const float* feat_query, int E, int shot, int Q, int D, float* auc, float* score, hipStream_t s) {
   if (E <= 0) return 0;
-  // Q <= 4096: the pair count 2 (Q / 2)^2 stays below 2^24, exact in fp32; with D <= 8192 the LDS is at most 48 KB
-  if (shot < 1 || Q < 2 || Q % 2 || Q > 4096 || D < 1 || D > 8192) return (int)hipErrorInvalidValue;
+  if (!proto_auc_dims(shot, Q, D)) return (int)hipErrorInvalidValue;
   const size_t lds = ((size_t)D + Q) * sizeof(float);
   hipLaunchKernelGGL(proto_auc_kernel, dim3(E), dim3(256), lds, s, feat_shot, feat_query, shot, Q, D, auc, score);
+  return (int)hipGetLastError();
+}
+
+int launch_proto_auc_gather(const float* table, int N, int D, const void* shot_slots, const void* query_slots, int idx_is_int64, int E, int shot, int Q,
+                            float* auc, float* score, int* invalid, hipStream_t s) {
+  if (E <= 0) return 0;
+  if (N < 1 || !proto_auc_dims(shot, Q, D)) return (int)hipErrorInvalidValue;
+  const size_t lds = ((size_t)D + Q) * sizeof(float);
+  if (idx_is_int64)
+    hipLaunchKernelGGL(proto_auc_gather_kernel<long long>, dim3(E), dim3(256), lds, s, table, (const long long*)shot_slots, (const long long*)query_slots, N,
+                       shot, Q, D, auc, score, invalid);
+  else
+    hipLaunchKernelGGL(proto_auc_gather_kernel<int>, dim3(E), dim3(256), lds, s, table, (const int*)shot_slots, (const int*)query_slots, N, shot, Q, D, auc,
+                       score, invalid);
   return (int)hipGetLastError();
 }
 

@@ -1247,6 +1247,34 @@ class ops:
             _lib.check(lib.fsvit_proto_auc(_ptr(feat_shot), _ptr(feat_query), E, shot, Q, D, _ptr(auc), _ptr(score), _stream_ptr(dev)))
         return (auc, score) if want_score else auc
 
+    @staticmethod
+    def proto_auc_gather(table, shot_slots, query_slots, invalid, want_score=False):
+        """The reduction of `proto_auc` over rows of a feature table: table [N,D] fp32, shot_slots [E,shot] (the shots of class 0), query_slots [E,Q]
+        (positives first, then as many negatives), both int32 or both int64 -> auc [E] fp32, with want_score also score [E,Q]; for the same rows the bits
+        of `proto_auc`.  invalid [1] int32 is raised by one per slot outside [0, N); such an episode's outputs are NaN.  Limits: fsvit_proto_auc_gather
+        (fsvit.h)."""
+        _require_cuda(table, shot_slots, query_slots, invalid)
+        lib = _lib.load()
+        table, = ops._head_in(table)
+        if (table.dim() != 2 or shot_slots.dim() != 2 or query_slots.dim() != 2 or shot_slots.shape[0] != query_slots.shape[0]
+                or shot_slots.dtype not in (torch.int32, torch.int64) or query_slots.dtype != shot_slots.dtype):
+            raise ValueError('expected table [N,D], shot_slots [E,shot] and query_slots [E,Q] of one dtype, int32 / int64')
+        if invalid.dtype != torch.int32 or invalid.numel() != 1:
+            raise ValueError('invalid: one int32')
+        shot_slots, query_slots = shot_slots.contiguous(), query_slots.contiguous()
+        N, D = table.shape
+        E, shot = shot_slots.shape
+        Q = query_slots.shape[1]
+        dev = table.device
+        auc = torch.empty(E, dtype=torch.float32, device=dev)
+        score = torch.empty(E, Q, dtype=torch.float32, device=dev) if want_score else None
+        if E == 0:                                               # (an empty tensor has no address to hand over)
+            return (auc, score) if want_score else auc
+        with torch.cuda.device(dev):
+            _lib.check(lib.fsvit_proto_auc_gather(_ptr(table), N, D, _ptr(shot_slots), _ptr(query_slots), int(shot_slots.dtype == torch.int64), E, shot, Q,
+                                                  _ptr(auc), _ptr(score), _ptr(invalid), _stream_ptr(dev)))
+        return (auc, score) if want_score else auc
+
     # ---- operator entry points of the memory-bound training kernels (fsvit_op_*: tests, tools).  Maps are [M, C] / NHWC tensors in the storage
     # dtype (fp32 or bf16), statistics / parameters fp32; outputs and the kernels' `partial` scratch are allocated here.
     @staticmethod

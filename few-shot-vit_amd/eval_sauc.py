@@ -5,26 +5,34 @@ stream, seeds and launch batching as `test_few_shot.evaluate`, which this module
 passes and one `ops.proto_auc` launch - no per-episode host sync - and the multi-rank path exchanges the AUCs through the same
 `parallel.gather_in_stream_order` call.
 
-  python -m fewshot_vit_amd.eval_sauc --config few-shot-vit_amd/configs/test_synthetic.yaml --shot 1 --sauc"""
+`--feature-cache` / `feature_cache=True` (off by default): a flush encodes only the images no earlier flush has seen into a
+`feature_table.FeatureTable` and reduces over its rows (`FeatureTable.auc`, fsvit_proto_auc_gather) - the same `va_lst` from at most one encoder pass
+per image of the split.  Without `--sauc` the switch is `eval_cached.evaluate`'s.
+
+  python -m fewshot_vit_amd.eval_sauc --config few-shot-vit_amd/configs/test_synthetic.yaml --shot 1 --sauc [--feature-cache]"""
 import argparse
 
 import numpy as np
 import torch
 import yaml
 
-from . import datasets, parallel, test_few_shot, utils
+from . import datasets, eval_cached, parallel, test_few_shot, utils
 from .datasets.samplers import CategoriesSampler
 from .engine import ops
+from .feature_table import FeatureTable
 from .utils import few_shot as fs
 
 
 def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch_batches=None, numerics=None,
-             rank=0, world=1, device=None, log=print, collect_pred=False, sauc=False):
-    """sauc=False: `test_few_shot.evaluate` itself.  sauc=True: the same dict, where `va_lst` holds one AUC per EPISODE as the reference's loop appends
-    them (:107-112), `acc` their mean, `ci` their 95 % interval and `loss` the untouched averager's value."""
-    if not sauc:
-        return test_few_shot.evaluate(config, shot=shot, test_epochs=test_epochs, n_batch=n_batch, ep_per_batch=ep_per_batch, launch_batches=launch_batches,
-                                      numerics=numerics, rank=rank, world=world, device=device, log=log, collect_pred=collect_pred)
+             rank=0, world=1, device=None, log=print, collect_pred=False, sauc=False, feature_cache=False):
+    """sauc=False: `eval_cached.evaluate` - `test_few_shot.evaluate` itself with the cache off, plus the two image counters.  sauc=True: the same dict,
+    where `va_lst` holds one AUC per EPISODE as the reference's loop appends them (:107-112), `acc` their mean, `ci` their 95 % interval and `loss` the
+    untouched averager's value; out['images_requested'] / out['images_encoded'] are the images this rank's flushes read / pushed through the encoder
+    (equal without the cache)."""
+    if not sauc:                                            # (both drivers carry the same keys, whatever the switches)
+        return eval_cached.evaluate(config, shot=shot, test_epochs=test_epochs, n_batch=n_batch, ep_per_batch=ep_per_batch, launch_batches=launch_batches,
+                                    numerics=numerics, rank=rank, world=world, device=device, log=log, collect_pred=collect_pred,
+                                    feature_cache=feature_cache)
     if collect_pred:
         raise ValueError('collect_pred: --sauc scores against one prototype, there is no per-query arg-max to collect')
     import time
@@ -43,6 +51,8 @@ def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch
     engine = model.encoder.engine()
     if launch_batches is None:
         launch_batches = test_few_shot.default_launch_batches(engine, ep_per_batch * n_way * (shot + n_query), engine.img_size, device)
+    table = FeatureTable.for_dataset(model, dataset) if feature_cache else None
+    n_dense = 0                                             # images the dense route's flushes encoded: the shots of class 0 and all queries
 
     np.random.seed(12345)                                  # fixes the episode stream (:76)
     out = None
@@ -53,9 +63,15 @@ def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch
         aucs, pending, last_label = [], [], None
 
         def flush():
+            nonlocal n_dense
             if not pending:
                 return
             E = len(pending) * ep_per_batch
+            if table is not None:                           # only the images no earlier flush has seen go through the encoder
+                aucs.append(table.auc(torch.stack(list(pending)), shot, n_query).view(len(pending), ep_per_batch))
+                pending.clear()
+                return
+            n_dense += E * (shot + n_way * n_query)
             if hasattr(dataset, 'gather'):                  # device-resident dataset: the shots of class 0, then all queries, in one gather
                 idx = torch.stack(list(pending)).view(E, n_way, shot + n_query)
                 data = dataset.gather(torch.cat([idx[:, 0, :shot].reshape(-1), idx[:, :, shot:].reshape(-1)]))
@@ -79,6 +95,8 @@ def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch
                 if ramp:
                     ramp.pop(0)
         flush()
+        if table is not None:
+            table.check()                                    # raises if the reduction met a slot outside the table
         mine = torch.cat(aucs).double() if aucs else torch.zeros(0, ep_per_batch, dtype=torch.float64, device=device)
         allv = parallel.gather_in_stream_order(mine, n_batch, rank, world).cpu().numpy()     # the one exchange: [n_batch, ep_per_batch]
         per_batch_items = ep_per_batch * n_way * (shot + n_query)
@@ -90,6 +108,7 @@ def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch
         out['loop_seconds'] = time.perf_counter() - t_loop      # the keys of test_few_shot.evaluate's dict, all of them
         out['launch_batches'] = launch_batches
         out['phase_seconds'] = {'dataset': t_dataset - t_call, 'model': t_model - t_dataset, 'engine': t_loop - t_model, 'loop': out['loop_seconds']}
+        out['images_requested'], out['images_encoded'] = (table.n_requests, table.n_encoded) if table is not None else (n_dense, n_dense)
         if rank == 0:
             log('test epoch {}: acc={:.2f} +- {:.2f} (%), loss={:.4f} (@{})'.format(epoch, out['acc'] * 100, out['ci'] * 100, out['loss'], last_label))
     return out
@@ -106,6 +125,8 @@ def make_parser():
     parser.add_argument('--ep-per-batch', type=int, default=1)
     parser.add_argument('--launch-batches', type=int, default=None, help='reference batches per engine launch (default: one encoder chunk)')
     parser.add_argument('--numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'], help="default: FSVIT_NUMERICS or 'bf16'")
+    parser.add_argument('--feature-cache', action='store_true',
+                        help='encode every image once into a feature table and run the episodes over its rows (same numbers, fewer encoder passes)')
     return parser
 
 
@@ -118,7 +139,7 @@ def main(argv=None):
     torch.cuda.set_device(local)
     evaluate(config, shot=args.shot, test_epochs=args.test_epochs, n_batch=args.episodes, ep_per_batch=args.ep_per_batch,
              launch_batches=args.launch_batches, numerics=args.numerics, rank=rank, world=world,
-             device=torch.device('cuda', local), log=utils.log, sauc=args.sauc)
+             device=torch.device('cuda', local), log=utils.log, sauc=args.sauc, feature_cache=args.feature_cache)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -4,7 +4,8 @@ The reference's evaluation (test_phase/test_few_shot.py:76-92) encodes every ima
 test split are 160 000 (1-shot) or 200 000 (5-shot) encoder passes.  In eval mode the transform is deterministic (Resize -> CenterCrop), BatchNorm
 uses its running statistics and the engines give the same bits for an image whatever launch it sits in, so the feature of image i is a function
 of i alone.  The table keeps it: `ensure` encodes the images it has not seen (ascending image order, the engine's chunks) and hands back slot numbers,
-`episodes` runs the episode head over those slots in one launch (fsvit_proto_head_gather, head.hip) - no image tensor, no feature copy.
+`episodes` runs the episode head over those slots in one launch (fsvit_proto_head_gather, head.hip) - no image tensor, no feature copy; `auc` does
+the same for the `--sauc` reduction (fsvit_proto_auc_gather, proto_bank.hip) and encodes only the images that reduction reads.
 
 TokenTable does the same for the DeepEMD head (eval_deepemd -feature_cache, train_deepemd -eval_feature_cache): its rows are whole node sets - the
 token map of an image, or the features of its grid patches - with the head's node preparation done once per image, and `logits` runs the
@@ -100,6 +101,22 @@ class FeatureTable(_SlotTable):
             raise ValueError(f'episodes: {idx.numel()} indices are not a whole number of {way}-way {shot}+{n_query} episodes')
         slots = self.ensure(idx).view(-1, way, shot + n_query).to(self.device)       # (a blocking copy: the host array is a temporary)
         return ops.proto_head_gather(self.feat[:self.n_encoded], slots, shot, temp, self.invalid, method)
+
+    def auc(self, idx, shot, n_query):
+        """The `--sauc` reduction.  idx: host tensor of dataset indices of 2-way episodes, [G, ep_per_batch * 2 * (shot + n_query)] as the sampler yields
+        them (class-major) -> auc [E], E = G * ep_per_batch: the bits of `ops.proto_auc` on the gathered images.  Only what the reduction reads is
+        encoded - the `shot` shots of class 0 and all 2 * n_query queries, class 0's (the positives) first; the shots of class 1 are never touched
+        (the reference scores against `x_shot[:, 0]`).  `ensure`, then one launch."""
+        from .engine import ops
+        idx = torch.as_tensor(idx)
+        per_episode = 2 * (shot + n_query)
+        if idx.numel() % per_episode:
+            raise ValueError(f'auc: {idx.numel()} indices are not a whole number of 2-way {shot}+{n_query} episodes')
+        idx = idx.reshape(-1, 2, shot + n_query)
+        E = idx.shape[0]
+        used = torch.cat([idx[:, 0, :shot].reshape(-1), idx[:, :, shot:].reshape(-1)])
+        slots = self.ensure(used).to(self.device)                     # (a blocking copy: the host array is a temporary)
+        return ops.proto_auc_gather(self.feat[:self.n_encoded], slots[:E * shot].view(E, shot), slots[E * shot:].view(E, 2 * n_query), self.invalid)
 
     @classmethod
     def for_dataset(cls, model, dataset, chunk_images=None):

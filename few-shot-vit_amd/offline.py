@@ -14,7 +14,12 @@ the flattened gradients over RCCL.  The strong / weak augmentation pair comes fr
 batch on the GPU, datasets/transforms.py:DeviceStrongWeakPair; the reference keys it on `split: train`); with any other dataset the teacher sees
 the same image as the student unless the dataset returns three items.  `weak_randaug: 0.2` next to it switches on the weak view's
 RandomApply([RandAugment], p = 0.2) (a third launch, fsvit_image_rand_augment; timm's algorithm restated, not pinned against timm; off by
-default).  Not restated: tensorboard, dataset visualisation, `epoch_ex`.
+default).  With `fs_dataset` in the YAML the reference's fs-eval block (:343-367) runs every `eval_fs_epoch` epochs (default 5) and at the last
+epoch: 5-way 1- and 5-shot, `fs_batches` (default 200) batches of 4 episodes with the validation loop's head, accuracies in `trlog['fsa-1']` /
+`trlog['fsa-5']`.  `eval_feature_cache: true` (default false): the validation loop and the fs-eval block take their logits from one
+feature_table.FeatureTable per evaluation dataset - every image an evaluation touches is encoded once (the 1- and 5-shot pass share one fill), the head
+runs over all episodes of an evaluation in one launch (fsvit_proto_head_gather); the tables are emptied after each epoch's training steps.
+Not restated: tensorboard, dataset visualisation, `epoch_ex`.
 
   python -m fewshot_vit_amd.offline --config few-shot-vit_amd/configs/offline_synthetic.yaml
 """
@@ -65,6 +70,34 @@ def few_shot_eval(model, dataset, sampler, n_way, n_shot, n_query, ep_per_batch,
     return la.item(), aa.item()
 
 
+def table_eval_logits(table, sampler, n_way, n_shot, n_query):
+    """The logits of one whole evaluation from a feature_table.FeatureTable (`eval_feature_cache: true`): the sampler's epoch is drawn first (the draws
+    do not depend on the encoder and the sampler is the loop's only consumer of np.random), the table encodes the images it has not seen, and the head
+    of `few_shot_eval` - cosine prototypes on the pooled feature, temperature 10.0 - runs over all episodes in one launch
+    -> [n_batches, ep_per_batch * n_way * n_query, n_way], batch g being the `logits` of the g-th pass of that loop."""
+    batches = [idx for idx in sampler]
+    if not batches:
+        return torch.zeros(0, 0, n_way, device=table.device)
+    idx = torch.stack(batches)
+    logits, _, _ = table.episodes(idx, n_way, n_shot, n_query, 10.0, 'cos')
+    table.check()
+    return logits.view(idx.shape[0], -1, n_way)
+
+
+def few_shot_eval_table(table, sampler, n_way, n_shot, n_query, ep_per_batch):
+    """`few_shot_eval` over `table_eval_logits`: loss and accuracy of every batch by the lines of that loop, on the device, then one copy to the host;
+    the averagers are fed in batch order."""
+    logits = table_eval_logits(table, sampler, n_way, n_shot, n_query)
+    label = fs.make_nk_label(n_way, n_query, ep_per_batch=ep_per_batch).to(logits.device)
+    la, aa = utils.Averager(), utils.Averager()
+    if logits.shape[0]:
+        stats = torch.stack([torch.stack([F.cross_entropy(lg, label), (torch.argmax(lg, dim=1) == label).float().mean()]) for lg in logits]).cpu()
+        for loss, acc in stats.tolist():
+            la.add(loss)
+            aa.add(acc)
+    return la.item(), aa.item()
+
+
 def distill_step(model, teacher, optimizer, criterion_tl, data, weak_data, label, tl_soft_k=3, bp=10, world=1):
     """One SUN meta-training step (offline.py:283-303): student forward (token logits with the extra background class, global logits), global
     cross-entropy, frozen teacher forward on the weak view -> generate_softlabel, 0.5 x SoftTargetCrossEntropy on the student's token logits,
@@ -108,6 +141,11 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     train_dataset = datasets.make(config['train_dataset'], **config['train_dataset_args'])
     val_dataset = datasets.make(config['val_dataset'], **config['val_dataset_args'])
     val_sampler = CategoriesSampler(val_dataset.label, config.get('eval_batches', 200), n_way, n_shot + n_query, ep_per_batch=ep_per_batch)
+    fs_dataset, fs_samplers, n_shots = None, [], [1, 5]
+    if config.get('fs_dataset'):                                                             # the fs-eval block: 5-way 1- and 5-shot, 4 episodes per batch
+        fs_dataset = datasets.make(config['fs_dataset'], **(config.get('fs_dataset_args') or {}))
+        ef_epoch = config.get('eval_fs_epoch') or 5
+        fs_samplers = [CategoriesSampler(fs_dataset.label, config.get('fs_batches', 200), 5, n + 15, ep_per_batch=4) for n in n_shots]
     if hasattr(train_dataset, 'gather_pair'):                                                # ranks draw different views; a run is repeatable
         train_dataset.transform.manual_seed(config.get('seed', 0) + rank)
     if rank == 0:
@@ -131,6 +169,13 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     teacher.eval()
     if rank == 0:
         log('num params: {}'.format(utils.compute_n_params(model)))
+    tables = {}                                                                              # eval_feature_cache: one FeatureTable per evaluation dataset
+    if config.get('eval_feature_cache'):
+        from .feature_table import FeatureTable
+        model.eval()                                                                         # (a table is refused in train mode; the loop sets the mode)
+        tables['val'] = FeatureTable.for_dataset(model, val_dataset)
+        if fs_dataset is not None:
+            tables['fs'] = FeatureTable.for_dataset(model, fs_dataset)
 
     oa = config['optimizer_args']
     lr = float(oa['lr']) * (batch_size / 512)                                                # :232
@@ -142,13 +187,13 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     criterion_tl = SoftTargetCrossEntropy()
     max_va = 0.
     timer_used, timer_epoch = utils.Timer(), utils.Timer()
-    trlog = {k: [] for k in ('tl', 'ta', 'vl', 'va')}
+    trlog = {k: [] for k in ['tl', 'ta', 'vl', 'va'] + (['fsa-' + str(n) for n in n_shots] if fs_dataset is not None else [])}
     n_local = batch_size // world
     gen = torch.Generator().manual_seed(config.get('seed', 0))
 
     for epoch in range(1, max_epoch + 1):
         timer_epoch.s()
-        aves = {k: utils.Averager() for k in trlog}
+        aves = {k: utils.Averager() for k in ('tl', 'ta', 'vl', 'va')}
         model.train()
         perm = torch.randperm(len(train_dataset), generator=gen)                            # DataLoader(shuffle=True): same stream on every rank
         n_batches = config.get('train_batches') or (len(train_dataset) // batch_size)
@@ -160,18 +205,38 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
             aves['ta'].add(float(acc))
 
         model.eval()
+        for table in tables.values():
+            table.reset()                                                                    # the training steps above changed the weights
         np.random.seed(0)
-        vl, va = few_shot_eval(model, val_dataset, val_sampler, n_way, n_shot, n_query, ep_per_batch, device)
+        if 'val' in tables:
+            vl, va = few_shot_eval_table(tables['val'], val_sampler, n_way, n_shot, n_query, ep_per_batch)
+        else:
+            vl, va = few_shot_eval(model, val_dataset, val_sampler, n_way, n_shot, n_query, ep_per_batch, device)
         aves['vl'].add(vl)
         aves['va'].add(va)
+        eval_fs = fs_dataset is not None and (epoch % ef_epoch == 0 or epoch == max_epoch)
+        if eval_fs:                                                                          # :343-367: the head of the validation loop, accuracy only
+            for n, sampler in zip(n_shots, fs_samplers):
+                np.random.seed(0)
+                if 'fs' in tables:                                                           # the 5-shot pass finds the 1-shot pass's images encoded
+                    _, fsa = few_shot_eval_table(tables['fs'], sampler, 5, n, 15, 4)
+                else:
+                    _, fsa = few_shot_eval(model, fs_dataset, sampler, 5, n, 15, 4, device)
+                aves['fsa-' + str(n)] = utils.Averager()
+                aves['fsa-' + str(n)].add(fsa)
+        if rank == 0:
+            for nm, table in tables.items():
+                if nm == 'val' or eval_fs:
+                    log('epoch {}, {} feature cache: {} images encoded for {} requested'.format(epoch, nm, table.n_encoded, table.n_requests))
         lr_scheduler.step(epoch - 1)                                                         # :373
         for k, v in aves.items():
             aves[k] = v.item()
             trlog[k].append(aves[k])
         if rank == 0:
-            log('epoch {}, train {:.4f}|{:.4f}, val {:.4f}|{:.4f}, {} {}/{}'.format(
-                epoch, aves['tl'], aves['ta'], aves['vl'], aves['va'], utils.time_str(timer_epoch.t()), utils.time_str(timer_used.t()),
-                utils.time_str(timer_used.t() / epoch * max_epoch)))
+            log('epoch {}, train {:.4f}|{:.4f}, val {:.4f}|{:.4f}{}, {} {}/{}'.format(
+                epoch, aves['tl'], aves['ta'], aves['vl'], aves['va'],
+                ', fs' + ''.join(' {}: {:.4f}'.format(n, aves['fsa-' + str(n)]) for n in n_shots) if eval_fs else '',
+                utils.time_str(timer_epoch.t()), utils.time_str(timer_used.t()), utils.time_str(timer_used.t() / epoch * max_epoch)))
             training = {'epoch': epoch, 'optimizer': config.get('optimizer'), 'optimizer_args': config['optimizer_args'],
                         'optimizer_sd': optimizer.state_dict()}
             margs = dict(config['model_args'])

@@ -10,6 +10,9 @@ multi-GPU = one process per GPU with one gradient all-reduce per step and rank-s
 (RandomResizedCrop + RandomHorizontalFlip, the reference's train_classifier_mini / _tiered configs) runs on the GPU, seeded with `seed` + rank,
 and so does `{augment: randaug}`: the reference's `cropaug` pipeline (timm's create_transform: bicubic crop + flip -> RandAugment -> Normalize
 -> RandomErasing) under our own name, because its RandAugment draw restates timm's published algorithm without timm at hand to pin it.
+`eval_feature_cache: true` (default false): the few-shot evaluation takes its logits from one feature_table.FeatureTable over `fs_dataset` - every
+image the rank's episodes touch is encoded once per evaluation (the 1- and 5-shot pass share one fill), the head reads its rows through the index
+table (fsvit_proto_head_gather); the table is emptied before each evaluation.
 Not restated: tensorboard, dataset visualisation, the `crop` augmentation; the name `cropaug` itself stays refused.
 
   python -m fewshot_vit_amd.train_classifier --config few-shot-vit_amd/configs/train_classifier_synthetic.yaml
@@ -79,6 +82,11 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
     if fs_dataset is not None:                                                               # :109-111
         fs_model = models.make('meta-baseline', encoder=None)
         fs_model.encoder = model.encoder
+    fs_table = None
+    if fs_model is not None and config.get('eval_feature_cache'):                            # one FeatureTable over fs_dataset, shared by both shot settings
+        from .feature_table import FeatureTable
+        fs_model.eval()                                                                      # (a table is refused in train mode; the loop sets the mode)
+        fs_table = FeatureTable.for_dataset(fs_model, fs_dataset)
     if rank == 0:
         log('num params: {}'.format(utils.compute_n_params(model)))
 
@@ -134,10 +142,26 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
                 aves['va'].add(utils.compute_acc(logits, label), len(idx))
         if fs_model is not None and (epoch % ef_epoch == 0 or epoch == max_epoch):
             fs_model.eval()
+            if fs_table is not None:
+                fs_table.reset()                                                             # the training steps above changed the weights
             for i, n_shot in enumerate(n_shots):                                             # :178-191
                 np.random.seed(0)
                 sums = torch.zeros(2, dtype=torch.float64, device=device)
-                for idx in fs_samplers[i]:
+                if fs_table is not None:             # the rank's batches are drawn first, their unseen images encoded once, the head run in one launch
+                    batches = [idx for idx in fs_samplers[i]]
+                    if batches:
+                        temp = float(fs_model.temp.detach()) if isinstance(fs_model.temp, torch.Tensor) else float(fs_model.temp)
+                        logits, _, _ = fs_table.episodes(torch.stack(batches), 5, n_shot, 15, temp, fs_model.method)
+                        fs_table.check()
+                        label = fs.make_nk_label(5, 15, ep_per_batch=4).to(device)
+                        accs = (logits.view(len(batches), -1, 5).argmax(2) == label).double().mean(dim=1).cpu()      # per batch, one copy
+                        total = 0.0
+                        for a in accs.tolist():      # the order of the `sums +=` below
+                            total += a
+                        sums += torch.tensor([total, float(len(batches))], dtype=torch.float64).to(device)
+                    if rank == 0 and i == len(n_shots) - 1:
+                        log('epoch {}, fs feature cache: {} images encoded for {} requested'.format(epoch, fs_table.n_encoded, fs_table.n_requests))
+                for idx in (fs_samplers[i] if fs_table is None else ()):
                     data = torch.stack([fs_dataset[int(j)][0] for j in idx]).to(device)
                     x_shot, x_query = fs.split_shot_query(data, 5, n_shot, 15, ep_per_batch=4)
                     label = fs.make_nk_label(5, 15, ep_per_batch=4).to(device)

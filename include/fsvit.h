@@ -238,6 +238,16 @@ int fsvit_proto_bank_topk(const float* query_dev, const float* proto_dev, const 
  * feat_query_dev [E,Q,D], the first Q / 2 queries positive -> auc_dev [E] = roc_auc_score of the cosine scores against the normalised mean shot
  * = (#{pos > neg} + #{pos == neg} / 2) / (Q / 2)^2; score_dev [E,Q] optional.  Limits: shot >= 1, Q even, 2 <= Q <= 4096.  E == 0 is a no-op. */
 int fsvit_proto_auc(const float* feat_shot_dev, const float* feat_query_dev, int E, int shot, int Q, int D, float* auc_dev, float* score_dev, void* stream);
+/* The same reduction over rows gathered from a feature table (one encoder feature per image, kept across episodes): table_dev [N,D] fp32,
+ * shot_slots_dev [E,shot] the slots of class 0's shots (class 1's shots are never read), query_slots_dev [E,Q] the slots of the queries, the first Q / 2
+ * positive (both int64 when idx_is_int64, else int32) -> auc_dev [E], score_dev [E,Q] (optional).  For the same rows the outputs carry the bits of
+ * fsvit_proto_auc (one device body serves both kernels); they do not depend on E or on the other episodes.
+ * A slot outside [0, N) never becomes an address: the row is read from slot 0, the episode's auc and score row are written as NaN and *invalid_dev (an int
+ * the caller zeroes once) is raised by one per such entry.
+ * Limits and refusals (FSVIT_ERR_ARG, nothing launched, nothing written): those of fsvit_proto_auc - shot >= 1, Q even, 2 <= Q <= 4096, 1 <= D <= 8192 - and
+ * N >= 1, non-NULL table / shot_slots / query_slots / auc / invalid.  E == 0 is a no-op. */
+int fsvit_proto_auc_gather(const float* table_dev, int N, int D, const void* shot_slots_dev, const void* query_slots_dev, int idx_is_int64, int E, int shot,
+                           int Q, float* auc_dev, float* score_dev, int* invalid_dev, void* stream);
 
 /* ---------------------------------------------------------------- operator level (tests, reuse)
  * Implicit-GEMM conv with fused epilogue; see few-shot-vit_amd/csrc/conv_gemm.h for the layout.
