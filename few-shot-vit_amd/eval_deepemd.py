@@ -22,6 +22,7 @@ import yaml
 
 from . import datasets, models, utils
 from .datasets.samplers import CategoriesSampler
+from .episodic import gather_images, launch_groups
 from .utils import few_shot as fs
 
 
@@ -85,38 +86,21 @@ def evaluate(args, log=print, collect=None):
     model.sfc_generator = gen
     sampler = CategoriesSampler(dataset.label, args.test_episode, args.way, args.shot + args.query)
     label = fs.make_nk_label(args.way, args.query).to(device)
-    accs, pending = [], []
+    accs = []
     table = None
     if feature_cache:
         from .feature_table import TokenTable
         table = TokenTable.for_dataset(model, dataset)
 
-    def flush():
-        if not pending:
-            return
-        G = len(pending)
-        idx = torch.stack(list(pending)).view(-1)
-        if table is not None:
-            with torch.no_grad():
-                logits = table.logits(idx, args.way, args.shot, args.query, model)
-            accs.append((logits.argmax(dim=-1) == label).float().mean(dim=1))
-            pending.clear()
-            return
-        if hasattr(dataset, 'gather'):
-            data = dataset.gather(idx)
-        else:
-            data = torch.stack([dataset[int(i)][0] for i in idx]).to(device)
-        x_shot, x_query = fs.split_shot_query(data, args.way, args.shot, args.query, ep_per_batch=G)
+    for group in launch_groups(sampler, args.episodes_per_launch):
+        idx = torch.stack(group).view(-1)
         with torch.no_grad():
-            logits = model(x_shot, x_query)
+            if table is not None:
+                logits = table.logits(idx, args.way, args.shot, args.query, model)
+            else:
+                x_shot, x_query = fs.split_shot_query(gather_images(dataset, idx, device), args.way, args.shot, args.query, ep_per_batch=len(group))
+                logits = model(x_shot, x_query)
         accs.append((logits.argmax(dim=-1) == label).float().mean(dim=1))
-        pending.clear()
-
-    for idx in sampler:
-        pending.append(idx)
-        if len(pending) == args.episodes_per_launch:
-            flush()
-    flush()
     model.check_status()                                     # the one synchronisation: raises if any transportation problem hit a loop bound
     if table is not None:
         table.check()

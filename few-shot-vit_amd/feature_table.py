@@ -16,6 +16,8 @@ at the device; only `episodes` / `logits` and `for_dataset` need the GPU.  The t
 import numpy as np
 import torch
 
+from .episodic import gather_images
+
 
 class _SlotTable:
     """The host bookkeeping both tables share: image -> slot, the counters, the order and the size of the encoder calls.  A subclass keeps the rows
@@ -136,11 +138,7 @@ class FeatureTable(_SlotTable):
         def encode_fn(index):
             if model.training:
                 raise RuntimeError('FeatureTable: the model went back to train mode; reset() the table and fill it in eval mode')
-            if hasattr(dataset, 'gather'):
-                x = dataset.gather(index)
-            else:
-                x = torch.stack([dataset[int(i)][0] for i in index]).to(device, non_blocking=True)
-            return model.encoder.engine().forward(x)          # (re-packed by the encoder when a weight changed)
+            return model.encoder.engine().forward(gather_images(dataset, index, device))        # (re-packed by the encoder when a weight changed)
 
         return cls(encode_fn, len(dataset), engine.out_dim, device, chunk_images or engine.chunk_images)
 
@@ -227,12 +225,8 @@ class TokenTable(_SlotTable):
         def encode_fn(index):
             if model.training:
                 raise RuntimeError('TokenTable: the model went back to train mode; reset() the table and fill it in eval mode')
-            if hasattr(dataset, 'gather'):
-                x = dataset.gather(index)
-            else:
-                x = torch.stack([dataset[int(i)][0] for i in index]).to(device, non_blocking=True)
             with torch.no_grad():
-                return model.encode(x, patches)                # (the engine is re-packed by the encoder when a weight changed)
+                return model.encode(gather_images(dataset, index, device), patches)      # (the engine is re-packed by the encoder when a weight changed)
 
         # model.encode reads the token map of the encoder's last launch: a chunk must fit one launch of the engine
         return cls(encode_fn, len(dataset), device, chunk_images or max(1, engine.chunk_images // per_image))

@@ -3,6 +3,7 @@
 import torch
 import torch.nn as nn
 
+from ..episodic import head_temp
 from .models import make as _make
 from .models import register
 
@@ -97,7 +98,7 @@ class MetaBaseline(nn.Module):
         feat = self._encode_eval(x_query, 'predict')
         if bank.method != self.method:
             raise ValueError(f'predict: the bank was built for {bank.method!r}, the model scores with {self.method!r}')
-        temp = self.temp.detach() if isinstance(self.temp, torch.Tensor) else float(self.temp)
+        temp = head_temp(self, on_device=True)
         return bank.logits(feat, temp)
 
     def predict_topk(self, bank, x_query, k):
@@ -108,10 +109,9 @@ class MetaBaseline(nn.Module):
         feat = self._encode_eval(x_query, 'predict_topk')
         if bank.method != self.method:
             raise ValueError(f'predict_topk: the bank was built for {bank.method!r}, the model scores with {self.method!r}')
-        temp = self.temp.detach() if isinstance(self.temp, torch.Tensor) else float(self.temp)
+        temp = head_temp(self, on_device=True)
         return bank.topk(feat, k, temp)
 
     def _forward_eval(self, x_shot, x_query):
         engine = self.encoder.engine()
-        temp = float(self.temp.detach()) if isinstance(self.temp, torch.Tensor) else float(self.temp)
-        return engine.meta_baseline_forward(x_shot, x_query, temp, self.method)
+        return engine.meta_baseline_forward(x_shot, x_query, head_temp(self), self.method)

@@ -33,6 +33,7 @@ import yaml
 
 from . import datasets, models, parallel, utils
 from .datasets.samplers import CategoriesSampler
+from .episodic import table_episode_logits
 from .models.classifier import FsvitAdamW, SoftTargetCrossEntropy, generate_softlabel
 from .utils import few_shot as fs
 from .utils.schedulers import CosineLRScheduler
@@ -71,17 +72,10 @@ def few_shot_eval(model, dataset, sampler, n_way, n_shot, n_query, ep_per_batch,
 
 
 def table_eval_logits(table, sampler, n_way, n_shot, n_query):
-    """The logits of one whole evaluation from a feature_table.FeatureTable (`eval_feature_cache: true`): the sampler's epoch is drawn first (the draws
-    do not depend on the encoder and the sampler is the loop's only consumer of np.random), the table encodes the images it has not seen, and the head
-    of `few_shot_eval` - cosine prototypes on the pooled feature, temperature 10.0 - runs over all episodes in one launch
+    """The logits of one whole evaluation from a feature_table.FeatureTable (`eval_feature_cache: true`): `episodic.table_episode_logits` with the head
+    of `few_shot_eval` - cosine prototypes on the pooled feature, temperature 10.0
     -> [n_batches, ep_per_batch * n_way * n_query, n_way], batch g being the `logits` of the g-th pass of that loop."""
-    batches = [idx for idx in sampler]
-    if not batches:
-        return torch.zeros(0, 0, n_way, device=table.device)
-    idx = torch.stack(batches)
-    logits, _, _ = table.episodes(idx, n_way, n_shot, n_query, 10.0, 'cos')
-    table.check()
-    return logits.view(idx.shape[0], -1, n_way)
+    return table_episode_logits(table, sampler, n_way, n_shot, n_query, 10.0, 'cos')
 
 
 def few_shot_eval_table(table, sampler, n_way, n_shot, n_query, ep_per_batch):

@@ -19,6 +19,7 @@ import torch
 
 from . import models
 from .datasets.folder_datasets import ImageFolder
+from .episodic import head_temp
 from .models.proto_bank import PrototypeBank
 
 
@@ -118,7 +119,7 @@ def main(argv=None):
         else:
             paths, truth = [os.path.join(args.query, n) for n in _listdir(args.query)], None
         feat = encode_files(model, paths, size, box, device)
-        temp = model.temp.detach() if isinstance(model.temp, torch.Tensor) else float(model.temp)
+        temp = head_temp(model, on_device=True)
         if args.topk is not None:
             top_c, top_l, top_p = (t.cpu() for t in bank.topk(feat, args.topk, temp))
             pred = top_c[:, 0]

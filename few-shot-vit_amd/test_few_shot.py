@@ -11,170 +11,30 @@ MI355X-native differences (results are unchanged by them):
     nn.DataParallel;
   * `--episodes` limits the number of batches (BASELINE config 1 uses 100) without changing the stream.
 
+The protocol itself - seeds, launch loop, statistics exchange, averagers, result dict, command line - is `episodic.evaluate`, shared with
+`eval_cached` and `eval_sauc`; this driver is its dense prototype-head route.
+
   python -m fewshot_vit_amd.test_few_shot --config few-shot-vit_amd/configs/test_synthetic.yaml --shot 5
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m fewshot_vit_amd.test_few_shot ...
 """
-import argparse
-
-import numpy as np
-import torch
-import yaml
-
-from . import datasets, models, parallel, utils
-from .datasets.samplers import CategoriesSampler
-from .utils import few_shot as fs
-
-
-def fix_random_seeds(seed=12345):
-    torch.manual_seed(seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed_all(seed)
-    np.random.seed(seed)
-
-
-def build_model(config, numerics=None):
-    """`load` / `load_encoder` handling of test_few_shot.py:56-63."""
-    if config.get('load') is None:
-        model = models.make('meta-baseline', encoder=None)
-    else:
-        model = models.load(torch.load(config['load'], map_location='cpu'))
-    if config.get('load_encoder') is not None:
-        model.encoder = models.load(torch.load(config['load_encoder'], map_location='cpu')).encoder
-    if config.get('synthetic_checkpoint'):            # offline stand-in: procedural weights + calibrated BN
-        from . import synthetic
-        model = models.make('meta-baseline', encoder=config['synthetic_checkpoint'], encoder_args={})
-        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
-        model.load_state_dict(synthetic.synthetic_checkpoint_sd(shapes, calib=config['synthetic_checkpoint']))
-    if model.encoder is None:
-        raise ValueError('config must provide load, load_encoder or synthetic_checkpoint')
-    if numerics is not None:
-        model.encoder.numerics = numerics
-    return model
-
-
-def default_launch_batches(engine, images_per_batch, img_size, device):
-    """Reference batches (`ep_per_batch` episodes each) per engine launch when the caller does not say: one encoder chunk's worth of images (12 800
-    for the Visformer: the size the persistent kernels are tuned and benched at), bounded so that the launch's fp32 input and its
-    uint8 -> fp32 transform output stay within a quarter of the free device memory."""
-    n_img = engine.chunk_images
-    free = torch.cuda.mem_get_info(device)[0]
-    n_img = min(n_img, max(images_per_batch, int(0.25 * free) // (3 * img_size * img_size * 4)))
-    return max(1, n_img // images_per_batch)
+from . import episodic
+from .episodic import build_model, default_launch_batches, fix_random_seeds      # noqa: F401  (the names this driver has always exported)
 
 
 def evaluate(config, shot=1, test_epochs=1, n_batch=2000, ep_per_batch=1, launch_batches=None, numerics=None,
              rank=0, world=1, device=None, log=print, collect_pred=False):
     """launch_batches: reference batches per engine launch; None (the default, also the CLI's) = `default_launch_batches` - the benched
     configuration (128 five-shot episodes of 100 images)."""
-    import time
-    t_call = time.perf_counter()
-    fix_random_seeds(12345)
-    dataset = datasets.make(config['dataset'], **config['dataset_args'])
-    t_dataset = time.perf_counter()
-    n_way, n_query = 5, 15
-    sampler = CategoriesSampler(dataset.label, n_batch, n_way, shot + n_query, ep_per_batch=ep_per_batch,
-                                rank=rank, world_size=world, shard=parallel.sampler_shard(world))
-    device = device or torch.device('cuda', torch.cuda.current_device())
-    model = build_model(config, numerics).to(device).eval()
-    if rank == 0:
-        log('num params: {}'.format(utils.compute_n_params(model)))
-    t_model = time.perf_counter()
-    engine = model.encoder.engine()
-    temp = float(model.temp.detach()) if isinstance(model.temp, torch.Tensor) else float(model.temp)
-    if launch_batches is None:
-        launch_batches = default_launch_batches(engine, ep_per_batch * n_way * (shot + n_query), engine.img_size, device)
-
-    np.random.seed(12345)                                  # fixes the episode stream (test_few_shot.py:76)
-    out = None
-    torch.cuda.synchronize(device)
-    t_loop = time.perf_counter()
-    # the reference keeps ONE pair of averagers and ONE va_lst across epochs (test_few_shot.py:73-74 sit outside the epoch loop), so the
-    # accuracy / CI printed for epoch e covers every batch of epochs 1..e
-    aves_va, aves_vl, va_lst = utils.Averager(), utils.Averager(), []
-    for epoch in range(1, test_epochs + 1):
-        accs, losses, last_label = [], [], None
-        pending, preds = [], []
-
-        def flush():
-            if not pending:
-                return
-            G = len(pending)
-            if hasattr(dataset, 'gather'):                  # device-resident dataset: gather + transform on the GPU
-                # the index list is permuted on the host so that the transform writes all shot images, then all query images: x_shot / x_query
-                # are views of its output (fs.split_shot_query on the class-major batch would copy 1 GB per 128-episode launch)
-                idx = torch.stack(list(pending)).view(G * ep_per_batch, n_way, shot + n_query)
-                n_s = G * ep_per_batch * n_way * shot
-                data = dataset.gather(torch.cat([idx[:, :, :shot].reshape(-1), idx[:, :, shot:].reshape(-1)]))
-                x_shot = data[:n_s].view(G * ep_per_batch, n_way, shot, *data.shape[1:])
-                x_query = data[n_s:].view(G * ep_per_batch, n_way * n_query, *data.shape[1:])
-            else:
-                data = torch.stack([torch.stack([dataset[int(i)][0] for i in idx]) for idx in pending])   # [G, E*way*(S+Q), 3,H,W]
-                data = data.view(G * ep_per_batch * n_way * (shot + n_query), *data.shape[2:]).to(device, non_blocking=True)
-                x_shot, x_query = fs.split_shot_query(data, n_way, shot, n_query, ep_per_batch=G * ep_per_batch)
-            logits, acc, loss = engine.meta_baseline_forward(x_shot, x_query, temp, model.method, want_stats=True)
-            if collect_pred:                                         # per-query arg-max of every episode (agreement tests between numerics modes)
-                preds.append(logits.argmax(-1).to(torch.uint8).cpu())
-            accs.append(acc.view(G, ep_per_batch).mean(dim=1))       # per reference batch
-            losses.append(loss.view(G, ep_per_batch).mean(dim=1))
-            pending.clear()
-
-        # the first launch is small so that the GPU starts while the host is still drawing the stream; from then on the sampler runs under the
-        # previous launch.  (Round 5: with the native sampler a full launch of 128 episodes is 6 ms of host time, so one 32-episode step replaces the
-        # 8 / 16 / 32 / 64 ramp of the 100-us-per-episode numpy sampler - small launches run the persistent kernels at half their efficiency.)
-        ramp = [n for n in (32,) if n < launch_batches]
-        for idx in sampler:
-            pending.append(idx)
-            last_label = dataset.label[int(idx[-1])]
-            if len(pending) == (ramp[0] if ramp else launch_batches):
-                flush()
-                if ramp:
-                    ramp.pop(0)
-        flush()
-        mine = torch.stack([torch.cat(accs), torch.cat(losses)], dim=1).double() if accs else torch.zeros(0, 2, dtype=torch.float64, device=device)
-        allv = parallel.gather_in_stream_order(mine, n_batch, rank, world).cpu().numpy()     # the one exchange
-        va_lst.extend(allv[:, 0].tolist())
-        per_batch_items = ep_per_batch * n_way * (shot + n_query)
-        for a, l in allv:
-            aves_va.add(a, per_batch_items)
-            aves_vl.add(l, per_batch_items)
-        out = dict(acc=aves_va.item(), ci=float(utils.mean_confidence_interval(va_lst)) if len(va_lst) > 1 else float('nan'),
-                   loss=aves_vl.item(), n=len(va_lst), last_label=last_label, va_lst=list(va_lst))
-        if collect_pred:
-            out['pred'] = torch.cat(preds) if preds else torch.zeros(0, n_way * n_query, dtype=torch.uint8)
-        # sampler -> gather + transform -> encoder + head -> statistics exchange, everything after model / dataset construction (the gather above synchronised)
-        out['loop_seconds'] = time.perf_counter() - t_loop
-        out['launch_batches'] = launch_batches
-        out['phase_seconds'] = {'dataset': t_dataset - t_call, 'model': t_model - t_dataset, 'engine': t_loop - t_model, 'loop': out['loop_seconds']}
-        if rank == 0:
-            log('test epoch {}: acc={:.2f} +- {:.2f} (%), loss={:.4f} (@{})'.format(
-                epoch, out['acc'] * 100, out['ci'] * 100, out['loss'], last_label))
+    out = episodic.evaluate(config, 5, episodic.proto_dense, episodic.reduce_batches, shot=shot, test_epochs=test_epochs, n_batch=n_batch,
+                            ep_per_batch=ep_per_batch, launch_batches=launch_batches, numerics=numerics, rank=rank, world=world, device=device, log=log,
+                            collect_pred=collect_pred)
+    if out is not None:                                     # the reference driver's dict carries no image counters (eval_cached's does)
+        del out['images_requested'], out['images_encoded']
     return out
 
 
 def main():
-    parser = argparse.ArgumentParser()
-    parser.add_argument('--config', default='./configs/test_few_shot.yaml')
-    parser.add_argument('--shot', type=int, default=1)
-    parser.add_argument('--test-epochs', type=int, default=1)
-    parser.add_argument('--gpu', default=None, help='kept for CLI compatibility; use torchrun for multi-GPU')
-    parser.add_argument('--episodes', type=int, default=2000, help='number of batches (reference: 2000)')
-    parser.add_argument('--ep-per-batch', type=int, default=1)
-    parser.add_argument('--launch-batches', type=int, default=None, help='reference batches per engine launch (default: one encoder chunk, 12 800 images = 128 five-shot episodes)')
-    parser.add_argument('--numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'],
-                        help="default: FSVIT_NUMERICS or 'bf16' (throughput mode: logits within ~5e-2 of the reference's, 98.8 %% arg-max agreement). "
-                             "'f16' runs at 0.93 x the rate with 7 x tighter logits (~8e-3, 99.85 %%) when the checkpoint's weights fit the fp16 range; "
-                             "'bf16x2' / 'f16x2' meet the reference's logits within 1e-3 at 0.24 x the rate; 'parity' = exact fp32 (0.12 x)")
-    args = parser.parse_args()
-    config = yaml.load(open(args.config, 'r'), Loader=yaml.FullLoader)
-    if args.gpu is not None and ',' not in args.gpu:
-        utils.set_gpu(args.gpu)
-    rank, world, local = parallel.init_from_env()
-    torch.cuda.set_device(local)
-    evaluate(config, shot=args.shot, test_epochs=args.test_epochs, n_batch=args.episodes, ep_per_batch=args.ep_per_batch,
-             launch_batches=args.launch_batches, numerics=args.numerics, rank=rank, world=world,
-             device=torch.device('cuda', local), log=utils.log)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    episodic.run_cli(evaluate, episodic.make_parser())
 
 
 if __name__ == '__main__':

@@ -27,16 +27,14 @@ import yaml
 
 from . import datasets, models, parallel, utils
 from .datasets.samplers import CategoriesSampler
+from .episodic import gather_images, head_temp, table_episode_logits
 from .models.classifier import FsvitAdamW
 from .utils import few_shot as fs
 from .utils.schedulers import CosineLRScheduler
 
 
 def _gather(dataset, idx, device):
-    if hasattr(dataset, 'gather'):                                                           # device-resident datasets: one launch per batch
-        return dataset.gather(idx).to(device, non_blocking=True), torch.tensor([int(dataset.label[int(i)]) for i in idx], device=device)
-    items = [dataset[int(i)] for i in idx]
-    return torch.stack([it[0] for it in items]).to(device, non_blocking=True), torch.tensor([int(it[-1]) for it in items], device=device)
+    return gather_images(dataset, idx, device), torch.tensor([int(dataset.label[int(i)]) for i in idx], device=device)
 
 
 def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, save_root='./save'):
@@ -148,17 +146,14 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
                 np.random.seed(0)
                 sums = torch.zeros(2, dtype=torch.float64, device=device)
                 if fs_table is not None:             # the rank's batches are drawn first, their unseen images encoded once, the head run in one launch
-                    batches = [idx for idx in fs_samplers[i]]
-                    if batches:
-                        temp = float(fs_model.temp.detach()) if isinstance(fs_model.temp, torch.Tensor) else float(fs_model.temp)
-                        logits, _, _ = fs_table.episodes(torch.stack(batches), 5, n_shot, 15, temp, fs_model.method)
-                        fs_table.check()
+                    logits = table_episode_logits(fs_table, fs_samplers[i], 5, n_shot, 15, head_temp(fs_model), fs_model.method)
+                    if logits.shape[0]:
                         label = fs.make_nk_label(5, 15, ep_per_batch=4).to(device)
-                        accs = (logits.view(len(batches), -1, 5).argmax(2) == label).double().mean(dim=1).cpu()      # per batch, one copy
+                        accs = (logits.argmax(2) == label).double().mean(dim=1).cpu()                               # per batch, one copy
                         total = 0.0
                         for a in accs.tolist():      # the order of the `sums +=` below
                             total += a
-                        sums += torch.tensor([total, float(len(batches))], dtype=torch.float64).to(device)
+                        sums += torch.tensor([total, float(logits.shape[0])], dtype=torch.float64).to(device)
                     if rank == 0 and i == len(n_shots) - 1:
                         log('epoch {}, fs feature cache: {} images encoded for {} requested'.format(epoch, fs_table.n_encoded, fs_table.n_requests))
                 for idx in (fs_samplers[i] if fs_table is None else ()):

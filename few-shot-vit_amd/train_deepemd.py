@@ -36,6 +36,7 @@ import yaml
 
 from . import datasets, models, utils
 from .datasets.samplers import CategoriesSampler
+from .episodic import gather_images, launch_groups
 from .eval_deepemd import parse_patch_list, patch_dataset_args
 from .models.deepemd import load_encoder_params
 from .utils import few_shot as fs
@@ -81,12 +82,6 @@ def make_optimizer(model, args):
     return optimizer, torch.optim.lr_scheduler.StepLR(optimizer, step_size=args.step_size, gamma=args.gamma)
 
 
-def _gather(dataset, idx, device):
-    if hasattr(dataset, 'gather'):
-        return dataset.gather(idx)
-    return torch.stack([dataset[int(i)][0] for i in idx]).to(device)
-
-
 def _seed_dataset(dataset, seed):
     transform = getattr(dataset, 'transform', None)
     if hasattr(transform, 'manual_seed'):
@@ -121,7 +116,7 @@ def train_epoch(model, optimizer, dataset, args, epoch, device):
     zeroed = torch.zeros((), dtype=torch.int64, device=device)
     n = 0
     for n, idx in enumerate(sampler, 1):
-        x_shot, x_query = fs.split_shot_query(_gather(dataset, idx, device), args.way, args.shot, args.query)
+        x_shot, x_query = fs.split_shot_query(gather_images(dataset, idx, device), args.way, args.shot, args.query)
         loss, acc = task_backward(model, x_shot, x_query, label, args.bs)
         sums += torch.stack([loss, acc]).double()
         zeroed += guard_and_step(model, optimizer, n % args.bs == 0)
@@ -142,29 +137,19 @@ def evaluate(model, dataset, args, n_episode, device, seed=None, table=None):
         _seed_dataset(dataset, seed)
         model.sfc_generator = torch.Generator().manual_seed(seed)
     sampler = CategoriesSampler(dataset.label, n_episode, args.way, args.shot + args.query)
-    losses, accs, pending = [], [], []
-
-    def flush():
-        if not pending:
-            return
-        G = len(pending)
-        idx = torch.stack(list(pending)).view(-1)
+    losses, accs = [], []
+    for group in launch_groups(sampler, args.episodes_per_launch):
+        G = len(group)
+        idx = torch.stack(group).view(-1)
         label = fs.make_nk_label(args.way, args.query, ep_per_batch=G).to(device)
         with torch.no_grad():
             if table is not None:
                 logits = table.logits(idx, args.way, args.shot, args.query, model).view(-1, args.way)
             else:
-                x_shot, x_query = fs.split_shot_query(_gather(dataset, idx, device), args.way, args.shot, args.query, ep_per_batch=G)
+                x_shot, x_query = fs.split_shot_query(gather_images(dataset, idx, device), args.way, args.shot, args.query, ep_per_batch=G)
                 logits = model(x_shot, x_query).view(-1, args.way)
         losses.append(F.cross_entropy(logits, label, reduction='none').view(G, -1).mean(dim=1))
         accs.append((logits.argmax(dim=1) == label).float().view(G, -1).mean(dim=1))
-        pending.clear()
-
-    for idx in sampler:
-        pending.append(idx)
-        if len(pending) == args.episodes_per_launch:
-            flush()
-    flush()
     model.check_status()
     if table is not None:
         table.check()

@@ -30,20 +30,8 @@ import yaml
 
 from . import datasets, models, parallel, utils
 from .datasets.samplers import CategoriesSampler
+from .episodic import fix_random_seeds, gather_images, head_temp
 from .utils import few_shot as fs
-
-
-def fix_random_seeds(seed=12345):
-    torch.manual_seed(seed)
-    if torch.cuda.is_available():
-        torch.cuda.manual_seed_all(seed)
-    np.random.seed(seed)
-
-
-def _batch(dataset, idx, device):
-    if hasattr(dataset, 'gather'):                       # device-resident dataset: gather + transform on the GPU
-        return dataset.gather(idx)
-    return torch.stack([dataset[int(i)][0] for i in idx]).to(device, non_blocking=True)
 
 
 def build_model(config):
@@ -149,7 +137,7 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
         np.random.seed(epoch)
         for idx in train_sampler:                               # every rank replays the same stream ...
             idx = parallel.shard_episode_axis(idx, ep_per_batch, rank, world)                            # ... and keeps its episodes
-            data = _batch(train_dataset, idx, device)
+            data = gather_images(train_dataset, idx, device)
             x_shot, x_query = fs.split_shot_query(data, n_train_way, n_train_shot, n_train_query, ep_per_batch=ep_local)
             label = fs.make_nk_label(n_train_way, n_train_query, ep_per_batch=ep_local).to(device)
             loss, acc = train_step(model, optimizer, x_shot, x_query, label, n_train_way, world, bucket)
@@ -167,7 +155,7 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
                     tables[nm] = FeatureTable.for_dataset(model, ds)
                 table = tables[nm]
                 table.reset()                                   # the training steps above changed the weights
-                temp = model.temp.detach() if isinstance(model.temp, torch.Tensor) else float(model.temp)
+                temp = head_temp(model, on_device=True)
             np.random.seed(0)
             sums = torch.zeros(3, dtype=torch.float64, device=device)     # sum loss, sum acc, n batches
             for idx in sampler:
@@ -176,7 +164,7 @@ def main(config, name=None, tag=None, rank=0, world=1, device=None, log=None, sa
                     if table is not None:
                         logits = table.episodes(idx, n_way, n_shot, n_query, temp, model.method)[0].view(-1, n_way)
                     else:
-                        data = _batch(ds, idx, device)
+                        data = gather_images(ds, idx, device)
                         x_shot, x_query = fs.split_shot_query(data, n_way, n_shot, n_query, ep_per_batch=4)
                         logits = model(x_shot, x_query).view(-1, n_way)
                     sums += torch.stack([F.cross_entropy(logits, label).double(), (logits.argmax(1) == label).double().mean(),

@@ -62,6 +62,26 @@ def test_eval_sauc_with_the_cache_reports_the_same_numbers(tmp_path, shot, ep_pe
     print(f'sauc shot {shot}: {b["images_encoded"]} images encoded for {b["images_requested"]} requested, auc {b["va_lst"]}')
 
 
+def test_eval_sauc_routes_agree_through_the_ramp_and_two_epochs():
+    """Both AUC routes of episodic.evaluate on the 8-class x 24-image split behind visformer_micro_80 in bf16: 40 batches at launch_batches=36 are a
+    32-batch first launch and one of 8, twice; the averagers and va_lst run on across the epochs.  The table encodes no image twice (<= 192); the dense
+    route encodes per episode the shot of class 0 and the 2 x 15 queries."""
+    from fewshot_vit_amd import eval_sauc
+    config = {'dataset': 'synthetic-images', 'dataset_args': dict(split='test', n_classes=8, n_per_class=24, seed=3), 'synthetic_checkpoint': 'visformer_micro_80'}
+    logs_a, logs_b = [], []
+    kw = dict(shot=1, n_batch=40, launch_batches=36, test_epochs=2, numerics='bf16', sauc=True)
+    a = eval_sauc.evaluate(config, feature_cache=False, log=logs_a.append, **kw)
+    b = eval_sauc.evaluate(config, feature_cache=True, log=logs_b.append, **kw)
+    print(f'sauc ramp: acc {a["acc"]} +- {a["ci"]}, encoded {b["images_encoded"]} of {b["images_requested"]} requested, dense {a["images_requested"]}')
+    assert set(a) == set(b)
+    for k in ('va_lst', 'acc', 'ci', 'loss', 'n', 'last_label', 'launch_batches'):
+        assert a[k] == b[k], k
+    assert logs_a == logs_b and len(logs_a) == 3                           # num params, then one line per epoch, the same text
+    assert len(a['va_lst']) == 80 and np.isfinite(a['va_lst']).all()
+    assert b['images_encoded'] <= 192
+    assert a['images_requested'] == 2 * 40 * (1 + 2 * 15)
+
+
 def test_eval_sauc_without_sauc_takes_the_cached_episode_driver(tmp_path):
     from fewshot_vit_amd import eval_cached, eval_sauc
     config = _sauc_config(tmp_path)

@@ -166,8 +166,8 @@ def test_evaluate_with_the_cache_reports_the_same_numbers(tmp_path, encoder, sho
 
 
 def test_cached_driver_follows_test_few_shot_through_the_ramp_and_two_epochs(tmp_path):
-    """eval_cached.evaluate carries its own copy of test_few_shot.evaluate's loop: the 32-batch first launch, the launch grouping after it, the averagers
-    and va_lst kept across epochs and the result dict are held to test_few_shot.evaluate itself, value for value."""
+    """eval_cached.evaluate runs episodic.evaluate's loop with the table route: the 32-batch first launch, the launch grouping after it, the averagers
+    and va_lst kept across epochs and the result dict are held to test_few_shot.evaluate (the dense route), value for value."""
     from fewshot_vit_amd import eval_cached, test_few_shot
     config = _eval_config('visformer_micro_80', tmp_path)
     logs_a, logs_b = [], []
