@@ -213,6 +213,9 @@ SIGNATURES = {
     'fsvit_op_emd_solve_counts': (_i, [_fp, _fp, _fp, _i, _i, _fp, _vp, _vp, _vp]),
     'fsvit_emd_sfc_workspace_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
     'fsvit_emd_sfc_steps': (_i, [_fp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _fp, _fp, _vp, _vp, _sz, _vp]),
+    'fsvit_emd_bank_accumulate': (_i, [_fp, _vp, _i, _i, _i, _i, _i, _fp, _vp, _vp, _vp]),
+    'fsvit_emd_bank_finalize': (_i, [_fp, _vp, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _vp]),
+    'fsvit_emd_rerank': (_i, [_fp, _fp, _fp, _i, _fp, _fp, _fp, _vp, _i, _vp, _i, _i, _i, _f, _i, _fp, _vp, _fp, _fp, _vp, _vp, _vp]),
     'fsvit_sampler_draw': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 

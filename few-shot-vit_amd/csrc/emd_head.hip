@@ -17,6 +17,9 @@
 //  * emd_sfc_kernel: the 5-shot SFC fine-tune (get_sfc, :83-107) as one on-device loop, one workgroup per episode: per mini-batch update the SFC's
 //    nodes, the problems of the mini-batch (emd_pair_wave, the body emd_pair_kernel runs too), dlogits, the backward onto the SFC and the momentum
 //    update, separated by block barriers that every wave reaches.  Opt-in (DeepEMD(sfc_fused=True)); the default route calls the kernels above.
+//  * emd_bank_accumulate_kernel / emd_bank_finalize_kernel / emd_rerank_kernel: a labelled support set (models/emd_bank.TokenBank).  Per class the sum
+//    of its support maps and their count; from them the class map, its prepared nodes (emd_prep_token / emd_prep_pooled) and a unit-length token mean for
+//    a cosine shortlist; then per query only the shortlisted (query, class) problems (emd_pair_wave), ranked in the launch that solves them.
 #include "fsvit_common.h"
 #include "kernels.h"
 #include "../../include/fsvit.h"
@@ -660,6 +663,169 @@ int launch_emd_head_gather(const float* tok, const float* xhat, const float* poo
                                                      status, invalid, s);
 }
 
+// ---- a labelled support set for the head: a bank of class token maps (models/emd_bank.TokenBank), and the exact re-rank of a shortlist of classes.
+// Accumulate: proto_bank_accumulate_kernel's scheme over rows of N * C floats (its entry stops at D = 8192): one workgroup per (class, 256-wide slice)
+// scans the label array, so a class's rows are added in ascending support index on top of the stored sum whatever the launch geometry - no
+// floating-point atomics, and two calls over a split give the bits of one.
+constexpr int EMD_BANK_SLICE = 256;
+
+template <typename L>
+__global__ __launch_bounds__(EMD_BANK_SLICE) void emd_bank_accumulate_kernel(const float* __restrict__ tok, const L* __restrict__ label, int S, int n_classes,
+                                                                             int D, float* __restrict__ sum, int* __restrict__ count,
+                                                                             int* __restrict__ invalid) {
+  __shared__ int n_class, n_bad;
+  const int c = blockIdx.x, t = threadIdx.x, d = blockIdx.y * EMD_BANK_SLICE + t;
+  if (blockIdx.y == 0) {           // the class's count (and, in the workgroup of class 0, the labels no class takes): integer sums, any order
+    if (t == 0) { n_class = 0; n_bad = 0; }
+    __syncthreads();
+    int mine = 0, bad = 0;
+    for (int s = t; s < S; s += EMD_BANK_SLICE) {
+      const L l = label[s];
+      mine += (l == (L)c);
+      bad += (l < (L)0 || l >= (L)n_classes);
+    }
+    if (mine) atomicAdd(&n_class, mine);
+    if (bad && c == 0) atomicAdd(&n_bad, bad);
+    __syncthreads();
+    if (t == 0) {
+      count[c] += n_class;
+      if (c == 0 && n_bad) atomicAdd(invalid, n_bad);
+    }
+  }
+  if (d >= D) return;              // (after the barriers above: uniform over the workgroups with blockIdx.y == 0, which all reach them)
+  float acc = sum[(size_t)c * D + d];
+  for (int s = 0; s < S; ++s)
+    if (label[s] == (L)c) acc += tok[(size_t)s * D + d];      // a label outside [0, n_classes) equals no c: its row is never read
+  sum[(size_t)c * D + d] = acc;
+}
+
+int launch_emd_bank_accumulate(const float* tok, const void* label, int label_is_int64, int S, int n_classes, int N, int C, float* sum, int* count,
+                               int* invalid, hipStream_t s) {
+  if (S <= 0) return 0;
+  const int D = N * C;
+  const dim3 grid(n_classes, (D + EMD_BANK_SLICE - 1) / EMD_BANK_SLICE);
+  return label_is_int64 ? launch(emd_bank_accumulate_kernel<long long>, grid, dim3(EMD_BANK_SLICE), 0, s, tok, (const long long*)label, S, n_classes, D, sum,
+                                 count, invalid)
+                        : launch(emd_bank_accumulate_kernel<int>, grid, dim3(EMD_BANK_SLICE), 0, s, tok, (const int*)label, S, n_classes, D, sum, count, invalid);
+}
+
+// Finalize, one workgroup per class: tok = sum / count, then what emd_prep_kernel makes of that map (emd_prep_token / emd_prep_pooled: the same
+// bodies on the same values, so the bits of fsvit_emd_table_prep), and proto = pooled / max(|pooled|, 1e-12), the class's row for the cosine shortlist.
+// A class without examples: empty = 1 and zero rows everywhere.  (tok, xhat and pooled carry no __restrict__: written and read back in this launch.)
+__global__ __launch_bounds__(256) void emd_bank_finalize_kernel(const float* __restrict__ sum, const int* __restrict__ count, int N, int C, float* tok_all,
+                                                                float* xhat_all, float* pooled_all, float* __restrict__ proto_all,
+                                                                int* __restrict__ empty) {
+  const int cls = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int NC = N * C;
+  const int n = count[cls];
+  const float* srow = sum + (size_t)cls * NC;
+  float* tok = tok_all + (size_t)cls * NC;
+  float* xhat = xhat_all + (size_t)cls * NC;
+  float* pooled = pooled_all + (size_t)cls * C;
+  float* proto = proto_all + (size_t)cls * C;
+  if (tid == 0) empty[cls] = n <= 0;
+  if (n <= 0) {                                                  // uniform over the workgroup, before its first barrier
+    for (int i = tid; i < NC; i += 256) { tok[i] = 0.f; xhat[i] = 0.f; }
+    for (int k = tid; k < C; k += 256) { pooled[k] = 0.f; proto[k] = 0.f; }
+    return;
+  }
+  const float fn = (float)n;
+  for (int t = wave; t < N; t += 4) {
+    for (int k = lane; k < C; k += 64) tok[t * C + k] = srow[t * C + k] / fn;      // emd_prep_token's lane pattern: a lane reads back its own stores
+    emd_prep_token(tok + t * C, xhat + t * C, C, lane);
+  }
+  __syncthreads();
+  for (int k = tid; k < C; k += 256) pooled[k] = emd_prep_pooled(tok, N, C, k);
+  __syncthreads();
+  float ss = 0.f;                                                // every wave forms the same |pooled|^2 in the same order
+  for (int k = lane; k < C; k += 64) ss += pooled[k] * pooled[k];
+  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+  for (int k = tid; k < C; k += 256) proto[k] = pooled[k] * inv;
+}
+
+int launch_emd_bank_finalize(const float* sum, const int* count, int n_classes, int N, int C, float* tok, float* xhat, float* pooled, float* proto, int* empty,
+                             hipStream_t s) {
+  return launch(emd_bank_finalize_kernel, dim3(n_classes), dim3(256), 0, s, sum, count, N, C, tok, xhat, pooled, proto, empty);
+}
+
+// Re-rank: query q against the classes cand[q][0 .. M) of the bank, one workgroup per query.  Wave w solves candidates w, w + EMD_WAVES, ..
+// (emd_pair_wave: the problems, and the bits, of emd_gather_kernel on the same prepared rows) and leaves each logit in LDS; after the one block barrier
+// wave 0 ranks the M values, one lane per candidate.  Every wave reaches that barrier: no wave returns early and the barrier sits under no condition
+// (the discipline of emd_sfc_kernel; emd_gather_kernel, which has no barrier, returns early for a bad slot - this kernel must not).
+// A candidate: -1 is an empty slot; an entry < -1 or >= n_classes raises *invalid by one and is an empty slot from then on - it never becomes an address;
+// an empty slot and a class flagged `empty` score -inf and are not solved.  Order of the ranked list: the larger logit, then the lower class, then the
+// lower candidate position, an empty slot (class -1: it holds nothing) after every class - the tail convention of proto_bank_topk, whose lists are the
+// usual candidates.  prob = softmax over the finite entries of the row's M logits.
+__device__ __forceinline__ bool emd_rank_before(float v, unsigned c, int i, float w, unsigned d, int j) {      // class -1 compares as 0xffffffff
+  return v > w || (v == w && (c < d || (c == d && i < j)));
+}
+
+__global__ __launch_bounds__(64 * EMD_WAVES) void emd_rerank_kernel(const float* __restrict__ qtok, const float* __restrict__ qxhat,
+                                                                    const float* __restrict__ qpooled, const float* __restrict__ btok,
+                                                                    const float* __restrict__ bxhat, const float* __restrict__ bpooled,
+                                                                    const int* __restrict__ empty, int n_classes, const int* __restrict__ cand, int M, int K,
+                                                                    int N, int C, float scale, float* __restrict__ logits, int* __restrict__ classes,
+                                                                    float* __restrict__ values, float* __restrict__ prob, int* __restrict__ status_count,
+                                                                    int* __restrict__ invalid) {
+  __shared__ float lds[EMD_WAVES][2][EMD_TILE];
+  __shared__ float lg[32];                                       // the row's logits in candidate order (M <= 32)
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const size_t q = blockIdx.x, NC = (size_t)N * C;
+  const int* cq = cand + q * M;
+  float* c = lds[wave][0];
+  float* F = lds[wave][1];
+  for (int m = wave; m < M; m += EMD_WAVES) {
+    int cl = __builtin_amdgcn_readfirstlane(cq[m]);
+    if (cl < -1 || cl >= n_classes) {
+      if (lane == 0) atomicAdd(invalid, 1);
+      cl = -1;
+    }
+    float v = -INFINITY;
+    if (cl >= 0 && !__builtin_amdgcn_readfirstlane(empty[cl])) {                // wave-uniform: all 64 lanes enter the solver together
+      int st;
+      const float s = emd_pair_wave(qtok + q * NC, btok + (size_t)cl * NC, qxhat + q * NC, bxhat + (size_t)cl * NC, qpooled + q * C, bpooled + (size_t)cl * C,
+                                    N, C, c, F, lane, st);
+      v = s * scale;
+      if (st && lane == 0) atomicAdd(status_count, 1);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");      // the tiles are reused by this wave's next problem
+    }
+    if (lane == 0) lg[m] = v;
+  }
+  __syncthreads();
+  if (wave == 0) {                                                // (no barrier below this line)
+    const bool on = lane < M;
+    const int raw = on ? cq[lane] : -1;
+    const int cls = (raw < -1 || raw >= n_classes) ? -1 : raw;
+    const float v = on ? lg[lane] : -INFINITY;
+    int rank = 0;
+    for (int i = 0; i < M; ++i) {                                 // M uniform steps: how many candidates come before this lane's
+      const float vi = emd_lane_f(v, i);
+      const int ci = emd_lane_i(cls, i);
+      rank += emd_rank_before(vi, (unsigned)ci, i, v, (unsigned)cls, lane) ? 1 : 0;
+    }
+    const float mx = wave_max(v);                                 // lanes >= M hold -inf
+    const float e = (v > -INFINITY) ? expf(v - mx) : 0.f;         // (mx is finite wherever v is)
+    const float den = wave_sum(e);
+    const float p = e > 0.f ? e / den : 0.f;
+    if (on) {
+      if (logits) logits[q * M + lane] = v;
+      if (rank < K) {
+        classes[q * K + rank] = cls;
+        values[q * K + rank] = v;
+        prob[q * K + rank] = p;
+      }
+    }
+  }
+}
+
+int launch_emd_rerank(const float* qtok, const float* qxhat, const float* qpooled, int Q, const float* btok, const float* bxhat, const float* bpooled,
+                      const int* empty, int n_classes, const int* cand, int M, int N, int C, float temperature, int K, float* logits, int* classes,
+                      float* values, float* prob, int* status_count, int* invalid, hipStream_t s) {
+  if (Q <= 0) return 0;
+  return launch(emd_rerank_kernel, dim3(Q), dim3(64 * EMD_WAVES), 0, s, qtok, qxhat, qpooled, btok, bxhat, bpooled, empty, n_classes, cand, M, K, N, C,
+                temperature / (float)N, logits, classes, values, prob, status_count, invalid);
+}
+
 int launch_emd_head_backward(const float* shot_tok, const float* query_tok, const float* dlogits, const float* flow, int E, int P, int Q, int N, int C,
                              float temperature, float* d_shot, float* d_query, void* ws, hipStream_t s) {
   if (E <= 0 || P <= 0 || Q <= 0) return 0;
@@ -748,6 +914,52 @@ extern "C" int fsvit_emd_head_gather(const float* tok, const float* xhat, const 
   int rc = fsvit::launch_emd_head_gather(tok, xhat, pooled, n_slots, query_slots, proto_slots_or_null, slots_are_int64, proto_tok_or_null, E, P, Q, N, C,
                                          temperature, logits, status, invalid, workspace_or_null, (hipStream_t)stream);
   if (rc) return fsvit_set_error(rc, "fsvit_emd_head_gather: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+// ---- token-map bank and shortlist re-rank: limits as fsvit.h states them
+static const char* emd_bank_shape_bad(int n_classes, int N, int C) {
+  if (n_classes < 1 || n_classes > 65536) return "n_classes must be 1 .. 65536";
+  if (N < 1 || N > 32) return "N must be 1 .. 32 (one lane per node)";
+  if (C < 64 || C % 64 || C > 16384) return "C must be a positive multiple of 64, at most 16384";
+  return nullptr;
+}
+
+extern "C" int fsvit_emd_bank_accumulate(const float* tok, const void* labels, int label_is_int64, int S, int n_classes, int N, int C, float* sum, int* count,
+                                         int* invalid, void* stream) {
+  if (S < 0 || S > (1 << 24)) EMD_FAIL("fsvit_emd_bank_accumulate: S = %d is outside [0, 2^24]", S);
+  if (const char* why = emd_bank_shape_bad(n_classes, N, C)) EMD_FAIL("fsvit_emd_bank_accumulate: n_classes = %d, N = %d, C = %d: %s", n_classes, N, C, why);
+  if (S == 0) return 0;                                          // nothing is touched (an empty array has no address to hand over)
+  if (!tok || !labels || !sum || !count || !invalid) EMD_FAIL("fsvit_emd_bank_accumulate: null argument");
+  int rc = fsvit::launch_emd_bank_accumulate(tok, labels, label_is_int64, S, n_classes, N, C, sum, count, invalid, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_bank_accumulate: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int fsvit_emd_bank_finalize(const float* sum, const int* count, int n_classes, int N, int C, float* tok, float* xhat, float* pooled, float* proto,
+                                       int* empty, void* stream) {
+  if (!sum || !count || !tok || !xhat || !pooled || !proto || !empty) EMD_FAIL("fsvit_emd_bank_finalize: null argument");
+  if (const char* why = emd_bank_shape_bad(n_classes, N, C)) EMD_FAIL("fsvit_emd_bank_finalize: n_classes = %d, N = %d, C = %d: %s", n_classes, N, C, why);
+  int rc = fsvit::launch_emd_bank_finalize(sum, count, n_classes, N, C, tok, xhat, pooled, proto, empty, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_bank_finalize: %s", hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int fsvit_emd_rerank(const float* query_tok, const float* query_xhat, const float* query_pooled, int Q, const float* bank_tok,
+                                const float* bank_xhat, const float* bank_pooled, const int* bank_empty, int n_classes, const int* cand, int M, int N, int C,
+                                float temperature, int K, float* logits_or_null, int* classes, float* values, float* prob, int* status_count, int* invalid,
+                                void* stream) {
+  if (Q < 0 || Q > (1 << 24)) EMD_FAIL("fsvit_emd_rerank: Q = %d is outside [0, 2^24]", Q);
+  if (M < 1 || M > 32 || K < 1 || K > M) EMD_FAIL("fsvit_emd_rerank: K = %d, M = %d: 1 <= K <= M <= 32 (one lane per candidate)", K, M);
+  if (const char* why = emd_bank_shape_bad(n_classes, N, C)) EMD_FAIL("fsvit_emd_rerank: n_classes = %d, N = %d, C = %d: %s", n_classes, N, C, why);
+  if (!(temperature - temperature == 0.0f)) EMD_FAIL("fsvit_emd_rerank: temperature is not finite");
+  if (Q == 0) return 0;                                          // nothing is touched (an empty array has no address to hand over)
+  if (!query_tok || !query_xhat || !query_pooled || !bank_tok || !bank_xhat || !bank_pooled || !bank_empty || !cand || !classes || !values || !prob ||
+      !status_count || !invalid)
+    EMD_FAIL("fsvit_emd_rerank: null argument");
+  int rc = fsvit::launch_emd_rerank(query_tok, query_xhat, query_pooled, Q, bank_tok, bank_xhat, bank_pooled, bank_empty, n_classes, cand, M, N, C, temperature,
+                                    K, logits_or_null, classes, values, prob, status_count, invalid, (hipStream_t)stream);
+  if (rc) return fsvit_set_error(rc, "fsvit_emd_rerank: %s", hipGetErrorString((hipError_t)rc));
   return 0;
 }
 

@@ -55,6 +55,14 @@ size_t emd_head_gather_workspace_bytes(int E, int P, int N, int C);
 int launch_emd_head_gather(const float* tok, const float* xhat, const float* pooled, int n_slots, const void* query_slots, const void* proto_slots,
                            int slots_are_int64, const float* proto_tok, int E, int P, int Q, int N, int C, float temperature, float* logits, int* status,
                            int* invalid, void* ws, hipStream_t s);
+// a bank of class token maps over a labelled support set, and the exact re-rank of a shortlist (limits: fsvit_emd_bank_* / fsvit_emd_rerank of fsvit.h)
+int launch_emd_bank_accumulate(const float* tok, const void* label, int label_is_int64, int S, int n_classes, int N, int C, float* sum, int* count,
+                               int* invalid, hipStream_t s);
+int launch_emd_bank_finalize(const float* sum, const int* count, int n_classes, int N, int C, float* tok, float* xhat, float* pooled, float* proto, int* empty,
+                             hipStream_t s);
+int launch_emd_rerank(const float* qtok, const float* qxhat, const float* qpooled, int Q, const float* btok, const float* bxhat, const float* bpooled,
+                      const int* empty, int n_classes, const int* cand, int M, int N, int C, float temperature, int K, float* logits, int* classes,
+                      float* values, float* prob, int* status_count, int* invalid, hipStream_t s);
 int launch_emd_solve(const float* cost, const float* w1, const float* w2, int B, int N, float* flow, int* status, int* naug, hipStream_t s);
 // The 5-shot SFC fine-tune on the device, one workgroup per episode.  workspace = emd_sfc_workspace_bytes(E, way, n, bs, N, C)
 size_t emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C);

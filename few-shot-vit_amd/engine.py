@@ -1770,6 +1770,103 @@ class ops:
                                                  0 if ws is None else ws.numel(), _stream_ptr(dev)))
         return logits, status
 
+    # ---- a bank of class token maps over a labelled support set, and the exact re-rank of a shortlist (emd_head.hip; limits in fsvit.h)
+    @staticmethod
+    def _f32_dense(what, *ts):
+        for t in ts:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f'{what}: expected contiguous float32 tensors, got {t.dtype} {tuple(t.shape)}')
+
+    @staticmethod
+    def emd_bank_accumulate(tok, labels, sum_, count, invalid):
+        """tok [S,N,C] (any float type), labels [S] (int32 / int64) added into the bank state in place: sum_ [n_classes,N,C] fp32, count [n_classes]
+        int32, invalid [1] int32 (the number of labels outside [0, n_classes); they add nothing else).  Rows of a class are added in ascending index on
+        top of the stored sum: two calls over a split give the bits of one."""
+        _require_cuda(tok, labels, sum_, count, invalid)
+        if tok.dim() != 3 or sum_.dim() != 3 or tuple(tok.shape[1:]) != tuple(sum_.shape[1:]):
+            raise ValueError('expected tok [S,N,C] and sum [n_classes,N,C]')
+        n_classes, N, Cc = sum_.shape
+        ops._f32_dense('emd_bank_accumulate: sum', sum_)
+        ops._bank_state(None, count, invalid, n_classes, 0)
+        if labels.dtype not in (torch.int32, torch.int64) or labels.dim() != 1 or labels.shape[0] != tok.shape[0]:
+            raise ValueError('expected labels [S] int32 / int64 for tok [S,N,C]')
+        tok, labels = tok.detach().contiguous().float(), labels.contiguous()
+        with torch.cuda.device(tok.device):
+            _lib.check(_lib.load().fsvit_emd_bank_accumulate(_ptr(tok), _ptr(labels), int(labels.dtype == torch.int64), tok.shape[0], n_classes, N, Cc,
+                                                             _ptr(sum_), _ptr(count), _ptr(invalid), _stream_ptr(tok.device)))
+
+    @staticmethod
+    def emd_bank_finalize(sum_, count):
+        """-> (tok [n_classes,N,C] = sum / count, xhat [n_classes,N,C] and pooled [n_classes,C]: the bits of emd_table_prep(tok), proto [n_classes,C] =
+        F.normalize(pooled), empty [n_classes] int32: 1 where count == 0, all outputs of such a class zero rows)."""
+        _require_cuda(sum_, count)
+        if sum_.dim() != 3:
+            raise ValueError('expected sum [n_classes,N,C]')
+        n_classes, N, Cc = sum_.shape
+        ops._f32_dense('emd_bank_finalize: sum', sum_)
+        ops._bank_state(None, count, None, n_classes, 0)
+        dev = sum_.device
+        tok, xhat = torch.empty_like(sum_), torch.empty_like(sum_)
+        pooled, proto = (torch.empty(n_classes, Cc, dtype=torch.float32, device=dev) for _ in range(2))
+        empty = torch.empty(n_classes, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().fsvit_emd_bank_finalize(_ptr(sum_), _ptr(count), n_classes, N, Cc, _ptr(tok), _ptr(xhat), _ptr(pooled), _ptr(proto),
+                                                           _ptr(empty), _stream_ptr(dev)))
+        return tok, xhat, pooled, proto, empty
+
+    @staticmethod
+    def check_shortlist(k, shortlist, what):
+        """the list lengths of a shortlist re-rank: ints with 1 <= k <= shortlist <= 32 (shortlist None: the caller's default, only k is checked); the
+        arguments alone decide, so callers check them before they look at a device"""
+        ops.check_topk_k(k, what)
+        if shortlist is None:
+            return
+        if isinstance(shortlist, bool) or not isinstance(shortlist, int) or not 1 <= shortlist <= 32:
+            raise ValueError(f'{what}: shortlist = {shortlist!r} is outside [1, 32]')
+        if k > shortlist:
+            raise ValueError(f'{what}: k = {k} exceeds the shortlist of {shortlist}')
+
+    @staticmethod
+    def emd_rerank(query, bank, cand, temperature, k, status_count=None, invalid=None, want_logits=False):
+        """query = (tok [Q,N,C], xhat [Q,N,C], pooled [Q,C]) as emd_table_prep writes them, bank = (tok, xhat, pooled, empty) of emd_bank_finalize
+        (proto is not read), cand [Q,M] int32 class numbers (-1: an empty slot) -> (classes [Q,k] int32, values [Q,k], prob [Q,k], logits [Q,M] in
+        candidate order or None, status_count [1] int32, invalid [1] int32).  Only the Q * M listed problems are solved (the bits of emd_head_gather
+        for the same rows); the row is ranked by larger logit, lower class, lower position, empty slots (class -1, -inf) last; prob is the softmax
+        over the row's M logits.  status_count / invalid are ADDED to when given (problems at a loop bound of the solver; candidates outside
+        [-1, n_classes), which are treated as -1).  1 <= k <= M <= 32."""
+        ops.check_topk_k(k, 'emd_rerank')
+        _require_cuda(*query, *bank, cand, status_count, invalid)
+        qtok, qxhat, qpooled = query
+        btok, bxhat, bpooled, empty = bank
+        if qtok.dim() != 3 or btok.dim() != 3 or tuple(qtok.shape[1:]) != tuple(btok.shape[1:]):
+            raise ValueError('expected query tok [Q,N,C] and bank tok [n_classes,N,C]')
+        Q, N, Cc = qtok.shape
+        n_classes = btok.shape[0]
+        if qxhat.shape != qtok.shape or tuple(qpooled.shape) != (Q, Cc) or bxhat.shape != btok.shape or tuple(bpooled.shape) != (n_classes, Cc):
+            raise ValueError('expected xhat of the shape of tok and pooled [.,C] on either side')
+        ops._f32_dense('emd_rerank', qtok, qxhat, qpooled, btok, bxhat, bpooled)
+        if empty.dtype != torch.int32 or tuple(empty.shape) != (n_classes,) or not empty.is_contiguous():
+            raise ValueError('empty: contiguous int32 [n_classes]')
+        if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != Q:
+            raise ValueError('expected cand [Q,M] int32')
+        M = cand.shape[1]
+        if not k <= M <= 32:
+            raise ValueError(f'emd_rerank: k = {k}, M = {M}: 1 <= k <= M <= 32')
+        cand = cand.contiguous()
+        dev = qtok.device
+        status_count = torch.zeros(1, dtype=torch.int32, device=dev) if status_count is None else status_count
+        invalid = torch.zeros(1, dtype=torch.int32, device=dev) if invalid is None else invalid
+        ops._bank_state(None, None, status_count, 0, 0)
+        ops._bank_state(None, None, invalid, 0, 0)
+        classes = torch.empty(Q, k, dtype=torch.int32, device=dev)
+        values, prob = torch.empty(Q, k, dtype=torch.float32, device=dev), torch.empty(Q, k, dtype=torch.float32, device=dev)
+        logits = torch.empty(Q, M, dtype=torch.float32, device=dev) if want_logits else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().fsvit_emd_rerank(_ptr(qtok), _ptr(qxhat), _ptr(qpooled), Q, _ptr(btok), _ptr(bxhat), _ptr(bpooled), _ptr(empty), n_classes,
+                                                    _ptr(cand), M, N, Cc, float(temperature), k, _ptr(logits), _ptr(classes), _ptr(values), _ptr(prob),
+                                                    _ptr(status_count), _ptr(invalid), _stream_ptr(dev)))
+        return classes, values, prob, logits, status_count, invalid
+
     _emd_sfc_ws = {}
 
     @staticmethod

@@ -123,6 +123,60 @@ class DeepEMD(nn.Module):
         proto = shot_tok[:, :, 0] if shot == 1 else self.get_sfc(shot_tok, generator=self.sfc_generator)
         return self.emd_forward(proto, query_tok)
 
+    # ---- a labelled support set of any shape: encode once into a TokenBank, query many times (eval mode, whole images only)
+    def _encode_eval(self, x, what):
+        if self.deepemd != 'fcn':
+            raise NotImplementedError(f"fsvit: DeepEMD.{what} is built for deepemd='fcn' (one token map per image), not {self.deepemd!r}")
+        if self.training:
+            raise RuntimeError(f'DeepEMD.{what} is an eval-mode entry: call model.eval() first')
+        if x.dim() != 4:
+            raise ValueError(f'{what}: expected images [N,3,H,W]')
+        if not x.is_cuda:
+            raise RuntimeError('fsvit: DeepEMD.%s got images on %s; the HIP engine needs an MI355X (no CPU fallback)' % (what, x.device))
+        chunk = self.encoder.engine().chunk_images              # encode() reads the token map of the engine's last launch: one launch per chunk
+        with torch.no_grad():
+            tok = torch.cat([self.encode(x[i:i + chunk], False) for i in range(0, x.shape[0], chunk)]) if x.shape[0] else self.encode(x, False)
+        if tok.shape[1] > MAX_NODES:
+            raise NotImplementedError(f'fsvit: a {tok.shape[1]}-token map; the DeepEMD head holds at most {MAX_NODES} nodes')
+        return tok
+
+    def _scored(self, bank, fn):
+        before = bank.status_count.clone()
+        out = fn()
+        self.add_status(bank.status_count - before)
+        return out
+
+    def fit(self, x_support, y_support, n_classes=None, bank=None):
+        """x_support [S,3,H,W], y_support [S] integer labels -> TokenBank holding their token maps (the class map of a class is the mean of its support
+        maps; no SFC fine-tune).  `bank`: extend this one instead of making one; otherwise `n_classes` (None: int(y_support.max()) + 1, one device
+        read) sizes a new bank."""
+        from .emd_bank import TokenBank
+        tok = self._encode_eval(x_support, 'fit')
+        y = y_support.to(tok.device)
+        if y.dim() != 1 or y.shape[0] != tok.shape[0]:
+            raise ValueError('fit: expected one label per support image')
+        if bank is None:
+            if n_classes is None:
+                n_classes = int(y.max()) + 1
+            bank = TokenBank(n_classes, tok.shape[1], tok.shape[2], tok.device)
+        elif (bank.N, bank.C) != tuple(tok.shape[1:]):
+            raise ValueError(f'fit: the bank holds maps of {bank.N} x {bank.C}, the encoder gives {tok.shape[1]} x {tok.shape[2]}')
+        return bank.add(tok, y)
+
+    def predict(self, bank, x_query):
+        """x_query [Q,3,H,W] -> logits [Q, bank.n_classes]: every query against every class map with the model's temperature (TokenBank.logits)"""
+        tok = self._encode_eval(x_query, 'predict')
+        return self._scored(bank, lambda: bank.logits(tok, self.temperature))
+
+    def predict_topk(self, bank, x_query, k, shortlist=None):
+        """x_query [Q,3,H,W] -> (classes [Q,k] int64, logits [Q,k], prob [Q,k]) of TokenBank.topk: a shortlist of `shortlist` classes (None: min(32,
+        bank.n_classes)) by the cosine of token means, re-ranked by their exact logits.  With shortlist >= bank.n_classes the head of a stable
+        descending sort of predict(bank, x_query)'s rows.  1 <= k <= shortlist <= 32."""
+        from ..engine import ops
+        ops.check_shortlist(k, shortlist, 'predict_topk')
+        tok = self._encode_eval(x_query, 'predict_topk')
+        return self._scored(bank, lambda: bank.topk(tok, k, self.temperature, shortlist))
+
     def emd_forward(self, proto, query_tok):
         """emd_forward_1shot (:67-81): proto [E,P,N,C], query_tok [E,Q,N,C] -> logits [E,Q,P]."""
         from ..engine import ops

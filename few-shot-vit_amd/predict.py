@@ -10,7 +10,13 @@ counts, method, class names); `--load-bank F` restores one, and together with `-
 without re-encoding the earlier ones.  The CSV has one row per query image: file, pred_class (the class number), logit_0 .. logit_{way-1}.
 With `--topk K` (1 <= K <= 32) only the K best classes of every image are formed - the full logits are neither computed nor stored, which is what a
 bank of tens of thousands of classes needs - and the row is file, pred_class, pred_name, then class_i, name_i, logit_i, prob_i for i = 0 .. K-1 in
-descending order (ties: the lower class); prob is the softmax probability over all classes; a rank beyond the number of classes holds class -1."""
+descending order (ties: the lower class); prob is the softmax probability over all classes; a rank beyond the number of classes holds class -1.
+
+`--head deepemd` scores with the DeepEMD head of a SUN-D checkpoint instead (models.deepemd, whole-image token maps): the support folder becomes a
+TokenBank of class token maps (the mean map of a class), `--temperature T` is the head's temperature, and `--encoder NAME` names the encoder when
+the checkpoint carries no `model_args`.  Without `--topk` every query is scored against every class; with `--topk K` only a shortlist of
+`--shortlist M` classes (default min(32, classes), K <= M <= 32), drawn by the cosine of token means, is scored exactly, and prob is the softmax over
+that shortlist.  A stored bank records its head and loads only under the same one.  The CSV columns are the same."""
 import argparse
 import csv
 import os
@@ -20,6 +26,7 @@ import torch
 from . import models
 from .datasets.folder_datasets import ImageFolder
 from .episodic import head_temp
+from .models.emd_bank import TokenBank
 from .models.proto_bank import PrototypeBank
 
 
@@ -63,16 +70,44 @@ def load_model(path, method=None, numerics=None):
     return model
 
 
+def encode_file_maps(model, paths, image_size, box_size, device, batch=1024):
+    """token maps [len(paths), N, C] of the files through a DeepEMD model's encoder, `batch` images decoded and uploaded at a time"""
+    ds = ImageFolder.from_files(paths, [0] * len(paths), image_size, box_size, device, cache_bytes=0)      # every file is read once
+    return torch.cat([model._encode_eval(ds.gather(list(range(i, min(i + batch, len(paths))))), 'predict') for i in range(0, len(paths), batch)])
+
+
+def load_deepemd(path, encoder=None, numerics=None, temperature=12.5):
+    """A DeepEMD model around the encoder of a SUN-D (or pre-training) checkpoint: the encoder is the checkpoint's `model_args` one, else `encoder`"""
+    from .models import deepemd
+    ck = torch.load(path, map_location='cpu')
+    margs = ck.get('model_args') if isinstance(ck, dict) else None
+    if margs is not None:
+        encoder, encoder_args = margs['encoder'], dict(margs.get('encoder_args', {}))
+    elif encoder is None:
+        raise SystemExit('predict: the checkpoint has no model_args; name its encoder with --encoder NAME')
+    else:
+        encoder_args = {}
+    model = models.make('deepemd', encoder=encoder, encoder_args=encoder_args, temperature=temperature)
+    model.load_state_dict(deepemd.encoder_state_dict(ck, set(model.state_dict().keys())), strict=True)
+    if numerics is not None:
+        model.encoder.numerics = numerics
+    return model
+
+
 def make_parser():
     p = argparse.ArgumentParser(prog='python -m fewshot_vit_amd.predict', description=__doc__.split('\n\n')[0])
-    p.add_argument('--load', required=True, metavar='CKPT', help="a 'meta-baseline' checkpoint (the training drivers' schema)")
+    p.add_argument('--load', required=True, metavar='CKPT', help="a 'meta-baseline' checkpoint (the training drivers' schema); with --head deepemd a SUN-D checkpoint")
     p.add_argument('--support', metavar='DIR', help='labelled support set: one sub-folder per class')
     p.add_argument('--query', metavar='DIR', help='images to classify: a flat folder, or class sub-folders (prints the accuracy)')
     p.add_argument('--method', choices=['cos', 'sqr'], default=None, help="default: the checkpoint's")
     p.add_argument('--numerics', default=None, choices=[None, 'bf16', 'f16', 'bf16x2', 'f16x2', 'parity'], help="default: FSVIT_NUMERICS or 'bf16'")
     p.add_argument('--out', metavar='preds.csv', help='file,pred_class,logit_0.. per query image (with --topk: file,pred_class,pred_name,class_0,name_0,logit_0,prob_0,..)')
     p.add_argument('--topk', type=int, default=None, metavar='K', help='keep only the K best classes per image, 1..32, with their probabilities: no full logits')
-    p.add_argument('--save-bank', metavar='F', help='store the prototype bank after --support was added')
+    p.add_argument('--head', choices=['proto', 'deepemd'], default='proto', help="proto: cosine / distance to class prototypes; deepemd: the DeepEMD head of a SUN-D checkpoint")
+    p.add_argument('--shortlist', type=int, default=None, metavar='M', help='--head deepemd with --topk K: score exactly only the M best classes by the cosine of token means, K <= M <= 32 (default min(32, classes))')
+    p.add_argument('--temperature', type=float, default=12.5, metavar='T', help='--head deepemd: the temperature of the head')
+    p.add_argument('--encoder', default=None, metavar='NAME', help='--head deepemd: the encoder of a checkpoint without model_args')
+    p.add_argument('--save-bank', metavar='F', help='store the bank (of prototypes, or with --head deepemd of class token maps) after --support was added')
     p.add_argument('--load-bank', metavar='F', help='start from a stored bank; with --support: extend it')
     p.add_argument('--image-size', type=int, default=None, help="default: the encoder's input size")
     p.add_argument('--box-size', type=int, default=None, help='Resize target before the centre crop (default: image size * 8 / 7, the 256 -> 224 ratio)')
@@ -85,18 +120,28 @@ def main(argv=None):
         raise SystemExit('predict: give --support DIR, --load-bank F or both')
     if args.topk is not None and not 1 <= args.topk <= 32:
         raise SystemExit('predict: --topk K needs 1 <= K <= 32')
+    deepemd = args.head == 'deepemd'
+    if args.shortlist is not None and not (deepemd and args.topk is not None and args.topk <= args.shortlist <= 32):
+        raise SystemExit('predict: --shortlist M goes with --head deepemd --topk K and needs K <= M <= 32')
     if not torch.cuda.is_available():
         raise RuntimeError('fsvit: predict needs an MI355X (no CPU fallback)')
     device = torch.device('cuda', torch.cuda.current_device())
-    model = load_model(args.load, args.method, args.numerics).to(device).eval()
+    if deepemd:
+        model = load_deepemd(args.load, args.encoder, args.numerics, args.temperature).to(device).eval()
+        encode = encode_file_maps
+    else:
+        model = load_model(args.load, args.method, args.numerics).to(device).eval()
+        encode = encode_files
     size = args.image_size or model.encoder.cfg['img_size']
     box = args.box_size or (size * 8) // 7
     bank, classes = None, None
     if args.load_bank:
         saved = torch.load(args.load_bank, map_location='cpu')
+        if saved.get('head', 'proto') != args.head:               # (a file from before the flag holds a prototype bank)
+            raise ValueError(f"{args.load_bank} holds a bank of --head {saved.get('head', 'proto')}, this run scores with --head {args.head}")
         classes = list(saved['classes'])
-        bank = PrototypeBank.from_state_dict(saved['bank'], device)
-        if bank.method != model.method:
+        bank = (TokenBank if deepemd else PrototypeBank).from_state_dict(saved['bank'], device)
+        if not deepemd and bank.method != model.method:
             raise ValueError(f'{args.load_bank} was built for {bank.method!r}, the model scores with {model.method!r}')
     if args.support:
         if classes is None:
@@ -104,13 +149,14 @@ def main(argv=None):
             if not classes:
                 raise ValueError(f'{args.support}: no class sub-folders')
         paths, labels = list_labelled(args.support, classes)
-        feat = encode_files(model, paths, size, box, device)
+        feat = encode(model, paths, size, box, device)
         if bank is None:
-            bank = PrototypeBank(len(classes), feat.shape[1], model.method, device)
+            bank = TokenBank(len(classes), feat.shape[1], feat.shape[2], device) if deepemd else PrototypeBank(len(classes), feat.shape[1], model.method, device)
         bank.add(feat, torch.tensor(labels, dtype=torch.int64, device=device)).check()
-    print('bank: {} classes, {} support images ({})'.format(len(classes), int(bank.counts.sum()), bank.method))
+    print('bank: {} classes, {} support images ({})'.format(len(classes), int(bank.counts.sum()), 'deepemd' if deepemd else bank.method))
     if args.save_bank:
-        torch.save({'bank': {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in bank.state_dict().items()}, 'classes': classes}, args.save_bank)
+        torch.save({'bank': {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in bank.state_dict().items()}, 'classes': classes,
+                    'head': args.head}, args.save_bank)
     out = {'bank': bank, 'classes': classes}
     if args.query:
         sub = class_folders(args.query)
@@ -118,16 +164,24 @@ def main(argv=None):
             paths, truth = list_labelled(args.query, classes)
         else:
             paths, truth = [os.path.join(args.query, n) for n in _listdir(args.query)], None
-        feat = encode_files(model, paths, size, box, device)
-        temp = head_temp(model, on_device=True)
+        feat = encode(model, paths, size, box, device)
+        temp = model.temperature if deepemd else head_temp(model, on_device=True)
         if args.topk is not None:
-            top_c, top_l, top_p = (t.cpu() for t in bank.topk(feat, args.topk, temp))
+            top = bank.topk(feat, args.topk, temp, args.shortlist) if deepemd else bank.topk(feat, args.topk, temp)
+            top_c, top_l, top_p = (t.cpu() for t in top)
             pred = top_c[:, 0]
             out.update(files=paths, pred=pred, topk_classes=top_c, topk_logits=top_l, topk_prob=top_p)
         else:
-            pred, logits = bank.predict(feat, temp)
+            if deepemd:
+                logits = bank.logits(feat, temp)
+                pred = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, 0]            # the first maximum of every row
+            else:
+                pred, logits = bank.predict(feat, temp)
             pred, logits = pred.cpu(), logits.cpu()
             out.update(files=paths, pred=pred, logits=logits)
+        if deepemd:
+            from .models.deepemd import check_status_count
+            check_status_count(bank.status_count)
         if truth is not None:
             out['acc'] = float((pred == torch.tensor(truth)).double().mean()) if paths else float('nan')
             print('accuracy: {:.2f} % over {} images'.format(out['acc'] * 100, len(paths)))

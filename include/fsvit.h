@@ -772,6 +772,37 @@ size_t fsvit_emd_sfc_workspace_bytes(int E, int way, int n, int bs, int N, int C
 int fsvit_emd_sfc_steps(const float* support_dev, const int* label_dev, const int* ids_dev, int n_steps, int first, int E, int way, int n, int bs, int N,
                         int C, float temperature, float lr, float momentum, float dampening, float* sfc_dev, float* buf_dev, int* status_count_dev,
                         void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The head over a labelled support set: a bank of class token maps, filled once (ragged classes, any number of calls) and queried many times, and the
+ * exact re-rank of a shortlist of classes per query (models/emd_bank.TokenBank).  All tensors fp32 and dense.  Shared refusals (FSVIT_ERR_ARG and a
+ * message, nothing launched): a NULL pointer that is not marked optional, n_classes < 1 or > 65536, N < 1 or N > 32, C not a positive multiple of 64 or above 16384.
+ *
+ * Accumulate: tok_dev [S][N][C], label_dev [S] (int64 when label_is_int64, else int32) -> sum_dev [n_classes][N][C] +=, count_dev [n_classes] +=,
+ * *invalid_dev += the number of labels outside [0, n_classes), which contribute nothing else (their rows are not read).  The caller zeroes the three
+ * outputs once.  A class's rows are added in ascending support index on top of the stored sum, without floating-point atomics: deterministic, and two
+ * calls over a split give the bits of one call (the contract of fsvit_proto_bank_accumulate, whose rows end at D = 8192).  S == 0 is a no-op; S < 0 or
+ * S > 2^24 refused. */
+int fsvit_emd_bank_accumulate(const float* tok_dev, const void* label_dev, int label_is_int64, int S, int n_classes, int N, int C, float* sum_dev,
+                              int* count_dev, int* invalid_dev, void* stream);
+/* Finalize: tok_dev [n_classes][N][C] = sum / count (the class map: the mean of the class's support maps, what get_sfc starts from); xhat_dev
+ * [n_classes][N][C] and pooled_dev [n_classes][C] = the bits fsvit_emd_table_prep gives for that tok; proto_dev [n_classes][C] = pooled / max(|pooled|,
+ * 1e-12) (F.normalize), a row for a cosine shortlist (fsvit_proto_bank_topk); empty_dev [n_classes] = 1 where count == 0 - all outputs of such a class
+ * are zero rows - else 0. */
+int fsvit_emd_bank_finalize(const float* sum_dev, const int* count_dev, int n_classes, int N, int C, float* tok_dev, float* xhat_dev, float* pooled_dev,
+                            float* proto_dev, int* empty_dev, void* stream);
+/* Re-rank: query q (rows of query_tok / query_xhat [Q][N][C], query_pooled [Q][C] as fsvit_emd_table_prep writes them) is scored against the classes
+ * cand_dev [Q][M] (int32 class numbers) of a finalized bank, only those M problems are solved, and the row is ranked in the same launch.  For the same
+ * prepared rows a logit has the bits of fsvit_emd_head_gather.  A candidate: -1 is an empty slot; an entry < -1 or >= n_classes raises *invalid_dev by
+ * one and is treated as -1 - it never becomes an address; an empty slot and a class flagged in bank_empty_dev score -inf and are not solved; duplicates
+ * are allowed and each is scored.  Outputs: logits_or_null_dev [Q][M] in candidate order; classes_dev [Q][K] (int32), values_dev [Q][K], prob_dev [Q][K]:
+ * the K first of the row in the order larger logit, then lower class, then lower candidate position, where an empty slot (it keeps class -1) comes
+ * after every class, as the (-inf, -1) tail of fsvit_proto_bank_topk does; prob = the softmax over the finite entries of the row's M logits, 0 for a
+ * -inf entry and for a row without a finite entry.  *status_count_dev (an int the caller zeroes once) is raised by one per problem that stopped at a
+ * loop bound of the solver; *invalid_dev likewise per bad candidate (integer atomic adds).  Limits: 1 <= K <= M <= 32, 0 <= Q <= 2^24 (Q == 0 touches
+ * nothing), a finite temperature; refusals as above. */
+int fsvit_emd_rerank(const float* query_tok_dev, const float* query_xhat_dev, const float* query_pooled_dev, int Q, const float* bank_tok_dev,
+                     const float* bank_xhat_dev, const float* bank_pooled_dev, const int* bank_empty_dev, int n_classes, const int* cand_dev, int M, int N,
+                     int C, float temperature, int K, float* logits_or_null_dev, int* classes_dev, float* values_dev, float* prob_dev,
+                     int* status_count_dev, int* invalid_dev, void* stream);
 
 /* ---------------------------------------------------------------- episode sampler (host only, no GPU)
  * The draws of `CategoriesSampler.__iter__` (test_phase/datasets/samplers.py:19-35) replayed natively on the legacy numpy generator state: per episode
