@@ -46,6 +46,13 @@ class Param(C.Structure):
     _fields_ = [('name', C.c_char_p), ('data', C.c_void_p), ('grad', C.c_void_p), ('numel', C.c_int64)]
 
 
+class ConvEvalArgs(C.Structure):
+    """fsvit_conv_eval_args of fsvit.h (fsvit_op_conv_eval)"""
+    _fields_ = ([(n, C.c_void_p) for n in ('x', 'w', 'bias', 'res', 'pos', 'y', 'x2', 'stats', 'c1f_raw', 'c1f_raw2', 'c1f_patches', 'c1f_w', 'c1f_bias')] +
+                [(n, C.c_int) for n in ('B', 'H', 'W', 'Cin', 'x_cstride', 'KH', 'KW', 'stride', 'pad', 'N', 'y_cstride', 'Kw', 'groups', 'act', 'res_first',
+                                        'x2_cstride', 'K2', 'pool2', 'y_rpi', 'y_row0', 'x_planar', 'y_planar', 'w_cpad', 'c1f_split', 'c1f_kw')])
+
+
 # name -> (restype, argtypes); every symbol include/fsvit.h declares
 _vp, _fp, _i, _f, _sz = C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_size_t
 SIGNATURES = {
@@ -119,6 +126,9 @@ SIGNATURES = {
     'fsvit_im2col27': (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),
     'fsvit_stem_conv1': (_i, [_fp, _vp, _i, _fp, _vp, _vp, _i, _i, _i, _vp]),
     'fsvit_stem_conv1_dt': (_i, [_fp, _vp, _i, _fp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'fsvit_op_stem_conv1': (_i, [_fp, _vp, _i, _fp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_stage1_block_eval': (_i, [_vp, _vp, _vp, _fp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'fsvit_op_conv_eval': (_i, [C.POINTER(ConvEvalArgs), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     'fsvit_maxpool2_pos': (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _i, _vp]),
     'fsvit_pool_affine': (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     'fsvit_visformer_trainer_create': (_i, [C.POINTER(VisformerCfg), _i, C.POINTER(_vp)]),

@@ -1293,6 +1293,92 @@ extern "C" int fsvit_stage1_block_hw(const void* x, void* y, const void* w1, con
   return 0;
 }
 
+/* fsvit_stage1_block_hw with the conv3 weights the engines hand the kernel: prescaled != 0 builds the 8 x W3 image with launch_stage1_w4_prescale (as
+ * visformer pack does for every stage-1 block) and launches stage1_w4_kernel<true, true> on it; prescaled == 0 is fsvit_stage1_block_hw (<true, false>). */
+extern "C" int fsvit_op_stage1_block_eval(const void* x, void* y, const void* w1, const float* b1, const void* w2, const void* w3, int B, int H, int W, int dtype,
+                                          int prescaled, void* stream) {
+  const int kdt = dtype;
+  if (!x || !y || !w1 || !b1 || !w2 || !w3 || x == y || B <= 0) return fail(FSVIT_ERR_ARG, "fsvit_op_stage1_block_eval: bad argument");
+  if (dtype != FSVIT_BF16 && dtype != FSVIT_F16) return fail(FSVIT_ERR_ARG, "fsvit_op_stage1_block_eval: 16-bit storage only (bf16 / f16)");
+  if (H != W || !K(stage1_ring_supported)(1, 128, 256, 8, W)) return fail(FSVIT_ERR_ARG, "fsvit_op_stage1_block_eval: square maps of 4 .. 20 tokens a side");
+  if ((long)B * H * W >= (1L << 31) - 256) return fail(FSVIT_ERR_ARG, "fsvit_op_stage1_block_eval: map too large");
+  hipStream_t st = (hipStream_t)stream;
+  if (!prescaled) {
+    RC_TRY(K(launch_stage1_ring)(x, y, w1, b1, w2, w3, B, H, W, st, nullptr));
+    return 0;
+  }
+  const int n3 = 128 * 256;
+  void* w3s = nullptr;
+  HIP_TRY(hipMalloc(&w3s, (size_t)n3 * 2));
+  int rc = K(launch_stage1_w4_prescale)(w3, w3s, n3, st);
+  if (rc == 0) rc = K(launch_stage1_ring)(x, y, w1, b1, w2, w3, B, H, W, st, w3s);
+  (void)hipStreamSynchronize(st);
+  (void)hipFree(w3s);
+  if (rc != 0) return hipfail((hipError_t)rc, "fsvit_op_stage1_block_eval");
+  return 0;
+}
+
+/* Every field of ConvGemmParams an evaluation launch sets, through launch_conv_gemm (fsvit.h: fsvit_conv_eval_args).  Refuses what the kernels would misread:
+ * the row-chunk-planar operands, the 128-channel weight image, the C1F fields and `stats` only where the eligibility functions accept them. */
+extern "C" int fsvit_op_conv_eval(const fsvit_conv_eval_args* a, int dtype, int* route, int* stats_rows, void* stream) {
+  const int kdt = dtype;
+  static const char fn[] = "fsvit_op_conv_eval";
+  if (!a) return fail(FSVIT_ERR_ARG, "%s: null argument", fn);
+  if (!known_dtype(dtype)) return fail(FSVIT_ERR_ARG, "%s: unknown dtype %d", fn, dtype);
+  if ((!a->x && !a->c1f_raw) || !a->w || !a->y || a->x == a->y) return fail(FSVIT_ERR_ARG, "%s: null argument, or y == x", fn);
+  if (a->act != FSVIT_ACT_NONE && a->act != FSVIT_ACT_GELU && a->act != FSVIT_ACT_LRELU) return fail(FSVIT_ERR_ARG, "%s: act %d (none | GELU | LeakyReLU)", fn, a->act);
+  if (a->B < 1 || a->H < 1 || a->W < 1 || a->Cin < 1 || a->N < 1 || a->groups < 1 || a->KH < 1 || a->KW < 1 || a->stride < 1 || a->pad < 0 ||
+      a->H + 2 * a->pad < a->KH || a->W + 2 * a->pad < a->KW)
+    return fail(FSVIT_ERR_ARG, "%s: bad geometry", fn);
+  const int es = storage_bytes(dtype), epc = 16 / es, bke = 128 / es;
+  if (a->Cin % epc || a->x_cstride % epc || a->x_cstride < a->groups * a->Cin || a->N % 4 || a->y_cstride % 4 || a->y_cstride < a->groups * a->N || a->Kw % bke ||
+      a->Kw < a->KH * a->KW * a->Cin)
+    return fail(FSVIT_ERR_ARG, "%s: alignment: Cin / x_cstride %% %d, N / y_cstride %% 4, Kw %% %d and >= KH * KW * Cin", fn, epc, bke);
+  if (a->KH * a->KW > 1 && !is_pow2(a->Cin) && a->Cin % 32) return fail(FSVIT_ERR_ARG, "%s: a multi-tap conv needs a power-of-two Cin or a multiple of 32", fn);
+  Layer L; L.w = const_cast<void*>(a->w); L.bias = const_cast<float*>(a->bias); L.N = a->N; L.K = a->KH * a->KW * a->Cin; L.Kw = a->Kw; L.groups = a->groups;
+  ConvGemmParams p = conv_params(L, a->x, a->y, a->B, a->H, a->W, a->Cin, a->x_cstride, a->KH, a->KW, a->stride, a->pad, a->y_cstride, a->act, a->res,
+                                 a->res_first ? 1 : 0, a->pos);
+  if ((long)a->B * p.OH * p.OW > 0x7fffffffL - 256) return fail(FSVIT_ERR_ARG, "%s: map too large", fn);
+  if (a->x2 || a->K2 || a->x2_cstride) {      // the tail operand: one more K slice behind the main columns
+    if (!a->x2 || a->K2 < 1 || a->K2 > bke || a->x2_cstride < a->K2 || a->x2_cstride % epc || a->groups != 1 || a->Kw < (a->w_cpad ? 9 * a->w_cpad : L.K) + bke)
+      return fail(FSVIT_ERR_ARG, "%s: tail operand: x2, 1 <= K2 <= %d <= x2_cstride, one group, Kw >= K + %d", fn, bke, bke);
+    p.x2 = a->x2; p.x2_cstride = a->x2_cstride; p.K2 = a->K2;
+  }
+  if (a->pool2) {
+    if (a->res || a->y_rpi || (p.OH & 1) || (p.OW & 1) || a->stride != 1) return fail(FSVIT_ERR_ARG, "%s: pool2 needs even OH / OW, stride 1, no residual, dense rows", fn);
+    p.pool2 = 1;
+  }
+  if (a->y_rpi || a->y_row0) {
+    if (a->y_row0 < 0 || a->y_rpi < a->y_row0 + p.OH * p.OW) return fail(FSVIT_ERR_ARG, "%s: y_rpi %d < y_row0 %d + OH * OW", fn, a->y_rpi, a->y_row0);
+    p.y_rpi = a->y_rpi; p.y_row0 = a->y_row0;
+  }
+  p.x_planar = a->x_planar ? 1 : 0; p.y_planar = a->y_planar ? 1 : 0; p.w_cpad = a->w_cpad;
+  if ((p.x_planar || p.y_planar || p.w_cpad) && !K(conv3x3_halo_eligible)(p, kg(dtype)))
+    return fail(FSVIT_ERR_ARG, "%s: planar operands / the 128-channel weight image on a layer conv3x3_halo does not take", fn);
+  if (a->c1f_raw || a->c1f_raw2 || a->c1f_patches || a->c1f_w || a->c1f_bias || a->c1f_kw || a->c1f_split) {
+    if (!a->c1f_raw || !a->c1f_patches || !a->c1f_w || !a->c1f_bias || a->c1f_kw < 32 || a->c1f_split < 0 || a->c1f_split > a->B ||
+        (a->c1f_split < a->B && !a->c1f_raw2) || !K(conv3x3_halo_c1f_supported)(p, kg(dtype)))
+      return fail(FSVIT_ERR_ARG, "%s: C1F: raw images, patches, conv1 weights (row length >= 32) and bias on the planar 64 -> 128 layer of 40 x 40 maps only", fn);
+    p.c1f_raw = a->c1f_raw; p.c1f_raw2 = a->c1f_raw2; p.c1f_split = a->c1f_split; p.c1f_patches = a->c1f_patches;
+    p.c1f_w = a->c1f_w; p.c1f_bias = a->c1f_bias; p.c1f_kw = a->c1f_kw;
+  } else if (!a->x) {
+    return fail(FSVIT_ERR_ARG, "%s: null argument", fn);
+  }
+  int rows = 0;
+  if (a->stats) {
+    if (p.c1f_raw) return fail(FSVIT_ERR_ARG, "%s: stats with C1F", fn);
+    rows = K(conv_stats_rows)(p, kg(dtype));
+    if (rows <= 0) return fail(FSVIT_ERR_ARG, "%s: this layer's kernel has no statistics epilogue", fn);
+    p.stats = a->stats;
+    if ((p.x_planar || p.y_planar || p.w_cpad) && !K(conv3x3_halo_eligible)(p, kg(dtype)))
+      return fail(FSVIT_ERR_ARG, "%s: stats with a planar output / the 128-channel weight image", fn);
+  }
+  if (stats_rows) *stats_rows = rows;
+  if (route) *route = K(conv_gemm_route)(p, kg(dtype));
+  RC_TRY(K(launch_conv_gemm)(p, kg(dtype), (hipStream_t)stream));
+  return 0;
+}
+
 extern "C" int fsvit_conv3x3_wgrad(const void* x, const void* dz, float* dw, int B, int H, int W, int O, int Ig, int groups, int dtype, void* stream) {
   const int kdt = dtype;
   if (!x || !dz || !dw) return fail(FSVIT_ERR_ARG, "null argument");
@@ -1567,11 +1653,15 @@ extern "C" int fsvit_stem_conv1(const float* x, const void* w, int kw, const flo
   return fsvit_stem_conv1_dt(x, w, kw, bias, patches, c1, B, H, W, FSVIT_BF16, stream);
 }
 extern "C" int fsvit_stem_conv1_dt(const float* x, const void* w, int kw, const float* bias, void* patches, void* c1, int B, int H, int W, int dtype, void* stream) {
+  return fsvit_op_stem_conv1(x, w, kw, bias, patches, c1, B, H, W, dtype, 0, stream);
+}
+extern "C" int fsvit_op_stem_conv1(const float* x, const void* w, int kw, const float* bias, void* patches, void* c1, int B, int H, int W, int dtype, int c1_planar,
+                                   void* stream) {
   const int kdt = dtype;
   if (!half_dtype(dtype)) return fail(FSVIT_ERR_ARG, "fsvit_stem_conv1: 16-bit storage only (bf16 / f16)");
   if (!x || !w || !patches || !c1 || kw < 32) return fail(FSVIT_ERR_ARG, "bad argument");
   if (H != W || !K(stem_conv1_supported)(1, H, 64)) return fail(FSVIT_ERR_ARG, "fsvit_stem_conv1: only 80x80 images, 64 output channels are built");
-  RC_TRY(K(launch_stem_conv1)(x, patches, c1, w, kw, bias, B, (hipStream_t)stream, 0));
+  RC_TRY(K(launch_stem_conv1)(x, patches, c1, w, kw, bias, B, (hipStream_t)stream, c1_planar ? 1 : 0));
   return 0;
 }
 

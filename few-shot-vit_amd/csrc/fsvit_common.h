@@ -179,7 +179,10 @@ __device__ __forceinline__ void fill(unsigned char* tab, int t, int nthreads) {
     const int i = e - TN, a = i >= 0 ? i : -1 - i;
     const float z8 = __builtin_bit_cast(float, (unsigned)(TLO + a) << 16);
     const float z = i >= 0 ? 8.0f * z8 : -8.0f * z8;
-    reinterpret_cast<bf16*>(tab)[e] = (bf16)(gelu_erf(z) * 0.125f);
+    // negative half: z Phi(z) through erfc - 1 + erff(z / sqrt 2) cancels there (no correct digit below z = -4.4, exactly 0 below -5.6), and the entries
+    // reach z = -31.875; the positive half keeps the erff form (1 + erf in [1, 2]: no cancellation)
+    const float g = i >= 0 ? gelu_erf(z) : 0.5f * z * erfcf(z * -0.70710678118654752440f);
+    reinterpret_cast<bf16*>(tab)[e] = (bf16)(g * 0.125f);
   }
 }
 // packed bf16 code pair of (z0 / 8, z1 / 8) -> packed signed table indices (steps T2 .. T4 of the kernels' micro-stages, here in one piece)

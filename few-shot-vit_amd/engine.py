@@ -601,6 +601,40 @@ class ops:
                                                  _stream_ptr(x.device)))
         return y
 
+    @staticmethod
+    def stage1_block_eval(x, w1, b1, w2, w3, prescaled):
+        """stage1_block_hw as the engines launch it (fsvit_op_stage1_block_eval): prescaled = True runs stage1_w4_kernel<true, true> on the 8 x W3 image
+        built by the engines' own prescale launch, False the <true, false> instantiation on W3."""
+        _require_cuda(x, w1, w2, w3, b1)
+        dt = ops._dt16(x, w1, w2, w3)
+        y = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().fsvit_op_stage1_block_eval(_ptr(x), _ptr(y), _ptr(w1), _ptr(b1), _ptr(w2), _ptr(w3), x.shape[0], x.shape[1], x.shape[2], dt,
+                                                              int(bool(prescaled)), _stream_ptr(x.device)))
+        return y
+
+    @staticmethod
+    def conv_eval(y, numerics=None, **fields):
+        """fsvit_op_conv_eval: one launch through the evaluation dispatcher.  `fields` are those of fsvit_conv_eval_args (fsvit.h) - tensors (or None) for the
+        pointer fields, ints for the rest, everything left out 0 / NULL; y is the caller's output buffer (its dtype is the storage type unless `numerics`
+        names a two-limb mode).  -> (route, stats_rows)."""
+        _require_cuda(y)
+        a = _lib.ConvEvalArgs()
+        names = {n for n, _ in _lib.ConvEvalArgs._fields_}
+        fields = dict(fields, y=y)
+        for k, v in fields.items():
+            if k not in names:
+                raise TypeError(f'conv_eval: unknown field {k}')
+            if torch.is_tensor(v):
+                _require_cuda(v)
+                v = v.data_ptr()
+            setattr(a, k, v)
+        route, rows = C.c_int(-1), C.c_int(-1)
+        with torch.cuda.device(y.device):
+            _lib.check(_lib.load().fsvit_op_conv_eval(C.byref(a), DTYPES[numerics] if numerics else ops._dt(y), C.byref(route), C.byref(rows),
+                                                      _stream_ptr(y.device)))
+        return route.value, rows.value
+
     # ---- distillation head (sun_meta_training/offline.py): fp32, token-major rows
     @staticmethod
     def linear(x, w, b=None):
@@ -809,8 +843,9 @@ class ops:
         return out
 
     @staticmethod
-    def stem_conv1(x, w, bias):
-        """im2col + stem conv1 + LeakyReLU in one pass (stem.hip): x [B,3,80,80] fp32, w [64, kw] bf16 -> (patches [B*1600,32], c1 [B*1600,64])."""
+    def stem_conv1(x, w, bias, c1_planar=False):
+        """im2col + stem conv1 + LeakyReLU in one pass (stem.hip): x [B,3,80,80] fp32, w [64, kw] bf16 -> (patches [B*1600,32], c1 [B*1600,64]).
+        c1_planar: c1 in the row-chunk-planar layout of the eval stem (fsvit_op_stem_conv1), the same number of elements."""
         _require_cuda(x, w)
         if x.dtype != torch.float32:
             raise TypeError(f'stem_conv1 reads the fp32 image, got {x.dtype}')
@@ -820,8 +855,12 @@ class ops:
         patches = torch.empty(B * (H // 2) * (W // 2), 32, dtype=w.dtype, device=x.device)
         c1 = torch.empty(B * (H // 2) * (W // 2), 64, dtype=w.dtype, device=x.device)
         with torch.cuda.device(x.device):
-            _lib.check(lib.fsvit_stem_conv1_dt(_ptr(x.contiguous()), _ptr(w), w.shape[-1], _ptr(bias), _ptr(patches), _ptr(c1), B, H, W, dt,
-                                               _stream_ptr(x.device)))
+            if c1_planar:
+                _lib.check(lib.fsvit_op_stem_conv1(_ptr(x.contiguous()), _ptr(w), w.shape[-1], _ptr(bias), _ptr(patches), _ptr(c1), B, H, W, dt, 1,
+                                                   _stream_ptr(x.device)))
+            else:
+                _lib.check(lib.fsvit_stem_conv1_dt(_ptr(x.contiguous()), _ptr(w), w.shape[-1], _ptr(bias), _ptr(patches), _ptr(c1), B, H, W, dt,
+                                                   _stream_ptr(x.device)))
         return patches, c1
 
     @staticmethod

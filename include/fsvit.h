@@ -346,6 +346,43 @@ int fsvit_vit_ln_qkv_attention_dt(const void* x_dev, const void* wqkv_dev, int k
                                   int heads, int hdp, float eps, float scale, int dtype, void* stream);
 int fsvit_stem_conv1_dt(const float* x_nchw_dev, const void* w_dev, int kw, const float* bias_dev, void* patches_dev, void* c1_dev,
                         int B, int H, int W, int dtype, void* stream);
+/* ---------------------------------------------------------------- operator entries of the evaluation stem / conv / stage-1 kernels (tests)
+ * fsvit_stem_conv1_dt with the layout of c1 spelled out: c1_planar != 0 stores c1 row-chunk-planar (element (b, row, col, c) at
+ * ((b * 40 + row) * 8 + c / 8) * 320 + col * 8 + c % 8), the layout the planar eval stem hands to conv2; 0: NHWC rows. */
+int fsvit_op_stem_conv1(const float* x_nchw_dev, const void* w_dev, int kw, const float* bias_dev, void* patches_dev, void* c1_dev,
+                        int B, int H, int W, int dtype, int c1_planar, void* stream);
+/* fsvit_stage1_block_hw as the engines launch it: prescaled != 0 runs the kernel on the 8 x W3 image (built per call by the same prescale launch the
+ * engines use at load time), prescaled == 0 on W3 itself.  The two are specified to be bit-identical.  A test entry: with prescaled != 0 it allocates the
+ * image, SYNCHRONISES the stream and frees it on every call. */
+int fsvit_op_stage1_block_eval(const void* x_dev, void* y_dev, const void* w1_dev, const float* b1_dev, const void* w2_dev, const void* w3_dev, int B, int H,
+                               int W, int dtype, int prescaled, void* stream);
+/* One conv / GEMM launch through the evaluation dispatcher with every operand an engine can set.  Fields as in fsvit_conv_gemm, plus:
+ *   x2 / x2_cstride / K2   the tail operand (one more K slice over rows aligned with the output pixels; its weights are the last slice of the packed rows);
+ *   pool2                  2 x 2 max-pool behind the activation, pos added to the pooled pixels;
+ *   y_rpi / y_row0         output row m of image b goes to row b * y_rpi + y_row0 + m % (OH * OW) (0 / 0: dense);
+ *   x_planar / y_planar    that map is row-chunk-planar: element (b, row, col, c) at ((b * H + row) * (C / 8) + c / 8) * W * 8 + col * 8 + c % 8;
+ *   w_cpad                 128: the weights are the 128-channel image of a 96-channel layer;
+ *   c1f_*                  conv2 of the eval stem builds conv1's map on-chip from the raw NCHW fp32 images (x is not read) - images [0, c1f_split)
+ *                          from c1f_raw, the rest from c1f_raw2 - and stores the im2col patch rows [B * H * W][32] to c1f_patches;
+ *   stats                  per-workgroup partial sums of y and y^2 of the training forward: *stats_rows partial rows [rows][2][y_cstride] fp32.
+ * Planar operands, w_cpad, the C1F fields and stats are accepted only for the layers whose kernel has them (FSVIT_ERR_ARG otherwise).
+ * *route (may be NULL): 0 conv3x3_halo, 1 gemm256, 2 conv_gemm_v2, 3 the two-limb grouped 3x3 kernel. */
+typedef struct fsvit_conv_eval_args {
+  const void *x, *w;
+  const float* bias;
+  const void* res;
+  const float* pos;
+  void* y;
+  const void* x2;
+  float* stats;
+  const float *c1f_raw, *c1f_raw2;
+  void* c1f_patches;
+  const void* c1f_w;
+  const float* c1f_bias;
+  int B, H, W, Cin, x_cstride, KH, KW, stride, pad, N, y_cstride, Kw, groups, act, res_first;
+  int x2_cstride, K2, pool2, y_rpi, y_row0, x_planar, y_planar, w_cpad, c1f_split, c1f_kw;
+} fsvit_conv_eval_args;
+int fsvit_op_conv_eval(const fsvit_conv_eval_args* args, int dtype, int* route, int* stats_rows, void* stream);
 /* ---------------------------------------------------------------- distillation head
  * Replaces, for sun_meta_training/offline.py: `LinearClassifier.forward` / its autograd (models/classifier.py:27-34) as used by
  * `TokenLabelOffline` (models/token_label.py:36-60) on the 25 tokens and on the pooled feature, `generate_softlabel`
